@@ -11,10 +11,14 @@ rows are sharded across the ranks (--layout: contiguous | interleaved | block:k 
 rows / (2 N), the best of profiles/r03_cfg4_bands.json) and gathered to rank 0 over RCCL: total work
 is fixed, so scaling is "strong".  Rank 0 prints ONE JSON line.
 
+A plain run sets up, warms up, times ONE block of EXACTLY `--steps` frames and prints the line; `--dump-outputs DIR` writes
+what the last timed frame rendered (DIR/image.npy, float32; see dump_outputs).  Everything below except `value /
+ms_per_step` is measured only with `--full`.
+
 What is measured:
   value / ms_per_step ... EXACTLY `--steps` frames between barrier + synchronize on both sides, `--frames-in-flight`
-                          frames overlapped on the GPU (default 4).  The block is repeated until >= 2 s of frames
-                          have been timed and the MEDIAN block is reported (a 20-frame block lasts 3.3 ms).
+                          frames overlapped on the GPU (default 4).  With `--full` the block is repeated until >= 2 s of
+                          frames have been timed and the MEDIAN block is reported (a 20-frame block lasts 3.3 ms).
   serial ................ the same frames strictly one after the other on ONE stream (a second renderer, 8192 compositor
                           waves): single-frame latency, and every kernel has the GPU to itself, so its launch duration
                           is a clean per-kernel number.  `roofline` is computed from THIS phase; the rocprofv3 summary
@@ -140,6 +144,34 @@ def hbm_delivered(dev):
                 "how": "torch Tensor.copy_ of 1 GiB on this device (2 GiB moved), median of 10, after the timed region"}
     except Exception as e:      # noqa: BLE001 -- context only
         return {"copy_GBps": None, "how": "not measured: %s" % e}
+
+
+DUMP_BYTES = 64 << 20    # --dump-outputs: at most this much in all
+DUMP_SEED = 0x5A3D1E     # the fixed pixel sample of a frame larger than that
+
+
+def fetch_outputs(fbs, H):
+    """what a caller of the timed path receives from the frame just finished: one (H, W, 4) float32 framebuffer per view
+    (an RGBA16F target is widened exactly), copied to the host before anything else renders into it"""
+    if len(fbs) == 1:
+        return {"image": fbs[0][:H].float().cpu().numpy()}
+    return {"image_view%d" % v: fb[:H].float().cpu().numpy() for v, fb in enumerate(fbs)}
+
+
+def dump_outputs(d, outputs):
+    """DIR/<name>.npy (float32) for every output.  Frames above DUMP_BYTES in all are sampled: the same DUMP_SEED pixels of
+    every view, <name>.npy = (k, 4) float32 values and <name>_pixel_index.npy = (k,) float64 flat indices (row * W + column)"""
+    os.makedirs(d, exist_ok=True)
+    total = sum(a.nbytes for a in outputs.values())
+    for name, a in outputs.items():
+        if total <= DUMP_BYTES:
+            np.save(os.path.join(d, name + ".npy"), a)
+            continue
+        H, W = a.shape[:2]
+        k = min(H * W, (DUMP_BYTES // len(outputs)) // (4 * 4 + 8))
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(H * W, size=k, replace=False))
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(a.reshape(H * W, 4)[idx]))
+        np.save(os.path.join(d, name + "_pixel_index.npy"), idx.astype(np.float64))
 
 
 def measure(E, args, key, ply=None, primary=True):
@@ -397,10 +429,12 @@ def measure(E, args, key, ply=None, primary=True):
     blocks, enqs = [], []
     el, enq = timed_block(args.warmup)
     blocks.append(el); enqs.append(enq)
+    # what the first block's last frame rendered (a plain run times this block alone); copied before anything else renders
+    outputs = fetch_outputs(state["fbs"], H) if (rank == 0 and primary and args.dump_outputs) else None
     # (MSPLAT_BENCH_ONE_DEVICE: N processes time-share ONE GPU over gloo -- a control-flow check whose blocks escalate to 2.5 s each once
     #  the runtime juggles both processes' queues; it is not a measurement and gets a short timed phase)
     min_s, max_b = (0.25, 12) if E.one_dev else (MIN_TIMED_SECONDS, MAX_BLOCKS)
-    nblocks = int(min(max_b, max(1, math.ceil(min_s / max(el, 1e-6)))))
+    nblocks = int(min(max_b, max(1, math.ceil(min_s / max(el, 1e-6))))) if args.full else 1
     for b in range(1, nblocks):
         el, enq = timed_block(args.warmup + b * args.steps)
         blocks.append(el); enqs.append(enq)
@@ -412,6 +446,46 @@ def measure(E, args, key, ply=None, primary=True):
         prof = r.timings()                        # sampled stage events of the overlapped frames
     tp_flight = r.two_pass_info()                 # the latest frame of the timed region (None: one pass)
     tp_frames_flight, tp_share_flight = r.two_pass_state(args.two_pass_share)
+    fps = args.steps / elapsed
+    ms = 1e3 * elapsed / args.steps
+    rs = r
+
+    def finish(out):
+        """the line's end: dump / image of rank 0, every context closed, the scene's scratch files removed"""
+        if outputs is not None:
+            dump_outputs(args.dump_outputs, outputs)
+        if rank == 0 and primary and args.save_image:
+            img = state["fbs"][0][:H].float().cpu().numpy()
+            camera.write_image(args.save_image, img)
+        if rs is not r:
+            rs.close()
+        r.close()
+        if scene_dir:
+            import shutil
+            shutil.rmtree(scene_dir, ignore_errors=True)
+        return out
+
+    out = {
+        "metric": "frames_per_sec", "value": fps, "unit": "frames/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": ms, "higher_is_better": True,
+        "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic" if not ply else "file",
+        "gsplats_per_sec": n * fps / 1e9,
+        "rccl_ranks": (E.pg["world_size"] if E.pg["backend"] == "nccl" else 0) if world > 1 else 1,
+        "process_group": E.pg if world > 1 else None,
+        "full": bool(args.full),
+    }
+    if not args.full:
+        # a plain run: the timed block and what it says about itself; the statistics, checks and baselines are --full's
+        out["config"] = {"workload": wl["desc"], "key": key, "splats": n, "width": W, "height": H, "views": views, "framebuffer": wl["fb"],
+                         "sharding": ("bin rows of %d px over %d ranks, layout %s" % (TILE, world, lay)) if world > 1 else "none (one GPU)",
+                         "layout_model": lay_model, "frames_in_flight": P, "gpu_max_hw_queues": os.environ.get("GPU_MAX_HW_QUEUES"),
+                         "cu_partition": [p for p, _ in r.cu_partitions()], "async_submit": bool(r._async),
+                         "two_pass": {"mode": args.two_pass,
+                                      "timed_region": dict(tp_flight, frames_total=tp_frames_flight, share_pass1=tp_share_flight) if tp_flight else None},
+                         "cameras": ("cameras.json, %d poses" % len(scene_cams)) if scene_cams else "64-step orbit"}
+        out.update({"timed_blocks": len(blocks), "timed_seconds": float(np.sum(blocks)), "stages_ms": prof,
+                    "host_enqueue_ms_per_frame": 1e3 * enqueue / args.steps})
+        return finish(out)
 
     # ---- serial phase: the same frames one at a time on ONE stream (clean per-kernel durations, latency) ----
     if P == 1:
@@ -490,8 +564,6 @@ def measure(E, args, key, ply=None, primary=True):
         if (world > 1 and gathers is not None) else None
 
     phase("gather check done")
-    fps = args.steps / elapsed
-    ms = 1e3 * elapsed / args.steps
     # algorithmic bytes of the whole frame:  B = 16 N + (8+68+S+48) V + views (52 D + W H bpp)
     S = 244
     B_frame = 16.0 * n + (8 + 68 + S + 48) * V + (52.0 * D_total + W * H * bpp) * views
@@ -589,13 +661,7 @@ def measure(E, args, key, ply=None, primary=True):
         if prof_serial and prof_serial.get("project", 0) > 0 else None,
     }
     roof["hbm_delivered"] = hbm_delivered(dev) if (world == 1 and primary) else None      # (N > 1: the N = 1 line of the same box has it)
-    out = {
-        "metric": "frames_per_sec", "value": fps, "unit": "frames/s", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": ms, "higher_is_better": True,
-        "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic" if not ply else "file",
-        "gsplats_per_sec": n * fps / 1e9,
-        "rccl_ranks": (E.pg["world_size"] if E.pg["backend"] == "nccl" else 0) if world > 1 else 1,
-        "process_group": E.pg if world > 1 else None,
+    out.update({
         "config": {"workload": wl["desc"], "key": key, "splats": n, "width": W, "height": H,
                    "views": views, "framebuffer": wl["fb"],
                    "sharding": ("bin rows of %d px over %d ranks, layout %s%s" % (TILE, world, lay, " (contiguous bands, rank 0 weighted %d %% of another rank)" % lay_k if lay_kind == "weighted" else "")) if world > 1 else "none (one GPU)",
@@ -628,7 +694,7 @@ def measure(E, args, key, ply=None, primary=True):
         "frame_moved_frac_serial": min(1.0, (B_moved / (serial_ms * 1e-3)) / HBM_PEAK),
         "survey_8d_formula_GB": B_frame / 1e9,
         "roofline": roof,
-    }
+    })
     if gcheck is not None:
         out["gather_check"] = gcheck
     if tp_check is not None:
@@ -642,16 +708,7 @@ def measure(E, args, key, ply=None, primary=True):
 
     if rank == 0 and world == 1 and primary and not args.no_cpu_baseline:
         out["cpu_baseline"], out["cpu_baseline_literal"] = cpu_baseline(cloud, wl, cams_for, projs, vp, nf, args.cpu_frames)
-    if rank == 0 and primary and args.save_image:
-        img = state["fbs"][0][:H].float().cpu().numpy()
-        camera.write_image(args.save_image, img)
-    if rs is not r:
-        rs.close()
-    r.close()
-    if scene_dir:
-        import shutil
-        shutil.rmtree(scene_dir, ignore_errors=True)
-    return out
+    return finish(out)
 
 
 def main():
@@ -661,7 +718,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--workload", default="cfg2", choices=sorted(WORKLOADS))
     ap.add_argument("--also", default=None, help="comma-separated extra workloads measured after the primary one and "
-                    "embedded under \"also\" (default: cfg4 when --gpus > 1 -- the row-sharded BASELINE configs[3])")
+                    "embedded under \"also\" (default with --full: cfg4 when --gpus > 1 -- the row-sharded BASELINE configs[3])")
     ap.add_argument("--ply", default=None, help="render a real scene instead of the synthetic workload (BASELINE configs[2]: "
                     "Inria point_cloud.ply); cameras.json next to it (or up to two directories above) is replayed")
     ap.add_argument("--layout", default="auto", help="N > 1: how the bin rows are dealt to the ranks: contiguous | interleaved | "
@@ -697,6 +754,12 @@ def main():
                          "0 = the calling thread does (A/B); default: on with frames in flight")
     ap.add_argument("--timing-stride", type=int, default=8,
                     help="record per-stage hipEvents on every n-th frame of the timed region (0 = never)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: timed blocks repeated for >= 2 s (median), serial phase, roofline, "
+                         "statistics frames, two-pass / gather checks, HBM copy, CPU baselines, the default --also workload of N > 1")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last frame of the (first) timed block rendered as DIR/<name>.npy (float32, at most 64 MB in all: "
+                         "a fixed sample of the pixels of a larger frame)")
     args = ap.parse_args()
 
     import torch
@@ -714,8 +777,8 @@ def main():
                          % (args.gpus, E.world, args.gpus))
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs a GPU (no CPU fallback in the product path)")
-    if E.rank == 0:
-        graft.build()
+    if E.rank == 0 and not os.environ.get("MSPLAT_LIB_PATH") and graft._stale(graft.LIB, graft.SOURCES + graft.HEADERS):
+        graft.build()         # only a missing or out-of-date library is built here: a built tree is read, never written
     # MSPLAT_BENCH_ONE_DEVICE=1: debug aid for 1-GPU boxes -- every rank uses device 0 and the gather
     # runs over gloo; it exercises the N > 1 control flow (bands, gather, max-over-ranks timing), not xGMI.
     E.one_dev = os.environ.get("MSPLAT_BENCH_ONE_DEVICE") == "1"
@@ -743,7 +806,7 @@ def main():
     torch.cuda.set_stream(E.stream)
 
     out = measure(E, args, args.workload, ply=args.ply, primary=True)
-    also = args.also if args.also is not None else ("cfg4" if (E.world > 1 and args.workload == "cfg2" and not args.ply) else "")
+    also = args.also if args.also is not None else ("cfg4" if (args.full and E.world > 1 and args.workload == "cfg2" and not args.ply) else "")
     extra = {}
     for key in [k for k in also.split(",") if k]:
         if key not in WORKLOADS:

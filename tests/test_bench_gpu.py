@@ -6,6 +6,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -55,7 +56,7 @@ def _check_contract(d, n):
 
 
 def test_bench_single_gpu_json_contract():
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--cpu-frames", "1"] + QUICK,
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--full", "--cpu-frames", "1"] + QUICK,
                        cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     d = _line(p.stdout)
@@ -68,6 +69,52 @@ def test_bench_single_gpu_json_contract():
     assert d["value"] > 10 * cb["value"]                   # sanity only: the ratio says nothing about the kernels
 
 
+def test_bench_plain_run_times_exactly_the_steps_and_dumps_the_last_frame(tmp_path):
+    """a plain run (no --full): ONE timed block of exactly --steps frames, the headline fields and nothing measured beside them;
+    --dump-outputs writes the framebuffer of the last timed frame"""
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2",
+                        "--dump-outputs", str(tmp_path / "cfg2")], cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-2000:]
+    d = _line(p.stdout)
+    assert d["metric"] == "frames_per_sec" and d["unit"] == "frames/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["steps"] == 6 and d["warmup"] == 2 and d["timed_blocks"] == 1 and d["full"] is False
+    assert d["value"] > 0 and d["ms_per_step"] > 0 and abs(d["value"] * d["ms_per_step"] - 1e3) < 1e-3 * 1e3
+    assert abs(d["timed_seconds"] - 6 * d["ms_per_step"] * 1e-3) < 1e-9
+    assert "BASELINE configs[1]" in d["config"]["workload"] and d["config"]["splats"] == 1000000
+    for k in ("roofline", "serial", "cpu_baseline", "two_pass_check", "gather_check", "also"):
+        assert k not in d, k
+    img = np.load(str(tmp_path / "cfg2" / "image.npy"))
+    assert img.dtype == np.float32 and img.shape == (1080, 1920, 4) and np.isfinite(img).all()
+    assert (img[..., :3].sum(-1) > 0).mean() > 0.05
+
+
+def test_bench_dump_is_the_last_timed_frame_and_repeats(tmp_path):
+    """two plain runs with the same arguments dump the same frame, and it is what one context renders for the last timed step
+    (orbit step warmup + steps - 1)"""
+    for run in ("a", "b"):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "tiny", "--steps", "9",
+                            "--warmup", "3", "--dump-outputs", str(tmp_path / run)], cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        assert _line(p.stdout)["timed_blocks"] == 1
+    a, b = np.load(str(tmp_path / "a" / "image.npy")), np.load(str(tmp_path / "b" / "image.npy"))
+    assert sorted(os.listdir(str(tmp_path / "a"))) == ["image.npy"] and a.shape == (360, 640, 4) and a.dtype == np.float32
+    np.testing.assert_array_equal(a, b)
+    sys.path.insert(0, ROOT)
+    import math
+    from splatapult_amd import SplatRenderer, camera, synthetic
+    cloud = synthetic.make_cloud(20_000, seed=7, full_sh=True, pos_sigma=1.5)
+    cam = camera.orbit(7.0, 2.0 * math.pi * (3 + 9 - 1) / 64.0)
+    proj = camera.perspective(camera.FOVY, 640 / 360)
+    vp, nf = [0, 0, 640, 360], [camera.Z_NEAR, camera.Z_FAR]
+    r = SplatRenderer(device=0)
+    assert r.Init(cloud, False, False), r.last_error()
+    r.Sort(cam, proj, vp, nf)
+    img = r.Render(cam, proj, vp, nf)
+    r.close()
+    assert (img[..., :3].sum(-1) > 0).any()
+    np.testing.assert_array_equal(a, img)
+
+
 def test_bench_two_ranks_one_device_control_flow():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -76,7 +123,7 @@ def test_bench_two_ranks_one_device_control_flow():
     env = dict(os.environ, MSPLAT_BENCH_ONE_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
-                        "--gpus", "2", "--no-cpu-baseline", "--also", ""] + QUICK,
+                        "--gpus", "2", "--full", "--no-cpu-baseline", "--also", ""] + QUICK,
                        cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
     assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-2500:])
     d = _line(p.stdout)
@@ -101,7 +148,7 @@ def test_bench_two_ranks_one_device_control_flow():
     # the weighted contiguous bands through the same control flow: rank 0 owns 2.5x the rows of rank 1, gathered bit-exactly
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
-                        "--gpus", "2", "--no-cpu-baseline", "--also", "", "--layout", "weighted:250"] + QUICK,
+                        "--gpus", "2", "--full", "--no-cpu-baseline", "--also", "", "--layout", "weighted:250"] + QUICK,
                        cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
     assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-2500:])
     d = _line(p.stdout)
@@ -123,7 +170,7 @@ def test_bench_peer_store_check_child_mode():
 
 def test_bench_two_pass_workload_reports_what_the_passes_did():
     """a 6 M-splat workload with two-pass frames forced on: the line says what pass 1 and pass 2 did, and no stage fraction exceeds 1"""
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "cfg3", "--two-pass", "on",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--full", "--workload", "cfg3", "--two-pass", "on",
                         "--no-cpu-baseline", "--steps", "6", "--warmup", "2", "--prewarm", "12", "--serial-frames", "16", "--profile-frames", "1"],
                        cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]

@@ -1,5 +1,6 @@
 """CPU tests of the host side of the boundary: Ply / GaussianCloud re-implementation against the
-REAL reference parser (oracle/_ref, built from /root/reference/src/ply.cpp) and the oracle's
+REAL reference parser (oracle/_ref, built from the reference's src/ply.cpp; its recorded results where that was not built,
+tests/ref_ply_cases.py) and the oracle's
 load-time math, plus the matrix helpers and the synthetic generator."""
 import json
 import os
@@ -9,17 +10,11 @@ import pytest
 
 from oracle import oracle as orc
 from splatapult_amd import GaussianCloud, _capi, camera, synthetic
+from tests import ref_ply_cases
 from tests.golden.make_golden import PLY_NAMES
+from tests.ref_ply_cases import ref_read
 
 import ctypes as C
-
-needs_ref = pytest.mark.skipif(orc.ref_ply_lib() is None, reason="oracle/_ref not built (no reference checkout)")
-
-
-def write(path, header_lines, payload=b""):
-    with open(path, "wb") as f:
-        f.write(("\n".join(header_lines) + "\n").encode())
-        f.write(payload)
 
 
 def our_parse(path, full_sh=True):
@@ -29,9 +24,8 @@ def our_parse(path, full_sh=True):
 
 # ---- Ply parser vs the reference's own parser -------------------------------------------------
 
-@needs_ref
 def test_test_ply_offsets_match_reference_parser(golden_dir):
-    cnt, vs, props, raw = orc.ref_ply_read(os.path.join(golden_dir, "test.ply"), PLY_NAMES + ["nx", "ny", "nz"])
+    cnt, vs, props, raw = ref_read("test_ply", os.path.join(golden_dir, "test.ply"), PLY_NAMES + ["nx", "ny", "nz"])
     assert cnt == 16 and vs == 248
     assert props["x"][2] == 0 and props["f_dc_0"][2] == 24 and props["f_rest_44"][2] == 212
     assert props["opacity"][2] == 216 and props["scale_0"][2] == 220 and props["rot_0"][2] == 232
@@ -39,14 +33,12 @@ def test_test_ply_offsets_match_reference_parser(golden_dir):
     assert int(g["vertex_count"]) == cnt and int(g["vertex_size"]) == vs
 
 
-@needs_ref
-def test_import_ply_equals_reference_parse_plus_oracle_math(golden_dir, tmp_path):
+def test_import_ply_equals_reference_parse_plus_oracle_math(tmp_path):
     """ImportPly == (reference Ply::Parse) o (oracle restatement of gaussiancloud.cpp:254-361), bit for bit"""
-    a = synthetic.generate(300, seed=5)
-    path = str(tmp_path / "s.ply")
-    synthetic.write_ply(path, a)
-    for p, full in ((os.path.join(golden_dir, "test.ply"), True), (path, True), (path, False)):
-        cnt, vs, props, raw = orc.ref_ply_read(p, PLY_NAMES)
+    paths = ref_ply_cases.write_files(tmp_path)
+    for key, full in (("test_ply", True), ("synth300", True), ("synth300", False)):
+        p = paths[key]
+        cnt, vs, props, raw = ref_read(key, p, PLY_NAMES)
         v = raw.reshape(cnt, vs).view(np.float32)
 
         def c(n):
@@ -61,43 +53,19 @@ def test_import_ply_equals_reference_parse_plus_oracle_math(golden_dir, tmp_path
         np.testing.assert_array_equal(gc.as_array(), exp)
 
 
-@needs_ref
 def test_header_variants_accept_reject_like_reference(tmp_path):
     """comments, type aliases, odd property sets, malformed headers: same verdict as the reference parser"""
-    pay = np.arange(12, dtype="<f4").tobytes()
-    cases = {
-        "ok_comments": (["ply", "comment hello", "format binary_little_endian 1.0", "comment x", "element vertex 3",
-                         "property float x", "comment mid", "property float32 y", "property float z",
-                         "property float opacity", "end_header"], pay),
-        "ok_mixed_types": (["ply", "format binary_little_endian 1.0", "element vertex 1", "property uchar a",
-                            "property int16 b", "property double c", "property uint d", "property float x",
-                            "end_header"], bytes(19)),
-        "bad_magic": (["plx", "format binary_little_endian 1.0", "element vertex 0", "end_header"], b""),
-        "big_endian": (["ply", "format binary_big_endian 1.0", "element vertex 0", "end_header"], b""),
-        "ascii": (["ply", "format ascii 1.0", "element vertex 0", "end_header"], b""),
-        "no_element": (["ply", "format binary_little_endian 1.0", "property float x", "end_header"], b""),
-        "element_face": (["ply", "format binary_little_endian 1.0", "element face 3", "end_header"], b""),
-        "list_property": (["ply", "format binary_little_endian 1.0", "element vertex 1",
-                           "property list uchar int vertex_indices", "end_header"], b""),
-        "bad_type": (["ply", "format binary_little_endian 1.0", "element vertex 1", "property half x", "end_header"], b""),
-        "not_property": (["ply", "format binary_little_endian 1.0", "element vertex 1", "element face 2",
-                          "end_header"], b""),
-        "truncated_header": (["ply", "format binary_little_endian 1.0", "element vertex 1", "property float x"], b""),
-        "empty": ([], b""),
-        "zero_vertices": (["ply", "format binary_little_endian 1.0", "element vertex 0", "property float x",
-                           "end_header"], b""),
-    }
     L = _capi.lib()
-    for name, (hdr, payload) in cases.items():
-        p = str(tmp_path / (name + ".ply"))
-        write(p, hdr, payload)
-        ref = orc.ref_ply_read(p, ["x", "y", "z", "a", "b", "c", "d", "opacity"])
+    paths = ref_ply_cases.write_files(tmp_path)
+    for name in ref_ply_cases.HEADER_CASES:
+        p = paths[name]
+        ref = ref_read(name, p, ["x", "y", "z", "a", "b", "c", "d", "opacity"])
         ok, gc = our_parse(p)
         assert ok == (ref is not None), name
         if ref is not None:
             assert gc.GetNumGaussians() == ref[0], name
     # offsets of the mixed-type header accumulate exactly like the reference's (ply.cpp:106-112)
-    ref = orc.ref_ply_read(str(tmp_path / "ok_mixed_types.ply"), ["a", "b", "c", "d", "x"])
+    ref = ref_read("ok_mixed_types", paths["ok_mixed_types"], ["a", "b", "c", "d", "x"])
     assert {k: v[2] for k, v in ref[2].items()} == {"a": 0, "b": 1, "c": 3, "d": 11, "x": 15} and ref[1] == 19
     del L
 
