@@ -3,9 +3,8 @@
  * SplatRenderer::Sort()/Render() hot path.  This header is what an integrator binds; parity-test taps, probes and experiment
  * switches are in msplat_debug.h; the reasoning behind every default is in INTEGRATION.md (Appendix A) and DESIGN.md.
  *
- * The reference has no plugin/FFI layer: the seam is the C++ class SplatRenderer (/root/reference/src/splatrenderer.h:23-67)
- * fed by GaussianCloud (src/gaussiancloud.h:17-91).  Every entry point names the reference interface it replaces; the C++ shim
- * splatapult_amd/host/msplat_host.hpp re-creates the reference's class surface on top of this ABI.
+ * The reference's seam is the C++ class SplatRenderer (src/splatrenderer.h:23-67) fed by GaussianCloud (src/gaussiancloud.h:17-91);
+ * every entry point names the reference interface it replaces; splatapult_amd/host/msplat_host.hpp re-creates that class surface.
  *
  * Conventions (the reference's): matrices are float[16], column-major like glm; cameraMat = camera-to-world; viewport =
  * (x, y, W, H); nearFar = (near, far).  Functions return 0 (MSPLAT_OK) or a negative MSPLAT_ERR_* and never throw.  A context
@@ -76,12 +75,9 @@ typedef struct msplat_config {
 /* Byte offsets of the attributes inside one AoS record: the BinaryAttribute offsets SplatRenderer::BuildVertexArrayObject binds
  * (splatrenderer.cpp:345-391; gaussiancloud.cpp:633-657).  r_sh1 .. b_sh3 are ignored unless full_sh. */
 typedef struct msplat_attr_offsets {
-    uint32_t pos_with_alpha;
-    uint32_t r_sh0, g_sh0, b_sh0;
+    uint32_t pos_with_alpha, r_sh0, g_sh0, b_sh0;
     uint32_t cov3_col0, cov3_col1, cov3_col2;
-    uint32_t r_sh1, r_sh2, r_sh3;
-    uint32_t g_sh1, g_sh2, g_sh3;
-    uint32_t b_sh1, b_sh2, b_sh3;
+    uint32_t r_sh1, r_sh2, r_sh3, g_sh1, g_sh2, g_sh3, b_sh1, b_sh2, b_sh3;
 } msplat_attr_offsets;
 
 typedef struct msplat_stats {
@@ -121,18 +117,21 @@ int msplat_upload_cloud(msplat_ctx* ctx, const void* aos, uint64_t n, uint32_t s
  * BinaryAttribute::Read); without all of f_rest, or with full_sh == 0, the cloud is SH degree 0 (gaussiancloud.cpp:188-205). */
 typedef struct msplat_ply_layout {
     uint32_t vertex_size;
-    int32_t x, y, z;
-    int32_t f_dc[3];
+    int32_t x, y, z, f_dc[3];
     int32_t f_rest[45];
-    int32_t opacity;
-    int32_t scale[3];
-    int32_t rot[4];
+    int32_t opacity, scale[3], rot[4];
 } msplat_ply_layout;
 int msplat_upload_ply_vertices(msplat_ctx* ctx, const void* vertices, uint64_t n, const msplat_ply_layout* layout, int full_sh);
 /* Ply::Parse (ply.cpp:72-87) on the host + the ingest kernel: GaussianCloud::ImportPly + SplatRenderer::Init in one call */
 int msplat_upload_ply(msplat_ctx* ctx, const char* path, int import_full_sh);
 /* the device cloud in the reference's interleaved layout (100 B / 244 B records), upload numbering */
 int msplat_download_cloud(msplat_ctx* ctx, void* aos_out, uint64_t cap_bytes);
+/* f_rest storage of the context's NEXT splat upload, any route (INTEGRATION.md 12).  SH_FP16: IEEE fp16, nearest even, 160 / 96-B
+ * records; pixels = FP32 of the fp16-rounded cloud; a finite |f_rest| >= 65520 fails the upload (MSPLAT_ERR_UNSUPPORTED).  Attached
+ * contexts render the owner's storage; points ignore it.  get: storage of the cloud rendered (-1: no cloud / NULL). */
+enum { MSPLAT_STORAGE_FP32 = 0, MSPLAT_STORAGE_SH_FP16 = 1 };
+int msplat_set_cloud_storage(msplat_ctx* ctx, int32_t storage);
+int msplat_get_cloud_storage(const msplat_ctx* ctx);
 
 /* ---- SplatRenderer::Sort (splatrenderer.cpp:153-312): cull + depth key (presort_compute.glsl:31-57), stable ascending 32-bit
  * radix sort; the sorted index list stays context state for the following renders.  Asynchronous: the reference's 4-byte
@@ -212,6 +211,7 @@ int msplat_group_upload_cloud(msplat_group* g, const void* aos, uint64_t n, uint
                               const msplat_attr_offsets* off, int full_sh);
 int msplat_group_upload_gaussian_cloud(msplat_group* g, const msplat_cloud* c);
 int msplat_group_upload_ply(msplat_group* g, const char* path, int import_full_sh);
+int msplat_group_set_cloud_storage(msplat_group* g, int32_t storage);   /* msplat_set_cloud_storage on every context */
 int msplat_group_set_layout(msplat_group* g, int32_t kind, int32_t block_rows);
 int msplat_group_set_band_cull(msplat_group* g, int enable);
 int msplat_group_sort(msplat_group* g, const float cameraMat[16], const float projMat[16], const float viewport[4],

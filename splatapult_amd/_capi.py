@@ -20,6 +20,8 @@ TWO_PASS_AUTO, TWO_PASS_ON, TWO_PASS_OFF = 0, 1, 2          # msplat_config.two_
 BANDS_CONTIGUOUS, BANDS_INTERLEAVED, BANDS_BLOCK_INTERLEAVED, BANDS_ROOT_WEIGHTED = 0, 1, 2, 3
 EXCHANGE_WIRE_FP16 = 1              # msplat_band_exchange flags
 CU_ALL, CU_EVEN, CU_ODD = 0, 1, 2    # msplat_config.cu_partition
+STORAGE_FP32, STORAGE_SH_FP16 = 0, 1  # msplat_set_cloud_storage: f_rest as fp32 or IEEE fp16
+CLOUD_STORAGES = {"fp32": STORAGE_FP32, "sh_fp16": STORAGE_SH_FP16}
 # "weighted": contiguous bands, rank 0 (the gather's root) weighted block_rows PERCENT of another rank (msplat.h)
 BAND_KINDS = {"contiguous": BANDS_CONTIGUOUS, "interleaved": BANDS_INTERLEAVED, "block": BANDS_BLOCK_INTERLEAVED,
               "weighted": BANDS_ROOT_WEIGHTED}
@@ -100,6 +102,9 @@ SYMBOLS = [
     ("msplat_group_upload_cloud", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(AttrOffsets), C.c_int]),
     ("msplat_group_upload_gaussian_cloud", C.c_int, [C.c_void_p, C.c_void_p]),
     ("msplat_group_upload_ply", C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
+    ("msplat_group_set_cloud_storage", C.c_int, [C.c_void_p, C.c_int32]),
+    ("msplat_set_cloud_storage", C.c_int, [C.c_void_p, C.c_int32]),
+    ("msplat_get_cloud_storage", C.c_int, [C.c_void_p]),
     ("msplat_group_set_layout", C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     ("msplat_group_set_band_cull", C.c_int, [C.c_void_p, C.c_int]),
     ("msplat_group_sort", C.c_int, [C.c_void_p, _F16, _F16, _F16, _F16]),

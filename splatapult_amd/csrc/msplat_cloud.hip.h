@@ -27,9 +27,12 @@ struct PlyLayout {             // mirrors msplat_ply_layout (include/msplat.h)
     int32_t rot[4];
 };
 
-template <bool FULL_SH>
+// STORAGE = kStorageShFp16: the records are written compact (msplat_common.hip.h: sh16_pack); *n_over counts the f_rest values
+// beyond the fp16 range (the upload then fails)
+template <bool FULL_SH, int STORAGE = kStorageFp32>
 __global__ __launch_bounds__(64) void ingest_kernel(const char* __restrict__ raw, uint64_t n, PlyLayout L,
-                                                    float4* __restrict__ pos4, float4* __restrict__ recs)
+                                                    float4* __restrict__ pos4, float4* __restrict__ recs,
+                                                    uint32_t* __restrict__ n_over)
 {
     extern __shared__ __attribute__((aligned(16))) char s_raw[];
     constexpr int F4 = FULL_SH ? 16 : 8;
@@ -96,8 +99,19 @@ __global__ __launch_bounds__(64) void ingest_kernel(const char* __restrict__ raw
             f[16 + c * 3 + r] = s;
         }
     pos4[i] = make_float4(f[0], f[1], f[2], footprint_bound(&f[16], f[3]));      // .w: world-space footprint bound for the band cull
+    if constexpr (STORAGE == kStorageShFp16) {
+        constexpr int CF4 = cloud_f4(kStorageShFp16, FULL_SH);
+        uint32_t w[CF4 * 4];
+        const uint32_t over = sh16_pack<FULL_SH>(f, w);
+        if (over) atomicAdd(n_over, over);
 #pragma unroll
-    for (int k = 0; k < F4; ++k) recs[i * F4 + k] = make_float4(f[4 * k], f[4 * k + 1], f[4 * k + 2], f[4 * k + 3]);
+        for (int k = 0; k < CF4; ++k)
+            recs[i * CF4 + k] = make_float4(__uint_as_float(w[4 * k]), __uint_as_float(w[4 * k + 1]), __uint_as_float(w[4 * k + 2]),
+                                            __uint_as_float(w[4 * k + 3]));
+    } else {
+#pragma unroll
+        for (int k = 0; k < F4; ++k) recs[i * F4 + k] = make_float4(f[4 * k], f[4 * k + 1], f[4 * k + 2], f[4 * k + 3]);
+    }
 }
 
 // ------------------------------------------------------------------------------------------

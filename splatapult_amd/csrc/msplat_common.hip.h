@@ -262,6 +262,92 @@ __host__ __device__ inline float footprint_bound(const float* S, float alpha)
     return bnd > 1.17549435e-38f ? bnd : 1.17549435e-38f;
 }
 
+// ------------------------------------------------------------------------------------------
+// Cloud storage (msplat_set_cloud_storage; mirrors MSPLAT_STORAGE_*).  FP32: the padded records of 16 (full SH) or 8 float4 with
+// the reference's float order.  SH_FP16: a 16-float fp32 head -- x y z alpha, DC r g b, Sigma[9] -- bit for bit the FP32 values,
+// then the f_rest slots of the FP32 record as IEEE fp16 (band 1 of r g b first, so a degree-1 record is a prefix of a full one),
+// two per dword, low half first; zero padding to 10 (full SH: 160 B) or 6 float4 (degree 1: 96 B).
+// The conversions are integer bit operations: they do not depend on a wave's denorm mode and keep fp16 subnormals both ways.
+// ------------------------------------------------------------------------------------------
+constexpr int kStorageFp32 = 0, kStorageShFp16 = 1;
+__host__ __device__ constexpr int cloud_f4(int storage, bool full_sh)
+{
+    return storage == kStorageShFp16 ? (full_sh ? 10 : 6) : (full_sh ? 16 : 8);
+}
+__host__ __device__ constexpr int sh16_count(bool full_sh) { return full_sh ? 45 : 9; }
+// fp32 record float of head slot h (0..15) and of half h (0..44)
+__host__ __device__ constexpr int sh16_head_slot(int h) { return h < 4 ? h : (h < 7 ? 4 + 4 * (h - 4) : 16 + (h - 7)); }
+__host__ __device__ constexpr int sh16_half_slot(int h) { return h < 9 ? 5 + 4 * (h / 3) + h % 3 : 25 + (h - 9); }
+
+// round to nearest even, like numpy.float16 (subnormals included); NaN keeps its sign and top payload bits
+__host__ __device__ inline uint32_t f32_to_f16_bits(uint32_t x)
+{
+    const uint32_t sign = (x >> 16) & 0x8000u, a = x & 0x7FFFFFFFu;
+    if (a > 0x7F800000u) {
+        const uint32_t m = (a >> 13) & 0x3FFu;
+        return sign | 0x7C00u | (m ? m : 1u);
+    }
+    if (a >= 0x477FF000u) return sign | 0x7C00u;                  // >= 65520 (and inf): inf
+    if (a >= 0x38800000u) return sign | ((a - 0x38000000u + 0xFFFu + ((a >> 13) & 1u)) >> 13);   // normal fp16
+    if (a <= 0x33000000u) return sign;                            // <= 2^-25: zero (2^-25 itself is the tie with 0)
+    const uint32_t m = (a & 0x7FFFFFu) | 0x800000u, s = 126u - (a >> 23);      // subnormal fp16: m * 2^-s units of 2^-24
+    uint32_t q = m >> s;
+    const uint32_t rem = m & ((1u << s) - 1u), half = 1u << (s - 1u);
+    if (rem > half || (rem == half && (q & 1u))) ++q;
+    return sign | q;
+}
+
+__host__ __device__ inline uint32_t f16_bits_to_f32_bits(uint32_t h)
+{
+    const uint32_t sign = (h & 0x8000u) << 16, e = (h >> 10) & 0x1Fu, m = h & 0x3FFu;
+    if (e == 31u) return sign | 0x7F800000u | (m << 13);
+    if (e != 0u) return sign | (((h & 0x7FFFu) << 13) + 0x38000000u);
+    // subnormal or zero: m * 2^-24 exactly, built from m's leading bit (2^-24 .. 2^-15 are normal fp32 numbers)
+    if (m == 0u) return sign;
+    const uint32_t k = 31u - (uint32_t)__builtin_clz(m);          // m = 1.f * 2^k
+    return sign | ((103u + k) << 23) | ((m << (23u - k)) & 0x7FFFFFu);
+}
+
+__host__ __device__ inline uint32_t f32_bits(float v) { uint32_t u; __builtin_memcpy(&u, &v, 4); return u; }
+__host__ __device__ inline float f32_from_bits(uint32_t u) { float v; __builtin_memcpy(&v, &u, 4); return v; }
+
+// FP32 record floats f[] -> the SH_FP16 record w[cloud_f4(kStorageShFp16, FULL_SH) * 4]; returns the number of finite f_rest values
+// that fp16 cannot hold (|c| >= 65520 rounds to inf)
+template <bool FULL_SH>
+__host__ __device__ inline uint32_t sh16_pack(const float* f, uint32_t* w)
+{
+    constexpr int NW = cloud_f4(kStorageShFp16, FULL_SH) * 4, NH = sh16_count(FULL_SH);
+    uint32_t over = 0u;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) w[k] = f32_bits(f[sh16_head_slot(k)]);
+#pragma unroll
+    for (int j = 0; j < NW - 16; ++j) {
+        uint32_t v = 0u;
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+            const int h = 2 * j + p;
+            if (h < NH) {
+                const uint32_t x = f32_bits(f[sh16_half_slot(h)]), a = x & 0x7FFFFFFFu;
+                over += (a >= 0x477FF000u && a < 0x7F800000u) ? 1u : 0u;
+                v |= f32_to_f16_bits(x) << (16 * p);
+            }
+        }
+        w[16 + j] = v;
+    }
+    return over;
+}
+
+// the inverse: fills the 16 head slots and the f_rest slots of an FP32 record f[] (padding slots are left alone)
+template <bool FULL_SH>
+__host__ __device__ inline void sh16_unpack(const uint32_t* w, float* f)
+{
+    constexpr int NH = sh16_count(FULL_SH);
+#pragma unroll
+    for (int k = 0; k < 16; ++k) f[sh16_head_slot(k)] = f32_from_bits(w[k]);
+#pragma unroll
+    for (int h = 0; h < NH; ++h) f[sh16_half_slot(h)] = f32_from_bits(f16_bits_to_f32_bits((w[16 + h / 2] >> (16 * (h & 1))) & 0xFFFFu));
+}
+
 // Milder form: only GROUPS of g consecutive chunks share an XCD (workgroups p and p + 8 of every block of 8 g, which are
 // dispatched right after one another): the partial cache lines at the seams between the runs that g neighbouring chunks write
 // next to each other are then merged in that XCD's L2 before they go to HBM, without giving each XCD one long region of the

@@ -44,6 +44,8 @@ struct Buf {
 struct CloudStore {
     int device = 0;
     Buf pos4, recs;
+    int storage = kStorageFp32;   // MSPLAT_STORAGE_* of the records, and their float4 count (cloud_f4; 1 for a point cloud)
+    int F4 = 0;
     // spatial storage order (r4): slot j holds the splat uploaded as order_host[j]; one bounding box per kBoxSplats slots
     bool reordered = false;
     std::vector<uint32_t> order_host;
@@ -127,6 +129,8 @@ struct msplat_ctx {
     // cloud
     uint64_t N = 0;
     bool full_sh = false;
+    int cloud_storage = kStorageFp32;    // the store's MSPLAT_STORAGE_* (what project_kernel reads)
+    int storage_cfg = kStorageFp32;      // msplat_set_cloud_storage: what the next splat upload stores
     bool has_cloud = false;
     bool has_sort = false;
     std::shared_ptr<CloudStore> store;   // owns pos4 / recs (possibly shared with other contexts)
@@ -1215,9 +1219,14 @@ static void issue_projection(RenderChain& rc, int mode, float occ_frac)
     }
     const ProjParams pp = proj_params(fp);
     uint32_t* zq = (mode != PROJ_LISTED && ctx->depth_bits) ? (uint32_t*)ctx->zq.p : nullptr;
-#define MSPLAT_PROJECT(SH, MODE, GRID, DV, EX, V1)                                                                          \
-    hipLaunchKernelGGL((project_kernel<SH, MODE>), dim3(GRID), dim3(kProjThreads), 0, s, (const uint32_t*)ctx->valA.p, DV,  \
+#define MSPLAT_PROJECT_ST(SH, MODE, ST, GRID, DV, EX, V1)                                                                     \
+    hipLaunchKernelGGL((project_kernel<SH, MODE, ST>), dim3(GRID), dim3(kProjThreads), 0, s, (const uint32_t*)ctx->valA.p, DV, \
                        (const float4*)ctx->recs.p, pp, (float4*)ctx->rec2d.p, (uint32_t*)ctx->rect.p, zq, EX, V1)
+#define MSPLAT_PROJECT(SH, MODE, GRID, DV, EX, V1)                                                                          \
+    do {                                                                                                                    \
+        if (ctx->cloud_storage == kStorageShFp16) MSPLAT_PROJECT_ST(SH, MODE, kStorageShFp16, GRID, DV, EX, V1);            \
+        else MSPLAT_PROJECT_ST(SH, MODE, kStorageFp32, GRID, DV, EX, V1);                                                   \
+    } while (0)
     if (mode == PROJ_PASS1) {
         // (project_kernel's first pass computes the cut and leaves it in occ[0])
         const ProjExtra ex{nullptr, occ, nullptr, occ_frac};
@@ -1241,6 +1250,7 @@ static void issue_projection(RenderChain& rc, int mode, float occ_frac)
         else MSPLAT_PROJECT(false, PROJ_PLAIN, pgrid, (const uint32_t*)d_Vsort, ex, ProjNoView1{0});
     }
 #undef MSPLAT_PROJECT
+#undef MSPLAT_PROJECT_ST
 }
 
 // bin lists over the current rectangles: column pass (bin1_*), row pass (radix_*<MODE_PAIR>), list offsets + work order.

@@ -448,6 +448,18 @@ int msplat_group_upload_ply(msplat_group* g, const char* path, int import_full_s
     return for_all(g, [&](uint32_t i) { return msplat_upload_ply(g->ctx[i], path, import_full_sh); });
 }
 
+int msplat_group_set_cloud_storage(msplat_group* g, int32_t storage)
+{
+    if (!g) return gfail(nullptr, MSPLAT_ERR_INVALID_ARG, "group is NULL");
+    if (storage != MSPLAT_STORAGE_FP32 && storage != MSPLAT_STORAGE_SH_FP16)
+        return gfail(g, MSPLAT_ERR_INVALID_ARG, "msplat_group_set_cloud_storage: unknown storage %d", storage);
+    for (msplat_ctx* c : g->ctx) {
+        const int rc = msplat_set_cloud_storage(c, storage);
+        if (rc) return gfail(g, rc, "%s", msplat_last_error(c));
+    }
+    return MSPLAT_OK;
+}
+
 int msplat_group_set_layout(msplat_group* g, int32_t kind, int32_t block_rows)
 {
     if (!g) return gfail(nullptr, MSPLAT_ERR_INVALID_ARG, "group is NULL");

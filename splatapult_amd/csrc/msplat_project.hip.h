@@ -38,7 +38,9 @@ constexpr int kProjThreads = 64;          // one wave per workgroup: wave-privat
 // one wave-block of 64 ranks: cooperative gather of the records, then the vertex + geometry stage per lane (rank r, rank rl inside
 // its view; lanes with !valid take part in the gather only).  s_stage: 64 * STRIDE floats of wave-private LDS.
 // vm / pm / eye: the view's matrices (kernarg words: they stay in SGPRs); SECOND: the second view of a two-view chain.
-template <bool FULL_SH, bool SECOND>
+// STORAGE = kStorageShFp16: compact records (msplat_common.hip.h), gathered the same way -- piece p = 64 it + lane of load it is
+// piece p % F4 of record p / F4 -- and widened into the FP32 record's slots, so that everything after the gather runs unchanged.
+template <bool FULL_SH, bool SECOND, int STORAGE = kStorageFp32>
 __device__ __forceinline__ void project_block(const uint32_t r, const uint32_t rl, const bool valid, const int lane,
                                               const uint32_t* __restrict__ sorted_idx, const float4* __restrict__ recs,
                                               const ProjParams& fp, const float* vm, const float* pm, const float* eye,
@@ -49,27 +51,53 @@ __device__ __forceinline__ void project_block(const uint32_t r, const uint32_t r
     constexpr int RPI = 64 / F4;              // records fetched per wave-wide load instruction
     constexpr int STRIDE = F4 * 4 + 4;        // dwords
     const uint32_t i = valid ? sorted_idx[rl] : 0u;
-    {
-        const int sub = lane % F4;
-        float4 tmp[F4];
-#pragma unroll
-        for (int it = 0; it < F4; ++it) {
-            const int owner = it * RPI + lane / F4;
-            const uint32_t oi = __shfl(i, owner, 64);
-            tmp[it] = recs[(size_t)oi * F4 + sub];
-        }
-#pragma unroll
-        for (int it = 0; it < F4; ++it) {
-            const int owner = it * RPI + lane / F4;
-            *reinterpret_cast<float4*>(&s_stage[owner * STRIDE + sub * 4]) = tmp[it];
-        }
-    }
-    __syncthreads();
     float f[F4 * 4];
+    if constexpr (STORAGE == kStorageFp32) {
+        {
+            const int sub = lane % F4;
+            float4 tmp[F4];
 #pragma unroll
-    for (int k = 0; k < F4; ++k) {
-        const float4 v = *reinterpret_cast<const float4*>(&s_stage[lane * STRIDE + k * 4]);
-        f[4 * k + 0] = v.x; f[4 * k + 1] = v.y; f[4 * k + 2] = v.z; f[4 * k + 3] = v.w;
+            for (int it = 0; it < F4; ++it) {
+                const int owner = it * RPI + lane / F4;
+                const uint32_t oi = __shfl(i, owner, 64);
+                tmp[it] = recs[(size_t)oi * F4 + sub];
+            }
+#pragma unroll
+            for (int it = 0; it < F4; ++it) {
+                const int owner = it * RPI + lane / F4;
+                *reinterpret_cast<float4*>(&s_stage[owner * STRIDE + sub * 4]) = tmp[it];
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < F4; ++k) {
+            const float4 v = *reinterpret_cast<const float4*>(&s_stage[lane * STRIDE + k * 4]);
+            f[4 * k + 0] = v.x; f[4 * k + 1] = v.y; f[4 * k + 2] = v.z; f[4 * k + 3] = v.w;
+        }
+    } else {
+        constexpr int CF4 = cloud_f4(STORAGE, FULL_SH);
+        constexpr int CSTRIDE = CF4 * 4 + 4;      // dwords
+        float4 tmp[CF4];
+#pragma unroll
+        for (int it = 0; it < CF4; ++it) {
+            const int p = it * 64 + lane;
+            const uint32_t oi = __shfl(i, p / CF4, 64);
+            tmp[it] = recs[(size_t)oi * CF4 + p % CF4];
+        }
+#pragma unroll
+        for (int it = 0; it < CF4; ++it) {
+            const int p = it * 64 + lane;
+            *reinterpret_cast<float4*>(&s_stage[(p / CF4) * CSTRIDE + (p % CF4) * 4]) = tmp[it];
+        }
+        __syncthreads();
+        uint32_t w[CF4 * 4];
+#pragma unroll
+        for (int k = 0; k < CF4; ++k) {
+            const float4 v = *reinterpret_cast<const float4*>(&s_stage[lane * CSTRIDE + k * 4]);
+            w[4 * k + 0] = __float_as_uint(v.x); w[4 * k + 1] = __float_as_uint(v.y);
+            w[4 * k + 2] = __float_as_uint(v.z); w[4 * k + 3] = __float_as_uint(v.w);
+        }
+        sh16_unpack<FULL_SH>(w, f);
     }
     if (!valid) return;
     const float x = f[0], y = f[1], z = f[2], alpha = f[3];
@@ -243,7 +271,7 @@ struct ProjExtra {
     float occ_share;             // PROJ_PASS1: share of the visible splats in pass 1
 };
 
-template <bool FULL_SH, int MODE>
+template <bool FULL_SH, int MODE, int STORAGE = kStorageFp32>
 __global__ __launch_bounds__(kProjThreads) void project_kernel(const uint32_t* __restrict__ sorted_idx,
                                                                const uint32_t* __restrict__ d_V,
                                                                const float4* __restrict__ recs,
@@ -256,14 +284,13 @@ __global__ __launch_bounds__(kProjThreads) void project_kernel(const uint32_t* _
     // PROJ_PASS1: ranks below cut = occ_cut(V, occ_share) only get an empty rectangle, their records are not fetched; the cut is
     // left in d_cut[0] (= occ[0]).  PROJ_LISTED: the *d_V ranks to project are listed (any order); records and rectangles are
     // stored by rank as always.
-    // Records are 256 B (full SH) or 128 B (base) and line aligned.  The gather by sorted index is
+    // Records are 256 B (full SH) or 128 B (base) and line aligned (SH_FP16: 160 / 96 B).  The gather by sorted index is
     // done cooperatively (project_block): F4 consecutive lanes fetch one whole record (coalesced 256/128 B), the wave
     // stages 64 records in LDS, then every lane reads its own record back (stride 68/36 dwords keeps
     // the ds_read_b128 accesses conflict free).
     __builtin_amdgcn_s_setprio(kProjPrio);
     MSPLAT_STAMP(KID_PROJECT);
-    constexpr int F4 = FULL_SH ? 16 : 8;
-    constexpr int STRIDE = F4 * 4 + 4;        // dwords
+    constexpr int STRIDE = cloud_f4(STORAGE, FULL_SH) * 4 + 4;        // dwords
     __shared__ __attribute__((aligned(16))) float s_stage[64 * STRIDE];
     const uint32_t V = *d_V;
     const int lane = threadIdx.x;
@@ -274,7 +301,7 @@ __global__ __launch_bounds__(kProjThreads) void project_kernel(const uint32_t* _
         for (uint32_t s0 = blockIdx.x * kProjThreads; s0 < V; s0 += gridDim.x * kProjThreads) {
             const bool ok = s0 + lane < V;
             const uint32_t rk = ok ? ex.rank_list[s0 + lane] : 0u;
-            project_block<FULL_SH, false>(rk, rk, ok, lane, sorted_idx, recs, fp, fp.view, fp.proj, fp.eye, out_rec, out_rect, out_zq, s_stage);
+            project_block<FULL_SH, false, STORAGE>(rk, rk, ok, lane, sorted_idx, recs, fp, fp.view, fp.proj, fp.eye, out_rec, out_rect, out_zq, s_stage);
             __syncthreads();              // s_stage is reused
         }
     } else if constexpr (MODE == PROJ_PASS1) {
@@ -283,7 +310,7 @@ __global__ __launch_bounds__(kProjThreads) void project_kernel(const uint32_t* _
         if (blockIdx.x == 0 && lane == 0) { ex.d_cut[0] = cut; ex.d_cut[1] = 0u; ex.d_cut[2] = 0u; }      // occ[0 .. 2] for the kernels that follow
         for (uint32_t i = blockIdx.x * kProjThreads + lane; i < cut; i += gridDim.x * kProjThreads) out_rect[i] = kRectEmpty;
         for (uint32_t r0 = cut + blockIdx.x * kProjThreads; r0 < V; r0 += gridDim.x * kProjThreads) {
-            project_block<FULL_SH, false>(r0 + lane, r0 + lane, r0 + lane < V, lane, sorted_idx, recs, fp, fp.view, fp.proj, fp.eye, out_rec, out_rect, out_zq, s_stage);
+            project_block<FULL_SH, false, STORAGE>(r0 + lane, r0 + lane, r0 + lane < V, lane, sorted_idx, recs, fp, fp.view, fp.proj, fp.eye, out_rec, out_rect, out_zq, s_stage);
             __syncthreads();
         }
     } else if constexpr (MODE == PROJ_TWO_VIEWS) {
@@ -296,16 +323,16 @@ __global__ __launch_bounds__(kProjThreads) void project_kernel(const uint32_t* _
         const uint32_t r = blockIdx.x * kProjThreads + lane;
         if (blockIdx.x * kProjThreads >= V1) {                        // wave-uniform
             const uint32_t rl = r - V1;                               // rank inside the view
-            project_block<FULL_SH, true>(r, rl, rl < V, lane, sorted_idx, recs, fp, v1.view, v1.proj, v1.eye, out_rec, out_rect, out_zq, s_stage);
+            project_block<FULL_SH, true, STORAGE>(r, rl, rl < V, lane, sorted_idx, recs, fp, v1.view, v1.proj, v1.eye, out_rec, out_rect, out_zq, s_stage);
         } else {
             const bool valid = r < V;
             if (!valid) out_rect[r] = kRectEmpty;                     // (the gap between the views, and nothing else)
-            project_block<FULL_SH, false>(r, r, valid, lane, sorted_idx, recs, fp, fp.view, fp.proj, fp.eye, out_rec, out_rect, out_zq, s_stage);
+            project_block<FULL_SH, false, STORAGE>(r, r, valid, lane, sorted_idx, recs, fp, fp.view, fp.proj, fp.eye, out_rec, out_rect, out_zq, s_stage);
         }
     } else {
         if (blockIdx.x * kProjThreads >= V) return;
         const uint32_t r = blockIdx.x * kProjThreads + lane;
-        project_block<FULL_SH, false>(r, r, r < V, lane, sorted_idx, recs, fp, fp.view, fp.proj, fp.eye, out_rec, out_rect, out_zq, s_stage);
+        project_block<FULL_SH, false, STORAGE>(r, r, r < V, lane, sorted_idx, recs, fp, fp.view, fp.proj, fp.eye, out_rec, out_rect, out_zq, s_stage);
     }
 }
 

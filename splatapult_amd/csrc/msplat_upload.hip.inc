@@ -43,7 +43,9 @@ static int prepare_cloud_buffers(msplat_ctx* ctx, uint64_t n, bool full_sh, cons
     ctx->has_render = false;
     ctx->N = n;
     ctx->full_sh = full_sh;
-    const int F4 = ctx->point_mode ? 1 : (ctx->full_sh ? 16 : 8);
+    // the storage kind belongs to the store: attached contexts render the owner's, point clouds are always FP32
+    const int storage = share ? share->storage : (ctx->point_mode ? kStorageFp32 : ctx->storage_cfg);
+    const int F4 = ctx->point_mode ? 1 : cloud_f4(storage, ctx->full_sh);
     const size_t alloc_n = std::max<uint64_t>(n, 1);
     int rc;
     if (share) {
@@ -52,8 +54,9 @@ static int prepare_cloud_buffers(msplat_ctx* ctx, uint64_t n, bool full_sh, cons
         ctx->store = share;
     } else {
         const size_t need_pos = alloc_n * 16, need_rec = alloc_n * F4 * 16;
+        // (a store of another storage kind is not reused: device_bytes then describes the records in use)
         const bool reuse = ctx->store && ctx->store.use_count() == 1 && ctx->store->pos4.bytes >= need_pos &&
-                           ctx->store->recs.bytes >= need_rec;
+                           ctx->store->recs.bytes >= need_rec && ctx->store->storage == storage;
         if (!reuse) {
             if (ctx->store && ctx->store.use_count() == 1)
                 ctx->device_bytes -= ctx->store->pos4.bytes + ctx->store->recs.bytes;
@@ -69,6 +72,8 @@ static int prepare_cloud_buffers(msplat_ctx* ctx, uint64_t n, bool full_sh, cons
             ctx->device_bytes += need_pos + need_rec;
             ctx->store = st;
         }
+        ctx->store->storage = storage;
+        ctx->store->F4 = F4;
         // a fresh upload starts in upload order (spatial_reorder runs once the cloud is on the device)
         ctx->store->reordered = false;
         ctx->store->order_host.clear();
@@ -77,6 +82,7 @@ static int prepare_cloud_buffers(msplat_ctx* ctx, uint64_t n, bool full_sh, cons
     }
     ctx->pos4 = ctx->store->pos4;
     ctx->recs = ctx->store->recs;
+    ctx->cloud_storage = ctx->store->storage;
     if ((rc = buf_alloc(ctx, ctx->keyA, alloc_n * 4))) return rc;
     if ((rc = buf_alloc(ctx, ctx->keyB, alloc_n * 4))) return rc;
     if ((rc = buf_alloc(ctx, ctx->valA, alloc_n * 4))) return rc;
@@ -149,7 +155,7 @@ static int spatial_reorder(msplat_ctx* ctx)
     CloudStore& st = *ctx->store;
     hipStream_t s = ctx->stream;
     const uint32_t N = (uint32_t)n64;
-    const int F4 = ctx->full_sh ? 16 : 8;
+    const int F4 = st.F4;
     const size_t need_pos = (size_t)N * 16, need_rec = (size_t)N * F4 * 16;
     void *npos = nullptr, *nrec = nullptr;
     if (hipMalloc(&npos, need_pos) != hipSuccess || hipMalloc(&nrec, need_rec) != hipSuccess) {
@@ -239,7 +245,9 @@ int msplat_upload_cloud(msplat_ctx* ctx, const void* aos, uint64_t n, uint32_t s
     ctx->point_mode = false;
     int rc = prepare_cloud_buffers(ctx, n, full_sh != 0, nullptr);
     if (rc) return rc;
-    const int F4 = ctx->full_sh ? 16 : 8;
+    const int F4 = ctx->store->F4;
+    const bool sh16 = ctx->cloud_storage == kStorageShFp16;
+    uint64_t n_over = 0;
 
     // repack: reference AoS (100 B / 244 B, arbitrary offsets) -> 16-byte aligned padded records with the
     // reference's float order (gaussiancloud.cpp:32-56), plus the vec4(x,y,z,1) array of splatrenderer.cpp:106-111
@@ -269,7 +277,8 @@ int msplat_upload_cloud(msplat_ctx* ctx, const void* aos, uint64_t n, uint32_t s
         const size_t cnt = (size_t)std::min<uint64_t>(chunk, n - base);
         for (size_t j = 0; j < cnt; ++j) {
             const uint8_t* rec = src + (base + j) * stride_bytes;
-            float* d = stage_rec.data() + j * F4 * 4;
+            float full[64];
+            float* d = sh16 ? full : stage_rec.data() + j * F4 * 4;
             std::memcpy(d + 0, rec + off->pos_with_alpha, 16);
             std::memcpy(d + 4, rec + off->r_sh0, 16);
             std::memcpy(d + 8, rec + off->g_sh0, 16);
@@ -285,10 +294,17 @@ int msplat_upload_cloud(msplat_ctx* ctx, const void* aos, uint64_t n, uint32_t s
             }
             float* p = stage_pos.data() + j * 4;
             p[0] = d[0]; p[1] = d[1]; p[2] = d[2]; p[3] = footprint_bound(d + 16, d[3]);      // .w: footprint bound for the band cull
+            if (sh16) {
+                uint32_t* w = reinterpret_cast<uint32_t*>(stage_rec.data() + j * F4 * 4);
+                n_over += ctx->full_sh ? sh16_pack<true>(d, w) : sh16_pack<false>(d, w);
+            }
         }
         HIP_TRY(ctx, hipMemcpy((char*)ctx->recs.p + base * F4 * 16, stage_rec.data(), cnt * F4 * 16, hipMemcpyHostToDevice));
         HIP_TRY(ctx, hipMemcpy((char*)ctx->pos4.p + base * 16, stage_pos.data(), cnt * 16, hipMemcpyHostToDevice));
     }
+    if (n_over)
+        return fail(ctx, MSPLAT_ERR_UNSUPPORTED, "msplat_upload_cloud: %llu f_rest values are beyond the fp16 range (|c| >= 65520) "
+                    "of MSPLAT_STORAGE_SH_FP16", (unsigned long long)n_over);
     if ((rc = spatial_reorder(ctx))) return rc;
     ctx->has_cloud = true;
     return MSPLAT_OK;
@@ -321,24 +337,32 @@ int msplat_upload_ply_vertices(msplat_ctx* ctx, const void* vertices, uint64_t n
     if (n) {
         Buf raw;
         if ((rc = buf_alloc(ctx, raw, (size_t)n * vs + 16))) return rc;
+        uint32_t* d_over = reinterpret_cast<uint32_t*>((char*)raw.p + (size_t)n * vs);      // (vs is a multiple of 4)
+        uint32_t n_over = 0;
+        const bool sh16 = ctx->cloud_storage == kStorageShFp16;
         hipError_t e = hipMemcpyAsync(raw.p, vertices, (size_t)n * vs, hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(d_over, 0, 4, ctx->stream);
         if (e == hipSuccess) {
             const int grid = (int)div_up(n, 64);
             const size_t lds = (size_t)64 * vs + 16;
             PlyLayout kl;
             static_assert(sizeof(PlyLayout) == sizeof(msplat_ply_layout), "layout mirror out of sync");
             std::memcpy(&kl, layout, sizeof(kl));
-            if (full)
-                hipLaunchKernelGGL(ingest_kernel<true>, dim3(grid), dim3(64), lds, ctx->stream, (const char*)raw.p, n,
-                                   kl, (float4*)ctx->pos4.p, (float4*)ctx->recs.p);
-            else
-                hipLaunchKernelGGL(ingest_kernel<false>, dim3(grid), dim3(64), lds, ctx->stream, (const char*)raw.p, n,
-                                   kl, (float4*)ctx->pos4.p, (float4*)ctx->recs.p);
+#define MSPLAT_INGEST(SH, ST)                                                                                              \
+    hipLaunchKernelGGL((ingest_kernel<SH, ST>), dim3(grid), dim3(64), lds, ctx->stream, (const char*)raw.p, n, kl,        \
+                       (float4*)ctx->pos4.p, (float4*)ctx->recs.p, d_over)
+            if (sh16) { if (full) MSPLAT_INGEST(true, kStorageShFp16); else MSPLAT_INGEST(false, kStorageShFp16); }
+            else { if (full) MSPLAT_INGEST(true, kStorageFp32); else MSPLAT_INGEST(false, kStorageFp32); }
+#undef MSPLAT_INGEST
             e = hipGetLastError();
         }
+        if (e == hipSuccess && sh16) e = hipMemcpyAsync(&n_over, d_over, 4, hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
         buf_free(ctx, raw);
         if (e != hipSuccess) return fail(ctx, MSPLAT_ERR_HIP, "GPU ingest failed: %s", hipGetErrorString(e));
+        if (n_over)
+            return fail(ctx, MSPLAT_ERR_UNSUPPORTED, "msplat_upload_ply_vertices: %u f_rest values are beyond the fp16 range "
+                        "(|c| >= 65520) of MSPLAT_STORAGE_SH_FP16", n_over);
     }
     if ((rc = spatial_reorder(ctx))) return rc;
     ctx->has_cloud = true;
@@ -481,7 +505,8 @@ int msplat_download_cloud(msplat_ctx* ctx, void* aos_out, uint64_t cap_bytes)
     if (!ctx) return fail(nullptr, MSPLAT_ERR_INVALID_ARG, "ctx is NULL");
     if (!ctx->has_cloud) return fail(ctx, MSPLAT_ERR_NO_CLOUD, "no cloud uploaded");
     if (ctx->point_mode) return fail(ctx, MSPLAT_ERR_UNSUPPORTED, "msplat_download_cloud: the context holds a point cloud");
-    const int F4 = ctx->full_sh ? 16 : 8;
+    const int F4 = ctx->store->F4;
+    const bool sh16 = ctx->cloud_storage == kStorageShFp16;      // widened back to fp32
     const size_t rec_floats = ctx->full_sh ? 61 : 25;
     if (cap_bytes < ctx->N * rec_floats * 4) return fail(ctx, MSPLAT_ERR_INVALID_ARG, "output buffer too small");
     if (ctx->N == 0) return MSPLAT_OK;
@@ -500,9 +525,36 @@ int msplat_download_cloud(msplat_ctx* ctx, void* aos_out, uint64_t cap_bytes)
     for (uint64_t base = 0; base < ctx->N; base += chunk) {
         const size_t cnt = (size_t)std::min<uint64_t>(chunk, ctx->N - base);
         HIP_TRY(ctx, hipMemcpy(stage.data(), (const char*)ctx->recs.p + base * F4 * 16, cnt * F4 * 16, hipMemcpyDeviceToHost));
-        for (size_t j = 0; j < cnt; ++j)
-            std::memcpy(dst + (ro ? (size_t)ctx->store->order_host[base + j] : base + j) * rec_floats, stage.data() + j * F4 * 4, rec_floats * 4);
+        for (size_t j = 0; j < cnt; ++j) {
+            const float* r = stage.data() + j * F4 * 4;
+            float full[64];
+            if (sh16) {
+                const uint32_t* w = reinterpret_cast<const uint32_t*>(r);
+                if (ctx->full_sh) sh16_unpack<true>(w, full); else sh16_unpack<false>(w, full);
+                r = full;
+            }
+            std::memcpy(dst + (ro ? (size_t)ctx->store->order_host[base + j] : base + j) * rec_floats, r, rec_floats * 4);
+        }
     }
     return MSPLAT_OK;
 }
 
+
+// Storage of the higher-order SH (f_rest) for the context's NEXT splat upload (MSPLAT_STORAGE_*; see msplat_common.hip.h for the
+// SH_FP16 record).  A cloud already on the device keeps its storage.
+int msplat_set_cloud_storage(msplat_ctx* ctx, int32_t storage)
+{
+    drain_async(ctx);
+    if (!ctx) return fail(nullptr, MSPLAT_ERR_INVALID_ARG, "ctx is NULL");
+    if (storage != MSPLAT_STORAGE_FP32 && storage != MSPLAT_STORAGE_SH_FP16)
+        return fail(ctx, MSPLAT_ERR_INVALID_ARG, "msplat_set_cloud_storage: storage must be MSPLAT_STORAGE_FP32 or _SH_FP16 (got %d)",
+                    storage);
+    ctx->storage_cfg = storage;
+    return MSPLAT_OK;
+}
+
+int msplat_get_cloud_storage(const msplat_ctx* ctx)
+{
+    if (!ctx || !ctx->has_cloud) return -1;
+    return ctx->point_mode ? MSPLAT_STORAGE_FP32 : ctx->cloud_storage;
+}

@@ -111,6 +111,10 @@ public:
     void SetTwoPass(int mode) { cfg.two_pass = mode; }
     bool TwoPassInfo(uint64_t out[8]) const { return ctx != nullptr && msplat_get_two_pass_info(ctx, out) == MSPLAT_OK; }
 
+    // msplat_set_cloud_storage (before Init; also on the ConfigureDevices path): MSPLAT_STORAGE_FP32 (default) or
+    // MSPLAT_STORAGE_SH_FP16 -- f_rest stored as IEEE fp16, pixels equal to an FP32 render of the fp16-rounded cloud (msplat.h)
+    void SetCloudStorage(int storage) { cloudStorage = storage; }
+
     // splatrenderer.cpp:50-151.  false after logging on failure.  The cloud is copied to the device and
     // not retained; useRgcSortOverride is accepted and ignored (one HIP sort replaces both GL sorters).
     bool Init(std::shared_ptr<GaussianCloud> gaussianCloud, bool isFramebufferSRGBEnabledIn, bool useRgcSortOverrideIn)
@@ -142,6 +146,10 @@ public:
         }
         ctx = ctxs[0];
         cur = framesInFlight - 1;            // the first Sort lands on context 0
+        if (msplat_set_cloud_storage(ctx, cloudStorage) != MSPLAT_OK) {      // (attached contexts render ctxs[0]'s storage)
+            std::fprintf(stderr, "[msplat][E] %s\n", msplat_last_error(ctx));
+            return false;
+        }
         msplat_attr_offsets off{};
         off.pos_with_alpha = (uint32_t)gaussianCloud->GetPosWithAlphaAttrib().offset;
         off.r_sh0 = (uint32_t)gaussianCloud->GetR_SH0Attrib().offset;
@@ -310,6 +318,10 @@ protected:
         msplat_group_set_band_cull(group, groupBandCull ? 1 : 0);
         if (groupExchange != MSPLAT_EXCHANGE_PEER_STORE && msplat_group_set_exchange(group, groupExchange) != MSPLAT_OK)
             std::fprintf(stderr, "[msplat][W] SetGroupExchange: %s\n", msplat_group_last_error(group));
+        if (msplat_group_set_cloud_storage(group, cloudStorage) != MSPLAT_OK) {
+            std::fprintf(stderr, "[msplat][E] %s\n", msplat_group_last_error(group));
+            return false;
+        }
         msplat_attr_offsets off{};
         off.pos_with_alpha = (uint32_t)cloud.GetPosWithAlphaAttrib().offset;
         off.r_sh0 = (uint32_t)cloud.GetR_SH0Attrib().offset;
@@ -356,6 +368,7 @@ protected:
     msplat_ctx* ctx = nullptr;           // == ctxs[cur]
     int cur = 0;
     int framesInFlight = 1;
+    int cloudStorage = MSPLAT_STORAGE_FP32;
     msplat_config cfg{sizeof(msplat_config), 0, MSPLAT_FB_RGBA32F, 0, -1.0f, 0, nullptr, 0, 0, 0, 0};
     void* target = nullptr;
     uint64_t targetPitch = 0;

@@ -42,15 +42,24 @@ class _FrameArgs:
         return self.p_cam, self.p_proj, self.p_vp, self.p_nf
 
 
+def _storage_kind(name):
+    """cloud_storage argument -> MSPLAT_STORAGE_*"""
+    if name not in _capi.CLOUD_STORAGES:
+        raise ValueError("cloud_storage must be one of %s (got %r)" % (sorted(_capi.CLOUD_STORAGES), name))
+    return _capi.CLOUD_STORAGES[name]
+
+
 class SplatRenderer:
     def __init__(self, device=0, fb_format="fp32", t_epsilon=-1.0, pair_capacity=0, stream=None,
                  enable_timing=False, frames_in_flight=1, rank_mode=_capi.RANK_AUTO, frame_mode=None,
                  spatial_order=_capi.SPATIAL_AUTO, async_submit=None, two_pass=_capi.TWO_PASS_AUTO, compositor_waves=None,
-                 cu_partition=None):
+                 cu_partition=None, cloud_storage="fp32"):
         """frames_in_flight > 1: every Sort moves on to the next of that many contexts (own stream and
         per-frame buffers, ONE shared cloud -- msplat_attach_cloud), so successive frames overlap on the
         GPU; Render and the getters use the context of the latest Sort.  `stream` is only used with depth 1;
-        consume a frame after wait_on_stream() / synchronize(), one framebuffer per frame in flight."""
+        consume a frame after wait_on_stream() / synchronize(), one framebuffer per frame in flight.
+        cloud_storage: "fp32" (default) or "sh_fp16" -- f_rest stored as IEEE fp16 (msplat_set_cloud_storage)."""
+        self._storage = _storage_kind(cloud_storage)
         self.numBlocksPerWorkgroup = 1024      # accepted and ignored (splatrenderer.h:39)
         self._lib = _capi.lib()
         self._ctx = None
@@ -149,6 +158,11 @@ class SplatRenderer:
             self._ctxs.append(h)
         self._ctx = self._ctxs[0]
         self._cur = self._depth - 1          # the first Sort lands on context 0
+        for h in self._ctxs:                 # (the attached contexts render context 0's storage anyway)
+            if self._lib.msplat_set_cloud_storage(h, self._storage) != _capi.OK:
+                self._err = self._lib.msplat_last_error(h).decode()
+                self.close()
+                return False
         return True
 
     def _attach_all(self):
@@ -175,6 +189,11 @@ class SplatRenderer:
         out = np.zeros((max(self._n, 1), 61 if full_sh else 25), np.float32)
         _capi.check(self._ctx, self._lib.msplat_download_cloud(self._ctx, out.ctypes.data, out.nbytes))
         return out[:self._n]
+
+    def cloud_storage(self):
+        """"fp32" / "sh_fp16": how the uploaded cloud is stored (msplat_get_cloud_storage); None without a cloud"""
+        k = self._lib.msplat_get_cloud_storage(self._ctx) if self._ctx else -1
+        return {v: n for n, v in _capi.CLOUD_STORAGES.items()}.get(k)
 
     def last_error(self):
         if self._ctx:
@@ -443,7 +462,8 @@ class SplatRendererGroup:
     with a device framebuffer (memory of devices[0]) the other devices' compositors write into it directly over xGMI."""
 
     def __init__(self, devices, fb_format="fp32", t_epsilon=-1.0, layout="contiguous", block_rows=1, band_cull=False,
-                 enable_timing=False):
+                 enable_timing=False, cloud_storage="fp32"):
+        self._storage = _storage_kind(cloud_storage)
         self._lib = _capi.lib()
         self._g = None
         self._args = _FrameArgs()
@@ -491,6 +511,7 @@ class SplatRendererGroup:
         self._g = g
         self._check(self._lib.msplat_group_set_layout(g, _capi.BAND_KINDS[self._layout], self._block_rows))
         self._check(self._lib.msplat_group_set_band_cull(g, 1 if self._band_cull else 0))
+        self._check(self._lib.msplat_group_set_cloud_storage(g, self._storage))
         if isinstance(gaussianCloud, GaussianCloud):
             rc = self._lib.msplat_group_upload_gaussian_cloud(g, gaussianCloud.handle)
         else:
