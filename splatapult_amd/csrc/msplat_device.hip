@@ -22,6 +22,7 @@
 #include <mutex>
 #include <thread>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/msplat.h"
@@ -36,6 +37,7 @@ thread_local std::string g_last_error;
 struct Buf {
     void* p = nullptr;
     size_t bytes = 0;
+    bool frame_table = false;   // zeroed from inside every frame: clear_frame_tables restores it after a failed launch
 };
 
 // The uploaded cloud (read-only after upload).  Held by shared_ptr so that several contexts -- one per
@@ -240,6 +242,7 @@ struct msplat_ctx {
     bool comp_waves_auto = true;   // nobody chose a pool size: up to 20 k work items every item gets its own wave (r2: a wave
                                    // that pulls a second item pays an atomic + two dependent loads; 17.6 k items: -8 %)
     uint64_t device_bytes = 0;
+    std::vector<Buf*> bufs;     // every member Buf that buf_alloc has allocated: what msplat_destroy frees, clear_frame_tables walks
 };
 
 namespace {
@@ -284,6 +287,11 @@ int buf_alloc(msplat_ctx* c, Buf& b, size_t bytes)
     HIP_TRY(c, hipMalloc(&b.p, bytes));
     b.bytes = bytes;
     c->device_bytes += bytes;
+    // a member of the context (not a caller's temporary, which the caller frees): noted once for msplat_destroy
+    const char* at = reinterpret_cast<const char*>(&b);
+    if (at >= reinterpret_cast<const char*>(c) && at < reinterpret_cast<const char*>(c + 1) &&
+        std::find(c->bufs.begin(), c->bufs.end(), &b) == c->bufs.end())
+        c->bufs.push_back(&b);
     return MSPLAT_OK;
 }
 
@@ -307,6 +315,46 @@ int grid_for(uint32_t nchunks)
     // grid-stride kernels: enough workgroups to fill 256 CUs x 8, never more than the chunk count
     const uint32_t cap = 256u * 8u;
     return (int)std::max(1u, std::min(nchunks, cap));
+}
+
+// ---- run-time value -> template argument.  A launch that exists for several values of a template parameter is written ONCE, in a
+// generic lambda that receives each value as a tag:  with_flag(ctx->full_sh, [&](auto SH) { ... kernel<SH.value> ... });
+// A dispatcher instantiates the lambda for every value it lists, nested dispatchers for the cross product of their lists: a selection
+// that is not a cross product (the splat compositor's six forms, the wide sort's upsweep) names its combinations at the call site.
+template <bool B> using flag_t = std::bool_constant<B>;
+template <int V> using int_t = std::integral_constant<int, V>;
+
+template <class F> inline void with_flag(bool v, F&& f)
+{
+    if (v) f(flag_t<true>{}); else f(flag_t<false>{});
+}
+
+// v out of a fixed list; a value that is not listed takes the last one
+template <int V0, int... Vs, class F> inline void with_int(int v, F&& f)
+{
+    if constexpr (sizeof...(Vs) == 0) f(int_t<V0>{});
+    else if (v == V0) f(int_t<V0>{});
+    else with_int<Vs...>(v, f);
+}
+
+// keys per thread of the 8-bit radix passes (msplat_common.hip.h, kSortItems)
+template <class F> inline void with_sort_items(bool large, F&& f)
+{
+    with_int<kSortItemsLarge, kSortItems>(large ? kSortItemsLarge : kSortItems, f);
+}
+
+// The (keys per thread, threads) forms of the wide sort's kernels: the ONE list behind sort_impl's dispatch (with_ws_shape) and
+// msplat_create's dynamic-LDS requests.  ws_items is 8 or 16 and ws_threads kWsThreads or kWsThreadsSmall (prepare_cloud_buffers).
+template <class F> inline void for_each_ws_shape(F&& f)
+{
+    f(int_t<8>{}, int_t<kWsThreads>{});
+    f(int_t<16>{}, int_t<kWsThreads>{});
+    f(int_t<8>{}, int_t<kWsThreadsSmall>{});
+    f(int_t<16>{}, int_t<kWsThreadsSmall>{});
+}
+template <class F> inline void with_ws_shape(uint32_t items, uint32_t threads, F&& f)
+{
+    for_each_ws_shape([&](auto I, auto T) { if (items == (uint32_t)I.value && threads == (uint32_t)T.value) f(I, T); });
 }
 
 // host matrix helpers (implemented in msplat_host.cpp)
@@ -374,7 +422,7 @@ int msplat_create(msplat_ctx** out, const msplat_config* cfg)
         // cu_partition (r6): the stream runs on the even or the odd CU positions of every XCD.  Mask bit 8 c + x is CU c of XCD x, and a
         // set bit enables CU c in EVERY XCD (tools/ubench_cumask.hip): a partition by XCD does not exist.  Two of four frames in
         // flight per half: each stream's launches compete with one other stream's instead of three (sort and binning stages -27 %,
-        // projection and compositor slower, the frame 3-5 % faster: tools/gpu_r6_q.sh).  Without the extension: every CU, as before.
+        // projection and compositor slower, the frame 3-5 % faster: EXPERIMENTS.md, "Two frames per half of the CUs").  Without the extension: every CU, as before.
         e = hipErrorNotSupported;
         if (c.cu_partition == MSPLAT_CU_EVEN || c.cu_partition == MSPLAT_CU_ODD) {
             hipDeviceProp_t prop;
@@ -405,6 +453,7 @@ int msplat_create(msplat_ctx** out, const msplat_config* cfg)
     if (rc == MSPLAT_OK) rc = buf_alloc(ctx, ctx->counters, 16 * sizeof(uint32_t));
     if (rc == MSPLAT_OK) rc = buf_alloc(ctx, ctx->totals1, 256 * sizeof(uint32_t));
     if (rc == MSPLAT_OK) rc = buf_alloc(ctx, ctx->queue, kQueueShards * kQueueStride * sizeof(uint32_t));
+    ctx->queue.frame_table = ctx->bincnt.frame_table = true;
     if (rc == MSPLAT_OK) rc = buf_alloc(ctx, ctx->tile_start, (65536 + 1024 + 16) * sizeof(uint32_t));
     if (rc == MSPLAT_OK) rc = buf_alloc(ctx, ctx->bincnt, (65536 + 1024 + 16) * sizeof(uint32_t));
     if (rc == MSPLAT_OK && hipMemsetAsync(ctx->bincnt.p, 0, ctx->bincnt.bytes, ctx->stream) != hipSuccess) rc = MSPLAT_ERR_HIP;
@@ -450,14 +499,10 @@ int msplat_create(msplat_ctx** out, const msplat_config* cfg)
             if (lds_state[dslot] == 0) lds_state[dslot] = [] {
                 bool ok = true;
                 auto want = [&](const void* f, size_t bytes) { ok = ok && hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess; };
-                want(reinterpret_cast<const void*>(&ws_downsweep<true, 8, kWsThreads>), ws_downsweep_lds(8, kWsThreads));
-                want(reinterpret_cast<const void*>(&ws_downsweep<false, 8, kWsThreads>), ws_downsweep_lds(8, kWsThreads));
-                want(reinterpret_cast<const void*>(&ws_downsweep<true, 16, kWsThreads>), ws_downsweep_lds(16, kWsThreads));
-                want(reinterpret_cast<const void*>(&ws_downsweep<false, 16, kWsThreads>), ws_downsweep_lds(16, kWsThreads));
-                want(reinterpret_cast<const void*>(&ws_downsweep<true, 8, kWsThreadsSmall>), ws_downsweep_lds(8, kWsThreadsSmall));
-                want(reinterpret_cast<const void*>(&ws_downsweep<false, 8, kWsThreadsSmall>), ws_downsweep_lds(8, kWsThreadsSmall));
-                want(reinterpret_cast<const void*>(&ws_downsweep<true, 16, kWsThreadsSmall>), ws_downsweep_lds(16, kWsThreadsSmall));
-                want(reinterpret_cast<const void*>(&ws_downsweep<false, 16, kWsThreadsSmall>), ws_downsweep_lds(16, kWsThreadsSmall));
+                for_each_ws_shape([&](auto I, auto T) {
+                    want(reinterpret_cast<const void*>(&ws_downsweep<true, I.value, T.value>), ws_downsweep_lds(I.value, T.value));
+                    want(reinterpret_cast<const void*>(&ws_downsweep<false, I.value, T.value>), ws_downsweep_lds(I.value, T.value));
+                });
                 return ok ? 1 : -1;
             }();
             if (lds_state[dslot] < 0) { (void)hipGetLastError(); ctx->wide_sort = false; }
@@ -506,13 +551,7 @@ void msplat_destroy(msplat_ctx* ctx)
     ctx->store.reset();
     if (ctx->join_ev) (void)hipEventDestroy(ctx->join_ev);
     if (ctx->h_flags) (void)hipHostFree(ctx->h_flags);
-    Buf* all[] = {&ctx->keyA, &ctx->keyB, &ctx->valA, &ctx->valB, &ctx->hist, &ctx->gsumS[0], &ctx->gsumS[1], &ctx->gsumB1, &ctx->gsumB2,
-                  &ctx->totals, &ctx->counters, &ctx->rec2d, &ctx->rect, &ctx->totals1, &ctx->tile_start, &ctx->tile_order,
-                  &ctx->hist1, &ctx->pairsA, &ctx->pairsB, &ctx->hist2, &ctx->fb, &ctx->probe, &ctx->zq, &ctx->sprite, &ctx->queue, &ctx->occ, &ctx->occ_mask, &ctx->occ_fin,
-                  &ctx->occ_state, &ctx->occ_live, &ctx->occ_boxdead, &ctx->occ_unf,
-                  &ctx->wsHist, &ctx->wsGsum[0], &ctx->wsGsum[1], &ctx->wsGsum[2], &ctx->vmask, &ctx->bincnt, &ctx->heavy, &ctx->heavy_flag,
-                  &ctx->live_list, &ctx->live_cnt};
-    for (Buf* b : all) buf_free(ctx, *b);
+    for (Buf* b : ctx->bufs) buf_free(ctx, *b);
     if (ctx->ev_ok)
         for (auto& set : ctx->ev)
             for (auto& ev : set) (void)hipEventDestroy(ev);
@@ -670,14 +709,11 @@ int msplat_stream_wait(msplat_ctx* ctx, void* stream)
     drain_async(ctx);
     if (!ctx) return fail(nullptr, MSPLAT_ERR_INVALID_ARG, "ctx is NULL");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if ((hipStream_t)stream == ctx->stream) {
-        std::string msg;
-        if (take_async_warning(ctx, msg)) return fail(ctx, MSPLAT_ERR_PAIR_OVERFLOW_EARLIER, "%s", msg.c_str());
-        return MSPLAT_OK;
+    if ((hipStream_t)stream != ctx->stream) {
+        if (!ctx->join_ev) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->join_ev, hipEventDisableTiming));
+        HIP_TRY(ctx, hipEventRecord(ctx->join_ev, ctx->stream));
+        HIP_TRY(ctx, hipStreamWaitEvent((hipStream_t)stream, ctx->join_ev, 0));
     }
-    if (!ctx->join_ev) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->join_ev, hipEventDisableTiming));
-    HIP_TRY(ctx, hipEventRecord(ctx->join_ev, ctx->stream));
-    HIP_TRY(ctx, hipStreamWaitEvent((hipStream_t)stream, ctx->join_ev, 0));
     std::string msg;
     if (take_async_warning(ctx, msg)) return fail(ctx, MSPLAT_ERR_PAIR_OVERFLOW_EARLIER, "%s", msg.c_str());
     return MSPLAT_OK;
@@ -692,6 +728,20 @@ int msplat_wait_event(msplat_ctx* ctx, void* event)
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, (hipEvent_t)event, 0));
     return MSPLAT_OK;
+}
+
+// exclusive scan of a chunk-major histogram table along the chunks.  The element count is only known on the device,
+// so the variant is picked from the cloud size: up to 2 M splats (a few thousand chunk rows at most) the 16-workgroup
+// version, beyond that one workgroup per digit.
+static void launch_scan(hipStream_t s, bool small, uint32_t* hist, uint32_t hist_stride, const uint32_t* d_n,
+                        uint32_t n_static, uint32_t n_cap, uint32_t chunk, uint32_t* totals)
+{
+    if (small)
+        hipLaunchKernelGGL(radix_scan_small, dim3(kScanSmallBlocks), dim3(kThreads), 0, s, hist, d_n, n_static, n_cap, chunk,
+                           totals);
+    else
+        hipLaunchKernelGGL(radix_scan, dim3(256), dim3(kThreads), 0, s, hist, hist_stride, d_n, n_static, n_cap, chunk,
+                           totals);
 }
 
 #include "msplat_upload.hip.inc"
@@ -751,20 +801,6 @@ static int make_frame_params(msplat_ctx* ctx, const float cameraMat[16], const f
     return MSPLAT_OK;
 }
 
-// exclusive scan of a chunk-major histogram table along the chunks.  The element count is only known on the device,
-// so the variant is picked from the cloud size: up to 2 M splats (a few thousand chunk rows at most) the 16-workgroup
-// version, beyond that one workgroup per digit.
-static void launch_scan(hipStream_t s, bool small, uint32_t* hist, uint32_t hist_stride, const uint32_t* d_n,
-                        uint32_t n_static, uint32_t n_cap, uint32_t chunk, uint32_t* totals)
-{
-    if (small)
-        hipLaunchKernelGGL(radix_scan_small, dim3(kScanSmallBlocks), dim3(kThreads), 0, s, hist, d_n, n_static, n_cap, chunk,
-                           totals);
-    else
-        hipLaunchKernelGGL(radix_scan, dim3(256), dim3(kThreads), 0, s, hist, hist_stride, d_n, n_static, n_cap, chunk,
-                           totals);
-}
-
 // The scan-free passes keep their tables clean for the NEXT frame from inside the frame (every group table is zeroed by a
 // later kernel of the same frame, the bin counts by their consumer, the minimum-key words by the other parity's pass 0), so
 // a frame whose launches did not all go out leaves them in an unknown state: after any launch error the context is marked
@@ -772,13 +808,9 @@ static void launch_scan(hipStream_t s, bool small, uint32_t* hist, uint32_t hist
 static int clear_frame_tables(msplat_ctx* ctx)
 {
     hipStream_t s = ctx->stream;
-    Buf* zero[] = {&ctx->gsumS[0], &ctx->gsumS[1], &ctx->gsumB1, &ctx->gsumB2, &ctx->wsGsum[0], &ctx->wsGsum[1], &ctx->wsGsum[2],
-                   &ctx->bincnt};
-    for (Buf* b : zero)
-        if (b->p) HIP_TRY(ctx, hipMemsetAsync(b->p, 0, b->bytes, s));
+    for (Buf* b : ctx->bufs)        // (the group tables, the bin counts, the queue heads, the heavy-chunk lists)
+        if (b->frame_table && b->p) HIP_TRY(ctx, hipMemsetAsync(b->p, 0, b->bytes, s));
     HIP_TRY(ctx, hipMemsetAsync((uint32_t*)ctx->counters.p + 10, 0xFF, 2 * sizeof(uint32_t), s));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->queue.p, 0, ctx->queue.bytes, s));
-    if (ctx->heavy.p) HIP_TRY(ctx, hipMemsetAsync(ctx->heavy.p, 0, ctx->heavy.bytes, s));
     ctx->tables_dirty = false;
     return MSPLAT_OK;
 }
@@ -831,6 +863,62 @@ static int note_async_result(msplat_ctx* ctx, int rc)
     return rc;
 }
 
+// What every frame call checks first, in this order; `who` names the entry point in the messages, `missing` says what a Render
+// lacks of its targets (NULL: nothing; a Sort has none and need not follow a Sort)
+static int begin_frame(msplat_ctx* ctx, const char* who, bool render, const char* missing, const float cameraMat[16],
+                       const float projMat[16], const float viewport[4], const float nearFar[2], FrameParams& fp)
+{
+    if (!ctx) return fail(nullptr, MSPLAT_ERR_INVALID_ARG, "ctx is NULL");
+    if (!ctx->has_cloud) return fail(ctx, MSPLAT_ERR_NO_CLOUD, "%s: no cloud uploaded", who);
+    if (render && !ctx->has_sort) return fail(ctx, MSPLAT_ERR_NO_SORT, "%s: msplat_sort has not been called", who);
+    if (missing) return fail(ctx, MSPLAT_ERR_INVALID_ARG, "%s: %s", who, missing);
+    return make_frame_params(ctx, cameraMat, projMat, viewport, nearFar, fp);
+}
+
+extern "C++" {      // (templates)
+
+// The async wrapper of msplat_sort / msplat_render / msplat_render_stereo: impl(cam0, proj0, cam1, proj1, viewport, nearFar) issues the
+// frame (one view: cam1 / proj1 repeat cam0 / proj0).  On a context with a worker a call that hands nothing back to its caller
+// (`deferrable`) is queued with copies of its arrays; any other call first waits until the worker has issued what is queued.
+// (TWO_VIEWS is a template argument so that a one-view call copies and queues one set of arrays, as it always did)
+template <bool TWO_VIEWS, class Impl>
+static int submit_frame(msplat_ctx* ctx, bool deferrable, const float* cam0, const float* proj0, const float* cam1, const float* proj1,
+                        const float* viewport, const float* nearFar, Impl impl)
+{
+    if (ctx && ctx->worker && g_on_worker_of != ctx) {
+        if (deferrable) {
+            FrameArgs a, b;
+            if (!a.load(cam0, proj0, viewport, nearFar) || (TWO_VIEWS && !b.load(cam1, proj1, viewport, nearFar))) {
+                ctx->worker->drain();           // (ctx->err is the worker's while it runs)
+                return fail(ctx, MSPLAT_ERR_INVALID_ARG, "NULL matrix/viewport argument");
+            }
+            if constexpr (TWO_VIEWS)
+                ctx->worker->post([ctx, a, b, impl] { return note_async_result(ctx, impl(a.cam, a.proj, b.cam, b.proj, a.vp, a.nf)); });
+            else
+                ctx->worker->post([ctx, a, impl] { return note_async_result(ctx, impl(a.cam, a.proj, a.cam, a.proj, a.vp, a.nf)); });
+            return MSPLAT_OK;
+        }
+        ctx->worker->drain();           // a host image is filled before the call returns: nothing to defer
+    }
+    return impl(cam0, proj0, cam1, proj1, viewport, nearFar);
+}
+
+// A frame's work between the poll for an EARLIER device-output frame's pair overflow (the buffer grows; this frame is still done)
+// and the report of that overflow, which follows work that succeeded
+template <class Work>
+static int with_pending_overflow(msplat_ctx* ctx, Work&& work)
+{
+    std::string pending_msg;
+    const int pending = poll_async_overflow(ctx, pending_msg);
+    if (pending == MSPLAT_ERR_HIP) return pending;
+    const int rc = work();
+    if (rc) return rc;
+    if (pending) return fail(ctx, MSPLAT_ERR_PAIR_OVERFLOW_EARLIER, "%s", pending_msg.c_str());
+    return MSPLAT_OK;
+}
+
+}  // extern "C++"
+
 static int sort_impl(msplat_ctx* ctx, const float cameraMat[16], const float projMat[16], const float viewport[4], const float nearFar[2]);
 static int render_impl(msplat_ctx* ctx, const float cameraMat[16], const float projMat[16], const float viewport[4],
                        const float nearFar[2], void* rgba, uint64_t pitch_bytes, int out_is_device);
@@ -838,29 +926,25 @@ static int render_impl(msplat_ctx* ctx, const float cameraMat[16], const float p
 int msplat_sort(msplat_ctx* ctx, const float cameraMat[16], const float projMat[16],
                 const float viewport[4], const float nearFar[2])
 {
-    if (ctx && ctx->worker && g_on_worker_of != ctx) {
-        FrameArgs a;
-        if (!a.load(cameraMat, projMat, viewport, nearFar)) {
-            ctx->worker->drain();           // (ctx->err is the worker's while it runs)
-            return fail(ctx, MSPLAT_ERR_INVALID_ARG, "NULL matrix/viewport argument");
-        }
-        ctx->worker->post([ctx, a] { return note_async_result(ctx, sort_impl(ctx, a.cam, a.proj, a.vp, a.nf)); });
-        return MSPLAT_OK;
-    }
-    return sort_impl(ctx, cameraMat, projMat, viewport, nearFar);
+    return submit_frame<false>(ctx, true, cameraMat, projMat, cameraMat, projMat, viewport, nearFar,
+                        [ctx](const float* cam, const float* proj, const float*, const float*, const float* vp, const float* nf) {
+                            return sort_impl(ctx, cam, proj, vp, nf);
+                        });
 }
+
+static int issue_sort(msplat_ctx* ctx, const FrameParams& fp);
 
 static int sort_impl(msplat_ctx* ctx, const float cameraMat[16], const float projMat[16],
                      const float viewport[4], const float nearFar[2])
 {
-    if (!ctx) return fail(nullptr, MSPLAT_ERR_INVALID_ARG, "ctx is NULL");
-    if (!ctx->has_cloud) return fail(ctx, MSPLAT_ERR_NO_CLOUD, "msplat_sort: no cloud uploaded");
     FrameParams fp;
-    int rc = make_frame_params(ctx, cameraMat, projMat, viewport, nearFar, fp);
+    int rc = begin_frame(ctx, "msplat_sort", false, nullptr, cameraMat, projMat, viewport, nearFar, fp);
     if (rc) return rc;
-    std::string pending_msg;
-    const int pending = poll_async_overflow(ctx, pending_msg);     // the sort itself is still performed
-    if (pending == MSPLAT_ERR_HIP) return pending;
+    return with_pending_overflow(ctx, [&] { return issue_sort(ctx, fp); });     // the sort itself is still performed
+}
+
+static int issue_sort(msplat_ctx* ctx, const FrameParams& fp)
+{
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     const uint32_t N = (uint32_t)ctx->N;
@@ -877,13 +961,14 @@ static int sort_impl(msplat_ctx* ctx, const float cameraMat[16], const float pro
     const int grid = grid_for(div_up(N, chunk));
 
     if (ctx->tables_dirty) {
-        rc = clear_frame_tables(ctx);
+        int rc = clear_frame_tables(ctx);
         if (rc) return rc;
     }
     const bool timed = ctx->ev_ok && (ctx->sort_calls++ % ctx->timing_stride) == 0;
     const int tset = (int)(ctx->sort_sets % msplat_ctx::kEvSets);
     if (timed) HIP_TRY(ctx, hipEventRecord(ctx->ev[tset][0], s));
-    if (ctx->wide_sort) {
+    const bool wide = ctx->wide_sort;
+    if (wide) {
         // three passes of 10 + (8..11) + (8..11) key bits (msplat_sort.hip.h, ws_*): 6 launches.
         // pass 0: positions -> raw keys + visibility bits in keyB / vmask -> (keyA, valA); pass 1: A -> B; pass 2: B -> A
         uint32_t* mk_cur = counters + 10 + (ctx->sort_parity & 1u);
@@ -905,131 +990,100 @@ static int sort_impl(msplat_ctx* ctx, const float cameraMat[16], const float pro
         uint32_t items = lb.list != nullptr ? 8u : items0;
         int wgrid = grid_for(div_up(N, ctx->ws_threads * items));
         const uint32_t* dV = d_V;
-#define MSPLAT_WS_T(KERNEL, CULLF, LDS, T, ...)                                                                          \
-    do {                                                                                                                \
-        if (items == 16u) hipLaunchKernelGGL((KERNEL<CULLF, 16, T>), dim3(wgrid), dim3(T), LDS(16, T), s, __VA_ARGS__); \
-        else hipLaunchKernelGGL((KERNEL<CULLF, 8, T>), dim3(wgrid), dim3(T), LDS(8, T), s, __VA_ARGS__);                       \
-    } while (0)
-#define MSPLAT_WS(KERNEL, CULLF, LDS, ...)                                                                              \
-    do {                                                                                                                \
-        if (ctx->ws_threads == (uint32_t)kWsThreadsSmall) MSPLAT_WS_T(KERNEL, CULLF, LDS, kWsThreadsSmall, __VA_ARGS__); \
-        else MSPLAT_WS_T(KERNEL, CULLF, LDS, kWsThreads, __VA_ARGS__);                                                  \
-    } while (0)
-#define MSPLAT_NO_LDS(I, T) 0
-        // The upsweeps have no order to keep.  One frame at a time and 4096-key chunks (up to 2 M splats): twice the threads per
-        // chunk, half the keys per thread -- 241 workgroups of 16 waves instead of 8 at 1 M: sort 57.4 -> 55.7 us.  Not at 6 M
-        // (158 -> 166 us) and not for frames in flight (-0.5 %): `tools/archive/gpu_round3_q2.sh`.
-#define MSPLAT_WS_UP(CULLF, ...)                                                                                        \
-    do {                                                                                                                \
-        if (items == 8u && ctx->ws_threads == (uint32_t)kWsThreads)                                                     \
-            hipLaunchKernelGGL((ws_upsweep<CULLF, 4, 2 * kWsThreads>), dim3(wgrid), dim3(2 * kWsThreads), 0, s, __VA_ARGS__); \
-        else MSPLAT_WS(ws_upsweep, CULLF, MSPLAT_NO_LDS, __VA_ARGS__);                                                    \
-    } while (0)
-        if (fp.band_cull)
-            MSPLAT_WS_UP(2, (const uint32_t*)nullptr, pos, kB, vm, (const uint32_t*)nullptr, N, N, 0, mk_cur,
-                      mk_next, whist, gt(0), gsh, gt(-1), gw, fp, lb);
-        else
-            MSPLAT_WS_UP(1, (const uint32_t*)nullptr, pos, kB, vm, (const uint32_t*)nullptr, N, N, 0, mk_cur,
-                      mk_next, whist, gt(0), gsh, gt(-1), gw, fp, lb);
-        MSPLAT_WS(ws_downsweep, true, ws_downsweep_lds, (const uint32_t*)kB, (const uint32_t*)nullptr, (const unsigned long long*)vm,
+        auto upsweep = [&](auto CULL, const auto&... args) {
+            // The upsweeps have no order to keep.  One frame at a time and 4096-key chunks (up to 2 M splats): twice the threads per
+            // chunk, half the keys per thread -- 241 workgroups of 16 waves instead of 8 at 1 M: sort 57.4 -> 55.7 us.  Not at 6 M
+            // (158 -> 166 us) and not for frames in flight (-0.5 %): EXPERIMENTS.md, "The upsweeps keep no order".
+            if (items == 8u && ctx->ws_threads == (uint32_t)kWsThreads)
+                hipLaunchKernelGGL((ws_upsweep<CULL.value, 4, 2 * kWsThreads>), dim3(wgrid), dim3(2 * kWsThreads), 0, s, args...);
+            else
+                with_ws_shape(items, ctx->ws_threads, [&](auto I, auto T) {
+                    hipLaunchKernelGGL((ws_upsweep<CULL.value, I.value, T.value>), dim3(wgrid), dim3(T.value), 0, s, args...);
+                });
+        };
+        auto downsweep = [&](auto CULL, const auto&... args) {
+            with_ws_shape(items, ctx->ws_threads, [&](auto I, auto T) {
+                hipLaunchKernelGGL((ws_downsweep<CULL.value, I.value, T.value>), dim3(wgrid), dim3(T.value),
+                                   ws_downsweep_lds(I.value, T.value), s, args...);
+            });
+        };
+        with_int<2, 1>(fp.band_cull ? 2 : 1, [&](auto CULL) {
+            upsweep(CULL, (const uint32_t*)nullptr, pos, kB, vm, (const uint32_t*)nullptr, N, N, 0, mk_cur,
+                    mk_next, whist, gt(0), gsh, gt(-1), gw, fp, lb);
+        });
+        downsweep(flag_t<true>{}, (const uint32_t*)kB, (const uint32_t*)nullptr, (const unsigned long long*)vm,
                   (const uint32_t*)nullptr, N, N, 0, (const uint32_t*)mk_cur, (const uint32_t*)whist, (const uint32_t*)gt(0), gsh, kA, vA,
                   d_V, lb);
         items = items12;
         wgrid = grid_for(div_up(N, ctx->ws_threads * items));
-        MSPLAT_WS_UP(0, (const uint32_t*)kA, (const float4*)nullptr, (uint32_t*)nullptr,
-                  (unsigned long long*)nullptr, dV, 0u, N, 1, mk_cur, mk_next, whist, gt(1), gsh, gt(0), gw, fp);
-        MSPLAT_WS(ws_downsweep, false, ws_downsweep_lds, (const uint32_t*)kA, (const uint32_t*)vA, (const unsigned long long*)nullptr, dV,
-                  0u, N, 1, (const uint32_t*)mk_cur, (const uint32_t*)whist, (const uint32_t*)gt(1), gsh, kB, vB, (uint32_t*)nullptr);
-        MSPLAT_WS_UP(0, (const uint32_t*)kB, (const float4*)nullptr, (uint32_t*)nullptr,
-                  (unsigned long long*)nullptr, dV, 0u, N, 2, mk_cur, mk_next, whist, gt(2), gsh, gt(1), gw, fp);
-        MSPLAT_WS(ws_downsweep, false, ws_downsweep_lds, (const uint32_t*)kB, (const uint32_t*)vB, (const unsigned long long*)nullptr, dV,
-                  0u, N, 2, (const uint32_t*)mk_cur, (const uint32_t*)whist, (const uint32_t*)gt(2), gsh, kA, vA, (uint32_t*)nullptr);
-#undef MSPLAT_NO_LDS
-#undef MSPLAT_WS
-#undef MSPLAT_WS_T
-#undef MSPLAT_WS_UP
-        if (timed) {
-            HIP_TRY(ctx, hipEventRecord(ctx->ev[tset][1], s));
-            ctx->sort_sets++;
+        for (int pass = 1; pass < 3; ++pass) {
+            uint32_t *kin = pass == 1 ? kA : kB, *vin = pass == 1 ? vA : vB, *kout = pass == 1 ? kB : kA, *vout = pass == 1 ? vB : vA;
+            upsweep(int_t<0>{}, (const uint32_t*)kin, (const float4*)nullptr, (uint32_t*)nullptr,
+                    (unsigned long long*)nullptr, dV, 0u, N, pass, mk_cur, mk_next, whist, gt(pass), gsh, gt(pass - 1), gw, fp);
+            downsweep(flag_t<false>{}, (const uint32_t*)kin, (const uint32_t*)vin, (const unsigned long long*)nullptr, dV,
+                      0u, N, pass, (const uint32_t*)mk_cur, (const uint32_t*)whist, (const uint32_t*)gt(pass), gsh, kout, vout, (uint32_t*)nullptr);
         }
-        const hipError_t le = hipGetLastError();
-        if (le != hipSuccess) {
-            // e.g. the dynamic-LDS request was not honoured on this device: later frames take the four 8-bit passes, which
-            // need no opt-in (this frame is lost; the tables are restored before the next one)
-            ctx->tables_dirty = true;
-            ctx->wide_sort = ctx->wide_sort_cfg = false;
-            return fail(ctx, MSPLAT_ERR_HIP, "msplat_sort: a kernel launch of the three-pass sort failed (%s); the context falls back "
-                        "to the 8-bit passes from the next frame on", hipGetErrorString(le));
+    } else {
+        // scan-free passes (2 launches each) while the chunk table is small, else upsweep + scan + downsweep
+        const bool fused = ctx->scan_free && div_up(N, chunk) <= kFusedMaxChunks;
+        auto gacc = [&](int pass) { return fused ? (uint32_t*)ctx->gsumS[pass & 1].p : nullptr; };
+        auto gzero = [&](int pass) { return (uint32_t*)ctx->gsumS[(pass + 1) & 1].p; };      // always: keeps both tables clean
+        auto upsweep = [&](auto MODE, auto BAND, const auto&... args) {
+            with_sort_items(large, [&](auto IT) {
+                hipLaunchKernelGGL((radix_upsweep<MODE.value, IT.value, BAND.value>), dim3(grid), dim3(kThreads), 0, s, args...);
+            });
+        };
+        auto downsweep = [&](auto MODE, auto BAND, const auto&... args) {
+            with_sort_items(large, [&](auto IT) {
+                with_flag(ctx->atomic_rank, [&](auto AR) {
+                    hipLaunchKernelGGL((radix_downsweep<MODE.value, true, AR.value, IT.value, BAND.value>), dim3(grid), dim3(kThreads), 0, s,
+                                       args...);
+                });
+            });
+        };
+        // pass 0: cull + key fused into the first radix pass (presort_compute.glsl + byte 0 of the sort)
+        const LiveBoxes lb = list_live_boxes(ctx, fp, ctx->h_flags ? __atomic_load_n(ctx->h_flags + 1, __ATOMIC_RELAXED) : 0u);
+        // (r6: frames without the band-restricted cull -- every single-GPU frame -- run instantiations that leave its code out)
+        with_flag(fp.band_cull != 0, [&](auto BAND) {
+            upsweep(int_t<MODE_CULL>{}, BAND, (const uint32_t*)nullptr, pos, (const uint32_t*)nullptr, N, N, 0, hist, ctx->hist_stride, gacc(0),
+                    gzero(0), ctx->gsumS_rows, fp, (const uint32_t*)nullptr, (uint32_t*)nullptr, ctx->gsupS, lb);
+            if (!fused) launch_scan(s, !large, hist, ctx->hist_stride, nullptr, N, N, chunk, totals);
+            downsweep(int_t<MODE_CULL>{}, BAND, (const uint32_t*)nullptr, (const uint32_t*)nullptr, pos, (const uint32_t*)nullptr, N, N, 0,
+                      (const uint32_t*)hist, ctx->hist_stride, (const uint32_t*)totals, kB, vB, d_V, (const uint32_t*)nullptr,
+                      (const uint32_t*)gacc(0), (uint32_t*)nullptr, fp, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr,
+                      (uint32_t*)nullptr, 0, 0, ctx->gsupS, lb);
+        });
+        // passes 1..3 on the V survivors (V stays on the device; splatrenderer.cpp:195-204's readback is gone)
+        for (int pass = 1; pass < 4; ++pass) {
+            uint32_t* kin = (pass & 1) ? kB : kA;
+            uint32_t* vin = (pass & 1) ? vB : vA;
+            uint32_t* kout = (pass & 1) ? kA : kB;
+            uint32_t* vout = (pass & 1) ? vA : vB;
+            upsweep(int_t<MODE_KEYS>{}, flag_t<true>{}, (const uint32_t*)kin, (const float4*)nullptr, (const uint32_t*)d_V, 0u, N, pass * 8, hist,
+                    ctx->hist_stride, gacc(pass), gzero(pass), ctx->gsumS_rows, fp, (const uint32_t*)nullptr, (uint32_t*)nullptr,
+                    ctx->gsupS);
+            if (!fused) launch_scan(s, !large, hist, ctx->hist_stride, d_V, 0u, N, chunk, totals);
+            downsweep(int_t<MODE_KEYS>{}, flag_t<true>{}, (const uint32_t*)kin, (const uint32_t*)vin, (const float4*)nullptr, (const uint32_t*)d_V, 0u, N,
+                      pass * 8, (const uint32_t*)hist, ctx->hist_stride, (const uint32_t*)totals, kout, vout, (uint32_t*)nullptr,
+                      (const uint32_t*)nullptr, (const uint32_t*)gacc(pass), (uint32_t*)nullptr, fp, (uint32_t*)nullptr,
+                      (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, 0, 0, ctx->gsupS);
         }
-        ctx->has_sort = true;
-        if (pending) return fail(ctx, MSPLAT_ERR_PAIR_OVERFLOW_EARLIER, "%s", pending_msg.c_str());
-        return MSPLAT_OK;
     }
-    // scan-free passes (2 launches each) while the chunk table is small, else upsweep + scan + downsweep
-    const bool fused = ctx->scan_free && div_up(N, chunk) <= kFusedMaxChunks;
-    auto gacc = [&](int pass) { return fused ? (uint32_t*)ctx->gsumS[pass & 1].p : nullptr; };
-    auto gzero = [&](int pass) { return (uint32_t*)ctx->gsumS[(pass + 1) & 1].p; };      // always: keeps both tables clean
-#define MSPLAT_UPSWEEP_B(MODE, BAND, ...)                                                                               \
-    do {                                                                                                                \
-        if (large) hipLaunchKernelGGL((radix_upsweep<MODE, kSortItemsLarge, BAND>), dim3(grid), dim3(kThreads), 0, s, __VA_ARGS__); \
-        else hipLaunchKernelGGL((radix_upsweep<MODE, kSortItems, BAND>), dim3(grid), dim3(kThreads), 0, s, __VA_ARGS__);            \
-    } while (0)
-#define MSPLAT_DOWNSWEEP_B(MODE, BAND, ...)                                                                                      \
-    do {                                                                                                                         \
-        if (large) {                                                                                                             \
-            if (ctx->atomic_rank) hipLaunchKernelGGL((radix_downsweep<MODE, true, true, kSortItemsLarge, BAND>), dim3(grid), dim3(kThreads), 0, s, __VA_ARGS__); \
-            else hipLaunchKernelGGL((radix_downsweep<MODE, true, false, kSortItemsLarge, BAND>), dim3(grid), dim3(kThreads), 0, s, __VA_ARGS__);                 \
-        } else {                                                                                                                 \
-            if (ctx->atomic_rank) hipLaunchKernelGGL((radix_downsweep<MODE, true, true, kSortItems, BAND>), dim3(grid), dim3(kThreads), 0, s, __VA_ARGS__);      \
-            else hipLaunchKernelGGL((radix_downsweep<MODE, true, false, kSortItems, BAND>), dim3(grid), dim3(kThreads), 0, s, __VA_ARGS__);                      \
-        }                                                                                                                        \
-    } while (0)
-#define MSPLAT_UPSWEEP(MODE, ...) MSPLAT_UPSWEEP_B(MODE, true, __VA_ARGS__)
-#define MSPLAT_DOWNSWEEP(MODE, ...) MSPLAT_DOWNSWEEP_B(MODE, true, __VA_ARGS__)
-    // pass 0: cull + key fused into the first radix pass (presort_compute.glsl + byte 0 of the sort)
-    const LiveBoxes lb = list_live_boxes(ctx, fp, ctx->h_flags ? __atomic_load_n(ctx->h_flags + 1, __ATOMIC_RELAXED) : 0u);
-    // (r6: frames without the band-restricted cull -- every single-GPU frame -- run instantiations that leave its code out)
-#define MSPLAT_PASS0(BAND)                                                                                                              \
-    do {                                                                                                                                \
-        MSPLAT_UPSWEEP_B(MODE_CULL, BAND, (const uint32_t*)nullptr, pos, (const uint32_t*)nullptr, N, N, 0, hist, ctx->hist_stride, gacc(0), \
-                         gzero(0), ctx->gsumS_rows, fp, (const uint32_t*)nullptr, (uint32_t*)nullptr, ctx->gsupS, lb);                 \
-        if (!fused) launch_scan(s, ctx->N <= (2u << 20), hist, ctx->hist_stride, nullptr, N, N, chunk, totals);                       \
-        MSPLAT_DOWNSWEEP_B(MODE_CULL, BAND, (const uint32_t*)nullptr, (const uint32_t*)nullptr, pos, (const uint32_t*)nullptr, N, N, 0, \
-                           (const uint32_t*)hist, ctx->hist_stride, (const uint32_t*)totals, kB, vB, d_V, (const uint32_t*)nullptr,    \
-                           (const uint32_t*)gacc(0), (uint32_t*)nullptr, fp, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, \
-                           (uint32_t*)nullptr, 0, 0, ctx->gsupS, lb);                                                                  \
-    } while (0)
-    if (fp.band_cull) MSPLAT_PASS0(true); else MSPLAT_PASS0(false);
-#undef MSPLAT_PASS0
-    // passes 1..3 on the V survivors (V stays on the device; splatrenderer.cpp:195-204's readback is gone)
-    for (int pass = 1; pass < 4; ++pass) {
-        uint32_t* kin = (pass & 1) ? kB : kA;
-        uint32_t* vin = (pass & 1) ? vB : vA;
-        uint32_t* kout = (pass & 1) ? kA : kB;
-        uint32_t* vout = (pass & 1) ? vA : vB;
-        MSPLAT_UPSWEEP(MODE_KEYS, (const uint32_t*)kin, (const float4*)nullptr, (const uint32_t*)d_V, 0u, N, pass * 8, hist,
-                       ctx->hist_stride, gacc(pass), gzero(pass), ctx->gsumS_rows, fp, (const uint32_t*)nullptr, (uint32_t*)nullptr,
-                       ctx->gsupS);
-        if (!fused) launch_scan(s, ctx->N <= (2u << 20), hist, ctx->hist_stride, d_V, 0u, N, chunk, totals);
-        MSPLAT_DOWNSWEEP(MODE_KEYS, (const uint32_t*)kin, (const uint32_t*)vin, (const float4*)nullptr, (const uint32_t*)d_V, 0u, N,
-                         pass * 8, (const uint32_t*)hist, ctx->hist_stride, (const uint32_t*)totals, kout, vout, (uint32_t*)nullptr,
-                         (const uint32_t*)nullptr, (const uint32_t*)gacc(pass), (uint32_t*)nullptr, fp, (uint32_t*)nullptr,
-                         (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, 0, 0, ctx->gsupS);
-    }
-#undef MSPLAT_UPSWEEP
-#undef MSPLAT_DOWNSWEEP
-#undef MSPLAT_UPSWEEP_B
-#undef MSPLAT_DOWNSWEEP_B
     if (timed) {
         HIP_TRY(ctx, hipEventRecord(ctx->ev[tset][1], s));
         ctx->sort_sets++;
     }
-    if (hipGetLastError() != hipSuccess) {
+    const hipError_t le = hipGetLastError();
+    if (le != hipSuccess) {
         ctx->tables_dirty = true;
-        return fail(ctx, MSPLAT_ERR_HIP, "msplat_sort: a kernel launch failed");
+        if (!wide) return fail(ctx, MSPLAT_ERR_HIP, "msplat_sort: a kernel launch failed");
+        // e.g. the dynamic-LDS request was not honoured on this device: later frames take the four 8-bit passes, which
+        // need no opt-in (this frame is lost; the tables are restored before the next one)
+        ctx->wide_sort = ctx->wide_sort_cfg = false;
+        return fail(ctx, MSPLAT_ERR_HIP, "msplat_sort: a kernel launch of the three-pass sort failed (%s); the context falls back "
+                    "to the 8-bit passes from the next frame on", hipGetErrorString(le));
     }
     ctx->has_sort = true;
-    if (pending) return fail(ctx, MSPLAT_ERR_PAIR_OVERFLOW_EARLIER, "%s", pending_msg.c_str());
     return MSPLAT_OK;
 }
 
@@ -1101,6 +1155,17 @@ static bool occlusion_plan(msplat_ctx* ctx, const FrameParams& fp, bool stereo, 
         // ahead); more than 30 % unfinished is a strike (the next probe takes a larger share), three strikes a pause that doubles
         // every time; otherwise two passes stay on, steered, until three looks in a row say otherwise.
         enum { OFF = 0, PROBE = 1, WAIT = 2, ON = 3 };
+        // more than 30 % unfinished.  false: the third strike, one pass for a pause that doubles every time
+        auto strike = [&]() {
+            if (++ctx->occ_strikes >= 3u) {
+                ctx->occ_state_auto = OFF;
+                ctx->occ_off = ctx->occ_backoff;
+                ctx->occ_backoff = std::min(ctx->occ_backoff * 2u, 16384u);
+                return false;
+            }
+            set_share(ctx->occ_frac * 1.5f);
+            return true;
+        };
         if (ctx->occ_state_auto == OFF) {
             if (ctx->occ_off != 0u) { --ctx->occ_off; return no(); }
             ctx->occ_state_auto = PROBE;
@@ -1121,13 +1186,7 @@ static bool occlusion_plan(msplat_ctx* ctx, const FrameParams& fp, bool stereo, 
             }
             ctx->occ_wait_frames = 0u;
             if (ufrac > 0.3f) {
-                if (++ctx->occ_strikes >= 3u) {
-                    ctx->occ_state_auto = OFF;
-                    ctx->occ_off = ctx->occ_backoff;
-                    ctx->occ_backoff = std::min(ctx->occ_backoff * 2u, 16384u);
-                    return no();
-                }
-                set_share(ctx->occ_frac * 1.5f);
+                if (!strike()) return no();
                 ctx->occ_state_auto = PROBE;
                 ctx->occ_probe_left = 4u;
             } else {
@@ -1138,13 +1197,7 @@ static bool occlusion_plan(msplat_ctx* ctx, const FrameParams& fp, bool stereo, 
             }
         } else if (ctx->occ_state_auto == ON && fresh && !ctx->occ_pinned) {
             if (ufrac > 0.3f) {
-                if (++ctx->occ_strikes >= 3u) {
-                    ctx->occ_state_auto = OFF;
-                    ctx->occ_off = ctx->occ_backoff;
-                    ctx->occ_backoff = std::min(ctx->occ_backoff * 2u, 16384u);
-                    return no();
-                }
-                set_share(ctx->occ_frac * 1.5f);
+                if (!strike()) return no();
             } else {
                 ctx->occ_strikes = 0u;
                 steer();
@@ -1219,38 +1272,30 @@ static void issue_projection(RenderChain& rc, int mode, float occ_frac)
     }
     const ProjParams pp = proj_params(fp);
     uint32_t* zq = (mode != PROJ_LISTED && ctx->depth_bits) ? (uint32_t*)ctx->zq.p : nullptr;
-#define MSPLAT_PROJECT_ST(SH, MODE, ST, GRID, DV, EX, V1)                                                                     \
-    hipLaunchKernelGGL((project_kernel<SH, MODE, ST>), dim3(GRID), dim3(kProjThreads), 0, s, (const uint32_t*)ctx->valA.p, DV, \
-                       (const float4*)ctx->recs.p, pp, (float4*)ctx->rec2d.p, (uint32_t*)ctx->rect.p, zq, EX, V1)
-#define MSPLAT_PROJECT(SH, MODE, GRID, DV, EX, V1)                                                                          \
-    do {                                                                                                                    \
-        if (ctx->cloud_storage == kStorageShFp16) MSPLAT_PROJECT_ST(SH, MODE, kStorageShFp16, GRID, DV, EX, V1);            \
-        else MSPLAT_PROJECT_ST(SH, MODE, kStorageFp32, GRID, DV, EX, V1);                                                   \
-    } while (0)
+    auto project = [&](auto MODE, int grid, const uint32_t* dV, const ProjExtra& ex, const auto& v1) {
+        with_flag(ctx->full_sh, [&](auto SH) {
+            with_int<kStorageShFp16, kStorageFp32>(ctx->cloud_storage, [&](auto ST) {
+                hipLaunchKernelGGL((project_kernel<SH.value, MODE.value, ST.value>), dim3(grid), dim3(kProjThreads), 0, s,
+                                   (const uint32_t*)ctx->valA.p, dV, (const float4*)ctx->recs.p, pp, (float4*)ctx->rec2d.p,
+                                   (uint32_t*)ctx->rect.p, zq, ex, v1);
+            });
+        });
+    };
     if (mode == PROJ_PASS1) {
         // (project_kernel's first pass computes the cut and leaves it in occ[0])
         const ProjExtra ex{nullptr, occ, nullptr, occ_frac};
-        const int grid = std::min(pgrid, kProjGridTwoPass);
-        if (ctx->full_sh) MSPLAT_PROJECT(true, PROJ_PASS1, grid, (const uint32_t*)d_Vsort, ex, ProjNoView1{0});
-        else MSPLAT_PROJECT(false, PROJ_PASS1, grid, (const uint32_t*)d_Vsort, ex, ProjNoView1{0});
+        project(int_t<PROJ_PASS1>{}, std::min(pgrid, kProjGridTwoPass), (const uint32_t*)d_Vsort, ex, ProjNoView1{0});
     } else if (mode == PROJ_LISTED) {
         // the listed ranks behind the cut (occ[1] of them)
         const ProjExtra ex{ctx->d_flags ? ctx->d_flags + 7 : (uint32_t*)nullptr, nullptr, (const uint32_t*)ctx->occ_live.p, 0.0f};
-        const int grid = std::min(pgrid, kProjGridTwoPass);
-        if (ctx->full_sh) MSPLAT_PROJECT(true, PROJ_LISTED, grid, (const uint32_t*)(occ + 1), ex, ProjNoView1{0});
-        else MSPLAT_PROJECT(false, PROJ_LISTED, grid, (const uint32_t*)(occ + 1), ex, ProjNoView1{0});
+        project(int_t<PROJ_LISTED>{}, std::min(pgrid, kProjGridTwoPass), (const uint32_t*)(occ + 1), ex, ProjNoView1{0});
     } else if (rc.stereo) {
         const ProjExtra ex{rc.d_Vframe, nullptr, nullptr, 0.0f};
-        const ProjView1 v1 = proj_view1(fp);
-        if (ctx->full_sh) MSPLAT_PROJECT(true, PROJ_TWO_VIEWS, pgrid, (const uint32_t*)d_Vsort, ex, v1);
-        else MSPLAT_PROJECT(false, PROJ_TWO_VIEWS, pgrid, (const uint32_t*)d_Vsort, ex, v1);
+        project(int_t<PROJ_TWO_VIEWS>{}, pgrid, (const uint32_t*)d_Vsort, ex, proj_view1(fp));
     } else {
         const ProjExtra ex{nullptr, nullptr, nullptr, 0.0f};
-        if (ctx->full_sh) MSPLAT_PROJECT(true, PROJ_PLAIN, pgrid, (const uint32_t*)d_Vsort, ex, ProjNoView1{0});
-        else MSPLAT_PROJECT(false, PROJ_PLAIN, pgrid, (const uint32_t*)d_Vsort, ex, ProjNoView1{0});
+        project(int_t<PROJ_PLAIN>{}, pgrid, (const uint32_t*)d_Vsort, ex, ProjNoView1{0});
     }
-#undef MSPLAT_PROJECT
-#undef MSPLAT_PROJECT_ST
 }
 
 // bin lists over the current rectangles: column pass (bin1_*), row pass (radix_*<MODE_PAIR>), list offsets + work order.
@@ -1297,35 +1342,23 @@ static void issue_binning(RenderChain& rc, int keep_overflow, int occ_pass)
     // merge in that XCD's L2.  Measured r4 (serial binning, groups of 0 / 2 / 4 / 8 / 16 / 32): 6 M / 4096^2 328 / 320 / 316 / 315 /
     // 315 / 313 us, scene-like 6 M 201 / 194 / 194 / 195, 1 M unchanged (57); the fully XCD-contiguous mapping of r3 was slower.
     const int xcdg = 8;
+    const bool small = ctx->N <= (2u << 20);      // (launch_scan)
     // (bin1_upsweep also clears the row pass's group table: its consumer, the previous frame's row downsweep, is long done)
-#define MSPLAT_BIN1(CH)                                                                                                       \
-    do {                                                                                                                      \
-        hipLaunchKernelGGL(bin1_upsweep<CH>, dim3(g1), dim3(kThreads), 0, s, (const uint32_t*)ctx->rect.p, d_V,               \
-                           (uint32_t*)ctx->hist1.p, ctx->hist1_stride, d_overflow, fused1 ? gB1 : nullptr, gB2,               \
-                           ctx->gsumB2_rows, hv_cur, hv_next, (uint8_t*)ctx->heavy_flag.p, heavy_slots, ctx->gsupB1,          \
-                           keep_overflow, d_first);                                                                           \
-        if (!fused1)                                                                                                          \
-            launch_scan(s, ctx->N <= (2u << 20), (uint32_t*)ctx->hist1.p, ctx->hist1_stride, d_V, 0u, N, bchunk, totals1);     \
-        if (ctx->atomic_rank)                                                                                                 \
-            hipLaunchKernelGGL((bin1_downsweep<true, CH>), dim3(g1 + nhelp), dim3(kThreads), 0, s,                            \
-                               (const uint32_t*)ctx->rect.p, d_V, (const uint32_t*)ctx->hist1.p, ctx->hist1_stride,           \
-                               (const uint32_t*)totals1, (uint32_t*)ctx->pairsA.p, cap, d_D, d_overflow, ctx->d_flags,        \
-                               async_overflow_flag ? 1 : 0, fused1 ? (const uint32_t*)gB1 : nullptr, fused1 ? totals1 : nullptr, \
-                               xcdg, (const uint32_t*)hv_cur, (const uint8_t*)ctx->heavy_flag.p,                               \
-                               (uint32_t)nhelp, fp.tiles_x, ctx->gsupB1, (const uint32_t*)d_Vsort,                            \
-                               (keep_overflow && ctx->d_flags) ? ctx->d_flags + 8 : (uint32_t*)nullptr, ctx->occ_seq, d_first); \
-        else                                                                                                                  \
-            hipLaunchKernelGGL((bin1_downsweep<false, CH>), dim3(g1 + nhelp), dim3(kThreads), 0, s,                           \
-                               (const uint32_t*)ctx->rect.p, d_V, (const uint32_t*)ctx->hist1.p, ctx->hist1_stride,           \
-                               (const uint32_t*)totals1, (uint32_t*)ctx->pairsA.p, cap, d_D, d_overflow, ctx->d_flags,        \
-                               async_overflow_flag ? 1 : 0, fused1 ? (const uint32_t*)gB1 : nullptr, fused1 ? totals1 : nullptr, \
-                               xcdg, (const uint32_t*)hv_cur, (const uint8_t*)ctx->heavy_flag.p,                               \
-                               (uint32_t)nhelp, fp.tiles_x, ctx->gsupB1, (const uint32_t*)d_Vsort,                            \
-                               (keep_overflow && ctx->d_flags) ? ctx->d_flags + 8 : (uint32_t*)nullptr, ctx->occ_seq, d_first); \
-    } while (0)
-    // (bin1_upsweep also clears the row pass's group table: its consumer, the previous frame's row downsweep, is long done)
-    MSPLAT_BIN1(kBinChunk);
-#undef MSPLAT_BIN1
+    hipLaunchKernelGGL(bin1_upsweep<kBinChunk>, dim3(g1), dim3(kThreads), 0, s, (const uint32_t*)ctx->rect.p, d_V,
+                       (uint32_t*)ctx->hist1.p, ctx->hist1_stride, d_overflow, fused1 ? gB1 : nullptr, gB2,
+                       ctx->gsumB2_rows, hv_cur, hv_next, (uint8_t*)ctx->heavy_flag.p, heavy_slots, ctx->gsupB1,
+                       keep_overflow, d_first);
+    if (!fused1)
+        launch_scan(s, small, (uint32_t*)ctx->hist1.p, ctx->hist1_stride, d_V, 0u, N, bchunk, totals1);
+    with_flag(ctx->atomic_rank, [&](auto AR) {
+        hipLaunchKernelGGL((bin1_downsweep<AR.value, kBinChunk>), dim3(g1 + nhelp), dim3(kThreads), 0, s,
+                           (const uint32_t*)ctx->rect.p, d_V, (const uint32_t*)ctx->hist1.p, ctx->hist1_stride,
+                           (const uint32_t*)totals1, (uint32_t*)ctx->pairsA.p, cap, d_D, d_overflow, ctx->d_flags,
+                           async_overflow_flag ? 1 : 0, fused1 ? (const uint32_t*)gB1 : nullptr, fused1 ? totals1 : nullptr,
+                           xcdg, (const uint32_t*)hv_cur, (const uint8_t*)ctx->heavy_flag.p,
+                           (uint32_t)nhelp, fp.tiles_x, ctx->gsupB1, (const uint32_t*)d_Vsort,
+                           (keep_overflow && ctx->d_flags) ? ctx->d_flags + 8 : (uint32_t*)nullptr, ctx->occ_seq, d_first);
+    });
     // pass 2: stable partition by tile row (one generic radix pass on the top byte); words become (tx<<24)|rank
     // The heaviest-first order of the bins only pays when every work item has its own wave (the hardware then starts the
     // waves in item order: 83 -> 97 us without it at config 2); persistent waves that pull items from the queue balance
@@ -1345,22 +1378,16 @@ static void issue_binning(RenderChain& rc, int keep_overflow, int occ_pass)
                        nullptr, d_D, 0u, cap, 24, (uint32_t*)ctx->hist2.p, ctx->hist2_stride, fused2 ? gB2 : nullptr, gB1,
                        ctx->gsumB1_rows, fp, (const uint32_t*)totals1, bincnt, ctx->gsupB2);
     if (!fused2)
-        launch_scan(s, ctx->N <= (2u << 20), (uint32_t*)ctx->hist2.p, ctx->hist2_stride, d_D, 0u, cap, (uint32_t)kPairChunk, totals2);
+        launch_scan(s, small, (uint32_t*)ctx->hist2.p, ctx->hist2_stride, d_D, 0u, cap, (uint32_t)kPairChunk, totals2);
     const int g2d = g2 + 1;
-    if (ctx->atomic_rank)
-        hipLaunchKernelGGL((radix_downsweep<MODE_PAIR, false, true>), dim3(g2d), dim3(kThreads), 0, s,
+    with_flag(ctx->atomic_rank, [&](auto AR) {
+        hipLaunchKernelGGL((radix_downsweep<MODE_PAIR, false, AR.value>), dim3(g2d), dim3(kThreads), 0, s,
                            (const uint32_t*)ctx->pairsA.p, nullptr, nullptr, d_D, 0u, cap, 24,
                            (const uint32_t*)ctx->hist2.p, ctx->hist2_stride, (const uint32_t*)totals2,
                            (uint32_t*)ctx->pairsB.p, nullptr, nullptr, (const uint32_t*)totals1,
                            fused2 ? (const uint32_t*)gB2 : nullptr, fused2 ? totals2 : nullptr, fp, bincnt,
                            (uint32_t*)ctx->tile_start.p, (uint32_t*)ctx->tile_order.p, d_queue, ntiles, (ordered ? 1 : 0) | 2, ctx->gsupB2);
-    else
-        hipLaunchKernelGGL((radix_downsweep<MODE_PAIR, false, false>), dim3(g2d), dim3(kThreads), 0, s,
-                           (const uint32_t*)ctx->pairsA.p, nullptr, nullptr, d_D, 0u, cap, 24,
-                           (const uint32_t*)ctx->hist2.p, ctx->hist2_stride, (const uint32_t*)totals2,
-                           (uint32_t*)ctx->pairsB.p, nullptr, nullptr, (const uint32_t*)totals1,
-                           fused2 ? (const uint32_t*)gB2 : nullptr, fused2 ? totals2 : nullptr, fp, bincnt,
-                           (uint32_t*)ctx->tile_start.p, (uint32_t*)ctx->tile_order.p, d_queue, ntiles, (ordered ? 1 : 0) | 2, ctx->gsupB2);
+    });
     rc.ordered = ordered;
     rc.comp_items = comp_items;
     rc.comp_pool = comp_pool;
@@ -1382,6 +1409,7 @@ static int issue_compositor(RenderChain& rc, int occ_pass, int ev_c0, int ev_c1)
     uint32_t* fin = occ_pass ? (uint32_t*)ctx->occ_fin.p : nullptr;
     float4* state = occ_pass ? (float4*)ctx->occ_state.p : nullptr;
     const uint32_t* d_nbins = occ_pass == 2 ? occ + 2 : nullptr;      // second chain of a two-pass frame: the listed unfinished bins
+    const bool f16 = ctx->cfg.fb_format == MSPLAT_FB_RGBA16F;
 
     // persistent compositor: a fixed pool of waves pulls (bin, quadrant) items; never more waves than items
     const int cgrid = std::min(ntiles * 4, ctx->comp_waves);     // work items = (bin, quadrant) (the draw-order compositors)
@@ -1393,29 +1421,21 @@ static int issue_compositor(RenderChain& rc, int occ_pass, int ev_c0, int ev_c1)
     if (ntiles > 0 && ctx->point_mode) {
         // sprites in draw order (optionally against the emulated depth buffer)
         const uint32_t* zqp = ctx->depth_bits ? (const uint32_t*)ctx->zq.p : nullptr;
-        if (ctx->cfg.fb_format == MSPLAT_FB_RGBA16F)
-            hipLaunchKernelGGL(composite_points_kernel<true>, dim3(cgrid), dim3(kCompThreads), 0, s,
+        with_flag(f16, [&](auto F16) {
+            hipLaunchKernelGGL(composite_points_kernel<F16.value>, dim3(cgrid), dim3(kCompThreads), 0, s,
                                (const uint32_t*)ctx->tile_start.p, (const uint32_t*)ctx->pairsB.p,
                                (const float4*)ctx->rec2d.p, zqp, (const float4*)ctx->sprite.p, ctx->sprite_params, d_out,
                                pitch, fp, cap, (const uint32_t*)ctx->tile_order.p, d_queue, (uint32_t)ntiles * 4u);
-        else
-            hipLaunchKernelGGL(composite_points_kernel<false>, dim3(cgrid), dim3(kCompThreads), 0, s,
-                               (const uint32_t*)ctx->tile_start.p, (const uint32_t*)ctx->pairsB.p,
-                               (const float4*)ctx->rec2d.p, zqp, (const float4*)ctx->sprite.p, ctx->sprite_params, d_out,
-                               pitch, fp, cap, (const uint32_t*)ctx->tile_order.p, d_queue, (uint32_t)ntiles * 4u);
+        });
         ctx->comp_kernel_timed = false;
     } else if (ntiles > 0 && (ctx->depth_bits != 0 || ctx->rop != 0)) {
         // emulated depth buffer: draw-order walk, no early termination
-        if (ctx->cfg.fb_format == MSPLAT_FB_RGBA16F)
-            hipLaunchKernelGGL(composite_depth_kernel<true>, dim3(cgrid), dim3(kCompThreads), 0, s,
+        with_flag(f16, [&](auto F16) {
+            hipLaunchKernelGGL(composite_depth_kernel<F16.value>, dim3(cgrid), dim3(kCompThreads), 0, s,
                                (const uint32_t*)ctx->tile_start.p, (const uint32_t*)ctx->pairsB.p,
                                (const float4*)ctx->rec2d.p, (const uint32_t*)ctx->zq.p, d_out, pitch, fp, cap,
                                (const uint32_t*)ctx->tile_order.p, d_queue, (uint32_t)ntiles * 4u);
-        else
-            hipLaunchKernelGGL(composite_depth_kernel<false>, dim3(cgrid), dim3(kCompThreads), 0, s,
-                               (const uint32_t*)ctx->tile_start.p, (const uint32_t*)ctx->pairsB.p,
-                               (const float4*)ctx->rec2d.p, (const uint32_t*)ctx->zq.p, d_out, pitch, fp, cap,
-                               (const uint32_t*)ctx->tile_order.p, d_queue, (uint32_t)ntiles * 4u);
+        });
         ctx->comp_kernel_timed = false;
     } else if (ntiles > 0) {
         // on sampled frames the dominant kernel gets exact dispatch begin/end events (the plain stream
@@ -1427,7 +1447,6 @@ static int issue_compositor(RenderChain& rc, int occ_pass, int ev_c0, int ev_c1)
         const uint32_t* pb = (const uint32_t*)ctx->pairsB.p;
         const float4* r2 = (const float4*)ctx->rec2d.p;
         const uint32_t* ord = occ_pass == 2 ? (const uint32_t*)ctx->occ_unf.p : (const uint32_t*)ctx->tile_order.p + (ordered ? 0 : 65536);
-        const bool f16 = ctx->cfg.fb_format == MSPLAT_FB_RGBA16F;
         // wave issue priority by item number where the items are numbered heaviest-first (every item on its own wave); none for
         // persistent waves that walk the bins in storage order (r3, 4 frames in flight: none / by item number / by list length
         // = 5.82 / 5.76 / 5.79 k frames/s, i.e. no effect there)
@@ -1436,22 +1455,22 @@ static int issue_compositor(RenderChain& rc, int occ_pass, int ev_c0, int ev_c1)
         const CompParams cp = comp_params(fp);
         const CompExtra ex{d_out1, fin, state, d_nbins, probe};
         const int prio = occ_pass == 2 ? 0 : prio_mode;
-#define MSPLAT_COMPOSITE(F16, OCC, TWO, PROBE)                                                                                     \
-        hipExtLaunchKernelGGL((composite_kernel<F16, OCC, TWO, PROBE>), dim3(grid), dim3(kCompThreads), 0, s, e0, e1, 0, ts, pb, r2,  \
-                              d_out, pitch, cp, cap, ord, d_queue, comp_items, prio, ex)
-#define MSPLAT_COMPOSITE_F(F16)                                                                                                    \
-        do {                                                                                                                       \
-            if (occ_pass == 1) MSPLAT_COMPOSITE(F16, 1, false, false);                                                             \
-            else if (occ_pass == 2) MSPLAT_COMPOSITE(F16, 2, false, false);                                                        \
-            else if (stereo && probe) MSPLAT_COMPOSITE(F16, 0, true, true);                                                        \
-            else if (stereo) MSPLAT_COMPOSITE(F16, 0, true, false);                                                                \
-            else if (probe) MSPLAT_COMPOSITE(F16, 0, false, true);                                                                 \
-            else MSPLAT_COMPOSITE(F16, 0, false, false);                                                                           \
-        } while (0)
+        // six of the twelve (OCC, TWO_VIEWS, PROBE) forms exist per format
         // (occlusion_plan never chooses two passes for two views in one chain or while the probe is on)
-        if (f16) MSPLAT_COMPOSITE_F(true); else MSPLAT_COMPOSITE_F(false);
-#undef MSPLAT_COMPOSITE_F
-#undef MSPLAT_COMPOSITE
+        auto composite = [&](auto OCC, auto TWO, auto PROBE) {
+            with_flag(f16, [&](auto F16) {
+                hipExtLaunchKernelGGL((composite_kernel<F16.value, OCC.value, TWO.value, PROBE.value>), dim3(grid), dim3(kCompThreads), 0, s,
+                                      e0, e1, 0, ts, pb, r2, d_out, pitch, cp, cap, ord, d_queue, comp_items, prio, ex);
+            });
+        };
+        constexpr flag_t<true> yes{};
+        constexpr flag_t<false> no{};
+        if (occ_pass == 1) composite(int_t<1>{}, no, no);
+        else if (occ_pass == 2) composite(int_t<2>{}, no, no);
+        else if (stereo && probe) composite(int_t<0>{}, yes, yes);
+        else if (stereo) composite(int_t<0>{}, yes, no);
+        else if (probe) composite(int_t<0>{}, no, yes);
+        else composite(int_t<0>{}, no, no);
         ctx->comp_kernel_timed = timed;
     } else {
         ctx->comp_kernel_timed = false;
@@ -1549,56 +1568,28 @@ int msplat_render(msplat_ctx* ctx, const float cameraMat[16], const float projMa
                   const float viewport[4], const float nearFar[2],
                   void* rgba, uint64_t pitch_bytes, int out_is_device)
 {
-    if (ctx && ctx->worker && g_on_worker_of != ctx) {
-        if (out_is_device && rgba) {
-            FrameArgs a;
-            if (!a.load(cameraMat, projMat, viewport, nearFar)) {
-                ctx->worker->drain();
-                return fail(ctx, MSPLAT_ERR_INVALID_ARG, "NULL matrix/viewport argument");
-            }
-            ctx->worker->post([ctx, a, rgba, pitch_bytes] {
-                return note_async_result(ctx, render_impl(ctx, a.cam, a.proj, a.vp, a.nf, rgba, pitch_bytes, 1));
-            });
-            return MSPLAT_OK;
-        }
-        ctx->worker->drain();           // a host image is filled before the call returns: nothing to defer
-    }
-    return render_impl(ctx, cameraMat, projMat, viewport, nearFar, rgba, pitch_bytes, out_is_device);
+    return submit_frame<false>(ctx, out_is_device && rgba, cameraMat, projMat, cameraMat, projMat, viewport, nearFar,
+                        [=](const float* cam, const float* proj, const float*, const float*, const float* vp, const float* nf) {
+                            return render_impl(ctx, cam, proj, vp, nf, rgba, pitch_bytes, out_is_device);
+                        });
 }
 
-static int render_impl(msplat_ctx* ctx, const float cameraMat[16], const float projMat[16],
-                       const float viewport[4], const float nearFar[2],
-                       void* rgba, uint64_t pitch_bytes, int out_is_device)
+// rows of the target: 0 = tightly packed (`tight` bytes)
+static int resolve_pitch(msplat_ctx* ctx, const char* who, const FrameParams& fp, uint64_t& pitch_bytes, size_t& tight)
 {
-    if (!ctx) return fail(nullptr, MSPLAT_ERR_INVALID_ARG, "ctx is NULL");
-    if (!ctx->has_cloud) return fail(ctx, MSPLAT_ERR_NO_CLOUD, "msplat_render: no cloud uploaded");
-    if (!ctx->has_sort) return fail(ctx, MSPLAT_ERR_NO_SORT, "msplat_render: msplat_sort has not been called");
-    if (!rgba) return fail(ctx, MSPLAT_ERR_INVALID_ARG, "msplat_render: rgba is NULL");
-    FrameParams fp;
-    int rc = make_frame_params(ctx, cameraMat, projMat, viewport, nearFar, fp);
-    if (rc) return rc;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t bpp = ctx->cfg.fb_format == MSPLAT_FB_RGBA16F ? 8 : 16;
-    const size_t tight = (size_t)fp.width * bpp;
+    tight = (size_t)fp.width * bpp;
     if (pitch_bytes == 0) pitch_bytes = tight;
     if (pitch_bytes < tight || pitch_bytes % bpp != 0)
-        return fail(ctx, MSPLAT_ERR_INVALID_ARG, "msplat_render: pitch %llu too small / misaligned for width %d",
+        return fail(ctx, MSPLAT_ERR_INVALID_ARG, "%s: pitch %llu too small / misaligned for width %d", who,
                     (unsigned long long)pitch_bytes, fp.width);
-    ctx->last_fp = fp;
-    if (ctx->tables_dirty && (rc = clear_frame_tables(ctx))) return rc;
-    if (ctx->point_mode && !ctx->sprite.p && (rc = build_sprite(ctx, nullptr, 0, 0))) return rc;   // built-in sphere sprite
-    std::string pending_msg;
-    const int pending = poll_async_overflow(ctx, pending_msg);     // an EARLIER frame; this one is still rendered
-    if (pending == MSPLAT_ERR_HIP) return pending;
+    return MSPLAT_OK;
+}
 
-    if (out_is_device) {
-        rc = launch_render(ctx, fp, rgba, pitch_bytes, true);
-        if (rc) return rc;
-        ctx->has_render = true;
-        if (pending) return fail(ctx, MSPLAT_ERR_PAIR_OVERFLOW_EARLIER, "%s", pending_msg.c_str());
-        return MSPLAT_OK;
-    }
-    // host output: render into an internal device framebuffer, copy back, grow the pair buffer on overflow
+// host output: render into an internal device framebuffer, copy back, grow the pair buffer on overflow
+static int render_to_host(msplat_ctx* ctx, const FrameParams& fp, void* rgba, uint64_t pitch_bytes, size_t tight)
+{
+    int rc;
     if ((rc = buf_alloc(ctx, ctx->fb, tight * fp.height))) return rc;
     RenderPlan plan;
     for (int attempt = 0; attempt < 6; ++attempt) {
@@ -1625,8 +1616,6 @@ static int render_impl(msplat_ctx* ctx, const float cameraMat[16], const float p
             } else {
                 HIP_TRY(ctx, hipMemcpy2D(rgba, pitch_bytes, ctx->fb.p, tight, tight, fp.height, hipMemcpyDeviceToHost));
             }
-            ctx->has_render = true;
-            if (pending) return fail(ctx, MSPLAT_ERR_PAIR_OVERFLOW_EARLIER, "%s", pending_msg.c_str());
             return MSPLAT_OK;
         }
         // overflow: cnt[2] holds the required pair count
@@ -1637,6 +1626,35 @@ static int render_impl(msplat_ctx* ctx, const float cameraMat[16], const float p
         if ((rc = ensure_pair_capacity(ctx, need))) return rc;
     }
     return fail(ctx, MSPLAT_ERR_PAIR_OVERFLOW, "pair buffer could not be grown");
+}
+
+// what every Render does once its FrameParams and pitch stand (rgba1: the second view of two in one chain)
+static int render_frame(msplat_ctx* ctx, const FrameParams& fp, void* rgba, void* rgba1, uint64_t pitch_bytes, size_t tight,
+                        int out_is_device)
+{
+    int rc;
+    ctx->last_fp = fp;
+    if (ctx->tables_dirty && (rc = clear_frame_tables(ctx))) return rc;
+    if (ctx->point_mode && !ctx->sprite.p && (rc = build_sprite(ctx, nullptr, 0, 0))) return rc;   // built-in sphere sprite
+    return with_pending_overflow(ctx, [&] {      // an EARLIER frame; this one is still rendered
+        const int r = out_is_device ? launch_render(ctx, fp, rgba, pitch_bytes, true, rgba1)
+                                    : render_to_host(ctx, fp, rgba, pitch_bytes, tight);
+        if (r == MSPLAT_OK) ctx->has_render = true;
+        return r;
+    });
+}
+
+static int render_impl(msplat_ctx* ctx, const float cameraMat[16], const float projMat[16],
+                       const float viewport[4], const float nearFar[2],
+                       void* rgba, uint64_t pitch_bytes, int out_is_device)
+{
+    FrameParams fp;
+    int rc = begin_frame(ctx, "msplat_render", true, rgba ? nullptr : "rgba is NULL", cameraMat, projMat, viewport, nearFar, fp);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    size_t tight = 0;
+    if ((rc = resolve_pitch(ctx, "msplat_render", fp, pitch_bytes, tight))) return rc;
+    return render_frame(ctx, fp, rgba, nullptr, pitch_bytes, tight, out_is_device);
 }
 
 // buffers indexed by draw-order rank, for 2 N + 64 ranks (two views in one chain)
@@ -1670,33 +1688,18 @@ int msplat_render_stereo(msplat_ctx* ctx, const float cameraMat0[16], const floa
                          const float projMat1[16], const float viewport[4], const float nearFar[2], void* rgba0, void* rgba1,
                          uint64_t pitch_bytes, int out_is_device)
 {
-    if (ctx && ctx->worker && g_on_worker_of != ctx) {
-        if (out_is_device && rgba0 && rgba1) {
-            FrameArgs a, b;
-            if (!a.load(cameraMat0, projMat0, viewport, nearFar) || !b.load(cameraMat1, projMat1, viewport, nearFar)) {
-                ctx->worker->drain();
-                return fail(ctx, MSPLAT_ERR_INVALID_ARG, "NULL matrix/viewport argument");
-            }
-            ctx->worker->post([ctx, a, b, rgba0, rgba1, pitch_bytes] {
-                return note_async_result(ctx, render_stereo_impl(ctx, a.cam, a.proj, b.cam, b.proj, a.vp, a.nf, rgba0, rgba1, pitch_bytes, 1));
-            });
-            return MSPLAT_OK;
-        }
-        ctx->worker->drain();
-    }
-    return render_stereo_impl(ctx, cameraMat0, projMat0, cameraMat1, projMat1, viewport, nearFar, rgba0, rgba1, pitch_bytes, out_is_device);
+    return submit_frame<true>(ctx, out_is_device && rgba0 && rgba1, cameraMat0, projMat0, cameraMat1, projMat1, viewport, nearFar,
+                        [=](const float* cam0, const float* proj0, const float* cam1, const float* proj1, const float* vp, const float* nf) {
+                            return render_stereo_impl(ctx, cam0, proj0, cam1, proj1, vp, nf, rgba0, rgba1, pitch_bytes, out_is_device);
+                        });
 }
 
 static int render_stereo_impl(msplat_ctx* ctx, const float cam0[16], const float proj0[16], const float cam1[16], const float proj1[16],
                               const float viewport[4], const float nearFar[2], void* rgba0, void* rgba1, uint64_t pitch_bytes,
                               int out_is_device)
 {
-    if (!ctx) return fail(nullptr, MSPLAT_ERR_INVALID_ARG, "ctx is NULL");
-    if (!ctx->has_cloud) return fail(ctx, MSPLAT_ERR_NO_CLOUD, "msplat_render_stereo: no cloud uploaded");
-    if (!ctx->has_sort) return fail(ctx, MSPLAT_ERR_NO_SORT, "msplat_render_stereo: msplat_sort has not been called");
-    if (!rgba0 || !rgba1) return fail(ctx, MSPLAT_ERR_INVALID_ARG, "msplat_render_stereo: a target is NULL");
     FrameParams fp, fp1;
-    int rc = make_frame_params(ctx, cam0, proj0, viewport, nearFar, fp);
+    int rc = begin_frame(ctx, "msplat_render_stereo", true, rgba0 && rgba1 ? nullptr : "a target is NULL", cam0, proj0, viewport, nearFar, fp);
     if (!rc) rc = make_frame_params(ctx, cam1, proj1, viewport, nearFar, fp1);
     if (rc) return rc;
     const bool batched = !ctx->banded && !ctx->point_mode && ctx->depth_bits == 0 && ctx->rop == 0 && ctx->N <= (1ull << 23) &&
@@ -1708,12 +1711,8 @@ static int render_stereo_impl(msplat_ctx* ctx, const float cam0[16], const float
         return rc1 ? rc1 : rc;
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t bpp = ctx->cfg.fb_format == MSPLAT_FB_RGBA16F ? 8 : 16;
-    const size_t tight = (size_t)fp.width * bpp;
-    if (pitch_bytes == 0) pitch_bytes = tight;
-    if (pitch_bytes < tight || pitch_bytes % bpp != 0)
-        return fail(ctx, MSPLAT_ERR_INVALID_ARG, "msplat_render_stereo: pitch %llu too small / misaligned for width %d",
-                    (unsigned long long)pitch_bytes, fp.width);
+    size_t tight = 0;
+    if ((rc = resolve_pitch(ctx, "msplat_render_stereo", fp, pitch_bytes, tight))) return rc;
     if ((rc = ensure_stereo_ranks(ctx))) return rc;
     fp.views = 2;
     fp.rows_view = fp.tiles_y;
@@ -1721,16 +1720,7 @@ static int render_stereo_impl(msplat_ctx* ctx, const float cam0[16], const float
     std::memcpy(fp.view1, fp1.view, sizeof(fp.view1));
     std::memcpy(fp.proj1, fp1.proj, sizeof(fp.proj1));
     std::memcpy(fp.eye1, fp1.eye, sizeof(fp.eye1));
-    ctx->last_fp = fp;
-    if (ctx->tables_dirty && (rc = clear_frame_tables(ctx))) return rc;
-    std::string pending_msg;
-    const int pending = poll_async_overflow(ctx, pending_msg);
-    if (pending == MSPLAT_ERR_HIP) return pending;
-    rc = launch_render(ctx, fp, rgba0, pitch_bytes, true, rgba1);
-    if (rc) return rc;
-    ctx->has_render = true;
-    if (pending) return fail(ctx, MSPLAT_ERR_PAIR_OVERFLOW_EARLIER, "%s", pending_msg.c_str());
-    return MSPLAT_OK;
+    return render_frame(ctx, fp, rgba0, rgba1, pitch_bytes, tight, 1);
 }
 
 #include "msplat_getters.hip.inc"

@@ -9,6 +9,7 @@ static int alloc_group_table(msplat_ctx* ctx, Buf& b, uint32_t& rows, uint64_t n
     int rc = buf_alloc(ctx, b, (size_t)rows * 256 * sizeof(uint32_t));
     if (rc) return rc;
     rows = (uint32_t)(b.bytes / (256 * sizeof(uint32_t)));
+    b.frame_table = true;
     HIP_TRY(ctx, hipMemsetAsync(b.p, 0, b.bytes, ctx->stream));
     return MSPLAT_OK;
 }
@@ -113,6 +114,7 @@ static int prepare_cloud_buffers(msplat_ctx* ctx, uint64_t n, bool full_sh, cons
         const size_t gwords = (size_t)((nch >> ctx->ws_gshift) + 2) * kWsMaxBins;
         for (auto& g : ctx->wsGsum) {
             if ((rc = buf_alloc(ctx, g, gwords * 4))) return rc;
+            g.frame_table = true;
             HIP_TRY(ctx, hipMemsetAsync(g.p, 0, g.bytes, ctx->stream));
         }
         ctx->ws_gsum_words = (uint32_t)gwords;
@@ -126,6 +128,7 @@ static int prepare_cloud_buffers(msplat_ctx* ctx, uint64_t n, bool full_sh, cons
     if (ctx->depth_bits != 0 && (rc = buf_alloc(ctx, ctx->zq, alloc_n * 4))) return rc;
     // (column pass: 1024-rank chunks; 2048 measured r3 at 6 M: binning 183 -> 191 us at 1080p, 459 -> 453 us at 4096^2)
     if ((rc = buf_alloc(ctx, ctx->heavy, (size_t)2 * (1 + kHeavyCap) * 4))) return rc;
+    ctx->heavy.frame_table = true;
     HIP_TRY(ctx, hipMemsetAsync(ctx->heavy.p, 0, ctx->heavy.bytes, ctx->stream));
     if ((rc = buf_alloc(ctx, ctx->heavy_flag, (size_t)div_up(alloc_n, kBinChunk) + 64))) return rc;
     HIP_TRY(ctx, hipMemsetAsync(ctx->heavy_flag.p, 0, ctx->heavy_flag.bytes, ctx->stream));
@@ -136,9 +139,6 @@ static int prepare_cloud_buffers(msplat_ctx* ctx, uint64_t n, bool full_sh, cons
                                           : std::max<uint64_t>(1ull << 22, std::min<uint64_t>(32 * n, 1ull << 30));
     return ensure_pair_capacity(ctx, cap);
 }
-
-static void launch_scan(hipStream_t s, bool small, uint32_t* hist, uint32_t hist_stride, const uint32_t* d_n,
-                        uint32_t n_static, uint32_t n_cap, uint32_t chunk, uint32_t* totals);
 
 // Spatial storage order (r4, msplat_common.hip.h: box_live).  Called at the end of an upload, the cloud being on the device in
 // UPLOAD order: Morton codes of the positions, a stable sort of (code, upload index) with the library's own 8-bit radix passes,
@@ -186,18 +186,18 @@ static int spatial_reorder(msplat_ctx* ctx)
     uint32_t* totals = (uint32_t*)ctx->totals.p;
     for (int pass = 0; pass < 4; ++pass) {          // A -> B -> A -> B -> A
         uint32_t *kin = (pass & 1) ? kB : kA, *vin = (pass & 1) ? vB : vA, *kout = (pass & 1) ? kA : kB, *vout = (pass & 1) ? vA : vB;
-#define MSPLAT_SP_UP(IT) hipLaunchKernelGGL((radix_upsweep<MODE_KEYS, IT>), dim3(grid), dim3(kThreads), 0, s, (const uint32_t*)kin, \
-        (const float4*)nullptr, (const uint32_t*)nullptr, N, N, pass * 8, hist, ctx->hist_stride, (uint32_t*)nullptr, (uint32_t*)nullptr, 0u, fp0)
-#define MSPLAT_SP_DOWN(AR, IT) hipLaunchKernelGGL((radix_downsweep<MODE_KEYS, true, AR, IT>), dim3(grid), dim3(kThreads), 0, s, \
-        (const uint32_t*)kin, (const uint32_t*)vin, (const float4*)nullptr, (const uint32_t*)nullptr, N, N, pass * 8, (const uint32_t*)hist, \
-        ctx->hist_stride, (const uint32_t*)totals, kout, vout, (uint32_t*)nullptr, (const uint32_t*)nullptr, (const uint32_t*)nullptr,     \
-        (uint32_t*)nullptr, fp0)
-        if (large) MSPLAT_SP_UP(kSortItemsLarge); else MSPLAT_SP_UP(kSortItems);
-        launch_scan(s, !large, hist, ctx->hist_stride, nullptr, N, N, chunk, totals);
-        if (large) { if (ctx->atomic_rank) MSPLAT_SP_DOWN(true, kSortItemsLarge); else MSPLAT_SP_DOWN(false, kSortItemsLarge); }
-        else { if (ctx->atomic_rank) MSPLAT_SP_DOWN(true, kSortItems); else MSPLAT_SP_DOWN(false, kSortItems); }
-#undef MSPLAT_SP_UP
-#undef MSPLAT_SP_DOWN
+        with_sort_items(large, [&](auto IT) {
+            hipLaunchKernelGGL((radix_upsweep<MODE_KEYS, IT.value>), dim3(grid), dim3(kThreads), 0, s, (const uint32_t*)kin,
+                               (const float4*)nullptr, (const uint32_t*)nullptr, N, N, pass * 8, hist, ctx->hist_stride, (uint32_t*)nullptr,
+                               (uint32_t*)nullptr, 0u, fp0);
+            launch_scan(s, !large, hist, ctx->hist_stride, nullptr, N, N, chunk, totals);
+            with_flag(ctx->atomic_rank, [&](auto AR) {
+                hipLaunchKernelGGL((radix_downsweep<MODE_KEYS, true, AR.value, IT.value>), dim3(grid), dim3(kThreads), 0, s,
+                                   (const uint32_t*)kin, (const uint32_t*)vin, (const float4*)nullptr, (const uint32_t*)nullptr, N, N, pass * 8,
+                                   (const uint32_t*)hist, ctx->hist_stride, (const uint32_t*)totals, kout, vout, (uint32_t*)nullptr,
+                                   (const uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr, fp0);
+            });
+        });
     }
     hipLaunchKernelGGL(gather_cloud_kernel, dim3(2048), dim3(kThreads), 0, s, (const uint32_t*)vA, N, F4, pos,
                        (const float4*)st.recs.p, (float4*)npos, (float4*)nrec);
@@ -348,12 +348,12 @@ int msplat_upload_ply_vertices(msplat_ctx* ctx, const void* vertices, uint64_t n
             PlyLayout kl;
             static_assert(sizeof(PlyLayout) == sizeof(msplat_ply_layout), "layout mirror out of sync");
             std::memcpy(&kl, layout, sizeof(kl));
-#define MSPLAT_INGEST(SH, ST)                                                                                              \
-    hipLaunchKernelGGL((ingest_kernel<SH, ST>), dim3(grid), dim3(64), lds, ctx->stream, (const char*)raw.p, n, kl,        \
-                       (float4*)ctx->pos4.p, (float4*)ctx->recs.p, d_over)
-            if (sh16) { if (full) MSPLAT_INGEST(true, kStorageShFp16); else MSPLAT_INGEST(false, kStorageShFp16); }
-            else { if (full) MSPLAT_INGEST(true, kStorageFp32); else MSPLAT_INGEST(false, kStorageFp32); }
-#undef MSPLAT_INGEST
+            with_flag(full, [&](auto SH) {
+                with_int<kStorageShFp16, kStorageFp32>(ctx->cloud_storage, [&](auto ST) {
+                    hipLaunchKernelGGL((ingest_kernel<SH.value, ST.value>), dim3(grid), dim3(64), lds, ctx->stream, (const char*)raw.p, n, kl,
+                                       (float4*)ctx->pos4.p, (float4*)ctx->recs.p, d_over);
+                });
+            });
             e = hipGetLastError();
         }
         if (e == hipSuccess && sh16) e = hipMemcpyAsync(&n_over, d_over, 4, hipMemcpyDeviceToHost, ctx->stream);
