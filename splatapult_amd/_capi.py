@@ -209,14 +209,16 @@ class EarlierFrameOverflow(UserWarning):
     buffer (MSPLAT_ERR_PAIR_OVERFLOW_EARLIER): that frame lacks splats and should be rendered again"""
 
 
-def check(ctx, rc):
+def check(handle, rc, last_error=None):
+    """raise / warn for the code a call on `handle` returned; last_error: the handle's error getter (default: a context's)"""
+    last_error = last_error or lib().msplat_last_error
     if rc == ERR_PAIR_OVERFLOW_EARLIER:          # a warning about a past frame: this call's result is valid
         import warnings
-        msg = lib().msplat_last_error(ctx)
+        msg = last_error(handle)
         warnings.warn(EarlierFrameOverflow(msg.decode() if msg else "an earlier frame overflowed the pair buffer"), stacklevel=3)
         return
     if rc != OK:
-        msg = lib().msplat_last_error(ctx)
+        msg = last_error(handle)
         raise MsplatError(rc, msg.decode() if msg else "")
 
 

@@ -83,7 +83,6 @@ struct Worker {
     }
 };
 
-
 // ---- RCCL, resolved at run time --------------------------------------------------------------------------------------------
 // (signatures: /opt/rocm/include/rccl/rccl.h:187-260,700-722,923-933; ncclUint8 = 1, ncclSuccess = 0)
 struct Rccl {
@@ -103,44 +102,46 @@ const Rccl& rccl()
 {
     static Rccl r = [] {
         Rccl x;
-        std::vector<std::string> names;
-        if (const char* e = getenv("MSPLAT_RCCL_LIB")) names.push_back(e);
         void* h = nullptr;
         // the copy the process already uses (its communicators belong to THAT copy), then the system's
         // (MSPLAT_RCCL_LIB, when set, is the only candidate: a wrong path is reported, not papered over)
-        if (names.empty())
+        if (const char* e = getenv("MSPLAT_RCCL_LIB")) {
+            h = dlopen(e, RTLD_NOW | RTLD_LOCAL);
+        } else {
             for (const char* n : {"librccl.so.1", "librccl.so"})
                 if (!h) h = dlopen(n, RTLD_NOW | RTLD_NOLOAD);
-        for (const std::string& n : names)
-            if (!h) h = dlopen(n.c_str(), RTLD_NOW | RTLD_LOCAL);
-        if (names.empty())
             for (const char* n : {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"})
                 if (!h) h = dlopen(n, RTLD_NOW | RTLD_LOCAL);
+        }
         if (!h) {
             const char* de = dlerror();          // (ONE call: dlerror() clears the error it returns -- ADVICE r5)
             x.why = std::string("librccl not found (") + (de ? de : "?") + "); set MSPLAT_RCCL_LIB";
             return x;
         }
-        bool all = true;
-        auto sym = [&](const char* n) { void* p = dlsym(h, n); if (!p) { all = false; x.why = std::string("librccl lacks ") + n; } return p; };
-        x.GroupStart = (int (*)())sym("ncclGroupStart");
-        x.GroupEnd = (int (*)())sym("ncclGroupEnd");
-        x.Send = (int (*)(const void*, size_t, int, int, void*, hipStream_t))sym("ncclSend");
-        x.Recv = (int (*)(void*, size_t, int, int, void*, hipStream_t))sym("ncclRecv");
-        x.CommInitAll = (int (*)(void**, int, const int*))sym("ncclCommInitAll");
-        x.CommDestroy = (int (*)(void*))sym("ncclCommDestroy");
-        x.GetErrorString = (const char* (*)(int))sym("ncclGetErrorString");
-        if (all) x.lib = h;
+        auto load = [&](auto& fn, const char* n) {           // (the pointer type is the member's)
+            fn = reinterpret_cast<std::decay_t<decltype(fn)>>(dlsym(h, n));
+            if (!fn) x.why = std::string("librccl lacks ") + n;
+        };
+        load(x.GroupStart, "ncclGroupStart");
+        load(x.GroupEnd, "ncclGroupEnd");
+        load(x.Send, "ncclSend");
+        load(x.Recv, "ncclRecv");
+        load(x.CommInitAll, "ncclCommInitAll");
+        load(x.CommDestroy, "ncclCommDestroy");
+        load(x.GetErrorString, "ncclGetErrorString");
+        if (x.why.empty()) x.lib = h;
         return x;
     }();
     return r;
 }
 constexpr int kNcclUint8 = 1;
 
-// the runs of consecutive bin rows rank `rank` of `world` owns under a standard layout, as pixel rows [y0, y0 + nrows) of an
-// image of H rows: f(y0, nrows).  (Runs end at block boundaries; contiguous bands are one run.)
-template <class F>
-int for_each_run(int32_t kind, int32_t block_rows, int32_t world, int32_t rank, int H, F&& f)
+// a run of consecutive pixel rows [y0, y0 + nrows) that travels to / from rank `peer`
+struct Run { int peer, y0, nrows; };
+
+// appends the runs of consecutive bin rows rank `rank` of `world` owns under a standard layout, as pixel rows of an image of H
+// rows, to `out`.  (Runs end at block boundaries; contiguous bands are one run.)
+int append_runs(int32_t kind, int32_t block_rows, int32_t world, int32_t rank, int H, int peer, std::vector<Run>* out)
 {
     const int T = msplat_tile_size(), rows_full = (H + T - 1) / T;
     int32_t first, count, block, stride;
@@ -153,11 +154,29 @@ int for_each_run(int32_t kind, int32_t block_rows, int32_t world, int32_t rank, 
         const int y0 = row * T, nrows = std::min(run * T, H - y0);
         v += run;
         if (nrows <= 0) break;
-        const int rc = f(y0, nrows);
-        if (rc) return rc;
+        out->push_back(Run{peer, y0, nrows});
     }
     return MSPLAT_OK;
 }
+
+// one RCCL group: step(run, index) posts the sends / receives of every run until one fails; a group that was opened is closed
+// either way.  Returns the first non-zero nccl code.
+template <class Step>
+int post_group(const Rccl& R, const std::vector<Run>& runs, Step&& step)
+{
+    int nrc = R.GroupStart();
+    if (nrc != 0) return nrc;
+    for (size_t k = 0; k < runs.size() && nrc == 0; ++k) nrc = step(runs[k], k);
+    const int erc = R.GroupEnd();
+    return nrc != 0 ? nrc : erc;
+}
+
+// rows of `width` >= 1 pixels of a framebuffer format: bytes per pixel and per tight row, and whether a pitch can hold them
+struct RowGeom {
+    size_t bpp, tight;
+    RowGeom(int fb_format, int width) : bpp(fb_format == MSPLAT_FB_RGBA16F ? 8 : 16), tight((size_t)width * bpp) {}
+    bool fits(size_t pitch) const { return pitch >= tight && pitch % bpp == 0; }
+};
 
 // ---- fp16 on the wire (MSPLAT_EXCHANGE_WIRE_FP16): the rows of an RGBA32F target travel as RGBA16F ---------------------------------
 // One thread per pixel of a run: float4 <-> four halves (round to nearest even).  `rows` pitch rows of `width` pixels; the packed side
@@ -183,6 +202,7 @@ __global__ __launch_bounds__(256) void unpack_rows_f16(const uint2* __restrict__
         reinterpret_cast<float4*>(dst + y * pitch)[x] = make_float4((float)pk.h[0], (float)pk.h[1], (float)pk.h[2], (float)pk.h[3]);
     }
 }
+dim3 rows_grid(int width, int rows) { return dim3((unsigned)std::min<size_t>(((size_t)width * rows + 255) / 256, 4096)); }
 
 }  // namespace
 
@@ -211,28 +231,32 @@ namespace {
 
 thread_local std::string g_group_error;
 
-int gfail(msplat_group* g, int code, const char* fmt, ...)
+std::string vformat(const char* fmt, va_list ap)
 {
     char buf[512];
+    vsnprintf(buf, sizeof(buf), fmt, ap);
+    return buf;
+}
+
+int gfail(msplat_group* g, int code, const char* fmt, ...)
+{
     va_list ap;
     va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
+    g_group_error = vformat(fmt, ap);
     va_end(ap);
-    g_group_error = buf;
-    if (g) g->err = buf;
+    if (g) g->err = g_group_error;
     return code;
 }
+#define GROUP_OR_FAIL(g) do { if (!(g)) return gfail(nullptr, MSPLAT_ERR_INVALID_ARG, "group is NULL"); } while (0)
 
 // failure inside rank i's part of a for_all (possibly on a worker thread): the text goes to the rank's own slot -- several
 // ranks may fail at once (they raced on g->err) -- and for_all reports it from the caller's thread
 int rfail(msplat_group* g, uint32_t i, int code, const char* fmt, ...)
 {
-    char buf[512];
     va_list ap;
     va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
+    g->rank_err[i] = vformat(fmt, ap);
     va_end(ap);
-    g->rank_err[i] = buf;
     return code;
 }
 
@@ -240,6 +264,7 @@ int rfail(msplat_group* g, uint32_t i, int code, const char* fmt, ...)
 // (MSPLAT_ERR_PAIR_OVERFLOW[_EARLIER] -- a deferred report about an EARLIER frame -- only if nothing worse happened)
 int for_all(msplat_group* g, const std::function<int(uint32_t)>& f)
 {
+    GROUP_OR_FAIL(g);            // (f is not called: the entry points that only fan out leave the check to this line)
     const uint32_t n = (uint32_t)g->ctx.size();
     for (auto& e : g->rank_err) e.clear();
     for (uint32_t i = 1; i < n; ++i) g->workers[i - 1]->post([&f, i] { return f(i); });
@@ -288,6 +313,90 @@ int plan_rows(msplat_group* g, const float viewport[4])
     return MSPLAT_OK;
 }
 
+// ---- msplat_group_render with a device target: what one rank does under each exchange ------------------------------------------
+struct Frame {
+    const float *cam, *proj, *vp, *nf;
+    void *rgba, *stream0;       // the target on device 0 (H rows `pitch` bytes apart, `tight` bytes of pixels in each); context 0's stream
+    size_t pitch, tight;
+    int H;
+};
+
+// rank i's staging framebuffer holds at least `need` bytes
+int ensure_stage(msplat_group* g, uint32_t i, size_t need)
+{
+    if (hipSetDevice(g->devices[i]) != hipSuccess) return rfail(g, i, MSPLAT_ERR_HIP, "hipSetDevice(%d) failed", g->devices[i]);
+    if (g->stage_bytes[i] >= need) return MSPLAT_OK;
+    (void)msplat_synchronize(g->ctx[i]);
+    if (g->stage[i]) (void)hipFree(g->stage[i]);
+    g->stage[i] = nullptr;
+    g->stage_bytes[i] = 0;
+    if (hipMalloc(&g->stage[i], need) != hipSuccess) return rfail(g, i, MSPLAT_ERR_HIP, "staging framebuffer: out of device memory");
+    g->stage_bytes[i] = need;
+    return MSPLAT_OK;
+}
+
+// no peer mapping: rank i renders into its staging framebuffer, as H rows of `pitch` bytes
+int render_staged(msplat_group* g, uint32_t i, const Frame& f, size_t pitch)
+{
+    const int e = ensure_stage(g, i, pitch * (size_t)f.H);
+    return e ? e : msplat_render(g->ctx[i], f.cam, f.proj, f.vp, f.nf, g->stage[i], pitch, 1);
+}
+
+// copy: a tight local image, then one copy per run of consecutive owned rows
+int render_and_copy(msplat_group* g, uint32_t i, const Frame& f)
+{
+    const int r = render_staged(g, i, f, f.tight);
+    if (r && r != MSPLAT_ERR_PAIR_OVERFLOW_EARLIER) return r;
+    std::vector<Run> runs;
+    const int pr = append_runs(g->kind, g->block_rows, (int32_t)g->ctx.size(), (int32_t)i, f.H, 0, &runs);
+    if (pr) return rfail(g, i, pr, "%s", msplat_last_error(nullptr));
+    hipStream_t s = (hipStream_t)msplat_get_stream(g->ctx[i]);
+    for (const Run& run : runs)
+        if (hipMemcpy2DAsync((char*)f.rgba + (size_t)run.y0 * f.pitch, f.pitch, (const char*)g->stage[i] + (size_t)run.y0 * f.tight,
+                             f.tight, f.tight, (size_t)run.nrows, hipMemcpyDeviceToDevice, s) != hipSuccess)
+            return rfail(g, i, MSPLAT_ERR_HIP, "hipMemcpy2DAsync (device %d -> %d) failed", g->devices[i], g->devices[0]);
+    return r;
+}
+
+// rank i's part of the frame: ranks >= 1 wait for the ordering event first, and context 0's stream waits for what they queued
+// (RCCL: they only render, with the target's pitch -- post_staged_rows makes context 0's stream receive their rows)
+int render_rank(msplat_group* g, uint32_t i, const Frame& f, bool use_rccl)
+{
+    msplat_ctx* c = g->ctx[i];
+    if (i != 0) { const int e = msplat_wait_event(c, g->order_ev); if (e) return e; }
+    if (i != 0 && use_rccl) return render_staged(g, i, f, f.pitch);
+    // rank 0 and peer store -- zero-copy: this device's compositor writes its rows where they belong in device 0's framebuffer
+    const int r = (i == 0 || g->peer_store[i]) ? msplat_render(c, f.cam, f.proj, f.vp, f.nf, f.rgba, f.pitch, 1) : render_and_copy(g, i, f);
+    if (i == 0 || (r && r != MSPLAT_ERR_PAIR_OVERFLOW_EARLIER)) return r;
+    const int j = msplat_stream_wait(c, f.stream0);
+    return j ? j : r;
+}
+
+// RCCL: every rank has rendered its rows into an image of its own with the target's pitch (a run of rows is then one contiguous
+// range on both sides); the caller's thread issues ALL sends and receives as one group: rank i's sends on its stream behind
+// its compositor, device 0's receives on context 0's stream -- synchronising that stream = frame complete
+int post_staged_rows(msplat_group* g, const Frame& f)
+{
+    const uint32_t n = (uint32_t)g->ctx.size();
+    // (contexts created with async_submit: every rank's worker has issued its render before the sends are queued behind it)
+    for (uint32_t i = 0; i < n; ++i) {
+        const int w = msplat_stream_wait(g->ctx[i], msplat_get_stream(g->ctx[i]));
+        if (w != MSPLAT_OK && w != MSPLAT_ERR_PAIR_OVERFLOW_EARLIER) return gfail(g, w, "msplat_group_render: %s", msplat_last_error(g->ctx[i]));
+    }
+    std::vector<Run> runs;                                             // (peer = the rank that owns and sends the run)
+    int pr = MSPLAT_OK;
+    for (uint32_t i = 1; i < n && pr == MSPLAT_OK; ++i) pr = append_runs(g->kind, g->block_rows, (int32_t)n, (int32_t)i, f.H, (int)i, &runs);
+    if (pr) return gfail(g, pr, "msplat_group_render: %s", msplat_last_error(nullptr));
+    const Rccl& R = rccl();
+    const int nrc = post_group(R, runs, [&](const Run& run, size_t) {
+        const size_t off = (size_t)run.y0 * f.pitch, bytes = (size_t)(run.nrows - 1) * f.pitch + f.tight;
+        const int e = R.Send((const char*)g->stage[run.peer] + off, bytes, kNcclUint8, 0, g->comms[run.peer],
+                             (hipStream_t)msplat_get_stream(g->ctx[run.peer]));
+        return e != 0 ? e : R.Recv((char*)f.rgba + off, bytes, kNcclUint8, run.peer, g->comms[0], (hipStream_t)f.stream0);
+    });
+    return nrc != 0 ? gfail(g, MSPLAT_ERR_HIP, "msplat_group_render: RCCL row exchange failed: %s", R.GetErrorString(nrc)) : MSPLAT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -310,17 +419,15 @@ int msplat_group_create(msplat_group** out, const int32_t* devices, uint32_t n, 
         std::memcpy(&c, cfg, cfg->struct_size);
         c.struct_size = sizeof(c);
     }
-    msplat_group* g = new msplat_group;
+    // (from here a failure is gfail(nullptr, ...): g_group_error keeps the text, `owner` destroys the half-built group)
+    std::unique_ptr<msplat_group, decltype(&msplat_group_destroy)> owner(new msplat_group, &msplat_group_destroy);
+    msplat_group* g = owner.get();
     g->fb_format = c.fb_format;
     for (uint32_t i = 0; i < n; ++i) {
         c.device = devices[i];
         msplat_ctx* h = nullptr;
         const int rc = msplat_create(&h, &c);
-        if (rc) {
-            gfail(nullptr, rc, "msplat_group_create: device %d: %s", devices[i], msplat_last_error(nullptr));
-            msplat_group_destroy(g);
-            return rc;
-        }
+        if (rc) return gfail(nullptr, rc, "msplat_group_create: device %d: %s", devices[i], msplat_last_error(nullptr));
         g->ctx.push_back(h);
         g->devices.push_back(devices[i]);
     }
@@ -328,11 +435,8 @@ int msplat_group_create(msplat_group** out, const int32_t* devices, uint32_t n, 
     g->stage.assign(n, nullptr);
     g->stage_bytes.assign(n, 0);
     g->rank_err.assign(n, std::string());
-    if (n > 1 && (hipSetDevice(devices[0]) != hipSuccess || hipEventCreateWithFlags(&g->order_ev, hipEventDisableTiming) != hipSuccess)) {
-        gfail(nullptr, MSPLAT_ERR_HIP, "msplat_group_create: cannot create the ordering event on device %d", devices[0]);
-        msplat_group_destroy(g);
-        return MSPLAT_ERR_HIP;
-    }
+    if (n > 1 && (hipSetDevice(devices[0]) != hipSuccess || hipEventCreateWithFlags(&g->order_ev, hipEventDisableTiming) != hipSuccess))
+        return gfail(nullptr, MSPLAT_ERR_HIP, "msplat_group_create: cannot create the ordering event on device %d", devices[0]);
     // peer mapping towards device 0: the other devices' compositors then write their rows into its framebuffer directly
     for (uint32_t i = 1; i < n; ++i) {
         if (devices[i] == devices[0]) continue;            // same device (tests): plain device memory
@@ -352,30 +456,24 @@ int msplat_group_create(msplat_group** out, const int32_t* devices, uint32_t n, 
         w->th = std::thread([w] { w->run(); });
     }
     if (const char* e = getenv("MSPLAT_GROUP_EXCHANGE")) {
-        const std::string x = e;
+        static const struct { const char* name; int exchange; } names[] = {
+            {"peer", MSPLAT_EXCHANGE_PEER_STORE}, {"peer_store", MSPLAT_EXCHANGE_PEER_STORE}, {"rccl", MSPLAT_EXCHANGE_RCCL}, {"copy", MSPLAT_EXCHANGE_COPY}};
         int want = -1;
-        if (x == "rccl") want = MSPLAT_EXCHANGE_RCCL;
-        else if (x == "copy") want = MSPLAT_EXCHANGE_COPY;
-        else if (x == "peer" || x == "peer_store") want = MSPLAT_EXCHANGE_PEER_STORE;
-        if (want < 0) {                 // a typo ("nccl") must not silently select the default
-            gfail(nullptr, MSPLAT_ERR_INVALID_ARG, "msplat_group_create: MSPLAT_GROUP_EXCHANGE=%s: expected peer | peer_store | rccl | copy", e);
-            msplat_group_destroy(g);
-            return MSPLAT_ERR_INVALID_ARG;
-        }
+        for (const auto& x : names)
+            if (std::strcmp(e, x.name) == 0) want = x.exchange;
+        if (want < 0)                   // a typo ("nccl") must not silently select the default
+            return gfail(nullptr, MSPLAT_ERR_INVALID_ARG, "msplat_group_create: MSPLAT_GROUP_EXCHANGE=%s: expected peer | peer_store | rccl | copy", e);
         const int rc = msplat_group_set_exchange(g, want);
-        if (rc) {                       // asked for in the environment and not available: say so instead of silently doing something else
-            gfail(nullptr, rc, "msplat_group_create: MSPLAT_GROUP_EXCHANGE=%s: %s", e, g->err.c_str());
-            msplat_group_destroy(g);
-            return rc;
-        }
+        if (rc)                         // asked for in the environment and not available: say so instead of silently doing something else
+            return gfail(nullptr, rc, "msplat_group_create: MSPLAT_GROUP_EXCHANGE=%s: %s", e, g->err.c_str());
     }
-    *out = g;
+    *out = owner.release();
     return MSPLAT_OK;
 }
 
 int msplat_group_set_exchange(msplat_group* g, int32_t exchange)
 {
-    if (!g) return gfail(nullptr, MSPLAT_ERR_INVALID_ARG, "group is NULL");
+    GROUP_OR_FAIL(g);
     const uint32_t n = (uint32_t)g->ctx.size();
     if (exchange == MSPLAT_EXCHANGE_PEER_STORE || exchange == MSPLAT_EXCHANGE_COPY) {
         for (uint32_t i = 1; i < n; ++i) g->peer_store[i] = exchange == MSPLAT_EXCHANGE_PEER_STORE && g->peer_ok[i];
@@ -432,25 +530,22 @@ int msplat_group_peer_store(const msplat_group* g, uint32_t i) { return (g && i 
 int msplat_group_upload_cloud(msplat_group* g, const void* aos, uint64_t n, uint32_t stride_bytes, const msplat_attr_offsets* off,
                               int full_sh)
 {
-    if (!g) return gfail(nullptr, MSPLAT_ERR_INVALID_ARG, "group is NULL");
     return for_all(g, [&](uint32_t i) { return msplat_upload_cloud(g->ctx[i], aos, n, stride_bytes, off, full_sh); });
 }
 
 int msplat_group_upload_gaussian_cloud(msplat_group* g, const msplat_cloud* c)
 {
-    if (!g) return gfail(nullptr, MSPLAT_ERR_INVALID_ARG, "group is NULL");
     return for_all(g, [&](uint32_t i) { return msplat_upload_gaussian_cloud(g->ctx[i], c); });
 }
 
 int msplat_group_upload_ply(msplat_group* g, const char* path, int import_full_sh)
 {
-    if (!g) return gfail(nullptr, MSPLAT_ERR_INVALID_ARG, "group is NULL");
     return for_all(g, [&](uint32_t i) { return msplat_upload_ply(g->ctx[i], path, import_full_sh); });
 }
 
 int msplat_group_set_cloud_storage(msplat_group* g, int32_t storage)
 {
-    if (!g) return gfail(nullptr, MSPLAT_ERR_INVALID_ARG, "group is NULL");
+    GROUP_OR_FAIL(g);
     if (storage != MSPLAT_STORAGE_FP32 && storage != MSPLAT_STORAGE_SH_FP16)
         return gfail(g, MSPLAT_ERR_INVALID_ARG, "msplat_group_set_cloud_storage: unknown storage %d", storage);
     for (msplat_ctx* c : g->ctx) {
@@ -462,7 +557,7 @@ int msplat_group_set_cloud_storage(msplat_group* g, int32_t storage)
 
 int msplat_group_set_layout(msplat_group* g, int32_t kind, int32_t block_rows)
 {
-    if (!g) return gfail(nullptr, MSPLAT_ERR_INVALID_ARG, "group is NULL");
+    GROUP_OR_FAIL(g);
     if (kind != MSPLAT_BANDS_CONTIGUOUS && kind != MSPLAT_BANDS_INTERLEAVED && kind != MSPLAT_BANDS_BLOCK_INTERLEAVED &&
         kind != MSPLAT_BANDS_ROOT_WEIGHTED)
         return gfail(g, MSPLAT_ERR_INVALID_ARG, "msplat_group_set_layout: unknown kind %d", kind);
@@ -476,7 +571,7 @@ int msplat_group_set_layout(msplat_group* g, int32_t kind, int32_t block_rows)
 
 int msplat_group_set_band_cull(msplat_group* g, int enable)
 {
-    if (!g) return gfail(nullptr, MSPLAT_ERR_INVALID_ARG, "group is NULL");
+    GROUP_OR_FAIL(g);
     g->band_cull = enable != 0;
     g->planned_rows = -1;
     return MSPLAT_OK;
@@ -485,122 +580,42 @@ int msplat_group_set_band_cull(msplat_group* g, int enable)
 int msplat_group_sort(msplat_group* g, const float cameraMat[16], const float projMat[16], const float viewport[4],
                       const float nearFar[2])
 {
-    if (!g) return gfail(nullptr, MSPLAT_ERR_INVALID_ARG, "group is NULL");
-    int rc = plan_rows(g, viewport);
-    if (rc) return rc;
-    return for_all(g, [&](uint32_t i) { return msplat_sort(g->ctx[i], cameraMat, projMat, viewport, nearFar); });
+    GROUP_OR_FAIL(g);
+    const int rc = plan_rows(g, viewport);
+    return rc ? rc : for_all(g, [&](uint32_t i) { return msplat_sort(g->ctx[i], cameraMat, projMat, viewport, nearFar); });
 }
 
 int msplat_group_render(msplat_group* g, const float cameraMat[16], const float projMat[16], const float viewport[4],
                         const float nearFar[2], void* rgba, uint64_t pitch_bytes, int out_is_device)
 {
-    if (!g) return gfail(nullptr, MSPLAT_ERR_INVALID_ARG, "group is NULL");
+    GROUP_OR_FAIL(g);
     if (!rgba) return gfail(g, MSPLAT_ERR_INVALID_ARG, "msplat_group_render: rgba is NULL");
     int rc = plan_rows(g, viewport);
     if (rc) return rc;
     const uint32_t n = (uint32_t)g->ctx.size();
     const int W = (int)viewport[2], H = (int)viewport[3];
-    const size_t bpp = g->fb_format == MSPLAT_FB_RGBA16F ? 8 : 16;
-    const size_t tight = (size_t)W * bpp;
-    if (pitch_bytes == 0) pitch_bytes = tight;
-    if (W < 1 || H < 1 || pitch_bytes < tight || pitch_bytes % bpp != 0)
+    const RowGeom q(g->fb_format, W);
+    const size_t pitch = pitch_bytes ? (size_t)pitch_bytes : q.tight;
+    if (W < 1 || H < 1 || !q.fits(pitch))
         return gfail(g, MSPLAT_ERR_INVALID_ARG, "msplat_group_render: pitch %llu too small / misaligned for a %dx%d target of %zu bytes per pixel",
-                     (unsigned long long)pitch_bytes, W, H, bpp);
+                     (unsigned long long)pitch, W, H, q.bpp);
     if (!out_is_device)         // host image: every context copies its own rows into it (msplat_render's band rule)
-        return for_all(g, [&](uint32_t i) { return msplat_render(g->ctx[i], cameraMat, projMat, viewport, nearFar, rgba, pitch_bytes, 0); });
+        return for_all(g, [&](uint32_t i) { return msplat_render(g->ctx[i], cameraMat, projMat, viewport, nearFar, rgba, pitch, 0); });
 
     // The frame inherits context 0's stream order on EVERY rank: whatever the caller queued on that stream before
     // this call -- typically the consumer of the previous frame in the same framebuffer -- is finished before any rank's
     // compositor or row copy writes into `rgba`, exactly as with a single context.  One event record + n - 1 stream waits.
-    void* stream0 = msplat_get_stream(g->ctx[0]);
-    if (n > 1) {
-        if (hipSetDevice(g->devices[0]) != hipSuccess || hipEventRecord(g->order_ev, (hipStream_t)stream0) != hipSuccess)
-            return gfail(g, MSPLAT_ERR_HIP, "msplat_group_render: cannot record the ordering event on device %d", g->devices[0]);
-    }
+    const Frame f{cameraMat, projMat, viewport, nearFar, rgba, msplat_get_stream(g->ctx[0]), pitch, q.tight, H};
+    if (n > 1 && (hipSetDevice(g->devices[0]) != hipSuccess || hipEventRecord(g->order_ev, (hipStream_t)f.stream0) != hipSuccess))
+        return gfail(g, MSPLAT_ERR_HIP, "msplat_group_render: cannot record the ordering event on device %d", g->devices[0]);
     const bool use_rccl = n > 1 && g->exchange == MSPLAT_EXCHANGE_RCCL && !g->comms.empty();
     g->last_exchange = n == 1 ? g->exchange : (use_rccl ? MSPLAT_EXCHANGE_RCCL : MSPLAT_EXCHANGE_COPY);
     for (uint32_t i = 1; i < n && !use_rccl; ++i)
         if (g->peer_store[i]) g->last_exchange = MSPLAT_EXCHANGE_PEER_STORE;
-    if (use_rccl) {
-        // every rank renders its rows into an image of its own with the target's pitch (a run of rows is then one contiguous
-        // range on both sides); the caller's thread then issues ALL sends and receives as one group: rank i's sends on its
-        // stream behind its compositor, device 0's receives on context 0's stream -- synchronising that stream = frame complete
-        rc = for_all(g, [&](uint32_t i) -> int {
-            msplat_ctx* c = g->ctx[i];
-            if (i == 0) return msplat_render(c, cameraMat, projMat, viewport, nearFar, rgba, pitch_bytes, 1);
-            const int j = msplat_wait_event(c, g->order_ev);
-            if (j) return j;
-            if (hipSetDevice(g->devices[i]) != hipSuccess) return rfail(g, i, MSPLAT_ERR_HIP, "hipSetDevice(%d) failed", g->devices[i]);
-            const size_t need = (size_t)pitch_bytes * (size_t)H;
-            if (g->stage_bytes[i] < need) {
-                (void)msplat_synchronize(c);
-                if (g->stage[i]) (void)hipFree(g->stage[i]);
-                g->stage[i] = nullptr;
-                g->stage_bytes[i] = 0;
-                if (hipMalloc(&g->stage[i], need) != hipSuccess) return rfail(g, i, MSPLAT_ERR_HIP, "staging framebuffer: out of device memory");
-                g->stage_bytes[i] = need;
-            }
-            return msplat_render(c, cameraMat, projMat, viewport, nearFar, g->stage[i], pitch_bytes, 1);
-        });
-        if (rc && rc != MSPLAT_ERR_PAIR_OVERFLOW_EARLIER) return rc;
-        // (contexts created with async_submit: every rank's worker has issued its render before the sends are queued behind it)
-        for (uint32_t i = 0; i < n; ++i) {
-            const int w = msplat_stream_wait(g->ctx[i], msplat_get_stream(g->ctx[i]));
-            if (w != MSPLAT_OK && w != MSPLAT_ERR_PAIR_OVERFLOW_EARLIER) return gfail(g, w, "msplat_group_render: %s", msplat_last_error(g->ctx[i]));
-        }
-        const Rccl& R = rccl();
-        int nrc = R.GroupStart();
-        for (uint32_t i = 1; i < n && nrc == 0; ++i) {
-            hipStream_t si = (hipStream_t)msplat_get_stream(g->ctx[i]);
-            const int prc = for_each_run(g->kind, g->block_rows, (int32_t)n, (int32_t)i, H, [&](int y0, int nrows) -> int {
-                const size_t off = (size_t)y0 * pitch_bytes, bytes = (size_t)(nrows - 1) * pitch_bytes + tight;
-                int e = R.Send((const char*)g->stage[i] + off, bytes, kNcclUint8, 0, g->comms[i], si);
-                if (e == 0) e = R.Recv((char*)rgba + off, bytes, kNcclUint8, (int)i, g->comms[0], (hipStream_t)stream0);
-                if (e != 0) nrc = e;
-                return e != 0 ? MSPLAT_ERR_HIP : MSPLAT_OK;
-            });
-            if (prc && nrc == 0) { (void)R.GroupEnd(); return gfail(g, prc, "msplat_group_render: %s", msplat_last_error(nullptr)); }
-        }
-        const int erc = R.GroupEnd();
-        if (nrc == 0) nrc = erc;
-        if (nrc != 0) return gfail(g, MSPLAT_ERR_HIP, "msplat_group_render: RCCL row exchange failed: %s", R.GetErrorString(nrc));
-        return rc;
-    }
-    rc = for_all(g, [&](uint32_t i) -> int {
-        msplat_ctx* c = g->ctx[i];
-        if (i != 0) { const int j = msplat_wait_event(c, g->order_ev); if (j) return j; }
-        if (i == 0 || g->peer_store[i]) {
-            // zero-copy: this device's compositor writes its rows where they belong in device 0's framebuffer
-            int r = msplat_render(c, cameraMat, projMat, viewport, nearFar, rgba, pitch_bytes, 1);
-            if (r && r != MSPLAT_ERR_PAIR_OVERFLOW_EARLIER) return r;
-            if (i != 0) { const int j = msplat_stream_wait(c, stream0); if (j) return j; }
-            return r;
-        }
-        // no peer mapping: render into a local image, then one copy per run of consecutive owned rows
-        if (hipSetDevice(g->devices[i]) != hipSuccess) return rfail(g, i, MSPLAT_ERR_HIP, "hipSetDevice(%d) failed", g->devices[i]);
-        const size_t need = tight * (size_t)H;
-        if (g->stage_bytes[i] < need) {
-            (void)msplat_synchronize(c);
-            if (g->stage[i]) (void)hipFree(g->stage[i]);
-            g->stage[i] = nullptr;
-            g->stage_bytes[i] = 0;
-            if (hipMalloc(&g->stage[i], need) != hipSuccess) return rfail(g, i, MSPLAT_ERR_HIP, "staging framebuffer: out of device memory");
-            g->stage_bytes[i] = need;
-        }
-        int r = msplat_render(c, cameraMat, projMat, viewport, nearFar, g->stage[i], tight, 1);
-        if (r && r != MSPLAT_ERR_PAIR_OVERFLOW_EARLIER) return r;
-        hipStream_t s = (hipStream_t)msplat_get_stream(c);
-        const int pr = for_each_run(g->kind, g->block_rows, (int32_t)n, (int32_t)i, H, [&](int y0, int nrows) -> int {
-            if (hipMemcpy2DAsync((char*)rgba + (size_t)y0 * pitch_bytes, pitch_bytes, (const char*)g->stage[i] + (size_t)y0 * tight,
-                                 tight, tight, (size_t)nrows, hipMemcpyDeviceToDevice, s) != hipSuccess)
-                return rfail(g, i, MSPLAT_ERR_HIP, "hipMemcpy2DAsync (device %d -> %d) failed", g->devices[i], g->devices[0]);
-            return MSPLAT_OK;
-        });
-        if (pr) { if (g->rank_err[i].empty()) rfail(g, i, pr, "%s", msplat_last_error(nullptr)); return pr; }
-        const int j = msplat_stream_wait(c, stream0);
-        return j ? j : r;
-    });
-    return rc;
+    rc = for_all(g, [&](uint32_t i) { return render_rank(g, i, f, use_rccl); });
+    if (!use_rccl || (rc && rc != MSPLAT_ERR_PAIR_OVERFLOW_EARLIER)) return rc;
+    const int prc = post_staged_rows(g, f);
+    return prc ? prc : rc;
 }
 
 // ---- the exchange for one process per GPU --------------------------------------------------------------------------------------
@@ -615,13 +630,12 @@ static int band_exchange_impl(msplat_ctx* ctx, void* comm, int32_t rank, int32_t
         return gfail(nullptr, MSPLAT_ERR_INVALID_ARG, "msplat_band_exchange: NULL communicator / framebuffer or empty image");
     const bool wire16 = (flags & MSPLAT_EXCHANGE_WIRE_FP16) != 0;
     // the pixel size is the CONTEXT's target format (it used to be inferred from the pitch)
-    const size_t bpp = msplat_get_fb_format(ctx) == MSPLAT_FB_RGBA16F ? 8u : 16u;
-    const size_t tight = (size_t)width * bpp;
-    if (wire16 && bpp != 16u)
+    const RowGeom q(msplat_get_fb_format(ctx), width);
+    if (wire16 && q.bpp != 16u)
         return gfail(nullptr, MSPLAT_ERR_INVALID_ARG, "msplat_band_exchange: MSPLAT_EXCHANGE_WIRE_FP16 needs an RGBA32F target");
-    if (pitch_bytes < tight || pitch_bytes % bpp != 0)
+    if (!q.fits((size_t)pitch_bytes))
         return gfail(nullptr, MSPLAT_ERR_INVALID_ARG, "msplat_band_exchange: pitch %llu too small / misaligned for width %d of %zu-byte pixels",
-                     (unsigned long long)pitch_bytes, width, bpp);
+                     (unsigned long long)pitch_bytes, width, q.bpp);
     const Rccl& R = rccl();
     if (!R.ok()) return gfail(nullptr, MSPLAT_ERR_UNSUPPORTED, "msplat_band_exchange: %s", R.why.c_str());
     hipStream_t s = (hipStream_t)msplat_get_stream(ctx);
@@ -630,73 +644,59 @@ static int band_exchange_impl(msplat_ctx* ctx, void* comm, int32_t rank, int32_t
     const int wrc = msplat_stream_wait(ctx, s);
     if (wrc != MSPLAT_OK && wrc != MSPLAT_ERR_PAIR_OVERFLOW_EARLIER) return gfail(nullptr, wrc, "msplat_band_exchange: %s", msplat_last_error(ctx));
 
-    // the runs this call sends and the runs it receives: (peer, first pixel row, rows)
-    struct Run { int peer, y0, nrows; };
-    std::vector<Run> sends, recvs;
+    // the runs this call sends (an owner: its own, to the root), then from nsend on the runs it receives (the root: every other rank's);
+    // loopback (tests, one rank): this rank plays owner and root at once -- its runs travel from src to dst through ncclSend / ncclRecv to itself
+    std::vector<Run> runs;
+    size_t nsend = 0;
     int prc = MSPLAT_OK;
+    auto add = [&](int32_t r, int peer) { if (!prc) prc = append_runs(kind, block_rows, world, r, height, peer, &runs); return runs.size(); };
     if (loopback) {
-        // (tests, one rank: this rank plays owner and root at once -- its runs travel from src to dst through ncclSend / ncclRecv to itself)
-        prc = for_each_run(kind, block_rows, world, rank, height, [&](int y0, int nrows) -> int {
-            sends.push_back(Run{0, y0, nrows}); recvs.push_back(Run{0, y0, nrows}); return MSPLAT_OK; });
-    } else if (rank == root) {
-        for (int32_t r = 0; r < world && prc == MSPLAT_OK; ++r)
-            if (r != root) prc = for_each_run(kind, block_rows, world, r, height, [&](int y0, int nrows) -> int { recvs.push_back(Run{r, y0, nrows}); return MSPLAT_OK; });
+        nsend = add(rank, 0);
+        add(rank, 0);
+    } else if (rank != root) {
+        nsend = add(rank, root);
     } else {
-        prc = for_each_run(kind, block_rows, world, rank, height, [&](int y0, int nrows) -> int { sends.push_back(Run{root, y0, nrows}); return MSPLAT_OK; });
+        for (int32_t r = 0; r < world; ++r)
+            if (r != root) add(r, r);
     }
     if (prc) return gfail(nullptr, prc, "msplat_band_exchange: %s", msplat_last_error(nullptr));
 
     // fp16 on the wire: a run is packed into (and received into) stream-ordered scratch; half the bytes cross the link
     char* scratch = nullptr;
-    std::vector<size_t> soff(sends.size()), roff(recvs.size());
+    std::vector<size_t> woff(runs.size());
     if (wire16) {
         size_t total = 0;
-        for (size_t i = 0; i < sends.size(); ++i) { soff[i] = total; total += (size_t)sends[i].nrows * width * 8; }
-        for (size_t i = 0; i < recvs.size(); ++i) { roff[i] = total; total += (size_t)recvs[i].nrows * width * 8; }
+        for (size_t i = 0; i < runs.size(); ++i) { woff[i] = total; total += (size_t)runs[i].nrows * width * 8; }
         if (total != 0 && hipMallocAsync((void**)&scratch, total, s) != hipSuccess) {
             (void)hipGetLastError();
             return gfail(nullptr, MSPLAT_ERR_HIP, "msplat_band_exchange: no memory for %zu bytes of fp16 rows", total);
         }
-        for (size_t i = 0; i < sends.size(); ++i) {
-            const size_t px = (size_t)sends[i].nrows * width;
-            hipLaunchKernelGGL(pack_rows_f16, dim3((unsigned)std::min<size_t>((px + 255) / 256, 4096)), dim3(256), 0, s,
-                               (const char*)src + (size_t)sends[i].y0 * pitch_bytes, (size_t)pitch_bytes, width, sends[i].nrows,
-                               (uint2*)(scratch + soff[i]));
-        }
+        for (size_t i = 0; i < nsend; ++i)
+            hipLaunchKernelGGL(pack_rows_f16, rows_grid(width, runs[i].nrows), dim3(256), 0, s, (const char*)src + (size_t)runs[i].y0 * pitch_bytes,
+                               (size_t)pitch_bytes, width, runs[i].nrows, (uint2*)(scratch + woff[i]));
     }
     // a run travels as ONE message when the rows are tight (pitch == width x pixel size: the usual case), else row by row inside
     // the same group: nothing outside the target's own pixels is read or written -- a target that is a window of a wider
     // surface keeps its neighbours, and the last row need not be followed by a full pitch; or as tight fp16 rows
-    const bool tight_rows = (size_t)pitch_bytes == tight;
-    auto post = [&](bool send, const Run& r, size_t scratch_off) -> int {
-        if (wire16)
-            return send ? R.Send(scratch + scratch_off, (size_t)r.nrows * width * 8, kNcclUint8, r.peer, comm, s)
-                        : R.Recv(scratch + scratch_off, (size_t)r.nrows * width * 8, kNcclUint8, r.peer, comm, s);
-        const int ops = tight_rows ? 1 : r.nrows;
-        const size_t bytes = tight_rows ? (size_t)r.nrows * tight : tight;
-        for (int k = 0; k < ops; ++k) {
-            const size_t off = (size_t)(r.y0 + k) * (size_t)pitch_bytes;
-            const int e = send ? R.Send((const char*)src + off, bytes, kNcclUint8, r.peer, comm, s)
-                               : R.Recv((char*)dst + off, bytes, kNcclUint8, r.peer, comm, s);
-            if (e != 0) return e;
-        }
-        return 0;
-    };
-    int nrc = R.GroupStart();
-    if (nrc == 0) {
-        for (size_t i = 0; i < sends.size() && nrc == 0; ++i) nrc = post(true, sends[i], wire16 ? soff[i] : 0);
-        for (size_t i = 0; i < recvs.size() && nrc == 0; ++i) nrc = post(false, recvs[i], wire16 ? roff[i] : 0);
-        const int erc = R.GroupEnd();
-        if (nrc == 0) nrc = erc;
-    }
+    const bool tight_rows = (size_t)pitch_bytes == q.tight;
+    const int nrc = post_group(R, runs, [&](const Run& r, size_t i) -> int {
+        const bool send = i < nsend;          // (a send reads from `from`, a receive writes to `to`)
+        auto post = [&](const void* from, void* to, size_t bytes) {
+            return send ? R.Send(from, bytes, kNcclUint8, r.peer, comm, s) : R.Recv(to, bytes, kNcclUint8, r.peer, comm, s);
+        };
+        if (wire16) return post(scratch + woff[i], scratch + woff[i], (size_t)r.nrows * width * 8);
+        const size_t off = (size_t)r.y0 * (size_t)pitch_bytes;
+        if (tight_rows) return post((const char*)src + off, (char*)dst + off, (size_t)r.nrows * q.tight);
+        int e = 0;
+        for (int k = 0; k < r.nrows && e == 0; ++k)
+            e = post((const char*)src + off + k * (size_t)pitch_bytes, (char*)dst + off + k * (size_t)pitch_bytes, q.tight);
+        return e;
+    });
     if (wire16) {
         if (nrc == 0)
-            for (size_t i = 0; i < recvs.size(); ++i) {
-                const size_t px = (size_t)recvs[i].nrows * width;
-                hipLaunchKernelGGL(unpack_rows_f16, dim3((unsigned)std::min<size_t>((px + 255) / 256, 4096)), dim3(256), 0, s,
-                                   (const uint2*)(scratch + roff[i]), (char*)dst + (size_t)recvs[i].y0 * pitch_bytes, (size_t)pitch_bytes,
-                                   width, recvs[i].nrows);
-            }
+            for (size_t i = nsend; i < runs.size(); ++i)
+                hipLaunchKernelGGL(unpack_rows_f16, rows_grid(width, runs[i].nrows), dim3(256), 0, s, (const uint2*)(scratch + woff[i]),
+                                   (char*)dst + (size_t)runs[i].y0 * pitch_bytes, (size_t)pitch_bytes, width, runs[i].nrows);
         if (scratch) (void)hipFreeAsync(scratch, s);
         if (hipGetLastError() != hipSuccess) return gfail(nullptr, MSPLAT_ERR_HIP, "msplat_band_exchange: a pack / unpack launch failed");
     }
@@ -719,7 +719,6 @@ int msplat_debug_band_exchange_loopback(msplat_ctx* ctx, void* comm, int32_t kin
 
 int msplat_group_synchronize(msplat_group* g)
 {
-    if (!g) return gfail(nullptr, MSPLAT_ERR_INVALID_ARG, "group is NULL");
     return for_all(g, [&](uint32_t i) { return msplat_synchronize(g->ctx[i]); });
 }
 

@@ -49,6 +49,24 @@ def _storage_kind(name):
     return _capi.CLOUD_STORAGES[name]
 
 
+def _aos_upload(cloud):
+    """(N, 25|61) float32 array in the reference AoS layout -> (the array, the arguments of msplat[_group]_upload_cloud after the handle)"""
+    aos = np.ascontiguousarray(cloud, np.float32)
+    assert aos.shape[1] in (25, 61)
+    off = _capi.AttrOffsets(0, 16, 32, 48, 64, 76, 88, 100, 116, 132, 148, 164, 180, 196, 212, 228)
+    return aos, (aos.ctypes.data, aos.shape[0], aos.shape[1] * 4, C.byref(off), 1 if aos.shape[1] == 61 else 0)
+
+
+def _host_frame(fb_format, vp, out=None):
+    """the (H, W, 4) host array a Render into host memory fills: `out` checked, or a new one"""
+    W, H = int(vp[2]), int(vp[3])
+    dt = np.float16 if fb_format == _capi.FB_RGBA16F else np.float32
+    if out is None:
+        out = np.zeros((H, W, 4), dt)
+    assert out.dtype == dt and out.shape == (H, W, 4) and out.flags["C_CONTIGUOUS"]
+    return out
+
+
 class SplatRenderer:
     def __init__(self, device=0, fb_format="fp32", t_epsilon=-1.0, pair_capacity=0, stream=None,
                  enable_timing=False, frames_in_flight=1, rank_mode=_capi.RANK_AUTO, frame_mode=None,
@@ -109,13 +127,9 @@ class SplatRenderer:
         if isinstance(gaussianCloud, GaussianCloud):
             rc = self._lib.msplat_upload_gaussian_cloud(self._ctx, gaussianCloud.handle)
             self._n = gaussianCloud.GetNumGaussians()
-        else:   # (N, 25|61) float32 array in the reference AoS layout
-            aos = np.ascontiguousarray(gaussianCloud, np.float32)
-            full = aos.shape[1] == 61
-            assert aos.shape[1] in (25, 61)
-            off = _capi.AttrOffsets(0, 16, 32, 48, 64, 76, 88, 100, 116, 132, 148, 164, 180, 196, 212, 228)
-            rc = self._lib.msplat_upload_cloud(self._ctx, aos.ctypes.data, aos.shape[0], aos.shape[1] * 4,
-                                               C.byref(off), 1 if full else 0)
+        else:
+            aos, args = _aos_upload(gaussianCloud)
+            rc = self._lib.msplat_upload_cloud(self._ctx, *args)
             self._n = aos.shape[0]
         if rc != _capi.OK:
             self._err = self._lib.msplat_last_error(self._ctx).decode()
@@ -213,16 +227,11 @@ class SplatRenderer:
         out=ndarray   -> filled in place
         out_ptr=int   -> device pointer (e.g. torch tensor .data_ptr()); asynchronous on the stream"""
         c, p, v, nf = self._args.load(cameraMat, projMat, viewport, nearFar)
-        vp = self._args.vp
         if out_ptr is not None:
             _capi.check(self._ctx, self._lib.msplat_render(self._ctx, c, p, v, nf, C.c_void_p(out_ptr),
                                                            pitch_bytes, 1))
             return None
-        W, H = int(vp[2]), int(vp[3])
-        dt = np.float16 if self._fb_format == _capi.FB_RGBA16F else np.float32
-        if out is None:
-            out = np.zeros((H, W, 4), dt)
-        assert out.dtype == dt and out.shape == (H, W, 4) and out.flags["C_CONTIGUOUS"]
+        out = _host_frame(self._fb_format, self._args.vp, out)
         _capi.check(self._ctx, self._lib.msplat_render(self._ctx, c, p, v, nf, out.ctypes.data, 0, 0))
         return out
 
@@ -239,9 +248,7 @@ class SplatRenderer:
             _capi.check(self._ctx, self._lib.msplat_render_stereo(self._ctx, c0, p0, c1, p1, v, nf, C.c_void_p(out_ptrs[0]),
                                                                   C.c_void_p(out_ptrs[1]), pitch_bytes, 1))
             return None
-        W, H = int(a0.vp[2]), int(a0.vp[3])
-        dt = np.float16 if self._fb_format == _capi.FB_RGBA16F else np.float32
-        outs = [np.zeros((H, W, 4), dt), np.zeros((H, W, 4), dt)]
+        outs = [_host_frame(self._fb_format, a0.vp), _host_frame(self._fb_format, a0.vp)]
         _capi.check(self._ctx, self._lib.msplat_render_stereo(self._ctx, c0, p0, c1, p1, v, nf, outs[0].ctypes.data,
                                                               outs[1].ctypes.data, 0, 0))
         return outs
@@ -473,6 +480,7 @@ class SplatRendererGroup:
         self._layout, self._block_rows, self._band_cull = layout, int(block_rows), bool(band_cull)
         self._timing = enable_timing
         self._err = ""
+        self._gerr = self._lib.msplat_group_last_error      # the error getter of _capi.check for a group handle
 
     def __del__(self):
         self.close()
@@ -484,14 +492,6 @@ class SplatRendererGroup:
 
     def last_error(self):
         return self._lib.msplat_group_last_error(self._g).decode() if self._g else self._err
-
-    def _check(self, rc):
-        if rc == _capi.ERR_PAIR_OVERFLOW_EARLIER:
-            import warnings
-            warnings.warn(_capi.EarlierFrameOverflow(self._lib.msplat_group_last_error(self._g).decode()), stacklevel=3)
-            return
-        if rc != _capi.OK:
-            raise _capi.MsplatError(rc, self._lib.msplat_group_last_error(self._g).decode())
 
     def Init(self, gaussianCloud, isFramebufferSRGBEnabled=False, useRgcSortOverride=False):
         del useRgcSortOverride
@@ -509,17 +509,14 @@ class SplatRendererGroup:
             self._err = self._lib.msplat_group_last_error(None).decode()
             return False
         self._g = g
-        self._check(self._lib.msplat_group_set_layout(g, _capi.BAND_KINDS[self._layout], self._block_rows))
-        self._check(self._lib.msplat_group_set_band_cull(g, 1 if self._band_cull else 0))
-        self._check(self._lib.msplat_group_set_cloud_storage(g, self._storage))
+        _capi.check(self._g, self._lib.msplat_group_set_layout(g, _capi.BAND_KINDS[self._layout], self._block_rows), self._gerr)
+        _capi.check(self._g, self._lib.msplat_group_set_band_cull(g, 1 if self._band_cull else 0), self._gerr)
+        _capi.check(self._g, self._lib.msplat_group_set_cloud_storage(g, self._storage), self._gerr)
         if isinstance(gaussianCloud, GaussianCloud):
             rc = self._lib.msplat_group_upload_gaussian_cloud(g, gaussianCloud.handle)
         else:
-            aos = np.ascontiguousarray(gaussianCloud, np.float32)
-            assert aos.shape[1] in (25, 61)
-            off = _capi.AttrOffsets(0, 16, 32, 48, 64, 76, 88, 100, 116, 132, 148, 164, 180, 196, 212, 228)
-            rc = self._lib.msplat_group_upload_cloud(g, aos.ctypes.data, aos.shape[0], aos.shape[1] * 4, C.byref(off),
-                                                     1 if aos.shape[1] == 61 else 0)
+            aos, args = _aos_upload(gaussianCloud)       # (aos: the memory args points into, kept until the call returns)
+            rc = self._lib.msplat_group_upload_cloud(g, *args)
         if rc != _capi.OK:
             self._err = self._lib.msplat_group_last_error(g).decode()
             return False
@@ -544,33 +541,28 @@ class SplatRendererGroup:
 
     def Sort(self, cameraMat, projMat, viewport, nearFar):
         c, p, v, nf = self._args.load(cameraMat, projMat, viewport, nearFar)
-        self._check(self._lib.msplat_group_sort(self._g, c, p, v, nf))
+        _capi.check(self._g, self._lib.msplat_group_sort(self._g, c, p, v, nf), self._gerr)
 
     def Render(self, cameraMat, projMat, viewport, nearFar, out=None, out_ptr=None, pitch_bytes=0):
         """out_ptr: device pointer ON devices[0] (asynchronous; synchronize() or wait on context 0's stream);
         otherwise a host array is filled / returned"""
         c, p, v, nf = self._args.load(cameraMat, projMat, viewport, nearFar)
-        vp = self._args.vp
         if out_ptr is not None:
-            self._check(self._lib.msplat_group_render(self._g, c, p, v, nf, C.c_void_p(out_ptr), pitch_bytes, 1))
+            _capi.check(self._g, self._lib.msplat_group_render(self._g, c, p, v, nf, C.c_void_p(out_ptr), pitch_bytes, 1), self._gerr)
             return None
-        W, H = int(vp[2]), int(vp[3])
-        dt = np.float16 if self._fb_format == _capi.FB_RGBA16F else np.float32
-        if out is None:
-            out = np.zeros((H, W, 4), dt)
-        assert out.dtype == dt and out.shape == (H, W, 4) and out.flags["C_CONTIGUOUS"]
-        self._check(self._lib.msplat_group_render(self._g, c, p, v, nf, out.ctypes.data, 0, 0))
+        out = _host_frame(self._fb_format, self._args.vp, out)
+        _capi.check(self._g, self._lib.msplat_group_render(self._g, c, p, v, nf, out.ctypes.data, 0, 0), self._gerr)
         return out
 
     def synchronize(self):
-        self._check(self._lib.msplat_group_synchronize(self._g))
+        _capi.check(self._g, self._lib.msplat_group_synchronize(self._g), self._gerr)
 
     EXCHANGES = ("peer_store", "rccl", "copy")      # MSPLAT_EXCHANGE_*
 
     def set_exchange(self, name):
         """how the other devices' rows reach devices[0]'s framebuffer: "peer_store" (default), "rccl" (ncclSend / ncclRecv over
         communicators from ncclCommInitAll) or "copy" (hipMemcpy2DAsync per run)"""
-        self._check(self._lib.msplat_group_set_exchange(self._g, self.EXCHANGES.index(name)))
+        _capi.check(self._g, self._lib.msplat_group_set_exchange(self._g, self.EXCHANGES.index(name)), self._gerr)
 
     def exchange(self):
         """the exchange the latest device-output Render used"""
