@@ -28,8 +28,7 @@ enum {
     MSPLAT_ERR_UNSUPPORTED = -6,   /* more than 2^24 splats, viewport beyond 8192 x 8192 */
     MSPLAT_ERR_PAIR_OVERFLOW = -7, /* (splat, bin) pair buffer too small, see msplat_render */
     MSPLAT_ERR_IO = -8,            /* PLY / JSON / image open or parse failure */
-    MSPLAT_ERR_PAIR_OVERFLOW_EARLIER = -9  /* a WARNING: this call did its work, but an earlier device-output render of the
-                                      context had overflowed the pair buffer (that frame lacks splats; the buffer has grown) */
+    MSPLAT_ERR_PAIR_OVERFLOW_EARLIER = -9  /* a WARNING: this call did its work, but an earlier device-output render had overflowed the pair buffer (that frame lacks splats; the buffer has grown) */
 };
 
 enum { MSPLAT_FB_RGBA32F = 0, MSPLAT_FB_RGBA16F = 1 };
@@ -38,8 +37,9 @@ enum { MSPLAT_TWO_PASS_AUTO = 0, MSPLAT_TWO_PASS_ON = 1, MSPLAT_TWO_PASS_OFF = 2
 enum { MSPLAT_SPATIAL_AUTO = 0, MSPLAT_SPATIAL_ON = 1, MSPLAT_SPATIAL_OFF = 2 };     /* msplat_config.spatial_order */
 enum { MSPLAT_FRAMES_AUTO = 0, MSPLAT_FRAMES_SERIAL = 1, MSPLAT_FRAMES_IN_FLIGHT = 2 }; /* msplat_config.frame_mode */
 enum { MSPLAT_RANK_AUTO = 0, MSPLAT_RANK_BALLOT = 1 };                               /* msplat_config.rank_mode */
-/* msplat_config.cu_partition: every CU, or the even / odd CU positions of every XCD (4 frames in flight alternate: +3-5 %) */
-enum { MSPLAT_CU_ALL = 0, MSPLAT_CU_EVEN = 1, MSPLAT_CU_ODD = 2 };
+enum { MSPLAT_CU_ALL = 0, MSPLAT_CU_EVEN = 1, MSPLAT_CU_ODD = 2 };   /* msplat_config.cu_partition: every CU, or the even / odd CU positions
+                                                                       of every XCD (4 frames in flight alternate: +3-5 %) */
+enum { MSPLAT_TARGET_CLEAR = 0, MSPLAT_TARGET_LOAD = 1, MSPLAT_TARGET_PREMULTIPLIED = 2 };   /* msplat_set_target_mode */
 enum { MSPLAT_BANDS_CONTIGUOUS = 0, MSPLAT_BANDS_INTERLEAVED = 1, MSPLAT_BANDS_BLOCK_INTERLEAVED = 2, MSPLAT_BANDS_ROOT_WEIGHTED = 3 };
 
 typedef struct msplat_ctx msplat_ctx;
@@ -63,11 +63,9 @@ typedef struct msplat_config {
     int32_t compositor_waves;  /* persistent compositor waves per render; 0 = default */
     int32_t rank_mode;         /* MSPLAT_RANK_*: lane-ordered LDS atomics (probed at create) or ballots for the stable ranking */
     int32_t frame_mode;        /* MSPLAT_FRAMES_*: the only context working on the GPU, or one of several frames in flight */
-    int32_t spatial_order;     /* MSPLAT_SPATIAL_*: may the cloud be STORED in Morton order (chunk-level cull; ties of the sort
-                                  are then in storage order, msplat_get_storage_order) */
-    int32_t async_submit;      /* != 0: msplat_sort / device-output msplat_render return at once, a worker thread of the context
-                                  issues their launches; a queued call's failure or overflow warning is returned by the next
-                                  msplat_synchronize / msplat_stream_wait */
+    int32_t spatial_order;     /* MSPLAT_SPATIAL_*: may the cloud be STORED in Morton order (chunk-level cull; sort ties then in storage order) */
+    int32_t async_submit;      /* != 0: msplat_sort / device-output msplat_render return at once, a worker thread of the context issues their
+                                  launches; a queued call's failure or overflow warning is returned by the next msplat_synchronize / _stream_wait */
     int32_t two_pass;          /* MSPLAT_TWO_PASS_*: may a Render run as two passes with occlusion feedback (same pixels) */
     int32_t cu_partition;      /* MSPLAT_CU_*: the CUs a stream the library creates itself (stream == NULL) may use; frames in flight */
 } msplat_config;
@@ -112,9 +110,8 @@ int msplat_tile_size(void);                             /* edge of the square sc
  * cloud (host memory, n records of stride_bytes) to the device; the caller may free it afterwards. */
 int msplat_upload_cloud(msplat_ctx* ctx, const void* aos, uint64_t n, uint32_t stride_bytes,
                         const msplat_attr_offsets* off, int full_sh);
-/* GPU ingest: GaussianCloud::ImportPly's per-vertex math (gaussiancloud.cpp:254-361) as a HIP kernel over the
- * raw PLY vertex block.  Byte offsets of the float properties inside one vertex; -1 = absent (reads as 0, like
- * BinaryAttribute::Read); without all of f_rest, or with full_sh == 0, the cloud is SH degree 0 (gaussiancloud.cpp:188-205). */
+/* GPU ingest (SURVEY.md 8f-1): GaussianCloud::ImportPly's per-vertex math (gaussiancloud.cpp:254-361) as a HIP kernel over the raw PLY vertex block.
+ * Byte offsets of the float properties in one vertex; -1 = absent (reads as 0, like BinaryAttribute::Read); without all of f_rest, or full_sh == 0: SH degree 0 (:188-205). */
 typedef struct msplat_ply_layout {
     uint32_t vertex_size;
     int32_t x, y, z, f_dc[3];
@@ -138,14 +135,13 @@ int msplat_get_cloud_storage(const msplat_ctx* ctx);
  * readback stall (splatrenderer.cpp:195-204) is not reproduced. */
 int msplat_sort(msplat_ctx* ctx, const float cameraMat[16], const float projMat[16], const float viewport[4], const float nearFar[2]);
 
-/* ---- SplatRenderer::Render (splatrenderer.cpp:315-343) plus the GL pipeline behind its glDrawElements: splat_vert / _geom /
- * _frag.glsl and the blend / clear state of app.cpp:144-164.  Writes W x H RGBA (float or half), row 0 = GL bottom row,
- * alpha = 1.  out_is_device != 0: `rgba` is device memory, the call is asynchronous on the stream; else host memory, the call
- * returns after the copy.  pitch_bytes = bytes between rows (0 = tight).
- * Pair-buffer overflow: a host-output render grows the buffer and retries.  A device-output render cannot know; the NEXT
- * msplat_sort / msplat_render / msplat_synchronize of the context grows the buffer (unless pair_capacity fixed it) and reports
- * it once -- msplat_synchronize: MSPLAT_ERR_PAIR_OVERFLOW; sort / render, whose own work is done: MSPLAT_ERR_PAIR_OVERFLOW_EARLIER.
- * The frame that overflowed lacks splats in its last bin columns and should be rendered again. */
+/* ---- SplatRenderer::Render (splatrenderer.cpp:315-343) plus the GL pipeline behind its glDrawElements: splat_vert / _geom / _frag.glsl and
+ * the blend / clear state of app.cpp:144-164.  Writes W x H RGBA (float or half), row 0 = GL bottom row, alpha = 1 (msplat_set_target_mode: or
+ * over the target's contents).  out_is_device != 0: `rgba` is device memory, the call is asynchronous on the stream; else host memory, the
+ * call returns after the copy.  pitch_bytes = bytes between rows (0 = tight).
+ * Pair-buffer overflow: a host-output render grows the buffer and retries.  A device-output render cannot know; the NEXT msplat_sort /
+ * msplat_render / msplat_synchronize of the context grows the buffer (unless pair_capacity fixed it) and reports it once -- msplat_synchronize:
+ * MSPLAT_ERR_PAIR_OVERFLOW; sort / render, whose own work is done: _EARLIER.  That frame lacks splats in its last bin columns: render it again. */
 int msplat_render(msplat_ctx* ctx, const float cameraMat[16], const float projMat[16], const float viewport[4],
                   const float nearFar[2], void* rgba, uint64_t pitch_bytes, int out_is_device);
 /* the reference's VR frame -- Sort with the first eye, Render per eye (app.cpp:603-607) -- as ONE chain of launches; the same
@@ -156,20 +152,18 @@ int msplat_render_stereo(msplat_ctx* ctx, const float cameraMat0[16], const floa
 /* blocks until everything queued on the context (and issued by its worker thread) has finished */
 int msplat_synchronize(msplat_ctx* ctx);
 
-/* ---- frames in flight.  The reference queues successive frames on one GL command stream and the driver overlaps them; here
- * the overlap is explicit: one context per frame in flight (own stream and per-frame buffers), the cloud uploaded into the
- * first and attached to the others, frame k issued on context k % depth.  Bit-identical to a single context.  The shims do
- * the rotation (SetFramesInFlight).  Start the process with GPU_MAX_HW_QUEUES=8. */
+/* ---- frames in flight.  The reference queues successive frames on one GL command stream and the driver overlaps them; here the overlap is
+ * explicit: one context per frame in flight (own stream and per-frame buffers), the cloud uploaded into the first and attached to the others, frame k
+ * on context k % depth.  Bit-identical to a single context.  The shims rotate (SetFramesInFlight).  Start with GPU_MAX_HW_QUEUES=8 (INTEGRATION.md 6). */
 int msplat_attach_cloud(msplat_ctx* ctx, msplat_ctx* owner);        /* `ctx` renders `owner`'s cloud (same device), no copy */
 int msplat_stream_wait(msplat_ctx* ctx, void* stream);              /* `stream` (hipStream_t) waits for the context's work so far */
 int msplat_wait_event(msplat_ctx* ctx, void* event);                /* the context's stream waits for `event` (hipEvent_t) */
 void* msplat_get_stream(msplat_ctx* ctx);                           /* the hipStream_t the context launches on */
 int msplat_get_fb_format(const msplat_ctx* ctx);                    /* MSPLAT_FB_* the context was created with (-1: NULL) */
 
-/* ---- rows of the screen on several GPUs (no reference counterpart).  The context owns blocks of `block`
- * consecutive bin rows (msplat_tile_size() pixels; row 0 = GL bottom) starting at first_row, first_row + stride, ..., at most
- * row_count rows (0 = all).  The framebuffer handed to msplat_render is always the full image; only owned rows are written;
- * pixels are bit-identical to the unbanded frame.  msplat_set_band(mod, rem) = interleaved single rows. */
+/* ---- rows of the screen on several GPUs (SURVEY.md 8e; no reference counterpart).  The context owns blocks of `block` consecutive bin rows
+ * (msplat_tile_size() pixels; row 0 = GL bottom) starting at first_row, first_row + stride, ..., at most row_count rows (0 = all).  msplat_render
+ * is always handed the full image; only owned rows are written (and read), bit-identical to the unbanded frame.  msplat_set_band(mod, rem) = interleaved single rows. */
 int msplat_set_band(msplat_ctx* ctx, int32_t row_mod, int32_t row_rem);
 int msplat_set_band_layout(msplat_ctx* ctx, int32_t first_row, int32_t row_count, int32_t block, int32_t stride);
 /* the standard layouts (MSPLAT_BANDS_*) for rank `rank` of `world` over rows_full bin rows; host arithmetic only */
@@ -181,23 +175,21 @@ int msplat_band_plan_weighted(int32_t rows_full, int32_t world, const float* wei
 int msplat_band_root_weight(int32_t rows_full, int32_t world, double fixed_ms, double ms_per_row, double row_bytes, double link_gbps, int overlap);
 /* msplat_sort also drops splats whose footprint cannot reach an owned row (mono rendering; msplat_sort_count describes the band only) */
 int msplat_set_band_cull(msplat_ctx* ctx, int enable);
-/* The exchange, one process per GPU (the north star's "RCCL over xGMI only for the final row gather"): rank `root` posts one
- * receive per run of foreign rows straight into its framebuffer, the owners send their runs from where the compositor left
- * them, all in ONE ncclGroupStart/End, on the context's stream.  `comm` = the caller's ncclComm_t (librccl is loaded at the
- * first call: no link-time dependency), `kind` / `block_rows` = the layout every rank set with msplat_band_plan.  `rgba` =
- * device memory of `height` rows of pitch_bytes, pixels of the context's fb_format (tight rows: one message per run; else row by
- * row in the same group, so a window of a wider surface keeps its neighbours).  world == 1: nothing to do.
+/* The exchange, one process per GPU (the north star's "RCCL over xGMI only for the final row gather"): rank `root` posts one receive per run of
+ * foreign rows straight into its framebuffer, the owners send their runs from where the compositor left them, all in ONE ncclGroupStart/End, on
+ * the context's stream.  `comm` = the caller's ncclComm_t (librccl is loaded at the first call: no link-time dependency), `kind` / `block_rows` =
+ * the layout every rank set with msplat_band_plan.  `rgba` = device memory of `height` rows of pitch_bytes, pixels of the context's fb_format (tight
+ * rows: one message per run; else row by row in the same group, so a window of a wider surface keeps its neighbours).  world == 1: nothing to do.
  * flags: MSPLAT_EXCHANGE_WIRE_FP16 (RGBA32F targets only): rows cross the link as RGBA16F -- half the bytes; the gathered rows
  * then differ from the owners' by one fp16 rounding, |d| <= 2^-11 |value| (values beyond 65504 become inf), root's own rows not. */
 enum { MSPLAT_EXCHANGE_WIRE_FP16 = 1 };
 int msplat_band_exchange(msplat_ctx* ctx, void* comm, int32_t rank, int32_t world, int32_t root, int32_t kind, int32_t block_rows,
                          void* rgba, uint64_t pitch_bytes, int32_t width, int32_t height, int32_t flags);
 
-/* ---- several GPUs, ONE process: the reference's shape, a single-threaded host calling Sort / Render (app.cpp:1067-1068).
- * One context per listed device, replicated cloud, bin rows partitioned (default MSPLAT_BANDS_CONTIGUOUS).  The only exchange
- * is the row gather into `rgba` on devices[0]: peer stores from the other devices' compositors (default; no staging), RCCL
- * send / recv (msplat_group_set_exchange), or a 2-D copy where no peer mapping exists.  Context 0's stream waits for the
- * others: synchronising it, or msplat_group_synchronize, means the frame is complete.  cfg as msplat_create (device ignored). */
+/* ---- several GPUs, ONE process: the reference's shape, a single-threaded host calling Sort / Render (app.cpp:1067-1068).  One context per
+ * listed device, replicated cloud, bin rows partitioned (default MSPLAT_BANDS_CONTIGUOUS).  The only exchange is the row gather into `rgba` on
+ * devices[0]: peer stores from the other devices' compositors (default; no staging), RCCL send / recv (msplat_group_set_exchange), or a 2-D copy
+ * where no peer mapping exists.  Context 0's stream waits for the others: synchronising it, or msplat_group_synchronize, means the frame is complete.  cfg as msplat_create (device ignored). */
 enum { MSPLAT_EXCHANGE_PEER_STORE = 0, MSPLAT_EXCHANGE_RCCL = 1, MSPLAT_EXCHANGE_COPY = 2 };
 int msplat_group_create(msplat_group** out, const int32_t* devices, uint32_t n, const msplat_config* cfg);
 void msplat_group_destroy(msplat_group* g);
@@ -212,6 +204,8 @@ int msplat_group_upload_cloud(msplat_group* g, const void* aos, uint64_t n, uint
 int msplat_group_upload_gaussian_cloud(msplat_group* g, const msplat_cloud* c);
 int msplat_group_upload_ply(msplat_group* g, const char* path, int import_full_sh);
 int msplat_group_set_cloud_storage(msplat_group* g, int32_t storage);   /* msplat_set_cloud_storage on every context */
+/* msplat_set_target_mode on every context.  LOAD: MSPLAT_ERR_UNSUPPORTED (the staging exchanges hold no destination rows to blend over) */
+int msplat_group_set_target_mode(msplat_group* g, int32_t mode);
 int msplat_group_set_layout(msplat_group* g, int32_t kind, int32_t block_rows);
 int msplat_group_set_band_cull(msplat_group* g, int enable);
 int msplat_group_sort(msplat_group* g, const float cameraMat[16], const float projMat[16], const float viewport[4],
@@ -222,8 +216,7 @@ int msplat_group_synchronize(msplat_group* g);
 
 /* ---- results of the latest Sort / Render (these synchronise) ---- */
 int msplat_sort_count(msplat_ctx* ctx, uint32_t* v);            /* sortCount (splatrenderer.cpp:198-199) */
-/* the element buffer of splatrenderer.cpp:296-311: upload indices of the visible splats in draw order (ascending key = far to
- * near; equal keys in ascending storage slot) */
+/* the element buffer of splatrenderer.cpp:296-311: upload indices of the visible splats in draw order (ascending key = far to near; ties by storage slot) */
 int msplat_get_sorted_indices(msplat_ctx* ctx, uint32_t* dst, uint32_t cap);
 int msplat_get_sorted_keys(msplat_ctx* ctx, uint32_t* dst, uint32_t cap);
 /* dst[slot] = upload index (identity unless the cloud was reordered; *reordered says which); dst may be NULL */
@@ -231,13 +224,22 @@ int msplat_get_storage_order(msplat_ctx* ctx, uint32_t* dst, uint64_t cap, int* 
 int msplat_get_stats(msplat_ctx* ctx, msplat_stats* out);
 int msplat_get_timings(msplat_ctx* ctx, msplat_timings* out);
 
-/* ---- what the GL app's render target does (for callers who diff against its pixels; draw-order walk, several times slower).
- * Depth test: GL_DEPTH_TEST is on (app.cpp:163) and live wherever the target has a depth attachment (default
- * back buffer, 24 bits, sdl_main.cpp:79; XR swapchains); bits = 0 (default) models the colour-only --fp16 / --fp32 FBO.
- * Target rounding (SURVEY.md 8a-12, app.cpp:1012-1020): the RGBA8 back buffer clamps and stores 8-bit unorm after EVERY blend,
- * the --fp16 target rounds to fp16 after every blend; MSPLAT_ROP_NONE (default) accumulates in fp32 and rounds once. */
+/* ---- what the GL app's render target does (for callers who diff against its pixels; draw-order walk, several times slower).  Depth test
+ * (SURVEY.md 8f-4): GL_DEPTH_TEST is on (app.cpp:163) and live wherever the target has a depth attachment (default back buffer, 24 bits,
+ * sdl_main.cpp:79; XR swapchains); bits = 0 (default) models the colour-only --fp16 / --fp32 FBO.  Target rounding (SURVEY.md 8a-12, app.cpp:1012-1020):
+ * the RGBA8 back buffer clamps and stores 8-bit unorm after EVERY blend, --fp16 rounds to fp16 after every blend; MSPLAT_ROP_NONE (default): fp32, rounded once. */
 int msplat_set_depth_test(msplat_ctx* ctx, int depth_bits);
 int msplat_set_target_emulation(msplat_ctx* ctx, int rop);
+/* ---- the target's contents: the reference never clears in Render; it blends (GL_ONE, GL_ONE_MINUS_SRC_ALPHA, app.cpp:154-156) over what app.cpp drew
+ * before.  For the following msplat_render / _stereo of the context, per pixel with C = the splats' premultiplied colour and T = the transmittance WHERE
+ * THE WALK STOPPED (early termination leaves it below t_epsilon, not at its limit: an error <= t_epsilon |dst|; t_epsilon = 0 removes it):
+ * CLEAR (default) writes (C, 1); PREMULTIPLIED (C, 1 - T), that blend over a target cleared to (0,0,0,0), a layer for a compositor; LOAD reads dst, the
+ * pixel `rgba` holds (host output: the caller's array), and writes rgb = fma(T, dst.rgb, C), a = fma(T, dst.a - 1, 1) -- RGBA16F: read as half, blended
+ * in fp32, rounded once; a pixel no splat reaches (T == 1) keeps its bits; dst lies behind every splat (also under msplat_set_depth_test).  LOAD is not idempotent: after MSPLAT_ERR_PAIR_OVERFLOW[_EARLIER]
+ * a device-output caller restores dst before rendering the frame again.  Banded contexts read and write owned rows only.  MSPLAT_ERR_UNSUPPORTED, at
+ * whichever call comes second: a non-CLEAR mode with a target emulation != MSPLAT_ROP_NONE, a point cloud, or (at the Render) msplat_set_tile_probe. */
+int msplat_set_target_mode(msplat_ctx* ctx, int32_t mode);
+int msplat_get_target_mode(const msplat_ctx* ctx);          /* -1: NULL */
 
 /* ---- scene data: GaussianCloud / Ply (gaussiancloud.h:17-91, ply.h:19-46) ---- */
 msplat_cloud* msplat_cloud_create(int import_full_sh);          /* GaussianCloud::GaussianCloud(Options{importFullSH}) */
@@ -264,16 +266,14 @@ int msplat_cameras_floor_plane(const char* path, float normal_out[3], float pos_
 int msplat_vrconfig_import_json(const char* path, float floor_mat_out[16]);                /* VrConfig (vrconfig.cpp:20-65) */
 int msplat_vrconfig_export_json(const char* path, const float floor_mat[16]);
 int msplat_find_config_file(const char* ply_path, const char* config_name, char* out, uint32_t cap);   /* app.cpp:89-119 */
-/* W x H float RGBA (row 0 = bottom) -> 8-bit ".ppm" / PNG, top row first: clamp + round like an RGBA8 target, optional
- * LinearToSRGB (util.cpp:357-367) */
+/* W x H float RGBA (row 0 = bottom) -> 8-bit ".ppm" / PNG, top row first: clamp + round like an RGBA8 target, optional LinearToSRGB (util.cpp:357-367) */
 int msplat_write_image(const char* path, const float* rgba, int width, int height, int encode_srgb);
 /* 8-bit non-interlaced PNG (what Image::Load accepts, core/image.cpp:72-101) -> RGBA8, top row first; NULL queries the size */
 int msplat_read_image(const char* path, uint8_t* rgba8_out, uint64_t cap, uint32_t* width_out, uint32_t* height_out);
 
-/* ---- point-cloud renderer: PointCloud (pointcloud.h:15-48) + PointRenderer (pointrenderer.h:23-57,
- * pointrenderer.cpp:48-196).  A context holds EITHER a splat cloud or a point cloud; with points, msplat_sort is the same
- * presort + radix sort and msplat_render the sprite pipeline (point_*.glsl + the blend state of app.cpp:153-156):
- * PointRenderer::Render == msplat_sort + msplat_render with the same matrices. */
+/* ---- point-cloud renderer (SURVEY.md 8f-4): PointCloud (pointcloud.h:15-48) + PointRenderer (pointrenderer.h:23-57, pointrenderer.cpp:48-196).
+ * A context holds EITHER a splat cloud or a point cloud; with points, msplat_sort is the same presort + radix sort and msplat_render the sprite
+ * pipeline (point_*.glsl + the blend state of app.cpp:153-156): PointRenderer::Render == msplat_sort + msplat_render with the same matrices. */
 msplat_points* msplat_points_create(int use_linear_colors);
 void msplat_points_destroy(msplat_points* p);
 int msplat_points_import_ply(msplat_points* p, const char* path);

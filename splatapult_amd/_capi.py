@@ -22,6 +22,9 @@ EXCHANGE_WIRE_FP16 = 1              # msplat_band_exchange flags
 CU_ALL, CU_EVEN, CU_ODD = 0, 1, 2    # msplat_config.cu_partition
 STORAGE_FP32, STORAGE_SH_FP16 = 0, 1  # msplat_set_cloud_storage: f_rest as fp32 or IEEE fp16
 CLOUD_STORAGES = {"fp32": STORAGE_FP32, "sh_fp16": STORAGE_SH_FP16}
+# msplat_set_target_mode: overwrite with (C, 1); blend over the target's contents; write the layer (C, 1 - T)
+TARGET_CLEAR, TARGET_LOAD, TARGET_PREMULTIPLIED = 0, 1, 2
+TARGET_MODES = {"clear": TARGET_CLEAR, "load": TARGET_LOAD, "premultiplied": TARGET_PREMULTIPLIED}
 # "weighted": contiguous bands, rank 0 (the gather's root) weighted block_rows PERCENT of another rank (msplat.h)
 BAND_KINDS = {"contiguous": BANDS_CONTIGUOUS, "interleaved": BANDS_INTERLEAVED, "block": BANDS_BLOCK_INTERLEAVED,
               "weighted": BANDS_ROOT_WEIGHTED}
@@ -133,6 +136,9 @@ SYMBOLS = [
     ("msplat_set_point_sprite", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]),
     ("msplat_set_depth_test", C.c_int, [C.c_void_p, C.c_int]),
     ("msplat_set_target_emulation", C.c_int, [C.c_void_p, C.c_int]),
+    ("msplat_set_target_mode", C.c_int, [C.c_void_p, C.c_int32]),
+    ("msplat_get_target_mode", C.c_int, [C.c_void_p]),
+    ("msplat_group_set_target_mode", C.c_int, [C.c_void_p, C.c_int32]),
     ("msplat_attach_cloud", C.c_int, [C.c_void_p, C.c_void_p]),
     ("msplat_stream_wait", C.c_int, [C.c_void_p, C.c_void_p]),
     ("msplat_wait_event", C.c_int, [C.c_void_p, C.c_void_p]),

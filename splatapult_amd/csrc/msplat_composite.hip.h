@@ -67,6 +67,9 @@ constexpr int kCompOcc = 5;        // occupancy bound handed to the compiler (<=
 // frame; TWO_VIEWS = both eyes in one chain; PROBE = per-item counters.  The plain frame's instantiation <F16, 0, false, false>
 // carries none of the others' registers (r4 passed them at run time on top of the ~500-byte FrameParams: 81 VGPRs / 14 SGPR spills
 // against r3's 79 / 5) and takes the eleven words of CompParams instead of five 4x4 matrices.
+// TM = MSPLAT_TARGET_* (msplat_set_target_mode): what the final store -- the one place that writes pixels -- does with the target's
+// contents.  kTargetClear: (C, 1), the code of every instantiation that existed before the parameter.  The inner loop never sees it.
+constexpr int kTargetClear = 0, kTargetLoad = 1, kTargetPremultiplied = 2;      // MSPLAT_TARGET_* (include/msplat.h)
 struct CompExtra {
     void* out1;                  // TWO_VIEWS: the second view's target (bin rows >= rows_view belong to it)
     uint32_t* fin;               // OCC != 0: per (bin, quadrant) 0xFFFFFFFF = final, else entries composited by pass 1
@@ -75,7 +78,7 @@ struct CompExtra {
     uint32_t* probe;             // PROBE: 8 words per work item
 };
 
-template <bool F16, int OCC, bool TWO_VIEWS, bool PROBE>
+template <bool F16, int OCC, bool TWO_VIEWS, bool PROBE, int TM = kTargetClear>
 __global__ __launch_bounds__(kCompThreads, kCompOcc) void composite_kernel(const uint32_t* __restrict__ tile_start,
                                                                  const uint32_t* __restrict__ pairs,
                                                                  const float4* __restrict__ rec,
@@ -379,12 +382,42 @@ __global__ __launch_bounds__(kCompThreads, kCompOcc) void composite_kernel(const
     for (int k = 0; k < NS; ++k) {
         if (inside[k] && !carry) {
             char* row = (char*)(second ? ex.out1 : out) + (size_t)(ybase + 4 * k) * pitch_bytes;
+            float4 px = make_float4(cr[k >> 1][k & 1], cg[k >> 1][k & 1], cb[k >> 1][k & 1], 1.0f);
+            if (TM != kTargetClear) {
+                // the GL blend (GL_ONE, GL_ONE_MINUS_SRC_ALPHA, app.cpp:154-156) is linear in the destination: over dst the frame is
+                // C + T dst, alpha 1 - T (1 - dst.a).  T = 2^-118 Ts is exact; the forms keep an opaque dst opaque.  The pixel is read
+                // and written once, by this lane.
+                const float t = T[k >> 1][k & 1] * 0x1p-118f;
+                if (TM == kTargetPremultiplied) {
+                    px.w = 1.0f - t;
+                } else {
+                    float4 d;
+                    if (F16) {
+                        union { _Float16 h[4]; uint2 u; } in;
+                        in.u = ((const uint2*)row)[x];
+                        d = make_float4((float)in.h[0], (float)in.h[1], (float)in.h[2], (float)in.h[3]);
+                    } else {
+                        d = ((const float4*)row)[x];
+                    }
+                    px.x = __builtin_fmaf(t, d.x, px.x);
+                    px.y = __builtin_fmaf(t, d.y, px.y);
+                    px.z = __builtin_fmaf(t, d.z, px.z);
+                    px.w = __builtin_fmaf(t, d.w - 1.0f, 1.0f);
+                    // A pixel no splat reached (t == 1: every weight was 0, so C is 0 too) is handed through as it is: the formulas
+                    // would round d.w - 1 for |d.w| < 0.5, turn -0 into +0 and -- this wave flushes fp32 denormals -- a denormal into 0
+                    if (t == 1.0f) px = d;
+                }
+                // RGBA16F: the value is rounded to fp32 and THEN to half in every mode -- left alone, the compiler may fold an fma or
+                // subtraction and the conversion into one v_fma_mixlo_f16 (a single rounding to half: LOAD over zeros then differed
+                // from PREMULTIPLIED by an fp16 ulp in a few pixels per frame)
+                if (F16) asm volatile("" : "+v"(px.x), "+v"(px.y), "+v"(px.z), "+v"(px.w));
+            }
             if (F16) {
                 union { _Float16 h[4]; uint2 u; } pk;
-                pk.h[0] = (_Float16)cr[k >> 1][k & 1]; pk.h[1] = (_Float16)cg[k >> 1][k & 1]; pk.h[2] = (_Float16)cb[k >> 1][k & 1]; pk.h[3] = (_Float16)1.0f;
+                pk.h[0] = (_Float16)px.x; pk.h[1] = (_Float16)px.y; pk.h[2] = (_Float16)px.z; pk.h[3] = (_Float16)px.w;
                 ((uint2*)row)[x] = pk.u;
             } else {
-                ((float4*)row)[x] = make_float4(cr[k >> 1][k & 1], cg[k >> 1][k & 1], cb[k >> 1][k & 1], 1.0f);
+                ((float4*)row)[x] = px;
             }
         }
     }
@@ -418,7 +451,10 @@ __device__ __forceinline__ float rop_store(float x, int rop)
     return x;
 }
 
-template <bool HALF>
+// TM (msplat_set_target_mode, MSPLAT_ROP_NONE only): kTargetLoad starts the running colour AND alpha from the target's pixel, the
+// draw-order blend then runs over it (a = w + (1 - w) a); kTargetPremultiplied starts from (0, 0, 0, 0).  The emulated depth buffer
+// is cleared to 1.0 either way: the target's contents lie behind every splat.
+template <bool HALF, int TM = kTargetClear>
 __global__ __launch_bounds__(kCompThreads) void composite_depth_kernel(const uint32_t* __restrict__ tile_start,
                                                                        const uint32_t* __restrict__ pairs,
                                                                        const float4* __restrict__ rec,
@@ -444,10 +480,26 @@ __global__ __launch_bounds__(kCompThreads) void composite_depth_kernel(const uin
             uint32_t start = tile_start[bin], end = tile_start[bin + 1];
             if (start > cap) start = cap;
             if (end > cap) end = cap;
-            float cr[4], cg[4], cb[4];
+            float cr[4], cg[4], cb[4], ca[4];
             uint32_t zbuf[4];
 #pragma unroll
-            for (int k = 0; k < 4; ++k) { cr[k] = 0.0f; cg[k] = 0.0f; cb[k] = 0.0f; zbuf[k] = 0xFFFFFFFFu; }   // cleared to 1.0
+            for (int k = 0; k < 4; ++k) { cr[k] = 0.0f; cg[k] = 0.0f; cb[k] = 0.0f; ca[k] = 0.0f; zbuf[k] = 0xFFFFFFFFu; }   // cleared to 1.0
+            if (TM == kTargetLoad) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    if (x < fp.width && ybase + 4 * k < fp.height) {
+                        const char* row = (const char*)out + (size_t)(ybase + 4 * k) * pitch_bytes;
+                        if (HALF) {
+                            union { _Float16 h[4]; uint2 u; } in;
+                            in.u = ((const uint2*)row)[x];
+                            cr[k] = (float)in.h[0]; cg[k] = (float)in.h[1]; cb[k] = (float)in.h[2]; ca[k] = (float)in.h[3];
+                        } else {
+                            const float4 d = ((const float4*)row)[x];
+                            cr[k] = d.x; cg[k] = d.y; cb[k] = d.z; ca[k] = d.w;
+                        }
+                    }
+                }
+            }
             const float X0 = (float)(tx * kTile) + 0.5f, X1 = X0 + (float)(kTile - 1);
             const float Y0 = (float)(ty * kTile) + 0.5f, Y1 = Y0 + (float)(kTile - 1);
             for (uint32_t base = start; base < end; base += kCompThreads) {      // ascending = draw order
@@ -517,6 +569,7 @@ __global__ __launch_bounds__(kCompThreads) void composite_depth_kernel(const uin
                             cr[k] = rop_store(sr + oma * cr[k], fp.rop);
                             cg[k] = rop_store(sg + oma * cg[k], fp.rop);
                             cb[k] = rop_store(sb + oma * cb[k], fp.rop);
+                            if (TM != kTargetClear) ca[k] = w + oma * ca[k];
                             zbuf[k] = zj;
                         }
                     }
@@ -527,12 +580,13 @@ __global__ __launch_bounds__(kCompThreads) void composite_depth_kernel(const uin
             for (int k = 0; k < 4; ++k) {
                 if (x < fp.width && ybase + 4 * k < fp.height) {
                     char* row = (char*)out + (size_t)(ybase + 4 * k) * pitch_bytes;
+                    const float a = TM != kTargetClear ? ca[k] : 1.0f;
                     if (HALF) {
                         union { _Float16 h[4]; uint2 u; } pk;
-                        pk.h[0] = (_Float16)cr[k]; pk.h[1] = (_Float16)cg[k]; pk.h[2] = (_Float16)cb[k]; pk.h[3] = (_Float16)1.0f;
+                        pk.h[0] = (_Float16)cr[k]; pk.h[1] = (_Float16)cg[k]; pk.h[2] = (_Float16)cb[k]; pk.h[3] = (_Float16)a;
                         ((uint2*)row)[x] = pk.u;
                     } else {
-                        ((float4*)row)[x] = make_float4(cr[k], cg[k], cb[k], 1.0f);
+                        ((float4*)row)[x] = make_float4(cr[k], cg[k], cb[k], a);
                     }
                 }
             }

@@ -180,6 +180,7 @@ struct msplat_ctx {
     Buf zq;         // uint32[N] quantised window depth per rank (only with msplat_set_depth_test)
     int depth_bits = 0;
     int rop = 0;            // render-target emulation for the draw-order compositor (msplat_set_target_emulation)
+    int target_mode = MSPLAT_TARGET_CLEAR;     // what a Render does with the target's contents (msplat_set_target_mode)
     // point-cloud mode: pos4 = positions, recs = float4 colours, sprite = float4 mip chain
     bool point_mode = false;
     Buf sprite;
@@ -673,9 +674,34 @@ int msplat_set_target_emulation(msplat_ctx* ctx, int rop)
     if (rop != MSPLAT_ROP_NONE && ctx->point_mode)
         return fail(ctx, MSPLAT_ERR_UNSUPPORTED, "msplat_set_target_emulation: the point-cloud sprite compositor has no render-target "
                     "emulation (the context holds a point cloud)");
+    if (rop != MSPLAT_ROP_NONE && ctx->target_mode != MSPLAT_TARGET_CLEAR)
+        return fail(ctx, MSPLAT_ERR_UNSUPPORTED, "msplat_set_target_emulation: per-blend rounding over a loaded or premultiplied target is "
+                    "not defined (msplat_set_target_mode is not MSPLAT_TARGET_CLEAR)");
     ctx->rop = rop;
     return MSPLAT_OK;
 }
+
+// What a Render does with the target's contents (include/msplat.h): CLEAR overwrites with (C, 1), PREMULTIPLIED writes the layer
+// (C, 1 - T), LOAD blends the frame over the pixels the target holds.  Only the compositors' final stores differ
+// (msplat_composite.hip.h, TM); a combination they are not instantiated for is refused here, at msplat_set_target_emulation, at the
+// point uploads or -- the tile probe -- by the Render.
+int msplat_set_target_mode(msplat_ctx* ctx, int32_t mode)
+{
+    drain_async(ctx);
+    if (!ctx) return fail(nullptr, MSPLAT_ERR_INVALID_ARG, "ctx is NULL");
+    if (mode != MSPLAT_TARGET_CLEAR && mode != MSPLAT_TARGET_LOAD && mode != MSPLAT_TARGET_PREMULTIPLIED)
+        return fail(ctx, MSPLAT_ERR_INVALID_ARG, "msplat_set_target_mode: mode must be MSPLAT_TARGET_CLEAR, _LOAD or _PREMULTIPLIED (got %d)", mode);
+    if (mode != MSPLAT_TARGET_CLEAR && ctx->rop != MSPLAT_ROP_NONE)
+        return fail(ctx, MSPLAT_ERR_UNSUPPORTED, "msplat_set_target_mode: per-blend rounding over a loaded or premultiplied target is not "
+                    "defined (msplat_set_target_emulation is not MSPLAT_ROP_NONE)");
+    if (mode != MSPLAT_TARGET_CLEAR && ctx->point_mode)
+        return fail(ctx, MSPLAT_ERR_UNSUPPORTED, "msplat_set_target_mode: the point-cloud sprite compositor overwrites its target (the "
+                    "context holds a point cloud)");
+    ctx->target_mode = mode;
+    return MSPLAT_OK;
+}
+
+int msplat_get_target_mode(const msplat_ctx* ctx) { return ctx ? ctx->target_mode : -1; }
 
 // Frames in flight: `ctx` renders `owner`'s cloud (no copy).  Each context keeps its own stream and
 // per-frame buffers, so consecutive frames issued round-robin over several contexts overlap on the GPU
@@ -690,6 +716,9 @@ int msplat_attach_cloud(msplat_ctx* ctx, msplat_ctx* owner)
     if (owner->device != ctx->device)
         return fail(ctx, MSPLAT_ERR_INVALID_ARG, "msplat_attach_cloud: contexts are on different devices (%d, %d)",
                     ctx->device, owner->device);
+    if (owner->point_mode && ctx->target_mode != MSPLAT_TARGET_CLEAR)
+        return fail(ctx, MSPLAT_ERR_UNSUPPORTED, "msplat_attach_cloud: the owner holds a point cloud, and the sprite compositor overwrites "
+                    "its target (msplat_set_target_mode is not MSPLAT_TARGET_CLEAR)");
     ctx->point_mode = owner->point_mode;
     int rc = prepare_cloud_buffers(ctx, owner->N, owner->full_sh, owner->store);
     if (rc) return rc;
@@ -1431,10 +1460,12 @@ static int issue_compositor(RenderChain& rc, int occ_pass, int ev_c0, int ev_c1)
     } else if (ntiles > 0 && (ctx->depth_bits != 0 || ctx->rop != 0)) {
         // emulated depth buffer: draw-order walk, no early termination
         with_flag(f16, [&](auto F16) {
-            hipLaunchKernelGGL(composite_depth_kernel<F16.value>, dim3(cgrid), dim3(kCompThreads), 0, s,
-                               (const uint32_t*)ctx->tile_start.p, (const uint32_t*)ctx->pairsB.p,
-                               (const float4*)ctx->rec2d.p, (const uint32_t*)ctx->zq.p, d_out, pitch, fp, cap,
-                               (const uint32_t*)ctx->tile_order.p, d_queue, (uint32_t)ntiles * 4u);
+            with_int<kTargetLoad, kTargetPremultiplied, kTargetClear>(ctx->target_mode, [&](auto TM) {
+                hipLaunchKernelGGL((composite_depth_kernel<F16.value, TM.value>), dim3(cgrid), dim3(kCompThreads), 0, s,
+                                   (const uint32_t*)ctx->tile_start.p, (const uint32_t*)ctx->pairsB.p,
+                                   (const float4*)ctx->rec2d.p, (const uint32_t*)ctx->zq.p, d_out, pitch, fp, cap,
+                                   (const uint32_t*)ctx->tile_order.p, d_queue, (uint32_t)ntiles * 4u);
+            });
         });
         ctx->comp_kernel_timed = false;
     } else if (ntiles > 0) {
@@ -1457,20 +1488,29 @@ static int issue_compositor(RenderChain& rc, int occ_pass, int ev_c0, int ev_c1)
         const int prio = occ_pass == 2 ? 0 : prio_mode;
         // six of the twelve (OCC, TWO_VIEWS, PROBE) forms exist per format
         // (occlusion_plan never chooses two passes for two views in one chain or while the probe is on)
-        auto composite = [&](auto OCC, auto TWO, auto PROBE) {
+        // and the four without the probe once more per non-CLEAR target mode (render_frame refuses the probe with those)
+        auto composite = [&](auto OCC, auto TWO, auto PROBE, auto TM) {
             with_flag(f16, [&](auto F16) {
-                hipExtLaunchKernelGGL((composite_kernel<F16.value, OCC.value, TWO.value, PROBE.value>), dim3(grid), dim3(kCompThreads), 0, s,
+                hipExtLaunchKernelGGL((composite_kernel<F16.value, OCC.value, TWO.value, PROBE.value, TM.value>), dim3(grid), dim3(kCompThreads), 0, s,
                                       e0, e1, 0, ts, pb, r2, d_out, pitch, cp, cap, ord, d_queue, comp_items, prio, ex);
             });
         };
         constexpr flag_t<true> yes{};
         constexpr flag_t<false> no{};
-        if (occ_pass == 1) composite(int_t<1>{}, no, no);
-        else if (occ_pass == 2) composite(int_t<2>{}, no, no);
-        else if (stereo && probe) composite(int_t<0>{}, yes, yes);
-        else if (stereo) composite(int_t<0>{}, yes, no);
-        else if (probe) composite(int_t<0>{}, no, yes);
-        else composite(int_t<0>{}, no, no);
+        constexpr int_t<kTargetClear> clear{};
+        if (ctx->target_mode != MSPLAT_TARGET_CLEAR)
+            with_int<kTargetLoad, kTargetPremultiplied>(ctx->target_mode, [&](auto TM) {
+                if (occ_pass == 1) composite(int_t<1>{}, no, no, TM);
+                else if (occ_pass == 2) composite(int_t<2>{}, no, no, TM);
+                else if (stereo) composite(int_t<0>{}, yes, no, TM);
+                else composite(int_t<0>{}, no, no, TM);
+            });
+        else if (occ_pass == 1) composite(int_t<1>{}, no, no, clear);
+        else if (occ_pass == 2) composite(int_t<2>{}, no, no, clear);
+        else if (stereo && probe) composite(int_t<0>{}, yes, yes, clear);
+        else if (stereo) composite(int_t<0>{}, yes, no, clear);
+        else if (probe) composite(int_t<0>{}, no, yes, clear);
+        else composite(int_t<0>{}, no, no, clear);
         ctx->comp_kernel_timed = timed;
     } else {
         ctx->comp_kernel_timed = false;
@@ -1586,6 +1626,32 @@ static int resolve_pitch(msplat_ctx* ctx, const char* who, const FrameParams& fp
     return MSPLAT_OK;
 }
 
+// The rows of a host image that belong to the context, between the caller's buffer and the internal framebuffer: the whole image, or
+// (band mode) only the owned bin rows -- as documented for msplat_set_band, so several bands can be assembled in one host image
+static int copy_host_rows(msplat_ctx* ctx, const FrameParams& fp, void* rgba, uint64_t pitch_bytes, size_t tight, bool to_host)
+{
+    auto copy = [&](int y0, int rows) {
+        char* host = (char*)rgba + (size_t)y0 * pitch_bytes;
+        char* dev = (char*)ctx->fb.p + (size_t)y0 * tight;
+        return to_host ? hipMemcpy2D(host, pitch_bytes, dev, tight, tight, rows, hipMemcpyDeviceToHost)
+                       : hipMemcpy2DAsync(dev, tight, host, pitch_bytes, tight, rows, hipMemcpyHostToDevice, ctx->stream);
+    };
+    if (!ctx->banded) {
+        HIP_TRY(ctx, copy(0, fp.height));
+        return MSPLAT_OK;
+    }
+    for (int vy = 0; vy < fp.tiles_y;) {
+        const int y0 = band_real_row(fp, vy) * kBin;
+        int run = 1;                  // consecutive owned rows travel in one copy
+        while (vy + run < fp.tiles_y && band_real_row(fp, vy + run) == band_real_row(fp, vy) + run) ++run;
+        vy += run;
+        const int rows = std::min(kBin * run, fp.height - y0);
+        if (rows <= 0) break;
+        HIP_TRY(ctx, copy(y0, rows));
+    }
+    return MSPLAT_OK;
+}
+
 // host output: render into an internal device framebuffer, copy back, grow the pair buffer on overflow
 static int render_to_host(msplat_ctx* ctx, const FrameParams& fp, void* rgba, uint64_t pitch_bytes, size_t tight)
 {
@@ -1593,31 +1659,15 @@ static int render_to_host(msplat_ctx* ctx, const FrameParams& fp, void* rgba, ui
     if ((rc = buf_alloc(ctx, ctx->fb, tight * fp.height))) return rc;
     RenderPlan plan;
     for (int attempt = 0; attempt < 6; ++attempt) {
+        // MSPLAT_TARGET_LOAD: the caller's rows are the destination -- before EVERY attempt, because blending over the target is
+        // not idempotent: a retry would otherwise run over the half-blended frame of the attempt that overflowed
+        if (ctx->target_mode == MSPLAT_TARGET_LOAD && (rc = copy_host_rows(ctx, fp, rgba, pitch_bytes, tight, false))) return rc;
         rc = launch_render(ctx, fp, ctx->fb.p, tight, false, nullptr, &plan);
         if (rc) return rc;
         uint32_t cnt[4];
         HIP_TRY(ctx, hipMemcpyAsync(cnt, ctx->counters.p, sizeof(cnt), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        if (cnt[2] == 0) {
-            if (ctx->banded) {
-                // band mode: only the owned bin rows are written to the caller's buffer (as documented for
-                // msplat_set_band), so several bands can be assembled in one host image
-                for (int vy = 0; vy < fp.tiles_y;) {
-                    const int y0 = band_real_row(fp, vy) * kBin;
-                    int run = 1;                  // consecutive owned rows leave in one copy
-                    while (vy + run < fp.tiles_y && band_real_row(fp, vy + run) == band_real_row(fp, vy) + run) ++run;
-                    vy += run;
-                    const int rows = std::min(kBin * run, fp.height - y0);
-                    if (rows <= 0) break;
-                    HIP_TRY(ctx, hipMemcpy2D((char*)rgba + (size_t)y0 * pitch_bytes, pitch_bytes,
-                                             (const char*)ctx->fb.p + (size_t)y0 * tight, tight, tight, rows,
-                                             hipMemcpyDeviceToHost));
-                }
-            } else {
-                HIP_TRY(ctx, hipMemcpy2D(rgba, pitch_bytes, ctx->fb.p, tight, tight, fp.height, hipMemcpyDeviceToHost));
-            }
-            return MSPLAT_OK;
-        }
+        if (cnt[2] == 0) return copy_host_rows(ctx, fp, rgba, pitch_bytes, tight, true);
         // overflow: cnt[2] holds the required pair count
         const uint64_t need = (uint64_t)cnt[2] + (cnt[2] >> 2) + 1024;
         if (ctx->cfg.pair_capacity != 0 || need > 0x7FFFFFFFull)
@@ -1636,6 +1686,9 @@ static int render_frame(msplat_ctx* ctx, const FrameParams& fp, void* rgba, void
     ctx->last_fp = fp;
     if (ctx->tables_dirty && (rc = clear_frame_tables(ctx))) return rc;
     if (ctx->point_mode && !ctx->sprite.p && (rc = build_sprite(ctx, nullptr, 0, 0))) return rc;   // built-in sphere sprite
+    // (no compositor instantiation counts per work item AND reads the target: refused, never rendered as MSPLAT_TARGET_CLEAR)
+    if (ctx->target_mode != MSPLAT_TARGET_CLEAR && ctx->probe_on)
+        return fail(ctx, MSPLAT_ERR_UNSUPPORTED, "msplat_render: the tile probe (msplat_set_tile_probe) exists for MSPLAT_TARGET_CLEAR only");
     return with_pending_overflow(ctx, [&] {      // an EARLIER frame; this one is still rendered
         const int r = out_is_device ? launch_render(ctx, fp, rgba, pitch_bytes, true, rgba1)
                                     : render_to_host(ctx, fp, rgba, pitch_bytes, tight);

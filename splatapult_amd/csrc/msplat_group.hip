@@ -555,6 +555,23 @@ int msplat_group_set_cloud_storage(msplat_group* g, int32_t storage)
     return MSPLAT_OK;
 }
 
+// msplat_set_target_mode on every context.  PREMULTIPLIED reads nothing and works with every exchange; LOAD is refused: the staging
+// exchanges (copy, RCCL) render a rank's rows into a framebuffer of its own, which holds no destination rows to blend over.
+int msplat_group_set_target_mode(msplat_group* g, int32_t mode)
+{
+    GROUP_OR_FAIL(g);
+    if (mode != MSPLAT_TARGET_CLEAR && mode != MSPLAT_TARGET_LOAD && mode != MSPLAT_TARGET_PREMULTIPLIED)
+        return gfail(g, MSPLAT_ERR_INVALID_ARG, "msplat_group_set_target_mode: unknown mode %d", mode);
+    if (mode == MSPLAT_TARGET_LOAD)
+        return gfail(g, MSPLAT_ERR_UNSUPPORTED, "msplat_group_set_target_mode: MSPLAT_TARGET_LOAD is not available on a group (a rank "
+                     "that stages its rows has no destination rows to blend over); MSPLAT_TARGET_PREMULTIPLIED is");
+    for (msplat_ctx* c : g->ctx) {
+        const int rc = msplat_set_target_mode(c, mode);
+        if (rc) return gfail(g, rc, "%s", msplat_last_error(c));
+    }
+    return MSPLAT_OK;
+}
+
 int msplat_group_set_layout(msplat_group* g, int32_t kind, int32_t block_rows)
 {
     GROUP_OR_FAIL(g);

@@ -474,6 +474,9 @@ int msplat_upload_points(msplat_ctx* ctx, const void* aos, uint64_t n, uint32_t 
     if (ctx->rop != MSPLAT_ROP_NONE)
         return fail(ctx, MSPLAT_ERR_UNSUPPORTED, "msplat_upload_points: render-target emulation is set on this context and the "
                     "sprite compositor has none (msplat_set_target_emulation(ctx, MSPLAT_ROP_NONE) first)");
+    if (ctx->target_mode != MSPLAT_TARGET_CLEAR)
+        return fail(ctx, MSPLAT_ERR_UNSUPPORTED, "msplat_upload_points: a target mode is set on this context and the sprite compositor "
+                    "overwrites its target (msplat_set_target_mode(ctx, MSPLAT_TARGET_CLEAR) first)");
     ctx->point_mode = true;
     int rc = prepare_cloud_buffers(ctx, n, false, nullptr);
     if (rc) { ctx->point_mode = false; return rc; }

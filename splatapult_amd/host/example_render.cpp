@@ -3,10 +3,12 @@
 // Sort + Render into an explicit RGBA32F framebuffer, dumped as a binary PPM-like float file.
 //
 //   g++ -std=c++17 -I. splatapult_amd/host/example_render.cpp -Lsplatapult_amd/lib -lmsplat -o example_render
-//   ./example_render scene.ply out.f32 [width height] [--nosh] [--frames-in-flight N] [--devices 0,1,2,...]
+//   ./example_render scene.ply out.f32 [width height] [--nosh] [--frames-in-flight N] [--devices 0,1,2,...] [--over-gradient]
 // With --frames-in-flight N the same frame is issued N + 1 times round-robin over N contexts that share the cloud
 // (SplatRenderer::SetFramesInFlight); the last one is written.  With --devices the frame's bin rows are dealt to the
-// listed GPUs (SplatRenderer::ConfigureDevices, msplat_group_*): same pixels.
+// listed GPUs (SplatRenderer::ConfigureDevices, msplat_group_*): same pixels.  With --over-gradient the target is first filled with
+// a vertical gradient -- standing in for what App::Render draws before the splats (app.cpp:1046-1063) -- and the frame is blended
+// over it (SplatRenderer::SetTargetMode(MSPLAT_TARGET_LOAD)), as the reference's Render does with its bound framebuffer.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -23,12 +25,13 @@ int main(int argc, char** argv)
         return 2;
     }
     int W = 1024, H = 768;   // the reference's default window (sdl_main.cpp:92)
-    bool nosh = false;
+    bool nosh = false, overGradient = false;
     if (argc >= 5 && argv[3][0] != '-') { W = std::atoi(argv[3]); H = std::atoi(argv[4]); }
     int inFlight = 1;
     std::vector<int> devices;
     for (int i = 3; i < argc; ++i) {
         nosh = nosh || !std::strcmp(argv[i], "--nosh");
+        overGradient = overGradient || !std::strcmp(argv[i], "--over-gradient");
         if (!std::strcmp(argv[i], "--frames-in-flight") && i + 1 < argc) inFlight = std::atoi(argv[i + 1]);
         if (!std::strcmp(argv[i], "--devices") && i + 1 < argc)
             for (const char* p = argv[i + 1]; *p;) {
@@ -57,7 +60,14 @@ int main(int argc, char** argv)
 
     std::vector<float> fb((size_t)W * H * 4);
     renderer.SetRenderTarget(fb.data(), 0, /*isDevicePointer=*/false);
+    if (overGradient && !renderer.SetTargetMode(MSPLAT_TARGET_LOAD)) return 1;
     for (int k = 0; k < (inFlight > 1 ? inFlight + 1 : 1); ++k) {
+        if (overGradient)            // every frame starts from the backdrop: LOAD blends over whatever the target holds
+            for (int y = 0; y < H; ++y)
+                for (int x = 0; x < W; ++x) {
+                    float* px = &fb[((size_t)y * W + x) * 4];
+                    px[0] = 0.1f; px[1] = 0.2f; px[2] = 0.2f + 0.6f * (float)y / (float)H; px[3] = 1.0f;
+                }
         renderer.Sort(cameraMat, projMat, viewport, nearFar);       // moves on to the next context
         renderer.Render(cameraMat, projMat, viewport, nearFar);
     }

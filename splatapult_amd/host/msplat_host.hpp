@@ -271,6 +271,24 @@ public:
         for (msplat_ctx* h : ctxs) msplat_set_target_emulation(h, rop);
     }
 
+    // what Render does with the render target's contents (msplat_set_target_mode; after Init, on every context of the rotation):
+    // MSPLAT_TARGET_CLEAR (default) overwrites with (C, 1); MSPLAT_TARGET_LOAD blends the splats over what the target holds -- the
+    // reference's Render, which never clears (app.cpp:154-156,1046-1068); MSPLAT_TARGET_PREMULTIPLIED writes the layer (C, 1 - T).
+    // A device group takes CLEAR and PREMULTIPLIED.
+    bool SetTargetMode(int mode)
+    {
+        if (group && msplat_group_set_target_mode(group, mode) != MSPLAT_OK) {
+            std::fprintf(stderr, "[msplat][E] SetTargetMode: %s\n", msplat_group_last_error(group));
+            return false;
+        }
+        for (msplat_ctx* h : ctxs)
+            if (msplat_set_target_mode(h, mode) != MSPLAT_OK) {
+                std::fprintf(stderr, "[msplat][E] SetTargetMode: %s\n", msplat_last_error(h));
+                return false;
+            }
+        return true;
+    }
+
     // blocks until every frame in flight has finished
     // (also where a pair-buffer overflow of an earlier device-target Render is reported, see msplat_render)
     void Synchronize()

@@ -57,10 +57,20 @@ def _aos_upload(cloud):
     return aos, (aos.ctypes.data, aos.shape[0], aos.shape[1] * 4, C.byref(off), 1 if aos.shape[1] == 61 else 0)
 
 
-def _host_frame(fb_format, vp, out=None):
-    """the (H, W, 4) host array a Render into host memory fills: `out` checked, or a new one"""
+def _target_mode(name):
+    """set_target_mode argument -> MSPLAT_TARGET_*"""
+    if name not in _capi.TARGET_MODES:
+        raise ValueError("target mode must be one of %s (got %r)" % (sorted(_capi.TARGET_MODES), name))
+    return _capi.TARGET_MODES[name]
+
+
+def _host_frame(fb_format, vp, out=None, load=False):
+    """the (H, W, 4) host array a Render into host memory fills: `out` checked, or a new one (load: the array's content is the
+    destination the frame is blended over, so there has to be one)"""
     W, H = int(vp[2]), int(vp[3])
     dt = np.float16 if fb_format == _capi.FB_RGBA16F else np.float32
+    if out is None and load:
+        raise ValueError('target mode "load" blends over the target\'s contents: pass out= (or out_ptr=)')
     if out is None:
         out = np.zeros((H, W, 4), dt)
     assert out.dtype == dt and out.shape == (H, W, 4) and out.flags["C_CONTIGUOUS"]
@@ -109,6 +119,7 @@ class SplatRenderer:
         # flight (msplat.h, MSPLAT_FRAMES_*)
         self._frame_mode = int(frame_mode) if frame_mode is not None else (_capi.FRAMES_IN_FLIGHT if self._depth > 1 else _capi.FRAMES_AUTO)
         self._n = 0
+        self._load = False                     # set_target_mode("load"): a host Render needs the destination in out=
 
     def __del__(self):
         self.close()
@@ -139,6 +150,7 @@ class SplatRenderer:
     def _create(self, isFramebufferSRGBEnabled):
         """one context per frame in flight; context 0 receives the cloud"""
         self.close()
+        self._load = False                   # (new contexts start in MSPLAT_TARGET_CLEAR)
         cfg = _capi.Config()
         cfg.struct_size = C.sizeof(_capi.Config)
         cfg.device = self._device
@@ -231,14 +243,15 @@ class SplatRenderer:
             _capi.check(self._ctx, self._lib.msplat_render(self._ctx, c, p, v, nf, C.c_void_p(out_ptr),
                                                            pitch_bytes, 1))
             return None
-        out = _host_frame(self._fb_format, self._args.vp, out)
+        out = _host_frame(self._fb_format, self._args.vp, out, self._load)
         _capi.check(self._ctx, self._lib.msplat_render(self._ctx, c, p, v, nf, out.ctypes.data, 0, 0))
         return out
 
     def RenderStereo(self, cameraMats, projMats, viewport, nearFar, out_ptrs=None, pitch_bytes=0):
         """both eyes of the latest Sort in ONE chain of launches (msplat_render_stereo; the reference renders them one after the
         other, app.cpp:603-607): same pixels as two Render calls.  out_ptrs: two device pointers (asynchronous), else two host
-        arrays are returned"""
+        arrays are returned -- not in target mode "load", which needs the destinations: ValueError without out_ptrs (render the
+        eyes with two Render(out=...) calls instead)"""
         a0, a1 = self._args, getattr(self, "_args1", None)
         if a1 is None:
             a1 = self._args1 = _FrameArgs()
@@ -248,7 +261,7 @@ class SplatRenderer:
             _capi.check(self._ctx, self._lib.msplat_render_stereo(self._ctx, c0, p0, c1, p1, v, nf, C.c_void_p(out_ptrs[0]),
                                                                   C.c_void_p(out_ptrs[1]), pitch_bytes, 1))
             return None
-        outs = [_host_frame(self._fb_format, a0.vp), _host_frame(self._fb_format, a0.vp)]
+        outs = [_host_frame(self._fb_format, a0.vp, None, self._load), _host_frame(self._fb_format, a0.vp, None, self._load)]
         _capi.check(self._ctx, self._lib.msplat_render_stereo(self._ctx, c0, p0, c1, p1, v, nf, outs[0].ctypes.data,
                                                               outs[1].ctypes.data, 0, 0))
         return outs
@@ -284,6 +297,20 @@ class SplatRenderer:
         mode = {None: _capi.ROP_NONE, "none": _capi.ROP_NONE, "rgba8": _capi.ROP_RGBA8, "fp16": _capi.ROP_RGBA16F}[rop]
         for h in self._ctxs:
             _capi.check(h, self._lib.msplat_set_target_emulation(h, mode))
+
+    def set_target_mode(self, mode):
+        """what Render does with the target's contents (msplat_set_target_mode), on every context of the rotation: "clear"
+        (default) overwrites with (C, 1); "premultiplied" writes the layer (C, 1 - T); "load" blends the frame over the pixels the
+        target holds -- with a host out= array its content is the destination, and out=None is an error"""
+        m = _target_mode(mode)
+        for h in self._ctxs:
+            _capi.check(h, self._lib.msplat_set_target_mode(h, m))
+        self._load = m == _capi.TARGET_LOAD
+
+    def target_mode(self):
+        """"clear" / "load" / "premultiplied" of the current context (msplat_get_target_mode); None without a context"""
+        k = self._lib.msplat_get_target_mode(self._ctx) if self._ctx else -1
+        return {v: n for n, v in _capi.TARGET_MODES.items()}.get(k)
 
     def synchronize(self):
         """blocks until every frame in flight has been issued (async_submit) AND has finished on the GPU"""
@@ -553,6 +580,11 @@ class SplatRendererGroup:
         out = _host_frame(self._fb_format, self._args.vp, out)
         _capi.check(self._g, self._lib.msplat_group_render(self._g, c, p, v, nf, out.ctypes.data, 0, 0), self._gerr)
         return out
+
+    def set_target_mode(self, mode):
+        """msplat_group_set_target_mode: "clear" or "premultiplied"; "load" is refused (MSPLAT_ERR_UNSUPPORTED: a rank that stages
+        its rows has no destination rows to blend over)"""
+        _capi.check(self._g, self._lib.msplat_group_set_target_mode(self._g, _target_mode(mode)), self._gerr)
 
     def synchronize(self):
         _capi.check(self._g, self._lib.msplat_group_synchronize(self._g), self._gerr)
