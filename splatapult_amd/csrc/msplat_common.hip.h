@@ -86,7 +86,7 @@ struct StampScope {
 #endif
 // kernel ids of the stamps (tools/stamp_timeline.py names them)
 enum { KID_WS_UP_CULL = 1, KID_WS_DOWN_CULL = 2, KID_WS_UP = 3, KID_WS_DOWN = 4, KID_PROJECT = 5, KID_BIN1_UP = 6, KID_BIN1_DOWN = 7,
-       KID_ROW_UP = 8, KID_ROW_DOWN = 9, KID_TILE_START = 10, KID_COMPOSITE = 11, KID_BOX_CULL = 12, KID_RADIX_UP = 13, KID_RADIX_DOWN = 14 };
+       KID_ROW_UP = 8, KID_ROW_DOWN = 9, KID_COMPOSITE = 11, KID_BOX_CULL = 12, KID_RADIX_UP = 13, KID_RADIX_DOWN = 14 };
 
 // Per-frame constants, passed by value (lives in SGPRs / kernarg segment).
 struct FrameParams {
@@ -197,8 +197,9 @@ __host__ __device__ __forceinline__ int band_last_owned_upto(const P& fp, int t)
     return k * fp.band_block + (j < fp.band_block ? j : fp.band_block - 1);
 }
 
-// inclusive scan of one uint32 per thread across a 256-thread workgroup.
-__device__ __forceinline__ uint32_t block_incl_scan(uint32_t v, uint32_t* s_tmp4, uint32_t& total)
+// inclusive scan of one uint32 per thread across a workgroup of WAVES waves (s_tmp: WAVES words); ends with a barrier
+template <int WAVES = 4>
+__device__ __forceinline__ uint32_t block_incl_scan(uint32_t v, uint32_t* s_tmp, uint32_t& total)
 {
     const int lane = threadIdx.x & 63;
     const int w = threadIdx.x >> 6;
@@ -207,13 +208,13 @@ __device__ __forceinline__ uint32_t block_incl_scan(uint32_t v, uint32_t* s_tmp4
         uint32_t t = __shfl_up(v, d, 64);
         if (lane >= d) v += t;
     }
-    if (lane == 63) s_tmp4[w] = v;
+    if (lane == 63) s_tmp[w] = v;
     __syncthreads();
     uint32_t off = 0;
     total = 0;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        uint32_t s = s_tmp4[k];
+    for (int k = 0; k < WAVES; ++k) {
+        uint32_t s = s_tmp[k];
         if (k < w) off += s;
         total += s;
     }
@@ -221,10 +222,39 @@ __device__ __forceinline__ uint32_t block_incl_scan(uint32_t v, uint32_t* s_tmp4
     return v + off;
 }
 
+// last index i <= hi with tab[i] <= x (tab ascending, tab[0] <= x): binary search of a fixed number of steps, 2^STEPS > hi
+template <int STEPS>
+__device__ __forceinline__ uint32_t last_le(const uint32_t* tab, uint32_t x, uint32_t hi)
+{
+    uint32_t lo = 0;
+#pragma unroll
+    for (int s = 0; s < STEPS; ++s) {
+        const uint32_t mid = (lo + hi + 1u) >> 1;
+        if (tab[mid] <= x) lo = mid; else hi = mid - 1u;
+    }
+    return lo;
+}
+
+// elements a pass walks: the count an earlier kernel left on the device (d_n) or a static one, at most n_cap
+__device__ __forceinline__ uint32_t active_count(const uint32_t* d_n, uint32_t n_static, uint32_t n_cap) { return min(d_n ? *d_n : n_static, n_cap); }
+
+// stores one pixel of a target row: RGBA16F (F16) or RGBA32F
+template <bool F16>
+__device__ __forceinline__ void store_px(void* row, int x, const float4 px)
+{
+    if (F16) {
+        union { _Float16 h[4]; uint2 u; } pk;
+        pk.h[0] = (_Float16)px.x; pk.h[1] = (_Float16)px.y; pk.h[2] = (_Float16)px.z; pk.h[3] = (_Float16)px.w;
+        ((uint2*)row)[x] = pk.u;
+    } else {
+        ((float4*)row)[x] = px;
+    }
+}
+
 // Workgroup b is observed to run on XCD b % 8 (MI355X_MICROARCH.md; speed only, never correctness).
 // Remap so that each XCD processes a CONTIGUOUS range of chunks.  Measured r1: using it for the
-// scatter kernels (radix/bin1 downsweep) was 5-15 % SLOWER than the plain round-robin mapping, so it
-// is currently unused there.
+// scatter kernels (radix/bin1 downsweep) was 5-15 % SLOWER than the plain round-robin mapping.  Today ws_downsweep uses it
+// whenever its grid allows, radix_downsweep<MODE_PAIR> and bin1_downsweep on request (do_order bit 1, xcd_map == 1): see ws_downsweep.
 __device__ __forceinline__ uint32_t xcd_contiguous(uint32_t b, uint32_t n)
 {
     const uint32_t q = n >> 3, r = n & 7u, xcd = b & 7u, idx = b >> 3;
@@ -514,9 +544,10 @@ __global__ __launch_bounds__(kBoxGroup) void box_cull_kernel(const CullBox* __re
 }
 
 // exclusive prefix of the segment counts: s_lpre[g] = live boxes before segment g, s_lpre[256] = all of them.  Every thread of a
-// workgroup of >= 256 threads must call it (WAVES = its waves; s_tmp: WAVES words).  Ends with a barrier.
+// workgroup of >= 256 threads must call it (WAVES = its waves; s_tmp: WAVES words).  Ends with a barrier.  Returns the number of
+// virtual positions pass 0 walks: the listed boxes are dense there (the cloud's last box may be partial: LiveChunk's `in`).
 template <int WAVES>
-__device__ __forceinline__ void live_prefix(const LiveBoxes& lb, uint32_t* s_lpre, uint32_t* s_tmp)
+__device__ __forceinline__ uint32_t live_prefix(const LiveBoxes& lb, uint32_t* s_lpre, uint32_t* s_tmp)
 {
     const uint32_t t = threadIdx.x;
     uint32_t v = (t < 256u && t < lb.wgs) ? lb.cnt[t] : 0u;
@@ -539,20 +570,33 @@ __device__ __forceinline__ void live_prefix(const LiveBoxes& lb, uint32_t* s_lpr
     if (t < 256u) s_lpre[t] = v + off - c;
     if (t == 0u) s_lpre[256] = total;
     __syncthreads();
+    return s_lpre[256] * (uint32_t)kBoxSplats;
 }
 
 // storage box number of the vb-th live box (0xFFFFFFFF beyond the last)
 __device__ __forceinline__ uint32_t live_box_at(const LiveBoxes& lb, const uint32_t* s_lpre, uint32_t vb)
 {
     if (vb >= s_lpre[256]) return 0xFFFFFFFFu;
-    uint32_t lo = 0, hi = 255;                  // last segment g with s_lpre[g] <= vb
-#pragma unroll
-    for (int st = 0; st < 8; ++st) {
-        const uint32_t mid = (lo + hi + 1u) >> 1;
-        if (s_lpre[mid] <= vb) lo = mid; else hi = mid - 1u;
-    }
-    return lb.list[lo * kBoxGroup + (vb - s_lpre[lo])];
+    const uint32_t g = last_le<8>(s_lpre, vb, 255u);         // its segment
+    return lb.list[g * kBoxGroup + (vb - s_lpre[g])];
 }
+
+// One chunk of pass 0: virtual positions first, first + 1, ... of n; with a list (compact) s_box holds the chunk's live boxes
+// (live_box_at of chunk * boxes per chunk + 0, 1, ...).
+struct LiveChunk {      // {lb, s_box, compact, first, n}: mind the order of the last two
+    const LiveBoxes& lb;
+    const uint32_t* s_box;
+    bool compact;
+    uint32_t first, n;
+    // storage index of virtual position i (== i without a list); `in`: the position holds a splat
+    __device__ __forceinline__ uint32_t storage_of(uint32_t i, bool& in) const
+    {
+        if (!compact) { in = i < n; return i; }
+        const uint32_t e = i - first, bx = s_box[e / kBoxSplats], st = bx * kBoxSplats + (e % kBoxSplats);
+        in = bx != 0xFFFFFFFFu && st < lb.n_storage;
+        return st;
+    }
+};
 
 // two-pass frames (msplat_occlusion.hip.h): first rank of pass 1 for V visible splats and a share of them in pass 1
 __device__ __forceinline__ uint32_t occ_cut(uint32_t V, float share)

@@ -412,13 +412,7 @@ __global__ __launch_bounds__(kCompThreads, kCompOcc) void composite_kernel(const
                 // from PREMULTIPLIED by an fp16 ulp in a few pixels per frame)
                 if (F16) asm volatile("" : "+v"(px.x), "+v"(px.y), "+v"(px.z), "+v"(px.w));
             }
-            if (F16) {
-                union { _Float16 h[4]; uint2 u; } pk;
-                pk.h[0] = (_Float16)px.x; pk.h[1] = (_Float16)px.y; pk.h[2] = (_Float16)px.z; pk.h[3] = (_Float16)px.w;
-                ((uint2*)row)[x] = pk.u;
-            } else {
-                ((float4*)row)[x] = px;
-            }
+            store_px<F16>(row, x, px);
         }
     }
     __syncthreads();      // s_rec is reused by the next tile
@@ -451,55 +445,36 @@ __device__ __forceinline__ float rop_store(float x, int rop)
     return x;
 }
 
-// TM (msplat_set_target_mode, MSPLAT_ROP_NONE only): kTargetLoad starts the running colour AND alpha from the target's pixel, the
-// draw-order blend then runs over it (a = w + (1 - w) a); kTargetPremultiplied starts from (0, 0, 0, 0).  The emulated depth buffer
-// is cleared to 1.0 either way: the target's contents lie behind every splat.
-template <bool HALF, int TM = kTargetClear>
-__global__ __launch_bounds__(kCompThreads) void composite_depth_kernel(const uint32_t* __restrict__ tile_start,
-                                                                       const uint32_t* __restrict__ pairs,
-                                                                       const float4* __restrict__ rec,
-                                                                       const uint32_t* __restrict__ zq,
-                                                                       void* __restrict__ out, size_t pitch_bytes,
-                                                                       FrameParams fp, uint32_t cap,
-                                                                       const uint32_t* __restrict__ order,
-                                                                       uint32_t* __restrict__ queue, uint32_t ntiles)
+// a lane's four pixels (x, ybase + 4k), one per 16x4 strip, in the draw-order compositors: running colour and alpha, emulated depth buffer
+struct DrawPixels { float cr[4], cg[4], cb[4], ca[4]; uint32_t zbuf[4]; };
+
+// The draw-order tile walk of composite_depth_kernel and composite_points_kernel (one wave per 16x16 tile, lists walked far to near
+// in batches of 64, single-head queue).  The kernel declares the LDS (s_rec: kCompThreads * 3, s_z: kCompThreads) and supplies
+// initial(px, x, ybase): what the cleared pixels start from; relevant(p0, p1, p2, X0, X1, Y0, Y1): can the record touch a pixel
+// centre of the tile; shade(px, r, zj, fx, ybase): blends the staged record r[0..2] of depth zj into the lane's pixels;
+// final_alpha(px, k): the alpha stored with pixel k.  depth_test: the records' quantised depths zq[rank] are staged too.
+template <bool HALF, class Initial, class Relevant, class Shade, class FinalAlpha>
+__device__ __forceinline__ void draw_order_walk(const uint32_t* __restrict__ tile_start, const uint32_t* __restrict__ pairs,
+                                                const float4* __restrict__ rec, const uint32_t* __restrict__ zq, bool depth_test,
+                                                void* __restrict__ out, size_t pitch_bytes, const FrameParams& fp, uint32_t cap,
+                                                const uint32_t* __restrict__ order, uint32_t* __restrict__ queue, uint32_t ntiles,
+                                                float4* s_rec, uint32_t* s_z,
+                                                Initial initial, Relevant relevant, Shade shade, FinalAlpha final_alpha)
 {
-    __shared__ float4 s_rec[kCompThreads * 3];
-    __shared__ uint32_t s_z[kCompThreads];
-    const int lane = threadIdx.x;
-    const int lx = lane & 15, ly = lane >> 4;
+    const int lane = threadIdx.x, lx = lane & 15, ly = lane >> 4;
     for (uint32_t qpos = blockIdx.x; qpos < ntiles;) {
-        const int bin = (int)order[qpos >> 2];
-        const int quad = (int)(qpos & 3u);
+        const int bin = (int)order[qpos >> 2], quad = (int)(qpos & 3u);
         const int bvy = bin / fp.tiles_x;
         const int tx = (bin - bvy * fp.tiles_x) * 2 + (quad & 1);
         const int ty = band_real_row(fp, bvy) * 2 + (quad >> 1);
         if (tx * kTile < fp.width && ty * kTile < fp.height) {
             const int x = tx * kTile + lx, ybase = ty * kTile + ly;
             const float fx = (float)x + 0.5f;
-            uint32_t start = tile_start[bin], end = tile_start[bin + 1];
-            if (start > cap) start = cap;
-            if (end > cap) end = cap;
-            float cr[4], cg[4], cb[4], ca[4];
-            uint32_t zbuf[4];
+            const uint32_t start = min(tile_start[bin], cap), end = min(tile_start[bin + 1], cap);
+            DrawPixels px;
 #pragma unroll
-            for (int k = 0; k < 4; ++k) { cr[k] = 0.0f; cg[k] = 0.0f; cb[k] = 0.0f; ca[k] = 0.0f; zbuf[k] = 0xFFFFFFFFu; }   // cleared to 1.0
-            if (TM == kTargetLoad) {
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    if (x < fp.width && ybase + 4 * k < fp.height) {
-                        const char* row = (const char*)out + (size_t)(ybase + 4 * k) * pitch_bytes;
-                        if (HALF) {
-                            union { _Float16 h[4]; uint2 u; } in;
-                            in.u = ((const uint2*)row)[x];
-                            cr[k] = (float)in.h[0]; cg[k] = (float)in.h[1]; cb[k] = (float)in.h[2]; ca[k] = (float)in.h[3];
-                        } else {
-                            const float4 d = ((const float4*)row)[x];
-                            cr[k] = d.x; cg[k] = d.y; cb[k] = d.z; ca[k] = d.w;
-                        }
-                    }
-                }
-            }
+            for (int k = 0; k < 4; ++k) { px.cr[k] = 0.0f; px.cg[k] = 0.0f; px.cb[k] = 0.0f; px.ca[k] = 0.0f; px.zbuf[k] = 0xFFFFFFFFu; }   // cleared to 1.0
+            initial(px, x, ybase);
             const float X0 = (float)(tx * kTile) + 0.5f, X1 = X0 + (float)(kTile - 1);
             const float Y0 = (float)(ty * kTile) + 0.5f, Y1 = Y0 + (float)(kTile - 1);
             for (uint32_t base = start; base < end; base += kCompThreads) {      // ascending = draw order
@@ -515,79 +490,25 @@ __global__ __launch_bounds__(kCompThreads) void composite_depth_kernel(const uin
                     asm volatile("" : "+v"(rank));
                     const float4* src = rec + (size_t)rank * 3;
                     p0 = src[0]; p1 = src[1]; p2 = src[2];
-                    if (fp.depth_bits != 0) z = zq[rank];
-                    // same exact footprint-vs-tile test as composite_kernel
-                    const float qa = p0.z, qb = p0.w, qc = p1.x, la = p1.y;
-                    const float dxl = X0 - p0.x, dxh = X1 - p0.x, dyl = Y0 - p0.y, dyh = Y1 - p0.y;
-                    rel = true;
-                    if (!(dxl <= 0.0f && dxh >= 0.0f && dyl <= 0.0f && dyh >= 0.0f)) {
-                        float emax = -1e30f;
-                        const float i2c = __builtin_amdgcn_rcpf(2.0f * qc), i2a = __builtin_amdgcn_rcpf(2.0f * qa);
-#pragma unroll
-                        for (int s = 0; s < 2; ++s) {
-                            const float dx = s ? dxh : dxl;
-                            const float dy = fminf(fmaxf(-qb * dx * i2c, dyl), dyh);
-                            emax = fmaxf(emax, (qc * dy + qb * dx) * dy + qa * dx * dx + la);
-                            const float ey = s ? dyh : dyl;
-                            const float ex = fminf(fmaxf(-qb * ey * i2a, dxl), dxh);
-                            emax = fmaxf(emax, (qa * ex + qb * ey) * ex + qc * ey * ey + la);
-                        }
-                        rel = emax > -8.05f;
-                    }
+                    if (depth_test) z = zq[rank];
+                    rel = relevant(p0, p1, p2, X0, X1, Y0, Y1);
                 }
                 const uint64_t relmask = __ballot(rel);
                 const uint32_t n = (uint32_t)__popcll(relmask);
                 if (rel) {
                     const int slot = __popcll(relmask & ((1ull << lane) - 1ull));     // keeps draw order
-                    s_rec[slot * 3 + 0] = p0;
-                    s_rec[slot * 3 + 1] = p1;
-                    s_rec[slot * 3 + 2] = p2;
+                    s_rec[slot * 3 + 0] = p0; s_rec[slot * 3 + 1] = p1; s_rec[slot * 3 + 2] = p2;
                     s_z[slot] = z;
                 }
                 __syncthreads();
-                for (uint32_t j = 0; j < n; ++j) {
-                    const float4 a = s_rec[j * 3 + 0];      // px, py, A, B
-                    const float4 b = s_rec[j * 3 + 1];      // C, log2(alpha), r, g
-                    const float blue = s_rec[j * 3 + 2].x;
-                    const uint32_t zj = s_z[j];
-                    const float dx = fx - a.x;
-                    const float base_e = __builtin_fmaf(a.z * dx, dx, b.y);
-                    const float lin = a.w * dx;
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const float dy = ((float)(ybase + 4 * k) + 0.5f) - a.y;
-                        const float e = __builtin_fmaf(dy, __builtin_fmaf(b.x, dy, lin), base_e);
-                        // splat_frag.glsl:37-40 discard, then GL_LESS against the emulated depth buffer
-                        if (e > -8.0f && (fp.depth_bits == 0 || zj < zbuf[k])) {
-                            const float w = __builtin_amdgcn_exp2f(e);
-                            // splat_frag.glsl:27-28: out = (w rgb, w); GL_ONE, GL_ONE_MINUS_SRC_ALPHA
-                            float sr = w * b.z, sg = w * b.w, sb = w * blue;
-                            if (fp.rop == 1) {      // fixed-point target: the source colour is clamped before the blend
-                                sr = fminf(fmaxf(sr, 0.0f), 1.0f); sg = fminf(fmaxf(sg, 0.0f), 1.0f); sb = fminf(fmaxf(sb, 0.0f), 1.0f);
-                            }
-                            const float oma = 1.0f - w;
-                            cr[k] = rop_store(sr + oma * cr[k], fp.rop);
-                            cg[k] = rop_store(sg + oma * cg[k], fp.rop);
-                            cb[k] = rop_store(sb + oma * cb[k], fp.rop);
-                            if (TM != kTargetClear) ca[k] = w + oma * ca[k];
-                            zbuf[k] = zj;
-                        }
-                    }
-                }
+                for (uint32_t j = 0; j < n; ++j) shade(px, s_rec + j * 3, s_z[j], fx, ybase);
                 __syncthreads();
             }
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 if (x < fp.width && ybase + 4 * k < fp.height) {
                     char* row = (char*)out + (size_t)(ybase + 4 * k) * pitch_bytes;
-                    const float a = TM != kTargetClear ? ca[k] : 1.0f;
-                    if (HALF) {
-                        union { _Float16 h[4]; uint2 u; } pk;
-                        pk.h[0] = (_Float16)cr[k]; pk.h[1] = (_Float16)cg[k]; pk.h[2] = (_Float16)cb[k]; pk.h[3] = (_Float16)a;
-                        ((uint2*)row)[x] = pk.u;
-                    } else {
-                        ((float4*)row)[x] = make_float4(cr[k], cg[k], cb[k], a);
-                    }
+                    store_px<HALF>(row, x, make_float4(px.cr[k], px.cg[k], px.cb[k], final_alpha(px, k)));
                 }
             }
         }
@@ -595,6 +516,84 @@ __global__ __launch_bounds__(kCompThreads) void composite_depth_kernel(const uin
         if (threadIdx.x == 0) nq = atomicAdd(queue, 1u);
         qpos = gridDim.x + __builtin_amdgcn_readfirstlane(nq);
     }
+}
+
+// TM (msplat_set_target_mode, MSPLAT_ROP_NONE only): kTargetLoad starts the running colour AND alpha from the target's pixel, the
+// draw-order blend then runs over it (a = w + (1 - w) a); kTargetPremultiplied starts from (0, 0, 0, 0).  The emulated depth buffer
+// is cleared to 1.0 either way: the target's contents lie behind every splat.
+template <bool HALF, int TM = kTargetClear>
+__global__ __launch_bounds__(kCompThreads) void composite_depth_kernel(const uint32_t* __restrict__ tile_start, const uint32_t* __restrict__ pairs,
+                                                                       const float4* __restrict__ rec, const uint32_t* __restrict__ zq,
+                                                                       void* __restrict__ out, size_t pitch_bytes, FrameParams fp, uint32_t cap,
+                                                                       const uint32_t* __restrict__ order, uint32_t* __restrict__ queue, uint32_t ntiles)
+{
+    __shared__ float4 s_rec[kCompThreads * 3];
+    __shared__ uint32_t s_z[kCompThreads];
+    auto initial = [&](DrawPixels& px, int x, int ybase) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (TM == kTargetLoad && x < fp.width && ybase + 4 * k < fp.height) {
+                const char* row = (const char*)out + (size_t)(ybase + 4 * k) * pitch_bytes;
+                if (HALF) {
+                    union { _Float16 h[4]; uint2 u; } in;
+                    in.u = ((const uint2*)row)[x];
+                    px.cr[k] = (float)in.h[0]; px.cg[k] = (float)in.h[1]; px.cb[k] = (float)in.h[2]; px.ca[k] = (float)in.h[3];
+                } else {
+                    const float4 d = ((const float4*)row)[x];
+                    px.cr[k] = d.x; px.cg[k] = d.y; px.cb[k] = d.z; px.ca[k] = d.w;
+                }
+            }
+        }
+    };
+    // same exact footprint-vs-tile test as composite_kernel
+    auto relevant = [](const float4& p0, const float4& p1, const float4&, float X0, float X1, float Y0, float Y1) -> bool {
+        const float qa = p0.z, qb = p0.w, qc = p1.x, la = p1.y;
+        const float dxl = X0 - p0.x, dxh = X1 - p0.x, dyl = Y0 - p0.y, dyh = Y1 - p0.y;
+        if (dxl <= 0.0f && dxh >= 0.0f && dyl <= 0.0f && dyh >= 0.0f) return true;
+        float emax = -1e30f;
+        const float i2c = __builtin_amdgcn_rcpf(2.0f * qc), i2a = __builtin_amdgcn_rcpf(2.0f * qa);
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            const float dx = s ? dxh : dxl;
+            const float dy = fminf(fmaxf(-qb * dx * i2c, dyl), dyh);
+            emax = fmaxf(emax, (qc * dy + qb * dx) * dy + qa * dx * dx + la);
+            const float ey = s ? dyh : dyl;
+            const float ex = fminf(fmaxf(-qb * ey * i2a, dxl), dxh);
+            emax = fmaxf(emax, (qa * ex + qb * ey) * ex + qc * ey * ey + la);
+        }
+        return emax > -8.05f;
+    };
+    auto shade = [&](DrawPixels& px, const float4* r, uint32_t zj, float fx, int ybase) {
+        const float4 a = r[0];      // px, py, A, B
+        const float4 b = r[1];      // C, log2(alpha), r, g
+        const float blue = r[2].x;
+        const float dx = fx - a.x;
+        const float base_e = __builtin_fmaf(a.z * dx, dx, b.y);
+        const float lin = a.w * dx;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float dy = ((float)(ybase + 4 * k) + 0.5f) - a.y;
+            const float e = __builtin_fmaf(dy, __builtin_fmaf(b.x, dy, lin), base_e);
+            // splat_frag.glsl:37-40 discard, then GL_LESS against the emulated depth buffer
+            if (e > -8.0f && (fp.depth_bits == 0 || zj < px.zbuf[k])) {
+                const float w = __builtin_amdgcn_exp2f(e);
+                // splat_frag.glsl:27-28: out = (w rgb, w); GL_ONE, GL_ONE_MINUS_SRC_ALPHA
+                float sr = w * b.z, sg = w * b.w, sb = w * blue;
+                if (fp.rop == 1) {      // fixed-point target: the source colour is clamped before the blend
+                    sr = fminf(fmaxf(sr, 0.0f), 1.0f); sg = fminf(fmaxf(sg, 0.0f), 1.0f); sb = fminf(fmaxf(sb, 0.0f), 1.0f);
+                }
+                const float oma = 1.0f - w;
+                px.cr[k] = rop_store(sr + oma * px.cr[k], fp.rop);
+                px.cg[k] = rop_store(sg + oma * px.cg[k], fp.rop);
+                px.cb[k] = rop_store(sb + oma * px.cb[k], fp.rop);
+                if (TM != kTargetClear) px.ca[k] = w + oma * px.ca[k];
+                px.zbuf[k] = zj;
+            }
+        }
+    };
+    auto final_alpha = [](const DrawPixels& px, int k) -> float { return TM != kTargetClear ? px.ca[k] : 1.0f; };
+    draw_order_walk<HALF>(tile_start, pairs, rec, zq, fp.depth_bits != 0, out, pitch_bytes, fp, cap, order, queue, ntiles, s_rec, s_z,
+                          initial, relevant, shade, final_alpha);
 }
 
 }  // namespace msplat

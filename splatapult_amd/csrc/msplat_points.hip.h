@@ -122,7 +122,7 @@ __device__ __forceinline__ float4 sprite_sample(const float4* __restrict__ tex, 
     return make_float4(a.x * g + b.x * f, a.y * g + b.y * f, a.z * g + b.z * f, a.w * g + b.w * f);
 }
 
-// draw-order walk like composite_depth_kernel (optional emulated depth test: zq == nullptr -> colour only)
+// draw_order_walk over the sprites (optional emulated depth test: zq == nullptr -> colour only)
 template <bool HALF>
 __global__ __launch_bounds__(kCompThreads) void composite_points_kernel(const uint32_t* __restrict__ tile_start,
                                                                         const uint32_t* __restrict__ pairs,
@@ -136,94 +136,37 @@ __global__ __launch_bounds__(kCompThreads) void composite_points_kernel(const ui
 {
     __shared__ float4 s_rec[kCompThreads * 3];
     __shared__ uint32_t s_z[kCompThreads];
-    const int lane = threadIdx.x;
-    const int lx = lane & 15, ly = lane >> 4;
-    for (uint32_t qpos = blockIdx.x; qpos < ntiles;) {
-        const int bin = (int)order[qpos >> 2];
-        const int quad = (int)(qpos & 3u);
-        const int bvy = bin / fp.tiles_x;
-        const int tx = (bin - bvy * fp.tiles_x) * 2 + (quad & 1);
-        const int ty = band_real_row(fp, bvy) * 2 + (quad >> 1);
-        if (tx * kTile < fp.width && ty * kTile < fp.height) {
-            const int x = tx * kTile + lx, ybase = ty * kTile + ly;
-            const float fx = (float)x + 0.5f;
-            uint32_t start = tile_start[bin], end = tile_start[bin + 1];
-            if (start > cap) start = cap;
-            if (end > cap) end = cap;
-            float cr[4], cg[4], cb[4];
-            uint32_t zbuf[4];
+    auto initial = [](DrawPixels&, int, int) {};
+    // some pixel centre of the tile inside [c - h, c + h) on both axes
+    auto relevant = [](const float4& p0, const float4&, const float4&, float X0, float X1, float Y0, float Y1) -> bool {
+        return (p0.x - p0.z <= X1) && (p0.x + p0.z > X0) && (p0.y - p0.w <= Y1) && (p0.y + p0.w > Y0);
+    };
+    auto shade = [&](DrawPixels& px, const float4* r, uint32_t zj, float fx, int ybase) {
+        const float4 q = r[0];      // cx, cy, hx, hy
+        const float4 col = r[1];
+        const float lambda = r[2].x;
+        const float xlo = q.x - q.z, xhi = q.x + q.z;
+        if (!(fx >= xlo && fx < xhi)) return;
+        const float u = (fx - xlo) / (2.0f * q.z);
+        const float ylo = q.y - q.w, yhi = q.y + q.w;
 #pragma unroll
-            for (int k = 0; k < 4; ++k) { cr[k] = 0.0f; cg[k] = 0.0f; cb[k] = 0.0f; zbuf[k] = 0xFFFFFFFFu; }
-            const float X0 = (float)(tx * kTile) + 0.5f, X1 = X0 + (float)(kTile - 1);
-            const float Y0 = (float)(ty * kTile) + 0.5f, Y1 = Y0 + (float)(kTile - 1);
-            for (uint32_t base = start; base < end; base += kCompThreads) {
-                const uint32_t cnt = min((uint32_t)kCompThreads, end - base);
-                float4 p0 = make_float4(0, 0, 0, 0), p1 = p0, p2 = p0;
-                uint32_t z = 0;
-                bool rel = false;
-                if (lane < (int)cnt) {
-                    uint32_t rank = pairs[base + lane] & kRankMask;
-                    asm volatile("" : "+v"(rank));          // see composite_depth_kernel (hipcc mask/mad folding)
-                    const float4* src = rec + (size_t)rank * 3;
-                    p0 = src[0]; p1 = src[1]; p2 = src[2];
-                    if (zq != nullptr) z = zq[rank];
-                    // some pixel centre of the tile inside [c - h, c + h) on both axes
-                    rel = (p0.x - p0.z <= X1) && (p0.x + p0.z > X0) && (p0.y - p0.w <= Y1) && (p0.y + p0.w > Y0);
-                }
-                const uint64_t relmask = __ballot(rel);
-                const uint32_t n = (uint32_t)__popcll(relmask);
-                if (rel) {
-                    const int slot = __popcll(relmask & ((1ull << lane) - 1ull));
-                    s_rec[slot * 3 + 0] = p0;
-                    s_rec[slot * 3 + 1] = p1;
-                    s_rec[slot * 3 + 2] = p2;
-                    s_z[slot] = z;
-                }
-                __syncthreads();
-                for (uint32_t j = 0; j < n; ++j) {
-                    const float4 q = s_rec[j * 3 + 0];      // cx, cy, hx, hy
-                    const float4 col = s_rec[j * 3 + 1];
-                    const float lambda = s_rec[j * 3 + 2].x;
-                    const uint32_t zj = s_z[j];
-                    const float xlo = q.x - q.z, xhi = q.x + q.z;
-                    if (!(fx >= xlo && fx < xhi)) continue;
-                    const float u = (fx - xlo) / (2.0f * q.z);
-                    const float ylo = q.y - q.w, yhi = q.y + q.w;
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const float fy = (float)(ybase + 4 * k) + 0.5f;
-                        if (fy >= ylo && fy < yhi && (zq == nullptr || zj < zbuf[k])) {
-                            const float v = (fy - ylo) / (2.0f * q.w);
-                            const float4 tx4 = sprite_sample(tex, sp, u, v, lambda);
-                            const float sa = col.w * tx4.w;                  // point_frag.glsl:24
-                            const float oma = 1.0f - sa;
-                            cr[k] = ((col.w * col.x) * tx4.x) + oma * cr[k];     // point_frag.glsl:23, GL_ONE / 1 - src.a
-                            cg[k] = ((col.w * col.y) * tx4.y) + oma * cg[k];
-                            cb[k] = ((col.w * col.z) * tx4.z) + oma * cb[k];
-                            zbuf[k] = zj;                                    // no discard in point_frag: always writes depth
-                        }
-                    }
-                }
-                __syncthreads();
-            }
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                if (x < fp.width && ybase + 4 * k < fp.height) {
-                    char* row = (char*)out + (size_t)(ybase + 4 * k) * pitch_bytes;
-                    if (HALF) {
-                        union { _Float16 h[4]; uint2 u; } pk;
-                        pk.h[0] = (_Float16)cr[k]; pk.h[1] = (_Float16)cg[k]; pk.h[2] = (_Float16)cb[k]; pk.h[3] = (_Float16)1.0f;
-                        ((uint2*)row)[x] = pk.u;
-                    } else {
-                        ((float4*)row)[x] = make_float4(cr[k], cg[k], cb[k], 1.0f);
-                    }
-                }
+        for (int k = 0; k < 4; ++k) {
+            const float fy = (float)(ybase + 4 * k) + 0.5f;
+            if (fy >= ylo && fy < yhi && (zq == nullptr || zj < px.zbuf[k])) {
+                const float v = (fy - ylo) / (2.0f * q.w);
+                const float4 tx4 = sprite_sample(tex, sp, u, v, lambda);
+                const float sa = col.w * tx4.w;                  // point_frag.glsl:24
+                const float oma = 1.0f - sa;
+                px.cr[k] = ((col.w * col.x) * tx4.x) + oma * px.cr[k];     // point_frag.glsl:23, GL_ONE / 1 - src.a
+                px.cg[k] = ((col.w * col.y) * tx4.y) + oma * px.cg[k];
+                px.cb[k] = ((col.w * col.z) * tx4.z) + oma * px.cb[k];
+                px.zbuf[k] = zj;                                 // no discard in point_frag: always writes depth
             }
         }
-        uint32_t nq = 0;
-        if (threadIdx.x == 0) nq = atomicAdd(queue, 1u);
-        qpos = gridDim.x + __builtin_amdgcn_readfirstlane(nq);
-    }
+    };
+    auto final_alpha = [](const DrawPixels&, int) -> float { return 1.0f; };
+    draw_order_walk<HALF>(tile_start, pairs, rec, zq, zq != nullptr, out, pitch_bytes, fp, cap, order, queue, ntiles, s_rec, s_z,
+                          initial, relevant, shade, final_alpha);
 }
 
 }  // namespace msplat

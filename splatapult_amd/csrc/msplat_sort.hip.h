@@ -29,8 +29,6 @@ __global__ __launch_bounds__(kThreads) void lds_atomic_order_probe(uint32_t* __r
     for (int mod = 1; mod <= 256; mod = mod * 3 + 1) {          // 1, 4, 13, 40, 121 distinct digits
         for (int q = 0; q < 4; ++q) s_c[q][threadIdx.x] = 0;
         __syncthreads();
-        uint32_t expect_base[1];
-        (void)expect_base;
         for (int r = 0; r < 8; ++r) {
             uint32_t h = (uint32_t)(threadIdx.x * 2654435761u) ^ (uint32_t)(r * 40503u + blockIdx.x * 977u + mod);
             h ^= h >> 15; h *= 2246822519u; h ^= h >> 13;
@@ -122,12 +120,8 @@ __global__ __launch_bounds__(kThreads) void radix_upsweep(const uint32_t* __rest
     const bool compact = MODE == MODE_CULL && lb.list != nullptr;
     if (gsum_zero != nullptr)
         for (uint32_t row = blockIdx.x; row < gsum_zero_rows; row += gridDim.x) gsum_zero[(size_t)row * 256 + threadIdx.x] = 0u;
-    uint32_t n = d_n ? *d_n : n_static;
-    if (n > n_cap) n = n_cap;
-    if (compact) {
-        live_prefix<kThreads / 64>(lb, s_lpre, s_tmp4);
-        n = s_lpre[256] * (uint32_t)kBoxSplats;
-    }
+    uint32_t n = active_count(d_n, n_static, n_cap);
+    if (compact) n = live_prefix<kThreads / 64>(lb, s_lpre, s_tmp4);
     const uint32_t nchunks = (n + CHUNK - 1) / CHUNK;
     const bool count_bins = MODE == MODE_PAIR && bincnt != nullptr;
     if (count_bins) {
@@ -184,23 +178,17 @@ __global__ __launch_bounds__(kThreads) void radix_upsweep(const uint32_t* __rest
             // in s_bin[0][row], i.e. column c0)
             if (MODE == MODE_CULL) {
                 float4 pp[MODE == MODE_CULL ? ITEMS : 1];          // unconditional loads, all in flight together (see below)
-                // storage index of virtual position i (== i without a list); `in`: the position holds a splat
-                auto locate = [&](uint32_t i, bool& in) -> uint32_t {
-                    if (!compact) { in = i < n; return i; }
-                    const uint32_t e = i - base, bx = s_box[e / kBoxSplats], st = bx * kBoxSplats + (e % kBoxSplats);
-                    in = bx != 0xFFFFFFFFu && st < lb.n_storage;
-                    return st;
-                };
+                const LiveChunk lc{lb, s_box, compact, base, n};
 #pragma unroll
                 for (int r = 0; r < ITEMS; ++r) {
                     bool in;
-                    const uint32_t st = locate(base + r * kThreads + threadIdx.x, in);
+                    const uint32_t st = lc.storage_of(base + r * kThreads + threadIdx.x, in);
                     pp[r] = pos[in ? st : 0u];
                 }
 #pragma unroll
                 for (int r = 0; r < ITEMS; ++r) {
                     bool in;
-                    (void)locate(base + r * kThreads + threadIdx.x, in);
+                    (void)lc.storage_of(base + r * kThreads + threadIdx.x, in);
                     uint32_t key;
                     if (in && cull_key<BAND>(pp[r], fp, key)) atomicAdd(&s_hist[digit_of<MODE>(key, shift)], 1u);
                 }
@@ -317,8 +305,7 @@ __global__ __launch_bounds__(kThreads) void radix_scan(uint32_t* __restrict__ hi
                                                        uint32_t* __restrict__ totals)
 {
     __shared__ uint32_t s_tmp[4];
-    uint32_t n = d_n ? *d_n : n_static;
-    if (n > n_cap) n = n_cap;
+    uint32_t n = active_count(d_n, n_static, n_cap);
     const uint32_t nchunks = (n + chunk_size - 1) / chunk_size;
     uint32_t* col = hist + blockIdx.x;            // this digit's column of the chunk-major table
     uint32_t running = 0;
@@ -345,8 +332,7 @@ __global__ __launch_bounds__(kThreads) void radix_scan_small(uint32_t* __restric
 {
     constexpr int G = 32, DIG = 8, REG = 32;
     __shared__ uint32_t s_part[G][DIG + 1];
-    uint32_t n = d_n ? *d_n : n_static;
-    if (n > n_cap) n = n_cap;
+    uint32_t n = active_count(d_n, n_static, n_cap);
     const uint32_t nchunks = (n + chunk_size - 1) / chunk_size;
     const int dd = threadIdx.x & (DIG - 1), g = threadIdx.x / DIG;
     const uint32_t digit = blockIdx.x * DIG + dd;
@@ -500,12 +486,8 @@ __global__ __launch_bounds__(kThreads, (ATOMIC_RANK && MODE == MODE_KEYS && SORT
     constexpr int BPC = CHUNK / kBoxSplats;
     __shared__ uint32_t s_lpre[MODE == MODE_CULL ? 257 : 1], s_box[MODE == MODE_CULL ? BPC : 1];
     const bool compact = MODE == MODE_CULL && lb.list != nullptr;
-    uint32_t n = d_n ? *d_n : n_static;
-    if (n > n_cap) n = n_cap;
-    if (compact) {
-        live_prefix<kThreads / 64>(lb, s_lpre, s_tmp);
-        n = s_lpre[256] * (uint32_t)kBoxSplats;
-    }
+    uint32_t n = active_count(d_n, n_static, n_cap);
+    if (compact) n = live_prefix<kThreads / 64>(lb, s_lpre, s_tmp);
     const uint32_t nchunks = (n + CHUNK - 1) / CHUNK;
     const int lane = threadIdx.x & 63;
     const int w = threadIdx.x >> 6;
@@ -550,13 +532,7 @@ __global__ __launch_bounds__(kThreads, (ATOMIC_RANK && MODE == MODE_KEYS && SORT
         // fifth wave per SIMD: 16-byte loads)
         constexpr int kPosBatch = 4;
         float4 pp[MODE == MODE_CULL ? kPosBatch : 1];
-        // storage index of virtual position i (== i without a list); `in`: the position holds a splat
-        auto locate = [&](uint32_t i, bool& in) -> uint32_t {
-            if (!compact) { in = i < n; return i; }
-            const uint32_t e = i - chunk * CHUNK, bx = s_box[e / kBoxSplats], st = bx * kBoxSplats + (e % kBoxSplats);
-            in = bx != 0xFFFFFFFFu && st < lb.n_storage;
-            return st;
-        };
+        const LiveChunk lc{lb, s_box, compact, chunk * CHUNK, n};
 #pragma unroll
         for (int r = 0; r < ITEMS; ++r) {
             if (MODE == MODE_CULL && (r % kPosBatch) == 0) {
@@ -564,7 +540,7 @@ __global__ __launch_bounds__(kThreads, (ATOMIC_RANK && MODE == MODE_KEYS && SORT
                 for (int k = 0; k < kPosBatch; ++k)
                     if (r + k < ITEMS) {
                         bool in;
-                        const uint32_t st = locate(base + (r + k) * 64 + lane, in);
+                        const uint32_t st = lc.storage_of(base + (r + k) * 64 + lane, in);
                         pp[k] = pos[in ? st : 0u];
                     }
             }
@@ -574,7 +550,7 @@ __global__ __launch_bounds__(kThreads, (ATOMIC_RANK && MODE == MODE_KEYS && SORT
             val[r] = 0;
             if (MODE == MODE_CULL) {
                 bool in;
-                const uint32_t st = locate(i, in);
+                const uint32_t st = lc.storage_of(i, in);
                 valid[r] = in && cull_key<BAND>(pp[r % kPosBatch], fp, key[r]);
                 val[r] = st;
             } else if (valid[r]) {
@@ -632,15 +608,7 @@ __global__ __launch_bounds__(kThreads, (ATOMIC_RANK && MODE == MODE_KEYS && SORT
         }
         __syncthreads();
         uint32_t wave_col = 0;
-        if (MODE == MODE_PAIR) {       // column of the wave's first input position: last c with s_col[c] <= base
-            uint32_t lo = 0, hi = 255;
-#pragma unroll
-            for (int s = 0; s < 8; ++s) {
-                const uint32_t mid = (lo + hi + 1u) >> 1;
-                if (s_col[mid] <= base) lo = mid; else hi = mid - 1u;
-            }
-            wave_col = lo;
-        }
+        if (MODE == MODE_PAIR) wave_col = last_le<8>(s_col, base, 255u);      // column of the wave's first input position
 #pragma unroll
         for (int r = 0; r < ITEMS; ++r) {
             if (ATOMIC_RANK ? lrank[r] != 0xFFFFFFFFu : valid[r]) {
@@ -717,30 +685,6 @@ __device__ __forceinline__ void ws_digit_range(int pass, uint32_t minkey, int& s
     const int b1 = (rem + 1) >> 1;                       // <= 11 since B <= 32
     if (pass == 1) { shift = kWsBits0; bits = b1; }
     else { shift = kWsBits0 + b1; bits = rem - b1; }
-}
-
-// inclusive scan of one uint32 per thread across a workgroup of WAVES waves (s_tmp: WAVES words); ends with a barrier
-template <int WAVES>
-__device__ __forceinline__ uint32_t ws_block_incl_scan(uint32_t v, uint32_t* s_tmp, uint32_t& total)
-{
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t t = __shfl_up(v, d, 64);
-        if (lane >= d) v += t;
-    }
-    if (lane == 63) s_tmp[w] = v;
-    __syncthreads();
-    uint32_t off = 0;
-    total = 0;
-#pragma unroll
-    for (int k = 0; k < WAVES; ++k) {
-        const uint32_t s = s_tmp[k];
-        if (k < w) off += s;
-        total += s;
-    }
-    __syncthreads();
-    return v + off;
 }
 
 // Sum of n0 rows at rows0 plus n1 rows at rows1 (rows of `nbins` uint32, nbins = 256..2048), as quads: thread t receives in
@@ -845,12 +789,8 @@ __global__ __launch_bounds__(THREADS) void ws_upsweep(const uint32_t* __restrict
     if (gsum_zero != nullptr)
         for (uint32_t i = blockIdx.x * THREADS + threadIdx.x; i < gsum_zero_words; i += gridDim.x * THREADS) gsum_zero[i] = 0u;
     if (CULL && blockIdx.x == 0 && threadIdx.x == 0) *minkey_next = 0xFFFFFFFFu;      // the other frame parity's word
-    uint32_t n = d_n ? *d_n : n_static;
-    if (n > n_cap) n = n_cap;
-    if (compact) {
-        live_prefix<WAVES>(lb, s_lpre, s_tmpw);
-        n = s_lpre[256] * (uint32_t)kBoxSplats;                 // virtual positions (the cloud's last box may be partial: see `in`)
-    }
+    uint32_t n = active_count(d_n, n_static, n_cap);
+    if (compact) n = live_prefix<WAVES>(lb, s_lpre, s_tmpw);
     int shift, bits;
     ws_digit_range(pass, CULL ? 0u : *minkey_cur, shift, bits);
     const uint32_t nbins = 1u << bits, dmask = nbins - 1u;
@@ -871,19 +811,13 @@ __global__ __launch_bounds__(THREADS) void ws_upsweep(const uint32_t* __restrict
         const uint32_t base = chunk * CHUNK + (uint32_t)sub * (IPS * THREADS);
         float4 pp[CULL ? IPS : 1];
         uint32_t kk[CULL ? 1 : IPS];
-        // storage index of virtual position i (== i without a list); `in`: the position holds a splat
-        auto locate = [&](uint32_t i, bool& in) -> uint32_t {
-            if (!compact) { in = i < n; return i; }
-            const uint32_t e = i - chunk * CHUNK, bx = s_box[e / kBoxSplats], st = bx * kBoxSplats + (e % kBoxSplats);
-            in = bx != 0xFFFFFFFFu && st < lb.n_storage;
-            return st;
-        };
+        const LiveChunk lc{lb, s_box, compact, chunk * CHUNK, n};
 #pragma unroll
         for (int r = 0; r < IPS; ++r) {
             const uint32_t i = base + r * THREADS + threadIdx.x;
             if (CULL) {
                 bool in;
-                const uint32_t st = locate(i, in);
+                const uint32_t st = lc.storage_of(i, in);
                 pp[r] = pos[in ? st : 0u];                                              // (the cloud has >= 1 splat inside this loop)
             } else {
                 kk[r] = keys_in[min(i, n - 1u)];                                        // n >= 1 inside this loop
@@ -896,7 +830,7 @@ __global__ __launch_bounds__(THREADS) void ws_upsweep(const uint32_t* __restrict
             bool ok = false;
             if (CULL) {
                 bool in;
-                (void)locate(i, in);
+                (void)lc.storage_of(i, in);
                 if (in) ok = cull_key<CULL == 2>(pp[r], fp, key);
             } else if (i < n) {
                 key = kk[r];
@@ -974,10 +908,7 @@ __global__ __launch_bounds__(THREADS, ITEMS == 8 ? 4 : 2) void ws_downsweep(
 
     uint32_t n = CULL ? n_static : *d_n;         // (pass 0 walks the cloud, the later passes the visible count left on the device)
     if (n > n_cap) n = n_cap;
-    if (compact) {
-        live_prefix<WAVES>(lb, s_lpre, s_tmp);
-        n = s_lpre[256] * (uint32_t)kBoxSplats;
-    }
+    if (compact) n = live_prefix<WAVES>(lb, s_lpre, s_tmp);
     int shift, bits;
     ws_digit_range(pass, CULL ? 0u : *minkey_cur, shift, bits);
     const uint32_t nbins = 1u << bits, dmask = nbins - 1u, Q = nbins >> 2, half = nbins >> 1;
@@ -998,7 +929,7 @@ __global__ __launch_bounds__(THREADS, ITEMS == 8 ? 4 : 2) void ws_downsweep(
             const bool own = (uint32_t)t + (uint32_t)k * THREADS < Q;
             const uint32_t tsum = own ? tot[k].x + tot[k].y + tot[k].z + tot[k].w : 0u;
             uint32_t total;
-            const uint32_t e = run + ws_block_incl_scan<WAVES>(tsum, s_tmp, total) - tsum;
+            const uint32_t e = run + block_incl_scan<WAVES>(tsum, s_tmp, total) - tsum;
             gbase[k][0] = e; gbase[k][1] = e + tot[k].x; gbase[k][2] = gbase[k][1] + tot[k].y; gbase[k][3] = gbase[k][2] + tot[k].z;
             run += total;
         }
@@ -1069,7 +1000,7 @@ __global__ __launch_bounds__(THREADS, ITEMS == 8 ? 4 : 2) void ws_downsweep(
             }
             const uint32_t tsum = tot[0] + tot[1] + tot[2] + tot[3];
             uint32_t part_total;
-            const uint32_t e = chunk_count + ws_block_incl_scan<WAVES>(tsum, s_tmp, part_total) - tsum;
+            const uint32_t e = chunk_count + block_incl_scan<WAVES>(tsum, s_tmp, part_total) - tsum;
             chunk_count += part_total;
             if (own) {
                 uint32_t run[4] = {e, e + tot[0], e + tot[0] + tot[1], e + tot[0] + tot[1] + tot[2]};

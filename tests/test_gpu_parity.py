@@ -1385,7 +1385,7 @@ def test_sort_exact_for_every_key_range(zf, z, n, frame_mode):
 
 def test_wide_sort_and_legacy_sort_and_tile_tables_agree(monkeypatch):
     """MSPLAT_SORT=lsd8 (four 8-bit passes: the fallback without lane-ordered LDS atomics) and the in-flight kernel selection
-    (256-thread sort workgroups, tile_start_kernel / tile_order_kernel instead of the row pass's counts; msplat_config.frame_mode)
+    (256-thread sort workgroups; msplat_config.frame_mode)
     against the default: bit-identical keys, permutation, bin lists and pixels"""
     from splatapult_amd import _capi
     cloud = scenes.synth_cloud(150000, 77, log_scale_mean=-3.6)
