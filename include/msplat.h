@@ -108,8 +108,7 @@ int msplat_tile_size(void);                             /* edge of the square sc
 
 /* ---- upload: SplatRenderer::Init + BuildVertexArrayObject (splatrenderer.cpp:50-151,345-391).  Copies the interleaved
  * cloud (host memory, n records of stride_bytes) to the device; the caller may free it afterwards. */
-int msplat_upload_cloud(msplat_ctx* ctx, const void* aos, uint64_t n, uint32_t stride_bytes,
-                        const msplat_attr_offsets* off, int full_sh);
+int msplat_upload_cloud(msplat_ctx* ctx, const void* aos, uint64_t n, uint32_t stride_bytes, const msplat_attr_offsets* off, int full_sh);
 /* GPU ingest (SURVEY.md 8f-1): GaussianCloud::ImportPly's per-vertex math (gaussiancloud.cpp:254-361) as a HIP kernel over the raw PLY vertex block.
  * Byte offsets of the float properties in one vertex; -1 = absent (reads as 0, like BinaryAttribute::Read); without all of f_rest, or full_sh == 0: SH degree 0 (:188-205). */
 typedef struct msplat_ply_layout {
@@ -144,6 +143,15 @@ int msplat_sort(msplat_ctx* ctx, const float cameraMat[16], const float projMat[
  * MSPLAT_ERR_PAIR_OVERFLOW; sort / render, whose own work is done: _EARLIER.  That frame lacks splats in its last bin columns: render it again. */
 int msplat_render(msplat_ctx* ctx, const float cameraMat[16], const float projMat[16], const float viewport[4],
                   const float nearFar[2], void* rgba, uint64_t pitch_bytes, int out_is_device);
+/* ---- msplat_render plus a depth plane (INTEGRATION.md 14).  depth == NULL: msplat_render.  Else W x H float32 on every context (fp16 cannot resolve z_w near
+ * 1), row 0 = GL bottom, depth_pitch_bytes between rows (0 = tight), in `rgba`'s memory space.  With z_i = 0.5 ndc.z + 0.5 (window depth of splat i), T as above:
+ * depth = sum_i T_i w_i z_i + T * 1.0 -- the expected window depth over GL's clear depth 1.0 (app.cpp:160), MSPLAT_TARGET_LOAD's formula with colour z, dst = 1:
+ * in [0, 1], exactly 1.0 where no splat reaches.  Early termination leaves T below t_epsilon, not at its limit: the plane is high by <= t_epsilon; t_epsilon = 0
+ * removes the error.  Colour: msplat_render's bit for bit; the plane is the same in every target mode; banded contexts write owned rows.  MSPLAT_ERR_UNSUPPORTED
+ * with msplat_set_depth_test, a target emulation, points or the tile probe; _INVALID_ARG: depth pitch < 4 W or not a multiple of 4.  Out of scope: msplat_render_stereo
+ * (call per eye), the device group, msplat_band_exchange of the plane. */
+int msplat_render_depth(msplat_ctx* ctx, const float cameraMat[16], const float projMat[16], const float viewport[4], const float nearFar[2],
+                        void* rgba, uint64_t pitch_bytes, float* depth, uint64_t depth_pitch_bytes, int out_is_device);
 /* the reference's VR frame -- Sort with the first eye, Render per eye (app.cpp:603-607) -- as ONE chain of launches; the same
  * pixels as two msplat_render calls, bit for bit.  Host targets, banded contexts, points and the emulations go view by view. */
 int msplat_render_stereo(msplat_ctx* ctx, const float cameraMat0[16], const float projMat0[16], const float cameraMat1[16],
@@ -199,8 +207,7 @@ msplat_ctx* msplat_group_context(msplat_group* g, uint32_t i);  /* borrowed: sta
 int msplat_group_peer_store(const msplat_group* g, uint32_t i); /* 1: rank i writes device 0's framebuffer directly */
 int msplat_group_set_exchange(msplat_group* g, int32_t exchange);  /* MSPLAT_EXCHANGE_*; also MSPLAT_GROUP_EXCHANGE=rccl|copy|peer */
 int msplat_group_get_exchange(const msplat_group* g);              /* the exchange the latest msplat_group_render used */
-int msplat_group_upload_cloud(msplat_group* g, const void* aos, uint64_t n, uint32_t stride_bytes,
-                              const msplat_attr_offsets* off, int full_sh);
+int msplat_group_upload_cloud(msplat_group* g, const void* aos, uint64_t n, uint32_t stride_bytes, const msplat_attr_offsets* off, int full_sh);
 int msplat_group_upload_gaussian_cloud(msplat_group* g, const msplat_cloud* c);
 int msplat_group_upload_ply(msplat_group* g, const char* path, int import_full_sh);
 int msplat_group_set_cloud_storage(msplat_group* g, int32_t storage);   /* msplat_set_cloud_storage on every context */
@@ -208,12 +215,10 @@ int msplat_group_set_cloud_storage(msplat_group* g, int32_t storage);   /* mspla
 int msplat_group_set_target_mode(msplat_group* g, int32_t mode);
 int msplat_group_set_layout(msplat_group* g, int32_t kind, int32_t block_rows);
 int msplat_group_set_band_cull(msplat_group* g, int enable);
-int msplat_group_sort(msplat_group* g, const float cameraMat[16], const float projMat[16], const float viewport[4],
-                      const float nearFar[2]);
+int msplat_group_sort(msplat_group* g, const float cameraMat[16], const float projMat[16], const float viewport[4], const float nearFar[2]);
 int msplat_group_render(msplat_group* g, const float cameraMat[16], const float projMat[16], const float viewport[4],
                         const float nearFar[2], void* rgba, uint64_t pitch_bytes, int out_is_device);
 int msplat_group_synchronize(msplat_group* g);
-
 /* ---- results of the latest Sort / Render (these synchronise) ---- */
 int msplat_sort_count(msplat_ctx* ctx, uint32_t* v);            /* sortCount (splatrenderer.cpp:198-199) */
 /* the element buffer of splatrenderer.cpp:296-311: upload indices of the visible splats in draw order (ascending key = far to near; ties by storage slot) */
@@ -223,7 +228,6 @@ int msplat_get_sorted_keys(msplat_ctx* ctx, uint32_t* dst, uint32_t cap);
 int msplat_get_storage_order(msplat_ctx* ctx, uint32_t* dst, uint64_t cap, int* reordered);
 int msplat_get_stats(msplat_ctx* ctx, msplat_stats* out);
 int msplat_get_timings(msplat_ctx* ctx, msplat_timings* out);
-
 /* ---- what the GL app's render target does (for callers who diff against its pixels; draw-order walk, several times slower).  Depth test
  * (SURVEY.md 8f-4): GL_DEPTH_TEST is on (app.cpp:163) and live wherever the target has a depth attachment (default back buffer, 24 bits,
  * sdl_main.cpp:79; XR swapchains); bits = 0 (default) models the colour-only --fp16 / --fp32 FBO.  Target rounding (SURVEY.md 8a-12, app.cpp:1012-1020):
@@ -240,7 +244,6 @@ int msplat_set_target_emulation(msplat_ctx* ctx, int rop);
  * whichever call comes second: a non-CLEAR mode with a target emulation != MSPLAT_ROP_NONE, a point cloud, or (at the Render) msplat_set_tile_probe. */
 int msplat_set_target_mode(msplat_ctx* ctx, int32_t mode);
 int msplat_get_target_mode(const msplat_ctx* ctx);          /* -1: NULL */
-
 /* ---- scene data: GaussianCloud / Ply (gaussiancloud.h:17-91, ply.h:19-46) ---- */
 msplat_cloud* msplat_cloud_create(int import_full_sh);          /* GaussianCloud::GaussianCloud(Options{importFullSH}) */
 void msplat_cloud_destroy(msplat_cloud* c);
@@ -258,7 +261,6 @@ const void* msplat_cloud_raw_data(const msplat_cloud* c);       /* GetRawDataPtr
 int msplat_cloud_has_full_sh(const msplat_cloud* c);            /* HasFullSH */
 int msplat_cloud_attr_offsets(const msplat_cloud* c, msplat_attr_offsets* out);   /* Get*Attrib */
 int msplat_upload_gaussian_cloud(msplat_ctx* ctx, const msplat_cloud* c);
-
 /* ---- scene config files + image output (SURVEY.md 8f-2, 8f-3; host only) ---- */
 /* CamerasConfig::ImportJson (camerasconfig.cpp:20-67): camera-to-world matrices (float[16] each) and the two fov angles */
 int msplat_cameras_import_json(const char* path, float* mats16_out, float* fovs2_out, uint32_t cap, uint32_t* count_out);
@@ -270,7 +272,6 @@ int msplat_find_config_file(const char* ply_path, const char* config_name, char*
 int msplat_write_image(const char* path, const float* rgba, int width, int height, int encode_srgb);
 /* 8-bit non-interlaced PNG (what Image::Load accepts, core/image.cpp:72-101) -> RGBA8, top row first; NULL queries the size */
 int msplat_read_image(const char* path, uint8_t* rgba8_out, uint64_t cap, uint32_t* width_out, uint32_t* height_out);
-
 /* ---- point-cloud renderer (SURVEY.md 8f-4): PointCloud (pointcloud.h:15-48) + PointRenderer (pointrenderer.h:23-57, pointrenderer.cpp:48-196).
  * A context holds EITHER a splat cloud or a point cloud; with points, msplat_sort is the same presort + radix sort and msplat_render the sprite
  * pipeline (point_*.glsl + the blend state of app.cpp:153-156): PointRenderer::Render == msplat_sort + msplat_render with the same matrices. */
@@ -287,7 +288,6 @@ int msplat_upload_points(msplat_ctx* ctx, const void* aos, uint64_t n, uint32_t 
 int msplat_upload_point_cloud(msplat_ctx* ctx, const msplat_points* p);
 /* the sprite (texture/sphere.png, pointrenderer.cpp:54-64): RGBA8, top row first (Image::Load's flip + premultiplication, mip chain); NULL = built-in sphere */
 int msplat_set_point_sprite(msplat_ctx* ctx, const uint8_t* rgba8, uint32_t width, uint32_t height);
-
 /* ---- host matrix helpers used by the shims (glm closed forms; app.cpp:1042, util.cpp:420) ---- */
 void msplat_mat4_inverse(const float m[16], float out[16]);
 void msplat_mat4_mul(const float a[16], const float b[16], float out[16]);

@@ -69,6 +69,11 @@ constexpr int kCompOcc = 5;        // occupancy bound handed to the compiler (<=
 // against r3's 79 / 5) and takes the eleven words of CompParams instead of five 4x4 matrices.
 // TM = MSPLAT_TARGET_* (msplat_set_target_mode): what the final store -- the one place that writes pixels -- does with the target's
 // contents.  kTargetClear: (C, 1), the code of every instantiation that existed before the parameter.  The inner loop never sees it.
+// DEPTH (msplat_render_depth): the frame also hands out a W x H float32 depth plane -- window depth as one more colour channel, blended
+// over GL's clear depth 1.0 (app.cpp:160):  depth = sum_i T_i w_i z_i + T,  z_i = 0.5 ndc.z + 0.5 of splat i (project_kernel's out_zq with
+// depth_bits = 32: the float's bits).  z rides in the free word of the staged record, the inner loop gains one packed FMA per strip pair
+// and the final store writes the plane next to the colour, same lane, once.  DEPTH = false: the code of every instantiation that existed
+// before the parameter.
 constexpr int kTargetClear = 0, kTargetLoad = 1, kTargetPremultiplied = 2;      // MSPLAT_TARGET_* (include/msplat.h)
 struct CompExtra {
     void* out1;                  // TWO_VIEWS: the second view's target (bin rows >= rows_view belong to it)
@@ -76,9 +81,13 @@ struct CompExtra {
     float4* state;               // OCC != 0: (r, g, b, 2^118 T) per pixel of the tiles pass 1 leaves unfinished
     const uint32_t* d_nbins;     // OCC == 2: `order` lists *d_nbins bins -- the unfinished ones -- and the items are theirs alone
     uint32_t* probe;             // PROBE: 8 words per work item
+    const float* zw;             // DEPTH: window depth per rank
+    float* depth;                // DEPTH: the depth plane, rows of depth_pitch bytes (row 0 = GL bottom, like the colour)
+    size_t depth_pitch;
+    float* zstate;               // DEPTH, OCC != 0: the depth accumulator per pixel, beside `state`
 };
 
-template <bool F16, int OCC, bool TWO_VIEWS, bool PROBE, int TM = kTargetClear>
+template <bool F16, int OCC, bool TWO_VIEWS, bool PROBE, int TM = kTargetClear, bool DEPTH = false>
 __global__ __launch_bounds__(kCompThreads, kCompOcc) void composite_kernel(const uint32_t* __restrict__ tile_start,
                                                                  const uint32_t* __restrict__ pairs,
                                                                  const float4* __restrict__ rec,
@@ -176,12 +185,13 @@ __global__ __launch_bounds__(kCompThreads, kCompOcc) void composite_kernel(const
     // op in ~4 cycles but a packed v_pk_{fma,mul,add}_f32 does two per lane in the same slot (measured:
     // SQ_ACTIVE_INST_VALU / SQ_INSTS_VALU = 4.4 cycles), and this kernel is VALU bound.
     typedef float v2f __attribute__((ext_vector_type(2)));
-    v2f T[NP], cr[NP], cg[NP], cb[NP];
+    v2f T[NP], cr[NP], cg[NP], cb[NP], cz[NP];      // cz: DEPTH only
     bool inside[NS];
 #pragma unroll
     for (int h = 0; h < NP; ++h) {
         T[h] = (v2f){kScale, kScale};                // the transmittance scaled by 2^118
         cr[h] = (v2f){0.0f, 0.0f}; cg[h] = (v2f){0.0f, 0.0f}; cb[h] = (v2f){0.0f, 0.0f};
+        cz[h] = (v2f){0.0f, 0.0f};
     }
 #pragma unroll
     for (int k = 0; k < NS; ++k) inside[k] = (x < fp.width) && (ybase + 4 * k < fp.height);
@@ -191,6 +201,7 @@ __global__ __launch_bounds__(kCompThreads, kCompOcc) void composite_kernel(const
             if (inside[k]) {
                 const float4 st = state[(size_t)(ybase + 4 * k) * fp.width + x];
                 cr[k >> 1][k & 1] = st.x; cg[k >> 1][k & 1] = st.y; cb[k >> 1][k & 1] = st.z; T[k >> 1][k & 1] = st.w;
+                if (DEPTH) cz[k >> 1][k & 1] = ex.zstate[(size_t)(ybase + 4 * k) * fp.width + x];
             }
         }
     }
@@ -222,11 +233,13 @@ __global__ __launch_bounds__(kCompThreads, kCompOcc) void composite_kernel(const
     hiA -= cntA;
     uint32_t cnt = cntA;                                       // batch whose records are in p0..p2
     float4 p0 = make_float4(0, 0, 0, 0), p1 = p0, p2 = p0;
+    float pz = 0.0f;                                           // DEPTH: the window depth that travels with the record
     if (lane < (int)cnt) {
         uint32_t rk = rankA & kRankMask;
         asm volatile("" : "+v"(rk));              // keep the mask out of the address arithmetic (see composite_depth_kernel)
         const float4* src = rec + (size_t)rk * 3;
         p0 = src[0]; p1 = src[1]; p2 = src[2];
+        if (DEPTH) pz = ex.zw[rk];
     }
     cntA = min((uint32_t)kCompThreads, hiA - start);
     if (lane < (int)cntA) rankA = pairs[hiA - 1u - lane];
@@ -293,7 +306,7 @@ __global__ __launch_bounds__(kCompThreads, kCompOcc) void composite_kernel(const
                 // land in even VGPRs, which a packed operand can name directly (an odd one costs a v_mov)
                 s_rec[slot * 3 + 0] = make_float4(qc, c0, p1.z, c1);
                 s_rec[slot * 3 + 1] = make_float4(p1.w, c2, p2.x, qa);
-                s_rec[slot * 3 + 2] = make_float4(qb, 0.0f, 0.0f, 0.0f);
+                s_rec[slot * 3 + 2] = make_float4(qb, DEPTH ? pz : 0.0f, 0.0f, 0.0f);
             }
         }
         __syncthreads();
@@ -303,6 +316,7 @@ __global__ __launch_bounds__(kCompThreads, kCompOcc) void composite_kernel(const
             asm volatile("" : "+v"(rk));
             const float4* src = rec + (size_t)rk * 3;
             p0 = src[0]; p1 = src[1]; p2 = src[2];
+            if (DEPTH) pz = ex.zw[rk];
         }
         cntA = min((uint32_t)kCompThreads, hiA - start);
         if (lane < (int)cntA) rankA = pairs[hiA - 1u - lane];
@@ -316,16 +330,19 @@ __global__ __launch_bounds__(kCompThreads, kCompOcc) void composite_kernel(const
             float4 a = s_rec[0];          // c5, c0, r, c1
             float4 b = s_rec[1];          // g, c2, b, c3
             float c4 = s_rec[2].x;
+            float z = DEPTH ? s_rec[2].y : 0.0f;
 #pragma unroll 2
             for (uint32_t j = 0; j < n; ++j) {
                 // next record (slot n is a harmless over-read inside the 65-slot array)
                 const float4 na = s_rec[(j + 1) * 3 + 0];
                 const float4 nb = s_rec[(j + 1) * 3 + 1];
                 const float nc4 = s_rec[(j + 1) * 3 + 2].x;
+                const float nz = DEPTH ? s_rec[(j + 1) * 3 + 2].y : 0.0f;
                 const float base = __builtin_fmaf(__builtin_fmaf(b.w, u, a.w), u, a.y);      // c0 + c1 u + c3 u^2
                 const float lin = __builtin_fmaf(c4, u, b.y);                                // c2 + c4 u
                 const v2f vbase = (v2f){base, base}, vlin = (v2f){lin, lin}, vC = (v2f){a.x, a.x};
                 const v2f vr = (v2f){a.z, a.z}, vg = (v2f){b.x, b.x}, vb = (v2f){b.z, b.z};
+                const v2f vz = (v2f){z, z};
                 // Branch-free on purpose: the strips are independent dependency chains inside one basic
                 // block, so the in-order wave can overlap them.  w = 0 where the fragment shader discards.
 #pragma unroll
@@ -340,9 +357,10 @@ __global__ __launch_bounds__(kCompThreads, kCompOcc) void composite_kernel(const
                     cr[h] = __builtin_elementwise_fma(tw, vr, cr[h]);
                     cg[h] = __builtin_elementwise_fma(tw, vg, cg[h]);
                     cb[h] = __builtin_elementwise_fma(tw, vb, cb[h]);
+                    if (DEPTH) cz[h] = __builtin_elementwise_fma(tw, vz, cz[h]);
                     T[h] = __builtin_elementwise_fma(tw, (v2f){-kScale, -kScale}, T[h]);
                 }
-                a = na; b = nb; c4 = nc4;
+                a = na; b = nb; c4 = nc4; z = nz;
             }
         }
         if (PROBE) probe_inner += clock64() - probe_t1;
@@ -377,6 +395,11 @@ __global__ __launch_bounds__(kCompThreads, kCompOcc) void composite_kernel(const
         for (int k = 0; k < NS; ++k)
             if (inside[k])
                 state[(size_t)(ybase + 4 * k) * fp.width + x] = make_float4(cr[k >> 1][k & 1], cg[k >> 1][k & 1], cb[k >> 1][k & 1], T[k >> 1][k & 1]);
+        if (DEPTH) {
+#pragma unroll
+            for (int k = 0; k < NS; ++k)
+                if (inside[k]) ex.zstate[(size_t)(ybase + 4 * k) * fp.width + x] = cz[k >> 1][k & 1];
+        }
     }
 #pragma unroll
     for (int k = 0; k < NS; ++k) {
@@ -413,6 +436,13 @@ __global__ __launch_bounds__(kCompThreads, kCompOcc) void composite_kernel(const
                 if (F16) asm volatile("" : "+v"(px.x), "+v"(px.y), "+v"(px.z), "+v"(px.w));
             }
             store_px<F16>(row, x, px);
+            if (DEPTH) {
+                // expected window depth over the clear depth 1.0: the blend of kTargetLoad with colour z and dst = 1 (T = 2^-118 Ts is
+                // exact; a pixel no splat reached reads exactly 1).  Every z is <= 1 and the weights sum to 1 - T, but the partial sums
+                // are rounded: the minimum keeps the plane inside [0, 1] when z_w sits at 1
+                float* zrow = (float*)((char*)ex.depth + (size_t)(ybase + 4 * k) * ex.depth_pitch);
+                zrow[x] = fminf(cz[k >> 1][k & 1] + T[k >> 1][k & 1] * 0x1p-118f, 1.0f);
+            }
         }
     }
     __syncthreads();      // s_rec is reused by the next tile

@@ -177,7 +177,7 @@ struct msplat_ctx {
     uint64_t rank_cap = 0;      // draw-order ranks rec2d / rect / hist1 ... are sized for: N, or 2 N + 64 once msplat_render_stereo ran
     Buf rec2d;      // float4[3*N]
     Buf rect;       // uint32[N]
-    Buf zq;         // uint32[N] quantised window depth per rank (only with msplat_set_depth_test)
+    Buf zq;         // uint32[N] quantised window depth per rank (msplat_set_depth_test), or its float bits (msplat_render_depth)
     int depth_bits = 0;
     int rop = 0;            // render-target emulation for the draw-order compositor (msplat_set_target_emulation)
     int target_mode = MSPLAT_TARGET_CLEAR;     // what a Render does with the target's contents (msplat_set_target_mode)
@@ -195,6 +195,7 @@ struct msplat_ctx {
     Buf hist2;      // uint32[256 * hist2_stride]
     uint32_t hist2_stride = 0;
     Buf fb;         // internal framebuffer for host-output renders
+    Buf fbz;        // ... and their depth plane (msplat_render_depth): float[W * H]
     Buf probe;      // uint32[8 * work items] compositor probe (msplat_set_tile_probe)
     bool probe_on = false;
     // device-output renders never synchronise: a pair-buffer overflow is left in host-mapped memory by the
@@ -225,6 +226,7 @@ struct msplat_ctx {
     uint32_t two_pass_sets_mask = 0;         // timing sets recorded by two-pass frames
     // two-pass frame with occlusion feedback (msplat_occlusion.hip.h)
     Buf occ, occ_mask, occ_fin, occ_state, occ_live, occ_boxdead, occ_unf;
+    Buf occ_zstate;                          // float[W * H]: the depth accumulator beside occ_state (allocated by the first two-pass depth frame)
     int two_pass_mode = MSPLAT_TWO_PASS_AUTO;
     float occ_frac = 0.15f;                  // share of the visible splats that goes into pass 1 (0.15-0.3 is the optimum of the blobs, 0.02 of a camera inside a scene)
     uint32_t occ_streak = 0;                 // consecutive two-pass frames submitted (their feedback describes two-pass frames)
@@ -950,7 +952,8 @@ static int with_pending_overflow(msplat_ctx* ctx, Work&& work)
 
 static int sort_impl(msplat_ctx* ctx, const float cameraMat[16], const float projMat[16], const float viewport[4], const float nearFar[2]);
 static int render_impl(msplat_ctx* ctx, const float cameraMat[16], const float projMat[16], const float viewport[4],
-                       const float nearFar[2], void* rgba, uint64_t pitch_bytes, int out_is_device);
+                       const float nearFar[2], void* rgba, uint64_t pitch_bytes, int out_is_device, float* depth = nullptr,
+                       uint64_t depth_pitch_bytes = 0);
 
 int msplat_sort(msplat_ctx* ctx, const float cameraMat[16], const float projMat[16],
                 const float viewport[4], const float nearFar[2])
@@ -1280,6 +1283,8 @@ struct RenderChain {
     void *d_out, *d_out1;
     size_t pitch;
     bool async_overflow_flag;
+    float* d_depth;              // msplat_render_depth: the depth plane (NULL: a plain Render) and its pitch
+    size_t depth_pitch;
     // the compositor's schedule, decided where the bins are ordered (issue_binning) and used by issue_compositor
     bool ordered = true;
     uint32_t comp_items = 0, comp_pool = 0;
@@ -1299,8 +1304,14 @@ static void issue_projection(RenderChain& rc, int mode, float occ_frac)
                            (float4*)ctx->rec2d.p, (uint32_t*)ctx->rect.p, ctx->depth_bits ? (uint32_t*)ctx->zq.p : nullptr);
         return;
     }
-    const ProjParams pp = proj_params(fp);
+    ProjParams pp = proj_params(fp);
     uint32_t* zq = (mode != PROJ_LISTED && ctx->depth_bits) ? (uint32_t*)ctx->zq.p : nullptr;
+    if (rc.d_depth) {
+        // a depth frame: every projection of the frame leaves z_w = (float)(0.5 ndc.z + 0.5) per rank -- quantise_depth's 32-bit form
+        // is that float's bits (one product by 0.5, exact, and one rounded sum)
+        pp.depth_bits = 32;
+        zq = (uint32_t*)ctx->zq.p;
+    }
     auto project = [&](auto MODE, int grid, const uint32_t* dV, const ProjExtra& ex, const auto& v1) {
         with_flag(ctx->full_sh, [&](auto SH) {
             with_int<kStorageShFp16, kStorageFp32>(ctx->cloud_storage, [&](auto ST) {
@@ -1484,33 +1495,39 @@ static int issue_compositor(RenderChain& rc, int occ_pass, int ev_c0, int ev_c1)
         const int prio_mode = ordered ? 1 : 0;
         const int grid = (int)std::min<uint32_t>(comp_items, comp_pool);
         const CompParams cp = comp_params(fp);
-        const CompExtra ex{d_out1, fin, state, d_nbins, probe};
+        const CompExtra ex{d_out1, fin, state, d_nbins, probe, (const float*)ctx->zq.p, rc.d_depth, rc.depth_pitch,
+                           occ_pass ? (float*)ctx->occ_zstate.p : nullptr};
         const int prio = occ_pass == 2 ? 0 : prio_mode;
         // six of the twelve (OCC, TWO_VIEWS, PROBE) forms exist per format
         // (occlusion_plan never chooses two passes for two views in one chain or while the probe is on)
-        // and the four without the probe once more per non-CLEAR target mode (render_frame refuses the probe with those)
-        auto composite = [&](auto OCC, auto TWO, auto PROBE, auto TM) {
+        // and the four without the probe once more per non-CLEAR target mode (render_frame refuses the probe with those);
+        // a depth frame (one view, no probe: render_impl) has the three passes per target mode
+        auto composite = [&](auto OCC, auto TWO, auto PROBE, auto TM, auto DEPTH) {
             with_flag(f16, [&](auto F16) {
-                hipExtLaunchKernelGGL((composite_kernel<F16.value, OCC.value, TWO.value, PROBE.value, TM.value>), dim3(grid), dim3(kCompThreads), 0, s,
-                                      e0, e1, 0, ts, pb, r2, d_out, pitch, cp, cap, ord, d_queue, comp_items, prio, ex);
+                hipExtLaunchKernelGGL((composite_kernel<F16.value, OCC.value, TWO.value, PROBE.value, TM.value, DEPTH.value>), dim3(grid),
+                                      dim3(kCompThreads), 0, s, e0, e1, 0, ts, pb, r2, d_out, pitch, cp, cap, ord, d_queue, comp_items, prio, ex);
             });
         };
         constexpr flag_t<true> yes{};
         constexpr flag_t<false> no{};
         constexpr int_t<kTargetClear> clear{};
-        if (ctx->target_mode != MSPLAT_TARGET_CLEAR)
-            with_int<kTargetLoad, kTargetPremultiplied>(ctx->target_mode, [&](auto TM) {
-                if (occ_pass == 1) composite(int_t<1>{}, no, no, TM);
-                else if (occ_pass == 2) composite(int_t<2>{}, no, no, TM);
-                else if (stereo) composite(int_t<0>{}, yes, no, TM);
-                else composite(int_t<0>{}, no, no, TM);
+        if (rc.d_depth)
+            with_int<kTargetLoad, kTargetPremultiplied, kTargetClear>(ctx->target_mode, [&](auto TM) {
+                with_int<1, 2, 0>(occ_pass, [&](auto OCC) { composite(OCC, no, no, TM, yes); });
             });
-        else if (occ_pass == 1) composite(int_t<1>{}, no, no, clear);
-        else if (occ_pass == 2) composite(int_t<2>{}, no, no, clear);
-        else if (stereo && probe) composite(int_t<0>{}, yes, yes, clear);
-        else if (stereo) composite(int_t<0>{}, yes, no, clear);
-        else if (probe) composite(int_t<0>{}, no, yes, clear);
-        else composite(int_t<0>{}, no, no, clear);
+        else if (ctx->target_mode != MSPLAT_TARGET_CLEAR)
+            with_int<kTargetLoad, kTargetPremultiplied>(ctx->target_mode, [&](auto TM) {
+                if (occ_pass == 1) composite(int_t<1>{}, no, no, TM, no);
+                else if (occ_pass == 2) composite(int_t<2>{}, no, no, TM, no);
+                else if (stereo) composite(int_t<0>{}, yes, no, TM, no);
+                else composite(int_t<0>{}, no, no, TM, no);
+            });
+        else if (occ_pass == 1) composite(int_t<1>{}, no, no, clear, no);
+        else if (occ_pass == 2) composite(int_t<2>{}, no, no, clear, no);
+        else if (stereo && probe) composite(int_t<0>{}, yes, yes, clear, no);
+        else if (stereo) composite(int_t<0>{}, yes, no, clear, no);
+        else if (probe) composite(int_t<0>{}, no, yes, clear, no);
+        else composite(int_t<0>{}, no, no, clear, no);
         ctx->comp_kernel_timed = timed;
     } else {
         ctx->comp_kernel_timed = false;
@@ -1541,8 +1558,14 @@ static void issue_occlusion_gate(RenderChain& rc)
                        use_boxes ? (const uint32_t*)ctx->occ_boxdead.p : (const uint32_t*)nullptr, boxwords);
 }
 
+// the depth plane of a msplat_render_depth frame in device memory (p == NULL: a plain Render)
+struct DepthPlane {
+    float* p = nullptr;
+    size_t pitch = 0;
+};
+
 static int launch_render(msplat_ctx* ctx, const FrameParams& fp, void* d_out, size_t pitch, bool async_overflow_flag,
-                         void* d_out1 = nullptr, RenderPlan* plan = nullptr)
+                         void* d_out1 = nullptr, RenderPlan* plan = nullptr, DepthPlane depth = DepthPlane{})
 {
     hipStream_t s = ctx->stream;
     const bool stereo = fp.views == 2;
@@ -1550,7 +1573,7 @@ static int launch_render(msplat_ctx* ctx, const FrameParams& fp, void* d_out, si
     const uint32_t N = stereo ? (uint32_t)(2 * ctx->N + 64) : (uint32_t)ctx->N;
     RenderChain rc{ctx, fp, s, stereo, N, counters + 0, counters + 1, counters + 2, (uint32_t*)ctx->queue.p,
                    stereo ? counters + 9 : counters + 0, (uint32_t*)ctx->occ.p, fp.tiles_x * fp.tiles_y, (uint32_t)ctx->pair_cap,
-                   false, 0, (int)std::max(1u, div_up(N, kProjThreads)), d_out, d_out1, pitch, async_overflow_flag};
+                   false, 0, (int)std::max(1u, div_up(N, kProjThreads)), d_out, d_out1, pitch, async_overflow_flag, depth.p, depth.pitch};
     // Two-pass frame with occlusion feedback (msplat_occlusion.hip.h): the nearest R1 splats first, then only what the bins
     // they did not saturate still need.  Same pixels; chosen once per Render (occlusion_plan).  The retries of a host-output
     // frame whose pair buffer overflowed reuse the plan AND count as the same Render: the sampling counter, the two-pass
@@ -1564,6 +1587,13 @@ static int launch_render(msplat_ctx* ctx, const FrameParams& fp, void* d_out, si
         ctx->render_calls++;
     }
     const bool two_pass = plan->two_pass;
+    if (depth.p) {
+        // z_w per rank; the accumulator plane two passes hand over.  (A buffer that has to grow is freed first: hipFree waits for the
+        // frames that still read it.)
+        int arc = buf_alloc(ctx, ctx->zq, std::max<uint64_t>(std::max(ctx->rank_cap, ctx->N), 1) * 4);
+        if (!arc && two_pass) arc = buf_alloc(ctx, ctx->occ_zstate, (size_t)fp.width * fp.height * 4 + 64);
+        if (arc) return arc;
+    }
     const bool timed = rc.timed = ctx->ev_ok && ((ctx->render_calls - 1) % ctx->timing_stride) == 0;
     const int tset = rc.tset = (int)(ctx->render_sets % msplat_ctx::kEvSets);
     if (timed) HIP_TRY(ctx, hipEventRecord(ctx->ev[tset][2], s));
@@ -1614,6 +1644,17 @@ int msplat_render(msplat_ctx* ctx, const float cameraMat[16], const float projMa
                         });
 }
 
+// msplat_render plus a per-pixel depth plane (include/msplat.h); depth == NULL is msplat_render
+int msplat_render_depth(msplat_ctx* ctx, const float cameraMat[16], const float projMat[16], const float viewport[4],
+                        const float nearFar[2], void* rgba, uint64_t pitch_bytes, float* depth, uint64_t depth_pitch_bytes,
+                        int out_is_device)
+{
+    return submit_frame<false>(ctx, out_is_device && rgba, cameraMat, projMat, cameraMat, projMat, viewport, nearFar,
+                        [=](const float* cam, const float* proj, const float*, const float*, const float* vp, const float* nf) {
+                            return render_impl(ctx, cam, proj, vp, nf, rgba, pitch_bytes, out_is_device, depth, depth_pitch_bytes);
+                        });
+}
+
 // rows of the target: 0 = tightly packed (`tight` bytes)
 static int resolve_pitch(msplat_ctx* ctx, const char* who, const FrameParams& fp, uint64_t& pitch_bytes, size_t& tight)
 {
@@ -1627,12 +1668,13 @@ static int resolve_pitch(msplat_ctx* ctx, const char* who, const FrameParams& fp
 }
 
 // The rows of a host image that belong to the context, between the caller's buffer and the internal framebuffer: the whole image, or
-// (band mode) only the owned bin rows -- as documented for msplat_set_band, so several bands can be assembled in one host image
-static int copy_host_rows(msplat_ctx* ctx, const FrameParams& fp, void* rgba, uint64_t pitch_bytes, size_t tight, bool to_host)
+// (band mode) only the owned bin rows -- as documented for msplat_set_band, so several bands can be assembled in one host image.
+// `fb`: the internal plane (ctx->fb, or ctx->fbz for the depth plane of msplat_render_depth), rows of `tight` bytes
+static int copy_host_rows(msplat_ctx* ctx, const FrameParams& fp, void* rgba, uint64_t pitch_bytes, const Buf& fb, size_t tight, bool to_host)
 {
     auto copy = [&](int y0, int rows) {
         char* host = (char*)rgba + (size_t)y0 * pitch_bytes;
-        char* dev = (char*)ctx->fb.p + (size_t)y0 * tight;
+        char* dev = (char*)fb.p + (size_t)y0 * tight;
         return to_host ? hipMemcpy2D(host, pitch_bytes, dev, tight, tight, rows, hipMemcpyDeviceToHost)
                        : hipMemcpy2DAsync(dev, tight, host, pitch_bytes, tight, rows, hipMemcpyHostToDevice, ctx->stream);
     };
@@ -1652,22 +1694,30 @@ static int copy_host_rows(msplat_ctx* ctx, const FrameParams& fp, void* rgba, ui
     return MSPLAT_OK;
 }
 
-// host output: render into an internal device framebuffer, copy back, grow the pair buffer on overflow
-static int render_to_host(msplat_ctx* ctx, const FrameParams& fp, void* rgba, uint64_t pitch_bytes, size_t tight)
+// host output: render into an internal device framebuffer, copy back, grow the pair buffer on overflow.
+// depth (msplat_render_depth): a host plane of depth.pitch bytes per row, filled the same way from ctx->fbz -- every attempt writes
+// the whole internal plane, and the rows are copied after the one that did not overflow
+static int render_to_host(msplat_ctx* ctx, const FrameParams& fp, void* rgba, uint64_t pitch_bytes, size_t tight, DepthPlane depth)
 {
     int rc;
     if ((rc = buf_alloc(ctx, ctx->fb, tight * fp.height))) return rc;
+    const size_t ztight = (size_t)fp.width * sizeof(float);
+    if (depth.p && (rc = buf_alloc(ctx, ctx->fbz, ztight * fp.height))) return rc;
+    const DepthPlane dz{depth.p ? (float*)ctx->fbz.p : nullptr, ztight};
     RenderPlan plan;
     for (int attempt = 0; attempt < 6; ++attempt) {
         // MSPLAT_TARGET_LOAD: the caller's rows are the destination -- before EVERY attempt, because blending over the target is
         // not idempotent: a retry would otherwise run over the half-blended frame of the attempt that overflowed
-        if (ctx->target_mode == MSPLAT_TARGET_LOAD && (rc = copy_host_rows(ctx, fp, rgba, pitch_bytes, tight, false))) return rc;
-        rc = launch_render(ctx, fp, ctx->fb.p, tight, false, nullptr, &plan);
+        if (ctx->target_mode == MSPLAT_TARGET_LOAD && (rc = copy_host_rows(ctx, fp, rgba, pitch_bytes, ctx->fb, tight, false))) return rc;
+        rc = launch_render(ctx, fp, ctx->fb.p, tight, false, nullptr, &plan, dz);
         if (rc) return rc;
         uint32_t cnt[4];
         HIP_TRY(ctx, hipMemcpyAsync(cnt, ctx->counters.p, sizeof(cnt), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        if (cnt[2] == 0) return copy_host_rows(ctx, fp, rgba, pitch_bytes, tight, true);
+        if (cnt[2] == 0) {
+            if ((rc = copy_host_rows(ctx, fp, rgba, pitch_bytes, ctx->fb, tight, true))) return rc;
+            return depth.p ? copy_host_rows(ctx, fp, depth.p, depth.pitch, ctx->fbz, ztight, true) : MSPLAT_OK;
+        }
         // overflow: cnt[2] holds the required pair count
         const uint64_t need = (uint64_t)cnt[2] + (cnt[2] >> 2) + 1024;
         if (ctx->cfg.pair_capacity != 0 || need > 0x7FFFFFFFull)
@@ -1680,7 +1730,7 @@ static int render_to_host(msplat_ctx* ctx, const FrameParams& fp, void* rgba, ui
 
 // what every Render does once its FrameParams and pitch stand (rgba1: the second view of two in one chain)
 static int render_frame(msplat_ctx* ctx, const FrameParams& fp, void* rgba, void* rgba1, uint64_t pitch_bytes, size_t tight,
-                        int out_is_device)
+                        int out_is_device, DepthPlane depth = DepthPlane{})
 {
     int rc;
     ctx->last_fp = fp;
@@ -1690,8 +1740,8 @@ static int render_frame(msplat_ctx* ctx, const FrameParams& fp, void* rgba, void
     if (ctx->target_mode != MSPLAT_TARGET_CLEAR && ctx->probe_on)
         return fail(ctx, MSPLAT_ERR_UNSUPPORTED, "msplat_render: the tile probe (msplat_set_tile_probe) exists for MSPLAT_TARGET_CLEAR only");
     return with_pending_overflow(ctx, [&] {      // an EARLIER frame; this one is still rendered
-        const int r = out_is_device ? launch_render(ctx, fp, rgba, pitch_bytes, true, rgba1)
-                                    : render_to_host(ctx, fp, rgba, pitch_bytes, tight);
+        const int r = out_is_device ? launch_render(ctx, fp, rgba, pitch_bytes, true, rgba1, nullptr, depth)
+                                    : render_to_host(ctx, fp, rgba, pitch_bytes, tight, depth);
         if (r == MSPLAT_OK) ctx->has_render = true;
         return r;
     });
@@ -1699,15 +1749,30 @@ static int render_frame(msplat_ctx* ctx, const FrameParams& fp, void* rgba, void
 
 static int render_impl(msplat_ctx* ctx, const float cameraMat[16], const float projMat[16],
                        const float viewport[4], const float nearFar[2],
-                       void* rgba, uint64_t pitch_bytes, int out_is_device)
+                       void* rgba, uint64_t pitch_bytes, int out_is_device, float* depth, uint64_t depth_pitch_bytes)
 {
+    const char* who = depth ? "msplat_render_depth" : "msplat_render";
     FrameParams fp;
-    int rc = begin_frame(ctx, "msplat_render", true, rgba ? nullptr : "rgba is NULL", cameraMat, projMat, viewport, nearFar, fp);
+    int rc = begin_frame(ctx, who, true, rgba ? nullptr : "rgba is NULL", cameraMat, projMat, viewport, nearFar, fp);
     if (rc) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     size_t tight = 0;
-    if ((rc = resolve_pitch(ctx, "msplat_render", fp, pitch_bytes, tight))) return rc;
-    return render_frame(ctx, fp, rgba, nullptr, pitch_bytes, tight, out_is_device);
+    if ((rc = resolve_pitch(ctx, who, fp, pitch_bytes, tight))) return rc;
+    if (depth) {
+        // the plane comes from the front-to-back compositor's accumulators: the draw-order compositors (depth test, target
+        // emulation, sprites) and the probe's instantiations carry none
+        const char* why = ctx->point_mode ? "the context holds a point cloud (the sprite compositor has no depth output)"
+                          : ctx->depth_bits != 0 ? "msplat_set_depth_test is on (the draw-order compositor has no depth output)"
+                          : ctx->rop != MSPLAT_ROP_NONE ? "msplat_set_target_emulation is not MSPLAT_ROP_NONE (the draw-order compositor has no depth output)"
+                          : ctx->probe_on ? "the tile probe (msplat_set_tile_probe) has no instantiation with a depth output" : nullptr;
+        if (why) return fail(ctx, MSPLAT_ERR_UNSUPPORTED, "msplat_render_depth: %s", why);
+        const uint64_t ztight = (uint64_t)fp.width * sizeof(float);
+        if (depth_pitch_bytes == 0) depth_pitch_bytes = ztight;
+        if (depth_pitch_bytes < ztight || depth_pitch_bytes % sizeof(float) != 0)
+            return fail(ctx, MSPLAT_ERR_INVALID_ARG, "msplat_render_depth: depth pitch %llu too small / misaligned for width %d",
+                        (unsigned long long)depth_pitch_bytes, fp.width);
+    }
+    return render_frame(ctx, fp, rgba, nullptr, pitch_bytes, tight, out_is_device, DepthPlane{depth, (size_t)depth_pitch_bytes});
 }
 
 // buffers indexed by draw-order rank, for 2 N + 64 ranks (two views in one chain)

@@ -3,12 +3,14 @@
 // Sort + Render into an explicit RGBA32F framebuffer, dumped as a binary PPM-like float file.
 //
 //   g++ -std=c++17 -I. splatapult_amd/host/example_render.cpp -Lsplatapult_amd/lib -lmsplat -o example_render
-//   ./example_render scene.ply out.f32 [width height] [--nosh] [--frames-in-flight N] [--devices 0,1,2,...] [--over-gradient]
+//   ./example_render scene.ply out.f32 [width height] [--nosh] [--frames-in-flight N] [--devices 0,1,2,...] [--over-gradient] [--depth out_depth.f32]
 // With --frames-in-flight N the same frame is issued N + 1 times round-robin over N contexts that share the cloud
 // (SplatRenderer::SetFramesInFlight); the last one is written.  With --devices the frame's bin rows are dealt to the
 // listed GPUs (SplatRenderer::ConfigureDevices, msplat_group_*): same pixels.  With --over-gradient the target is first filled with
 // a vertical gradient -- standing in for what App::Render draws before the splats (app.cpp:1046-1063) -- and the frame is blended
 // over it (SplatRenderer::SetTargetMode(MSPLAT_TARGET_LOAD)), as the reference's Render does with its bound framebuffer.
+// With --depth the frame also hands out its depth plane (SplatRenderer::RenderWithDepth: W x H float32 window depth over the clear
+// depth 1.0, row 0 = bottom), written to the named file; one device only.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -28,11 +30,13 @@ int main(int argc, char** argv)
     bool nosh = false, overGradient = false;
     if (argc >= 5 && argv[3][0] != '-') { W = std::atoi(argv[3]); H = std::atoi(argv[4]); }
     int inFlight = 1;
+    const char* depthPath = nullptr;
     std::vector<int> devices;
     for (int i = 3; i < argc; ++i) {
         nosh = nosh || !std::strcmp(argv[i], "--nosh");
         overGradient = overGradient || !std::strcmp(argv[i], "--over-gradient");
         if (!std::strcmp(argv[i], "--frames-in-flight") && i + 1 < argc) inFlight = std::atoi(argv[i + 1]);
+        if (!std::strcmp(argv[i], "--depth") && i + 1 < argc) depthPath = argv[i + 1];
         if (!std::strcmp(argv[i], "--devices") && i + 1 < argc)
             for (const char* p = argv[i + 1]; *p;) {
                 devices.push_back(std::atoi(p));
@@ -59,6 +63,7 @@ int main(int argc, char** argv)
     msplat::vec2 nearFar{{zn, zf}};
 
     std::vector<float> fb((size_t)W * H * 4);
+    std::vector<float> depth(depthPath ? (size_t)W * H : 0);
     renderer.SetRenderTarget(fb.data(), 0, /*isDevicePointer=*/false);
     if (overGradient && !renderer.SetTargetMode(MSPLAT_TARGET_LOAD)) return 1;
     for (int k = 0; k < (inFlight > 1 ? inFlight + 1 : 1); ++k) {
@@ -69,7 +74,8 @@ int main(int argc, char** argv)
                     px[0] = 0.1f; px[1] = 0.2f; px[2] = 0.2f + 0.6f * (float)y / (float)H; px[3] = 1.0f;
                 }
         renderer.Sort(cameraMat, projMat, viewport, nearFar);       // moves on to the next context
-        renderer.Render(cameraMat, projMat, viewport, nearFar);
+        if (depthPath) renderer.RenderWithDepth(cameraMat, projMat, viewport, nearFar, depth.data());
+        else renderer.Render(cameraMat, projMat, viewport, nearFar);
     }
     renderer.Synchronize();
 
@@ -77,6 +83,12 @@ int main(int argc, char** argv)
     if (!f) return 1;
     std::fwrite(fb.data(), sizeof(float), fb.size(), f);
     std::fclose(f);
+    if (depthPath) {
+        FILE* fz = std::fopen(depthPath, "wb");
+        if (!fz) return 1;
+        std::fwrite(depth.data(), sizeof(float), depth.size(), fz);
+        std::fclose(fz);
+    }
     std::printf("%zu splats -> %dx%d RGBA32F (row 0 = bottom) written to %s\n", cloud->GetNumGaussians(), W, H, argv[2]);
     return 0;
 }

@@ -224,6 +224,28 @@ public:
         if (rc != MSPLAT_OK) std::fprintf(stderr, "[msplat][%c] Render: %s\n", Level(rc), msplat_last_error(ctx));
     }
 
+    // Render plus the per-pixel depth plane (msplat_render_depth): W x H float32 rows of depthPitchBytes (0 = tight) in the render
+    // target's memory space -- the splats' expected window depth over the clear depth 1.0, for compositing the layer with geometry
+    // or as an XR depth layer.  Uses the context of the latest Sort, like Render.  A device group has no depth output.
+    template <class Mat4, class Vec4, class Vec2>
+    void RenderWithDepth(const Mat4& cameraMat, const Mat4& projMat, const Vec4& viewport, const Vec2& nearFar, float* depth,
+                         uint64_t depthPitchBytes = 0)
+    {
+        static_assert(sizeof(Mat4) == 64 && sizeof(Vec4) == 16 && sizeof(Vec2) == 8, "glm-compatible layout expected");
+        if (!target || !depth) {
+            std::fprintf(stderr, "[msplat][E] RenderWithDepth: no render target set (SetRenderTarget) or no depth plane\n");
+            return;
+        }
+        if (group) {
+            std::fprintf(stderr, "[msplat][E] RenderWithDepth: a device group has no depth output\n");
+            return;
+        }
+        const int rc = msplat_render_depth(ctx, reinterpret_cast<const float*>(&cameraMat), reinterpret_cast<const float*>(&projMat),
+                                           reinterpret_cast<const float*>(&viewport), reinterpret_cast<const float*>(&nearFar), target,
+                                           targetPitch, depth, depthPitchBytes, targetIsDevice ? 1 : 0);
+        if (rc != MSPLAT_OK) std::fprintf(stderr, "[msplat][%c] RenderWithDepth: %s\n", Level(rc), msplat_last_error(ctx));
+    }
+
     // Both eyes of the latest Sort in one chain of launches (msplat_render_stereo): what the XR callback does with two Render
     // calls (app.cpp:603-607), for device targets at half the launches.  target1: the second eye's image (same pitch / kind as
     // the SetRenderTarget one, which receives the first eye).

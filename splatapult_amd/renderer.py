@@ -233,19 +233,38 @@ class SplatRenderer:
         self._ctx = self._ctxs[self._cur]
         _capi.check(self._ctx, self._lib.msplat_sort(self._ctx, c, p, v, nf))
 
-    def Render(self, cameraMat, projMat, viewport, nearFar, out=None, out_ptr=None, pitch_bytes=0):
+    def Render(self, cameraMat, projMat, viewport, nearFar, out=None, out_ptr=None, pitch_bytes=0, depth=None, depth_ptr=None,
+               depth_pitch_bytes=0):
         """splatrenderer.cpp:315-343 + the GL pipeline behind it.
         out=None      -> returns a new (H, W, 4) numpy array (float32 or float16), row 0 = GL bottom row
         out=ndarray   -> filled in place
-        out_ptr=int   -> device pointer (e.g. torch tensor .data_ptr()); asynchronous on the stream"""
+        out_ptr=int   -> device pointer (e.g. torch tensor .data_ptr()); asynchronous on the stream
+        The depth plane (msplat_render_depth: the splats' expected window depth over the clear depth 1.0, float32 on every
+        context) lives where the colour does: depth=(H, W) float32 array to fill, or True to have one allocated, with host
+        output -- the call then returns (image, depth); depth_ptr=int (rows of depth_pitch_bytes, 0 = tight) with out_ptr"""
         c, p, v, nf = self._args.load(cameraMat, projMat, viewport, nearFar)
         if out_ptr is not None:
+            if depth is not None:
+                raise ValueError("the depth plane lives in the colour's memory space: pass depth_ptr= with out_ptr=")
+            if depth_ptr is not None:
+                _capi.check(self._ctx, self._lib.msplat_render_depth(self._ctx, c, p, v, nf, C.c_void_p(out_ptr), pitch_bytes,
+                                                                     C.c_void_p(depth_ptr), depth_pitch_bytes, 1))
+                return None
             _capi.check(self._ctx, self._lib.msplat_render(self._ctx, c, p, v, nf, C.c_void_p(out_ptr),
                                                            pitch_bytes, 1))
             return None
+        if depth_ptr is not None:
+            raise ValueError("the depth plane lives in the colour's memory space: pass depth= with host output")
         out = _host_frame(self._fb_format, self._args.vp, out, self._load)
-        _capi.check(self._ctx, self._lib.msplat_render(self._ctx, c, p, v, nf, out.ctypes.data, 0, 0))
-        return out
+        if depth is None or depth is False:
+            _capi.check(self._ctx, self._lib.msplat_render(self._ctx, c, p, v, nf, out.ctypes.data, 0, 0))
+            return out
+        H, W = out.shape[:2]
+        if depth is True:
+            depth = np.empty((H, W), np.float32)
+        assert depth.dtype == np.float32 and depth.shape == (H, W) and depth.flags["C_CONTIGUOUS"]
+        _capi.check(self._ctx, self._lib.msplat_render_depth(self._ctx, c, p, v, nf, out.ctypes.data, 0, depth.ctypes.data, 0, 0))
+        return out, depth
 
     def RenderStereo(self, cameraMats, projMats, viewport, nearFar, out_ptrs=None, pitch_bytes=0):
         """both eyes of the latest Sort in ONE chain of launches (msplat_render_stereo; the reference renders them one after the
@@ -570,9 +589,15 @@ class SplatRendererGroup:
         c, p, v, nf = self._args.load(cameraMat, projMat, viewport, nearFar)
         _capi.check(self._g, self._lib.msplat_group_sort(self._g, c, p, v, nf), self._gerr)
 
-    def Render(self, cameraMat, projMat, viewport, nearFar, out=None, out_ptr=None, pitch_bytes=0):
+    def Render(self, cameraMat, projMat, viewport, nearFar, out=None, out_ptr=None, pitch_bytes=0, depth=None, depth_ptr=None,
+               depth_pitch_bytes=0):
         """out_ptr: device pointer ON devices[0] (asynchronous; synchronize() or wait on context 0's stream);
-        otherwise a host array is filled / returned"""
+        otherwise a host array is filled / returned.  A depth plane (SplatRenderer.Render's depth= / depth_ptr=) is refused:
+        the group's row gather moves the colour only"""
+        if (depth is not None and depth is not False) or depth_ptr is not None:
+            raise _capi.MsplatError(_capi.ERR_UNSUPPORTED, "a device group has no depth output (msplat_render_depth is per context): "
+                                    "render the depth plane with a SplatRenderer")
+        del depth_pitch_bytes
         c, p, v, nf = self._args.load(cameraMat, projMat, viewport, nearFar)
         if out_ptr is not None:
             _capi.check(self._g, self._lib.msplat_group_render(self._g, c, p, v, nf, C.c_void_p(out_ptr), pitch_bytes, 1), self._gerr)
