@@ -30,7 +30,6 @@ enum {
     MSPLAT_ERR_IO = -8,            /* PLY / JSON / image open or parse failure */
     MSPLAT_ERR_PAIR_OVERFLOW_EARLIER = -9  /* a WARNING: this call did its work, but an earlier device-output render had overflowed the pair buffer (that frame lacks splats; the buffer has grown) */
 };
-
 enum { MSPLAT_FB_RGBA32F = 0, MSPLAT_FB_RGBA16F = 1 };
 enum { MSPLAT_ROP_NONE = 0, MSPLAT_ROP_RGBA8 = 1, MSPLAT_ROP_RGBA16F = 2 };          /* msplat_set_target_emulation */
 enum { MSPLAT_TWO_PASS_AUTO = 0, MSPLAT_TWO_PASS_ON = 1, MSPLAT_TWO_PASS_OFF = 2 };  /* msplat_config.two_pass */
@@ -69,7 +68,6 @@ typedef struct msplat_config {
     int32_t two_pass;          /* MSPLAT_TWO_PASS_*: may a Render run as two passes with occlusion feedback (same pixels) */
     int32_t cu_partition;      /* MSPLAT_CU_*: the CUs a stream the library creates itself (stream == NULL) may use; frames in flight */
 } msplat_config;
-
 /* Byte offsets of the attributes inside one AoS record: the BinaryAttribute offsets SplatRenderer::BuildVertexArrayObject binds
  * (splatrenderer.cpp:345-391; gaussiancloud.cpp:633-657).  r_sh1 .. b_sh3 are ignored unless full_sh. */
 typedef struct msplat_attr_offsets {
@@ -77,7 +75,6 @@ typedef struct msplat_attr_offsets {
     uint32_t cov3_col0, cov3_col1, cov3_col2;
     uint32_t r_sh1, r_sh2, r_sh3, g_sh1, g_sh2, g_sh3, b_sh1, b_sh2, b_sh3;
 } msplat_attr_offsets;
-
 typedef struct msplat_stats {
     uint64_t num_splats;       /* N */
     uint32_t sort_count;       /* V: splats that survived the presort cull (sortCount) */
@@ -89,7 +86,6 @@ typedef struct msplat_stats {
     uint64_t device_bytes;     /* device memory held by the context */
     uint64_t pairs_tile16;     /* (splat, 16x16 tile) pairs covered by the footprints: SURVEY.md 8d's D */
 } msplat_stats;
-
 typedef struct msplat_timings {   /* milliseconds, averaged; names follow the reference's Tracy zones (splatrenderer.cpp:156-318) */
     float sort_total;          /* "SplatRenderer::Sort" (cull + key + sort) */
     float render_total;        /* "SplatRenderer::Render" */
@@ -98,7 +94,6 @@ typedef struct msplat_timings {   /* milliseconds, averaged; names follow the re
     float composite;           /* fragment + blend */
     float reserved[3];         /* [0] frames averaged, [1] compositor KERNEL time (dispatch begin / end events), [2] its launches */
 } msplat_timings;
-
 /* ---- context: SplatRenderer::SplatRenderer / ~SplatRenderer (splatrenderer.cpp:41-48) ---- */
 int msplat_create(msplat_ctx** out, const msplat_config* cfg);
 void msplat_destroy(msplat_ctx* ctx);
@@ -124,8 +119,13 @@ int msplat_upload_ply(msplat_ctx* ctx, const char* path, int import_full_sh);
 int msplat_download_cloud(msplat_ctx* ctx, void* aos_out, uint64_t cap_bytes);
 /* f_rest storage of the context's NEXT splat upload, any route (INTEGRATION.md 12).  SH_FP16: IEEE fp16, nearest even, 160 / 96-B
  * records; pixels = FP32 of the fp16-rounded cloud; a finite |f_rest| >= 65520 fails the upload (MSPLAT_ERR_UNSUPPORTED).  Attached
- * contexts render the owner's storage; points ignore it.  get: storage of the cloud rendered (-1: no cloud / NULL). */
+ * contexts render the owner's storage; points ignore it.  get: storage of the cloud rendered (-1: no cloud / NULL).
+ * SH_Q8 (full SH only; a degree-1 cloud is stored, and reported, as FP32): one 128-B record.  Per splat and SH band (9 / 15 / 21 values,
+ * r g b together), fp32: m = max |c|; step = m / 127 (0, codes 0, when m < 2^-64); code = clamp(rint(c / step), -127, 127), halves to even;
+ * stored c' = (float)code * step: |c - c'| <= (1/2 + 2^-16) step.  Pixels = FP32 of the cloud of c', which the download returns; a second
+ * Q8 round may move c' once more; a non-finite f_rest value fails the upload (MSPLAT_ERR_UNSUPPORTED, no cloud). */
 enum { MSPLAT_STORAGE_FP32 = 0, MSPLAT_STORAGE_SH_FP16 = 1 };
+enum { MSPLAT_STORAGE_SH_Q8 = 3 };
 int msplat_set_cloud_storage(msplat_ctx* ctx, int32_t storage);
 int msplat_get_cloud_storage(const msplat_ctx* ctx);
 

@@ -66,6 +66,12 @@ int msplat_debug_band_exchange_loopback(msplat_ctx* ctx, void* comm, int32_t kin
  * the runtime refused the mask); mask8 != NULL: the stream's CU mask as hipExtStreamGetCUMask reports it (8 words) ---- */
 int msplat_debug_cu_partition(msplat_ctx* ctx, uint32_t* mask8);
 
+/* ---- MSPLAT_STORAGE_SH_Q8 on one record, on the host (no context, no device): the pack / unpack pair every upload route and the
+ * download use.  rec_in / rec_out: the reference's 61-float record (rec_out: f_rest = code * step, the rest rec_in's bits);
+ * steps_out: the steps of SH bands 1-3; codes_out: the 45 codes in f_rest order (floats 5-7, 9-11, 13-15, 25-60 of the record).
+ * Returns the number of non-finite f_rest values (an upload fails when it is not 0), or MSPLAT_ERR_INVALID_ARG for a NULL ---- */
+int msplat_debug_sh_q8_round(const float rec_in[61], float rec_out[61], float steps_out[3], int8_t codes_out[45]);
+
 #ifdef __cplusplus
 }
 #endif

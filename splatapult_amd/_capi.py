@@ -22,6 +22,8 @@ EXCHANGE_WIRE_FP16 = 1              # msplat_band_exchange flags
 CU_ALL, CU_EVEN, CU_ODD = 0, 1, 2    # msplat_config.cu_partition
 STORAGE_FP32, STORAGE_SH_FP16 = 0, 1  # msplat_set_cloud_storage: f_rest as fp32 or IEEE fp16
 CLOUD_STORAGES = {"fp32": STORAGE_FP32, "sh_fp16": STORAGE_SH_FP16}
+STORAGE_SH_Q8 = 3  # one 128-B record per splat: f_rest as 8-bit codes with a step per SH band (full SH only)
+CLOUD_STORAGE_NAMES = {**CLOUD_STORAGES, "sh_q8": STORAGE_SH_Q8}  # every name the renderers take
 # msplat_set_target_mode: overwrite with (C, 1); blend over the target's contents; write the layer (C, 1 - T)
 TARGET_CLEAR, TARGET_LOAD, TARGET_PREMULTIPLIED = 0, 1, 2
 TARGET_MODES = {"clear": TARGET_CLEAR, "load": TARGET_LOAD, "premultiplied": TARGET_PREMULTIPLIED}
@@ -108,6 +110,7 @@ SYMBOLS = [
     ("msplat_group_set_cloud_storage", C.c_int, [C.c_void_p, C.c_int32]),
     ("msplat_set_cloud_storage", C.c_int, [C.c_void_p, C.c_int32]),
     ("msplat_get_cloud_storage", C.c_int, [C.c_void_p]),
+    ("msplat_debug_sh_q8_round", C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int8)]),
     ("msplat_group_set_layout", C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     ("msplat_group_set_band_cull", C.c_int, [C.c_void_p, C.c_int]),
     ("msplat_group_sort", C.c_int, [C.c_void_p, _F16, _F16, _F16, _F16]),

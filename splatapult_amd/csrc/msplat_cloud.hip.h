@@ -27,8 +27,8 @@ struct PlyLayout {             // mirrors msplat_ply_layout (include/msplat.h)
     int32_t rot[4];
 };
 
-// STORAGE = kStorageShFp16: the records are written compact (msplat_common.hip.h: sh16_pack); *n_over counts the f_rest values
-// beyond the fp16 range (the upload then fails)
+// STORAGE = kStorageShFp16 / kStorageShQ8: the records are written compact (msplat_common.hip.h: sh16_pack / sh8_pack); *n_over
+// counts the f_rest values beyond the fp16 range / the non-finite ones (the upload then fails)
 template <bool FULL_SH, int STORAGE = kStorageFp32>
 __global__ __launch_bounds__(64) void ingest_kernel(const char* __restrict__ raw, uint64_t n, PlyLayout L,
                                                     float4* __restrict__ pos4, float4* __restrict__ recs,
@@ -99,10 +99,11 @@ __global__ __launch_bounds__(64) void ingest_kernel(const char* __restrict__ raw
             f[16 + c * 3 + r] = s;
         }
     pos4[i] = make_float4(f[0], f[1], f[2], footprint_bound(&f[16], f[3]));      // .w: world-space footprint bound for the band cull
-    if constexpr (STORAGE == kStorageShFp16) {
-        constexpr int CF4 = cloud_f4(kStorageShFp16, FULL_SH);
+    if constexpr (STORAGE != kStorageFp32) {
+        constexpr int CF4 = cloud_f4(STORAGE, FULL_SH);
         uint32_t w[CF4 * 4];
-        const uint32_t over = sh16_pack<FULL_SH>(f, w);
+        uint32_t over;
+        if constexpr (STORAGE == kStorageShQ8) over = sh8_pack<FULL_SH>(f, w); else over = sh16_pack<FULL_SH>(f, w);
         if (over) atomicAdd(n_over, over);
 #pragma unroll
         for (int k = 0; k < CF4; ++k)

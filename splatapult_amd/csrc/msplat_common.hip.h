@@ -298,10 +298,14 @@ __host__ __device__ inline float footprint_bound(const float* S, float alpha)
 // then the f_rest slots of the FP32 record as IEEE fp16 (band 1 of r g b first, so a degree-1 record is a prefix of a full one),
 // two per dword, low half first; zero padding to 10 (full SH: 160 B) or 6 float4 (degree 1: 96 B).
 // The conversions are integer bit operations: they do not depend on a wave's denorm mode and keep fp16 subnormals both ways.
+// SH_Q8 (full SH only; a degree-1 cloud is stored FP32): the same 16-float head, then three fp32 steps -- one per SH band, shared by
+// r g b -- then the 45 f_rest values as one-byte codes (two's complement, in sh16_half_slot order, four per dword, low byte first)
+// and zero padding to 8 float4: 128 B, one cache line per splat.  Value = (float)code * step of the value's band (sh8_pack).
 // ------------------------------------------------------------------------------------------
-constexpr int kStorageFp32 = 0, kStorageShFp16 = 1;
+constexpr int kStorageFp32 = 0, kStorageShFp16 = 1, kStorageShQ8 = 3;
 __host__ __device__ constexpr int cloud_f4(int storage, bool full_sh)
 {
+    if (storage == kStorageShQ8 && full_sh) return 8;
     return storage == kStorageShFp16 ? (full_sh ? 10 : 6) : (full_sh ? 16 : 8);
 }
 __host__ __device__ constexpr int sh16_count(bool full_sh) { return full_sh ? 45 : 9; }
@@ -376,6 +380,71 @@ __host__ __device__ inline void sh16_unpack(const uint32_t* w, float* f)
     for (int k = 0; k < 16; ++k) f[sh16_head_slot(k)] = f32_from_bits(w[k]);
 #pragma unroll
     for (int h = 0; h < NH; ++h) f[sh16_half_slot(h)] = f32_from_bits(f16_bits_to_f32_bits((w[16 + h / 2] >> (16 * (h & 1))) & 0xFFFFu));
+}
+
+// SH band (0..2 = degree 1..3) of half h: sh16_half_slot order is band 1 of r g b, then per channel 5 values of band 2 and 7 of band 3
+__host__ __device__ constexpr int sh8_band(int h) { return h < 9 ? 0 : ((h - 9) % 12 < 5 ? 1 : 2); }
+
+// the correctly rounded fp32 quotient, written out on the device like every division of the projection
+__host__ __device__ inline float sh8_div(float a, float b)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __fdiv_rn(a, b);
+#else
+    return a / b;
+#endif
+}
+
+// FP32 record floats f[] -> the SH_Q8 record w[32]; returns the number of non-finite f_rest values (their codes are 0: the upload
+// fails).  Per band: m = max |c|; m < 2^-64: step 0, codes 0 (so that no quotient depends on a wave's denorm mode); else
+// step = m / 127 and code = clamp(rint(c / step), -127, 127), halves to even.
+template <bool FULL_SH>
+__host__ __device__ inline uint32_t sh8_pack(const float* f, uint32_t* w)
+{
+    static_assert(FULL_SH, "SH_Q8 records exist for full-SH clouds only");
+    constexpr int NH = sh16_count(true);
+    uint32_t bad = 0u;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) w[k] = f32_bits(f[sh16_head_slot(k)]);
+    float m[3] = {0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int h = 0; h < NH; ++h) {
+        const uint32_t a = f32_bits(f[sh16_half_slot(h)]) & 0x7FFFFFFFu;
+        bad += a >= 0x7F800000u ? 1u : 0u;
+        const float av = f32_from_bits(a);
+        m[sh8_band(h)] = av > m[sh8_band(h)] ? av : m[sh8_band(h)];      // (a NaN never becomes the maximum)
+    }
+    float step[3];
+#pragma unroll
+    for (int b = 0; b < 3; ++b) {
+        step[b] = m[b] < 0x1p-64f ? 0.0f : sh8_div(m[b], 127.0f);
+        w[16 + b] = f32_bits(step[b]);
+    }
+#pragma unroll
+    for (int j = 0; j < 13; ++j) w[19 + j] = 0u;
+#pragma unroll
+    for (int h = 0; h < NH; ++h) {
+        const float c = f[sh16_half_slot(h)], st = step[sh8_band(h)];
+        float q = st > 0.0f && st < 3.0e38f ? rintf(sh8_div(c, st)) : 0.0f;      // (an infinite step: a band with +-inf in it)
+        q = q < -127.0f ? -127.0f : (q > 127.0f ? 127.0f : q);
+        const int code = q == q ? (int)q : 0;
+        w[19 + h / 4] |= ((uint32_t)code & 0xFFu) << (8 * (h & 3));
+    }
+    return bad;
+}
+
+// the inverse: fills the 16 head slots and the f_rest slots of an FP32 record f[] (padding slots are left alone)
+template <bool FULL_SH>
+__host__ __device__ inline void sh8_unpack(const uint32_t* w, float* f)
+{
+    static_assert(FULL_SH, "SH_Q8 records exist for full-SH clouds only");
+#pragma unroll
+    for (int k = 0; k < 16; ++k) f[sh16_head_slot(k)] = f32_from_bits(w[k]);
+#pragma unroll
+    for (int h = 0; h < sh16_count(true); ++h) {
+        const int code = (int)(w[19 + h / 4] << (24 - 8 * (h & 3))) >> 24;      // sign-extended byte h
+        f[sh16_half_slot(h)] = (float)code * f32_from_bits(w[16 + sh8_band(h)]);
+    }
 }
 
 // Milder form: only GROUPS of g consecutive chunks share an XCD (workgroups p and p + 8 of every block of 8 g, which are

@@ -1314,10 +1314,12 @@ static void issue_projection(RenderChain& rc, int mode, float occ_frac)
     }
     auto project = [&](auto MODE, int grid, const uint32_t* dV, const ProjExtra& ex, const auto& v1) {
         with_flag(ctx->full_sh, [&](auto SH) {
-            with_int<kStorageShFp16, kStorageFp32>(ctx->cloud_storage, [&](auto ST) {
-                hipLaunchKernelGGL((project_kernel<SH.value, MODE.value, ST.value>), dim3(grid), dim3(kProjThreads), 0, s,
-                                   (const uint32_t*)ctx->valA.p, dV, (const float4*)ctx->recs.p, pp, (float4*)ctx->rec2d.p,
-                                   (uint32_t*)ctx->rect.p, zq, ex, v1);
+            with_int<kStorageShQ8, kStorageShFp16, kStorageFp32>(ctx->cloud_storage, [&](auto ST) {
+                if constexpr (ST.value == kStorageShQ8 && !SH.value) return;      // (no such store: prepare_cloud_buffers)
+                else
+                    hipLaunchKernelGGL((project_kernel<SH.value, MODE.value, ST.value>), dim3(grid), dim3(kProjThreads), 0, s,
+                                       (const uint32_t*)ctx->valA.p, dV, (const float4*)ctx->recs.p, pp, (float4*)ctx->rec2d.p,
+                                       (uint32_t*)ctx->rect.p, zq, ex, v1);
             });
         });
     };

@@ -546,7 +546,7 @@ int msplat_group_upload_ply(msplat_group* g, const char* path, int import_full_s
 int msplat_group_set_cloud_storage(msplat_group* g, int32_t storage)
 {
     GROUP_OR_FAIL(g);
-    if (storage != MSPLAT_STORAGE_FP32 && storage != MSPLAT_STORAGE_SH_FP16)
+    if (storage != MSPLAT_STORAGE_FP32 && storage != MSPLAT_STORAGE_SH_FP16 && storage != MSPLAT_STORAGE_SH_Q8)
         return gfail(g, MSPLAT_ERR_INVALID_ARG, "msplat_group_set_cloud_storage: unknown storage %d", storage);
     for (msplat_ctx* c : g->ctx) {
         const int rc = msplat_set_cloud_storage(c, storage);

@@ -38,8 +38,9 @@ constexpr int kProjThreads = 64;          // one wave per workgroup: wave-privat
 // one wave-block of 64 ranks: cooperative gather of the records, then the vertex + geometry stage per lane (rank r, rank rl inside
 // its view; lanes with !valid take part in the gather only).  s_stage: 64 * STRIDE floats of wave-private LDS.
 // vm / pm / eye: the view's matrices (kernarg words: they stay in SGPRs); SECOND: the second view of a two-view chain.
-// STORAGE = kStorageShFp16: compact records (msplat_common.hip.h), gathered the same way -- piece p = 64 it + lane of load it is
-// piece p % F4 of record p / F4 -- and widened into the FP32 record's slots, so that everything after the gather runs unchanged.
+// STORAGE = kStorageShFp16 / kStorageShQ8: compact records (msplat_common.hip.h), gathered the same way -- piece p = 64 it + lane of
+// load it is piece p % CF4 of record p / CF4 (SH_Q8: CF4 = 8, eight neighbouring lanes read one 128-B line) -- and widened into the
+// FP32 record's slots, so that everything after the gather runs unchanged.
 template <bool FULL_SH, bool SECOND, int STORAGE = kStorageFp32>
 __device__ __forceinline__ void project_block(const uint32_t r, const uint32_t rl, const bool valid, const int lane,
                                               const uint32_t* __restrict__ sorted_idx, const float4* __restrict__ recs,
@@ -97,7 +98,7 @@ __device__ __forceinline__ void project_block(const uint32_t r, const uint32_t r
             w[4 * k + 0] = __float_as_uint(v.x); w[4 * k + 1] = __float_as_uint(v.y);
             w[4 * k + 2] = __float_as_uint(v.z); w[4 * k + 3] = __float_as_uint(v.w);
         }
-        sh16_unpack<FULL_SH>(w, f);
+        if constexpr (STORAGE == kStorageShQ8) sh8_unpack<FULL_SH>(w, f); else sh16_unpack<FULL_SH>(w, f);
     }
     if (!valid) return;
     const float x = f[0], y = f[1], z = f[2], alpha = f[3];
@@ -284,7 +285,7 @@ __global__ __launch_bounds__(kProjThreads) void project_kernel(const uint32_t* _
     // PROJ_PASS1: ranks below cut = occ_cut(V, occ_share) only get an empty rectangle, their records are not fetched; the cut is
     // left in d_cut[0] (= occ[0]).  PROJ_LISTED: the *d_V ranks to project are listed (any order); records and rectangles are
     // stored by rank as always.
-    // Records are 256 B (full SH) or 128 B (base) and line aligned (SH_FP16: 160 / 96 B).  The gather by sorted index is
+    // Records are 256 B (full SH) or 128 B (base) and line aligned (SH_FP16: 160 / 96 B; SH_Q8: 128 B).  The gather by sorted index is
     // done cooperatively (project_block): F4 consecutive lanes fetch one whole record (coalesced 256/128 B), the wave
     // stages 64 records in LDS, then every lane reads its own record back (stride 68/36 dwords keeps
     // the ds_read_b128 accesses conflict free).

@@ -44,8 +44,10 @@ static int prepare_cloud_buffers(msplat_ctx* ctx, uint64_t n, bool full_sh, cons
     ctx->has_render = false;
     ctx->N = n;
     ctx->full_sh = full_sh;
-    // the storage kind belongs to the store: attached contexts render the owner's, point clouds are always FP32
-    const int storage = share ? share->storage : (ctx->point_mode ? kStorageFp32 : ctx->storage_cfg);
+    // the storage kind belongs to the store: attached contexts render the owner's, point clouds are always FP32, and so is a
+    // degree-1 cloud asked to be SH_Q8 (its FP32 record is one 128-B line already)
+    int storage = share ? share->storage : (ctx->point_mode ? kStorageFp32 : ctx->storage_cfg);
+    if (storage == kStorageShQ8 && !full_sh) storage = kStorageFp32;
     const int F4 = ctx->point_mode ? 1 : cloud_f4(storage, ctx->full_sh);
     const size_t alloc_n = std::max<uint64_t>(n, 1);
     int rc;
@@ -246,7 +248,7 @@ int msplat_upload_cloud(msplat_ctx* ctx, const void* aos, uint64_t n, uint32_t s
     int rc = prepare_cloud_buffers(ctx, n, full_sh != 0, nullptr);
     if (rc) return rc;
     const int F4 = ctx->store->F4;
-    const bool sh16 = ctx->cloud_storage == kStorageShFp16;
+    const bool sh16 = ctx->cloud_storage == kStorageShFp16, sh8 = ctx->cloud_storage == kStorageShQ8;
     uint64_t n_over = 0;
 
     // repack: reference AoS (100 B / 244 B, arbitrary offsets) -> 16-byte aligned padded records with the
@@ -278,7 +280,7 @@ int msplat_upload_cloud(msplat_ctx* ctx, const void* aos, uint64_t n, uint32_t s
         for (size_t j = 0; j < cnt; ++j) {
             const uint8_t* rec = src + (base + j) * stride_bytes;
             float full[64];
-            float* d = sh16 ? full : stage_rec.data() + j * F4 * 4;
+            float* d = sh16 || sh8 ? full : stage_rec.data() + j * F4 * 4;
             std::memcpy(d + 0, rec + off->pos_with_alpha, 16);
             std::memcpy(d + 4, rec + off->r_sh0, 16);
             std::memcpy(d + 8, rec + off->g_sh0, 16);
@@ -294,14 +296,18 @@ int msplat_upload_cloud(msplat_ctx* ctx, const void* aos, uint64_t n, uint32_t s
             }
             float* p = stage_pos.data() + j * 4;
             p[0] = d[0]; p[1] = d[1]; p[2] = d[2]; p[3] = footprint_bound(d + 16, d[3]);      // .w: footprint bound for the band cull
-            if (sh16) {
+            if (sh16 || sh8) {
                 uint32_t* w = reinterpret_cast<uint32_t*>(stage_rec.data() + j * F4 * 4);
-                n_over += ctx->full_sh ? sh16_pack<true>(d, w) : sh16_pack<false>(d, w);
+                if (sh8) n_over += sh8_pack<true>(d, w);
+                else n_over += ctx->full_sh ? sh16_pack<true>(d, w) : sh16_pack<false>(d, w);
             }
         }
         HIP_TRY(ctx, hipMemcpy((char*)ctx->recs.p + base * F4 * 16, stage_rec.data(), cnt * F4 * 16, hipMemcpyHostToDevice));
         HIP_TRY(ctx, hipMemcpy((char*)ctx->pos4.p + base * 16, stage_pos.data(), cnt * 16, hipMemcpyHostToDevice));
     }
+    if (n_over && sh8)
+        return fail(ctx, MSPLAT_ERR_UNSUPPORTED, "msplat_upload_cloud: %llu f_rest values are not finite: MSPLAT_STORAGE_SH_Q8 "
+                    "cannot quantise them", (unsigned long long)n_over);
     if (n_over)
         return fail(ctx, MSPLAT_ERR_UNSUPPORTED, "msplat_upload_cloud: %llu f_rest values are beyond the fp16 range (|c| >= 65520) "
                     "of MSPLAT_STORAGE_SH_FP16", (unsigned long long)n_over);
@@ -339,7 +345,7 @@ int msplat_upload_ply_vertices(msplat_ctx* ctx, const void* vertices, uint64_t n
         if ((rc = buf_alloc(ctx, raw, (size_t)n * vs + 16))) return rc;
         uint32_t* d_over = reinterpret_cast<uint32_t*>((char*)raw.p + (size_t)n * vs);      // (vs is a multiple of 4)
         uint32_t n_over = 0;
-        const bool sh16 = ctx->cloud_storage == kStorageShFp16;
+        const bool sh8 = ctx->cloud_storage == kStorageShQ8, counted = sh8 || ctx->cloud_storage == kStorageShFp16;
         hipError_t e = hipMemcpyAsync(raw.p, vertices, (size_t)n * vs, hipMemcpyHostToDevice, ctx->stream);
         if (e == hipSuccess) e = hipMemsetAsync(d_over, 0, 4, ctx->stream);
         if (e == hipSuccess) {
@@ -349,17 +355,22 @@ int msplat_upload_ply_vertices(msplat_ctx* ctx, const void* vertices, uint64_t n
             static_assert(sizeof(PlyLayout) == sizeof(msplat_ply_layout), "layout mirror out of sync");
             std::memcpy(&kl, layout, sizeof(kl));
             with_flag(full, [&](auto SH) {
-                with_int<kStorageShFp16, kStorageFp32>(ctx->cloud_storage, [&](auto ST) {
-                    hipLaunchKernelGGL((ingest_kernel<SH.value, ST.value>), dim3(grid), dim3(64), lds, ctx->stream, (const char*)raw.p, n, kl,
-                                       (float4*)ctx->pos4.p, (float4*)ctx->recs.p, d_over);
+                with_int<kStorageShQ8, kStorageShFp16, kStorageFp32>(ctx->cloud_storage, [&](auto ST) {
+                    if constexpr (ST.value == kStorageShQ8 && !SH.value) return;      // (no such store: prepare_cloud_buffers)
+                    else
+                        hipLaunchKernelGGL((ingest_kernel<SH.value, ST.value>), dim3(grid), dim3(64), lds, ctx->stream, (const char*)raw.p, n,
+                                           kl, (float4*)ctx->pos4.p, (float4*)ctx->recs.p, d_over);
                 });
             });
             e = hipGetLastError();
         }
-        if (e == hipSuccess && sh16) e = hipMemcpyAsync(&n_over, d_over, 4, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess && counted) e = hipMemcpyAsync(&n_over, d_over, 4, hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
         buf_free(ctx, raw);
         if (e != hipSuccess) return fail(ctx, MSPLAT_ERR_HIP, "GPU ingest failed: %s", hipGetErrorString(e));
+        if (n_over && sh8)
+            return fail(ctx, MSPLAT_ERR_UNSUPPORTED, "msplat_upload_ply_vertices: %u f_rest values are not finite: "
+                        "MSPLAT_STORAGE_SH_Q8 cannot quantise them", n_over);
         if (n_over)
             return fail(ctx, MSPLAT_ERR_UNSUPPORTED, "msplat_upload_ply_vertices: %u f_rest values are beyond the fp16 range "
                         "(|c| >= 65520) of MSPLAT_STORAGE_SH_FP16", n_over);
@@ -509,7 +520,7 @@ int msplat_download_cloud(msplat_ctx* ctx, void* aos_out, uint64_t cap_bytes)
     if (!ctx->has_cloud) return fail(ctx, MSPLAT_ERR_NO_CLOUD, "no cloud uploaded");
     if (ctx->point_mode) return fail(ctx, MSPLAT_ERR_UNSUPPORTED, "msplat_download_cloud: the context holds a point cloud");
     const int F4 = ctx->store->F4;
-    const bool sh16 = ctx->cloud_storage == kStorageShFp16;      // widened back to fp32
+    const bool sh16 = ctx->cloud_storage == kStorageShFp16, sh8 = ctx->cloud_storage == kStorageShQ8;      // widened back to fp32
     const size_t rec_floats = ctx->full_sh ? 61 : 25;
     if (cap_bytes < ctx->N * rec_floats * 4) return fail(ctx, MSPLAT_ERR_INVALID_ARG, "output buffer too small");
     if (ctx->N == 0) return MSPLAT_OK;
@@ -531,9 +542,10 @@ int msplat_download_cloud(msplat_ctx* ctx, void* aos_out, uint64_t cap_bytes)
         for (size_t j = 0; j < cnt; ++j) {
             const float* r = stage.data() + j * F4 * 4;
             float full[64];
-            if (sh16) {
+            if (sh16 || sh8) {
                 const uint32_t* w = reinterpret_cast<const uint32_t*>(r);
-                if (ctx->full_sh) sh16_unpack<true>(w, full); else sh16_unpack<false>(w, full);
+                if (sh8) sh8_unpack<true>(w, full);
+                else if (ctx->full_sh) sh16_unpack<true>(w, full); else sh16_unpack<false>(w, full);
                 r = full;
             }
             std::memcpy(dst + (ro ? (size_t)ctx->store->order_host[base + j] : base + j) * rec_floats, r, rec_floats * 4);
@@ -544,14 +556,14 @@ int msplat_download_cloud(msplat_ctx* ctx, void* aos_out, uint64_t cap_bytes)
 
 
 // Storage of the higher-order SH (f_rest) for the context's NEXT splat upload (MSPLAT_STORAGE_*; see msplat_common.hip.h for the
-// SH_FP16 record).  A cloud already on the device keeps its storage.
+// SH_FP16 and SH_Q8 records).  A cloud already on the device keeps its storage; an SH_Q8 upload without full SH stores FP32.
 int msplat_set_cloud_storage(msplat_ctx* ctx, int32_t storage)
 {
     drain_async(ctx);
     if (!ctx) return fail(nullptr, MSPLAT_ERR_INVALID_ARG, "ctx is NULL");
-    if (storage != MSPLAT_STORAGE_FP32 && storage != MSPLAT_STORAGE_SH_FP16)
-        return fail(ctx, MSPLAT_ERR_INVALID_ARG, "msplat_set_cloud_storage: storage must be MSPLAT_STORAGE_FP32 or _SH_FP16 (got %d)",
-                    storage);
+    if (storage != MSPLAT_STORAGE_FP32 && storage != MSPLAT_STORAGE_SH_FP16 && storage != MSPLAT_STORAGE_SH_Q8)
+        return fail(ctx, MSPLAT_ERR_INVALID_ARG, "msplat_set_cloud_storage: storage must be MSPLAT_STORAGE_FP32, _SH_FP16 or _SH_Q8 "
+                    "(got %d)", storage);
     ctx->storage_cfg = storage;
     return MSPLAT_OK;
 }
@@ -560,4 +572,19 @@ int msplat_get_cloud_storage(const msplat_ctx* ctx)
 {
     if (!ctx || !ctx->has_cloud) return -1;
     return ctx->point_mode ? MSPLAT_STORAGE_FP32 : ctx->cloud_storage;
+}
+
+// the SH_Q8 quantiser on one reference record (msplat_debug.h): the pack / unpack pair of the uploads and the download, no device
+int msplat_debug_sh_q8_round(const float rec_in[61], float rec_out[61], float steps_out[3], int8_t codes_out[45])
+{
+    if (!rec_in || !rec_out || !steps_out || !codes_out) return MSPLAT_ERR_INVALID_ARG;
+    float full[64] = {}, back[64] = {};
+    uint32_t w[32];
+    std::memcpy(full, rec_in, 61 * 4);
+    const uint32_t bad = sh8_pack<true>(full, w);
+    sh8_unpack<true>(w, back);
+    std::memcpy(rec_out, back, 61 * 4);
+    std::memcpy(steps_out, w + 16, 12);
+    for (int h = 0; h < 45; ++h) codes_out[h] = (int8_t)((w[19 + h / 4] >> (8 * (h & 3))) & 0xFFu);
+    return (int)bad;
 }

@@ -113,6 +113,7 @@ public:
 
     // msplat_set_cloud_storage (before Init; also on the ConfigureDevices path): MSPLAT_STORAGE_FP32 (default) or
     // MSPLAT_STORAGE_SH_FP16 -- f_rest stored as IEEE fp16, pixels equal to an FP32 render of the fp16-rounded cloud (msplat.h)
+    // or MSPLAT_STORAGE_SH_Q8 -- f_rest as 8-bit codes with a step per SH band, one 128-B record per splat (full-SH clouds only)
     void SetCloudStorage(int storage) { cloudStorage = storage; }
 
     // splatrenderer.cpp:50-151.  false after logging on failure.  The cloud is copied to the device and

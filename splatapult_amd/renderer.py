@@ -44,9 +44,9 @@ class _FrameArgs:
 
 def _storage_kind(name):
     """cloud_storage argument -> MSPLAT_STORAGE_*"""
-    if name not in _capi.CLOUD_STORAGES:
-        raise ValueError("cloud_storage must be one of %s (got %r)" % (sorted(_capi.CLOUD_STORAGES), name))
-    return _capi.CLOUD_STORAGES[name]
+    if name not in _capi.CLOUD_STORAGE_NAMES:
+        raise ValueError("cloud_storage must be one of %s (got %r)" % (sorted(_capi.CLOUD_STORAGE_NAMES), name))
+    return _capi.CLOUD_STORAGE_NAMES[name]
 
 
 def _aos_upload(cloud):
@@ -86,7 +86,8 @@ class SplatRenderer:
         per-frame buffers, ONE shared cloud -- msplat_attach_cloud), so successive frames overlap on the
         GPU; Render and the getters use the context of the latest Sort.  `stream` is only used with depth 1;
         consume a frame after wait_on_stream() / synchronize(), one framebuffer per frame in flight.
-        cloud_storage: "fp32" (default) or "sh_fp16" -- f_rest stored as IEEE fp16 (msplat_set_cloud_storage)."""
+        cloud_storage: "fp32" (default), "sh_fp16" -- f_rest stored as IEEE fp16 -- or "sh_q8" -- f_rest as 8-bit codes with a
+        step per SH band, one 128-B record per splat; a degree-1 cloud stays "fp32" (msplat_set_cloud_storage)."""
         self._storage = _storage_kind(cloud_storage)
         self.numBlocksPerWorkgroup = 1024      # accepted and ignored (splatrenderer.h:39)
         self._lib = _capi.lib()
@@ -217,9 +218,9 @@ class SplatRenderer:
         return out[:self._n]
 
     def cloud_storage(self):
-        """"fp32" / "sh_fp16": how the uploaded cloud is stored (msplat_get_cloud_storage); None without a cloud"""
+        """"fp32" / "sh_fp16" / "sh_q8": how the uploaded cloud is stored (msplat_get_cloud_storage); None without a cloud"""
         k = self._lib.msplat_get_cloud_storage(self._ctx) if self._ctx else -1
-        return {v: n for n, v in _capi.CLOUD_STORAGES.items()}.get(k)
+        return {v: n for n, v in _capi.CLOUD_STORAGE_NAMES.items()}.get(k)
 
     def last_error(self):
         if self._ctx:

@@ -1,18 +1,20 @@
-"""FP32 against SH_FP16 cloud storage (msplat_set_cloud_storage) under bench.py's own protocol.
+"""FP32 against SH_FP16 and SH_Q8 cloud storage (msplat_set_cloud_storage) under bench.py's own protocol.
 
 usage (GPU box, repo root):
-    python tools/cloud_storage_bench.py [--workloads cfg2,cfg3,cfg4,cfg5] [--steps 20] [--warmup 200] [--plain] [--out FILE]
+    python tools/cloud_storage_bench.py [--workloads cfg2,cfg3,cfg4,cfg5] [--storages fp32,sh_fp16,sh_q8] [--steps 20]
+                                        [--warmup 200] [--plain] [--out FILE]
 
 Every (workload, storage) runs `bench.py --gpus 1 --workload W --steps S --warmup K --full --no-cpu-baseline` in a child process
 (four frames in flight, cu_partition auto, median of S-frame blocks, the serial phase) with the renderer's cloud_storage default
-set to the storage under test: bench.py itself is imported, not edited.  A second child renders the workload's first view three
-times -- SH_FP16 storage of C, FP32 storage of round16(C) (f_rest rounded to fp16), FP32 storage of C -- and reports whether the
-first two agree bit for bit (`bit_exact`) and max|pixel difference| against FP32 storage of C (`max|diff|`).
+set to the storage under test: bench.py itself is imported, not edited.  A second child renders the workload's first view with
+FP32 storage of C and, per compact storage, with that storage of C and with FP32 storage of the cloud it stands for -- round16(C)
+(f_rest rounded to fp16) for SH_FP16, deq(C) (tests/sh_q8_rule.py: f_rest = code * step) for SH_Q8 -- and reports whether the
+last two agree bit for bit (`bit_exact`) and max|pixel difference| against FP32 storage of C (`max|diff|`).
 One JSON line per (workload, storage) on stdout (and appended to --out).
 
 Child modes (also what a profiler wraps: rocprofv3 ... -- python tools/cloud_storage_bench.py --child sh_fp16 -- <bench args>):
     --child STORAGE -- <bench.py arguments>       one bench.py run with that storage
-    --check WORKLOAD                              the three-render check of one workload
+    --check WORKLOAD [STORAGES]                   the render check of one workload
 """
 import argparse
 import json
@@ -42,32 +44,50 @@ def run_child_bench(storage, bench_args):
     return bench.main()
 
 
-def run_check(key):
+LABELS = {"fp32": ("fp32", None), "sh_fp16": ("SH fp16", "f32 (SH storage fp16)"), "sh_q8": ("SH q8", "f32 (SH storage q8)")}
+
+
+def run_check(key, storages):
     import bench
     import numpy as np
     from splatapult_amd import SplatRenderer, camera, synthetic
+    from tests.sh_q8_rule import deq
 
     wl = bench.WORKLOADS[key]
     aos = synthetic.make_cloud(wl["n"], seed=wl["seed"], full_sh=True, pos_sigma=wl["pos_sigma"]).as_array()
-    r16 = aos.copy()
-    r16[:, REST] = aos[:, REST].astype(np.float16).astype(np.float32)
+
+    def round16(a):
+        out = a.copy()
+        out[:, REST] = a[:, REST].astype(np.float16).astype(np.float32)
+        return out
+
+    stands_for = {"sh_fp16": round16, "sh_q8": deq}
     W, H = wl["W"], wl["H"]
     proj = camera.perspective(camera.FOVY, W / H)
     vp, nf = [0, 0, W, H], [camera.Z_NEAR, camera.Z_FAR]
     cams = [camera.pose((0.0, 0.0, wl["cam_z"]), 0.3)] if wl["views"] == 1 else \
         [camera.pose((-0.032, 0.0, wl["cam_z"]), 0.3), camera.pose((0.032, 0.0, wl["cam_z"]), 0.3)]
-    frames = []
-    for storage, a in (("sh_fp16", aos), ("fp32", r16), ("fp32", aos)):
+
+    def render(storage, a):
         r = SplatRenderer(device=0, fb_format=wl["fb"], cloud_storage=storage)
         if not r.Init(a, False, False):
             raise SystemExit("Init failed: " + r.last_error())
         r.Sort(cams[0], proj, vp, nf)
-        frames.append([r.Render(c, proj, vp, nf) for c in cams])
+        out = [r.Render(c, proj, vp, nf) for c in cams]
         r.close()
+        return out
+
     u = (lambda x: x.view(np.uint16 if x.dtype == np.float16 else np.uint32))
-    exact = all(np.array_equal(u(a), u(b)) for a, b in zip(frames[0], frames[1]))
-    diff = max(float(np.abs(a.astype(np.float64) - b.astype(np.float64)).max()) for a, b in zip(frames[0], frames[2]))
-    print(json.dumps({"workload": key, "bit_exact": bool(exact), "max|diff|": diff}))
+    ref = render("fp32", aos)
+    res = {"workload": key}
+    for storage in storages:
+        if storage == "fp32":
+            continue
+        got, want = render(storage, aos), render("fp32", stands_for[storage](aos))
+        exact = all(np.array_equal(u(a), u(b)) for a, b in zip(got, want))
+        diff = max(float(np.abs(a.astype(np.float64) - b.astype(np.float64)).max()) for a, b in zip(got, ref))
+        res[storage] = {"bit_exact": bool(exact), "max|diff|": diff}
+    print(json.dumps(res))
 
 
 def last_json(text):
@@ -83,10 +103,10 @@ def main():
         args = sys.argv[3:]
         return run_child_bench(sys.argv[2], args[1:] if args[:1] == ["--"] else args)
     if len(sys.argv) > 2 and sys.argv[1] == "--check":
-        return run_check(sys.argv[2])
+        return run_check(sys.argv[2], (sys.argv[3] if len(sys.argv) > 3 else "sh_fp16").split(","))
     ap = argparse.ArgumentParser()
     ap.add_argument("--workloads", default="cfg2,cfg3,cfg4,cfg5")
-    ap.add_argument("--storages", default="fp32,sh_fp16")
+    ap.add_argument("--storages", default="fp32,sh_fp16,sh_q8")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--plain", action="store_true", help="bench.py's plain run (one timed block, no serial phase) instead of --full")
@@ -95,7 +115,7 @@ def main():
     args = ap.parse_args()
     me = os.path.abspath(__file__)
     for key in [k for k in args.workloads.split(",") if k]:
-        chk = subprocess.run([sys.executable, me, "--check", key], cwd=ROOT, capture_output=True, text=True, timeout=args.timeout)
+        chk = subprocess.run([sys.executable, me, "--check", key, args.storages], cwd=ROOT, capture_output=True, text=True, timeout=args.timeout)
         check = last_json(chk.stdout)
         if chk.returncode != 0 or check is None:
             sys.stderr.write(chk.stdout[-3000:] + chk.stderr[-3000:])
@@ -111,13 +131,13 @@ def main():
                 sys.stderr.write(p.stdout[-3000:] + p.stderr[-3000:])
                 raise SystemExit("bench.py child for %s / %s failed (exit %d)" % (key, storage, p.returncode))
             cfg = out.setdefault("config", {})
-            if storage == "sh_fp16":
-                cfg["workload"] = cfg.get("workload", key) + " [cloud storage: SH fp16]"
-                out["dtype"] = "f32 (SH storage fp16)"
-                out["bit_exact"] = check["bit_exact"]
-                out["max|diff|"] = check["max|diff|"]
+            label, dtype = LABELS[storage]
+            cfg["workload"] = cfg.get("workload", key) + " [cloud storage: %s]" % label
+            if storage != "fp32":
+                out["dtype"] = dtype
+                out["bit_exact"] = check[storage]["bit_exact"]
+                out["max|diff|"] = check[storage]["max|diff|"]
             else:
-                cfg["workload"] = cfg.get("workload", key) + " [cloud storage: fp32]"
                 out["bit_exact"] = True                  # (the reference itself)
                 out["max|diff|"] = 0.0
             out["cloud_storage"] = storage

@@ -1,5 +1,5 @@
 #!/bin/bash
-# usage (GPU box, repo root): tools/pmc_traffic.sh <tag> [workload]
+# usage (GPU box, repo root): tools/pmc_traffic.sh <tag> [workload] [cloud storage: fp32 | sh_fp16 | sh_q8]
 # Collects HBM traffic of every kernel with rocprofv3 PMC counters, one counter family per pass
 # (FETCH_SIZE needs 3 TCC slots, WRITE_SIZE 2 -- MI355X_MICROARCH.md), no trace domains mixed in,
 # over `bench.py --frames-in-flight 1` (every kernel alone on the GPU), and writes
@@ -8,11 +8,14 @@ export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 TAG=$1
 WL=${2:-cfg2}
+# (a cloud storage: the same bench run through tools/cloud_storage_bench.py's child mode, which sets the renderer's default)
+BENCH="$R/bench.py"
+[ -n "$3" ] && BENCH="$R/tools/cloud_storage_bench.py --child $3 --"
 O=${PROFILE_OUT:-profile_out}
 mkdir -p $R/$O/pmc_$TAG
 for C in FETCH_SIZE WRITE_SIZE; do
   (cd /tmp && timeout 400 rocprofv3 --kernel-trace --pmc $C -d $R/$O/pmc_$TAG/$C -o run --output-format csv -- \
-     python $R/bench.py --workload $WL --frames-in-flight 1 --steps 8 --warmup 2 --prewarm 8 --serial-frames 8 --no-cpu-baseline --profile-frames 1 --timing-stride 0 > $R/$O/pmc_$TAG/$C.log 2>&1)
+     python $BENCH --workload $WL --frames-in-flight 1 --steps 8 --warmup 2 --prewarm 8 --serial-frames 8 --no-cpu-baseline --profile-frames 1 --timing-stride 0 > $R/$O/pmc_$TAG/$C.log 2>&1)
 done
 python - <<PY
 import csv, json, collections, glob
