@@ -57,6 +57,13 @@ int msplat_set_tile_probe(msplat_ctx* ctx, int enable);
 int msplat_debug_get_tile_probe8(msplat_ctx* ctx, uint32_t* dst8, uint32_t tile_cap);
 int msplat_get_composite_work(msplat_ctx* ctx, msplat_composite_work* out);
 
+/* ---- the compositor's schedule: the context's latest compositor launch, as the host chose it (no device work).  out[0] = work items
+ * ((bin, quadrant) tiles), [1] = grid: workgroups launched -- grid < items means persistent waves pulling from the work queue, grid ==
+ * items every item on its own wave --, [2] = 1 if the bins were walked heaviest-first, [3] = kernel kind: 0 the splat compositor, 1 the
+ * draw-order depth / target-rounding compositor, 2 points.  After a two-pass Render the numbers are those of its FIRST pass (the second
+ * pass's item count, the unfinished bins, exists on the device only; its grid is chosen the same way) ---- */
+int msplat_debug_get_compositor_launch(msplat_ctx* ctx, uint32_t out[4]);
+
 /* ---- msplat_band_exchange on ONE rank (tests on a one-GPU box): the runs of bin rows that rank `rank` of `world` owns travel
  * from src to dst through ncclSend / ncclRecv to the calling rank itself (`comm` = a 1-rank communicator) ---- */
 int msplat_debug_band_exchange_loopback(msplat_ctx* ctx, void* comm, int32_t kind, int32_t block_rows, int32_t world, int32_t rank,

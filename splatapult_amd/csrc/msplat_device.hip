@@ -237,6 +237,7 @@ struct msplat_ctx {
     uint32_t occ_probe_left = 0, occ_no_shrink = 0, occ_wait_frames = 0;
     bool occ_pinned = false;                 // msplat_debug_two_pass: the share is fixed
     bool last_render_two_pass = false;
+    uint32_t comp_launch[4] = {0, 0, 0, 0};  // msplat_debug_get_compositor_launch: items, grid, ordered, kernel kind of the latest compositor launch
     uint64_t frames_rendered = 0, frames_two_pass = 0;
 
     std::unique_ptr<AsyncWorker> worker;     // msplat_config.async_submit
@@ -1455,6 +1456,15 @@ static int issue_compositor(RenderChain& rc, int occ_pass, int ev_c0, int ev_c1)
 
     // persistent compositor: a fixed pool of waves pulls (bin, quadrant) items; never more waves than items
     const int cgrid = std::min(ntiles * 4, ctx->comp_waves);     // work items = (bin, quadrant) (the draw-order compositors)
+    // what msplat_debug_get_compositor_launch reports (host bookkeeping only).  The second pass of a two-pass frame keeps pass 1's
+    // numbers: its item count (the unfinished bins) exists on the device alone, its grid is computed like pass 1's
+    if (ntiles > 0 && occ_pass != 2) {
+        const bool draw_order = ctx->point_mode || ctx->depth_bits != 0 || ctx->rop != 0;
+        ctx->comp_launch[0] = draw_order ? (uint32_t)ntiles * 4u : comp_items;
+        ctx->comp_launch[1] = draw_order ? (uint32_t)cgrid : std::min(comp_items, comp_pool);
+        ctx->comp_launch[2] = ordered ? 1u : 0u;
+        ctx->comp_launch[3] = ctx->point_mode ? 2u : draw_order ? 1u : 0u;
+    }
     // (frames in flight: serialising the compositor launches of the contexts sharing a cloud with an event
     //  gate was measured r1 -- no gain over letting the hardware queues interleave them, dropped)
     if (ntiles > 0 && ctx->probe_on && ctx->probe.p && (ctx->point_mode || ctx->depth_bits != 0 || ctx->rop != 0))

@@ -323,6 +323,18 @@ int msplat_get_composite_work(msplat_ctx* ctx, msplat_composite_work* out)
     return MSPLAT_OK;
 }
 
+// the context's latest compositor launch as issue_compositor chose it: work items, workgroups launched, bins walked heaviest-first,
+// kernel kind (0 splat compositor, 1 draw-order depth / target-rounding compositor, 2 points).  grid < items: persistent waves
+// that pull from the work queue; grid == items: every item on its own wave.  A two-pass frame reports its first pass.
+int msplat_debug_get_compositor_launch(msplat_ctx* ctx, uint32_t out[4])
+{
+    drain_async(ctx);
+    if (!ctx || !out) return fail(ctx, MSPLAT_ERR_INVALID_ARG, "NULL argument");
+    if (!ctx->has_render) return fail(ctx, MSPLAT_ERR_NO_SORT, "no render yet");
+    for (int i = 0; i < 4; ++i) out[i] = ctx->comp_launch[i];
+    return MSPLAT_OK;
+}
+
 int msplat_debug_get_tile_lists(msplat_ctx* ctx, uint32_t* tile_start, uint32_t tile_cap,
                                 uint32_t* pairs, uint64_t pair_cap)
 {

@@ -450,6 +450,14 @@ class SplatRenderer:
         _capi.check(self._ctx, self._lib.msplat_get_composite_work(self._ctx, C.byref(w)))
         return {k: int(getattr(w, k)) for k, _ in _capi.CompositeWork._fields_}
 
+    def compositor_launch(self):
+        """(work items, grid, ordered, kind) of the current context's latest compositor launch (msplat_debug_get_compositor_launch):
+        grid < items = persistent waves on the work queue, grid == items = every item on its own wave; kind 0 splats, 1 the
+        draw-order depth / target-rounding compositor, 2 points; a two-pass Render reports its first pass"""
+        out = (C.c_uint32 * 4)()
+        _capi.check(self._ctx, self._lib.msplat_debug_get_compositor_launch(self._ctx, out))
+        return tuple(int(v) for v in out)
+
     def two_pass_state(self, share=0.0):
         """(two-pass Renders so far, share of the visible splats the next one puts into its first pass) summed / taken over the
         contexts; share > 0 pins the share (msplat_debug_two_pass), 0 leaves it to the feedback loop"""
