@@ -43,3 +43,19 @@ def default_view(W, H, z=7.0, yaw=0.0, pitch=0.0, x=0.0, y=0.0):
     cam = camera.pose((x, y, z), yaw, pitch)
     proj = camera.perspective(camera.FOVY, W / H)
     return cam, proj, [0, 0, W, H], NF
+
+
+def strip_view(W, H, yaw=0.0):
+    """a W x H crop around the centre of an 8192 x 8192, 90-degree frame (focal length 4096 px on both axes) seen from z = 7:
+    8192 x 64 and 64 x 8192 have 256 bins along one axis and 2 along the other"""
+    cam = camera.pose((0.0, 0.0, 7.0), yaw, 0.0)
+    proj = camera.create_projection(-W / 8192.0, W / 8192.0, H / 8192.0, -H / 8192.0)
+    return cam, proj, [0, 0, W, H], NF
+
+
+def strip_attrs(n, seed, W, H, hard):
+    """attributes of a cloud that lies inside the strip of strip_view(W, H): hard_attrs or a plain synthetic cloud whose
+    coordinate along the strip's short axis is scaled by min / max of the viewport's sides"""
+    a = hard_attrs(n, seed) if hard else synthetic.generate(n, seed=seed, pos_sigma=2.5, log_scale_mean=-3.6)
+    a["xyz"][:, 1 if W > H else 0] *= min(W, H) / max(W, H)
+    return a
