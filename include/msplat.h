@@ -30,14 +30,14 @@ enum {
     MSPLAT_ERR_IO = -8,            /* PLY / JSON / image open or parse failure */
     MSPLAT_ERR_PAIR_OVERFLOW_EARLIER = -9  /* a WARNING: this call did its work, but an earlier device-output render had overflowed the pair buffer (that frame lacks splats; the buffer has grown) */
 };
-enum { MSPLAT_FB_RGBA32F = 0, MSPLAT_FB_RGBA16F = 1 };
+enum { MSPLAT_FB_RGBA32F = 0, MSPLAT_FB_RGBA16F = 1, MSPLAT_FB_RGBA8 = 2, MSPLAT_FB_SRGB8_ALPHA8 = 3 };   /* msplat_config.fb_format; 8-bit: bytes R G B A */
+#define MSPLAT_FB_BYTES_PER_PIXEL(fb_format) ((fb_format) == MSPLAT_FB_RGBA32F ? 16u : (fb_format) == MSPLAT_FB_RGBA16F ? 8u : 4u)
 enum { MSPLAT_ROP_NONE = 0, MSPLAT_ROP_RGBA8 = 1, MSPLAT_ROP_RGBA16F = 2 };          /* msplat_set_target_emulation */
 enum { MSPLAT_TWO_PASS_AUTO = 0, MSPLAT_TWO_PASS_ON = 1, MSPLAT_TWO_PASS_OFF = 2 };  /* msplat_config.two_pass */
 enum { MSPLAT_SPATIAL_AUTO = 0, MSPLAT_SPATIAL_ON = 1, MSPLAT_SPATIAL_OFF = 2 };     /* msplat_config.spatial_order */
 enum { MSPLAT_FRAMES_AUTO = 0, MSPLAT_FRAMES_SERIAL = 1, MSPLAT_FRAMES_IN_FLIGHT = 2 }; /* msplat_config.frame_mode */
 enum { MSPLAT_RANK_AUTO = 0, MSPLAT_RANK_BALLOT = 1 };                               /* msplat_config.rank_mode */
-enum { MSPLAT_CU_ALL = 0, MSPLAT_CU_EVEN = 1, MSPLAT_CU_ODD = 2 };   /* msplat_config.cu_partition: every CU, or the even / odd CU positions
-                                                                       of every XCD (4 frames in flight alternate: +3-5 %) */
+enum { MSPLAT_CU_ALL = 0, MSPLAT_CU_EVEN = 1, MSPLAT_CU_ODD = 2 };   /* msplat_config.cu_partition: every CU, or the even / odd CU positions of every XCD (4 frames in flight alternate: +3-5 %, INTEGRATION 6) */
 enum { MSPLAT_TARGET_CLEAR = 0, MSPLAT_TARGET_LOAD = 1, MSPLAT_TARGET_PREMULTIPLIED = 2 };   /* msplat_set_target_mode */
 enum { MSPLAT_BANDS_CONTIGUOUS = 0, MSPLAT_BANDS_INTERLEAVED = 1, MSPLAT_BANDS_BLOCK_INTERLEAVED = 2, MSPLAT_BANDS_ROOT_WEIGHTED = 3 };
 
@@ -47,7 +47,7 @@ typedef struct msplat_group msplat_group;
 typedef struct msplat_points msplat_points;
 
 /* Construction parameters: the implicit GL state the reference's renderer lives in -- device = the GL context's GPU
- * (sdl_main.cpp:98-100), fb_format = App's --fp16 / --fp32 FBO (app.cpp:1000-1035), srgb = SplatRenderer::Init's
+ * (sdl_main.cpp:98-100), fb_format = App's --fp16 / --fp32 FBO or its 8-bit window, sRGB-encoded or not (app.cpp:1000-1035), srgb = SplatRenderer::Init's
  * isFramebufferSRGBEnabled (splatrenderer.cpp:60-72).  Fields were appended over time: a struct_size that ends before a field
  * selects its AUTO value.  Pixels, keys and lists do not depend on any field below `stream` (INTEGRATION.md Appendix A). */
 typedef struct msplat_config {
@@ -135,12 +135,13 @@ int msplat_get_cloud_storage(const msplat_ctx* ctx);
 int msplat_sort(msplat_ctx* ctx, const float cameraMat[16], const float projMat[16], const float viewport[4], const float nearFar[2]);
 
 /* ---- SplatRenderer::Render (splatrenderer.cpp:315-343) plus the GL pipeline behind its glDrawElements: splat_vert / _geom / _frag.glsl and
- * the blend / clear state of app.cpp:144-164.  Writes W x H RGBA (float or half), row 0 = GL bottom row, alpha = 1 (msplat_set_target_mode: or
+ * the blend / clear state of app.cpp:144-164.  Writes W x H RGBA (float, half or 4 bytes), row 0 = GL bottom row, alpha = 1 (msplat_set_target_mode: or
  * over the target's contents).  out_is_device != 0: `rgba` is device memory, the call is asynchronous on the stream; else host memory, the
- * call returns after the copy.  pitch_bytes = bytes between rows (0 = tight).
- * Pair-buffer overflow: a host-output render grows the buffer and retries.  A device-output render cannot know; the NEXT msplat_sort /
- * msplat_render / msplat_synchronize of the context grows the buffer (unless pair_capacity fixed it) and reports it once -- msplat_synchronize:
- * MSPLAT_ERR_PAIR_OVERFLOW; sort / render, whose own work is done: _EARLIER.  That frame lacks splats in its last bin columns: render it again. */
+ * call returns after the copy.  pitch_bytes = bytes between rows (0 = tight; else >= W pixels and a multiple of the pixel size, or MSPLAT_ERR_INVALID_ARG).
+ * 8-bit targets (INTEGRATION.md 15) round the fp32 value x an RGBA32F context stores, once: v = x > 0 ? (x > 1 ? 1 : x) : 0 (NaN -> 0), code = (uint8)(v * 255.0f + 0.5f),
+ * fp32 multiply, fp32 add, truncation.  MSPLAT_FB_SRGB8_ALPHA8: alpha so; r g b from e = v <= 0.0031308 ? 12.92 v : 1.055 v^(1/2.4) - 0.055 with |255 e - code| <= 0.5 + 2^-10.
+ * Pair-buffer overflow: a host-output render grows the buffer and retries.  A device-output render cannot know; the NEXT msplat_sort / msplat_render / msplat_synchronize
+ * of the context grows the buffer (unless pair_capacity fixed it) and reports it once -- msplat_synchronize: MSPLAT_ERR_PAIR_OVERFLOW; sort / render, whose own work is done: _EARLIER.  That frame lacks splats in its last bin columns: render it again. */
 int msplat_render(msplat_ctx* ctx, const float cameraMat[16], const float projMat[16], const float viewport[4],
                   const float nearFar[2], void* rgba, uint64_t pitch_bytes, int out_is_device);
 /* ---- msplat_render plus a depth plane (INTEGRATION.md 14).  depth == NULL: msplat_render.  Else W x H float32 on every context (fp16 cannot resolve z_w near
@@ -152,8 +153,7 @@ int msplat_render(msplat_ctx* ctx, const float cameraMat[16], const float projMa
  * (call per eye), the device group, msplat_band_exchange of the plane. */
 int msplat_render_depth(msplat_ctx* ctx, const float cameraMat[16], const float projMat[16], const float viewport[4], const float nearFar[2],
                         void* rgba, uint64_t pitch_bytes, float* depth, uint64_t depth_pitch_bytes, int out_is_device);
-/* the reference's VR frame -- Sort with the first eye, Render per eye (app.cpp:603-607) -- as ONE chain of launches; the same
- * pixels as two msplat_render calls, bit for bit.  Host targets, banded contexts, points and the emulations go view by view. */
+/* the reference's VR frame -- Sort with the first eye, Render per eye (app.cpp:603-607) -- as ONE chain of launches; the same pixels as two msplat_render calls, bit for bit.  Host targets, banded contexts, points and the emulations go view by view. */
 int msplat_render_stereo(msplat_ctx* ctx, const float cameraMat0[16], const float projMat0[16], const float cameraMat1[16],
                          const float projMat1[16], const float viewport[4], const float nearFar[2], void* rgba0, void* rgba1,
                          uint64_t pitch_bytes, int out_is_device);
@@ -233,13 +233,13 @@ int msplat_get_timings(msplat_ctx* ctx, msplat_timings* out);
  * sdl_main.cpp:79; XR swapchains); bits = 0 (default) models the colour-only --fp16 / --fp32 FBO.  Target rounding (SURVEY.md 8a-12, app.cpp:1012-1020):
  * the RGBA8 back buffer clamps and stores 8-bit unorm after EVERY blend, --fp16 rounds to fp16 after every blend; MSPLAT_ROP_NONE (default): fp32, rounded once. */
 int msplat_set_depth_test(msplat_ctx* ctx, int depth_bits);
-int msplat_set_target_emulation(msplat_ctx* ctx, int rop);
+int msplat_set_target_emulation(msplat_ctx* ctx, int rop);         /* MSPLAT_ERR_UNSUPPORTED on an MSPLAT_FB_SRGB8_ALPHA8 context: it rounds linear values */
 /* ---- the target's contents: the reference never clears in Render; it blends (GL_ONE, GL_ONE_MINUS_SRC_ALPHA, app.cpp:154-156) over what app.cpp drew
  * before.  For the following msplat_render / _stereo of the context, per pixel with C = the splats' premultiplied colour and T = the transmittance WHERE
  * THE WALK STOPPED (early termination leaves it below t_epsilon, not at its limit: an error <= t_epsilon |dst|; t_epsilon = 0 removes it):
  * CLEAR (default) writes (C, 1); PREMULTIPLIED (C, 1 - T), that blend over a target cleared to (0,0,0,0), a layer for a compositor; LOAD reads dst, the
- * pixel `rgba` holds (host output: the caller's array), and writes rgb = fma(T, dst.rgb, C), a = fma(T, dst.a - 1, 1) -- RGBA16F: read as half, blended
- * in fp32, rounded once; a pixel no splat reaches (T == 1) keeps its bits; dst lies behind every splat (also under msplat_set_depth_test).  LOAD is not idempotent: after MSPLAT_ERR_PAIR_OVERFLOW[_EARLIER]
+ * pixel `rgba` holds (host output: the caller's array), and writes rgb = fma(T, dst.rgb, C), a = fma(T, dst.a - 1, 1) -- RGBA16F: read as half, 8-bit: as (float)code / 255.0f
+ * (SRGB8_ALPHA8 r g b: decoded, c <= 0.04045 ? c / 12.92 : ((c + 0.055) / 1.055)^2.4), blended in fp32, rounded once; a pixel no splat reaches (T == 1) keeps its bits; dst lies behind every splat (also under msplat_set_depth_test).  LOAD is not idempotent: after MSPLAT_ERR_PAIR_OVERFLOW[_EARLIER]
  * a device-output caller restores dst before rendering the frame again.  Banded contexts read and write owned rows only.  MSPLAT_ERR_UNSUPPORTED, at
  * whichever call comes second: a non-CLEAR mode with a target emulation != MSPLAT_ROP_NONE, a point cloud, or (at the Render) msplat_set_tile_probe. */
 int msplat_set_target_mode(msplat_ctx* ctx, int32_t mode);

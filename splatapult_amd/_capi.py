@@ -11,7 +11,10 @@ OK = 0
 ERR_INVALID_ARG, ERR_NO_DEVICE, ERR_HIP, ERR_NO_CLOUD, ERR_NO_SORT, ERR_UNSUPPORTED, ERR_PAIR_OVERFLOW, ERR_IO = \
     -1, -2, -3, -4, -5, -6, -7, -8
 ERR_PAIR_OVERFLOW_EARLIER = -9      # the call did its work; an EARLIER device-output frame had overflowed the pair buffer
-FB_RGBA32F, FB_RGBA16F = 0, 1
+FB_RGBA32F, FB_RGBA16F, FB_RGBA8, FB_SRGB8_ALPHA8 = 0, 1, 2, 3
+FB_FORMATS = {"fp32": FB_RGBA32F, "fp16": FB_RGBA16F, "rgba8": FB_RGBA8, "srgb8": FB_SRGB8_ALPHA8}      # msplat_config.fb_format
+FB_NAMES = {v: n for n, v in FB_FORMATS.items()}
+FB_DTYPES = {FB_RGBA32F: "float32", FB_RGBA16F: "float16", FB_RGBA8: "uint8", FB_SRGB8_ALPHA8: "uint8"}  # host arrays, (H, W, 4)
 ROP_NONE, ROP_RGBA8, ROP_RGBA16F = 0, 1, 2
 RANK_AUTO, RANK_BALLOT = 0, 1
 FRAMES_AUTO, FRAMES_SERIAL, FRAMES_IN_FLIGHT = 0, 1, 2
@@ -231,6 +234,13 @@ def check(handle, rc, last_error=None):
     if rc != OK:
         msg = last_error(handle)
         raise MsplatError(rc, msg.decode() if msg else "")
+
+
+def fb_format(name):
+    """constructor argument ("fp32" | "fp16" | "rgba8" | "srgb8") -> MSPLAT_FB_*"""
+    if name not in FB_FORMATS:
+        raise ValueError("fb_format must be one of %s (got %r)" % (sorted(FB_FORMATS), name))
+    return FB_FORMATS[name]
 
 
 def band_plan(kind, rows_full, world, rank, block_rows=1):

@@ -238,16 +238,101 @@ __device__ __forceinline__ uint32_t last_le(const uint32_t* tab, uint32_t x, uin
 // elements a pass walks: the count an earlier kernel left on the device (d_n) or a static one, at most n_cap
 __device__ __forceinline__ uint32_t active_count(const uint32_t* d_n, uint32_t n_static, uint32_t n_cap) { return min(d_n ? *d_n : n_static, n_cap); }
 
-// stores one pixel of a target row: RGBA16F (F16) or RGBA32F
-template <bool F16>
+// ------------------------------------------------------------------------------------------
+// Target pixel formats: the values of MSPLAT_FB_* (include/msplat.h).  The compositors take the format as a template constant that
+// only load_px / store_px look at: the accumulators are fp32 in every instantiation and the inner loops never see it.
+constexpr int kFbF32 = 0, kFbF16 = 1, kFbUnorm8 = 2, kFbSrgb8 = 3;
+
+// sRGB8 -> linear (GL 4.6 8.24): entry k = (float)decode((double)((float)k / 255.0f)), decode(c) = c <= 0.04045 ? c / 12.92 :
+// ((c + 0.055) / 1.055)^2.4 in double.  tests/fb8_rule.py restates it; tests/test_fb8.py compares the two tables.
+static __device__ const float kSrgb8Decode[256] = {
+    0.0f, 0.000303526991f, 0.000607053982f, 0.000910580973f, 0.00121410796f, 0.00151763496f, 0.00182116195f, 0.00212468882f,
+    0.00242821593f, 0.00273174304f, 0.00303526991f, 0.00334653584f, 0.00367650739f, 0.00402471703f, 0.00439144205f, 0.00477695372f,
+    0.00518151699f, 0.00560539216f, 0.00604883349f, 0.00651209103f, 0.00699541066f, 0.00749903219f, 0.00802319311f, 0.00856812578f,
+    0.00913405884f, 0.00972121768f, 0.010329823f, 0.0109600946f, 0.0116122449f, 0.0122864889f, 0.0129830325f, 0.0137020834f,
+    0.0144438446f, 0.0152085163f, 0.0159962941f, 0.0168073773f, 0.017641956f, 0.0185002219f, 0.0193823632f, 0.0202885643f,
+    0.0212190114f, 0.0221738853f, 0.0231533684f, 0.024157634f, 0.0251868609f, 0.0262412224f, 0.0273208935f, 0.02842604f,
+    0.0295568351f, 0.0307134446f, 0.0318960324f, 0.0331047662f, 0.0343398079f, 0.0356013142f, 0.0368894525f, 0.0382043719f,
+    0.0395462364f, 0.0409151986f, 0.0423114114f, 0.043735031f, 0.045186203f, 0.0466650873f, 0.0481718257f, 0.0497065671f,
+    0.0512694642f, 0.0528606512f, 0.0544802807f, 0.0561284944f, 0.0578054376f, 0.0595112443f, 0.0612460598f, 0.063010022f,
+    0.0648032725f, 0.0666259453f, 0.0684781745f, 0.0703601018f, 0.0722718537f, 0.0742135718f, 0.0761853904f, 0.0781874284f,
+    0.0802198276f, 0.0822827145f, 0.0843762159f, 0.0865004659f, 0.088655591f, 0.090841718f, 0.0930589661f, 0.0953074694f,
+    0.0975873545f, 0.0998987332f, 0.10224174f, 0.104616493f, 0.107023105f, 0.109461717f, 0.111932434f, 0.114435382f,
+    0.116970673f, 0.119538434f, 0.122138776f, 0.124771819f, 0.127437681f, 0.130136475f, 0.13286832f, 0.135633335f,
+    0.138431624f, 0.141263291f, 0.144128472f, 0.147027269f, 0.149959788f, 0.152926162f, 0.155926466f, 0.158960834f,
+    0.162029386f, 0.165132195f, 0.168269396f, 0.171441108f, 0.174647406f, 0.177888423f, 0.18116425f, 0.18447499f,
+    0.187820777f, 0.191201687f, 0.194617838f, 0.198069319f, 0.20155625f, 0.205078736f, 0.208636865f, 0.212230757f,
+    0.215860531f, 0.219526231f, 0.223227978f, 0.226965904f, 0.23074007f, 0.23455061f, 0.238397598f, 0.242281154f,
+    0.246201351f, 0.25015831f, 0.254152119f, 0.258182883f, 0.262250692f, 0.266355634f, 0.270497829f, 0.274677336f,
+    0.278894305f, 0.283148766f, 0.287440866f, 0.291770667f, 0.296138287f, 0.300543815f, 0.304987341f, 0.309468955f,
+    0.313988745f, 0.318546802f, 0.323143244f, 0.327778131f, 0.332451552f, 0.337163657f, 0.341914445f, 0.346704096f,
+    0.351532638f, 0.356400162f, 0.361306816f, 0.366252631f, 0.371237695f, 0.376262158f, 0.38132605f, 0.386429459f,
+    0.391572505f, 0.396755248f, 0.401977807f, 0.407240242f, 0.412542641f, 0.417885095f, 0.423267692f, 0.428690523f,
+    0.434153676f, 0.439657211f, 0.445201218f, 0.450785816f, 0.456411034f, 0.462077022f, 0.467783809f, 0.473531514f,
+    0.479320198f, 0.48514995f, 0.491020888f, 0.496933013f, 0.502886474f, 0.50888133f, 0.514917672f, 0.520995617f,
+    0.527115166f, 0.533276439f, 0.539479494f, 0.545724511f, 0.55201143f, 0.55834043f, 0.564711511f, 0.571124852f,
+    0.577580452f, 0.584078431f, 0.590618849f, 0.597201824f, 0.603827357f, 0.610495567f, 0.617206573f, 0.623960435f,
+    0.630757153f, 0.637596905f, 0.644479692f, 0.651405632f, 0.658374846f, 0.665387332f, 0.672443151f, 0.679542482f,
+    0.686685324f, 0.693871796f, 0.701101899f, 0.708375812f, 0.715693533f, 0.723055124f, 0.730460763f, 0.73791045f,
+    0.745404243f, 0.752942204f, 0.760524511f, 0.768151164f, 0.775822222f, 0.783537805f, 0.791297972f, 0.799102724f,
+    0.806952298f, 0.814846575f, 0.822785735f, 0.830769897f, 0.838799f, 0.846873224f, 0.854992628f, 0.863157213f,
+    0.871367097f, 0.8796224f, 0.887923121f, 0.896269381f, 0.904661179f, 0.913098633f, 0.921581864f, 0.930110872f,
+    0.938685715f, 0.947306514f, 0.955973327f, 0.964686275f, 0.973445296f, 0.982250571f, 0.991102099f, 1.0f,
+};
+
+// the code an 8-bit unorm target stores for x (msplat.h: PresentRGBA8's rule, rop_store's rule): clamp -- NaN and -inf to 0, +inf to 1 --
+// then an fp32 multiply, an fp32 add (-ffp-contract=off keeps them apart) and truncation
+__device__ __forceinline__ uint32_t unorm8_code(float x)
+{
+    const float v = x > 0.0f ? (x > 1.0f ? 1.0f : x) : 0.0f;
+    return (uint32_t)(v * 255.0f + 0.5f);
+}
+
+// ... and for an sRGB-encoded channel (LinearToSRGB, util.cpp:357-367): e = 12.92 v below 0.0031308, else 1.055 v^(1/2.4) - 0.055 with
+// the power as exp2(log2(v) / 2.4) on the transcendental unit (v is a normal number there).  The contract is a margin, not bits:
+// |255 e - code| <= 0.5 + 2^-10 against e in double (~1 ulp each for v_log_f32 and v_exp_f32, |log2 v| < 8.4: about 1e-4 of a code)
+__device__ __forceinline__ uint32_t srgb8_code(float x)
+{
+    const float v = x > 0.0f ? (x > 1.0f ? 1.0f : x) : 0.0f;
+    const float e = v <= 0.0031308f ? 12.92f * v : 1.055f * __builtin_amdgcn_exp2f(__builtin_amdgcn_logf(v) * (1.0f / 2.4f)) - 0.055f;
+    return (uint32_t)(e * 255.0f + 0.5f);
+}
+
+// stores one pixel of a target row in the format FMT (kFb*).  8-bit targets: one dword per pixel, bytes R G B A in memory order
+template <int FMT>
 __device__ __forceinline__ void store_px(void* row, int x, const float4 px)
 {
-    if (F16) {
+    if (FMT == kFbF16) {
         union { _Float16 h[4]; uint2 u; } pk;
         pk.h[0] = (_Float16)px.x; pk.h[1] = (_Float16)px.y; pk.h[2] = (_Float16)px.z; pk.h[3] = (_Float16)px.w;
         ((uint2*)row)[x] = pk.u;
+    } else if (FMT == kFbUnorm8) {
+        ((uint32_t*)row)[x] = unorm8_code(px.x) | (unorm8_code(px.y) << 8) | (unorm8_code(px.z) << 16) | (unorm8_code(px.w) << 24);
+    } else if (FMT == kFbSrgb8) {
+        ((uint32_t*)row)[x] = srgb8_code(px.x) | (srgb8_code(px.y) << 8) | (srgb8_code(px.z) << 16) | (unorm8_code(px.w) << 24);
     } else {
         ((float4*)row)[x] = px;
+    }
+}
+
+// reads one pixel of a target row (MSPLAT_TARGET_LOAD's destination) as fp32.  8-bit targets: (float)code / 255.0f, an fp32 division;
+// the sRGB target's colour channels through the decode table, its alpha is linear
+template <int FMT>
+__device__ __forceinline__ float4 load_px(const void* row, int x)
+{
+    if (FMT == kFbF16) {
+        union { _Float16 h[4]; uint2 u; } in;
+        in.u = ((const uint2*)row)[x];
+        return make_float4((float)in.h[0], (float)in.h[1], (float)in.h[2], (float)in.h[3]);
+    } else if (FMT == kFbUnorm8) {
+        const uint32_t w = ((const uint32_t*)row)[x];
+        return make_float4((float)(w & 255u) / 255.0f, (float)((w >> 8) & 255u) / 255.0f, (float)((w >> 16) & 255u) / 255.0f,
+                           (float)(w >> 24) / 255.0f);
+    } else if (FMT == kFbSrgb8) {
+        const uint32_t w = ((const uint32_t*)row)[x];
+        return make_float4(kSrgb8Decode[w & 255u], kSrgb8Decode[(w >> 8) & 255u], kSrgb8Decode[(w >> 16) & 255u], (float)(w >> 24) / 255.0f);
+    } else {
+        return ((const float4*)row)[x];
     }
 }
 

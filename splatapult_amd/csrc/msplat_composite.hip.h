@@ -63,8 +63,9 @@ constexpr int kCompOcc = 5;        // occupancy bound handed to the compiler (<=
 // tw = Ts w' = T w exactly as before (powers of two), colours accumulate unchanged and Ts -= 2^118 tw.  The bias costs 4 bits
 // of the exponent's absolute precision (|e - 118| ~ 2^7 instead of <= 2^3): a relative error of 3e-6 in w.  Only e == -8
 // exactly (w == 1/256, which the reference discards) is kept: a measure-zero threshold flip.
-// Template parameters instead of run-time arguments (r5): F16 = RGBA16F target; OCC = 0 one pass, 1 / 2 the passes of a two-pass
-// frame; TWO_VIEWS = both eyes in one chain; PROBE = per-item counters.  The plain frame's instantiation <F16, 0, false, false>
+// Template parameters instead of run-time arguments (r5): FMT = the target's pixel format (kFb*: load_px / store_px); OCC = 0 one
+// pass, 1 / 2 the passes of a two-pass frame; TWO_VIEWS = both eyes in one chain; PROBE = per-item counters.  The plain frame's
+// instantiation <FMT, 0, false, false>
 // carries none of the others' registers (r4 passed them at run time on top of the ~500-byte FrameParams: 81 VGPRs / 14 SGPR spills
 // against r3's 79 / 5) and takes the eleven words of CompParams instead of five 4x4 matrices.
 // TM = MSPLAT_TARGET_* (msplat_set_target_mode): what the final store -- the one place that writes pixels -- does with the target's
@@ -87,7 +88,7 @@ struct CompExtra {
     float* zstate;               // DEPTH, OCC != 0: the depth accumulator per pixel, beside `state`
 };
 
-template <bool F16, int OCC, bool TWO_VIEWS, bool PROBE, int TM = kTargetClear, bool DEPTH = false>
+template <int FMT, int OCC, bool TWO_VIEWS, bool PROBE, int TM = kTargetClear, bool DEPTH = false>
 __global__ __launch_bounds__(kCompThreads, kCompOcc) void composite_kernel(const uint32_t* __restrict__ tile_start,
                                                                  const uint32_t* __restrict__ pairs,
                                                                  const float4* __restrict__ rec,
@@ -406,6 +407,7 @@ __global__ __launch_bounds__(kCompThreads, kCompOcc) void composite_kernel(const
         if (inside[k] && !carry) {
             char* row = (char*)(second ? ex.out1 : out) + (size_t)(ybase + 4 * k) * pitch_bytes;
             float4 px = make_float4(cr[k >> 1][k & 1], cg[k >> 1][k & 1], cb[k >> 1][k & 1], 1.0f);
+            bool keep = false;
             if (TM != kTargetClear) {
                 // the GL blend (GL_ONE, GL_ONE_MINUS_SRC_ALPHA, app.cpp:154-156) is linear in the destination: over dst the frame is
                 // C + T dst, alpha 1 - T (1 - dst.a).  T = 2^-118 Ts is exact; the forms keep an opaque dst opaque.  The pixel is read
@@ -414,28 +416,22 @@ __global__ __launch_bounds__(kCompThreads, kCompOcc) void composite_kernel(const
                 if (TM == kTargetPremultiplied) {
                     px.w = 1.0f - t;
                 } else {
-                    float4 d;
-                    if (F16) {
-                        union { _Float16 h[4]; uint2 u; } in;
-                        in.u = ((const uint2*)row)[x];
-                        d = make_float4((float)in.h[0], (float)in.h[1], (float)in.h[2], (float)in.h[3]);
-                    } else {
-                        d = ((const float4*)row)[x];
-                    }
+                    const float4 d = load_px<FMT>(row, x);
                     px.x = __builtin_fmaf(t, d.x, px.x);
                     px.y = __builtin_fmaf(t, d.y, px.y);
                     px.z = __builtin_fmaf(t, d.z, px.z);
                     px.w = __builtin_fmaf(t, d.w - 1.0f, 1.0f);
                     // A pixel no splat reached (t == 1: every weight was 0, so C is 0 too) is handed through as it is: the formulas
                     // would round d.w - 1 for |d.w| < 0.5, turn -0 into +0 and -- this wave flushes fp32 denormals -- a denormal into 0
-                    if (t == 1.0f) px = d;
+                    // (an 8-bit target's pixel is not stored at all: its four bytes stay, whatever decode and encode would make of them)
+                    if (t == 1.0f) { px = d; keep = FMT == kFbUnorm8 || FMT == kFbSrgb8; }
                 }
                 // RGBA16F: the value is rounded to fp32 and THEN to half in every mode -- left alone, the compiler may fold an fma or
                 // subtraction and the conversion into one v_fma_mixlo_f16 (a single rounding to half: LOAD over zeros then differed
                 // from PREMULTIPLIED by an fp16 ulp in a few pixels per frame)
-                if (F16) asm volatile("" : "+v"(px.x), "+v"(px.y), "+v"(px.z), "+v"(px.w));
+                if (FMT == kFbF16) asm volatile("" : "+v"(px.x), "+v"(px.y), "+v"(px.z), "+v"(px.w));
             }
-            store_px<F16>(row, x, px);
+            if (!keep) store_px<FMT>(row, x, px);
             if (DEPTH) {
                 // expected window depth over the clear depth 1.0: the blend of kTargetLoad with colour z and dst = 1 (T = 2^-118 Ts is
                 // exact; a pixel no splat reached reads exactly 1).  Every z is <= 1 and the weights sum to 1 - T, but the partial sums
@@ -483,7 +479,9 @@ struct DrawPixels { float cr[4], cg[4], cb[4], ca[4]; uint32_t zbuf[4]; };
 // initial(px, x, ybase): what the cleared pixels start from; relevant(p0, p1, p2, X0, X1, Y0, Y1): can the record touch a pixel
 // centre of the tile; shade(px, r, zj, fx, ybase): blends the staged record r[0..2] of depth zj into the lane's pixels;
 // final_alpha(px, k): the alpha stored with pixel k.  depth_test: the records' quantised depths zq[rank] are staged too.
-template <bool HALF, class Initial, class Relevant, class Shade, class FinalAlpha>
+// FMT: the target's pixel format (kFb*).  KEEP_UNTOUCHED (MSPLAT_TARGET_LOAD into an 8-bit target): a pixel no fragment wrote -- its
+// emulated depth is still the clear value: a fragment that writes leaves its own, smaller one -- is not stored, its bytes stay.
+template <int FMT, bool KEEP_UNTOUCHED, class Initial, class Relevant, class Shade, class FinalAlpha>
 __device__ __forceinline__ void draw_order_walk(const uint32_t* __restrict__ tile_start, const uint32_t* __restrict__ pairs,
                                                 const float4* __restrict__ rec, const uint32_t* __restrict__ zq, bool depth_test,
                                                 void* __restrict__ out, size_t pitch_bytes, const FrameParams& fp, uint32_t cap,
@@ -536,9 +534,9 @@ __device__ __forceinline__ void draw_order_walk(const uint32_t* __restrict__ til
             }
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                if (x < fp.width && ybase + 4 * k < fp.height) {
+                if (x < fp.width && ybase + 4 * k < fp.height && !(KEEP_UNTOUCHED && px.zbuf[k] == 0xFFFFFFFFu)) {
                     char* row = (char*)out + (size_t)(ybase + 4 * k) * pitch_bytes;
-                    store_px<HALF>(row, x, make_float4(px.cr[k], px.cg[k], px.cb[k], final_alpha(px, k)));
+                    store_px<FMT>(row, x, make_float4(px.cr[k], px.cg[k], px.cb[k], final_alpha(px, k)));
                 }
             }
         }
@@ -551,7 +549,7 @@ __device__ __forceinline__ void draw_order_walk(const uint32_t* __restrict__ til
 // TM (msplat_set_target_mode, MSPLAT_ROP_NONE only): kTargetLoad starts the running colour AND alpha from the target's pixel, the
 // draw-order blend then runs over it (a = w + (1 - w) a); kTargetPremultiplied starts from (0, 0, 0, 0).  The emulated depth buffer
 // is cleared to 1.0 either way: the target's contents lie behind every splat.
-template <bool HALF, int TM = kTargetClear>
+template <int FMT, int TM = kTargetClear>
 __global__ __launch_bounds__(kCompThreads) void composite_depth_kernel(const uint32_t* __restrict__ tile_start, const uint32_t* __restrict__ pairs,
                                                                        const float4* __restrict__ rec, const uint32_t* __restrict__ zq,
                                                                        void* __restrict__ out, size_t pitch_bytes, FrameParams fp, uint32_t cap,
@@ -564,14 +562,8 @@ __global__ __launch_bounds__(kCompThreads) void composite_depth_kernel(const uin
         for (int k = 0; k < 4; ++k) {
             if (TM == kTargetLoad && x < fp.width && ybase + 4 * k < fp.height) {
                 const char* row = (const char*)out + (size_t)(ybase + 4 * k) * pitch_bytes;
-                if (HALF) {
-                    union { _Float16 h[4]; uint2 u; } in;
-                    in.u = ((const uint2*)row)[x];
-                    px.cr[k] = (float)in.h[0]; px.cg[k] = (float)in.h[1]; px.cb[k] = (float)in.h[2]; px.ca[k] = (float)in.h[3];
-                } else {
-                    const float4 d = ((const float4*)row)[x];
-                    px.cr[k] = d.x; px.cg[k] = d.y; px.cb[k] = d.z; px.ca[k] = d.w;
-                }
+                const float4 d = load_px<FMT>(row, x);
+                px.cr[k] = d.x; px.cg[k] = d.y; px.cb[k] = d.z; px.ca[k] = d.w;
             }
         }
     };
@@ -622,8 +614,9 @@ __global__ __launch_bounds__(kCompThreads) void composite_depth_kernel(const uin
         }
     };
     auto final_alpha = [](const DrawPixels& px, int k) -> float { return TM != kTargetClear ? px.ca[k] : 1.0f; };
-    draw_order_walk<HALF>(tile_start, pairs, rec, zq, fp.depth_bits != 0, out, pitch_bytes, fp, cap, order, queue, ntiles, s_rec, s_z,
-                          initial, relevant, shade, final_alpha);
+    constexpr bool keep_untouched = TM == kTargetLoad && (FMT == kFbUnorm8 || FMT == kFbSrgb8);
+    draw_order_walk<FMT, keep_untouched>(tile_start, pairs, rec, zq, fp.depth_bits != 0, out, pitch_bytes, fp, cap, order, queue, ntiles,
+                                         s_rec, s_z, initial, relevant, shade, final_alpha);
 }
 
 }  // namespace msplat

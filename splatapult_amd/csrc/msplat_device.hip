@@ -395,8 +395,8 @@ int msplat_create(msplat_ctx** out, const msplat_config* cfg)
     }
     if (c.rank_mode != MSPLAT_RANK_AUTO && c.rank_mode != MSPLAT_RANK_BALLOT)
         return fail(nullptr, MSPLAT_ERR_INVALID_ARG, "msplat_create: bad rank_mode %d", c.rank_mode);
-    if (c.fb_format != MSPLAT_FB_RGBA32F && c.fb_format != MSPLAT_FB_RGBA16F)
-        return fail(nullptr, MSPLAT_ERR_INVALID_ARG, "msplat_create: bad fb_format %d", c.fb_format);
+    if (c.fb_format < MSPLAT_FB_RGBA32F || c.fb_format > MSPLAT_FB_SRGB8_ALPHA8)
+        return fail(nullptr, MSPLAT_ERR_INVALID_ARG, "msplat_create: bad fb_format %d (MSPLAT_FB_RGBA32F .. MSPLAT_FB_SRGB8_ALPHA8)", c.fb_format);
     if (c.spatial_order < MSPLAT_SPATIAL_AUTO || c.spatial_order > MSPLAT_SPATIAL_OFF)
         return fail(nullptr, MSPLAT_ERR_INVALID_ARG, "msplat_create: bad spatial_order %d", c.spatial_order);
     if (c.two_pass < MSPLAT_TWO_PASS_AUTO || c.two_pass > MSPLAT_TWO_PASS_OFF)
@@ -674,6 +674,9 @@ int msplat_set_target_emulation(msplat_ctx* ctx, int rop)
     if (!ctx) return fail(nullptr, MSPLAT_ERR_INVALID_ARG, "ctx is NULL");
     if (rop != MSPLAT_ROP_NONE && rop != MSPLAT_ROP_RGBA8 && rop != MSPLAT_ROP_RGBA16F)
         return fail(ctx, MSPLAT_ERR_INVALID_ARG, "msplat_set_target_emulation: rop must be MSPLAT_ROP_NONE, _RGBA8 or _RGBA16F (got %d)", rop);
+    if (rop != MSPLAT_ROP_NONE && ctx->cfg.fb_format == MSPLAT_FB_SRGB8_ALPHA8)
+        return fail(ctx, MSPLAT_ERR_UNSUPPORTED, "msplat_set_target_emulation: the emulation rounds LINEAR values after every blend, an "
+                    "MSPLAT_FB_SRGB8_ALPHA8 target holds sRGB-encoded ones: out of scope (use MSPLAT_FB_RGBA8)");
     if (rop != MSPLAT_ROP_NONE && ctx->point_mode)
         return fail(ctx, MSPLAT_ERR_UNSUPPORTED, "msplat_set_target_emulation: the point-cloud sprite compositor has no render-target "
                     "emulation (the context holds a point cloud)");
@@ -1452,7 +1455,8 @@ static int issue_compositor(RenderChain& rc, int occ_pass, int ev_c0, int ev_c1)
     uint32_t* fin = occ_pass ? (uint32_t*)ctx->occ_fin.p : nullptr;
     float4* state = occ_pass ? (float4*)ctx->occ_state.p : nullptr;
     const uint32_t* d_nbins = occ_pass == 2 ? occ + 2 : nullptr;      // second chain of a two-pass frame: the listed unfinished bins
-    const bool f16 = ctx->cfg.fb_format == MSPLAT_FB_RGBA16F;
+    // the target's pixel format (kFb* = MSPLAT_FB_*: msplat_create let nothing else in); only the kernels' load_px / store_px differ
+    auto with_format = [&](auto&& f) { with_int<kFbF16, kFbUnorm8, kFbSrgb8, kFbF32>(ctx->cfg.fb_format, f); };
 
     // persistent compositor: a fixed pool of waves pulls (bin, quadrant) items; never more waves than items
     const int cgrid = std::min(ntiles * 4, ctx->comp_waves);     // work items = (bin, quadrant) (the draw-order compositors)
@@ -1473,8 +1477,8 @@ static int issue_compositor(RenderChain& rc, int occ_pass, int ev_c0, int ev_c1)
     if (ntiles > 0 && ctx->point_mode) {
         // sprites in draw order (optionally against the emulated depth buffer)
         const uint32_t* zqp = ctx->depth_bits ? (const uint32_t*)ctx->zq.p : nullptr;
-        with_flag(f16, [&](auto F16) {
-            hipLaunchKernelGGL(composite_points_kernel<F16.value>, dim3(cgrid), dim3(kCompThreads), 0, s,
+        with_format([&](auto FMT) {
+            hipLaunchKernelGGL(composite_points_kernel<FMT.value>, dim3(cgrid), dim3(kCompThreads), 0, s,
                                (const uint32_t*)ctx->tile_start.p, (const uint32_t*)ctx->pairsB.p,
                                (const float4*)ctx->rec2d.p, zqp, (const float4*)ctx->sprite.p, ctx->sprite_params, d_out,
                                pitch, fp, cap, (const uint32_t*)ctx->tile_order.p, d_queue, (uint32_t)ntiles * 4u);
@@ -1482,9 +1486,9 @@ static int issue_compositor(RenderChain& rc, int occ_pass, int ev_c0, int ev_c1)
         ctx->comp_kernel_timed = false;
     } else if (ntiles > 0 && (ctx->depth_bits != 0 || ctx->rop != 0)) {
         // emulated depth buffer: draw-order walk, no early termination
-        with_flag(f16, [&](auto F16) {
+        with_format([&](auto FMT) {
             with_int<kTargetLoad, kTargetPremultiplied, kTargetClear>(ctx->target_mode, [&](auto TM) {
-                hipLaunchKernelGGL((composite_depth_kernel<F16.value, TM.value>), dim3(cgrid), dim3(kCompThreads), 0, s,
+                hipLaunchKernelGGL((composite_depth_kernel<FMT.value, TM.value>), dim3(cgrid), dim3(kCompThreads), 0, s,
                                    (const uint32_t*)ctx->tile_start.p, (const uint32_t*)ctx->pairsB.p,
                                    (const float4*)ctx->rec2d.p, (const uint32_t*)ctx->zq.p, d_out, pitch, fp, cap,
                                    (const uint32_t*)ctx->tile_order.p, d_queue, (uint32_t)ntiles * 4u);
@@ -1515,8 +1519,8 @@ static int issue_compositor(RenderChain& rc, int occ_pass, int ev_c0, int ev_c1)
         // and the four without the probe once more per non-CLEAR target mode (render_frame refuses the probe with those);
         // a depth frame (one view, no probe: render_impl) has the three passes per target mode
         auto composite = [&](auto OCC, auto TWO, auto PROBE, auto TM, auto DEPTH) {
-            with_flag(f16, [&](auto F16) {
-                hipExtLaunchKernelGGL((composite_kernel<F16.value, OCC.value, TWO.value, PROBE.value, TM.value, DEPTH.value>), dim3(grid),
+            with_format([&](auto FMT) {
+                hipExtLaunchKernelGGL((composite_kernel<FMT.value, OCC.value, TWO.value, PROBE.value, TM.value, DEPTH.value>), dim3(grid),
                                       dim3(kCompThreads), 0, s, e0, e1, 0, ts, pb, r2, d_out, pitch, cp, cap, ord, d_queue, comp_items, prio, ex);
             });
         };
@@ -1670,12 +1674,12 @@ int msplat_render_depth(msplat_ctx* ctx, const float cameraMat[16], const float 
 // rows of the target: 0 = tightly packed (`tight` bytes)
 static int resolve_pitch(msplat_ctx* ctx, const char* who, const FrameParams& fp, uint64_t& pitch_bytes, size_t& tight)
 {
-    const size_t bpp = ctx->cfg.fb_format == MSPLAT_FB_RGBA16F ? 8 : 16;
+    const size_t bpp = MSPLAT_FB_BYTES_PER_PIXEL(ctx->cfg.fb_format);
     tight = (size_t)fp.width * bpp;
     if (pitch_bytes == 0) pitch_bytes = tight;
     if (pitch_bytes < tight || pitch_bytes % bpp != 0)
-        return fail(ctx, MSPLAT_ERR_INVALID_ARG, "%s: pitch %llu too small / misaligned for width %d", who,
-                    (unsigned long long)pitch_bytes, fp.width);
+        return fail(ctx, MSPLAT_ERR_INVALID_ARG, "%s: pitch %llu too small / misaligned for width %d of %zu-byte pixels (at least %zu, a multiple of %zu)",
+                    who, (unsigned long long)pitch_bytes, fp.width, bpp, tight, bpp);
     return MSPLAT_OK;
 }
 

@@ -174,7 +174,7 @@ int post_group(const Rccl& R, const std::vector<Run>& runs, Step&& step)
 // rows of `width` >= 1 pixels of a framebuffer format: bytes per pixel and per tight row, and whether a pitch can hold them
 struct RowGeom {
     size_t bpp, tight;
-    RowGeom(int fb_format, int width) : bpp(fb_format == MSPLAT_FB_RGBA16F ? 8 : 16), tight((size_t)width * bpp) {}
+    RowGeom(int fb_format, int width) : bpp(MSPLAT_FB_BYTES_PER_PIXEL(fb_format)), tight((size_t)width * bpp) {}
     bool fits(size_t pitch) const { return pitch >= tight && pitch % bpp == 0; }
 };
 

@@ -123,7 +123,7 @@ __device__ __forceinline__ float4 sprite_sample(const float4* __restrict__ tex, 
 }
 
 // draw_order_walk over the sprites (optional emulated depth test: zq == nullptr -> colour only)
-template <bool HALF>
+template <int FMT>
 __global__ __launch_bounds__(kCompThreads) void composite_points_kernel(const uint32_t* __restrict__ tile_start,
                                                                         const uint32_t* __restrict__ pairs,
                                                                         const float4* __restrict__ rec,
@@ -165,8 +165,8 @@ __global__ __launch_bounds__(kCompThreads) void composite_points_kernel(const ui
         }
     };
     auto final_alpha = [](const DrawPixels&, int) -> float { return 1.0f; };
-    draw_order_walk<HALF>(tile_start, pairs, rec, zq, zq != nullptr, out, pitch_bytes, fp, cap, order, queue, ntiles, s_rec, s_z,
-                          initial, relevant, shade, final_alpha);
+    draw_order_walk<FMT, false>(tile_start, pairs, rec, zq, zq != nullptr, out, pitch_bytes, fp, cap, order, queue, ntiles, s_rec, s_z,
+                                initial, relevant, shade, final_alpha);
 }
 
 }  // namespace msplat

@@ -63,6 +63,12 @@ def row_runs(rows):
     return runs
 
 
+def _channel_bytes(dtype):
+    """bytes per channel of a framebuffer tensor's dtype: float32 4, float16 2, uint8 (MSPLAT_FB_RGBA8 / _SRGB8_ALPHA8) 1"""
+    d = str(dtype)
+    return 2 if d.endswith("float16") else 1 if d.endswith("uint8") else 4
+
+
 class BandGather:
     """Gathers the owned bin rows of every rank's full-size framebuffer into rank `dst`'s framebuffer.
 
@@ -79,7 +85,7 @@ class BandGather:
                          for t, c in row_runs(owned_rows(layout, tiles_y, world, src, block_rows))]
         else:
             self.plan = [(t, c, dst) for t, c in row_runs(self.rows)]
-        self.bytes_per_frame = sum(c for _, c, _ in self.plan) * tile * width * 4 * (2 if str(dtype).endswith("float16") else 4)
+        self.bytes_per_frame = sum(c for _, c, _ in self.plan) * tile * width * 4 * _channel_bytes(dtype)
 
     def owned(self, fb):
         """this rank's bin rows inside a (tiles_y*tile, W, 4) framebuffer (a copy when they are not evenly strided)"""
@@ -187,8 +193,8 @@ class CAbiBandGather:
         self.r, self.comm, self.rank, self.world, self.dst = renderer, comm, rank, world, dst
         self.kind, self.block_rows = _KIND[layout], int(block_rows)
         self.W, self.H = width, tiles_y * tile
-        self.pitch = width * (8 if str(dtype).endswith("float16") else 16)
-        self.wire_fp16 = bool(wire_fp16) and not str(dtype).endswith("float16")       # fp32 targets: RGBA16F on the wire
+        self.pitch = width * 4 * _channel_bytes(dtype)
+        self.wire_fp16 = bool(wire_fp16) and _channel_bytes(dtype) == 4       # fp32 targets: RGBA16F on the wire
 
     def __call__(self, fb):
         self.r.band_exchange(self.comm.handle, self.rank, self.world, self.dst, self.kind, self.block_rows, fb.data_ptr(),

@@ -3,7 +3,7 @@
 // Sort + Render into an explicit RGBA32F framebuffer, dumped as a binary PPM-like float file.
 //
 //   g++ -std=c++17 -I. splatapult_amd/host/example_render.cpp -Lsplatapult_amd/lib -lmsplat -o example_render
-//   ./example_render scene.ply out.f32 [width height] [--nosh] [--frames-in-flight N] [--devices 0,1,2,...] [--over-gradient] [--depth out_depth.f32]
+//   ./example_render scene.ply out.f32 [width height] [--nosh] [--frames-in-flight N] [--devices 0,1,2,...] [--over-gradient] [--depth out_depth.f32] [--srgb8 out.png]
 // With --frames-in-flight N the same frame is issued N + 1 times round-robin over N contexts that share the cloud
 // (SplatRenderer::SetFramesInFlight); the last one is written.  With --devices the frame's bin rows are dealt to the
 // listed GPUs (SplatRenderer::ConfigureDevices, msplat_group_*): same pixels.  With --over-gradient the target is first filled with
@@ -11,6 +11,8 @@
 // over it (SplatRenderer::SetTargetMode(MSPLAT_TARGET_LOAD)), as the reference's Render does with its bound framebuffer.
 // With --depth the frame also hands out its depth plane (SplatRenderer::RenderWithDepth: W x H float32 window depth over the clear
 // depth 1.0, row 0 = bottom), written to the named file; one device only.
+// With --srgb8 the target is an MSPLAT_FB_SRGB8_ALPHA8 one -- the reference's sRGB window: 4 bytes per pixel, encoded by the compositor's
+// final store -- and the PNG is written from those bytes (WritePNG), with no float frame in between; out.f32 is then not written.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -19,6 +21,7 @@
 #include <vector>
 
 #include "msplat_host.hpp"
+#include "scene_config.hpp"
 
 int main(int argc, char** argv)
 {
@@ -31,12 +34,14 @@ int main(int argc, char** argv)
     if (argc >= 5 && argv[3][0] != '-') { W = std::atoi(argv[3]); H = std::atoi(argv[4]); }
     int inFlight = 1;
     const char* depthPath = nullptr;
+    const char* srgb8Path = nullptr;
     std::vector<int> devices;
     for (int i = 3; i < argc; ++i) {
         nosh = nosh || !std::strcmp(argv[i], "--nosh");
         overGradient = overGradient || !std::strcmp(argv[i], "--over-gradient");
         if (!std::strcmp(argv[i], "--frames-in-flight") && i + 1 < argc) inFlight = std::atoi(argv[i + 1]);
         if (!std::strcmp(argv[i], "--depth") && i + 1 < argc) depthPath = argv[i + 1];
+        if (!std::strcmp(argv[i], "--srgb8") && i + 1 < argc) srgb8Path = argv[i + 1];
         if (!std::strcmp(argv[i], "--devices") && i + 1 < argc)
             for (const char* p = argv[i + 1]; *p;) {
                 devices.push_back(std::atoi(p));
@@ -50,6 +55,7 @@ int main(int argc, char** argv)
 
     SplatRenderer renderer;
     renderer.SetFramesInFlight(inFlight);
+    if (srgb8Path) renderer.Configure(/*device*/0, MSPLAT_FB_SRGB8_ALPHA8);
     if (devices.size() > 1) renderer.ConfigureDevices(devices, MSPLAT_BANDS_BLOCK_INTERLEAVED, 2);
     if (!renderer.Init(cloud, /*isFramebufferSRGBEnabled=*/false, /*useRgcSortOverride=*/false)) return 1;
 
@@ -64,6 +70,18 @@ int main(int argc, char** argv)
 
     std::vector<float> fb((size_t)W * H * 4);
     std::vector<float> depth(depthPath ? (size_t)W * H : 0);
+    if (srgb8Path) {
+        // the window's own format: bytes R G B A, row 0 = GL's bottom row; the PNG wants the top row first
+        std::vector<uint8_t> fb8((size_t)W * H * 4), png((size_t)W * H * 4);
+        renderer.SetRenderTarget(fb8.data(), 0, /*isDevicePointer=*/false);
+        renderer.Sort(cameraMat, projMat, viewport, nearFar);
+        renderer.Render(cameraMat, projMat, viewport, nearFar);
+        renderer.Synchronize();
+        for (int y = 0; y < H; ++y) std::memcpy(&png[(size_t)y * W * 4], &fb8[(size_t)(H - 1 - y) * W * 4], (size_t)W * 4);
+        if (!WritePNG(srgb8Path, png.data(), W, H)) return 1;
+        std::printf("%zu splats -> %dx%d SRGB8_ALPHA8 written to %s\n", cloud->GetNumGaussians(), W, H, srgb8Path);
+        return 0;
+    }
     renderer.SetRenderTarget(fb.data(), 0, /*isDevicePointer=*/false);
     if (overGradient && !renderer.SetTargetMode(MSPLAT_TARGET_LOAD)) return 1;
     for (int k = 0; k < (inFlight > 1 ? inFlight + 1 : 1); ++k) {

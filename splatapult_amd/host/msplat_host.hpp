@@ -11,7 +11,7 @@
 // (app.cpp:603-607, :1067-1068) compile as they are.
 //
 // The reference draws into "whatever GL framebuffer is bound"; here the target is explicit:
-// SetRenderTarget(ptr, pitch, isDevice) once (or per frame), then Render writes RGBA32F/16F rows,
+// SetRenderTarget(ptr, pitch, isDevice) once (or per frame), then Render writes RGBA32F / 16F / 8-bit rows,
 // row 0 = GL bottom row, alpha = 1.
 #pragma once
 
@@ -39,7 +39,8 @@ public:
     SplatRenderer(const SplatRenderer&) = delete;
     SplatRenderer& operator=(const SplatRenderer&) = delete;
 
-    // optional, before Init: device ordinal, framebuffer format (MSPLAT_FB_*), stream (hipStream_t)
+    // optional, before Init: device ordinal, framebuffer format (MSPLAT_FB_*: RGBA32F, RGBA16F, or the 4-byte RGBA8 / SRGB8_ALPHA8 --
+    // INTEGRATION.md 15; the render target then holds bytes R G B A), stream (hipStream_t)
     void Configure(int device, int fbFormat, void* stream = nullptr, float tEpsilon = -1.0f)
     {
         cfg.device = device;
@@ -91,7 +92,7 @@ public:
     bool ExchangeBands(void* comm, int root, int width, int height, int flags = 0)        // flags: MSPLAT_EXCHANGE_WIRE_FP16
     {
         if (!ctx || !targetIsDevice || !target) return false;
-        const uint64_t pitch = targetPitch ? targetPitch : (uint64_t)width * (cfg.fb_format == MSPLAT_FB_RGBA16F ? 8u : 16u);
+        const uint64_t pitch = targetPitch ? targetPitch : (uint64_t)width * MSPLAT_FB_BYTES_PER_PIXEL(cfg.fb_format);
         const int rc = msplat_band_exchange(ctx, comm, bandRank, bandWorld, root, bandKindSet, bandBlockRows, target, pitch, width, height, flags);
         if (rc != MSPLAT_OK) std::fprintf(stderr, "[msplat][E] ExchangeBands: %s\n", msplat_group_last_error(nullptr));
         return rc == MSPLAT_OK;

@@ -68,12 +68,15 @@ def _host_frame(fb_format, vp, out=None, load=False):
     """the (H, W, 4) host array a Render into host memory fills: `out` checked, or a new one (load: the array's content is the
     destination the frame is blended over, so there has to be one)"""
     W, H = int(vp[2]), int(vp[3])
-    dt = np.float16 if fb_format == _capi.FB_RGBA16F else np.float32
+    dt = _capi.FB_DTYPES[fb_format]      # float32, float16, or uint8 for the two 8-bit targets (bytes R G B A)
     if out is None and load:
         raise ValueError('target mode "load" blends over the target\'s contents: pass out= (or out_ptr=)')
     if out is None:
         out = np.zeros((H, W, 4), dt)
-    assert out.dtype == dt and out.shape == (H, W, 4) and out.flags["C_CONTIGUOUS"]
+    if not isinstance(out, np.ndarray) or out.dtype != dt or out.shape != (H, W, 4) or not out.flags["C_CONTIGUOUS"]:
+        raise ValueError("a %s target of %d x %d takes a C-contiguous %s array of shape (%d, %d, 4), not %s %s" % (
+            _capi.FB_NAMES[fb_format], W, H, np.dtype(dt).name, H, W, getattr(out, "dtype", type(out).__name__),
+            getattr(out, "shape", "")))
     return out
 
 
@@ -97,7 +100,7 @@ class SplatRenderer:
         self._depth = max(1, int(frames_in_flight))
         self._args = _FrameArgs()
         self._device = device
-        self._fb_format = {"fp32": _capi.FB_RGBA32F, "fp16": _capi.FB_RGBA16F}[fb_format]
+        self._fb_format = _capi.fb_format(fb_format)
         self._t_eps = t_epsilon
         self._pair_cap = pair_capacity
         self._stream = stream
@@ -237,7 +240,7 @@ class SplatRenderer:
     def Render(self, cameraMat, projMat, viewport, nearFar, out=None, out_ptr=None, pitch_bytes=0, depth=None, depth_ptr=None,
                depth_pitch_bytes=0):
         """splatrenderer.cpp:315-343 + the GL pipeline behind it.
-        out=None      -> returns a new (H, W, 4) numpy array (float32 or float16), row 0 = GL bottom row
+        out=None      -> returns a new (H, W, 4) numpy array (float32, float16 or -- the 8-bit targets -- uint8), row 0 = GL bottom row
         out=ndarray   -> filled in place
         out_ptr=int   -> device pointer (e.g. torch tensor .data_ptr()); asynchronous on the stream
         The depth plane (msplat_render_depth: the splats' expected window depth over the clear depth 1.0, float32 on every
@@ -530,7 +533,7 @@ class SplatRendererGroup:
         self._g = None
         self._args = _FrameArgs()
         self._devices = [int(d) for d in devices]
-        self._fb_format = {"fp32": _capi.FB_RGBA32F, "fp16": _capi.FB_RGBA16F}[fb_format]
+        self._fb_format = _capi.fb_format(fb_format)
         self._t_eps = t_epsilon
         self._layout, self._block_rows, self._band_cull = layout, int(block_rows), bool(band_cull)
         self._timing = enable_timing
