@@ -5,7 +5,7 @@ LIB = splatapult_amd/lib/libmsplat.so
 SRC = splatapult_amd/csrc/msplat_device.hip splatapult_amd/csrc/msplat_group.hip splatapult_amd/host/gaussian_scene.cpp splatapult_amd/host/scene_config.cpp \
       splatapult_amd/host/point_scene.cpp
 HDR = $(wildcard splatapult_amd/csrc/*.hip.h) $(wildcard splatapult_amd/csrc/*.hip.inc) splatapult_amd/host/gaussian_scene.hpp splatapult_amd/host/scene_config.hpp \
-      splatapult_amd/host/point_scene.hpp include/msplat.h include/msplat_debug.h
+      splatapult_amd/host/point_scene.hpp splatapult_amd/host/two_pass_controller.hpp include/msplat.h include/msplat_debug.h
 
 all: $(LIB) examples
 
@@ -22,11 +22,12 @@ build/example_%: splatapult_amd/host/example_%.cpp $(LIB) splatapult_amd/host/ms
 oracle:
 	$(MAKE) -C oracle
 
-# ASan + UBSan over the host half of the library (PLY / JSON / PNG parsers behind the C ABI): no GPU, no hipcc.
-# tests/sanitize/host_sanitize_driver.cpp stubs the device entry points and replays the golden files + hostile inputs.
+# ASan + UBSan over the host half of the library (PLY / JSON / PNG parsers behind the C ABI, the two-pass controller): no GPU, no hipcc.
+# tests/sanitize/host_sanitize_driver.cpp stubs the device entry points and replays the golden files + hostile inputs, then the
+# controller's probe, strike, pause and timeout paths.
 SAN = build/host_sanitize
 HOSTSRC = splatapult_amd/host/gaussian_scene.cpp splatapult_amd/host/scene_config.cpp splatapult_amd/host/point_scene.cpp
-sanitize: $(HOSTSRC) tests/sanitize/host_sanitize_driver.cpp include/msplat.h include/msplat_debug.h
+sanitize: $(HOSTSRC) tests/sanitize/host_sanitize_driver.cpp splatapult_amd/host/two_pass_controller.hpp include/msplat.h include/msplat_debug.h
 	mkdir -p build build/sanitize_scratch
 	$(CXX) -std=c++17 -O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined -I. \
 	    $(HOSTSRC) tests/sanitize/host_sanitize_driver.cpp -o $(SAN)

@@ -128,16 +128,16 @@ __global__ __launch_bounds__(kThreads, (ATOMIC_RANK && BIN_CHUNK == kBinChunk) ?
     MSPLAT_CHAIN_ENTER();
     MSPLAT_STAMP(KID_BIN1_DOWN);
     // d_first: see bin1_upsweep
-    // host_D2 (host-mapped): second binning chain of a two-pass frame -- its pair count, for the host's choice of the next share
+    // host_D2 (the host-mapped word kHostPass2Pairs): second binning chain of a two-pass frame -- its pair count and, kHostD2SeqOffset
+    // words on, the frame's number, for the host's choice of the next share
     // d_V_report: the Sort's own V for the host-mapped hint (with two views in one chain d_V counts the ranks of both)
     // The first nhelp workgroups are helpers for the heavy chunks (bin1_upsweep; first, so that they start with the launch):
     // helper h takes column block 1 + h % (kHeavyParts - 1) of chunk heavy[1 + h / (kHeavyParts - 1)] and exits at once when
     // there is no such chunk; the other nmain workgroups walk the chunks (grid-stride), a heavy chunk's main workgroup keeps
     // block 0.  A part sees every rectangle of the chunk clipped to its columns.
     // gsum != nullptr: scan-free path (hist = raw per-chunk column counts, see radix_upsweep); workgroup 0 then also
-    // publishes the column totals in totals_out for the row pass.  host_words (host-mapped): [0] pairs needed by an
-    // overflowed device-output frame, [1] V and [2] D of the latest frame (read by the host without synchronising,
-    // only to choose between the scan-free and the 3-kernel path for the NEXT frame's row pass)
+    // publishes the column totals in totals_out for the row pass.  host_words (host-mapped, HostWord in msplat_common.hip.h): read by the host
+    // without synchronising -- V and D only to choose between the scan-free and the 3-kernel path for the NEXT frame's row pass
     constexpr int PER = BIN_CHUNK / kThreads;          // rectangles per thread (blocked)
     __shared__ uint32_t s_off[BIN_CHUNK + 1];          // exclusive scan of the rectangle widths
     __shared__ uint32_t s_rect[BIN_CHUNK];
@@ -167,20 +167,20 @@ __global__ __launch_bounds__(kThreads, (ATOMIC_RANK && BIN_CHUNK == kBinChunk) ?
         if (!helper && mb == 0u && threadIdx.x == 255) {
             *d_D = incl;
             if (host_words != nullptr) {
-                __hip_atomic_store(host_words + 1, d_V_report ? *d_V_report : V, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                __hip_atomic_store(host_words + 2, incl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                __hip_atomic_store(host_words + 3, heavy[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);   // heavy chunks wanted
+                __hip_atomic_store(host_words + kHostV, d_V_report ? *d_V_report : V, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                __hip_atomic_store(host_words + kHostD, incl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                __hip_atomic_store(host_words + kHostHeavyChunks, heavy[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);   // heavy chunks wanted
             }
             if (host_D2 != nullptr) {
                 __hip_atomic_store(host_D2, incl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                __hip_atomic_store(host_D2 + 2, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);      // ... of which frame
+                __hip_atomic_store(host_D2 + kHostD2SeqOffset, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);      // ... of which frame
             }
             if (incl > cap) {
                 *d_overflow = incl;
                 // device-output renders never synchronise: leave the pair count this frame needed in host-mapped
                 // memory, where the next msplat_sort / msplat_render / msplat_synchronize on the context finds it
                 if (host_words != nullptr && report_overflow)
-                    __hip_atomic_store(host_words, incl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                    __hip_atomic_store(host_words + kHostOverflowPairs, incl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
             }
         }
     }

@@ -47,6 +47,53 @@ constexpr uint32_t kRankMask = 0x00FFFFFFu;
 
 enum { MODE_KEYS = 0, MODE_CULL = 1, MODE_PAIR = 2 };
 
+// ------------------------------------------------------------------------------------------
+// The three word tables kernels and host share.  These are the ONLY definitions of their layouts: no literal indexes them.
+// ------------------------------------------------------------------------------------------
+// Host-mapped status words (msplat_ctx::h_flags = the host's view, d_flags = the device's).  Kernels leave them with relaxed
+// system-scope stores; the host reads them without ever waiting for the GPU (host_word, msplat_device.hip), so every one describes
+// some EARLIER frame.  V, D and the heavy chunks only steer launch choices (any value gives the same pixels); the two-pass words
+// are the controller's feedback (host/two_pass_controller.hpp) and what msplat_get_two_pass_info reports.
+enum HostWord : int {
+    kHostOverflowPairs = 0,    // pairs needed by an overflowed device-output render (poll_async_overflow)        bin1_downsweep
+    kHostV = 1,                // ranks binned by the latest frame: the Sort's own V                               bin1_downsweep
+    kHostD = 2,                // ... and its pairs                                                               bin1_downsweep
+    kHostHeavyChunks = 3,      // heavy chunks its column pass wanted                                             bin1_downsweep
+    kHostPass1Pairs = 4,       // two-pass frame: pairs of pass 1                                                 occ_gate_kernel
+    kHostUnfinishedBins = 5,   // ... bins pass 1 left unfinished                                                 occ_gate_kernel
+    kHostPass1Splats = 6,      // ... splats in pass 1                                                            occ_gate_kernel
+    kHostListedRanks = 7,      // ... listed ranks of pass 2                                                      project_kernel<PROJ_LISTED>
+    kHostPass2Pairs = 8,       // ... pairs of pass 2                                         bin1_downsweep through host_D2
+    kHostPass1Seq = 9,         // number of the frame words 4 to 6 describe                                       occ_gate_kernel
+    kHostPass2Seq = 10,        // number of the frame word 8 describes                        bin1_downsweep through host_D2
+    kHostWordCount = 16
+};
+// bin1_downsweep gets the pass-2 words through one pointer, host_D2 = d_flags + kHostPass2Pairs: the frame number lies this far behind
+constexpr int kHostD2SeqOffset = kHostPass2Seq - kHostPass2Pairs;
+
+// Device counters (msplat_ctx::counters)
+enum Counter : int {
+    kCntV = 0,                 // visible splats of the latest Sort
+    kCntD = 1,                 // pairs of the latest binning chain
+    kCntOverflow = 2,          // pairs a frame needed beyond the capacity (0: none)
+    kCntDrawn = 4,             // msplat_get_stats: splats drawn (count_drawn_kernel) ...
+    kCntPairs16 = 6,           // ... and its 64-bit count of (splat, 16 x 16 tile) pairs: words 6..7, 8-byte aligned
+    kCntLdsProbe = 8,          // msplat_create: violations seen by lds_atomic_order_probe
+    kCntVframe2 = 9,           // two views in one chain: ranks the binning walks
+    kCntMinKey = 10,           // minimum key of the visible set, one word per sort parity: words 10..11
+    kCntOrderBad = 12,         // msplat_debug_verify_order: key / list violations, words 12..13
+    kCounterCount = 16
+};
+
+// Words of a two-pass frame (msplat_ctx::occ; msplat_occlusion.hip.h).  The cut is a multiple of 1024 = kBinChunk.
+enum OccWord : int {
+    kOccCut = 0,               // first rank of pass 1                                                            project_kernel<PROJ_PASS1>
+    kOccListed = 1,            // ranks behind the cut that pass the gate                                         occ_gate_kernel
+    kOccUnfinished = 2,        // bins pass 1 left unfinished                                                     occ_mask_kernel
+    kOccRanks2 = 4,            // ranks the second binning chain walks: V, or 0 when no bin is left               occ_mask_kernel
+    kOccWordCount = 16
+};
+
 // Workgroup residency stamps (r6; DIAGNOSTIC builds only: -DMSPLAT_STAMPS, tools/stamp_timeline.py).  rocprofv3 serialises dispatches
 // while it collects counters and this box has no PC sampling, so what frames IN FLIGHT do to each other was unknown.  With stamps
 // every workgroup of the frame's kernels leaves {kernel id, block, HW_ID, XCC_ID, start, end} (s_memrealtime: 100 MHz) in a hashed

@@ -27,6 +27,7 @@
 
 #include "../../include/msplat.h"
 #include "../../include/msplat_debug.h"
+#include "../host/two_pass_controller.hpp"
 
 using namespace msplat;
 
@@ -120,6 +121,13 @@ constexpr uint32_t kFusedMaxChunks = 1u << 20;     // scan-free passes up to thi
                                                // prefix is <= nchunks / 128 + 34 rows, so every table qualifies (r2, one level: 8192 rows,
                                                // beyond that the radix_scan kernels)
 
+// Slots of a timing-event set (msplat_ctx::ev).  The compositor's pair is the exact dispatch begin / end of the kernel
+// (hipExtLaunchKernelGGL); kEvPass2*: the second pass of a two-pass frame -- after the first compositor, after gate and projection,
+// after binning -- and kEvComp2* its compositor's pair
+enum EvSlot : int { kEvSortBegin = 0, kEvSortEnd = 1, kEvRenderBegin = 2, kEvProjected = 3, kEvBinned = 4, kEvRenderEnd = 5, kEvCompBegin = 6,
+                    kEvCompEnd = 7, kEvPass2Begin = 8, kEvPass2Projected = 9, kEvPass2Binned = 10, kEvComp2Begin = 11, kEvComp2End = 12,
+                    kEvSlots = 13 };
+
 struct msplat_ctx {
     msplat_config cfg{};
     int device = 0;
@@ -149,7 +157,7 @@ struct msplat_ctx {
     uint32_t gsumS_rows = 0, gsumB1_rows = 0, gsumB2_rows = 0;
     uint32_t gsupS = 0, gsupB1 = 0, gsupB2 = 0;     // supergroup rows at the head of each table (the group rows follow)
     // wide-digit 3-pass sort (r3, msplat_sort.hip.h ws_*): histogram rows of up to 2048 digits per chunk, one group
-    // table per pass, one visibility bit per splat, the visible set's minimum key per frame parity (counters[10..11])
+    // table per pass, one visibility bit per splat, the visible set's minimum key per frame parity (counters, kCntMinKey)
     Buf wsHist, wsGsum[3], vmask;
     Buf live_list, live_cnt;    // live bounding boxes of the latest Sort that ran box_cull_kernel (spatially ordered clouds)
     int spatial_mode = 0;       // msplat_config.spatial_order: 0 auto, 1 always, 2 never
@@ -171,7 +179,7 @@ struct msplat_ctx {
     bool scan_free = true;  // MSPLAT_SCAN_KERNELS=1 forces the 3-kernel (upsweep, scan, downsweep) passes
     Buf totals;     // uint32[256]  digit totals of the current radix pass (rows in binning pass 2)
     Buf totals1;    // uint32[256]  column totals of binning pass 1
-    Buf counters;   // uint32[16]: 0=V, 1=D, 2=overflow, 4=drawn, 6..7=pairs16 (u64), 8=probe
+    Buf counters;   // uint32[kCounterCount]: Counter, msplat_common.hip.h
     Buf queue;      // uint32[kQueueShards * kQueueStride]: the compositors' sharded work queue heads
     // render state
     uint64_t rank_cap = 0;      // draw-order ranks rec2d / rect / hist1 ... are sized for: N, or 2 N + 64 once msplat_render_stereo ran
@@ -200,7 +208,7 @@ struct msplat_ctx {
     bool probe_on = false;
     // device-output renders never synchronise: a pair-buffer overflow is left in host-mapped memory by the
     // binning kernel and picked up by the next call on the context (poll_async_overflow)
-    uint32_t* h_flags = nullptr;   // host view   [0] = pairs needed by an overflowed device-output render
+    uint32_t* h_flags = nullptr;   // host view of the kHostWordCount status words (HostWord, msplat_common.hip.h; host_word reads one)
     uint32_t* d_flags = nullptr;   // device view of the same words
     // band
     // owned bin rows: blocks of band_block rows starting at band_first, band_first + band_stride, ..., at most band_count
@@ -215,7 +223,7 @@ struct msplat_ctx {
     // per-stage hipEvent sets, recorded on every `timing_stride`-th call so that the event markers
     // (a few us of pipeline bubble each) do not perturb a throughput run; averaged by msplat_get_timings
     static constexpr int kEvSets = 32;
-    hipEvent_t ev[kEvSets][13]{};  // [6],[7] = exact dispatch start/stop of the compositor (hipExtLaunchKernelGGL); [8..12]: second pass of a two-pass frame
+    hipEvent_t ev[kEvSets][kEvSlots]{};      // slots: EvSlot, above
     bool ev_ok = false;
     int timing_stride = 1;
     uint64_t sort_calls = 0, render_calls = 0;
@@ -228,17 +236,10 @@ struct msplat_ctx {
     Buf occ, occ_mask, occ_fin, occ_state, occ_live, occ_boxdead, occ_unf;
     Buf occ_zstate;                          // float[W * H]: the depth accumulator beside occ_state (allocated by the first two-pass depth frame)
     int two_pass_mode = MSPLAT_TWO_PASS_AUTO;
-    float occ_frac = 0.15f;                  // share of the visible splats that goes into pass 1 (0.15-0.3 is the optimum of the blobs, 0.02 of a camera inside a scene)
-    uint32_t occ_streak = 0;                 // consecutive two-pass frames submitted (their feedback describes two-pass frames)
-    uint32_t occ_seq = 0, occ_change_seq = 0;   // number of the latest two-pass frame; first frame that ran with the current share
-    uint32_t occ_off = 0;                    // AUTO: frames left of a single-pass period after two passes did not pay
-    uint32_t occ_strikes = 0, occ_backoff = 1024; // ... decided after three looks; the pause doubles every time
-    int occ_state_auto = 0;                  // AUTO: 0 one pass, 1 probing (occ_probe_left frames), 2 waiting for the probe's feedback, 3 two passes
-    uint32_t occ_probe_left = 0, occ_no_shrink = 0, occ_wait_frames = 0;
-    bool occ_pinned = false;                 // msplat_debug_two_pass: the share is fixed
+    TwoPassController two_pass;              // ... when to run one, and with what share in pass 1 (host/two_pass_controller.hpp)
     bool last_render_two_pass = false;
     uint32_t comp_launch[4] = {0, 0, 0, 0};  // msplat_debug_get_compositor_launch: items, grid, ordered, kernel kind of the latest compositor launch
-    uint64_t frames_rendered = 0, frames_two_pass = 0;
+    uint64_t frames_two_pass = 0;
 
     std::unique_ptr<AsyncWorker> worker;     // msplat_config.async_submit
     bool atomic_rank = true;    // LDS atomics hand out ranks in lane order (probed at create)
@@ -262,6 +263,9 @@ int fail(msplat_ctx* c, int code, const char* fmt, ...)
     if (c) c->err = buf;
     return code;
 }
+
+// one host-mapped status word (HostWord, msplat_common.hip.h) as some earlier frame left it: a relaxed load, never a wait
+inline uint32_t host_word(const msplat_ctx* c, HostWord w) { return __atomic_load_n(c->h_flags + w, __ATOMIC_RELAXED); }
 
 // waits until the context's worker thread (if any) has issued everything queued; no-op on the worker itself
 thread_local const msplat_ctx* g_on_worker_of = nullptr;
@@ -454,7 +458,7 @@ int msplat_create(msplat_ctx** out, const msplat_config* cfg)
         ctx->timing_stride = c.enable_timing;
     }
     int rc = buf_alloc(ctx, ctx->totals, 256 * sizeof(uint32_t));
-    if (rc == MSPLAT_OK) rc = buf_alloc(ctx, ctx->counters, 16 * sizeof(uint32_t));
+    if (rc == MSPLAT_OK) rc = buf_alloc(ctx, ctx->counters, kCounterCount * sizeof(uint32_t));
     if (rc == MSPLAT_OK) rc = buf_alloc(ctx, ctx->totals1, 256 * sizeof(uint32_t));
     if (rc == MSPLAT_OK) rc = buf_alloc(ctx, ctx->queue, kQueueShards * kQueueStride * sizeof(uint32_t));
     ctx->queue.frame_table = ctx->bincnt.frame_table = true;
@@ -465,19 +469,19 @@ int msplat_create(msplat_ctx** out, const msplat_config* cfg)
 
     if (c.compositor_waves > 0) { ctx->comp_waves = std::max(64, (int)c.compositor_waves); ctx->comp_waves_auto = false; }
     if (rc == MSPLAT_OK) {
-        if (hipHostMalloc((void**)&ctx->h_flags, 64, hipHostMallocMapped) != hipSuccess ||
+        if (hipHostMalloc((void**)&ctx->h_flags, kHostWordCount * sizeof(uint32_t), hipHostMallocMapped) != hipSuccess ||
             hipHostGetDevicePointer((void**)&ctx->d_flags, ctx->h_flags, 0) != hipSuccess)
             rc = fail(ctx, MSPLAT_ERR_HIP, "msplat_create: cannot allocate the host-mapped status words");
         else
-            std::memset(ctx->h_flags, 0, 64);
+            std::memset(ctx->h_flags, 0, kHostWordCount * sizeof(uint32_t));
     }
-    if (rc == MSPLAT_OK && hipMemsetAsync(ctx->counters.p, 0, 16 * sizeof(uint32_t), ctx->stream) != hipSuccess)
+    if (rc == MSPLAT_OK && hipMemsetAsync(ctx->counters.p, 0, kCounterCount * sizeof(uint32_t), ctx->stream) != hipSuccess)
         rc = MSPLAT_ERR_HIP;
-    if (rc == MSPLAT_OK && hipMemsetAsync((uint32_t*)ctx->counters.p + 10, 0xFF, 2 * sizeof(uint32_t), ctx->stream) != hipSuccess)
+    if (rc == MSPLAT_OK && hipMemsetAsync((uint32_t*)ctx->counters.p + kCntMinKey, 0xFF, 2 * sizeof(uint32_t), ctx->stream) != hipSuccess)
         rc = MSPLAT_ERR_HIP;      // minimum key of the visible set, one word per frame parity
     if (rc == MSPLAT_OK) {
         // feature probe: stable ranks straight from LDS atomics need lane-ordered ds_add_rtn
-        uint32_t* bad = (uint32_t*)ctx->counters.p + 8;
+        uint32_t* bad = (uint32_t*)ctx->counters.p + kCntLdsProbe;
         hipLaunchKernelGGL(iota_kernel, dim3(65536 / kThreads), dim3(kThreads), 0, ctx->stream, (uint32_t*)ctx->tile_order.p + 65536);
         hipLaunchKernelGGL(lds_atomic_order_probe, dim3(64), dim3(kThreads), 0, ctx->stream, bad);
         uint32_t hbad = 1;
@@ -573,13 +577,12 @@ static int ensure_pair_capacity(msplat_ctx* ctx, uint64_t cap);
 // Returns MSPLAT_OK when nothing is pending; `msg` receives the text the caller reports after doing its own work.
 static int poll_async_overflow(msplat_ctx* ctx, std::string& msg)
 {
-    if (!ctx->h_flags) return MSPLAT_OK;
-    uint32_t need = __atomic_load_n(ctx->h_flags, __ATOMIC_RELAXED);
+    uint32_t need = host_word(ctx, kHostOverflowPairs);
     if (need == 0) return MSPLAT_OK;
     if (hipSetDevice(ctx->device) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess)
         return fail(ctx, MSPLAT_ERR_HIP, "hipStreamSynchronize failed while handling a pair-buffer overflow");
-    need = std::max(need, __atomic_load_n(ctx->h_flags, __ATOMIC_RELAXED));     // a later frame may have needed more
-    __atomic_store_n(ctx->h_flags, 0u, __ATOMIC_RELAXED);
+    need = std::max(need, host_word(ctx, kHostOverflowPairs));     // a later frame may have needed more
+    __atomic_store_n(ctx->h_flags + kHostOverflowPairs, 0u, __ATOMIC_RELAXED);
     const uint64_t old_cap = ctx->pair_cap;
     char buf[384];
     if (ctx->cfg.pair_capacity == 0 && (uint64_t)need + (need >> 2) + 1024 <= 0x7FFFFFFFull &&
@@ -845,7 +848,7 @@ static int clear_frame_tables(msplat_ctx* ctx)
     hipStream_t s = ctx->stream;
     for (Buf* b : ctx->bufs)        // (the group tables, the bin counts, the queue heads, the heavy-chunk lists)
         if (b->frame_table && b->p) HIP_TRY(ctx, hipMemsetAsync(b->p, 0, b->bytes, s));
-    HIP_TRY(ctx, hipMemsetAsync((uint32_t*)ctx->counters.p + 10, 0xFF, 2 * sizeof(uint32_t), s));
+    HIP_TRY(ctx, hipMemsetAsync((uint32_t*)ctx->counters.p + kCntMinKey, 0xFF, 2 * sizeof(uint32_t), s));
     ctx->tables_dirty = false;
     return MSPLAT_OK;
 }
@@ -985,7 +988,7 @@ static int issue_sort(msplat_ctx* ctx, const FrameParams& fp)
     hipStream_t s = ctx->stream;
     const uint32_t N = (uint32_t)ctx->N;
     uint32_t* counters = (uint32_t*)ctx->counters.p;
-    uint32_t* d_V = counters + 0;
+    uint32_t* d_V = counters + kCntV;
     uint32_t* hist = (uint32_t*)ctx->hist.p;
     uint32_t* totals = (uint32_t*)ctx->totals.p;
     const float4* pos = (const float4*)ctx->pos4.p;
@@ -1002,13 +1005,13 @@ static int issue_sort(msplat_ctx* ctx, const FrameParams& fp)
     }
     const bool timed = ctx->ev_ok && (ctx->sort_calls++ % ctx->timing_stride) == 0;
     const int tset = (int)(ctx->sort_sets % msplat_ctx::kEvSets);
-    if (timed) HIP_TRY(ctx, hipEventRecord(ctx->ev[tset][0], s));
+    if (timed) HIP_TRY(ctx, hipEventRecord(ctx->ev[tset][kEvSortBegin], s));
     const bool wide = ctx->wide_sort;
     if (wide) {
         // three passes of 10 + (8..11) + (8..11) key bits (msplat_sort.hip.h, ws_*): 6 launches.
         // pass 0: positions -> raw keys + visibility bits in keyB / vmask -> (keyA, valA); pass 1: A -> B; pass 2: B -> A
-        uint32_t* mk_cur = counters + 10 + (ctx->sort_parity & 1u);
-        uint32_t* mk_next = counters + 10 + ((ctx->sort_parity ^ 1u) & 1u);
+        uint32_t* mk_cur = counters + kCntMinKey + (ctx->sort_parity & 1u);
+        uint32_t* mk_next = counters + kCntMinKey + ((ctx->sort_parity ^ 1u) & 1u);
         ctx->sort_parity ^= 1u;
         uint32_t* whist = (uint32_t*)ctx->wsHist.p;
         unsigned long long* vm = (unsigned long long*)ctx->vmask.p;
@@ -1018,7 +1021,7 @@ static int issue_sort(msplat_ctx* ctx, const FrameParams& fp)
         // Passes 1 and 2 see only the V splats that survived the cull.  With 8192-key chunks and V << N (a band-culled rank of a
         // multi-GPU frame keeps 17 %, a camera inside a scene 40 %) they would run on ~100 workgroups: they take 4096-key chunks
         // when an EARLIER frame's V (host-mapped word, read without synchronising) was below 2 M.  Any choice is correct at any V.
-        const uint32_t last_V = ctx->h_flags ? __atomic_load_n(ctx->h_flags + 1, __ATOMIC_RELAXED) : 0u;
+        const uint32_t last_V = host_word(ctx, kHostV);
         const uint32_t items0 = ctx->ws_items;
         const uint32_t items12 = (items0 == 16u && last_V != 0u && (uint64_t)last_V + (last_V >> 2) <= (2u << 20)) ? 8u : items0;
         const LiveBoxes lb = list_live_boxes(ctx, fp, last_V);       // (launches box_cull_kernel when the view is a partial one)
@@ -1078,7 +1081,7 @@ static int issue_sort(msplat_ctx* ctx, const FrameParams& fp)
             });
         };
         // pass 0: cull + key fused into the first radix pass (presort_compute.glsl + byte 0 of the sort)
-        const LiveBoxes lb = list_live_boxes(ctx, fp, ctx->h_flags ? __atomic_load_n(ctx->h_flags + 1, __ATOMIC_RELAXED) : 0u);
+        const LiveBoxes lb = list_live_boxes(ctx, fp, host_word(ctx, kHostV));
         // (r6: frames without the band-restricted cull -- every single-GPU frame -- run instantiations that leave its code out)
         with_flag(fp.band_cull != 0, [&](auto BAND) {
             upsweep(int_t<MODE_CULL>{}, BAND, (const uint32_t*)nullptr, pos, (const uint32_t*)nullptr, N, N, 0, hist, ctx->hist_stride, gacc(0),
@@ -1106,7 +1109,7 @@ static int issue_sort(msplat_ctx* ctx, const FrameParams& fp)
         }
     }
     if (timed) {
-        HIP_TRY(ctx, hipEventRecord(ctx->ev[tset][1], s));
+        HIP_TRY(ctx, hipEventRecord(ctx->ev[tset][kEvSortEnd], s));
         ctx->sort_sets++;
     }
     const hipError_t le = hipGetLastError();
@@ -1123,142 +1126,28 @@ static int issue_sort(msplat_ctx* ctx, const FrameParams& fp)
     return MSPLAT_OK;
 }
 
-// Should this Render run as two passes (msplat_occlusion.hip.h), and with what share of the visible splats in pass 1?  Host
-// side only: reads what EARLIER frames of this context left in host-mapped memory (never waits); any answer gives the same
-// pixels.  Feedback of a two-pass frame: [4] pairs of pass 1, [8] pairs of pass 2, [5] unfinished bins.
-constexpr uint64_t kTwoPassMinSplats = 1u << 18;
-constexpr uint32_t kTwoPassMinVisibleSerial = 1500000u;
+// Should this Render run as two passes (msplat_occlusion.hip.h), and with what share of the visible splats in pass 1?  The policy
+// is host/two_pass_controller.hpp; here: what the context allows, the snapshot of the feedback words, the passes' buffers.
 constexpr int kProjGridTwoPass = 4096;       // one-wave workgroups of the grid-stride forms of project_kernel (9 fit a CU)
-constexpr float kOccFracMin = 1.0f / 256.0f, kOccFracMax = 0.75f;
 static bool occlusion_plan(msplat_ctx* ctx, const FrameParams& fp, bool stereo, float& frac)
 {
-    ctx->frames_rendered++;
-    auto no = [&]() { ctx->occ_streak = 0; return false; };
-    if (ctx->two_pass_mode == MSPLAT_TWO_PASS_OFF) return no();
-    if (stereo || ctx->point_mode || ctx->depth_bits != 0 || ctx->rop != 0 || ctx->probe_on) return no();
-    if (!ctx->scan_free) return no();            // (the chunk offset of pass 1's column pass exists in the scan-free form only)
-    if (fp.tiles_x * fp.tiles_y <= 0 || (fp.tiles_x + 1) * (fp.tiles_y + 1) > kOccSatMax) return no();      // (the table of unfinished bins)
-    const bool forced = ctx->two_pass_mode == MSPLAT_TWO_PASS_ON;
-    if (!forced && (ctx->N < kTwoPassMinSplats || ctx->frames_rendered <= 8)) return no();
-    // one frame at a time and few visible splats (a rank of a row-sharded frame, a 1 M-splat cloud): the nine extra launches
-    // are latency the skipped work does not buy back (rank 3 of 8 of config 4, V = 1 M: 0.33 -> 0.38 ms; with frames in flight
-    // the same rank gains 12 %)
-    if (!forced && ctx->cfg.frame_mode != MSPLAT_FRAMES_IN_FLIGHT && ctx->h_flags &&
-        __atomic_load_n(ctx->h_flags + 1, __ATOMIC_RELAXED) < kTwoPassMinVisibleSerial)
-        return no();
-    const size_t nbins = (size_t)fp.tiles_x * fp.tiles_y;
-
-    // Feedback of an earlier two-pass frame (host-mapped, never waited for): [4] pairs of pass 1, [8] pairs of pass 2, [5] bins
-    // pass 1 left unfinished, [9] / [10] the number of the frame the words of pass 1 / pass 2 describe.  Only a frame that ran
-    // with the CURRENT share is evidence -- the host may be a hundred frames ahead of the GPU.
-    bool fresh = false;
-    float ratio = 0.0f, ufrac = 0.0f;
-    if (ctx->h_flags) {
-        const uint32_t s1 = __atomic_load_n(ctx->h_flags + 9, __ATOMIC_RELAXED), s2 = __atomic_load_n(ctx->h_flags + 10, __ATOMIC_RELAXED);
-        const uint32_t d1 = __atomic_load_n(ctx->h_flags + 4, __ATOMIC_RELAXED), d2 = __atomic_load_n(ctx->h_flags + 8, __ATOMIC_RELAXED);
-        if (s1 == s2 && s1 != 0u && (int32_t)(s1 - ctx->occ_change_seq) >= 0 && d1 != 0u) {
-            fresh = true;
-            ratio = (float)d2 / (float)d1;
-            ufrac = (float)__atomic_load_n(ctx->h_flags + 5, __ATOMIC_RELAXED) / (float)nbins;
-        }
-    }
-    auto set_share = [&](float next) {
-        ctx->occ_frac = std::min(kOccFracMax, std::max(kOccFracMin, next));
-        ctx->occ_change_seq = ctx->occ_seq + 1u;           // the first frame that runs with it
-    };
-    // the share: pass 2 should stay well below pass 1 (a flat optimum: tools/occlusion_potential.py)
-    auto steer = [&]() {
-        // (the step from "pass 2 has nothing to do" to "pass 2 does most of the work" can be one notch: after growing, the share
-        //  is not shrunk again for 32 looks)
-        if (ratio > 0.6f) {
-            set_share(ctx->occ_frac * 1.25f);
-            ctx->occ_no_shrink = 32u;
-        } else if (ctx->occ_no_shrink != 0u) {
-            --ctx->occ_no_shrink;
-        } else if (ratio < 0.02f && ctx->occ_frac > kOccFracMin) {
-            set_share(ctx->occ_frac * 0.75f);          // nothing left for pass 2: too much in pass 1
-        } else if (ratio < 0.15f && ctx->occ_frac > kOccFracMin) {
-            set_share(ctx->occ_frac * 0.85f);
-        }
-    };
-    if (forced) {
-        if (fresh && !ctx->occ_pinned) steer();
-    } else {
-        // AUTO.  A bin pass 1 does not finish costs a second look; where a third of the bins never saturate whatever the share
-        // (a cloud seen from outside: its rim) and the cloud is small, the nine extra launches cost what the skipped splats save
-        // (BASELINE config 2: 5830 -> 5770 frames/s at best, serial 0.27 -> 0.33 ms).  So two passes are PROBED: four frames,
-        // then one pass again until their feedback is in (the probe must not cost a hundred slow frames because the host runs
-        // ahead); more than 30 % unfinished is a strike (the next probe takes a larger share), three strikes a pause that doubles
-        // every time; otherwise two passes stay on, steered, until three looks in a row say otherwise.
-        enum { OFF = 0, PROBE = 1, WAIT = 2, ON = 3 };
-        // more than 30 % unfinished.  false: the third strike, one pass for a pause that doubles every time
-        auto strike = [&]() {
-            if (++ctx->occ_strikes >= 3u) {
-                ctx->occ_state_auto = OFF;
-                ctx->occ_off = ctx->occ_backoff;
-                ctx->occ_backoff = std::min(ctx->occ_backoff * 2u, 16384u);
-                return false;
-            }
-            set_share(ctx->occ_frac * 1.5f);
-            return true;
-        };
-        if (ctx->occ_state_auto == OFF) {
-            if (ctx->occ_off != 0u) { --ctx->occ_off; return no(); }
-            ctx->occ_state_auto = PROBE;
-            ctx->occ_probe_left = 4u;
-            ctx->occ_strikes = 0u;
-            set_share(0.15f);
-        }
-        if (ctx->occ_state_auto == WAIT) {
-            if (!fresh) {
-                // feedback that never becomes fresh (the probe frames binned nothing: the camera looked away from the cloud):
-                // back to one pass with the usual pause instead of waiting for ever
-                if (++ctx->occ_wait_frames > 256u) {
-                    ctx->occ_wait_frames = 0u;
-                    ctx->occ_state_auto = OFF;
-                    ctx->occ_off = ctx->occ_backoff;
-                }
-                return no();
-            }
-            ctx->occ_wait_frames = 0u;
-            if (ufrac > 0.3f) {
-                if (!strike()) return no();
-                ctx->occ_state_auto = PROBE;
-                ctx->occ_probe_left = 4u;
-            } else {
-                ctx->occ_state_auto = ON;
-                ctx->occ_strikes = 0u;
-                ctx->occ_backoff = 1024u;
-                steer();
-            }
-        } else if (ctx->occ_state_auto == ON && fresh && !ctx->occ_pinned) {
-            if (ufrac > 0.3f) {
-                if (!strike()) return no();
-            } else {
-                ctx->occ_strikes = 0u;
-                steer();
-            }
-        }
-        if (ctx->occ_state_auto == PROBE) {
-            if (ctx->occ_probe_left == 0u) {
-                ctx->occ_state_auto = WAIT;
-                ctx->occ_wait_frames = 0u;
-                return no();
-            }
-            --ctx->occ_probe_left;
-        }
-    }
-    if (buf_alloc(ctx, ctx->occ, 64) || buf_alloc(ctx, ctx->occ_mask, (size_t)kOccSatMax * 2 + 64) ||
+    const size_t nbins = (size_t)std::max(fp.tiles_x * fp.tiles_y, 0);
+    // (scan_free: the chunk offset of pass 1's column pass exists in the scan-free form only; kOccSatMax: the table of unfinished bins)
+    const bool eligible = !stereo && !ctx->point_mode && ctx->depth_bits == 0 && ctx->rop == 0 && !ctx->probe_on && ctx->scan_free &&
+                          nbins != 0 && (fp.tiles_x + 1) * (fp.tiles_y + 1) <= kOccSatMax;
+    const TwoPassFrame frame{ctx->two_pass_mode, eligible, ctx->cfg.frame_mode == MSPLAT_FRAMES_IN_FLIGHT, ctx->N, host_word(ctx, kHostV), nbins};
+    const TwoPassFeedback fb{host_word(ctx, kHostPass1Pairs), host_word(ctx, kHostUnfinishedBins), host_word(ctx, kHostPass2Pairs),
+                             host_word(ctx, kHostPass1Seq), host_word(ctx, kHostPass2Seq)};
+    if (!ctx->two_pass.decide(frame, fb)) return false;
+    if (buf_alloc(ctx, ctx->occ, kOccWordCount * sizeof(uint32_t)) || buf_alloc(ctx, ctx->occ_mask, (size_t)kOccSatMax * 2 + 64) ||
         buf_alloc(ctx, ctx->occ_fin, nbins * 16 + 64) || buf_alloc(ctx, ctx->occ_state, (size_t)fp.width * fp.height * 16 + 64) ||
         buf_alloc(ctx, ctx->occ_live, ((size_t)ctx->N + 64) * 4) || buf_alloc(ctx, ctx->occ_boxdead, 2048 * 4 + 64) ||
         buf_alloc(ctx, ctx->occ_unf, nbins * 4 + 64)) {
         ctx->err.clear();                        // (no memory for the extra buffers: the frame runs in one pass)
-        return no();
+        return false;
     }
-    ctx->occ_seq++;                              // this frame's number (never 0)
-    if (ctx->occ_seq == 0u) ctx->occ_seq = 1u;
-    ctx->occ_streak++;
-    frac = ctx->occ_frac;
+    ctx->two_pass.commit();                      // this frame's number
+    frac = ctx->two_pass.share;
     return true;
 }
 
@@ -1328,13 +1217,13 @@ static void issue_projection(RenderChain& rc, int mode, float occ_frac)
         });
     };
     if (mode == PROJ_PASS1) {
-        // (project_kernel's first pass computes the cut and leaves it in occ[0])
+        // (project_kernel's first pass computes the cut and leaves it in occ[kOccCut])
         const ProjExtra ex{nullptr, occ, nullptr, occ_frac};
         project(int_t<PROJ_PASS1>{}, std::min(pgrid, kProjGridTwoPass), (const uint32_t*)d_Vsort, ex, ProjNoView1{0});
     } else if (mode == PROJ_LISTED) {
-        // the listed ranks behind the cut (occ[1] of them)
-        const ProjExtra ex{ctx->d_flags ? ctx->d_flags + 7 : (uint32_t*)nullptr, nullptr, (const uint32_t*)ctx->occ_live.p, 0.0f};
-        project(int_t<PROJ_LISTED>{}, std::min(pgrid, kProjGridTwoPass), (const uint32_t*)(occ + 1), ex, ProjNoView1{0});
+        // the listed ranks behind the cut (occ[kOccListed] of them)
+        const ProjExtra ex{ctx->d_flags ? ctx->d_flags + kHostListedRanks : (uint32_t*)nullptr, nullptr, (const uint32_t*)ctx->occ_live.p, 0.0f};
+        project(int_t<PROJ_LISTED>{}, std::min(pgrid, kProjGridTwoPass), (const uint32_t*)(occ + kOccListed), ex, ProjNoView1{0});
     } else if (rc.stereo) {
         const ProjExtra ex{rc.d_Vframe, nullptr, nullptr, 0.0f};
         project(int_t<PROJ_TWO_VIEWS>{}, pgrid, (const uint32_t*)d_Vsort, ex, proj_view1(fp));
@@ -1355,9 +1244,9 @@ static void issue_binning(RenderChain& rc, int keep_overflow, int occ_pass)
     const bool stereo = rc.stereo, async_overflow_flag = rc.async_overflow_flag;
     const int ntiles = rc.ntiles;
     uint32_t *d_Vsort = rc.d_Vsort, *d_D = rc.d_D, *d_overflow = rc.d_overflow, *d_queue = rc.d_queue, *occ = rc.occ, *d_Vframe = rc.d_Vframe;
-    // second chain of a two-pass frame: the binning walks occ[4] ranks (V, or 0 when pass 1 left no bin unfinished)
-    uint32_t* d_V = occ_pass == 2 ? occ + 4 : d_Vframe;
-    const uint32_t* d_first = occ_pass == 1 ? occ : nullptr;      // pass 1 bins the ranks from the cut on
+    // second chain of a two-pass frame: the binning walks occ[kOccRanks2] ranks (V, or 0 when pass 1 left no bin unfinished)
+    uint32_t* d_V = occ_pass == 2 ? occ + kOccRanks2 : d_Vframe;
+    const uint32_t* d_first = occ_pass == 1 ? occ + kOccCut : nullptr;      // pass 1 bins the ranks from the cut on
 
     // pass 1: stable partition by tile column, enumerated from the rank-ordered rectangles
     uint32_t* totals1 = (uint32_t*)ctx->totals1.p;
@@ -1370,7 +1259,7 @@ static void issue_binning(RenderChain& rc, int keep_overflow, int occ_pass)
     ctx->render_parity ^= 1u;
     // helper workgroups for as many split chunks as an EARLIER frame asked for (host-mapped word, read without synchronising),
     // with headroom; a frame that needs more runs its extra heavy chunks unsplit and the next launch adapts
-    const uint32_t last_heavy = ctx->h_flags ? __atomic_load_n(ctx->h_flags + 3, __ATOMIC_RELAXED) : 0u;
+    const uint32_t last_heavy = host_word(ctx, kHostHeavyChunks);
     const uint32_t heavy_slots = last_heavy != 0u ? std::min<uint32_t>(kHeavyCap, 2u * last_heavy + 8u) : 0u;
     const int nhelp = (int)(heavy_slots * (kHeavyParts - 1u));
     // scan-free variants while the chunk tables are small; the row pass's size (D) is only known on the device, so
@@ -1379,7 +1268,7 @@ static void issue_binning(RenderChain& rc, int keep_overflow, int occ_pass)
     // (r2, one-level group tables: the column pass's table was scanned by a kernel from 4096 rows on; with two levels every
     //  table that fits the supergroup rows is scan-free)
     const bool fused1 = ctx->scan_free && div_up(N, bchunk) <= kFusedMaxChunks;
-    const uint32_t last_D = ctx->h_flags ? __atomic_load_n(ctx->h_flags + 2, __ATOMIC_RELAXED) : 0u;
+    const uint32_t last_D = host_word(ctx, kHostD);
     const bool fused2 = ctx->scan_free && last_D != 0u && div_up((uint64_t)last_D + (last_D >> 2), kPairChunk) <= kFusedMaxChunks &&
                         div_up(cap, kPairChunk) <= ctx->hist2_stride;                  // (the tables hold every chunk the capacity allows)
     uint32_t* gB1 = (uint32_t*)ctx->gsumB1.p;
@@ -1403,7 +1292,7 @@ static void issue_binning(RenderChain& rc, int keep_overflow, int occ_pass)
                            async_overflow_flag ? 1 : 0, fused1 ? (const uint32_t*)gB1 : nullptr, fused1 ? totals1 : nullptr,
                            xcdg, (const uint32_t*)hv_cur, (const uint8_t*)ctx->heavy_flag.p,
                            (uint32_t)nhelp, fp.tiles_x, ctx->gsupB1, (const uint32_t*)d_Vsort,
-                           (keep_overflow && ctx->d_flags) ? ctx->d_flags + 8 : (uint32_t*)nullptr, ctx->occ_seq, d_first);
+                           (keep_overflow && ctx->d_flags) ? ctx->d_flags + kHostPass2Pairs : (uint32_t*)nullptr, ctx->two_pass.seq, d_first);
     });
     // pass 2: stable partition by tile row (one generic radix pass on the top byte); words become (tx<<24)|rank
     // The heaviest-first order of the bins only pays when every work item has its own wave (the hardware then starts the
@@ -1454,7 +1343,7 @@ static int issue_compositor(RenderChain& rc, int occ_pass, int ev_c0, int ev_c1)
     const size_t pitch = rc.pitch;
     uint32_t* fin = occ_pass ? (uint32_t*)ctx->occ_fin.p : nullptr;
     float4* state = occ_pass ? (float4*)ctx->occ_state.p : nullptr;
-    const uint32_t* d_nbins = occ_pass == 2 ? occ + 2 : nullptr;      // second chain of a two-pass frame: the listed unfinished bins
+    const uint32_t* d_nbins = occ_pass == 2 ? occ + kOccUnfinished : nullptr;      // second chain of a two-pass frame: the listed unfinished bins
     // the target's pixel format (kFb* = MSPLAT_FB_*: msplat_create let nothing else in); only the kernels' load_px / store_px differ
     auto with_format = [&](auto&& f) { with_int<kFbF16, kFbUnorm8, kFbSrgb8, kFbF32>(ctx->cfg.fb_format, f); };
 
@@ -1570,7 +1459,7 @@ static void issue_occlusion_gate(RenderChain& rc)
                            nboxes, fp, (const uint16_t*)ctx->occ_mask.p, (uint32_t*)ctx->occ_boxdead.p);
     hipLaunchKernelGGL(occ_gate_kernel, dim3(std::max(1u, div_up(N, kOccGateRanks))), dim3(kThreads), 0, s, (const uint32_t*)ctx->valA.p,
                        (const uint32_t*)d_Vsort, occ, (const float4*)ctx->pos4.p, (uint32_t*)ctx->rect.p, fp,
-                       (const uint16_t*)ctx->occ_mask.p, (uint32_t*)ctx->occ_live.p, ctx->d_flags, (const uint32_t*)d_D, ctx->occ_seq,
+                       (const uint16_t*)ctx->occ_mask.p, (uint32_t*)ctx->occ_live.p, ctx->d_flags, (const uint32_t*)d_D, ctx->two_pass.seq,
                        use_boxes ? (const uint32_t*)ctx->occ_boxdead.p : (const uint32_t*)nullptr, boxwords);
 }
 
@@ -1587,8 +1476,8 @@ static int launch_render(msplat_ctx* ctx, const FrameParams& fp, void* d_out, si
     const bool stereo = fp.views == 2;
     uint32_t* counters = (uint32_t*)ctx->counters.p;
     const uint32_t N = stereo ? (uint32_t)(2 * ctx->N + 64) : (uint32_t)ctx->N;
-    RenderChain rc{ctx, fp, s, stereo, N, counters + 0, counters + 1, counters + 2, (uint32_t*)ctx->queue.p,
-                   stereo ? counters + 9 : counters + 0, (uint32_t*)ctx->occ.p, fp.tiles_x * fp.tiles_y, (uint32_t)ctx->pair_cap,
+    RenderChain rc{ctx, fp, s, stereo, N, counters + kCntV, counters + kCntD, counters + kCntOverflow, (uint32_t*)ctx->queue.p,
+                   stereo ? counters + kCntVframe2 : counters + kCntV, (uint32_t*)ctx->occ.p, fp.tiles_x * fp.tiles_y, (uint32_t)ctx->pair_cap,
                    false, 0, (int)std::max(1u, div_up(N, kProjThreads)), d_out, d_out1, pitch, async_overflow_flag, depth.p, depth.pitch};
     // Two-pass frame with occlusion feedback (msplat_occlusion.hip.h): the nearest R1 splats first, then only what the bins
     // they did not saturate still need.  Same pixels; chosen once per Render (occlusion_plan).  The retries of a host-output
@@ -1612,33 +1501,33 @@ static int launch_render(msplat_ctx* ctx, const FrameParams& fp, void* d_out, si
     }
     const bool timed = rc.timed = ctx->ev_ok && ((ctx->render_calls - 1) % ctx->timing_stride) == 0;
     const int tset = rc.tset = (int)(ctx->render_sets % msplat_ctx::kEvSets);
-    if (timed) HIP_TRY(ctx, hipEventRecord(ctx->ev[tset][2], s));
+    if (timed) HIP_TRY(ctx, hipEventRecord(ctx->ev[tset][kEvRenderBegin], s));
     rc.occ = (uint32_t*)ctx->occ.p;              // (allocated by occlusion_plan with a context's first two-pass frame)
 
     // ---- the plain chain (also: both eyes in one chain, points, the emulations), or pass 1 of a two-pass frame ----
     issue_projection(rc, two_pass ? PROJ_PASS1 : PROJ_PLAIN, plan->frac);
-    if (timed) HIP_TRY(ctx, hipEventRecord(ctx->ev[tset][3], s));
+    if (timed) HIP_TRY(ctx, hipEventRecord(ctx->ev[tset][kEvProjected], s));
     issue_binning(rc, 0, two_pass ? 1 : 0);
-    if (timed) HIP_TRY(ctx, hipEventRecord(ctx->ev[tset][4], s));
-    int crc = issue_compositor(rc, two_pass ? 1 : 0, 6, 7);
+    if (timed) HIP_TRY(ctx, hipEventRecord(ctx->ev[tset][kEvBinned], s));
+    int crc = issue_compositor(rc, two_pass ? 1 : 0, kEvCompBegin, kEvCompEnd);
     if (crc) return crc;
     if (two_pass) {
         // ---- pass 2: gate, the listed ranks, the bins pass 1 left unfinished ----
-        if (timed) HIP_TRY(ctx, hipEventRecord(ctx->ev[tset][8], s));
+        if (timed) HIP_TRY(ctx, hipEventRecord(ctx->ev[tset][kEvPass2Begin], s));
         issue_occlusion_gate(rc);
         issue_projection(rc, PROJ_LISTED, 0.0f);
-        if (timed) HIP_TRY(ctx, hipEventRecord(ctx->ev[tset][9], s));
+        if (timed) HIP_TRY(ctx, hipEventRecord(ctx->ev[tset][kEvPass2Projected], s));
         const bool timed1 = ctx->comp_kernel_timed;
         issue_binning(rc, 1, 2);
-        if (timed) HIP_TRY(ctx, hipEventRecord(ctx->ev[tset][10], s));
-        crc = issue_compositor(rc, 2, 11, 12);
+        if (timed) HIP_TRY(ctx, hipEventRecord(ctx->ev[tset][kEvPass2Binned], s));
+        crc = issue_compositor(rc, 2, kEvComp2Begin, kEvComp2End);
         if (crc) return crc;
         ctx->comp_kernel_timed = ctx->comp_kernel_timed && timed1;
         if (first_attempt) ctx->frames_two_pass++;
     }
     ctx->last_render_two_pass = two_pass;
     if (timed) {
-        HIP_TRY(ctx, hipEventRecord(ctx->ev[tset][5], s));
+        HIP_TRY(ctx, hipEventRecord(ctx->ev[tset][kEvRenderEnd], s));
         if (ctx->comp_kernel_timed) ctx->comp_kernel_sets_mask |= 1u << tset; else ctx->comp_kernel_sets_mask &= ~(1u << tset);
         if (two_pass) ctx->two_pass_sets_mask |= 1u << tset; else ctx->two_pass_sets_mask &= ~(1u << tset);
         ctx->render_sets++;
@@ -1730,14 +1619,14 @@ static int render_to_host(msplat_ctx* ctx, const FrameParams& fp, void* rgba, ui
         uint32_t cnt[4];
         HIP_TRY(ctx, hipMemcpyAsync(cnt, ctx->counters.p, sizeof(cnt), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        if (cnt[2] == 0) {
+        if (cnt[kCntOverflow] == 0) {
             if ((rc = copy_host_rows(ctx, fp, rgba, pitch_bytes, ctx->fb, tight, true))) return rc;
             return depth.p ? copy_host_rows(ctx, fp, depth.p, depth.pitch, ctx->fbz, ztight, true) : MSPLAT_OK;
         }
-        // overflow: cnt[2] holds the required pair count
-        const uint64_t need = (uint64_t)cnt[2] + (cnt[2] >> 2) + 1024;
+        // overflow: the word holds the required pair count
+        const uint64_t need = (uint64_t)cnt[kCntOverflow] + (cnt[kCntOverflow] >> 2) + 1024;
         if (ctx->cfg.pair_capacity != 0 || need > 0x7FFFFFFFull)
-            return fail(ctx, MSPLAT_ERR_PAIR_OVERFLOW, "pair buffer too small: need %u, capacity %llu", cnt[2],
+            return fail(ctx, MSPLAT_ERR_PAIR_OVERFLOW, "pair buffer too small: need %u, capacity %llu", cnt[kCntOverflow],
                         (unsigned long long)ctx->pair_cap);
         if ((rc = ensure_pair_capacity(ctx, need))) return rc;
     }

@@ -35,7 +35,7 @@ int msplat_sort_count(msplat_ctx* ctx, uint32_t* v)
     if (!ctx || !v) return fail(ctx, MSPLAT_ERR_INVALID_ARG, "NULL argument");
     if (!ctx->has_sort) return fail(ctx, MSPLAT_ERR_NO_SORT, "no sort yet");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipMemcpyAsync(v, ctx->counters.p, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(v, (const uint32_t*)ctx->counters.p + kCntV, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return MSPLAT_OK;
 }
@@ -127,29 +127,28 @@ int msplat_get_stats(msplat_ctx* ctx, msplat_stats* out)
     uint32_t cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (ctx->has_render) {   // "drawn" is a statistic only: counted on demand, not in the frame
         uint32_t* counters = (uint32_t*)ctx->counters.p;
-        HIP_TRY(ctx, hipMemsetAsync(counters + 4, 0, 4 * sizeof(uint32_t), ctx->stream));
-        // counters + 6 is 8-byte aligned: the 64-bit pair count lives in words 6..7
+        HIP_TRY(ctx, hipMemsetAsync(counters + kCntDrawn, 0, (kCntLdsProbe - kCntDrawn) * sizeof(uint32_t), ctx->stream));     // drawn .. pairs16
         hipLaunchKernelGGL(count_drawn_kernel, dim3(256), dim3(kThreads), 0, ctx->stream, (const uint32_t*)ctx->rect.p,
-                           (const float4*)ctx->rec2d.p, counters + 0, ctx->last_fp, counters + 4,
-                           (unsigned long long*)(counters + 6));
+                           (const float4*)ctx->rec2d.p, counters + kCntV, ctx->last_fp, counters + kCntDrawn,
+                           (unsigned long long*)(counters + kCntPairs16));
     }
     HIP_TRY(ctx, hipMemcpyAsync(cnt, ctx->counters.p, sizeof(cnt), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     std::memset(out, 0, sizeof(*out));
     out->num_splats = ctx->N;
-    out->sort_count = ctx->has_sort ? cnt[0] : 0;
-    out->pairs = ctx->has_render ? cnt[1] : 0;
-    out->drawn = ctx->has_render ? cnt[4] : 0;
-    out->pairs_tile16 = ctx->has_render ? ((uint64_t)cnt[7] << 32 | cnt[6]) : 0;
+    out->sort_count = ctx->has_sort ? cnt[kCntV] : 0;
+    out->pairs = ctx->has_render ? cnt[kCntD] : 0;
+    out->drawn = ctx->has_render ? cnt[kCntDrawn] : 0;
+    out->pairs_tile16 = ctx->has_render ? ((uint64_t)cnt[kCntPairs16 + 1] << 32 | cnt[kCntPairs16]) : 0;
     out->tiles_x = ctx->last_fp.tiles_x;
     out->tiles_y = ctx->last_fp.tiles_y;
     out->width = ctx->last_fp.width;
     out->height = ctx->last_fp.height;
     out->pair_capacity = ctx->pair_cap;
     out->device_bytes = ctx->device_bytes;
-    if (ctx->has_render && cnt[2] != 0)
+    if (ctx->has_render && cnt[kCntOverflow] != 0)
         return fail(ctx, MSPLAT_ERR_PAIR_OVERFLOW, "last render overflowed the pair buffer: need %u, capacity %llu",
-                    cnt[2], (unsigned long long)ctx->pair_cap);
+                    cnt[kCntOverflow], (unsigned long long)ctx->pair_cap);
     return MSPLAT_OK;
 }
 
@@ -165,29 +164,29 @@ int msplat_get_timings(msplat_ctx* ctx, msplat_timings* out)
     const uint32_t ns = std::min<uint32_t>(ctx->sort_sets, msplat_ctx::kEvSets);
     for (uint32_t k = 0; k < ns; ++k) {
         float t = 0.0f;
-        HIP_TRY(ctx, hipEventElapsedTime(&t, ctx->ev[k][0], ctx->ev[k][1]));
+        HIP_TRY(ctx, hipEventElapsedTime(&t, ctx->ev[k][kEvSortBegin], ctx->ev[k][kEvSortEnd]));
         out->sort_total += t / ns;
     }
     const uint32_t nr = std::min<uint32_t>(ctx->render_sets, msplat_ctx::kEvSets);
     for (uint32_t k = 0; k < nr; ++k) {
         float a = 0, b = 0, c = 0, d = 0;
         const bool two = (ctx->two_pass_sets_mask & (1u << k)) != 0u;     // a two-pass frame: every stage ran twice
-        HIP_TRY(ctx, hipEventElapsedTime(&a, ctx->ev[k][2], ctx->ev[k][5]));
-        HIP_TRY(ctx, hipEventElapsedTime(&b, ctx->ev[k][2], ctx->ev[k][3]));
-        HIP_TRY(ctx, hipEventElapsedTime(&c, ctx->ev[k][3], ctx->ev[k][4]));
-        HIP_TRY(ctx, hipEventElapsedTime(&d, ctx->ev[k][4], ctx->ev[k][two ? 8 : 5]));
+        HIP_TRY(ctx, hipEventElapsedTime(&a, ctx->ev[k][kEvRenderBegin], ctx->ev[k][kEvRenderEnd]));
+        HIP_TRY(ctx, hipEventElapsedTime(&b, ctx->ev[k][kEvRenderBegin], ctx->ev[k][kEvProjected]));
+        HIP_TRY(ctx, hipEventElapsedTime(&c, ctx->ev[k][kEvProjected], ctx->ev[k][kEvBinned]));
+        HIP_TRY(ctx, hipEventElapsedTime(&d, ctx->ev[k][kEvBinned], ctx->ev[k][two ? kEvPass2Begin : kEvRenderEnd]));
         if (two) {
             float b2 = 0, c2 = 0, d2 = 0;
-            HIP_TRY(ctx, hipEventElapsedTime(&b2, ctx->ev[k][8], ctx->ev[k][9]));      // mask + gate + second projection
-            HIP_TRY(ctx, hipEventElapsedTime(&c2, ctx->ev[k][9], ctx->ev[k][10]));
-            HIP_TRY(ctx, hipEventElapsedTime(&d2, ctx->ev[k][10], ctx->ev[k][5]));
+            HIP_TRY(ctx, hipEventElapsedTime(&b2, ctx->ev[k][kEvPass2Begin], ctx->ev[k][kEvPass2Projected]));      // mask + gate + second projection
+            HIP_TRY(ctx, hipEventElapsedTime(&c2, ctx->ev[k][kEvPass2Projected], ctx->ev[k][kEvPass2Binned]));
+            HIP_TRY(ctx, hipEventElapsedTime(&d2, ctx->ev[k][kEvPass2Binned], ctx->ev[k][kEvRenderEnd]));
             b += b2; c += c2; d += d2;
         }
         out->render_total += a / nr; out->project += b / nr; out->binning += c / nr; out->composite += d / nr;
         if (ctx->comp_kernel_sets_mask & (1u << k)) {
             float e = 0, e2 = 0;
-            HIP_TRY(ctx, hipEventElapsedTime(&e, ctx->ev[k][6], ctx->ev[k][7]));
-            if (two) HIP_TRY(ctx, hipEventElapsedTime(&e2, ctx->ev[k][11], ctx->ev[k][12]));
+            HIP_TRY(ctx, hipEventElapsedTime(&e, ctx->ev[k][kEvCompBegin], ctx->ev[k][kEvCompEnd]));
+            if (two) HIP_TRY(ctx, hipEventElapsedTime(&e2, ctx->ev[k][kEvComp2Begin], ctx->ev[k][kEvComp2End]));
             out->reserved[1] += e + e2;  // summed here, averaged below
             out->reserved[2] += 1.0f;
         }
@@ -223,10 +222,9 @@ int msplat_debug_two_pass(msplat_ctx* ctx, float share, uint64_t* two_pass_frame
     drain_async(ctx);
     if (!ctx) return fail(nullptr, MSPLAT_ERR_INVALID_ARG, "ctx is NULL");
     if (!(share >= 0.0f && share <= 1.0f)) return fail(ctx, MSPLAT_ERR_INVALID_ARG, "msplat_debug_two_pass: share %g not in [0, 1]", (double)share);
-    ctx->occ_pinned = share > 0.0f;
-    if (ctx->occ_pinned) ctx->occ_frac = share;
+    ctx->two_pass.pin(share);
     if (two_pass_frames) *two_pass_frames = ctx->frames_two_pass;
-    if (share_now) *share_now = ctx->occ_frac;
+    if (share_now) *share_now = ctx->two_pass.share;
     return MSPLAT_OK;
 }
 
@@ -236,16 +234,16 @@ int msplat_get_two_pass_info(msplat_ctx* ctx, uint64_t out[8])
     if (!ctx || !out) return fail(ctx, MSPLAT_ERR_INVALID_ARG, "NULL argument");
     for (int k = 0; k < 8; ++k) out[k] = 0;
     out[0] = ctx->frames_two_pass;
-    if (!ctx->last_render_two_pass || !ctx->h_flags) { out[0] = ctx->last_render_two_pass ? out[0] : 0; return MSPLAT_OK; }
+    if (!ctx->last_render_two_pass) { out[0] = 0; return MSPLAT_OK; }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    out[1] = __atomic_load_n(ctx->h_flags + 6, __ATOMIC_RELAXED);
-    out[2] = __atomic_load_n(ctx->h_flags + 7, __ATOMIC_RELAXED);
-    out[3] = __atomic_load_n(ctx->h_flags + 4, __ATOMIC_RELAXED);
-    out[4] = __atomic_load_n(ctx->h_flags + 8, __ATOMIC_RELAXED);
-    out[5] = __atomic_load_n(ctx->h_flags + 5, __ATOMIC_RELAXED);
+    out[1] = host_word(ctx, kHostPass1Splats);
+    out[2] = host_word(ctx, kHostListedRanks);
+    out[3] = host_word(ctx, kHostPass1Pairs);
+    out[4] = host_word(ctx, kHostPass2Pairs);
+    out[5] = host_word(ctx, kHostUnfinishedBins);
     out[6] = (uint64_t)ctx->last_fp.tiles_x * (uint64_t)ctx->last_fp.tiles_y;
-    out[7] = __atomic_load_n(ctx->h_flags + 1, __ATOMIC_RELAXED);
+    out[7] = host_word(ctx, kHostV);
     return MSPLAT_OK;
 }
 
@@ -256,11 +254,11 @@ int msplat_debug_verify_order(msplat_ctx* ctx, uint32_t* key_violations, uint32_
     if (!ctx->has_sort) return fail(ctx, MSPLAT_ERR_NO_SORT, "no sort yet");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     uint32_t* counters = (uint32_t*)ctx->counters.p;
-    uint32_t* bad = counters + 12;
+    uint32_t* bad = counters + kCntOrderBad;
     HIP_TRY(ctx, hipMemsetAsync(bad, 0, 2 * sizeof(uint32_t), ctx->stream));
     const int nbins = ctx->has_render ? ctx->last_fp.tiles_x * ctx->last_fp.tiles_y : 0;
     hipLaunchKernelGGL(verify_order_kernel, dim3(1024), dim3(kThreads), 0, ctx->stream, (const uint32_t*)ctx->keyA.p,
-                       (const uint32_t*)ctx->valA.p, (const uint32_t*)counters, nbins ? (const uint32_t*)ctx->tile_start.p : nullptr,
+                       (const uint32_t*)ctx->valA.p, (const uint32_t*)(counters + kCntV), nbins ? (const uint32_t*)ctx->tile_start.p : nullptr,
                        (const uint32_t*)ctx->pairsB.p, (uint32_t)ctx->pair_cap, nbins, bad);
     uint32_t h[2] = {0, 0};
     HIP_TRY(ctx, hipMemcpyAsync(h, bad, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
@@ -348,7 +346,7 @@ int msplat_debug_get_tile_lists(msplat_ctx* ctx, uint32_t* tile_start, uint32_t 
     if (tile_start) HIP_TRY(ctx, hipMemcpy(tile_start, ctx->tile_start.p, (size_t)(ntiles + 1) * 4, hipMemcpyDeviceToHost));
     uint32_t cnt[4];
     HIP_TRY(ctx, hipMemcpy(cnt, ctx->counters.p, sizeof(cnt), hipMemcpyDeviceToHost));
-    const uint64_t d = std::min<uint64_t>(cnt[1], ctx->pair_cap);
+    const uint64_t d = std::min<uint64_t>(cnt[kCntD], ctx->pair_cap);
     if (pairs) {
         if (pair_cap < d) return fail(ctx, MSPLAT_ERR_INVALID_ARG, "pair capacity too small");
         if (d) HIP_TRY(ctx, hipMemcpy(pairs, ctx->pairsB.p, d * 4, hipMemcpyDeviceToHost));

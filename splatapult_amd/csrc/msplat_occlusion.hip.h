@@ -33,10 +33,9 @@ namespace msplat {
 // [0, col] (virtual rows in band mode, like the rectangles); row 0 and column 0 are zero.  uint16: at most kOccSatMax entries.
 constexpr int kOccSatMax = 24576;             // (tiles_x + 1) (tiles_y + 1): 4096 x 4096 pixels need 129 x 129
 
-// occ[0] = cut (first rank of pass 1, a multiple of 1024 = kBinChunk), occ[1] = splats behind the cut that pass the gate, occ[2] =
-// unfinished bins, occ[4] = ranks the second binning chain walks (occ_mask_kernel).  The cut is a pure function of V and the
-// share (occ_cut, msplat_common.hip.h), evaluated by project_kernel's first pass itself (its first workgroup also publishes it
-// and clears occ[1], occ[2]).
+// The frame's words occ[]: OccWord, msplat_common.hip.h.  The cut is a pure function of V and the share (occ_cut, there too),
+// evaluated by project_kernel's first pass itself (its first workgroup also publishes it and clears the listed ranks and the
+// unfinished bins).
 
 // ONE workgroup: fin[bin * 4 + quadrant] (composite_kernel, pass 1) -> the summed-area table of the bins with a tile to resume
 // (built in LDS: a row prefix per thread, then a column prefix per thread), their number
@@ -45,8 +44,8 @@ __global__ __launch_bounds__(kOccMaskThreads) void occ_mask_kernel(const uint32_
                                                             uint16_t* __restrict__ sat, uint32_t* __restrict__ occ,
                                                             const uint32_t* __restrict__ d_V, uint32_t* __restrict__ unf_bins)
 {
-    // also: unf_bins[0 .. occ[2]) = the unfinished bins (any order: the compositor's second launch walks these alone), and
-    // occ[4] = the rank count the second binning chain walks: V, or 0 when no bin is left (its kernels then find no work)
+    // also: unf_bins[0 .. occ[kOccUnfinished]) = the unfinished bins (any order: the compositor's second launch walks these alone),
+    // and occ[kOccRanks2] = the rank count the second binning chain walks: V, or 0 when no bin is left (its kernels then find no work)
     __shared__ uint16_t s_sat[kOccSatMax];
     __shared__ uint32_t s_cnt;
     const int stride = tiles_x + 1, nbins = tiles_x * tiles_y, nsat = stride * (tiles_y + 1);
@@ -81,8 +80,8 @@ __global__ __launch_bounds__(kOccMaskThreads) void occ_mask_kernel(const uint32_
     __syncthreads();
     for (int i = threadIdx.x; i < nsat; i += kOccMaskThreads) sat[i] = s_sat[i];
     if (threadIdx.x == 0) {
-        occ[2] = s_cnt;
-        occ[4] = s_cnt != 0u ? *d_V : 0u;
+        occ[kOccUnfinished] = s_cnt;
+        occ[kOccRanks2] = s_cnt != 0u ? *d_V : 0u;
     }
 }
 
@@ -191,14 +190,14 @@ __global__ __launch_bounds__(kThreads) void occ_gate_kernel(const uint32_t* __re
         for (uint32_t i = threadIdx.x; i < min(boxwords, 2048u); i += kThreads) s_dead[i] = boxdead[i];
     if (threadIdx.x == 0) s_n = 0u;
     __syncthreads();
-    const uint32_t V = *d_V, cut = occ[0];
+    const uint32_t V = *d_V, cut = occ[kOccCut];
     if (blockIdx.x == 0 && threadIdx.x == 0 && host_words != nullptr) {
         // feedback for the host's choice of the share in a LATER frame: pairs of pass 1, unfinished bins, splats in pass 1, and
         // which frame this is about
-        __hip_atomic_store(host_words + 4, *d_D, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        __hip_atomic_store(host_words + 5, occ[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        __hip_atomic_store(host_words + 6, V - cut, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        __hip_atomic_store(host_words + 9, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store(host_words + kHostPass1Pairs, *d_D, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store(host_words + kHostUnfinishedBins, occ[kOccUnfinished], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store(host_words + kHostPass1Splats, V - cut, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store(host_words + kHostPass1Seq, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
     const uint32_t base = blockIdx.x * (uint32_t)kOccGateRanks;
     if (base >= V) return;
@@ -277,7 +276,7 @@ __global__ __launch_bounds__(kThreads) void occ_gate_kernel(const uint32_t* __re
     __syncthreads();
     const uint32_t n = s_n;
     if (n == 0u) return;
-    if (threadIdx.x == 0) s_base = atomicAdd(&occ[1], n);
+    if (threadIdx.x == 0) s_base = atomicAdd(&occ[kOccListed], n);
     __syncthreads();
     for (uint32_t i = threadIdx.x; i < n; i += kThreads) live_list[s_base + i] = s_list[i];
 }

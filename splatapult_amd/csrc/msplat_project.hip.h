@@ -267,7 +267,7 @@ template <int MODE> struct ProjSecondView { using type = ProjNoView1; };
 template <> struct ProjSecondView<3> { using type = ProjView1; };
 struct ProjExtra {
     uint32_t* d_Veff;            // PROJ_TWO_VIEWS: ranks the binning walks (V1 + V); PROJ_LISTED: optional host-mapped count of listed ranks
-    uint32_t* d_cut;             // PROJ_PASS1: occ[0 .. 2]
+    uint32_t* d_cut;             // PROJ_PASS1: the frame's occ[] words (OccWord)
     const uint32_t* rank_list;   // PROJ_LISTED: the *d_V ranks to project (any order)
     float occ_share;             // PROJ_PASS1: share of the visible splats in pass 1
 };
@@ -283,7 +283,7 @@ __global__ __launch_bounds__(kProjThreads) void project_kernel(const uint32_t* _
                                                                typename ProjSecondView<MODE>::type v1)
 {
     // PROJ_PASS1: ranks below cut = occ_cut(V, occ_share) only get an empty rectangle, their records are not fetched; the cut is
-    // left in d_cut[0] (= occ[0]).  PROJ_LISTED: the *d_V ranks to project are listed (any order); records and rectangles are
+    // left in d_cut[kOccCut].  PROJ_LISTED: the *d_V ranks to project are listed (any order); records and rectangles are
     // stored by rank as always.
     // Records are 256 B (full SH) or 128 B (base) and line aligned (SH_FP16: 160 / 96 B; SH_Q8: 128 B).  The gather by sorted index is
     // done cooperatively (project_block): F4 consecutive lanes fetch one whole record (coalesced 256/128 B), the wave
@@ -308,7 +308,7 @@ __global__ __launch_bounds__(kProjThreads) void project_kernel(const uint32_t* _
     } else if constexpr (MODE == PROJ_PASS1) {
         // pass 1 of a two-pass frame: ranks [cut, V) are projected (grid-stride), the ranks behind the cut get empty rectangles
         const uint32_t cut = occ_cut(V, ex.occ_share);
-        if (blockIdx.x == 0 && lane == 0) { ex.d_cut[0] = cut; ex.d_cut[1] = 0u; ex.d_cut[2] = 0u; }      // occ[0 .. 2] for the kernels that follow
+        if (blockIdx.x == 0 && lane == 0) { ex.d_cut[kOccCut] = cut; ex.d_cut[kOccListed] = 0u; ex.d_cut[kOccUnfinished] = 0u; }      // for the kernels that follow
         for (uint32_t i = blockIdx.x * kProjThreads + lane; i < cut; i += gridDim.x * kProjThreads) out_rect[i] = kRectEmpty;
         for (uint32_t r0 = cut + blockIdx.x * kProjThreads; r0 < V; r0 += gridDim.x * kProjThreads) {
             project_block<FULL_SH, false, STORAGE>(r0 + lane, r0 + lane, r0 + lane < V, lane, sorted_idx, recs, fp, fp.view, fp.proj, fp.eye, out_rec, out_rect, out_zq, s_stage);

@@ -1,6 +1,8 @@
 // host_sanitize_driver.cpp -- ASan / UBSan job for the host half of libmsplat.so (SURVEY.md section 5's sanitizer
 // counterpart): the hand-written parsers behind a C ABI that is documented as never throwing --
-// PLY (gaussian_scene.cpp, point_scene.cpp), JSON + PNG inflate / deflate (scene_config.cpp).
+// PLY (gaussian_scene.cpp, point_scene.cpp), JSON + PNG inflate / deflate (scene_config.cpp) -- and a replay of the two-pass
+// controller (two_pass_controller.hpp: host policy whose pause and timeout paths take hundreds of frames of a large cloud to reach
+// on a GPU; expected values are read off the controller's rules, shares computed with its own float expressions).
 //
 //   make sanitize      builds the three host sources + this file with -fsanitize=address,undefined (no HIP needed)
 //                      and runs it on tests/golden/* plus a set of hostile inputs generated here.
@@ -8,6 +10,7 @@
 // The device entry points the host code forwards to are stubbed (they only receive what the parsers produced, so
 // the stubs also check that the buffers they are handed are fully readable).  Exit code 0 = every call returned
 // the expected status and the sanitizers stayed silent.
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -19,6 +22,7 @@
 
 #include "../../include/msplat.h"
 #include "../../include/msplat_debug.h"
+#include "../../splatapult_amd/host/two_pass_controller.hpp"
 
 static int g_fail = 0;
 static uint64_t g_stub_bytes = 0;
@@ -342,6 +346,184 @@ static void image_cases()
     }
 }
 
+// ---- the two-pass controller.  Every case: frames numbered from 1; AUTO, an eligible frame, frames in flight, 2^18 splats and 1000
+// bins unless it says otherwise ----
+using msplat::TwoPassController;
+using msplat::TwoPassFeedback;
+using msplat::TwoPassFrame;
+static const TwoPassFrame kAutoFrame{MSPLAT_TWO_PASS_AUTO, true, true, 1u << 18, 0u, 1000u};
+static const TwoPassFeedback kNoFeedback{0u, 0u, 0u, 0u, 0u};
+// one Render the way occlusion_plan runs it: the buffers always fit, so every yes is committed
+static bool render(TwoPassController& c, const TwoPassFrame& f, const TwoPassFeedback& fb)
+{
+    const bool yes = c.decide(f, fb);
+    if (yes) c.commit();
+    return yes;
+}
+// feedback {pairs of pass 1, unfinished bins, pairs of pass 2} of two-pass frame `seq`, both passes in
+static TwoPassFeedback feedback(uint32_t seq, uint32_t pairs1, uint32_t pairs2, uint32_t unfinished) { return {pairs1, unfinished, pairs2, seq, seq}; }
+static float clamp_share(float s) { return std::min(msplat::kOccFracMax, std::max(msplat::kOccFracMin, s)); }
+static bool same_but_frame_count(const TwoPassController& a, const TwoPassController& b)
+{
+    return a.share == b.share && a.seq == b.seq && a.change_seq == b.change_seq && a.off == b.off && a.strikes == b.strikes &&
+           a.backoff == b.backoff && a.state == b.state && a.probe_left == b.probe_left && a.no_shrink == b.no_shrink &&
+           a.wait_frames == b.wait_frames && a.pinned == b.pinned;
+}
+
+static void controller_no_feedback()
+{
+    TwoPassController c;
+    for (uint32_t n = 1; n <= 1299; ++n) {
+        const bool yes = render(c, kAutoFrame, kNoFeedback);
+        const bool probe1 = n >= 9 && n <= 12, probe2 = n >= 1295 && n <= 1298;
+        EXPECT(yes == (probe1 || probe2));
+        if (probe1) EXPECT(c.share == 0.15f && c.seq == n - 8);
+        if (probe2) EXPECT(c.share == 0.15f && c.seq == n - 1290);
+        if (n == 13 || n == 269) EXPECT(c.state == TwoPassController::WAIT);
+        // the 257th waiting look: one pass again, the usual pause, not doubled
+        if (n == 270) EXPECT(c.state == TwoPassController::OFF && c.off == 1024u && c.backoff == 1024u && c.wait_frames == 0u);
+        if (n == 1294) EXPECT(c.state == TwoPassController::OFF && c.off == 0u);
+    }
+    EXPECT(c.frames_rendered == 1299u && c.state == TwoPassController::WAIT);
+}
+
+static void controller_good_feedback()
+{
+    TwoPassController c;
+    for (uint32_t n = 1; n <= 13; ++n) (void)render(c, kAutoFrame, kNoFeedback);
+    EXPECT(c.seq == 4u && c.state == TwoPassController::WAIT);
+    // frame 14: the probe's feedback, 10 % unfinished, pass 2 at 0.3 of pass 1: two passes stay on, the share as it is
+    EXPECT(render(c, kAutoFrame, feedback(4, 1000, 300, 100)));
+    EXPECT(c.state == TwoPassController::ON && c.share == 0.15f && c.seq == 5u && c.strikes == 0u && c.backoff == 1024u);
+    // pass 2 does most of the work: the share grows, and does not shrink for 32 looks
+    float share = clamp_share(0.15f * 1.25f);
+    EXPECT(render(c, kAutoFrame, feedback(c.seq, 1000, 700, 100)));
+    EXPECT(c.share == share && c.no_shrink == 32u && c.change_seq == c.seq);
+    // a snapshot of a frame older than the share is not evidence
+    EXPECT(render(c, kAutoFrame, feedback(c.seq - 1u, 1000, 700, 100)));
+    EXPECT(c.share == share && c.no_shrink == 32u);
+    // ... nor are words of two different frames, or a frame that binned nothing
+    EXPECT(render(c, kAutoFrame, TwoPassFeedback{1000u, 100u, 700u, c.seq, c.seq - 1u}));
+    EXPECT(render(c, kAutoFrame, feedback(c.seq, 0, 700, 100)));
+    EXPECT(c.share == share && c.no_shrink == 32u);
+    for (uint32_t look = 1; look <= 32; ++look) {
+        EXPECT(render(c, kAutoFrame, feedback(c.seq, 1000, 10, 100)));
+        EXPECT(c.share == share && c.no_shrink == 32u - look);
+    }
+    // nothing left for pass 2 (ratio < 0.02), then little (< 0.15), then enough (0.3)
+    EXPECT(render(c, kAutoFrame, feedback(c.seq, 1000, 10, 100)));
+    share = clamp_share(share * 0.75f);
+    EXPECT(c.share == share && c.change_seq == c.seq);
+    EXPECT(render(c, kAutoFrame, feedback(c.seq, 1000, 100, 100)));
+    share = clamp_share(share * 0.85f);
+    EXPECT(c.share == share);
+    EXPECT(render(c, kAutoFrame, feedback(c.seq, 1000, 300, 100)));
+    EXPECT(c.share == share);
+    // the clamps: [1 / 256, 0.75]
+    for (int look = 0; look < 64; ++look) {
+        EXPECT(render(c, kAutoFrame, feedback(c.seq, 1000, 10, 100)));
+        share = share > msplat::kOccFracMin ? clamp_share(share * 0.75f) : share;
+        EXPECT(c.share == share);
+    }
+    EXPECT(c.share == 1.0f / 256.0f);
+    for (int look = 0; look < 64; ++look) {
+        EXPECT(render(c, kAutoFrame, feedback(c.seq, 1000, 700, 100)));
+        share = clamp_share(share * 1.25f);
+        EXPECT(c.share == share);
+    }
+    EXPECT(c.share == 0.75f && c.state == TwoPassController::ON);
+}
+
+static void controller_strikes()
+{
+    TwoPassController c;
+    for (uint32_t n = 1; n <= 13; ++n) (void)render(c, kAutoFrame, kNoFeedback);
+    // frame 14: 40 % unfinished.  Strike one: a larger share, probed again
+    EXPECT(render(c, kAutoFrame, feedback(4, 1000, 300, 400)));
+    float share = clamp_share(0.15f * 1.5f);
+    EXPECT(c.strikes == 1u && c.share == share && c.state == TwoPassController::PROBE && c.seq == 5u && c.change_seq == 5u);
+    for (uint32_t n = 15; n <= 17; ++n) EXPECT(render(c, kAutoFrame, feedback(4, 1000, 300, 400)));
+    EXPECT(c.seq == 8u);
+    EXPECT(!render(c, kAutoFrame, feedback(4, 1000, 300, 400)));             // frame 18
+    EXPECT(c.state == TwoPassController::WAIT);
+    {
+        // frame 19 still sees frame 4, which ran with the old share: the wait goes on
+        TwoPassController stale = c;
+        EXPECT(!render(stale, kAutoFrame, feedback(4, 1000, 300, 400)));
+        EXPECT(stale.state == TwoPassController::WAIT && stale.wait_frames == 1u && stale.strikes == 1u && stale.share == share);
+    }
+    // frame 19 sees frame 8: strike two
+    EXPECT(render(c, kAutoFrame, feedback(8, 1000, 300, 400)));
+    share = clamp_share(share * 1.5f);
+    EXPECT(share == clamp_share(0.15f * 1.5f * 1.5f));
+    EXPECT(c.strikes == 2u && c.share == share && c.seq == 9u && c.change_seq == 9u);
+    for (uint32_t n = 20; n <= 22; ++n) EXPECT(render(c, kAutoFrame, kNoFeedback));
+    EXPECT(c.seq == 12u);
+    EXPECT(!render(c, kAutoFrame, kNoFeedback));                            // frame 23
+    // frame 24 sees frame 12: strike three, a pause of 1024 frames, the next one 2048
+    EXPECT(!render(c, kAutoFrame, feedback(12, 1000, 300, 400)));
+    EXPECT(c.state == TwoPassController::OFF && c.off == 1024u && c.backoff == 2048u && c.seq == 12u);
+    for (uint32_t n = 25; n <= 1048; ++n) EXPECT(!render(c, kAutoFrame, feedback(12, 1000, 300, 400)));
+    EXPECT(c.off == 0u);
+    EXPECT(render(c, kAutoFrame, feedback(12, 1000, 300, 400)));            // frame 1049
+    EXPECT(c.share == 0.15f && c.state == TwoPassController::PROBE && c.strikes == 0u && c.seq == 13u && c.backoff == 2048u);
+    // three more strikes: the pause that follows is 2048 frames, the next 4096; good feedback resets it
+    c.strikes = 2u; c.state = TwoPassController::ON;
+    EXPECT(!render(c, kAutoFrame, feedback(13, 1000, 300, 400)));
+    EXPECT(c.off == 2048u && c.backoff == 4096u);
+    c.off = 0u; c.backoff = 16384u;
+    for (int n = 0; n < 5; ++n) (void)render(c, kAutoFrame, kNoFeedback);   // four probe frames, then the wait
+    EXPECT(render(c, kAutoFrame, feedback(c.seq, 1000, 300, 100)));
+    EXPECT(c.state == TwoPassController::ON && c.backoff == 1024u);
+    c.strikes = 2u; c.backoff = 16384u;
+    EXPECT(!render(c, kAutoFrame, feedback(c.seq, 1000, 300, 400)));
+    EXPECT(c.off == 16384u && c.backoff == 16384u);                         // the pause stops doubling at 16384
+}
+
+static void controller_forced_and_idle()
+{
+    // forced ON: yes from frame 1, whatever the cloud's size and the frame mode
+    const TwoPassFrame on{MSPLAT_TWO_PASS_ON, true, false, 100u, 0u, 1000u};
+    TwoPassController c;
+    EXPECT(render(c, on, kNoFeedback) && c.seq == 1u && c.share == 0.15f);
+    EXPECT(render(c, on, feedback(1, 1000, 700, 100)));                     // fresh feedback steers
+    float share = clamp_share(0.15f * 1.25f);
+    EXPECT(c.share == share && c.seq == 2u);
+    c.pin(0.4f);                                                            // a pinned share is returned unchanged
+    EXPECT(render(c, on, feedback(2, 1000, 700, 100)) && c.share == 0.4f && c.pinned);
+    c.pin(0.0f);
+    EXPECT(!c.pinned && c.share == 0.4f);
+    c.no_shrink = 0u;
+    EXPECT(render(c, on, feedback(c.seq, 1000, 100, 100)) && c.share == clamp_share(0.4f * 0.85f));
+    // a decision that is not committed (the buffers did not fit): the frame number stays, the probe frame is spent
+    TwoPassController u;
+    for (uint32_t n = 1; n <= 8; ++n) (void)render(u, kAutoFrame, kNoFeedback);
+    EXPECT(u.decide(kAutoFrame, kNoFeedback) && u.seq == 0u && u.probe_left == 3u && u.change_seq == 1u);
+    u.seq = 0xFFFFFFFFu;
+    u.commit();
+    EXPECT(u.seq == 1u);                                                    // never 0
+    // OFF, an ineligible frame, a small cloud under AUTO, one frame at a time with few visible splats: no, and nothing moves
+    TwoPassFrame off = kAutoFrame, ineligible = kAutoFrame, small = kAutoFrame, serial = kAutoFrame;
+    off.mode = MSPLAT_TWO_PASS_OFF;
+    ineligible.eligible = false;
+    small.splats = (1u << 18) - 1u;
+    serial.in_flight = false;
+    serial.visible = msplat::kTwoPassMinVisibleSerial - 1u;
+    TwoPassFrame forced_ineligible = on;
+    forced_ineligible.eligible = false;
+    for (const TwoPassFrame& f : {off, ineligible, small, serial, forced_ineligible}) {
+        TwoPassController idle;
+        for (uint32_t n = 1; n <= 300; ++n) EXPECT(!render(idle, f, feedback(4, 1000, 300, 100)));
+        EXPECT(same_but_frame_count(idle, TwoPassController{}) && idle.frames_rendered == 300u);
+    }
+    serial.visible = msplat::kTwoPassMinVisibleSerial;                      // enough visible splats: the probe starts with frame 9
+    TwoPassController s;
+    for (uint32_t n = 1; n <= 9; ++n) EXPECT(render(s, serial, kNoFeedback) == (n == 9));
+    TwoPassFrame forced_serial = on;                                        // forced ON ignores the rule
+    forced_serial.visible = 1u;
+    EXPECT(render(s, forced_serial, kNoFeedback));
+}
+
 int main(int argc, char** argv)
 {
     if (argc < 3) {
@@ -353,6 +535,10 @@ int main(int argc, char** argv)
     ply_cases(golden);
     json_cases(golden);
     image_cases();
+    controller_no_feedback();
+    controller_good_feedback();
+    controller_strikes();
+    controller_forced_and_idle();
     // matrix helpers (closed forms; singular input must not trap under UBSan)
     float z[16] = {0}, o[16];
     msplat_mat4_inverse(z, o);
