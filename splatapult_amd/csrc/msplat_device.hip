@@ -120,6 +120,7 @@ struct AsyncWorker {
 constexpr uint32_t kFusedMaxChunks = 1u << 20;     // scan-free passes up to this many chunk rows: with the two-level group tables (r3) a
                                                // prefix is <= nchunks / 128 + 34 rows, so every table qualifies (r2, one level: 8192 rows,
                                                // beyond that the radix_scan kernels)
+constexpr uint32_t kGridCap = 256u * 8u;           // most workgroups of a grid-stride launch (grid_for): 256 CUs x 8
 
 // Slots of a timing-event set (msplat_ctx::ev).  The compositor's pair is the exact dispatch begin / end of the kernel
 // (hipExtLaunchKernelGGL); kEvPass2*: the second pass of a two-pass frame -- after the first compositor, after gate and projection,
@@ -177,6 +178,7 @@ struct msplat_ctx {
     Buf heavy, heavy_flag;      // column pass: chunks with far more pairs than the others are split over several workgroups
     uint32_t render_parity = 0;
     bool scan_free = true;  // MSPLAT_SCAN_KERNELS=1 forces the 3-kernel (upsweep, scan, downsweep) passes
+    uint32_t grid_cap = kGridCap;   // grid_for's limit; MSPLAT_GRID_CAP=1..2048 lowers it (debug switch: the chunk loops take several turns)
     Buf totals;     // uint32[256]  digit totals of the current radix pass (rows in binning pass 2)
     Buf totals1;    // uint32[256]  column totals of binning pass 1
     Buf counters;   // uint32[kCounterCount]: Counter, msplat_common.hip.h
@@ -318,10 +320,9 @@ inline uint32_t div_up(uint64_t a, uint64_t b) { return (uint32_t)((a + b - 1) /
 constexpr size_t kProbeWords = 8;                                           // per compositor work item
 constexpr size_t kProbeBytes = (size_t)65536 * 8 * kProbeWords * sizeof(uint32_t);   // 256x256 bins x 4 quadrants x 2 halves
 
-int grid_for(uint32_t nchunks)
+int grid_for(uint32_t nchunks, uint32_t cap)
 {
-    // grid-stride kernels: enough workgroups to fill 256 CUs x 8, never more than the chunk count
-    const uint32_t cap = 256u * 8u;
+    // grid-stride kernels: enough workgroups to fill 256 CUs x 8, never more than the chunk count (cap = msplat_ctx::grid_cap)
     return (int)std::max(1u, std::min(nchunks, cap));
 }
 
@@ -494,6 +495,8 @@ int msplat_create(msplat_ctx** out, const msplat_config* cfg)
         ctx->wide_sort = true;
         ctx->ws_threads = c.frame_mode == MSPLAT_FRAMES_IN_FLIGHT ? (uint32_t)kWsThreadsSmall : (uint32_t)kWsThreads;
         if (const char* sk = getenv("MSPLAT_SORT")) ctx->wide_sort = std::string(sk) != "lsd8";
+        // debug switch: fewer workgroups than chunks, so that the chunk loops of the sort's and the binning's kernels take several turns
+        if (const char* gc = getenv("MSPLAT_GRID_CAP")) ctx->grid_cap = (uint32_t)std::min(std::max(atol(gc), 1L), (long)kGridCap);
         if (!ctx->atomic_rank) ctx->wide_sort = false;       // the wide kernels rank with lane-ordered LDS atomics only
         ctx->spatial_mode = c.spatial_order;
         if (ctx->wide_sort) {
@@ -997,7 +1000,7 @@ static int issue_sort(msplat_ctx* ctx, const FrameParams& fp)
     // chunk size by cloud size (msplat_common.hip.h, kSortItems): 2048 keys up to 2 M splats, 4096 beyond
     const bool large = ctx->N > (2u << 20);
     const uint32_t chunk = (uint32_t)kThreads * (large ? kSortItemsLarge : kSortItems);
-    const int grid = grid_for(div_up(N, chunk));
+    const int grid = grid_for(div_up(N, chunk), ctx->grid_cap);
 
     if (ctx->tables_dirty) {
         int rc = clear_frame_tables(ctx);
@@ -1027,7 +1030,7 @@ static int issue_sort(msplat_ctx* ctx, const FrameParams& fp)
         const LiveBoxes lb = list_live_boxes(ctx, fp, last_V);       // (launches box_cull_kernel when the view is a partial one)
         // pass 0 over listed boxes: fewer chunks than the cloud has, so 4096-key chunks keep the CUs covered (as for passes 1, 2)
         uint32_t items = lb.list != nullptr ? 8u : items0;
-        int wgrid = grid_for(div_up(N, ctx->ws_threads * items));
+        int wgrid = grid_for(div_up(N, ctx->ws_threads * items), ctx->grid_cap);
         const uint32_t* dV = d_V;
         auto upsweep = [&](auto CULL, const auto&... args) {
             // The upsweeps have no order to keep.  One frame at a time and 4096-key chunks (up to 2 M splats): twice the threads per
@@ -1054,7 +1057,7 @@ static int issue_sort(msplat_ctx* ctx, const FrameParams& fp)
                   (const uint32_t*)nullptr, N, N, 0, (const uint32_t*)mk_cur, (const uint32_t*)whist, (const uint32_t*)gt(0), gsh, kA, vA,
                   d_V, lb);
         items = items12;
-        wgrid = grid_for(div_up(N, ctx->ws_threads * items));
+        wgrid = grid_for(div_up(N, ctx->ws_threads * items), ctx->grid_cap);
         for (int pass = 1; pass < 3; ++pass) {
             uint32_t *kin = pass == 1 ? kA : kB, *vin = pass == 1 ? vA : vB, *kout = pass == 1 ? kB : kA, *vout = pass == 1 ? vB : vA;
             upsweep(int_t<0>{}, (const uint32_t*)kin, (const float4*)nullptr, (uint32_t*)nullptr,
@@ -1252,7 +1255,7 @@ static void issue_binning(RenderChain& rc, int keep_overflow, int occ_pass)
     uint32_t* totals1 = (uint32_t*)ctx->totals1.p;
     uint32_t* totals2 = (uint32_t*)ctx->totals.p;
     const uint32_t bchunk = (uint32_t)kBinChunk;
-    const int g1 = grid_for(div_up(N, bchunk));
+    const int g1 = grid_for(div_up(N, bchunk), ctx->grid_cap);
     // heavy chunks of the column pass (bin1_upsweep): list per frame parity, helper workgroups in front of the downsweep's grid
     uint32_t* hv_cur = (uint32_t*)ctx->heavy.p + (ctx->render_parity & 1u) * (1u + kHeavyCap);
     uint32_t* hv_next = (uint32_t*)ctx->heavy.p + ((ctx->render_parity ^ 1u) & 1u) * (1u + kHeavyCap);
@@ -1308,7 +1311,7 @@ static void issue_binning(RenderChain& rc, int keep_overflow, int occ_pass)
     // searched the offsets in the partitioned array with a kernel of their own, 1 % faster then; equal in r6 under the CU halves
     // -- 6290 / 6298, 2478-2514 / 2485-2494, 1363-1403 / 1384-1403 frames/s at 1 M, 6 M, 6 M / 4096^2 -- and removed: one launch less.)
     uint32_t* bincnt = (uint32_t*)ctx->bincnt.p;
-    const int g2 = grid_for(div_up(cap, kPairChunk));
+    const int g2 = grid_for(div_up(cap, kPairChunk), ctx->grid_cap);
     hipLaunchKernelGGL(radix_upsweep<MODE_PAIR>, dim3(g2), dim3(kThreads), 0, s, (const uint32_t*)ctx->pairsA.p,
                        nullptr, d_D, 0u, cap, 24, (uint32_t*)ctx->hist2.p, ctx->hist2_stride, fused2 ? gB2 : nullptr, gB1,
                        ctx->gsumB1_rows, fp, (const uint32_t*)totals1, bincnt, ctx->gsupB2);

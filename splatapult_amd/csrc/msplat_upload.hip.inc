@@ -181,7 +181,7 @@ static int spatial_reorder(msplat_ctx* ctx)
     hipLaunchKernelGGL(morton_kernel, dim3(div_up(N, kThreads)), dim3(kThreads), 0, s, pos, N, (const double*)acc, kA, vA);
     const bool large = n64 > (2u << 20);
     const uint32_t chunk = (uint32_t)kThreads * (large ? kSortItemsLarge : kSortItems);
-    const int grid = grid_for(div_up(N, chunk));
+    const int grid = grid_for(div_up(N, chunk), ctx->grid_cap);
     FrameParams fp0;
     std::memset(&fp0, 0, sizeof(fp0));
     uint32_t* hist = (uint32_t*)ctx->hist.p;
