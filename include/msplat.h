@@ -40,7 +40,6 @@ enum { MSPLAT_RANK_AUTO = 0, MSPLAT_RANK_BALLOT = 1 };                          
 enum { MSPLAT_CU_ALL = 0, MSPLAT_CU_EVEN = 1, MSPLAT_CU_ODD = 2 };   /* msplat_config.cu_partition: every CU, or the even / odd CU positions of every XCD (4 frames in flight alternate: +3-5 %, INTEGRATION 6) */
 enum { MSPLAT_TARGET_CLEAR = 0, MSPLAT_TARGET_LOAD = 1, MSPLAT_TARGET_PREMULTIPLIED = 2 };   /* msplat_set_target_mode */
 enum { MSPLAT_BANDS_CONTIGUOUS = 0, MSPLAT_BANDS_INTERLEAVED = 1, MSPLAT_BANDS_BLOCK_INTERLEAVED = 2, MSPLAT_BANDS_ROOT_WEIGHTED = 3 };
-
 typedef struct msplat_ctx msplat_ctx;
 typedef struct msplat_cloud msplat_cloud;
 typedef struct msplat_group msplat_group;
@@ -100,7 +99,6 @@ void msplat_destroy(msplat_ctx* ctx);
 const char* msplat_last_error(const msplat_ctx* ctx);   /* ctx may be NULL: global last error */
 const char* msplat_version_string(void);
 int msplat_tile_size(void);                             /* edge of the square screen bins (pixels) band rows refer to */
-
 /* ---- upload: SplatRenderer::Init + BuildVertexArrayObject (splatrenderer.cpp:50-151,345-391).  Copies the interleaved
  * cloud (host memory, n records of stride_bytes) to the device; the caller may free it afterwards. */
 int msplat_upload_cloud(msplat_ctx* ctx, const void* aos, uint64_t n, uint32_t stride_bytes, const msplat_attr_offsets* off, int full_sh);
@@ -128,12 +126,10 @@ enum { MSPLAT_STORAGE_FP32 = 0, MSPLAT_STORAGE_SH_FP16 = 1 };
 enum { MSPLAT_STORAGE_SH_Q8 = 3 };
 int msplat_set_cloud_storage(msplat_ctx* ctx, int32_t storage);
 int msplat_get_cloud_storage(const msplat_ctx* ctx);
-
 /* ---- SplatRenderer::Sort (splatrenderer.cpp:153-312): cull + depth key (presort_compute.glsl:31-57), stable ascending 32-bit
  * radix sort; the sorted index list stays context state for the following renders.  Asynchronous: the reference's 4-byte
  * readback stall (splatrenderer.cpp:195-204) is not reproduced. */
 int msplat_sort(msplat_ctx* ctx, const float cameraMat[16], const float projMat[16], const float viewport[4], const float nearFar[2]);
-
 /* ---- SplatRenderer::Render (splatrenderer.cpp:315-343) plus the GL pipeline behind its glDrawElements: splat_vert / _geom / _frag.glsl and
  * the blend / clear state of app.cpp:144-164.  Writes W x H RGBA (float, half or 4 bytes), row 0 = GL bottom row, alpha = 1 (msplat_set_target_mode: or
  * over the target's contents).  out_is_device != 0: `rgba` is device memory, the call is asynchronous on the stream; else host memory, the
@@ -153,6 +149,10 @@ int msplat_render(msplat_ctx* ctx, const float cameraMat[16], const float projMa
  * (call per eye), the device group, msplat_band_exchange of the plane. */
 int msplat_render_depth(msplat_ctx* ctx, const float cameraMat[16], const float projMat[16], const float viewport[4], const float nearFar[2],
                         void* rgba, uint64_t pitch_bytes, float* depth, uint64_t depth_pitch_bytes, int out_is_device);
+/* ---- msplat_render behind the caller's geometry (INTEGRATION.md 16): GL_LESS as app.cpp:160-163 sets it.  occluder == NULL: msplat_render.  Else W x H float32 window depths (the plane msplat_render_depth writes), row 0 = GL bottom, occluder_pitch_bytes between rows (0 = tight; else >= 4 W and a multiple of 4, or _INVALID_ARG), in `rgba`'s memory space, read-only.
+ * Per pixel p: msplat_render's frame with every splat i with !(z_i < occluder[p]) absent at p; z_i = 0.5 ndc.z + 0.5, one per splat (splat_geom.glsl:98).  A splat AT the plane's depth is hidden; NaN hides everything at its pixel; +inf or any value above 1 nothing.  Formats, target modes (LOAD: a pixel no surviving splat reaches keeps its bits), banded contexts (owned rows of the plane), pitches, host output and its retry, frames in flight, two-pass frames: msplat_render's.
+ * Device output, also with async_submit: the plane must stay valid and unchanged until the frame has run.  MSPLAT_ERR_UNSUPPORTED (the context stays usable): a point cloud, msplat_set_depth_test, a target emulation, the tile probe.  Out of scope: msplat_render_stereo (call per eye), the device group, msplat_render_depth's output in the same frame, seeding msplat_set_depth_test's emulated depth buffer. */
+int msplat_render_occluded(msplat_ctx* ctx, const float cameraMat[16], const float projMat[16], const float viewport[4], const float nearFar[2], void* rgba, uint64_t pitch_bytes, const float* occluder, uint64_t occluder_pitch_bytes, int out_is_device);
 /* the reference's VR frame -- Sort with the first eye, Render per eye (app.cpp:603-607) -- as ONE chain of launches; the same pixels as two msplat_render calls, bit for bit.  Host targets, banded contexts, points and the emulations go view by view. */
 int msplat_render_stereo(msplat_ctx* ctx, const float cameraMat0[16], const float projMat0[16], const float cameraMat1[16],
                          const float projMat1[16], const float viewport[4], const float nearFar[2], void* rgba0, void* rgba1,

@@ -75,6 +75,15 @@ constexpr int kCompOcc = 5;        // occupancy bound handed to the compiler (<=
 // depth_bits = 32: the float's bits).  z rides in the free word of the staged record, the inner loop gains one packed FMA per strip pair
 // and the final store writes the plane next to the colour, same lane, once.  DEPTH = false: the code of every instantiation that existed
 // before the parameter.
+// ZTEST (msplat_render_occluded): GL_LESS against a caller's W x H float32 plane of window depths (app.cpp:160-163: the reference draws its
+// geometry first and blends the splats over it under GL_DEPTH_TEST).  Splat i -- one z_i per splat, as for DEPTH, in the same free word of the
+// staged record -- is absent from pixel p unless z_i < plane[p].  Each lane keeps the plane's value of its four pixels (closed = -inf: outside
+// the image, or NaN), the wave their maximum: a record with !(z < max) is dropped at staging (which moves no batch boundary: the two-pass cut
+// stays where it is), and in the inner loop the weight of a pixel with !(z < plane) becomes an exact 0 -- a compare and a select per pixel after
+// the v_exp_f32; a zero weight is an exact no-op on every accumulator, as for the discard by underflow.  A tile without an open pixel goes
+// straight to its final store.  Pass 2 of a two-pass frame re-reads the plane: no new per-pixel state.  (Built and removed before any measurement: a second,
+// untested copy of the loop chosen per batch by a scalar branch when every staged record lies in front of the tile's MINIMUM -- two pass-1
+// instantiations then spilled VGPRs into scratch, EXPERIMENTS.md round 14.)  ZTEST = false: the code of every instantiation that existed before the parameter.
 constexpr int kTargetClear = 0, kTargetLoad = 1, kTargetPremultiplied = 2;      // MSPLAT_TARGET_* (include/msplat.h)
 struct CompExtra {
     void* out1;                  // TWO_VIEWS: the second view's target (bin rows >= rows_view belong to it)
@@ -86,9 +95,11 @@ struct CompExtra {
     float* depth;                // DEPTH: the depth plane, rows of depth_pitch bytes (row 0 = GL bottom, like the colour)
     size_t depth_pitch;
     float* zstate;               // DEPTH, OCC != 0: the depth accumulator per pixel, beside `state`
+    const float* occluder;       // ZTEST: the plane of window depths the splats are tested against (zw as for DEPTH), rows of occluder_pitch bytes
+    size_t occluder_pitch;
 };
 
-template <int FMT, int OCC, bool TWO_VIEWS, bool PROBE, int TM = kTargetClear, bool DEPTH = false>
+template <int FMT, int OCC, bool TWO_VIEWS, bool PROBE, int TM = kTargetClear, bool DEPTH = false, bool ZTEST = false>
 __global__ __launch_bounds__(kCompThreads, kCompOcc) void composite_kernel(const uint32_t* __restrict__ tile_start,
                                                                  const uint32_t* __restrict__ pairs,
                                                                  const float4* __restrict__ rec,
@@ -196,6 +207,15 @@ __global__ __launch_bounds__(kCompThreads, kCompOcc) void composite_kernel(const
     }
 #pragma unroll
     for (int k = 0; k < NS; ++k) inside[k] = (x < fp.width) && (ybase + 4 * k < fp.height);
+    v2f zp[NP];                                      // ZTEST only: the plane at the lane's pixels, -inf where nothing passes
+    if (ZTEST) {
+#pragma unroll
+        for (int k = 0; k < NS; ++k) {
+            float v = -__builtin_inff();
+            if (inside[k]) v = ((const float*)((const char*)ex.occluder + (size_t)(ybase + 4 * k) * ex.occluder_pitch))[x];
+            zp[k >> 1][k & 1] = v == v ? v : -__builtin_inff();      // NaN: closed
+        }
+    }
     if (occ_pass == 2) {
 #pragma unroll
         for (int k = 0; k < NS; ++k) {
@@ -240,11 +260,20 @@ __global__ __launch_bounds__(kCompThreads, kCompOcc) void composite_kernel(const
         asm volatile("" : "+v"(rk));              // keep the mask out of the address arithmetic (see composite_depth_kernel)
         const float4* src = rec + (size_t)rk * 3;
         p0 = src[0]; p1 = src[1]; p2 = src[2];
-        if (DEPTH) pz = ex.zw[rk];
+        if (DEPTH || ZTEST) pz = ex.zw[rk];
     }
     cntA = min((uint32_t)kCompThreads, hiA - start);
     if (lane < (int)cntA) rankA = pairs[hiA - 1u - lane];
     hiA -= cntA;
+    float tile_zmax = 0.0f;                                    // ZTEST: the most distant plane value of the tile
+    if (ZTEST) {
+        // (here, behind the first record loads: the plane's loads were issued before them and the reduction waits for those alone)
+        tile_zmax = fmaxf(fmaxf(zp[0].x, zp[0].y), fmaxf(zp[1].x, zp[1].y));
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) tile_zmax = fmaxf(tile_zmax, __shfl_xor(tile_zmax, d, 64));
+        tile_zmax = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, tile_zmax)));
+        if (!(tile_zmax > 0.0f)) alive = 0;                    // z_w >= 0: no splat passes anywhere in the tile
+    }
     const uint64_t probe_t0 = PROBE ? clock64() : 0ull;
     uint32_t probe_n = 0, probe_batches = 0, probe_useful = 0;      // probe_useful: (pixel, record) evaluations with w > 0
     uint64_t probe_inner = 0;
@@ -299,6 +328,7 @@ __global__ __launch_bounds__(kCompThreads, kCompOcc) void composite_kernel(const
                 emax = fmaxf(fmaxf(ep, em), fmaxf(fp_, fm_));
             }
             rel = rel && (inside_box || emax > -8.05f - kBias);
+            if (ZTEST) rel = rel && pz < tile_zmax;                  // behind the whole tile's plane
             const uint64_t relmask = __ballot(rel);
             n = (uint32_t)__popcll(relmask);
             if (rel) {
@@ -307,7 +337,7 @@ __global__ __launch_bounds__(kCompThreads, kCompOcc) void composite_kernel(const
                 // land in even VGPRs, which a packed operand can name directly (an odd one costs a v_mov)
                 s_rec[slot * 3 + 0] = make_float4(qc, c0, p1.z, c1);
                 s_rec[slot * 3 + 1] = make_float4(p1.w, c2, p2.x, qa);
-                s_rec[slot * 3 + 2] = make_float4(qb, DEPTH ? pz : 0.0f, 0.0f, 0.0f);
+                s_rec[slot * 3 + 2] = make_float4(qb, DEPTH || ZTEST ? pz : 0.0f, 0.0f, 0.0f);
             }
         }
         __syncthreads();
@@ -317,7 +347,7 @@ __global__ __launch_bounds__(kCompThreads, kCompOcc) void composite_kernel(const
             asm volatile("" : "+v"(rk));
             const float4* src = rec + (size_t)rk * 3;
             p0 = src[0]; p1 = src[1]; p2 = src[2];
-            if (DEPTH) pz = ex.zw[rk];
+            if (DEPTH || ZTEST) pz = ex.zw[rk];
         }
         cntA = min((uint32_t)kCompThreads, hiA - start);
         if (lane < (int)cntA) rankA = pairs[hiA - 1u - lane];
@@ -331,14 +361,14 @@ __global__ __launch_bounds__(kCompThreads, kCompOcc) void composite_kernel(const
             float4 a = s_rec[0];          // c5, c0, r, c1
             float4 b = s_rec[1];          // g, c2, b, c3
             float c4 = s_rec[2].x;
-            float z = DEPTH ? s_rec[2].y : 0.0f;
+            float z = DEPTH || ZTEST ? s_rec[2].y : 0.0f;
 #pragma unroll 2
             for (uint32_t j = 0; j < n; ++j) {
                 // next record (slot n is a harmless over-read inside the 65-slot array)
                 const float4 na = s_rec[(j + 1) * 3 + 0];
                 const float4 nb = s_rec[(j + 1) * 3 + 1];
                 const float nc4 = s_rec[(j + 1) * 3 + 2].x;
-                const float nz = DEPTH ? s_rec[(j + 1) * 3 + 2].y : 0.0f;
+                const float nz = DEPTH || ZTEST ? s_rec[(j + 1) * 3 + 2].y : 0.0f;
                 const float base = __builtin_fmaf(__builtin_fmaf(b.w, u, a.w), u, a.y);      // c0 + c1 u + c3 u^2
                 const float lin = __builtin_fmaf(c4, u, b.y);                                // c2 + c4 u
                 const v2f vbase = (v2f){base, base}, vlin = (v2f){lin, lin}, vC = (v2f){a.x, a.x};
@@ -353,6 +383,10 @@ __global__ __launch_bounds__(kCompThreads, kCompOcc) void composite_kernel(const
                     v2f w;           // discard by underflow (see the kernel's header)
                     w.x = __builtin_amdgcn_exp2f(e.x);
                     w.y = __builtin_amdgcn_exp2f(e.y);
+                    if (ZTEST) {     // GL_LESS against the plane: the fragment is not blended
+                        w.x = z < zp[h].x ? w.x : 0.0f;
+                        w.y = z < zp[h].y ? w.y : 0.0f;
+                    }
                     if (PROBE) probe_useful += (w.x > 0.0f ? 1u : 0u) + (w.y > 0.0f ? 1u : 0u);      // per lane; summed over the wave at the end
                     const v2f tw = T[h] * w;
                     cr[h] = __builtin_elementwise_fma(tw, vr, cr[h]);

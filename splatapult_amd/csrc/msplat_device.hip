@@ -206,6 +206,7 @@ struct msplat_ctx {
     uint32_t hist2_stride = 0;
     Buf fb;         // internal framebuffer for host-output renders
     Buf fbz;        // ... and their depth plane (msplat_render_depth): float[W * H]
+    Buf fbo;        // ... and the caller's occluder plane (msplat_render_occluded), staged once per call: float[W * H]
     Buf probe;      // uint32[8 * work items] compositor probe (msplat_set_tile_probe)
     bool probe_on = false;
     // device-output renders never synchronise: a pair-buffer overflow is left in host-mapped memory by the
@@ -963,7 +964,7 @@ static int with_pending_overflow(msplat_ctx* ctx, Work&& work)
 static int sort_impl(msplat_ctx* ctx, const float cameraMat[16], const float projMat[16], const float viewport[4], const float nearFar[2]);
 static int render_impl(msplat_ctx* ctx, const float cameraMat[16], const float projMat[16], const float viewport[4],
                        const float nearFar[2], void* rgba, uint64_t pitch_bytes, int out_is_device, float* depth = nullptr,
-                       uint64_t depth_pitch_bytes = 0);
+                       uint64_t depth_pitch_bytes = 0, const float* occluder = nullptr, uint64_t occluder_pitch_bytes = 0);
 
 int msplat_sort(msplat_ctx* ctx, const float cameraMat[16], const float projMat[16],
                 const float viewport[4], const float nearFar[2])
@@ -1181,6 +1182,8 @@ struct RenderChain {
     bool async_overflow_flag;
     float* d_depth;              // msplat_render_depth: the depth plane (NULL: a plain Render) and its pitch
     size_t depth_pitch;
+    const float* d_occluder;     // msplat_render_occluded: the plane the splats are depth-tested against (NULL: none) and its pitch
+    size_t occluder_pitch;
     // the compositor's schedule, decided where the bins are ordered (issue_binning) and used by issue_compositor
     bool ordered = true;
     uint32_t comp_items = 0, comp_pool = 0;
@@ -1202,9 +1205,9 @@ static void issue_projection(RenderChain& rc, int mode, float occ_frac)
     }
     ProjParams pp = proj_params(fp);
     uint32_t* zq = (mode != PROJ_LISTED && ctx->depth_bits) ? (uint32_t*)ctx->zq.p : nullptr;
-    if (rc.d_depth) {
-        // a depth frame: every projection of the frame leaves z_w = (float)(0.5 ndc.z + 0.5) per rank -- quantise_depth's 32-bit form
-        // is that float's bits (one product by 0.5, exact, and one rounded sum)
+    if (rc.d_depth || rc.d_occluder) {
+        // a depth frame, or one tested against an occluder plane: every projection of the frame leaves z_w = (float)(0.5 ndc.z + 0.5)
+        // per rank -- quantise_depth's 32-bit form is that float's bits (one product by 0.5, exact, and one rounded sum)
         pp.depth_bits = 32;
         zq = (uint32_t*)ctx->zq.p;
     }
@@ -1404,38 +1407,43 @@ static int issue_compositor(RenderChain& rc, int occ_pass, int ev_c0, int ev_c1)
         const int grid = (int)std::min<uint32_t>(comp_items, comp_pool);
         const CompParams cp = comp_params(fp);
         const CompExtra ex{d_out1, fin, state, d_nbins, probe, (const float*)ctx->zq.p, rc.d_depth, rc.depth_pitch,
-                           occ_pass ? (float*)ctx->occ_zstate.p : nullptr};
+                           occ_pass ? (float*)ctx->occ_zstate.p : nullptr, rc.d_occluder, rc.occluder_pitch};
         const int prio = occ_pass == 2 ? 0 : prio_mode;
         // six of the twelve (OCC, TWO_VIEWS, PROBE) forms exist per format
         // (occlusion_plan never chooses two passes for two views in one chain or while the probe is on)
         // and the four without the probe once more per non-CLEAR target mode (render_frame refuses the probe with those);
-        // a depth frame (one view, no probe: render_impl) has the three passes per target mode
-        auto composite = [&](auto OCC, auto TWO, auto PROBE, auto TM, auto DEPTH) {
+        // a depth frame (one view, no probe: render_impl) has the three passes per target mode, and so has an occluded frame
+        auto composite = [&](auto OCC, auto TWO, auto PROBE, auto TM, auto DEPTH, auto ZTEST) {
             with_format([&](auto FMT) {
-                hipExtLaunchKernelGGL((composite_kernel<FMT.value, OCC.value, TWO.value, PROBE.value, TM.value, DEPTH.value>), dim3(grid),
-                                      dim3(kCompThreads), 0, s, e0, e1, 0, ts, pb, r2, d_out, pitch, cp, cap, ord, d_queue, comp_items, prio, ex);
+                hipExtLaunchKernelGGL((composite_kernel<FMT.value, OCC.value, TWO.value, PROBE.value, TM.value, DEPTH.value, ZTEST.value>),
+                                      dim3(grid), dim3(kCompThreads), 0, s, e0, e1, 0, ts, pb, r2, d_out, pitch, cp, cap, ord, d_queue,
+                                      comp_items, prio, ex);
             });
         };
         constexpr flag_t<true> yes{};
         constexpr flag_t<false> no{};
         constexpr int_t<kTargetClear> clear{};
-        if (rc.d_depth)
+        if (rc.d_occluder)
             with_int<kTargetLoad, kTargetPremultiplied, kTargetClear>(ctx->target_mode, [&](auto TM) {
-                with_int<1, 2, 0>(occ_pass, [&](auto OCC) { composite(OCC, no, no, TM, yes); });
+                with_int<1, 2, 0>(occ_pass, [&](auto OCC) { composite(OCC, no, no, TM, no, yes); });
+            });
+        else if (rc.d_depth)
+            with_int<kTargetLoad, kTargetPremultiplied, kTargetClear>(ctx->target_mode, [&](auto TM) {
+                with_int<1, 2, 0>(occ_pass, [&](auto OCC) { composite(OCC, no, no, TM, yes, no); });
             });
         else if (ctx->target_mode != MSPLAT_TARGET_CLEAR)
             with_int<kTargetLoad, kTargetPremultiplied>(ctx->target_mode, [&](auto TM) {
-                if (occ_pass == 1) composite(int_t<1>{}, no, no, TM, no);
-                else if (occ_pass == 2) composite(int_t<2>{}, no, no, TM, no);
-                else if (stereo) composite(int_t<0>{}, yes, no, TM, no);
-                else composite(int_t<0>{}, no, no, TM, no);
+                if (occ_pass == 1) composite(int_t<1>{}, no, no, TM, no, no);
+                else if (occ_pass == 2) composite(int_t<2>{}, no, no, TM, no, no);
+                else if (stereo) composite(int_t<0>{}, yes, no, TM, no, no);
+                else composite(int_t<0>{}, no, no, TM, no, no);
             });
-        else if (occ_pass == 1) composite(int_t<1>{}, no, no, clear, no);
-        else if (occ_pass == 2) composite(int_t<2>{}, no, no, clear, no);
-        else if (stereo && probe) composite(int_t<0>{}, yes, yes, clear, no);
-        else if (stereo) composite(int_t<0>{}, yes, no, clear, no);
-        else if (probe) composite(int_t<0>{}, no, yes, clear, no);
-        else composite(int_t<0>{}, no, no, clear, no);
+        else if (occ_pass == 1) composite(int_t<1>{}, no, no, clear, no, no);
+        else if (occ_pass == 2) composite(int_t<2>{}, no, no, clear, no, no);
+        else if (stereo && probe) composite(int_t<0>{}, yes, yes, clear, no, no);
+        else if (stereo) composite(int_t<0>{}, yes, no, clear, no, no);
+        else if (probe) composite(int_t<0>{}, no, yes, clear, no, no);
+        else composite(int_t<0>{}, no, no, clear, no, no);
         ctx->comp_kernel_timed = timed;
     } else {
         ctx->comp_kernel_timed = false;
@@ -1472,8 +1480,15 @@ struct DepthPlane {
     size_t pitch = 0;
 };
 
+// the plane of window depths a msplat_render_occluded frame is tested against, in device memory (p == NULL: no test); read-only
+struct OccluderPlane {
+    const float* p = nullptr;
+    size_t pitch = 0;
+};
+
 static int launch_render(msplat_ctx* ctx, const FrameParams& fp, void* d_out, size_t pitch, bool async_overflow_flag,
-                         void* d_out1 = nullptr, RenderPlan* plan = nullptr, DepthPlane depth = DepthPlane{})
+                         void* d_out1 = nullptr, RenderPlan* plan = nullptr, DepthPlane depth = DepthPlane{},
+                         OccluderPlane occluder = OccluderPlane{})
 {
     hipStream_t s = ctx->stream;
     const bool stereo = fp.views == 2;
@@ -1481,7 +1496,8 @@ static int launch_render(msplat_ctx* ctx, const FrameParams& fp, void* d_out, si
     const uint32_t N = stereo ? (uint32_t)(2 * ctx->N + 64) : (uint32_t)ctx->N;
     RenderChain rc{ctx, fp, s, stereo, N, counters + kCntV, counters + kCntD, counters + kCntOverflow, (uint32_t*)ctx->queue.p,
                    stereo ? counters + kCntVframe2 : counters + kCntV, (uint32_t*)ctx->occ.p, fp.tiles_x * fp.tiles_y, (uint32_t)ctx->pair_cap,
-                   false, 0, (int)std::max(1u, div_up(N, kProjThreads)), d_out, d_out1, pitch, async_overflow_flag, depth.p, depth.pitch};
+                   false, 0, (int)std::max(1u, div_up(N, kProjThreads)), d_out, d_out1, pitch, async_overflow_flag, depth.p, depth.pitch,
+                   occluder.p, occluder.pitch};
     // Two-pass frame with occlusion feedback (msplat_occlusion.hip.h): the nearest R1 splats first, then only what the bins
     // they did not saturate still need.  Same pixels; chosen once per Render (occlusion_plan).  The retries of a host-output
     // frame whose pair buffer overflowed reuse the plan AND count as the same Render: the sampling counter, the two-pass
@@ -1495,11 +1511,11 @@ static int launch_render(msplat_ctx* ctx, const FrameParams& fp, void* d_out, si
         ctx->render_calls++;
     }
     const bool two_pass = plan->two_pass;
-    if (depth.p) {
-        // z_w per rank; the accumulator plane two passes hand over.  (A buffer that has to grow is freed first: hipFree waits for the
+    if (depth.p || occluder.p) {
+        // z_w per rank; (depth) the accumulator plane two passes hand over.  (A buffer that has to grow is freed first: hipFree waits for the
         // frames that still read it.)
         int arc = buf_alloc(ctx, ctx->zq, std::max<uint64_t>(std::max(ctx->rank_cap, ctx->N), 1) * 4);
-        if (!arc && two_pass) arc = buf_alloc(ctx, ctx->occ_zstate, (size_t)fp.width * fp.height * 4 + 64);
+        if (!arc && two_pass && depth.p) arc = buf_alloc(ctx, ctx->occ_zstate, (size_t)fp.width * fp.height * 4 + 64);
         if (arc) return arc;
     }
     const bool timed = rc.timed = ctx->ev_ok && ((ctx->render_calls - 1) % ctx->timing_stride) == 0;
@@ -1563,6 +1579,18 @@ int msplat_render_depth(msplat_ctx* ctx, const float cameraMat[16], const float 
                         });
 }
 
+// msplat_render with GL_LESS against a caller's plane of window depths (include/msplat.h); occluder == NULL is msplat_render
+int msplat_render_occluded(msplat_ctx* ctx, const float cameraMat[16], const float projMat[16], const float viewport[4],
+                           const float nearFar[2], void* rgba, uint64_t pitch_bytes, const float* occluder,
+                           uint64_t occluder_pitch_bytes, int out_is_device)
+{
+    return submit_frame<false>(ctx, out_is_device && rgba, cameraMat, projMat, cameraMat, projMat, viewport, nearFar,
+                        [=](const float* cam, const float* proj, const float*, const float*, const float* vp, const float* nf) {
+                            return render_impl(ctx, cam, proj, vp, nf, rgba, pitch_bytes, out_is_device, nullptr, 0, occluder,
+                                               occluder_pitch_bytes);
+                        });
+}
+
 // rows of the target: 0 = tightly packed (`tight` bytes)
 static int resolve_pitch(msplat_ctx* ctx, const char* who, const FrameParams& fp, uint64_t& pitch_bytes, size_t& tight)
 {
@@ -1605,19 +1633,26 @@ static int copy_host_rows(msplat_ctx* ctx, const FrameParams& fp, void* rgba, ui
 // host output: render into an internal device framebuffer, copy back, grow the pair buffer on overflow.
 // depth (msplat_render_depth): a host plane of depth.pitch bytes per row, filled the same way from ctx->fbz -- every attempt writes
 // the whole internal plane, and the rows are copied after the one that did not overflow
-static int render_to_host(msplat_ctx* ctx, const FrameParams& fp, void* rgba, uint64_t pitch_bytes, size_t tight, DepthPlane depth)
+// occluder (msplat_render_occluded): the caller's host plane, staged into ctx->fbo once -- it is only read, so a retry reuses it
+static int render_to_host(msplat_ctx* ctx, const FrameParams& fp, void* rgba, uint64_t pitch_bytes, size_t tight, DepthPlane depth,
+                          OccluderPlane occluder)
 {
     int rc;
     if ((rc = buf_alloc(ctx, ctx->fb, tight * fp.height))) return rc;
     const size_t ztight = (size_t)fp.width * sizeof(float);
     if (depth.p && (rc = buf_alloc(ctx, ctx->fbz, ztight * fp.height))) return rc;
     const DepthPlane dz{depth.p ? (float*)ctx->fbz.p : nullptr, ztight};
+    if (occluder.p) {
+        if ((rc = buf_alloc(ctx, ctx->fbo, ztight * fp.height))) return rc;
+        if ((rc = copy_host_rows(ctx, fp, const_cast<float*>(occluder.p), occluder.pitch, ctx->fbo, ztight, false))) return rc;
+    }
+    const OccluderPlane oz{occluder.p ? (const float*)ctx->fbo.p : nullptr, ztight};
     RenderPlan plan;
     for (int attempt = 0; attempt < 6; ++attempt) {
         // MSPLAT_TARGET_LOAD: the caller's rows are the destination -- before EVERY attempt, because blending over the target is
         // not idempotent: a retry would otherwise run over the half-blended frame of the attempt that overflowed
         if (ctx->target_mode == MSPLAT_TARGET_LOAD && (rc = copy_host_rows(ctx, fp, rgba, pitch_bytes, ctx->fb, tight, false))) return rc;
-        rc = launch_render(ctx, fp, ctx->fb.p, tight, false, nullptr, &plan, dz);
+        rc = launch_render(ctx, fp, ctx->fb.p, tight, false, nullptr, &plan, dz, oz);
         if (rc) return rc;
         uint32_t cnt[4];
         HIP_TRY(ctx, hipMemcpyAsync(cnt, ctx->counters.p, sizeof(cnt), hipMemcpyDeviceToHost, ctx->stream));
@@ -1638,7 +1673,7 @@ static int render_to_host(msplat_ctx* ctx, const FrameParams& fp, void* rgba, ui
 
 // what every Render does once its FrameParams and pitch stand (rgba1: the second view of two in one chain)
 static int render_frame(msplat_ctx* ctx, const FrameParams& fp, void* rgba, void* rgba1, uint64_t pitch_bytes, size_t tight,
-                        int out_is_device, DepthPlane depth = DepthPlane{})
+                        int out_is_device, DepthPlane depth = DepthPlane{}, OccluderPlane occluder = OccluderPlane{})
 {
     int rc;
     ctx->last_fp = fp;
@@ -1648,8 +1683,8 @@ static int render_frame(msplat_ctx* ctx, const FrameParams& fp, void* rgba, void
     if (ctx->target_mode != MSPLAT_TARGET_CLEAR && ctx->probe_on)
         return fail(ctx, MSPLAT_ERR_UNSUPPORTED, "msplat_render: the tile probe (msplat_set_tile_probe) exists for MSPLAT_TARGET_CLEAR only");
     return with_pending_overflow(ctx, [&] {      // an EARLIER frame; this one is still rendered
-        const int r = out_is_device ? launch_render(ctx, fp, rgba, pitch_bytes, true, rgba1, nullptr, depth)
-                                    : render_to_host(ctx, fp, rgba, pitch_bytes, tight, depth);
+        const int r = out_is_device ? launch_render(ctx, fp, rgba, pitch_bytes, true, rgba1, nullptr, depth, occluder)
+                                    : render_to_host(ctx, fp, rgba, pitch_bytes, tight, depth, occluder);
         if (r == MSPLAT_OK) ctx->has_render = true;
         return r;
     });
@@ -1657,9 +1692,10 @@ static int render_frame(msplat_ctx* ctx, const FrameParams& fp, void* rgba, void
 
 static int render_impl(msplat_ctx* ctx, const float cameraMat[16], const float projMat[16],
                        const float viewport[4], const float nearFar[2],
-                       void* rgba, uint64_t pitch_bytes, int out_is_device, float* depth, uint64_t depth_pitch_bytes)
+                       void* rgba, uint64_t pitch_bytes, int out_is_device, float* depth, uint64_t depth_pitch_bytes,
+                       const float* occluder, uint64_t occluder_pitch_bytes)
 {
-    const char* who = depth ? "msplat_render_depth" : "msplat_render";
+    const char* who = depth ? "msplat_render_depth" : occluder ? "msplat_render_occluded" : "msplat_render";
     FrameParams fp;
     int rc = begin_frame(ctx, who, true, rgba ? nullptr : "rgba is NULL", cameraMat, projMat, viewport, nearFar, fp);
     if (rc) return rc;
@@ -1680,7 +1716,22 @@ static int render_impl(msplat_ctx* ctx, const float cameraMat[16], const float p
             return fail(ctx, MSPLAT_ERR_INVALID_ARG, "msplat_render_depth: depth pitch %llu too small / misaligned for width %d",
                         (unsigned long long)depth_pitch_bytes, fp.width);
     }
-    return render_frame(ctx, fp, rgba, nullptr, pitch_bytes, tight, out_is_device, DepthPlane{depth, (size_t)depth_pitch_bytes});
+    if (occluder) {
+        // the test lives in the front-to-back compositor's inner loop: the draw-order compositors (depth test, target emulation,
+        // sprites) and the probe's instantiations have none
+        const char* why = ctx->point_mode ? "the context holds a point cloud (the sprite compositor has no occluder test)"
+                          : ctx->depth_bits != 0 ? "msplat_set_depth_test is on (the draw-order compositor's emulated depth buffer starts at the clear value)"
+                          : ctx->rop != MSPLAT_ROP_NONE ? "msplat_set_target_emulation is not MSPLAT_ROP_NONE (the draw-order compositor has no occluder test)"
+                          : ctx->probe_on ? "the tile probe (msplat_set_tile_probe) has no instantiation with an occluder test" : nullptr;
+        if (why) return fail(ctx, MSPLAT_ERR_UNSUPPORTED, "msplat_render_occluded: %s", why);
+        const uint64_t ztight = (uint64_t)fp.width * sizeof(float);
+        if (occluder_pitch_bytes == 0) occluder_pitch_bytes = ztight;
+        if (occluder_pitch_bytes < ztight || occluder_pitch_bytes % sizeof(float) != 0)
+            return fail(ctx, MSPLAT_ERR_INVALID_ARG, "msplat_render_occluded: occluder pitch %llu too small / misaligned for width %d",
+                        (unsigned long long)occluder_pitch_bytes, fp.width);
+    }
+    return render_frame(ctx, fp, rgba, nullptr, pitch_bytes, tight, out_is_device, DepthPlane{depth, (size_t)depth_pitch_bytes},
+                        OccluderPlane{occluder, (size_t)occluder_pitch_bytes});
 }
 
 // buffers indexed by draw-order rank, for 2 N + 64 ranks (two views in one chain)

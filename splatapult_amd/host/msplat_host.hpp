@@ -248,6 +248,29 @@ public:
         if (rc != MSPLAT_OK) std::fprintf(stderr, "[msplat][%c] RenderWithDepth: %s\n", Level(rc), msplat_last_error(ctx));
     }
 
+    // Render behind the caller's geometry (msplat_render_occluded): `occluder` = W x H float32 window depths, rows of pitchBytes (0 = tight)
+    // in the render target's memory space, e.g. the depth attachment of the mesh pass -- GL_LESS, as app.cpp:160-163 sets it: a splat with
+    // !(z_w < occluder) at a pixel is not blended there.  Read-only; with a device target it must stay valid until the frame has run.
+    // Uses the context of the latest Sort, like Render.  A device group takes no occluder plane.
+    template <class Mat4, class Vec4, class Vec2>
+    void RenderOccluded(const Mat4& cameraMat, const Mat4& projMat, const Vec4& viewport, const Vec2& nearFar, const float* occluder,
+                        uint64_t pitchBytes = 0)
+    {
+        static_assert(sizeof(Mat4) == 64 && sizeof(Vec4) == 16 && sizeof(Vec2) == 8, "glm-compatible layout expected");
+        if (!target || !occluder) {
+            std::fprintf(stderr, "[msplat][E] RenderOccluded: no render target set (SetRenderTarget) or no occluder plane\n");
+            return;
+        }
+        if (group) {
+            std::fprintf(stderr, "[msplat][E] RenderOccluded: a device group takes no occluder plane\n");
+            return;
+        }
+        const int rc = msplat_render_occluded(ctx, reinterpret_cast<const float*>(&cameraMat), reinterpret_cast<const float*>(&projMat),
+                                              reinterpret_cast<const float*>(&viewport), reinterpret_cast<const float*>(&nearFar), target,
+                                              targetPitch, occluder, pitchBytes, targetIsDevice ? 1 : 0);
+        if (rc != MSPLAT_OK) std::fprintf(stderr, "[msplat][%c] RenderOccluded: %s\n", Level(rc), msplat_last_error(ctx));
+    }
+
     // Both eyes of the latest Sort in one chain of launches (msplat_render_stereo): what the XR callback does with two Render
     // calls (app.cpp:603-607), for device targets at half the launches.  target1: the second eye's image (same pitch / kind as
     // the SetRenderTarget one, which receives the first eye).

@@ -238,15 +238,38 @@ class SplatRenderer:
         _capi.check(self._ctx, self._lib.msplat_sort(self._ctx, c, p, v, nf))
 
     def Render(self, cameraMat, projMat, viewport, nearFar, out=None, out_ptr=None, pitch_bytes=0, depth=None, depth_ptr=None,
-               depth_pitch_bytes=0):
+               depth_pitch_bytes=0, occluder=None, occluder_ptr=None, occluder_pitch_bytes=0):
         """splatrenderer.cpp:315-343 + the GL pipeline behind it.
         out=None      -> returns a new (H, W, 4) numpy array (float32, float16 or -- the 8-bit targets -- uint8), row 0 = GL bottom row
         out=ndarray   -> filled in place
         out_ptr=int   -> device pointer (e.g. torch tensor .data_ptr()); asynchronous on the stream
         The depth plane (msplat_render_depth: the splats' expected window depth over the clear depth 1.0, float32 on every
         context) lives where the colour does: depth=(H, W) float32 array to fill, or True to have one allocated, with host
-        output -- the call then returns (image, depth); depth_ptr=int (rows of depth_pitch_bytes, 0 = tight) with out_ptr"""
+        output -- the call then returns (image, depth); depth_ptr=int (rows of depth_pitch_bytes, 0 = tight) with out_ptr.
+        The occluder plane (msplat_render_occluded: window depths of the caller's geometry, GL_LESS -- a splat with
+        !(z_w < occluder) at a pixel is absent there) lives where the colour does too and is only read: occluder=(H, W) float32
+        array with host output, occluder_ptr=int (rows of occluder_pitch_bytes, 0 = tight; valid until the frame has run) with
+        out_ptr.  A frame has a depth output or an occluder plane, not both: MsplatError(ERR_UNSUPPORTED)"""
         c, p, v, nf = self._args.load(cameraMat, projMat, viewport, nearFar)
+        has_depth = (depth is not None and depth is not False) or depth_ptr is not None
+        if occluder is not None or occluder_ptr is not None:
+            if has_depth:
+                raise _capi.MsplatError(_capi.ERR_UNSUPPORTED, "a frame has either a depth output (msplat_render_depth) or an occluder "
+                                        "plane (msplat_render_occluded), not both")
+            if out_ptr is not None:
+                if occluder is not None:
+                    raise ValueError("the occluder plane lives in the colour's memory space: pass occluder_ptr= with out_ptr=")
+                _capi.check(self._ctx, self._lib.msplat_render_occluded(self._ctx, c, p, v, nf, C.c_void_p(out_ptr), pitch_bytes,
+                                                                        C.c_void_p(occluder_ptr), occluder_pitch_bytes, 1))
+                return None
+            if occluder_ptr is not None:
+                raise ValueError("the occluder plane lives in the colour's memory space: pass occluder= with host output")
+            out = _host_frame(self._fb_format, self._args.vp, out, self._load)
+            H, W = out.shape[:2]
+            assert occluder.dtype == np.float32 and occluder.shape == (H, W) and occluder.flags["C_CONTIGUOUS"]
+            _capi.check(self._ctx, self._lib.msplat_render_occluded(self._ctx, c, p, v, nf, out.ctypes.data, 0, occluder.ctypes.data,
+                                                                    occluder_pitch_bytes, 0))
+            return out
         if out_ptr is not None:
             if depth is not None:
                 raise ValueError("the depth plane lives in the colour's memory space: pass depth_ptr= with out_ptr=")
@@ -602,10 +625,14 @@ class SplatRendererGroup:
         _capi.check(self._g, self._lib.msplat_group_sort(self._g, c, p, v, nf), self._gerr)
 
     def Render(self, cameraMat, projMat, viewport, nearFar, out=None, out_ptr=None, pitch_bytes=0, depth=None, depth_ptr=None,
-               depth_pitch_bytes=0):
+               depth_pitch_bytes=0, occluder=None, occluder_ptr=None, occluder_pitch_bytes=0):
         """out_ptr: device pointer ON devices[0] (asynchronous; synchronize() or wait on context 0's stream);
         otherwise a host array is filled / returned.  A depth plane (SplatRenderer.Render's depth= / depth_ptr=) is refused:
-        the group's row gather moves the colour only"""
+        the group's row gather moves the colour only; so is an occluder plane (occluder= / occluder_ptr=): it lives on one device"""
+        if occluder is not None or occluder_ptr is not None:
+            raise _capi.MsplatError(_capi.ERR_UNSUPPORTED, "a device group takes no occluder plane (msplat_render_occluded is per context): "
+                                    "render behind geometry with a SplatRenderer")
+        del occluder_pitch_bytes
         if (depth is not None and depth is not False) or depth_ptr is not None:
             raise _capi.MsplatError(_capi.ERR_UNSUPPORTED, "a device group has no depth output (msplat_render_depth is per context): "
                                     "render the depth plane with a SplatRenderer")

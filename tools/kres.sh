@@ -16,7 +16,7 @@ for b, d in zip(blocks, dem):
     d = re.sub(r'\(.*', '', d).replace('void msplat::', '')
     if not flt.search(d): continue
     g = lambda k: (re.search(k + r': (\d+)', b) or [None, '?'])[1]
-    print('%-52s VGPR %3s SGPR %3s sgpr-spill %2s vgpr-spill %2s scratch %3s occ %s LDS %s' % (
-        d[:52], g('VGPRs'), g('SGPRs'), g('SGPRs Spill'), g('VGPRs Spill'), g(r'ScratchSize \[bytes/lane\]'),
+    print('%-54s VGPR %3s SGPR %3s sgpr-spill %2s vgpr-spill %2s scratch %3s occ %s LDS %s' % (
+        d[:54], g('VGPRs'), g('SGPRs'), g('SGPRs Spill'), g('VGPRs Spill'), g(r'ScratchSize \[bytes/lane\]'),
         g(r'Occupancy \[waves/SIMD\]'), g(r'LDS Size \[bytes/block\]')))
 PY
