@@ -138,25 +138,25 @@ int msplat_sort(msplat_ctx* ctx, const float cameraMat[16], const float projMat[
  * fp32 multiply, fp32 add, truncation.  MSPLAT_FB_SRGB8_ALPHA8: alpha so; r g b from e = v <= 0.0031308 ? 12.92 v : 1.055 v^(1/2.4) - 0.055 with |255 e - code| <= 0.5 + 2^-10.
  * Pair-buffer overflow: a host-output render grows the buffer and retries.  A device-output render cannot know; the NEXT msplat_sort / msplat_render / msplat_synchronize
  * of the context grows the buffer (unless pair_capacity fixed it) and reports it once -- msplat_synchronize: MSPLAT_ERR_PAIR_OVERFLOW; sort / render, whose own work is done: _EARLIER.  That frame lacks splats in its last bin columns: render it again. */
-int msplat_render(msplat_ctx* ctx, const float cameraMat[16], const float projMat[16], const float viewport[4],
-                  const float nearFar[2], void* rgba, uint64_t pitch_bytes, int out_is_device);
+int msplat_render(msplat_ctx* ctx, const float cameraMat[16], const float projMat[16], const float viewport[4], const float nearFar[2], void* rgba, uint64_t pitch_bytes, int out_is_device);
 /* ---- msplat_render plus a depth plane (INTEGRATION.md 14).  depth == NULL: msplat_render.  Else W x H float32 on every context (fp16 cannot resolve z_w near
  * 1), row 0 = GL bottom, depth_pitch_bytes between rows (0 = tight), in `rgba`'s memory space.  With z_i = 0.5 ndc.z + 0.5 (window depth of splat i), T as above:
  * depth = sum_i T_i w_i z_i + T * 1.0 -- the expected window depth over GL's clear depth 1.0 (app.cpp:160), MSPLAT_TARGET_LOAD's formula with colour z, dst = 1:
  * in [0, 1], exactly 1.0 where no splat reaches.  Early termination leaves T below t_epsilon, not at its limit: the plane is high by <= t_epsilon; t_epsilon = 0
  * removes the error.  Colour: msplat_render's bit for bit; the plane is the same in every target mode; banded contexts write owned rows.  MSPLAT_ERR_UNSUPPORTED
- * with msplat_set_depth_test, a target emulation, points or the tile probe; _INVALID_ARG: depth pitch < 4 W or not a multiple of 4.  Out of scope: msplat_render_stereo
- * (call per eye), the device group, msplat_band_exchange of the plane. */
-int msplat_render_depth(msplat_ctx* ctx, const float cameraMat[16], const float projMat[16], const float viewport[4], const float nearFar[2],
-                        void* rgba, uint64_t pitch_bytes, float* depth, uint64_t depth_pitch_bytes, int out_is_device);
+ * with msplat_set_depth_test, a target emulation, points or the tile probe; _INVALID_ARG: depth pitch < 4 W or not a multiple of 4.  Both eyes in one chain, or the
+ * plane over an occluder's values: msplat_render_stereo_layers / msplat_render_layers.  Out of scope: the device group, msplat_band_exchange of the plane. */
+int msplat_render_depth(msplat_ctx* ctx, const float cameraMat[16], const float projMat[16], const float viewport[4], const float nearFar[2], void* rgba, uint64_t pitch_bytes, float* depth, uint64_t depth_pitch_bytes, int out_is_device);
 /* ---- msplat_render behind the caller's geometry (INTEGRATION.md 16): GL_LESS as app.cpp:160-163 sets it.  occluder == NULL: msplat_render.  Else W x H float32 window depths (the plane msplat_render_depth writes), row 0 = GL bottom, occluder_pitch_bytes between rows (0 = tight; else >= 4 W and a multiple of 4, or _INVALID_ARG), in `rgba`'s memory space, read-only.
  * Per pixel p: msplat_render's frame with every splat i with !(z_i < occluder[p]) absent at p; z_i = 0.5 ndc.z + 0.5, one per splat (splat_geom.glsl:98).  A splat AT the plane's depth is hidden; NaN hides everything at its pixel; +inf or any value above 1 nothing.  Formats, target modes (LOAD: a pixel no surviving splat reaches keeps its bits), banded contexts (owned rows of the plane), pitches, host output and its retry, frames in flight, two-pass frames: msplat_render's.
- * Device output, also with async_submit: the plane must stay valid and unchanged until the frame has run.  MSPLAT_ERR_UNSUPPORTED (the context stays usable): a point cloud, msplat_set_depth_test, a target emulation, the tile probe.  Out of scope: msplat_render_stereo (call per eye), the device group, msplat_render_depth's output in the same frame, seeding msplat_set_depth_test's emulated depth buffer. */
+ * Device output, also with async_submit: the plane must stay valid and unchanged until the frame has run.  MSPLAT_ERR_UNSUPPORTED (the context stays usable): a point cloud, msplat_set_depth_test, a target emulation, the tile probe.  Both eyes in one chain, or msplat_render_depth's output in the same frame: msplat_render_stereo_layers / msplat_render_layers.  Out of scope: the device group, seeding msplat_set_depth_test's emulated depth buffer. */
 int msplat_render_occluded(msplat_ctx* ctx, const float cameraMat[16], const float projMat[16], const float viewport[4], const float nearFar[2], void* rgba, uint64_t pitch_bytes, const float* occluder, uint64_t occluder_pitch_bytes, int out_is_device);
+/* ---- msplat_render_occluded and msplat_render_depth in ONE frame (INTEGRATION.md 17): colour behind the caller's geometry plus the depth layer of the result, what the reference's XR frame (app.cpp:570-607: lines, camera path and carpet first, the splats blended over them under GL_LESS) hands an XR runtime.  Planes, pitches, memory space, lifetime, banded contexts, host output and its retry, frames in flight, async_submit: as for those two calls.  A NULL plane degrades: both NULL = msplat_render, depth only = msplat_render_depth, occluder only = msplat_render_occluded, the same kernels launched.  With both, per pixel p, o = occluder[p], z_i and T as above:  colour = msplat_render_occluded's, bit for bit, in every format and target mode;  depth[p] = min(fma(T, d0, sum_{i: z_i < o} T_i w_i z_i), 1),  d0 = o > 0 ? (o > 1 ? 1 : o) : 0 (NaN -> 0; the 8-bit targets' clamp) -- the expected window depth of the splats that pass the test over what the depth attachment holds, MSPLAT_TARGET_LOAD's formula with colour z and dst = the attachment.  An open plane (d0 = 1) gives msplat_render_depth's plane bit for bit; a pixel no surviving splat reaches holds d0 exactly; early termination leaves the plane high by <= t_epsilon * d0. In place: `depth` may be the occluder's own memory -- the same pointer AND the same pitch -- a depth attachment read and written in place (every pixel is read before it is written, by the lane that writes it; a two-pass frame never reads a tile again once it has written it).  Any other overlap of the two planes is undefined.  Like MSPLAT_TARGET_LOAD such a frame is not idempotent: after MSPLAT_ERR_PAIR_OVERFLOW[_EARLIER] a device-output caller restores the attachment before rendering the frame again (host output retries from the staged plane). MSPLAT_ERR_UNSUPPORTED (the context stays usable): a point cloud, msplat_set_depth_test, a target emulation, the tile probe.  Out of scope: the device group. */
+int msplat_render_layers(msplat_ctx* ctx, const float cameraMat[16], const float projMat[16], const float viewport[4], const float nearFar[2], void* rgba, uint64_t pitch_bytes, float* depth, uint64_t depth_pitch_bytes, const float* occluder, uint64_t occluder_pitch_bytes, int out_is_device);
 /* the reference's VR frame -- Sort with the first eye, Render per eye (app.cpp:603-607) -- as ONE chain of launches; the same pixels as two msplat_render calls, bit for bit.  Host targets, banded contexts, points and the emulations go view by view. */
-int msplat_render_stereo(msplat_ctx* ctx, const float cameraMat0[16], const float projMat0[16], const float cameraMat1[16],
-                         const float projMat1[16], const float viewport[4], const float nearFar[2], void* rgba0, void* rgba1,
-                         uint64_t pitch_bytes, int out_is_device);
+int msplat_render_stereo(msplat_ctx* ctx, const float cameraMat0[16], const float projMat0[16], const float cameraMat1[16], const float projMat1[16], const float viewport[4], const float nearFar[2], void* rgba0, void* rgba1, uint64_t pitch_bytes, int out_is_device);
+/* msplat_render_stereo with msplat_render_layers' planes per eye; the pitch of each kind is shared by the eyes.  depth0 / depth1 are both given or both NULL, and so are occluder0 / occluder1 (else MSPLAT_ERR_INVALID_ARG); all NULL = msplat_render_stereo.  One chain where msplat_render_stereo runs as one (device output, no bands, <= 2^23 splats, <= 128 bin rows per view), else view by view; either way each eye's colour and depth are bit for bit msplat_render_layers' with that eye's matrices after the same Sort. */
+int msplat_render_stereo_layers(msplat_ctx* ctx, const float cameraMat0[16], const float projMat0[16], const float cameraMat1[16], const float projMat1[16], const float viewport[4], const float nearFar[2], void* rgba0, void* rgba1, uint64_t pitch_bytes, float* depth0, float* depth1, uint64_t depth_pitch_bytes, const float* occluder0, const float* occluder1, uint64_t occluder_pitch_bytes, int out_is_device);
 /* blocks until everything queued on the context (and issued by its worker thread) has finished */
 int msplat_synchronize(msplat_ctx* ctx);
 

@@ -84,7 +84,13 @@ constexpr int kCompOcc = 5;        // occupancy bound handed to the compiler (<=
 // straight to its final store.  Pass 2 of a two-pass frame re-reads the plane: no new per-pixel state.  (Built and removed before any measurement: a second,
 // untested copy of the loop chosen per batch by a scalar branch when every staged record lies in front of the tile's MINIMUM -- two pass-1
 // instantiations then spilled VGPRs into scratch, EXPERIMENTS.md round 14.)  ZTEST = false: the code of every instantiation that existed before the parameter.
+// DEPTH && ZTEST (msplat_render_layers): both at once -- the loop gains exactly what each adds, the depth plane is blended over the occluder's
+// value d0 (clamped to [0, 1]) instead of the clear depth, from the zp registers the lane already holds: no new per-pixel state.  TWO_VIEWS takes
+// the second view's planes from ex.occluder1 / ex.depth1, rows counted in the view's own ty.
 constexpr int kTargetClear = 0, kTargetLoad = 1, kTargetPremultiplied = 2;      // MSPLAT_TARGET_* (include/msplat.h)
+// The occupancy bound of an instantiation: kCompOcc, except for the one-view DEPTH && ZTEST forms of the single pass and of pass 2, which spilled
+// 2-14 VGPRs into scratch under it (96 allocatable registers; pass 1 and the two-view form fit): those alone get 4 waves (EXPERIMENTS.md round 15)
+constexpr int comp_occ(int occ, bool two_views, bool depth, bool ztest) { return depth && ztest && !two_views && occ != 1 ? 4 : kCompOcc; }
 struct CompExtra {
     void* out1;                  // TWO_VIEWS: the second view's target (bin rows >= rows_view belong to it)
     uint32_t* fin;               // OCC != 0: per (bin, quadrant) 0xFFFFFFFF = final, else entries composited by pass 1
@@ -97,10 +103,12 @@ struct CompExtra {
     float* zstate;               // DEPTH, OCC != 0: the depth accumulator per pixel, beside `state`
     const float* occluder;       // ZTEST: the plane of window depths the splats are tested against (zw as for DEPTH), rows of occluder_pitch bytes
     size_t occluder_pitch;
+    const float* occluder1;      // TWO_VIEWS: the second view's planes, as out1 is its target; each kind's pitch is shared by the views
+    float* depth1;
 };
 
 template <int FMT, int OCC, bool TWO_VIEWS, bool PROBE, int TM = kTargetClear, bool DEPTH = false, bool ZTEST = false>
-__global__ __launch_bounds__(kCompThreads, kCompOcc) void composite_kernel(const uint32_t* __restrict__ tile_start,
+__global__ __launch_bounds__(kCompThreads, comp_occ(OCC, TWO_VIEWS, DEPTH, ZTEST)) void composite_kernel(const uint32_t* __restrict__ tile_start,
                                                                  const uint32_t* __restrict__ pairs,
                                                                  const float4* __restrict__ rec,
                                                                  void* __restrict__ out, size_t pitch_bytes,
@@ -212,7 +220,7 @@ __global__ __launch_bounds__(kCompThreads, kCompOcc) void composite_kernel(const
 #pragma unroll
         for (int k = 0; k < NS; ++k) {
             float v = -__builtin_inff();
-            if (inside[k]) v = ((const float*)((const char*)ex.occluder + (size_t)(ybase + 4 * k) * ex.occluder_pitch))[x];
+            if (inside[k]) v = ((const float*)((const char*)(second ? ex.occluder1 : ex.occluder) + (size_t)(ybase + 4 * k) * ex.occluder_pitch))[x];
             zp[k >> 1][k & 1] = v == v ? v : -__builtin_inff();      // NaN: closed
         }
     }
@@ -470,8 +478,17 @@ __global__ __launch_bounds__(kCompThreads, kCompOcc) void composite_kernel(const
                 // expected window depth over the clear depth 1.0: the blend of kTargetLoad with colour z and dst = 1 (T = 2^-118 Ts is
                 // exact; a pixel no splat reached reads exactly 1).  Every z is <= 1 and the weights sum to 1 - T, but the partial sums
                 // are rounded: the minimum keeps the plane inside [0, 1] when z_w sits at 1
-                float* zrow = (float*)((char*)ex.depth + (size_t)(ybase + 4 * k) * ex.depth_pitch);
-                zrow[x] = fminf(cz[k >> 1][k & 1] + T[k >> 1][k & 1] * 0x1p-118f, 1.0f);
+                // DEPTH && ZTEST (msplat_render_layers): over what the depth attachment holds instead, d0 = the plane's value clamped to
+                // [0, 1] by the 8-bit targets' rule -- from the registers the test ran on (-inf: closed or NaN, gives 0), read before this
+                // store: the plane may be the occluder's own memory.  One fma, so that d0 = 1 rounds like the sum above
+                float* zrow = (float*)((char*)(second ? ex.depth1 : ex.depth) + (size_t)(ybase + 4 * k) * ex.depth_pitch);
+                if (ZTEST) {
+                    const float o = zp[k >> 1][k & 1];
+                    const float d0 = o > 0.0f ? (o > 1.0f ? 1.0f : o) : 0.0f;
+                    zrow[x] = fminf(__builtin_fmaf(T[k >> 1][k & 1] * 0x1p-118f, d0, cz[k >> 1][k & 1]), 1.0f);
+                } else {
+                    zrow[x] = fminf(cz[k >> 1][k & 1] + T[k >> 1][k & 1] * 0x1p-118f, 1.0f);
+                }
             }
         }
     }

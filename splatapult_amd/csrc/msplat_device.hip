@@ -964,7 +964,8 @@ static int with_pending_overflow(msplat_ctx* ctx, Work&& work)
 static int sort_impl(msplat_ctx* ctx, const float cameraMat[16], const float projMat[16], const float viewport[4], const float nearFar[2]);
 static int render_impl(msplat_ctx* ctx, const float cameraMat[16], const float projMat[16], const float viewport[4],
                        const float nearFar[2], void* rgba, uint64_t pitch_bytes, int out_is_device, float* depth = nullptr,
-                       uint64_t depth_pitch_bytes = 0, const float* occluder = nullptr, uint64_t occluder_pitch_bytes = 0);
+                       uint64_t depth_pitch_bytes = 0, const float* occluder = nullptr, uint64_t occluder_pitch_bytes = 0,
+                       const char* who = nullptr);
 
 int msplat_sort(msplat_ctx* ctx, const float cameraMat[16], const float projMat[16],
                 const float viewport[4], const float nearFar[2])
@@ -1184,6 +1185,8 @@ struct RenderChain {
     size_t depth_pitch;
     const float* d_occluder;     // msplat_render_occluded: the plane the splats are depth-tested against (NULL: none) and its pitch
     size_t occluder_pitch;
+    float* d_depth1;             // two views in one chain (msplat_render_stereo_layers): the second view's planes, as d_out1 is its target
+    const float* d_occluder1;
     // the compositor's schedule, decided where the bins are ordered (issue_binning) and used by issue_compositor
     bool ordered = true;
     uint32_t comp_items = 0, comp_pool = 0;
@@ -1407,12 +1410,13 @@ static int issue_compositor(RenderChain& rc, int occ_pass, int ev_c0, int ev_c1)
         const int grid = (int)std::min<uint32_t>(comp_items, comp_pool);
         const CompParams cp = comp_params(fp);
         const CompExtra ex{d_out1, fin, state, d_nbins, probe, (const float*)ctx->zq.p, rc.d_depth, rc.depth_pitch,
-                           occ_pass ? (float*)ctx->occ_zstate.p : nullptr, rc.d_occluder, rc.occluder_pitch};
+                           occ_pass ? (float*)ctx->occ_zstate.p : nullptr, rc.d_occluder, rc.occluder_pitch, rc.d_occluder1, rc.d_depth1};
         const int prio = occ_pass == 2 ? 0 : prio_mode;
         // six of the twelve (OCC, TWO_VIEWS, PROBE) forms exist per format
         // (occlusion_plan never chooses two passes for two views in one chain or while the probe is on)
         // and the four without the probe once more per non-CLEAR target mode (render_frame refuses the probe with those);
-        // a depth frame (one view, no probe: render_impl) has the three passes per target mode, and so has an occluded frame
+        // a frame with a depth plane, an occluder plane or both (no probe: plane_checks) has the three passes per target mode, and
+        // the one pass of two views in one chain
         auto composite = [&](auto OCC, auto TWO, auto PROBE, auto TM, auto DEPTH, auto ZTEST) {
             with_format([&](auto FMT) {
                 hipExtLaunchKernelGGL((composite_kernel<FMT.value, OCC.value, TWO.value, PROBE.value, TM.value, DEPTH.value, ZTEST.value>),
@@ -1423,13 +1427,15 @@ static int issue_compositor(RenderChain& rc, int occ_pass, int ev_c0, int ev_c1)
         constexpr flag_t<true> yes{};
         constexpr flag_t<false> no{};
         constexpr int_t<kTargetClear> clear{};
-        if (rc.d_occluder)
+        if (rc.d_occluder || rc.d_depth)
             with_int<kTargetLoad, kTargetPremultiplied, kTargetClear>(ctx->target_mode, [&](auto TM) {
-                with_int<1, 2, 0>(occ_pass, [&](auto OCC) { composite(OCC, no, no, TM, no, yes); });
-            });
-        else if (rc.d_depth)
-            with_int<kTargetLoad, kTargetPremultiplied, kTargetClear>(ctx->target_mode, [&](auto TM) {
-                with_int<1, 2, 0>(occ_pass, [&](auto OCC) { composite(OCC, no, no, TM, yes, no); });
+                auto planes = [&](auto OCC, auto TWO) {
+                    if (rc.d_occluder && rc.d_depth) composite(OCC, TWO, no, TM, yes, yes);
+                    else if (rc.d_occluder) composite(OCC, TWO, no, TM, no, yes);
+                    else composite(OCC, TWO, no, TM, yes, no);
+                };
+                if (stereo) planes(int_t<0>{}, yes);
+                else with_int<1, 2, 0>(occ_pass, [&](auto OCC) { planes(OCC, no); });
             });
         else if (ctx->target_mode != MSPLAT_TARGET_CLEAR)
             with_int<kTargetLoad, kTargetPremultiplied>(ctx->target_mode, [&](auto TM) {
@@ -1478,12 +1484,14 @@ static void issue_occlusion_gate(RenderChain& rc)
 struct DepthPlane {
     float* p = nullptr;
     size_t pitch = 0;
+    float* p1 = nullptr;         // the second view's plane of two views in one chain (same pitch)
 };
 
 // the plane of window depths a msplat_render_occluded frame is tested against, in device memory (p == NULL: no test); read-only
 struct OccluderPlane {
     const float* p = nullptr;
     size_t pitch = 0;
+    const float* p1 = nullptr;   // the second view's plane of two views in one chain (same pitch)
 };
 
 static int launch_render(msplat_ctx* ctx, const FrameParams& fp, void* d_out, size_t pitch, bool async_overflow_flag,
@@ -1497,7 +1505,7 @@ static int launch_render(msplat_ctx* ctx, const FrameParams& fp, void* d_out, si
     RenderChain rc{ctx, fp, s, stereo, N, counters + kCntV, counters + kCntD, counters + kCntOverflow, (uint32_t*)ctx->queue.p,
                    stereo ? counters + kCntVframe2 : counters + kCntV, (uint32_t*)ctx->occ.p, fp.tiles_x * fp.tiles_y, (uint32_t)ctx->pair_cap,
                    false, 0, (int)std::max(1u, div_up(N, kProjThreads)), d_out, d_out1, pitch, async_overflow_flag, depth.p, depth.pitch,
-                   occluder.p, occluder.pitch};
+                   occluder.p, occluder.pitch, depth.p1, occluder.p1};
     // Two-pass frame with occlusion feedback (msplat_occlusion.hip.h): the nearest R1 splats first, then only what the bins
     // they did not saturate still need.  Same pixels; chosen once per Render (occlusion_plan).  The retries of a host-output
     // frame whose pair buffer overflowed reuse the plan AND count as the same Render: the sampling counter, the two-pass
@@ -1588,6 +1596,19 @@ int msplat_render_occluded(msplat_ctx* ctx, const float cameraMat[16], const flo
                         [=](const float* cam, const float* proj, const float*, const float*, const float* vp, const float* nf) {
                             return render_impl(ctx, cam, proj, vp, nf, rgba, pitch_bytes, out_is_device, nullptr, 0, occluder,
                                                occluder_pitch_bytes);
+                        });
+}
+
+// msplat_render_occluded and msplat_render_depth in one frame (include/msplat.h): the depth plane is blended over the occluder's
+// values.  A NULL plane degrades to the call without it
+int msplat_render_layers(msplat_ctx* ctx, const float cameraMat[16], const float projMat[16], const float viewport[4],
+                         const float nearFar[2], void* rgba, uint64_t pitch_bytes, float* depth, uint64_t depth_pitch_bytes,
+                         const float* occluder, uint64_t occluder_pitch_bytes, int out_is_device)
+{
+    return submit_frame<false>(ctx, out_is_device && rgba, cameraMat, projMat, cameraMat, projMat, viewport, nearFar,
+                        [=](const float* cam, const float* proj, const float*, const float*, const float* vp, const float* nf) {
+                            return render_impl(ctx, cam, proj, vp, nf, rgba, pitch_bytes, out_is_device, depth, depth_pitch_bytes, occluder,
+                                               occluder_pitch_bytes, "msplat_render_layers");
                         });
 }
 
@@ -1690,18 +1711,11 @@ static int render_frame(msplat_ctx* ctx, const FrameParams& fp, void* rgba, void
     });
 }
 
-static int render_impl(msplat_ctx* ctx, const float cameraMat[16], const float projMat[16],
-                       const float viewport[4], const float nearFar[2],
-                       void* rgba, uint64_t pitch_bytes, int out_is_device, float* depth, uint64_t depth_pitch_bytes,
-                       const float* occluder, uint64_t occluder_pitch_bytes)
+// What a frame with a depth plane and / or an occluder plane checks once its FrameParams stand: the configurations without such an
+// instantiation are refused, the planes' pitches resolved (0 = tight).  `who`: the entry point the messages name
+static int plane_checks(msplat_ctx* ctx, const char* who, const FrameParams& fp, bool depth, uint64_t& depth_pitch_bytes, bool occluder,
+                        uint64_t& occluder_pitch_bytes)
 {
-    const char* who = depth ? "msplat_render_depth" : occluder ? "msplat_render_occluded" : "msplat_render";
-    FrameParams fp;
-    int rc = begin_frame(ctx, who, true, rgba ? nullptr : "rgba is NULL", cameraMat, projMat, viewport, nearFar, fp);
-    if (rc) return rc;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    size_t tight = 0;
-    if ((rc = resolve_pitch(ctx, who, fp, pitch_bytes, tight))) return rc;
     if (depth) {
         // the plane comes from the front-to-back compositor's accumulators: the draw-order compositors (depth test, target
         // emulation, sprites) and the probe's instantiations carry none
@@ -1709,11 +1723,11 @@ static int render_impl(msplat_ctx* ctx, const float cameraMat[16], const float p
                           : ctx->depth_bits != 0 ? "msplat_set_depth_test is on (the draw-order compositor has no depth output)"
                           : ctx->rop != MSPLAT_ROP_NONE ? "msplat_set_target_emulation is not MSPLAT_ROP_NONE (the draw-order compositor has no depth output)"
                           : ctx->probe_on ? "the tile probe (msplat_set_tile_probe) has no instantiation with a depth output" : nullptr;
-        if (why) return fail(ctx, MSPLAT_ERR_UNSUPPORTED, "msplat_render_depth: %s", why);
+        if (why) return fail(ctx, MSPLAT_ERR_UNSUPPORTED, "%s: %s", who, why);
         const uint64_t ztight = (uint64_t)fp.width * sizeof(float);
         if (depth_pitch_bytes == 0) depth_pitch_bytes = ztight;
         if (depth_pitch_bytes < ztight || depth_pitch_bytes % sizeof(float) != 0)
-            return fail(ctx, MSPLAT_ERR_INVALID_ARG, "msplat_render_depth: depth pitch %llu too small / misaligned for width %d",
+            return fail(ctx, MSPLAT_ERR_INVALID_ARG, "%s: depth pitch %llu too small / misaligned for width %d", who,
                         (unsigned long long)depth_pitch_bytes, fp.width);
     }
     if (occluder) {
@@ -1723,13 +1737,30 @@ static int render_impl(msplat_ctx* ctx, const float cameraMat[16], const float p
                           : ctx->depth_bits != 0 ? "msplat_set_depth_test is on (the draw-order compositor's emulated depth buffer starts at the clear value)"
                           : ctx->rop != MSPLAT_ROP_NONE ? "msplat_set_target_emulation is not MSPLAT_ROP_NONE (the draw-order compositor has no occluder test)"
                           : ctx->probe_on ? "the tile probe (msplat_set_tile_probe) has no instantiation with an occluder test" : nullptr;
-        if (why) return fail(ctx, MSPLAT_ERR_UNSUPPORTED, "msplat_render_occluded: %s", why);
+        if (why) return fail(ctx, MSPLAT_ERR_UNSUPPORTED, "%s: %s", who, why);
         const uint64_t ztight = (uint64_t)fp.width * sizeof(float);
         if (occluder_pitch_bytes == 0) occluder_pitch_bytes = ztight;
         if (occluder_pitch_bytes < ztight || occluder_pitch_bytes % sizeof(float) != 0)
-            return fail(ctx, MSPLAT_ERR_INVALID_ARG, "msplat_render_occluded: occluder pitch %llu too small / misaligned for width %d",
+            return fail(ctx, MSPLAT_ERR_INVALID_ARG, "%s: occluder pitch %llu too small / misaligned for width %d", who,
                         (unsigned long long)occluder_pitch_bytes, fp.width);
     }
+    return MSPLAT_OK;
+}
+
+// who: the entry point the messages name (NULL: the one that takes exactly these planes)
+static int render_impl(msplat_ctx* ctx, const float cameraMat[16], const float projMat[16],
+                       const float viewport[4], const float nearFar[2],
+                       void* rgba, uint64_t pitch_bytes, int out_is_device, float* depth, uint64_t depth_pitch_bytes,
+                       const float* occluder, uint64_t occluder_pitch_bytes, const char* who)
+{
+    if (!who) who = depth ? "msplat_render_depth" : occluder ? "msplat_render_occluded" : "msplat_render";
+    FrameParams fp;
+    int rc = begin_frame(ctx, who, true, rgba ? nullptr : "rgba is NULL", cameraMat, projMat, viewport, nearFar, fp);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    size_t tight = 0;
+    if ((rc = resolve_pitch(ctx, who, fp, pitch_bytes, tight))) return rc;
+    if ((rc = plane_checks(ctx, who, fp, depth != nullptr, depth_pitch_bytes, occluder != nullptr, occluder_pitch_bytes))) return rc;
     return render_frame(ctx, fp, rgba, nullptr, pitch_bytes, tight, out_is_device, DepthPlane{depth, (size_t)depth_pitch_bytes},
                         OccluderPlane{occluder, (size_t)occluder_pitch_bytes});
 }
@@ -1752,9 +1783,18 @@ static int ensure_stereo_ranks(msplat_ctx* ctx)
     return MSPLAT_OK;
 }
 
-static int render_stereo_impl(msplat_ctx* ctx, const float cam0[16], const float proj0[16], const float cam1[16], const float proj1[16],
-                              const float viewport[4], const float nearFar[2], void* rgba0, void* rgba1, uint64_t pitch_bytes,
-                              int out_is_device);
+// the planes of a two-view frame (msplat_render_stereo_layers): one pitch per kind, a plane per eye or none
+struct StereoPlanes {
+    float *depth0 = nullptr, *depth1 = nullptr;
+    uint64_t depth_pitch = 0;
+    const float *occluder0 = nullptr, *occluder1 = nullptr;
+    uint64_t occluder_pitch = 0;
+    bool paired() const { return !depth0 == !depth1 && !occluder0 == !occluder1; }
+};
+
+static int render_stereo_impl(msplat_ctx* ctx, const char* who, const float cam0[16], const float proj0[16], const float cam1[16],
+                              const float proj1[16], const float viewport[4], const float nearFar[2], void* rgba0, void* rgba1,
+                              uint64_t pitch_bytes, int out_is_device, StereoPlanes pl = StereoPlanes{});
 
 // Two views of ONE Sort (the reference's VR frame: Sort with the first eye, Render per eye -- src/app.cpp:603-607) as a single
 // chain of launches: projection, binning and compositing each run once over both views' work instead of twice in a row (half
@@ -1767,29 +1807,52 @@ int msplat_render_stereo(msplat_ctx* ctx, const float cameraMat0[16], const floa
 {
     return submit_frame<true>(ctx, out_is_device && rgba0 && rgba1, cameraMat0, projMat0, cameraMat1, projMat1, viewport, nearFar,
                         [=](const float* cam0, const float* proj0, const float* cam1, const float* proj1, const float* vp, const float* nf) {
-                            return render_stereo_impl(ctx, cam0, proj0, cam1, proj1, vp, nf, rgba0, rgba1, pitch_bytes, out_is_device);
+                            return render_stereo_impl(ctx, "msplat_render_stereo", cam0, proj0, cam1, proj1, vp, nf, rgba0, rgba1, pitch_bytes,
+                                                      out_is_device);
                         });
 }
 
-static int render_stereo_impl(msplat_ctx* ctx, const float cam0[16], const float proj0[16], const float cam1[16], const float proj1[16],
-                              const float viewport[4], const float nearFar[2], void* rgba0, void* rgba1, uint64_t pitch_bytes,
-                              int out_is_device)
+// msplat_render_stereo with a depth plane and / or an occluder plane per eye (include/msplat.h): one chain where msplat_render_stereo
+// runs as one, else msplat_render_layers view by view; the same pixels and planes either way
+int msplat_render_stereo_layers(msplat_ctx* ctx, const float cameraMat0[16], const float projMat0[16], const float cameraMat1[16],
+                                const float projMat1[16], const float viewport[4], const float nearFar[2], void* rgba0, void* rgba1,
+                                uint64_t pitch_bytes, float* depth0, float* depth1, uint64_t depth_pitch_bytes, const float* occluder0,
+                                const float* occluder1, uint64_t occluder_pitch_bytes, int out_is_device)
+{
+    const StereoPlanes pl{depth0, depth1, depth_pitch_bytes, occluder0, occluder1, occluder_pitch_bytes};
+    return submit_frame<true>(ctx, out_is_device && rgba0 && rgba1 && pl.paired(), cameraMat0, projMat0, cameraMat1, projMat1, viewport, nearFar,
+                        [=](const float* cam0, const float* proj0, const float* cam1, const float* proj1, const float* vp, const float* nf) {
+                            return render_stereo_impl(ctx, "msplat_render_stereo_layers", cam0, proj0, cam1, proj1, vp, nf, rgba0, rgba1,
+                                                      pitch_bytes, out_is_device, pl);
+                        });
+}
+
+static int render_stereo_impl(msplat_ctx* ctx, const char* who, const float cam0[16], const float proj0[16], const float cam1[16],
+                              const float proj1[16], const float viewport[4], const float nearFar[2], void* rgba0, void* rgba1,
+                              uint64_t pitch_bytes, int out_is_device, StereoPlanes pl)
 {
     FrameParams fp, fp1;
-    int rc = begin_frame(ctx, "msplat_render_stereo", true, rgba0 && rgba1 ? nullptr : "a target is NULL", cam0, proj0, viewport, nearFar, fp);
+    const char* missing = !(rgba0 && rgba1) ? "a target is NULL"
+                          : !pl.paired() ? "depth0 / depth1 are both given or both NULL, and so are occluder0 / occluder1" : nullptr;
+    int rc = begin_frame(ctx, who, true, missing, cam0, proj0, viewport, nearFar, fp);
     if (!rc) rc = make_frame_params(ctx, cam1, proj1, viewport, nearFar, fp1);
     if (rc) return rc;
+    const bool planes = pl.depth0 || pl.occluder0;
+    const char* who1 = planes ? who : nullptr;       // (the plain stereo call's views have always spoken as msplat_render)
     const bool batched = !ctx->banded && !ctx->point_mode && ctx->depth_bits == 0 && ctx->rop == 0 && ctx->N <= (1ull << 23) &&
                          2 * fp.tiles_y <= 256 && out_is_device;
     if (!batched) {      // the plain form: one render per view (host targets are filled one after the other anyway)
-        rc = render_impl(ctx, cam0, proj0, viewport, nearFar, rgba0, pitch_bytes, out_is_device);
+        rc = render_impl(ctx, cam0, proj0, viewport, nearFar, rgba0, pitch_bytes, out_is_device, pl.depth0, pl.depth_pitch, pl.occluder0,
+                         pl.occluder_pitch, who1);
         if (rc && rc != MSPLAT_ERR_PAIR_OVERFLOW_EARLIER) return rc;
-        const int rc1 = render_impl(ctx, cam1, proj1, viewport, nearFar, rgba1, pitch_bytes, out_is_device);
+        const int rc1 = render_impl(ctx, cam1, proj1, viewport, nearFar, rgba1, pitch_bytes, out_is_device, pl.depth1, pl.depth_pitch,
+                                    pl.occluder1, pl.occluder_pitch, who1);
         return rc1 ? rc1 : rc;
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     size_t tight = 0;
-    if ((rc = resolve_pitch(ctx, "msplat_render_stereo", fp, pitch_bytes, tight))) return rc;
+    if ((rc = resolve_pitch(ctx, who, fp, pitch_bytes, tight))) return rc;
+    if ((rc = plane_checks(ctx, who, fp, pl.depth0 != nullptr, pl.depth_pitch, pl.occluder0 != nullptr, pl.occluder_pitch))) return rc;
     if ((rc = ensure_stereo_ranks(ctx))) return rc;
     fp.views = 2;
     fp.rows_view = fp.tiles_y;
@@ -1797,7 +1860,8 @@ static int render_stereo_impl(msplat_ctx* ctx, const float cam0[16], const float
     std::memcpy(fp.view1, fp1.view, sizeof(fp.view1));
     std::memcpy(fp.proj1, fp1.proj, sizeof(fp.proj1));
     std::memcpy(fp.eye1, fp1.eye, sizeof(fp.eye1));
-    return render_frame(ctx, fp, rgba0, rgba1, pitch_bytes, tight, 1);
+    return render_frame(ctx, fp, rgba0, rgba1, pitch_bytes, tight, 1, DepthPlane{pl.depth0, (size_t)pl.depth_pitch, pl.depth1},
+                        OccluderPlane{pl.occluder0, (size_t)pl.occluder_pitch, pl.occluder1});
 }
 
 #include "msplat_getters.hip.inc"

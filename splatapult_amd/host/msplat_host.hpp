@@ -271,6 +271,54 @@ public:
         if (rc != MSPLAT_OK) std::fprintf(stderr, "[msplat][%c] RenderOccluded: %s\n", Level(rc), msplat_last_error(ctx));
     }
 
+    // RenderOccluded and RenderWithDepth in one frame (msplat_render_layers): the colour behind the caller's geometry plus the depth
+    // layer of the result -- the splats that pass the test over the occluder's values clamped to [0, 1].  Either plane may be NULL
+    // (the call without it); `depth` may be the occluder's own memory with the same pitch: a depth attachment read and written in
+    // place.  Uses the context of the latest Sort, like Render.  A device group has no layers frame.
+    template <class Mat4, class Vec4, class Vec2>
+    void RenderLayers(const Mat4& cameraMat, const Mat4& projMat, const Vec4& viewport, const Vec2& nearFar, float* depth,
+                      uint64_t depthPitchBytes, const float* occluder, uint64_t occluderPitchBytes)
+    {
+        static_assert(sizeof(Mat4) == 64 && sizeof(Vec4) == 16 && sizeof(Vec2) == 8, "glm-compatible layout expected");
+        if (!target) {
+            std::fprintf(stderr, "[msplat][E] RenderLayers: no render target set (SetRenderTarget)\n");
+            return;
+        }
+        if (group) {
+            std::fprintf(stderr, "[msplat][E] RenderLayers: a device group has no layers frame\n");
+            return;
+        }
+        const int rc = msplat_render_layers(ctx, reinterpret_cast<const float*>(&cameraMat), reinterpret_cast<const float*>(&projMat),
+                                            reinterpret_cast<const float*>(&viewport), reinterpret_cast<const float*>(&nearFar), target,
+                                            targetPitch, depth, depthPitchBytes, occluder, occluderPitchBytes, targetIsDevice ? 1 : 0);
+        if (rc != MSPLAT_OK) std::fprintf(stderr, "[msplat][%c] RenderLayers: %s\n", Level(rc), msplat_last_error(ctx));
+    }
+
+    // RenderStereo with RenderLayers' planes per eye (msplat_render_stereo_layers): the reference's XR frame -- geometry first, the
+    // splats blended over it under GL_LESS, per eye (app.cpp:570-607) -- in one chain of launches for device targets.  depth0 / depth1
+    // are both given or both NULL, and so are occluder0 / occluder1; each kind's pitch is shared by the eyes.
+    template <class Mat4, class Vec4, class Vec2>
+    void RenderStereoLayers(const Mat4& cameraMat0, const Mat4& projMat0, const Mat4& cameraMat1, const Mat4& projMat1, const Vec4& viewport,
+                            const Vec2& nearFar, void* target1, float* depth0, float* depth1, uint64_t depthPitchBytes,
+                            const float* occluder0, const float* occluder1, uint64_t occluderPitchBytes)
+    {
+        static_assert(sizeof(Mat4) == 64 && sizeof(Vec4) == 16 && sizeof(Vec2) == 8, "glm-compatible layout expected");
+        if (!target || !target1) {
+            std::fprintf(stderr, "[msplat][E] RenderStereoLayers: no render target set (SetRenderTarget / target1)\n");
+            return;
+        }
+        if (group) {
+            std::fprintf(stderr, "[msplat][E] RenderStereoLayers: a device group has no layers frame\n");
+            return;
+        }
+        const int rc = msplat_render_stereo_layers(ctx, reinterpret_cast<const float*>(&cameraMat0), reinterpret_cast<const float*>(&projMat0),
+                                                   reinterpret_cast<const float*>(&cameraMat1), reinterpret_cast<const float*>(&projMat1),
+                                                   reinterpret_cast<const float*>(&viewport), reinterpret_cast<const float*>(&nearFar), target,
+                                                   target1, targetPitch, depth0, depth1, depthPitchBytes, occluder0, occluder1,
+                                                   occluderPitchBytes, targetIsDevice ? 1 : 0);
+        if (rc != MSPLAT_OK) std::fprintf(stderr, "[msplat][%c] RenderStereoLayers: %s\n", Level(rc), msplat_last_error(ctx));
+    }
+
     // Both eyes of the latest Sort in one chain of launches (msplat_render_stereo): what the XR callback does with two Render
     // calls (app.cpp:603-607), for device targets at half the launches.  target1: the second eye's image (same pitch / kind as
     // the SetRenderTarget one, which receives the first eye).

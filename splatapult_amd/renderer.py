@@ -249,13 +249,14 @@ class SplatRenderer:
         The occluder plane (msplat_render_occluded: window depths of the caller's geometry, GL_LESS -- a splat with
         !(z_w < occluder) at a pixel is absent there) lives where the colour does too and is only read: occluder=(H, W) float32
         array with host output, occluder_ptr=int (rows of occluder_pitch_bytes, 0 = tight; valid until the frame has run) with
-        out_ptr.  A frame has a depth output or an occluder plane, not both: MsplatError(ERR_UNSUPPORTED)"""
+        out_ptr.  Render takes a depth output or an occluder plane, not both (MsplatError(ERR_UNSUPPORTED)): the frame with both
+        is RenderLayers'"""
         c, p, v, nf = self._args.load(cameraMat, projMat, viewport, nearFar)
         has_depth = (depth is not None and depth is not False) or depth_ptr is not None
         if occluder is not None or occluder_ptr is not None:
             if has_depth:
-                raise _capi.MsplatError(_capi.ERR_UNSUPPORTED, "a frame has either a depth output (msplat_render_depth) or an occluder "
-                                        "plane (msplat_render_occluded), not both")
+                raise _capi.MsplatError(_capi.ERR_UNSUPPORTED, "Render takes either a depth output (msplat_render_depth) or an occluder "
+                                        "plane (msplat_render_occluded), not both: that frame is RenderLayers' (msplat_render_layers)")
             if out_ptr is not None:
                 if occluder is not None:
                     raise ValueError("the occluder plane lives in the colour's memory space: pass occluder_ptr= with out_ptr=")
@@ -311,6 +312,78 @@ class SplatRenderer:
         _capi.check(self._ctx, self._lib.msplat_render_stereo(self._ctx, c0, p0, c1, p1, v, nf, outs[0].ctypes.data,
                                                               outs[1].ctypes.data, 0, 0))
         return outs
+
+    @staticmethod
+    def _host_plane(name, plane, H, W):
+        if not isinstance(plane, np.ndarray) or plane.dtype != np.float32 or plane.shape != (H, W) or not plane.flags["C_CONTIGUOUS"]:
+            raise ValueError("%s takes a C-contiguous float32 array of shape (%d, %d)" % (name, H, W))
+        return plane
+
+    def RenderLayers(self, cameraMat, projMat, viewport, nearFar, out=None, out_ptr=None, pitch_bytes=0, depth=None, depth_ptr=None,
+                     depth_pitch_bytes=0, occluder=None, occluder_ptr=None, occluder_pitch_bytes=0):
+        """msplat_render_layers: Render's occluder plane and depth output in ONE frame -- the colour is the occluded frame's, the
+        depth plane the expected window depth of the splats that pass the test over the occluder's values clamped to [0, 1]
+        (min(fma(T, d0, sum T_i w_i z_i), 1)).  The arguments are Render's; a plane that is not given degrades the call to
+        msplat_render_depth / msplat_render_occluded / msplat_render.  The depth plane may BE the occluder plane (the same array,
+        or the same pointer and pitch): a depth attachment read and written in place.
+        Host output returns the image, or (image, depth) when a depth plane was asked for; device output returns None."""
+        c, p, v, nf = self._args.load(cameraMat, projMat, viewport, nearFar)
+        if out_ptr is not None:
+            if (depth is not None and depth is not False) or occluder is not None:
+                raise ValueError("the planes live in the colour's memory space: pass depth_ptr= / occluder_ptr= with out_ptr=")
+            _capi.check(self._ctx, self._lib.msplat_render_layers(self._ctx, c, p, v, nf, C.c_void_p(out_ptr), pitch_bytes,
+                                                                  C.c_void_p(depth_ptr), depth_pitch_bytes, C.c_void_p(occluder_ptr),
+                                                                  occluder_pitch_bytes, 1))
+            return None
+        if depth_ptr is not None or occluder_ptr is not None:
+            raise ValueError("the planes live in the colour's memory space: pass depth= / occluder= with host output")
+        out = _host_frame(self._fb_format, self._args.vp, out, self._load)
+        H, W = out.shape[:2]
+        if depth is False:
+            depth = None
+        if depth is True:
+            depth = np.empty((H, W), np.float32)
+        d = self._host_plane("depth=", depth, H, W).ctypes.data if depth is not None else None
+        o = self._host_plane("occluder=", occluder, H, W).ctypes.data if occluder is not None else None
+        _capi.check(self._ctx, self._lib.msplat_render_layers(self._ctx, c, p, v, nf, out.ctypes.data, 0, d, 0, o, 0, 0))
+        return out if depth is None else (out, depth)
+
+    def RenderStereoLayers(self, cameraMats, projMats, viewport, nearFar, out_ptrs=None, pitch_bytes=0, depth_ptrs=None,
+                           depth_pitch_bytes=0, occluder_ptrs=None, occluder_pitch_bytes=0, depth=False, occluders=None):
+        """msplat_render_stereo_layers: RenderStereo with RenderLayers' planes per eye; each eye's colour and depth plane are
+        RenderLayers' with that eye's matrices.  out_ptrs (two device pointers; asynchronous) with depth_ptrs / occluder_ptrs --
+        pairs of device pointers, one pitch per kind, None = no such plane -- runs as one chain; returns None.
+        Without out_ptrs host arrays are used, view by view: occluders = a pair of (H, W) float32 arrays or None, depth = True to
+        have the depth planes allocated (or a pair of arrays to fill); returns [image0, image1], or ([image0, image1], [depth0,
+        depth1]) when depth planes were asked for.  Not in target mode "load" (as for RenderStereo)."""
+        a0, a1 = self._args, getattr(self, "_args1", None)
+        if a1 is None:
+            a1 = self._args1 = _FrameArgs()
+        c0, p0, v, nf = a0.load(cameraMats[0], projMats[0], viewport, nearFar)
+        c1, p1, _, _ = a1.load(cameraMats[1], projMats[1], viewport, nearFar)
+        fn = self._lib.msplat_render_stereo_layers
+        if out_ptrs is not None:
+            if (depth is not None and depth is not False) or occluders is not None:
+                raise ValueError("the planes live in the colour's memory space: pass depth_ptrs= / occluder_ptrs= with out_ptrs=")
+            d0, d1 = depth_ptrs if depth_ptrs is not None else (None, None)
+            o0, o1 = occluder_ptrs if occluder_ptrs is not None else (None, None)
+            _capi.check(self._ctx, fn(self._ctx, c0, p0, c1, p1, v, nf, C.c_void_p(out_ptrs[0]), C.c_void_p(out_ptrs[1]), pitch_bytes,
+                                      C.c_void_p(d0), C.c_void_p(d1), depth_pitch_bytes, C.c_void_p(o0), C.c_void_p(o1),
+                                      occluder_pitch_bytes, 1))
+            return None
+        if depth_ptrs is not None or occluder_ptrs is not None:
+            raise ValueError("the planes live in the colour's memory space: pass depth= / occluders= with host output")
+        outs = [_host_frame(self._fb_format, a0.vp, None, self._load), _host_frame(self._fb_format, a0.vp, None, self._load)]
+        H, W = outs[0].shape[:2]
+        if depth is False:
+            depth = None
+        if depth is True:
+            depth = [np.empty((H, W), np.float32), np.empty((H, W), np.float32)]
+        d = [self._host_plane("depth=", z, H, W).ctypes.data for z in depth] if depth is not None else [None, None]
+        o = [self._host_plane("occluders=", z, H, W).ctypes.data for z in occluders] if occluders is not None else [None, None]
+        _capi.check(self._ctx, fn(self._ctx, c0, p0, c1, p1, v, nf, outs[0].ctypes.data, outs[1].ctypes.data, 0, d[0], d[1], 0, o[0], o[1],
+                                  0, 0))
+        return outs if depth is None else (outs, list(depth))
 
     # -- extensions -------------------------------------------------------------------------
     def set_band(self, row_mod, row_rem, band_cull=False):
@@ -644,6 +717,14 @@ class SplatRendererGroup:
         out = _host_frame(self._fb_format, self._args.vp, out)
         _capi.check(self._g, self._lib.msplat_group_render(self._g, c, p, v, nf, out.ctypes.data, 0, 0), self._gerr)
         return out
+
+    def RenderLayers(self, *args, **kw):
+        """refused (MsplatError(ERR_UNSUPPORTED), before a device is touched): the planes of msplat_render_layers live on one device,
+        and the group's row gather moves the colour only"""
+        raise _capi.MsplatError(_capi.ERR_UNSUPPORTED, "a device group has no layers frame (msplat_render_layers / "
+                                "msplat_render_stereo_layers are per context): render depth and occluder planes with a SplatRenderer")
+
+    RenderStereoLayers = RenderLayers
 
     def set_target_mode(self, mode):
         """msplat_group_set_target_mode: "clear" or "premultiplied"; "load" is refused (MSPLAT_ERR_UNSUPPORTED: a rank that stages
