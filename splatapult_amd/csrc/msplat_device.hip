@@ -330,7 +330,8 @@ int grid_for(uint32_t nchunks, uint32_t cap)
 // ---- run-time value -> template argument.  A launch that exists for several values of a template parameter is written ONCE, in a
 // generic lambda that receives each value as a tag:  with_flag(ctx->full_sh, [&](auto SH) { ... kernel<SH.value> ... });
 // A dispatcher instantiates the lambda for every value it lists, nested dispatchers for the cross product of their lists: a selection
-// that is not a cross product (the splat compositor's six forms, the wide sort's upsweep) names its combinations at the call site.
+// that is not a cross product names its combinations at the call site (the wide sort's upsweep) or leaves out the ones that do not
+// exist with `if constexpr` (project_kernel's stores, the splat compositor's probe forms).
 template <bool B> using flag_t = std::bool_constant<B>;
 template <int V> using int_t = std::integral_constant<int, V>;
 
@@ -889,6 +890,22 @@ struct FrameArgs {            // the caller's four arrays, copied: a queued call
     }
 };
 
+// A frame's planes in the colour's memory space, each kind with one pitch: the depth plane it writes (msplat_render_depth; NULL: none)
+// and the plane of window depths its splats are tested against (msplat_render_occluded; NULL: no test, read-only).  [1]: the second
+// view's planes of two views in one chain, as d_out1 is its target.  Copied by value into a queued call
+struct FramePlanes {
+    float* depth[2] = {nullptr, nullptr};
+    const float* occluder[2] = {nullptr, nullptr};
+    size_t depth_pitch = 0, occluder_pitch = 0;
+    bool any() const { return depth[0] || occluder[0]; }
+    bool paired() const { return !depth[0] == !depth[1] && !occluder[0] == !occluder[1]; }
+    FramePlanes view(int v) const { return {{depth[v]}, {occluder[v]}, depth_pitch, occluder_pitch}; }      // one view's, for a frame of its own
+};
+
+// "this frame goes to a draw-order compositor" (sprites, the emulated depth buffer, the target emulation), not to the front-to-back
+// splat compositor: no work queue, no two passes, no two views in one chain, no planes
+static bool draw_order_frame(const msplat_ctx* ctx) { return ctx->point_mode || ctx->depth_bits != 0 || ctx->rop != 0; }
+
 // result of a queued call: the first real failure is kept for msplat_synchronize; MSPLAT_ERR_PAIR_OVERFLOW_EARLIER (a past frame
 // was composited from truncated lists; the buffer has grown since) is kept as a warning for the next msplat_synchronize /
 // msplat_stream_wait, which return it once
@@ -962,10 +979,6 @@ static int with_pending_overflow(msplat_ctx* ctx, Work&& work)
 }  // extern "C++"
 
 static int sort_impl(msplat_ctx* ctx, const float cameraMat[16], const float projMat[16], const float viewport[4], const float nearFar[2]);
-static int render_impl(msplat_ctx* ctx, const float cameraMat[16], const float projMat[16], const float viewport[4],
-                       const float nearFar[2], void* rgba, uint64_t pitch_bytes, int out_is_device, float* depth = nullptr,
-                       uint64_t depth_pitch_bytes = 0, const float* occluder = nullptr, uint64_t occluder_pitch_bytes = 0,
-                       const char* who = nullptr);
 
 int msplat_sort(msplat_ctx* ctx, const float cameraMat[16], const float projMat[16],
                 const float viewport[4], const float nearFar[2])
@@ -1138,7 +1151,7 @@ static bool occlusion_plan(msplat_ctx* ctx, const FrameParams& fp, bool stereo, 
 {
     const size_t nbins = (size_t)std::max(fp.tiles_x * fp.tiles_y, 0);
     // (scan_free: the chunk offset of pass 1's column pass exists in the scan-free form only; kOccSatMax: the table of unfinished bins)
-    const bool eligible = !stereo && !ctx->point_mode && ctx->depth_bits == 0 && ctx->rop == 0 && !ctx->probe_on && ctx->scan_free &&
+    const bool eligible = !stereo && !draw_order_frame(ctx) && !ctx->probe_on && ctx->scan_free &&
                           nbins != 0 && (fp.tiles_x + 1) * (fp.tiles_y + 1) <= kOccSatMax;
     const TwoPassFrame frame{ctx->two_pass_mode, eligible, ctx->cfg.frame_mode == MSPLAT_FRAMES_IN_FLIGHT, ctx->N, host_word(ctx, kHostV), nbins};
     const TwoPassFeedback fb{host_word(ctx, kHostPass1Pairs), host_word(ctx, kHostUnfinishedBins), host_word(ctx, kHostPass2Pairs),
@@ -1181,12 +1194,7 @@ struct RenderChain {
     void *d_out, *d_out1;
     size_t pitch;
     bool async_overflow_flag;
-    float* d_depth;              // msplat_render_depth: the depth plane (NULL: a plain Render) and its pitch
-    size_t depth_pitch;
-    const float* d_occluder;     // msplat_render_occluded: the plane the splats are depth-tested against (NULL: none) and its pitch
-    size_t occluder_pitch;
-    float* d_depth1;             // two views in one chain (msplat_render_stereo_layers): the second view's planes, as d_out1 is its target
-    const float* d_occluder1;
+    FramePlanes planes;          // device memory
     // the compositor's schedule, decided where the bins are ordered (issue_binning) and used by issue_compositor
     bool ordered = true;
     uint32_t comp_items = 0, comp_pool = 0;
@@ -1208,7 +1216,7 @@ static void issue_projection(RenderChain& rc, int mode, float occ_frac)
     }
     ProjParams pp = proj_params(fp);
     uint32_t* zq = (mode != PROJ_LISTED && ctx->depth_bits) ? (uint32_t*)ctx->zq.p : nullptr;
-    if (rc.d_depth || rc.d_occluder) {
+    if (rc.planes.any()) {
         // a depth frame, or one tested against an occluder plane: every projection of the frame leaves z_w = (float)(0.5 ndc.z + 0.5)
         // per rank -- quantise_depth's 32-bit form is that float's bits (one product by 0.5, exact, and one rounded sum)
         pp.depth_bits = 32;
@@ -1307,7 +1315,7 @@ static void issue_binning(RenderChain& rc, int keep_overflow, int occ_pass)
     // The heaviest-first order of the bins only pays when every work item has its own wave (the hardware then starts the
     // waves in item order: 83 -> 97 us without it at config 2); persistent waves that pull items from the queue balance
     // themselves: they walk the bins in storage order (`tile_order` + 65536 holds 0, 1, 2, ...).
-    const bool wave_comp = !ctx->point_mode && ctx->depth_bits == 0 && ctx->rop == 0;
+    const bool wave_comp = !draw_order_frame(ctx);
     const uint32_t comp_items = (uint32_t)ntiles * 4u;
     // (every item on its own wave up to 20 k items, 40 k for two views in one chain: BASELINE configs[4] has 2 x 17.6 k)
     const uint32_t comp_pool = (ctx->comp_waves_auto && comp_items <= (stereo ? 40960u : 20480u)) ? comp_items : (uint32_t)ctx->comp_waves;
@@ -1353,6 +1361,8 @@ static int issue_compositor(RenderChain& rc, int occ_pass, int ev_c0, int ev_c1)
     uint32_t* fin = occ_pass ? (uint32_t*)ctx->occ_fin.p : nullptr;
     float4* state = occ_pass ? (float4*)ctx->occ_state.p : nullptr;
     const uint32_t* d_nbins = occ_pass == 2 ? occ + kOccUnfinished : nullptr;      // second chain of a two-pass frame: the listed unfinished bins
+    const FramePlanes& pl = rc.planes;
+    const bool draw_order = draw_order_frame(ctx);
     // the target's pixel format (kFb* = MSPLAT_FB_*: msplat_create let nothing else in); only the kernels' load_px / store_px differ
     auto with_format = [&](auto&& f) { with_int<kFbF16, kFbUnorm8, kFbSrgb8, kFbF32>(ctx->cfg.fb_format, f); };
 
@@ -1361,7 +1371,6 @@ static int issue_compositor(RenderChain& rc, int occ_pass, int ev_c0, int ev_c1)
     // what msplat_debug_get_compositor_launch reports (host bookkeeping only).  The second pass of a two-pass frame keeps pass 1's
     // numbers: its item count (the unfinished bins) exists on the device alone, its grid is computed like pass 1's
     if (ntiles > 0 && occ_pass != 2) {
-        const bool draw_order = ctx->point_mode || ctx->depth_bits != 0 || ctx->rop != 0;
         ctx->comp_launch[0] = draw_order ? (uint32_t)ntiles * 4u : comp_items;
         ctx->comp_launch[1] = draw_order ? (uint32_t)cgrid : std::min(comp_items, comp_pool);
         ctx->comp_launch[2] = ordered ? 1u : 0u;
@@ -1369,7 +1378,7 @@ static int issue_compositor(RenderChain& rc, int occ_pass, int ev_c0, int ev_c1)
     }
     // (frames in flight: serialising the compositor launches of the contexts sharing a cloud with an event
     //  gate was measured r1 -- no gain over letting the hardware queues interleave them, dropped)
-    if (ntiles > 0 && ctx->probe_on && ctx->probe.p && (ctx->point_mode || ctx->depth_bits != 0 || ctx->rop != 0))
+    if (ntiles > 0 && ctx->probe_on && ctx->probe.p && draw_order)
         // the draw-order compositors do not write the probe: leave zeros, not an earlier frame's counters
         HIP_TRY(ctx, hipMemsetAsync(ctx->probe.p, 0, (size_t)ntiles * 8 * kProbeWords * sizeof(uint32_t), s));
     if (ntiles > 0 && ctx->point_mode) {
@@ -1382,7 +1391,7 @@ static int issue_compositor(RenderChain& rc, int occ_pass, int ev_c0, int ev_c1)
                                pitch, fp, cap, (const uint32_t*)ctx->tile_order.p, d_queue, (uint32_t)ntiles * 4u);
         });
         ctx->comp_kernel_timed = false;
-    } else if (ntiles > 0 && (ctx->depth_bits != 0 || ctx->rop != 0)) {
+    } else if (ntiles > 0 && draw_order) {
         // emulated depth buffer: draw-order walk, no early termination
         with_format([&](auto FMT) {
             with_int<kTargetLoad, kTargetPremultiplied, kTargetClear>(ctx->target_mode, [&](auto TM) {
@@ -1409,14 +1418,9 @@ static int issue_compositor(RenderChain& rc, int occ_pass, int ev_c0, int ev_c1)
         const int prio_mode = ordered ? 1 : 0;
         const int grid = (int)std::min<uint32_t>(comp_items, comp_pool);
         const CompParams cp = comp_params(fp);
-        const CompExtra ex{d_out1, fin, state, d_nbins, probe, (const float*)ctx->zq.p, rc.d_depth, rc.depth_pitch,
-                           occ_pass ? (float*)ctx->occ_zstate.p : nullptr, rc.d_occluder, rc.occluder_pitch, rc.d_occluder1, rc.d_depth1};
+        const CompExtra ex{d_out1, fin, state, d_nbins, probe, (const float*)ctx->zq.p, pl.depth[0], pl.depth_pitch,
+                           occ_pass ? (float*)ctx->occ_zstate.p : nullptr, pl.occluder[0], pl.occluder_pitch, pl.occluder[1], pl.depth[1]};
         const int prio = occ_pass == 2 ? 0 : prio_mode;
-        // six of the twelve (OCC, TWO_VIEWS, PROBE) forms exist per format
-        // (occlusion_plan never chooses two passes for two views in one chain or while the probe is on)
-        // and the four without the probe once more per non-CLEAR target mode (render_frame refuses the probe with those);
-        // a frame with a depth plane, an occluder plane or both (no probe: plane_checks) has the three passes per target mode, and
-        // the one pass of two views in one chain
         auto composite = [&](auto OCC, auto TWO, auto PROBE, auto TM, auto DEPTH, auto ZTEST) {
             with_format([&](auto FMT) {
                 hipExtLaunchKernelGGL((composite_kernel<FMT.value, OCC.value, TWO.value, PROBE.value, TM.value, DEPTH.value, ZTEST.value>),
@@ -1426,30 +1430,21 @@ static int issue_compositor(RenderChain& rc, int occ_pass, int ev_c0, int ev_c1)
         };
         constexpr flag_t<true> yes{};
         constexpr flag_t<false> no{};
-        constexpr int_t<kTargetClear> clear{};
-        if (rc.d_occluder || rc.d_depth)
+        // The forms that exist per format: (OCC, TWO_VIEWS) = one pass, either pass of a two-pass frame, or the one pass of two views in
+        // one chain (occlusion_plan never chooses two passes for those); each per target mode; each of those with any set of planes --
+        // or, for one pass without planes in MSPLAT_TARGET_CLEAR, with the probe (render_frame / plane_checks refuse it elsewhere)
+        auto form = [&](auto OCC, auto TWO) {
             with_int<kTargetLoad, kTargetPremultiplied, kTargetClear>(ctx->target_mode, [&](auto TM) {
-                auto planes = [&](auto OCC, auto TWO) {
-                    if (rc.d_occluder && rc.d_depth) composite(OCC, TWO, no, TM, yes, yes);
-                    else if (rc.d_occluder) composite(OCC, TWO, no, TM, no, yes);
-                    else composite(OCC, TWO, no, TM, yes, no);
-                };
-                if (stereo) planes(int_t<0>{}, yes);
-                else with_int<1, 2, 0>(occ_pass, [&](auto OCC) { planes(OCC, no); });
+                if constexpr (OCC.value == 0 && TM.value == kTargetClear) {
+                    if (probe && !pl.any()) return composite(OCC, TWO, yes, TM, no, no);
+                }
+                with_flag(!!pl.depth[0], [&](auto DEPTH) {
+                    with_flag(!!pl.occluder[0], [&](auto ZTEST) { composite(OCC, TWO, no, TM, DEPTH, ZTEST); });
+                });
             });
-        else if (ctx->target_mode != MSPLAT_TARGET_CLEAR)
-            with_int<kTargetLoad, kTargetPremultiplied>(ctx->target_mode, [&](auto TM) {
-                if (occ_pass == 1) composite(int_t<1>{}, no, no, TM, no, no);
-                else if (occ_pass == 2) composite(int_t<2>{}, no, no, TM, no, no);
-                else if (stereo) composite(int_t<0>{}, yes, no, TM, no, no);
-                else composite(int_t<0>{}, no, no, TM, no, no);
-            });
-        else if (occ_pass == 1) composite(int_t<1>{}, no, no, clear, no, no);
-        else if (occ_pass == 2) composite(int_t<2>{}, no, no, clear, no, no);
-        else if (stereo && probe) composite(int_t<0>{}, yes, yes, clear, no, no);
-        else if (stereo) composite(int_t<0>{}, yes, no, clear, no, no);
-        else if (probe) composite(int_t<0>{}, no, yes, clear, no, no);
-        else composite(int_t<0>{}, no, no, clear, no, no);
+        };
+        if (stereo) form(int_t<0>{}, yes);
+        else with_int<1, 2, 0>(occ_pass, [&](auto OCC) { form(OCC, no); });
         ctx->comp_kernel_timed = timed;
     } else {
         ctx->comp_kernel_timed = false;
@@ -1480,23 +1475,10 @@ static void issue_occlusion_gate(RenderChain& rc)
                        use_boxes ? (const uint32_t*)ctx->occ_boxdead.p : (const uint32_t*)nullptr, boxwords);
 }
 
-// the depth plane of a msplat_render_depth frame in device memory (p == NULL: a plain Render)
-struct DepthPlane {
-    float* p = nullptr;
-    size_t pitch = 0;
-    float* p1 = nullptr;         // the second view's plane of two views in one chain (same pitch)
-};
-
-// the plane of window depths a msplat_render_occluded frame is tested against, in device memory (p == NULL: no test); read-only
-struct OccluderPlane {
-    const float* p = nullptr;
-    size_t pitch = 0;
-    const float* p1 = nullptr;   // the second view's plane of two views in one chain (same pitch)
-};
-
-static int launch_render(msplat_ctx* ctx, const FrameParams& fp, void* d_out, size_t pitch, bool async_overflow_flag,
-                         void* d_out1 = nullptr, RenderPlan* plan = nullptr, DepthPlane depth = DepthPlane{},
-                         OccluderPlane occluder = OccluderPlane{})
+// d_out1: the second view's target of two in one chain (else NULL); plan: a host-output frame's, kept over its retries (else NULL);
+// pl: the frame's planes in device memory
+static int launch_render(msplat_ctx* ctx, const FrameParams& fp, void* d_out, void* d_out1, size_t pitch, bool async_overflow_flag,
+                         RenderPlan* plan, const FramePlanes& pl)
 {
     hipStream_t s = ctx->stream;
     const bool stereo = fp.views == 2;
@@ -1504,8 +1486,7 @@ static int launch_render(msplat_ctx* ctx, const FrameParams& fp, void* d_out, si
     const uint32_t N = stereo ? (uint32_t)(2 * ctx->N + 64) : (uint32_t)ctx->N;
     RenderChain rc{ctx, fp, s, stereo, N, counters + kCntV, counters + kCntD, counters + kCntOverflow, (uint32_t*)ctx->queue.p,
                    stereo ? counters + kCntVframe2 : counters + kCntV, (uint32_t*)ctx->occ.p, fp.tiles_x * fp.tiles_y, (uint32_t)ctx->pair_cap,
-                   false, 0, (int)std::max(1u, div_up(N, kProjThreads)), d_out, d_out1, pitch, async_overflow_flag, depth.p, depth.pitch,
-                   occluder.p, occluder.pitch, depth.p1, occluder.p1};
+                   false, 0, (int)std::max(1u, div_up(N, kProjThreads)), d_out, d_out1, pitch, async_overflow_flag, pl};
     // Two-pass frame with occlusion feedback (msplat_occlusion.hip.h): the nearest R1 splats first, then only what the bins
     // they did not saturate still need.  Same pixels; chosen once per Render (occlusion_plan).  The retries of a host-output
     // frame whose pair buffer overflowed reuse the plan AND count as the same Render: the sampling counter, the two-pass
@@ -1519,11 +1500,11 @@ static int launch_render(msplat_ctx* ctx, const FrameParams& fp, void* d_out, si
         ctx->render_calls++;
     }
     const bool two_pass = plan->two_pass;
-    if (depth.p || occluder.p) {
+    if (pl.any()) {
         // z_w per rank; (depth) the accumulator plane two passes hand over.  (A buffer that has to grow is freed first: hipFree waits for the
         // frames that still read it.)
         int arc = buf_alloc(ctx, ctx->zq, std::max<uint64_t>(std::max(ctx->rank_cap, ctx->N), 1) * 4);
-        if (!arc && two_pass && depth.p) arc = buf_alloc(ctx, ctx->occ_zstate, (size_t)fp.width * fp.height * 4 + 64);
+        if (!arc && two_pass && pl.depth[0]) arc = buf_alloc(ctx, ctx->occ_zstate, (size_t)fp.width * fp.height * 4 + 64);
         if (arc) return arc;
     }
     const bool timed = rc.timed = ctx->ev_ok && ((ctx->render_calls - 1) % ctx->timing_stride) == 0;
@@ -1566,52 +1547,6 @@ static int launch_render(msplat_ctx* ctx, const FrameParams& fp, void* d_out, si
     return MSPLAT_OK;
 }
 
-int msplat_render(msplat_ctx* ctx, const float cameraMat[16], const float projMat[16],
-                  const float viewport[4], const float nearFar[2],
-                  void* rgba, uint64_t pitch_bytes, int out_is_device)
-{
-    return submit_frame<false>(ctx, out_is_device && rgba, cameraMat, projMat, cameraMat, projMat, viewport, nearFar,
-                        [=](const float* cam, const float* proj, const float*, const float*, const float* vp, const float* nf) {
-                            return render_impl(ctx, cam, proj, vp, nf, rgba, pitch_bytes, out_is_device);
-                        });
-}
-
-// msplat_render plus a per-pixel depth plane (include/msplat.h); depth == NULL is msplat_render
-int msplat_render_depth(msplat_ctx* ctx, const float cameraMat[16], const float projMat[16], const float viewport[4],
-                        const float nearFar[2], void* rgba, uint64_t pitch_bytes, float* depth, uint64_t depth_pitch_bytes,
-                        int out_is_device)
-{
-    return submit_frame<false>(ctx, out_is_device && rgba, cameraMat, projMat, cameraMat, projMat, viewport, nearFar,
-                        [=](const float* cam, const float* proj, const float*, const float*, const float* vp, const float* nf) {
-                            return render_impl(ctx, cam, proj, vp, nf, rgba, pitch_bytes, out_is_device, depth, depth_pitch_bytes);
-                        });
-}
-
-// msplat_render with GL_LESS against a caller's plane of window depths (include/msplat.h); occluder == NULL is msplat_render
-int msplat_render_occluded(msplat_ctx* ctx, const float cameraMat[16], const float projMat[16], const float viewport[4],
-                           const float nearFar[2], void* rgba, uint64_t pitch_bytes, const float* occluder,
-                           uint64_t occluder_pitch_bytes, int out_is_device)
-{
-    return submit_frame<false>(ctx, out_is_device && rgba, cameraMat, projMat, cameraMat, projMat, viewport, nearFar,
-                        [=](const float* cam, const float* proj, const float*, const float*, const float* vp, const float* nf) {
-                            return render_impl(ctx, cam, proj, vp, nf, rgba, pitch_bytes, out_is_device, nullptr, 0, occluder,
-                                               occluder_pitch_bytes);
-                        });
-}
-
-// msplat_render_occluded and msplat_render_depth in one frame (include/msplat.h): the depth plane is blended over the occluder's
-// values.  A NULL plane degrades to the call without it
-int msplat_render_layers(msplat_ctx* ctx, const float cameraMat[16], const float projMat[16], const float viewport[4],
-                         const float nearFar[2], void* rgba, uint64_t pitch_bytes, float* depth, uint64_t depth_pitch_bytes,
-                         const float* occluder, uint64_t occluder_pitch_bytes, int out_is_device)
-{
-    return submit_frame<false>(ctx, out_is_device && rgba, cameraMat, projMat, cameraMat, projMat, viewport, nearFar,
-                        [=](const float* cam, const float* proj, const float*, const float*, const float* vp, const float* nf) {
-                            return render_impl(ctx, cam, proj, vp, nf, rgba, pitch_bytes, out_is_device, depth, depth_pitch_bytes, occluder,
-                                               occluder_pitch_bytes, "msplat_render_layers");
-                        });
-}
-
 // rows of the target: 0 = tightly packed (`tight` bytes)
 static int resolve_pitch(msplat_ctx* ctx, const char* who, const FrameParams& fp, uint64_t& pitch_bytes, size_t& tight)
 {
@@ -1652,35 +1587,37 @@ static int copy_host_rows(msplat_ctx* ctx, const FrameParams& fp, void* rgba, ui
 }
 
 // host output: render into an internal device framebuffer, copy back, grow the pair buffer on overflow.
-// depth (msplat_render_depth): a host plane of depth.pitch bytes per row, filled the same way from ctx->fbz -- every attempt writes
-// the whole internal plane, and the rows are copied after the one that did not overflow
-// occluder (msplat_render_occluded): the caller's host plane, staged into ctx->fbo once -- it is only read, so a retry reuses it
-static int render_to_host(msplat_ctx* ctx, const FrameParams& fp, void* rgba, uint64_t pitch_bytes, size_t tight, DepthPlane depth,
-                          OccluderPlane occluder)
+// pl.depth[0] (msplat_render_depth): a host plane of pl.depth_pitch bytes per row, filled the same way from ctx->fbz -- every attempt
+// writes the whole internal plane, and the rows are copied after the one that did not overflow
+// pl.occluder[0] (msplat_render_occluded): the caller's host plane, staged into ctx->fbo once -- it is only read, so a retry reuses it
+static int render_to_host(msplat_ctx* ctx, const FrameParams& fp, void* rgba, uint64_t pitch_bytes, size_t tight, const FramePlanes& pl)
 {
     int rc;
     if ((rc = buf_alloc(ctx, ctx->fb, tight * fp.height))) return rc;
     const size_t ztight = (size_t)fp.width * sizeof(float);
-    if (depth.p && (rc = buf_alloc(ctx, ctx->fbz, ztight * fp.height))) return rc;
-    const DepthPlane dz{depth.p ? (float*)ctx->fbz.p : nullptr, ztight};
-    if (occluder.p) {
-        if ((rc = buf_alloc(ctx, ctx->fbo, ztight * fp.height))) return rc;
-        if ((rc = copy_host_rows(ctx, fp, const_cast<float*>(occluder.p), occluder.pitch, ctx->fbo, ztight, false))) return rc;
+    FramePlanes staged{{}, {}, ztight, ztight};      // the internal planes the chain sees
+    if (pl.depth[0]) {
+        if ((rc = buf_alloc(ctx, ctx->fbz, ztight * fp.height))) return rc;
+        staged.depth[0] = (float*)ctx->fbz.p;
     }
-    const OccluderPlane oz{occluder.p ? (const float*)ctx->fbo.p : nullptr, ztight};
+    if (pl.occluder[0]) {
+        if ((rc = buf_alloc(ctx, ctx->fbo, ztight * fp.height))) return rc;
+        if ((rc = copy_host_rows(ctx, fp, const_cast<float*>(pl.occluder[0]), pl.occluder_pitch, ctx->fbo, ztight, false))) return rc;
+        staged.occluder[0] = (const float*)ctx->fbo.p;
+    }
     RenderPlan plan;
     for (int attempt = 0; attempt < 6; ++attempt) {
         // MSPLAT_TARGET_LOAD: the caller's rows are the destination -- before EVERY attempt, because blending over the target is
         // not idempotent: a retry would otherwise run over the half-blended frame of the attempt that overflowed
         if (ctx->target_mode == MSPLAT_TARGET_LOAD && (rc = copy_host_rows(ctx, fp, rgba, pitch_bytes, ctx->fb, tight, false))) return rc;
-        rc = launch_render(ctx, fp, ctx->fb.p, tight, false, nullptr, &plan, dz, oz);
+        rc = launch_render(ctx, fp, ctx->fb.p, nullptr, tight, false, &plan, staged);
         if (rc) return rc;
         uint32_t cnt[4];
         HIP_TRY(ctx, hipMemcpyAsync(cnt, ctx->counters.p, sizeof(cnt), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         if (cnt[kCntOverflow] == 0) {
             if ((rc = copy_host_rows(ctx, fp, rgba, pitch_bytes, ctx->fb, tight, true))) return rc;
-            return depth.p ? copy_host_rows(ctx, fp, depth.p, depth.pitch, ctx->fbz, ztight, true) : MSPLAT_OK;
+            return pl.depth[0] ? copy_host_rows(ctx, fp, pl.depth[0], pl.depth_pitch, ctx->fbz, ztight, true) : MSPLAT_OK;
         }
         // overflow: the word holds the required pair count
         const uint64_t need = (uint64_t)cnt[kCntOverflow] + (cnt[kCntOverflow] >> 2) + 1024;
@@ -1694,7 +1631,7 @@ static int render_to_host(msplat_ctx* ctx, const FrameParams& fp, void* rgba, ui
 
 // what every Render does once its FrameParams and pitch stand (rgba1: the second view of two in one chain)
 static int render_frame(msplat_ctx* ctx, const FrameParams& fp, void* rgba, void* rgba1, uint64_t pitch_bytes, size_t tight,
-                        int out_is_device, DepthPlane depth = DepthPlane{}, OccluderPlane occluder = OccluderPlane{})
+                        int out_is_device, const FramePlanes& pl)
 {
     int rc;
     ctx->last_fp = fp;
@@ -1704,65 +1641,105 @@ static int render_frame(msplat_ctx* ctx, const FrameParams& fp, void* rgba, void
     if (ctx->target_mode != MSPLAT_TARGET_CLEAR && ctx->probe_on)
         return fail(ctx, MSPLAT_ERR_UNSUPPORTED, "msplat_render: the tile probe (msplat_set_tile_probe) exists for MSPLAT_TARGET_CLEAR only");
     return with_pending_overflow(ctx, [&] {      // an EARLIER frame; this one is still rendered
-        const int r = out_is_device ? launch_render(ctx, fp, rgba, pitch_bytes, true, rgba1, nullptr, depth, occluder)
-                                    : render_to_host(ctx, fp, rgba, pitch_bytes, tight, depth, occluder);
+        const int r = out_is_device ? launch_render(ctx, fp, rgba, rgba1, pitch_bytes, true, nullptr, pl)
+                                    : render_to_host(ctx, fp, rgba, pitch_bytes, tight, pl);
         if (r == MSPLAT_OK) ctx->has_render = true;
         return r;
     });
 }
 
-// What a frame with a depth plane and / or an occluder plane checks once its FrameParams stand: the configurations without such an
-// instantiation are refused, the planes' pitches resolved (0 = tight).  `who`: the entry point the messages name
-static int plane_checks(msplat_ctx* ctx, const char* who, const FrameParams& fp, bool depth, uint64_t& depth_pitch_bytes, bool occluder,
-                        uint64_t& occluder_pitch_bytes)
+// One kind of plane in the messages.  Both come from the front-to-back compositor -- the depth plane from its accumulators, the test
+// from its inner loop -- so the draw-order compositors (sprites, depth test, target emulation) and the probe's instantiations have none
+struct PlaneKind {
+    const char* name;
+    const char* why[4];          // refused: a point cloud, msplat_set_depth_test, msplat_set_target_emulation, the tile probe
+};
+static const PlaneKind kDepthPlane{"depth", {"the context holds a point cloud (the sprite compositor has no depth output)",
+                                             "msplat_set_depth_test is on (the draw-order compositor has no depth output)",
+                                             "msplat_set_target_emulation is not MSPLAT_ROP_NONE (the draw-order compositor has no depth output)",
+                                             "the tile probe (msplat_set_tile_probe) has no instantiation with a depth output"}};
+static const PlaneKind kOccluderPlane{"occluder", {"the context holds a point cloud (the sprite compositor has no occluder test)",
+                                                   "msplat_set_depth_test is on (the draw-order compositor's emulated depth buffer starts at the clear value)",
+                                                   "msplat_set_target_emulation is not MSPLAT_ROP_NONE (the draw-order compositor has no occluder test)",
+                                                   "the tile probe (msplat_set_tile_probe) has no instantiation with an occluder test"}};
+
+// What a frame checks for a plane it was given, once its FrameParams stand: the configurations without such an instantiation are
+// refused, the plane's pitch resolved (0 = tight).  `who`: the entry point the messages name
+static int plane_checks(msplat_ctx* ctx, const char* who, const FrameParams& fp, const PlaneKind& kind, size_t& pitch_bytes)
 {
-    if (depth) {
-        // the plane comes from the front-to-back compositor's accumulators: the draw-order compositors (depth test, target
-        // emulation, sprites) and the probe's instantiations carry none
-        const char* why = ctx->point_mode ? "the context holds a point cloud (the sprite compositor has no depth output)"
-                          : ctx->depth_bits != 0 ? "msplat_set_depth_test is on (the draw-order compositor has no depth output)"
-                          : ctx->rop != MSPLAT_ROP_NONE ? "msplat_set_target_emulation is not MSPLAT_ROP_NONE (the draw-order compositor has no depth output)"
-                          : ctx->probe_on ? "the tile probe (msplat_set_tile_probe) has no instantiation with a depth output" : nullptr;
-        if (why) return fail(ctx, MSPLAT_ERR_UNSUPPORTED, "%s: %s", who, why);
-        const uint64_t ztight = (uint64_t)fp.width * sizeof(float);
-        if (depth_pitch_bytes == 0) depth_pitch_bytes = ztight;
-        if (depth_pitch_bytes < ztight || depth_pitch_bytes % sizeof(float) != 0)
-            return fail(ctx, MSPLAT_ERR_INVALID_ARG, "%s: depth pitch %llu too small / misaligned for width %d", who,
-                        (unsigned long long)depth_pitch_bytes, fp.width);
-    }
-    if (occluder) {
-        // the test lives in the front-to-back compositor's inner loop: the draw-order compositors (depth test, target emulation,
-        // sprites) and the probe's instantiations have none
-        const char* why = ctx->point_mode ? "the context holds a point cloud (the sprite compositor has no occluder test)"
-                          : ctx->depth_bits != 0 ? "msplat_set_depth_test is on (the draw-order compositor's emulated depth buffer starts at the clear value)"
-                          : ctx->rop != MSPLAT_ROP_NONE ? "msplat_set_target_emulation is not MSPLAT_ROP_NONE (the draw-order compositor has no occluder test)"
-                          : ctx->probe_on ? "the tile probe (msplat_set_tile_probe) has no instantiation with an occluder test" : nullptr;
-        if (why) return fail(ctx, MSPLAT_ERR_UNSUPPORTED, "%s: %s", who, why);
-        const uint64_t ztight = (uint64_t)fp.width * sizeof(float);
-        if (occluder_pitch_bytes == 0) occluder_pitch_bytes = ztight;
-        if (occluder_pitch_bytes < ztight || occluder_pitch_bytes % sizeof(float) != 0)
-            return fail(ctx, MSPLAT_ERR_INVALID_ARG, "%s: occluder pitch %llu too small / misaligned for width %d", who,
-                        (unsigned long long)occluder_pitch_bytes, fp.width);
-    }
+    const int cause = ctx->point_mode ? 0 : ctx->depth_bits != 0 ? 1 : ctx->rop != MSPLAT_ROP_NONE ? 2 : ctx->probe_on ? 3 : -1;
+    if (cause >= 0) return fail(ctx, MSPLAT_ERR_UNSUPPORTED, "%s: %s", who, kind.why[cause]);
+    const size_t ztight = (size_t)fp.width * sizeof(float);
+    if (pitch_bytes == 0) pitch_bytes = ztight;
+    if (pitch_bytes < ztight || pitch_bytes % sizeof(float) != 0)
+        return fail(ctx, MSPLAT_ERR_INVALID_ARG, "%s: %s pitch %llu too small / misaligned for width %d", who, kind.name,
+                    (unsigned long long)pitch_bytes, fp.width);
     return MSPLAT_OK;
 }
 
-// who: the entry point the messages name (NULL: the one that takes exactly these planes)
-static int render_impl(msplat_ctx* ctx, const float cameraMat[16], const float projMat[16],
-                       const float viewport[4], const float nearFar[2],
-                       void* rgba, uint64_t pitch_bytes, int out_is_device, float* depth, uint64_t depth_pitch_bytes,
-                       const float* occluder, uint64_t occluder_pitch_bytes, const char* who)
+// ... for the planes that are present: the depth plane first
+static int plane_checks(msplat_ctx* ctx, const char* who, const FrameParams& fp, FramePlanes& pl)
 {
-    if (!who) who = depth ? "msplat_render_depth" : occluder ? "msplat_render_occluded" : "msplat_render";
+    const int rc = pl.depth[0] ? plane_checks(ctx, who, fp, kDepthPlane, pl.depth_pitch) : MSPLAT_OK;
+    return rc || !pl.occluder[0] ? rc : plane_checks(ctx, who, fp, kOccluderPlane, pl.occluder_pitch);
+}
+
+// who: the entry point the messages name (NULL: the one that takes exactly these planes)
+static int render_impl(msplat_ctx* ctx, const char* who, const float cameraMat[16], const float projMat[16], const float viewport[4],
+                       const float nearFar[2], void* rgba, uint64_t pitch_bytes, int out_is_device, FramePlanes pl)
+{
+    if (!who) who = pl.depth[0] ? "msplat_render_depth" : pl.occluder[0] ? "msplat_render_occluded" : "msplat_render";
     FrameParams fp;
     int rc = begin_frame(ctx, who, true, rgba ? nullptr : "rgba is NULL", cameraMat, projMat, viewport, nearFar, fp);
     if (rc) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     size_t tight = 0;
     if ((rc = resolve_pitch(ctx, who, fp, pitch_bytes, tight))) return rc;
-    if ((rc = plane_checks(ctx, who, fp, depth != nullptr, depth_pitch_bytes, occluder != nullptr, occluder_pitch_bytes))) return rc;
-    return render_frame(ctx, fp, rgba, nullptr, pitch_bytes, tight, out_is_device, DepthPlane{depth, (size_t)depth_pitch_bytes},
-                        OccluderPlane{occluder, (size_t)occluder_pitch_bytes});
+    if ((rc = plane_checks(ctx, who, fp, pl))) return rc;
+    return render_frame(ctx, fp, rgba, nullptr, pitch_bytes, tight, out_is_device, pl);
+}
+
+// The four one-view entry points (include/msplat.h) are one frame: a NULL plane degrades to the call without it.  Queued when the
+// image stays on the device; the planes travel by value
+static int submit_render(msplat_ctx* ctx, const char* who, const float cameraMat[16], const float projMat[16], const float viewport[4],
+                         const float nearFar[2], void* rgba, uint64_t pitch_bytes, int out_is_device, FramePlanes pl)
+{
+    return submit_frame<false>(ctx, out_is_device && rgba, cameraMat, projMat, cameraMat, projMat, viewport, nearFar,
+                        [=](const float* cam, const float* proj, const float*, const float*, const float* vp, const float* nf) {
+                            return render_impl(ctx, who, cam, proj, vp, nf, rgba, pitch_bytes, out_is_device, pl);
+                        });
+}
+
+int msplat_render(msplat_ctx* ctx, const float cameraMat[16], const float projMat[16],
+                  const float viewport[4], const float nearFar[2],
+                  void* rgba, uint64_t pitch_bytes, int out_is_device)
+{
+    return submit_render(ctx, nullptr, cameraMat, projMat, viewport, nearFar, rgba, pitch_bytes, out_is_device, FramePlanes{});
+}
+
+// msplat_render plus a per-pixel depth plane
+int msplat_render_depth(msplat_ctx* ctx, const float cameraMat[16], const float projMat[16], const float viewport[4],
+                        const float nearFar[2], void* rgba, uint64_t pitch_bytes, float* depth, uint64_t depth_pitch_bytes,
+                        int out_is_device)
+{
+    return submit_render(ctx, nullptr, cameraMat, projMat, viewport, nearFar, rgba, pitch_bytes, out_is_device, {{depth}, {}, depth_pitch_bytes, 0});
+}
+
+// msplat_render with GL_LESS against a caller's plane of window depths
+int msplat_render_occluded(msplat_ctx* ctx, const float cameraMat[16], const float projMat[16], const float viewport[4],
+                           const float nearFar[2], void* rgba, uint64_t pitch_bytes, const float* occluder,
+                           uint64_t occluder_pitch_bytes, int out_is_device)
+{
+    return submit_render(ctx, nullptr, cameraMat, projMat, viewport, nearFar, rgba, pitch_bytes, out_is_device, {{}, {occluder}, 0, occluder_pitch_bytes});
+}
+
+// msplat_render_occluded and msplat_render_depth in one frame: the depth plane is blended over the occluder's values
+int msplat_render_layers(msplat_ctx* ctx, const float cameraMat[16], const float projMat[16], const float viewport[4],
+                         const float nearFar[2], void* rgba, uint64_t pitch_bytes, float* depth, uint64_t depth_pitch_bytes,
+                         const float* occluder, uint64_t occluder_pitch_bytes, int out_is_device)
+{
+    return submit_render(ctx, "msplat_render_layers", cameraMat, projMat, viewport, nearFar, rgba, pitch_bytes, out_is_device,
+                         {{depth}, {occluder}, depth_pitch_bytes, occluder_pitch_bytes});
 }
 
 // buffers indexed by draw-order rank, for 2 N + 64 ranks (two views in one chain)
@@ -1783,53 +1760,16 @@ static int ensure_stereo_ranks(msplat_ctx* ctx)
     return MSPLAT_OK;
 }
 
-// the planes of a two-view frame (msplat_render_stereo_layers): one pitch per kind, a plane per eye or none
-struct StereoPlanes {
-    float *depth0 = nullptr, *depth1 = nullptr;
-    uint64_t depth_pitch = 0;
-    const float *occluder0 = nullptr, *occluder1 = nullptr;
-    uint64_t occluder_pitch = 0;
-    bool paired() const { return !depth0 == !depth1 && !occluder0 == !occluder1; }
-};
-
-static int render_stereo_impl(msplat_ctx* ctx, const char* who, const float cam0[16], const float proj0[16], const float cam1[16],
-                              const float proj1[16], const float viewport[4], const float nearFar[2], void* rgba0, void* rgba1,
-                              uint64_t pitch_bytes, int out_is_device, StereoPlanes pl = StereoPlanes{});
-
 // Two views of ONE Sort (the reference's VR frame: Sort with the first eye, Render per eye -- src/app.cpp:603-607) as a single
 // chain of launches: projection, binning and compositing each run once over both views' work instead of twice in a row (half
 // the launches, twice the work per launch: 0.50 -> 0.44 ms at BASELINE configs[4]).  Per view the arithmetic, the bin lists and
 // the pixels are exactly those of two msplat_render calls.  Falls back to those two calls for banded contexts, point clouds,
 // depth-test / render-target emulation, clouds beyond 2^23 splats and viewports taller than 4096 (128 bin rows per view).
-int msplat_render_stereo(msplat_ctx* ctx, const float cameraMat0[16], const float projMat0[16], const float cameraMat1[16],
-                         const float projMat1[16], const float viewport[4], const float nearFar[2], void* rgba0, void* rgba1,
-                         uint64_t pitch_bytes, int out_is_device)
-{
-    return submit_frame<true>(ctx, out_is_device && rgba0 && rgba1, cameraMat0, projMat0, cameraMat1, projMat1, viewport, nearFar,
-                        [=](const float* cam0, const float* proj0, const float* cam1, const float* proj1, const float* vp, const float* nf) {
-                            return render_stereo_impl(ctx, "msplat_render_stereo", cam0, proj0, cam1, proj1, vp, nf, rgba0, rgba1, pitch_bytes,
-                                                      out_is_device);
-                        });
-}
-
-// msplat_render_stereo with a depth plane and / or an occluder plane per eye (include/msplat.h): one chain where msplat_render_stereo
-// runs as one, else msplat_render_layers view by view; the same pixels and planes either way
-int msplat_render_stereo_layers(msplat_ctx* ctx, const float cameraMat0[16], const float projMat0[16], const float cameraMat1[16],
-                                const float projMat1[16], const float viewport[4], const float nearFar[2], void* rgba0, void* rgba1,
-                                uint64_t pitch_bytes, float* depth0, float* depth1, uint64_t depth_pitch_bytes, const float* occluder0,
-                                const float* occluder1, uint64_t occluder_pitch_bytes, int out_is_device)
-{
-    const StereoPlanes pl{depth0, depth1, depth_pitch_bytes, occluder0, occluder1, occluder_pitch_bytes};
-    return submit_frame<true>(ctx, out_is_device && rgba0 && rgba1 && pl.paired(), cameraMat0, projMat0, cameraMat1, projMat1, viewport, nearFar,
-                        [=](const float* cam0, const float* proj0, const float* cam1, const float* proj1, const float* vp, const float* nf) {
-                            return render_stereo_impl(ctx, "msplat_render_stereo_layers", cam0, proj0, cam1, proj1, vp, nf, rgba0, rgba1,
-                                                      pitch_bytes, out_is_device, pl);
-                        });
-}
-
+// pl: a depth plane and / or an occluder plane per eye, one pitch per kind (msplat_render_stereo_layers); the fallback is then
+// msplat_render_layers view by view -- the same pixels and planes either way
 static int render_stereo_impl(msplat_ctx* ctx, const char* who, const float cam0[16], const float proj0[16], const float cam1[16],
                               const float proj1[16], const float viewport[4], const float nearFar[2], void* rgba0, void* rgba1,
-                              uint64_t pitch_bytes, int out_is_device, StereoPlanes pl)
+                              uint64_t pitch_bytes, int out_is_device, FramePlanes pl)
 {
     FrameParams fp, fp1;
     const char* missing = !(rgba0 && rgba1) ? "a target is NULL"
@@ -1837,22 +1777,18 @@ static int render_stereo_impl(msplat_ctx* ctx, const char* who, const float cam0
     int rc = begin_frame(ctx, who, true, missing, cam0, proj0, viewport, nearFar, fp);
     if (!rc) rc = make_frame_params(ctx, cam1, proj1, viewport, nearFar, fp1);
     if (rc) return rc;
-    const bool planes = pl.depth0 || pl.occluder0;
-    const char* who1 = planes ? who : nullptr;       // (the plain stereo call's views have always spoken as msplat_render)
-    const bool batched = !ctx->banded && !ctx->point_mode && ctx->depth_bits == 0 && ctx->rop == 0 && ctx->N <= (1ull << 23) &&
-                         2 * fp.tiles_y <= 256 && out_is_device;
+    const bool batched = !ctx->banded && !draw_order_frame(ctx) && ctx->N <= (1ull << 23) && 2 * fp.tiles_y <= 256 && out_is_device;
     if (!batched) {      // the plain form: one render per view (host targets are filled one after the other anyway)
-        rc = render_impl(ctx, cam0, proj0, viewport, nearFar, rgba0, pitch_bytes, out_is_device, pl.depth0, pl.depth_pitch, pl.occluder0,
-                         pl.occluder_pitch, who1);
+        const char* who1 = pl.any() ? who : nullptr;     // (the plain stereo call's views have always spoken as msplat_render)
+        rc = render_impl(ctx, who1, cam0, proj0, viewport, nearFar, rgba0, pitch_bytes, out_is_device, pl.view(0));
         if (rc && rc != MSPLAT_ERR_PAIR_OVERFLOW_EARLIER) return rc;
-        const int rc1 = render_impl(ctx, cam1, proj1, viewport, nearFar, rgba1, pitch_bytes, out_is_device, pl.depth1, pl.depth_pitch,
-                                    pl.occluder1, pl.occluder_pitch, who1);
+        const int rc1 = render_impl(ctx, who1, cam1, proj1, viewport, nearFar, rgba1, pitch_bytes, out_is_device, pl.view(1));
         return rc1 ? rc1 : rc;
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     size_t tight = 0;
     if ((rc = resolve_pitch(ctx, who, fp, pitch_bytes, tight))) return rc;
-    if ((rc = plane_checks(ctx, who, fp, pl.depth0 != nullptr, pl.depth_pitch, pl.occluder0 != nullptr, pl.occluder_pitch))) return rc;
+    if ((rc = plane_checks(ctx, who, fp, pl))) return rc;
     if ((rc = ensure_stereo_ranks(ctx))) return rc;
     fp.views = 2;
     fp.rows_view = fp.tiles_y;
@@ -1860,8 +1796,35 @@ static int render_stereo_impl(msplat_ctx* ctx, const char* who, const float cam0
     std::memcpy(fp.view1, fp1.view, sizeof(fp.view1));
     std::memcpy(fp.proj1, fp1.proj, sizeof(fp.proj1));
     std::memcpy(fp.eye1, fp1.eye, sizeof(fp.eye1));
-    return render_frame(ctx, fp, rgba0, rgba1, pitch_bytes, tight, 1, DepthPlane{pl.depth0, (size_t)pl.depth_pitch, pl.depth1},
-                        OccluderPlane{pl.occluder0, (size_t)pl.occluder_pitch, pl.occluder1});
+    return render_frame(ctx, fp, rgba0, rgba1, pitch_bytes, tight, 1, pl);
+}
+
+// The two two-view entry points (include/msplat.h) are one frame too.  Half-given pairs of planes are refused at once, not queued
+static int submit_render_stereo(msplat_ctx* ctx, const char* who, const float cameraMat0[16], const float projMat0[16],
+                                const float cameraMat1[16], const float projMat1[16], const float viewport[4], const float nearFar[2],
+                                void* rgba0, void* rgba1, uint64_t pitch_bytes, int out_is_device, FramePlanes pl)
+{
+    return submit_frame<true>(ctx, out_is_device && rgba0 && rgba1 && pl.paired(), cameraMat0, projMat0, cameraMat1, projMat1, viewport, nearFar,
+                        [=](const float* cam0, const float* proj0, const float* cam1, const float* proj1, const float* vp, const float* nf) {
+                            return render_stereo_impl(ctx, who, cam0, proj0, cam1, proj1, vp, nf, rgba0, rgba1, pitch_bytes, out_is_device, pl);
+                        });
+}
+
+int msplat_render_stereo(msplat_ctx* ctx, const float cameraMat0[16], const float projMat0[16], const float cameraMat1[16],
+                         const float projMat1[16], const float viewport[4], const float nearFar[2], void* rgba0, void* rgba1,
+                         uint64_t pitch_bytes, int out_is_device)
+{
+    return submit_render_stereo(ctx, "msplat_render_stereo", cameraMat0, projMat0, cameraMat1, projMat1, viewport, nearFar, rgba0, rgba1,
+                                pitch_bytes, out_is_device, FramePlanes{});
+}
+
+int msplat_render_stereo_layers(msplat_ctx* ctx, const float cameraMat0[16], const float projMat0[16], const float cameraMat1[16],
+                                const float projMat1[16], const float viewport[4], const float nearFar[2], void* rgba0, void* rgba1,
+                                uint64_t pitch_bytes, float* depth0, float* depth1, uint64_t depth_pitch_bytes, const float* occluder0,
+                                const float* occluder1, uint64_t occluder_pitch_bytes, int out_is_device)
+{
+    return submit_render_stereo(ctx, "msplat_render_stereo_layers", cameraMat0, projMat0, cameraMat1, projMat1, viewport, nearFar, rgba0, rgba1,
+                                pitch_bytes, out_is_device, {{depth0, depth1}, {occluder0, occluder1}, depth_pitch_bytes, occluder_pitch_bytes});
 }
 
 #include "msplat_getters.hip.inc"

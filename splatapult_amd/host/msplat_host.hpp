@@ -208,22 +208,10 @@ public:
     template <class Mat4, class Vec4, class Vec2>
     void Render(const Mat4& cameraMat, const Mat4& projMat, const Vec4& viewport, const Vec2& nearFar)
     {
-        static_assert(sizeof(Mat4) == 64 && sizeof(Vec4) == 16 && sizeof(Vec2) == 8, "glm-compatible layout expected");
-        if (!target) {
-            std::fprintf(stderr, "[msplat][E] Render: no render target set (SetRenderTarget)\n");
-            return;
-        }
-        if (group) {
-            const int grc = msplat_group_render(group, reinterpret_cast<const float*>(&cameraMat), reinterpret_cast<const float*>(&projMat),
-                                                reinterpret_cast<const float*>(&viewport), reinterpret_cast<const float*>(&nearFar), target,
-                                                targetPitch, targetIsDevice ? 1 : 0);
-            if (grc != MSPLAT_OK) std::fprintf(stderr, "[msplat][%c] Render: %s\n", Level(grc), msplat_group_last_error(group));
-            return;
-        }
-        const int rc = msplat_render(ctx, reinterpret_cast<const float*>(&cameraMat), reinterpret_cast<const float*>(&projMat),
-                                     reinterpret_cast<const float*>(&viewport), reinterpret_cast<const float*>(&nearFar), target,
-                                     targetPitch, targetIsDevice ? 1 : 0);
-        if (rc != MSPLAT_OK) std::fprintf(stderr, "[msplat][%c] Render: %s\n", Level(rc), msplat_last_error(ctx));
+        RenderCall<Mat4, Vec4, Vec2>("Render", target != nullptr, "no render target set (SetRenderTarget)", nullptr, [&] {
+            return group ? msplat_group_render(group, F(cameraMat), F(projMat), F(viewport), F(nearFar), target, targetPitch, targetIsDevice ? 1 : 0)
+                         : msplat_render(ctx, F(cameraMat), F(projMat), F(viewport), F(nearFar), target, targetPitch, targetIsDevice ? 1 : 0);
+        });
     }
 
     // Render plus the per-pixel depth plane (msplat_render_depth): W x H float32 rows of depthPitchBytes (0 = tight) in the render
@@ -233,19 +221,11 @@ public:
     void RenderWithDepth(const Mat4& cameraMat, const Mat4& projMat, const Vec4& viewport, const Vec2& nearFar, float* depth,
                          uint64_t depthPitchBytes = 0)
     {
-        static_assert(sizeof(Mat4) == 64 && sizeof(Vec4) == 16 && sizeof(Vec2) == 8, "glm-compatible layout expected");
-        if (!target || !depth) {
-            std::fprintf(stderr, "[msplat][E] RenderWithDepth: no render target set (SetRenderTarget) or no depth plane\n");
-            return;
-        }
-        if (group) {
-            std::fprintf(stderr, "[msplat][E] RenderWithDepth: a device group has no depth output\n");
-            return;
-        }
-        const int rc = msplat_render_depth(ctx, reinterpret_cast<const float*>(&cameraMat), reinterpret_cast<const float*>(&projMat),
-                                           reinterpret_cast<const float*>(&viewport), reinterpret_cast<const float*>(&nearFar), target,
-                                           targetPitch, depth, depthPitchBytes, targetIsDevice ? 1 : 0);
-        if (rc != MSPLAT_OK) std::fprintf(stderr, "[msplat][%c] RenderWithDepth: %s\n", Level(rc), msplat_last_error(ctx));
+        RenderCall<Mat4, Vec4, Vec2>("RenderWithDepth", target && depth, "no render target set (SetRenderTarget) or no depth plane",
+                                     "a device group has no depth output", [&] {
+            return msplat_render_depth(ctx, F(cameraMat), F(projMat), F(viewport), F(nearFar), target, targetPitch, depth, depthPitchBytes,
+                                       targetIsDevice ? 1 : 0);
+        });
     }
 
     // Render behind the caller's geometry (msplat_render_occluded): `occluder` = W x H float32 window depths, rows of pitchBytes (0 = tight)
@@ -256,19 +236,11 @@ public:
     void RenderOccluded(const Mat4& cameraMat, const Mat4& projMat, const Vec4& viewport, const Vec2& nearFar, const float* occluder,
                         uint64_t pitchBytes = 0)
     {
-        static_assert(sizeof(Mat4) == 64 && sizeof(Vec4) == 16 && sizeof(Vec2) == 8, "glm-compatible layout expected");
-        if (!target || !occluder) {
-            std::fprintf(stderr, "[msplat][E] RenderOccluded: no render target set (SetRenderTarget) or no occluder plane\n");
-            return;
-        }
-        if (group) {
-            std::fprintf(stderr, "[msplat][E] RenderOccluded: a device group takes no occluder plane\n");
-            return;
-        }
-        const int rc = msplat_render_occluded(ctx, reinterpret_cast<const float*>(&cameraMat), reinterpret_cast<const float*>(&projMat),
-                                              reinterpret_cast<const float*>(&viewport), reinterpret_cast<const float*>(&nearFar), target,
-                                              targetPitch, occluder, pitchBytes, targetIsDevice ? 1 : 0);
-        if (rc != MSPLAT_OK) std::fprintf(stderr, "[msplat][%c] RenderOccluded: %s\n", Level(rc), msplat_last_error(ctx));
+        RenderCall<Mat4, Vec4, Vec2>("RenderOccluded", target && occluder, "no render target set (SetRenderTarget) or no occluder plane",
+                                     "a device group takes no occluder plane", [&] {
+            return msplat_render_occluded(ctx, F(cameraMat), F(projMat), F(viewport), F(nearFar), target, targetPitch, occluder, pitchBytes,
+                                          targetIsDevice ? 1 : 0);
+        });
     }
 
     // RenderOccluded and RenderWithDepth in one frame (msplat_render_layers): the colour behind the caller's geometry plus the depth
@@ -279,19 +251,11 @@ public:
     void RenderLayers(const Mat4& cameraMat, const Mat4& projMat, const Vec4& viewport, const Vec2& nearFar, float* depth,
                       uint64_t depthPitchBytes, const float* occluder, uint64_t occluderPitchBytes)
     {
-        static_assert(sizeof(Mat4) == 64 && sizeof(Vec4) == 16 && sizeof(Vec2) == 8, "glm-compatible layout expected");
-        if (!target) {
-            std::fprintf(stderr, "[msplat][E] RenderLayers: no render target set (SetRenderTarget)\n");
-            return;
-        }
-        if (group) {
-            std::fprintf(stderr, "[msplat][E] RenderLayers: a device group has no layers frame\n");
-            return;
-        }
-        const int rc = msplat_render_layers(ctx, reinterpret_cast<const float*>(&cameraMat), reinterpret_cast<const float*>(&projMat),
-                                            reinterpret_cast<const float*>(&viewport), reinterpret_cast<const float*>(&nearFar), target,
-                                            targetPitch, depth, depthPitchBytes, occluder, occluderPitchBytes, targetIsDevice ? 1 : 0);
-        if (rc != MSPLAT_OK) std::fprintf(stderr, "[msplat][%c] RenderLayers: %s\n", Level(rc), msplat_last_error(ctx));
+        RenderCall<Mat4, Vec4, Vec2>("RenderLayers", target != nullptr, "no render target set (SetRenderTarget)",
+                                     "a device group has no layers frame", [&] {
+            return msplat_render_layers(ctx, F(cameraMat), F(projMat), F(viewport), F(nearFar), target, targetPitch, depth, depthPitchBytes,
+                                        occluder, occluderPitchBytes, targetIsDevice ? 1 : 0);
+        });
     }
 
     // RenderStereo with RenderLayers' planes per eye (msplat_render_stereo_layers): the reference's XR frame -- geometry first, the
@@ -302,21 +266,12 @@ public:
                             const Vec2& nearFar, void* target1, float* depth0, float* depth1, uint64_t depthPitchBytes,
                             const float* occluder0, const float* occluder1, uint64_t occluderPitchBytes)
     {
-        static_assert(sizeof(Mat4) == 64 && sizeof(Vec4) == 16 && sizeof(Vec2) == 8, "glm-compatible layout expected");
-        if (!target || !target1) {
-            std::fprintf(stderr, "[msplat][E] RenderStereoLayers: no render target set (SetRenderTarget / target1)\n");
-            return;
-        }
-        if (group) {
-            std::fprintf(stderr, "[msplat][E] RenderStereoLayers: a device group has no layers frame\n");
-            return;
-        }
-        const int rc = msplat_render_stereo_layers(ctx, reinterpret_cast<const float*>(&cameraMat0), reinterpret_cast<const float*>(&projMat0),
-                                                   reinterpret_cast<const float*>(&cameraMat1), reinterpret_cast<const float*>(&projMat1),
-                                                   reinterpret_cast<const float*>(&viewport), reinterpret_cast<const float*>(&nearFar), target,
-                                                   target1, targetPitch, depth0, depth1, depthPitchBytes, occluder0, occluder1,
-                                                   occluderPitchBytes, targetIsDevice ? 1 : 0);
-        if (rc != MSPLAT_OK) std::fprintf(stderr, "[msplat][%c] RenderStereoLayers: %s\n", Level(rc), msplat_last_error(ctx));
+        RenderCall<Mat4, Vec4, Vec2>("RenderStereoLayers", target && target1, "no render target set (SetRenderTarget / target1)",
+                                     "a device group has no layers frame", [&] {
+            return msplat_render_stereo_layers(ctx, F(cameraMat0), F(projMat0), F(cameraMat1), F(projMat1), F(viewport), F(nearFar), target,
+                                               target1, targetPitch, depth0, depth1, depthPitchBytes, occluder0, occluder1,
+                                               occluderPitchBytes, targetIsDevice ? 1 : 0);
+        });
     }
 
     // Both eyes of the latest Sort in one chain of launches (msplat_render_stereo): what the XR callback does with two Render
@@ -326,12 +281,7 @@ public:
     void RenderStereo(const Mat4& cameraMat0, const Mat4& projMat0, const Mat4& cameraMat1, const Mat4& projMat1, const Vec4& viewport,
                       const Vec2& nearFar, void* target1)
     {
-        static_assert(sizeof(Mat4) == 64 && sizeof(Vec4) == 16 && sizeof(Vec2) == 8, "glm-compatible layout expected");
-        if (!target || !target1) {
-            std::fprintf(stderr, "[msplat][E] RenderStereo: no render target set (SetRenderTarget / target1)\n");
-            return;
-        }
-        if (group) {         // a device group renders its rows per view
+        if (group && target && target1) {         // a device group renders its rows per view
             Render(cameraMat0, projMat0, viewport, nearFar);
             void* keep = target;
             target = target1;
@@ -339,11 +289,10 @@ public:
             target = keep;
             return;
         }
-        const int rc = msplat_render_stereo(ctx, reinterpret_cast<const float*>(&cameraMat0), reinterpret_cast<const float*>(&projMat0),
-                                            reinterpret_cast<const float*>(&cameraMat1), reinterpret_cast<const float*>(&projMat1),
-                                            reinterpret_cast<const float*>(&viewport), reinterpret_cast<const float*>(&nearFar), target,
-                                            target1, targetPitch, targetIsDevice ? 1 : 0);
-        if (rc != MSPLAT_OK) std::fprintf(stderr, "[msplat][%c] RenderStereo: %s\n", Level(rc), msplat_last_error(ctx));
+        RenderCall<Mat4, Vec4, Vec2>("RenderStereo", target && target1, "no render target set (SetRenderTarget / target1)", nullptr, [&] {
+            return msplat_render_stereo(ctx, F(cameraMat0), F(projMat0), F(cameraMat1), F(projMat1), F(viewport), F(nearFar), target, target1,
+                                        targetPitch, targetIsDevice ? 1 : 0);
+        });
     }
 
     // replaces "the currently bound GL framebuffer" (app.cpp:1000-1035)
@@ -460,6 +409,23 @@ protected:
 
     // log level of a status code: MSPLAT_ERR_PAIR_OVERFLOW_EARLIER reports a PAST frame, the call itself did its work
     static char Level(int rc) { return rc == MSPLAT_ERR_PAIR_OVERFLOW_EARLIER ? 'W' : 'E'; }
+
+    template <class T> static const float* F(const T& v) { return reinterpret_cast<const float*>(&v); }
+
+    // What every Render method does around its library call: the layout check; "[msplat][E] <name>: <missing>" unless `ready`; the
+    // same with `noGroup` on a device group (NULL: the call serves a group too); call(), and its failure (void, like the reference)
+    template <class Mat4, class Vec4, class Vec2, class Call>
+    void RenderCall(const char* name, bool ready, const char* missing, const char* noGroup, Call call)
+    {
+        static_assert(sizeof(Mat4) == 64 && sizeof(Vec4) == 16 && sizeof(Vec2) == 8, "glm-compatible layout expected");
+        if (!ready || (group && noGroup)) {
+            std::fprintf(stderr, "[msplat][E] %s: %s\n", name, ready ? noGroup : missing);
+            return;
+        }
+        const int rc = call();
+        if (rc != MSPLAT_OK)
+            std::fprintf(stderr, "[msplat][%c] %s: %s\n", Level(rc), name, group ? msplat_group_last_error(group) : msplat_last_error(ctx));
+    }
 
     void DestroyContexts()
     {

@@ -80,6 +80,15 @@ def _host_frame(fb_format, vp, out=None, load=False):
     return out
 
 
+# what the ValueError says when a plane is not in the image's memory space: (with out_ptr, with host output), per plane the call names
+_LIVES = {"depth": ("the depth plane lives in the colour's memory space: pass depth_ptr= with out_ptr=",
+                    "the depth plane lives in the colour's memory space: pass depth= with host output"),
+          "occluder": ("the occluder plane lives in the colour's memory space: pass occluder_ptr= with out_ptr=",
+                       "the occluder plane lives in the colour's memory space: pass occluder= with host output"),
+          "planes": ("the planes live in the colour's memory space: pass depth_ptr= / occluder_ptr= with out_ptr=",
+                     "the planes live in the colour's memory space: pass depth= / occluder= with host output")}
+
+
 class SplatRenderer:
     def __init__(self, device=0, fb_format="fp32", t_epsilon=-1.0, pair_capacity=0, stream=None,
                  enable_timing=False, frames_in_flight=1, rank_mode=_capi.RANK_AUTO, frame_mode=None,
@@ -251,73 +260,94 @@ class SplatRenderer:
         array with host output, occluder_ptr=int (rows of occluder_pitch_bytes, 0 = tight; valid until the frame has run) with
         out_ptr.  Render takes a depth output or an occluder plane, not both (MsplatError(ERR_UNSUPPORTED)): the frame with both
         is RenderLayers'"""
-        c, p, v, nf = self._args.load(cameraMat, projMat, viewport, nearFar)
-        has_depth = (depth is not None and depth is not False) or depth_ptr is not None
-        if occluder is not None or occluder_ptr is not None:
-            if has_depth:
+        f = self._args.load(cameraMat, projMat, viewport, nearFar)
+        kind = "occluder" if occluder is not None or occluder_ptr is not None else "depth"
+        if kind == "occluder":
+            if (depth is not None and depth is not False) or depth_ptr is not None:
                 raise _capi.MsplatError(_capi.ERR_UNSUPPORTED, "Render takes either a depth output (msplat_render_depth) or an occluder "
                                         "plane (msplat_render_occluded), not both: that frame is RenderLayers' (msplat_render_layers)")
-            if out_ptr is not None:
-                if occluder is not None:
-                    raise ValueError("the occluder plane lives in the colour's memory space: pass occluder_ptr= with out_ptr=")
-                _capi.check(self._ctx, self._lib.msplat_render_occluded(self._ctx, c, p, v, nf, C.c_void_p(out_ptr), pitch_bytes,
-                                                                        C.c_void_p(occluder_ptr), occluder_pitch_bytes, 1))
-                return None
-            if occluder_ptr is not None:
-                raise ValueError("the occluder plane lives in the colour's memory space: pass occluder= with host output")
-            out = _host_frame(self._fb_format, self._args.vp, out, self._load)
-            H, W = out.shape[:2]
-            assert occluder.dtype == np.float32 and occluder.shape == (H, W) and occluder.flags["C_CONTIGUOUS"]
-            _capi.check(self._ctx, self._lib.msplat_render_occluded(self._ctx, c, p, v, nf, out.ctypes.data, 0, occluder.ctypes.data,
-                                                                    occluder_pitch_bytes, 0))
-            return out
-        if out_ptr is not None:
-            if depth is not None:
-                raise ValueError("the depth plane lives in the colour's memory space: pass depth_ptr= with out_ptr=")
-            if depth_ptr is not None:
-                _capi.check(self._ctx, self._lib.msplat_render_depth(self._ctx, c, p, v, nf, C.c_void_p(out_ptr), pitch_bytes,
-                                                                     C.c_void_p(depth_ptr), depth_pitch_bytes, 1))
-                return None
-            _capi.check(self._ctx, self._lib.msplat_render(self._ctx, c, p, v, nf, C.c_void_p(out_ptr),
-                                                           pitch_bytes, 1))
-            return None
-        if depth_ptr is not None:
-            raise ValueError("the depth plane lives in the colour's memory space: pass depth= with host output")
-        out = _host_frame(self._fb_format, self._args.vp, out, self._load)
-        if depth is None or depth is False:
-            _capi.check(self._ctx, self._lib.msplat_render(self._ctx, c, p, v, nf, out.ctypes.data, 0, 0))
-            return out
-        H, W = out.shape[:2]
-        if depth is True:
-            depth = np.empty((H, W), np.float32)
-        assert depth.dtype == np.float32 and depth.shape == (H, W) and depth.flags["C_CONTIGUOUS"]
-        _capi.check(self._ctx, self._lib.msplat_render_depth(self._ctx, c, p, v, nf, out.ctypes.data, 0, depth.ctypes.data, 0, 0))
-        return out, depth
+            depth = None
 
-    def RenderStereo(self, cameraMats, projMats, viewport, nearFar, out_ptrs=None, pitch_bytes=0):
-        """both eyes of the latest Sort in ONE chain of launches (msplat_render_stereo; the reference renders them one after the
-        other, app.cpp:603-607): same pixels as two Render calls.  out_ptrs: two device pointers (asynchronous), else two host
-        arrays are returned -- not in target mode "load", which needs the destinations: ValueError without out_ptrs (render the
-        eyes with two Render(out=...) calls instead)"""
-        a0, a1 = self._args, getattr(self, "_args1", None)
-        if a1 is None:
-            a1 = self._args1 = _FrameArgs()
-        c0, p0, v, nf = a0.load(cameraMats[0], projMats[0], viewport, nearFar)
-        c1, p1, _, _ = a1.load(cameraMats[1], projMats[1], viewport, nearFar)
-        if out_ptrs is not None:
-            _capi.check(self._ctx, self._lib.msplat_render_stereo(self._ctx, c0, p0, c1, p1, v, nf, C.c_void_p(out_ptrs[0]),
-                                                                  C.c_void_p(out_ptrs[1]), pitch_bytes, 1))
-            return None
-        outs = [_host_frame(self._fb_format, a0.vp, None, self._load), _host_frame(self._fb_format, a0.vp, None, self._load)]
-        _capi.check(self._ctx, self._lib.msplat_render_stereo(self._ctx, c0, p0, c1, p1, v, nf, outs[0].ctypes.data,
-                                                              outs[1].ctypes.data, 0, 0))
-        return outs
+        def call(rgba, pitch, d, o, dev):
+            if o is not None:
+                return self._lib.msplat_render_occluded(self._ctx, *f, C.c_void_p(rgba), pitch, C.c_void_p(o), occluder_pitch_bytes, dev)
+            if d is not None:
+                return self._lib.msplat_render_depth(self._ctx, *f, C.c_void_p(rgba), pitch, C.c_void_p(d), depth_pitch_bytes if dev else 0, dev)
+            return self._lib.msplat_render(self._ctx, *f, C.c_void_p(rgba), pitch, dev)
+
+        return self._render_one(call, out, out_ptr, pitch_bytes, depth, depth_ptr, occluder, occluder_ptr, self._asserted_plane,
+                                _LIVES[kind])
+
+    @staticmethod
+    def _asserted_plane(name, plane, H, W):
+        assert plane.dtype == np.float32 and plane.shape == (H, W) and plane.flags["C_CONTIGUOUS"]
+        return plane
 
     @staticmethod
     def _host_plane(name, plane, H, W):
         if not isinstance(plane, np.ndarray) or plane.dtype != np.float32 or plane.shape != (H, W) or not plane.flags["C_CONTIGUOUS"]:
             raise ValueError("%s takes a C-contiguous float32 array of shape (%d, %d)" % (name, H, W))
         return plane
+
+    def _render_one(self, call, out, out_ptr, pitch_bytes, depth, depth_ptr, occluder, occluder_ptr, plane, refusals):
+        """One view, behind Render and RenderLayers: the image and the planes are the caller's device pointers (returns None) or host
+        arrays -- `out` checked or made, depth=True allocated, each plane checked by `plane` -- and never one of each (`refusals`:
+        what the ValueError says with out_ptr / with host output).  call(rgba, pitch_bytes, depth, occluder, out_is_device) issues
+        the frame with the library function of its choice and returns its code"""
+        if out_ptr is not None:
+            if depth is not None or occluder is not None:
+                raise ValueError(refusals[0])
+            _capi.check(self._ctx, call(out_ptr, pitch_bytes, depth_ptr, occluder_ptr, 1))
+            return None
+        if depth_ptr is not None or occluder_ptr is not None:
+            raise ValueError(refusals[1])
+        out = _host_frame(self._fb_format, self._args.vp, out, self._load)
+        H, W = out.shape[:2]
+        if depth is False:
+            depth = None
+        if depth is True:
+            depth = np.empty((H, W), np.float32)
+        d = plane("depth=", depth, H, W).ctypes.data if depth is not None else None
+        o = plane("occluder=", occluder, H, W).ctypes.data if occluder is not None else None
+        _capi.check(self._ctx, call(out.ctypes.data, 0, d, o, 0))
+        return out if depth is None else (out, depth)
+
+    def _render_two(self, call, cameraMats, projMats, viewport, nearFar, out_ptrs, pitch_bytes, depth=None, depth_ptrs=None,
+                    occluders=None, occluder_ptrs=None):
+        """Two views, behind RenderStereo and RenderStereoLayers: as _render_one, with pairs.  call(frame, rgba0, rgba1, pitch_bytes,
+        (depth0, depth1), (occluder0, occluder1), out_is_device); frame: the six marshalled arrays"""
+        a0, a1 = self._args, getattr(self, "_args1", None)
+        if a1 is None:
+            a1 = self._args1 = _FrameArgs()
+        c0, p0, v, nf = a0.load(cameraMats[0], projMats[0], viewport, nearFar)
+        c1, p1, _, _ = a1.load(cameraMats[1], projMats[1], viewport, nearFar)
+        f, none = (c0, p0, c1, p1, v, nf), (None, None)
+        if out_ptrs is not None:
+            if depth is not None or occluders is not None:
+                raise ValueError("the planes live in the colour's memory space: pass depth_ptrs= / occluder_ptrs= with out_ptrs=")
+            _capi.check(self._ctx, call(f, out_ptrs[0], out_ptrs[1], pitch_bytes, depth_ptrs if depth_ptrs is not None else none,
+                                        occluder_ptrs if occluder_ptrs is not None else none, 1))
+            return None
+        if depth_ptrs is not None or occluder_ptrs is not None:
+            raise ValueError("the planes live in the colour's memory space: pass depth= / occluders= with host output")
+        outs = [_host_frame(self._fb_format, a0.vp, None, self._load), _host_frame(self._fb_format, a0.vp, None, self._load)]
+        H, W = outs[0].shape[:2]
+        if depth is True:
+            depth = [np.empty((H, W), np.float32), np.empty((H, W), np.float32)]
+        d = [self._host_plane("depth=", z, H, W).ctypes.data for z in depth] if depth is not None else none
+        o = [self._host_plane("occluders=", z, H, W).ctypes.data for z in occluders] if occluders is not None else none
+        _capi.check(self._ctx, call(f, outs[0].ctypes.data, outs[1].ctypes.data, 0, d, o, 0))
+        return outs if depth is None else (outs, list(depth))
+
+    def RenderStereo(self, cameraMats, projMats, viewport, nearFar, out_ptrs=None, pitch_bytes=0):
+        """both eyes of the latest Sort in ONE chain of launches (msplat_render_stereo; the reference renders them one after the
+        other, app.cpp:603-607): same pixels as two Render calls.  out_ptrs: two device pointers (asynchronous), else two host
+        arrays are returned -- not in target mode "load", which needs the destinations: ValueError without out_ptrs (render the
+        eyes with two Render(out=...) calls instead)"""
+        def call(f, rgba0, rgba1, pitch, d, o, dev):
+            return self._lib.msplat_render_stereo(self._ctx, *f, C.c_void_p(rgba0), C.c_void_p(rgba1), pitch, dev)
+
+        return self._render_two(call, cameraMats, projMats, viewport, nearFar, out_ptrs, pitch_bytes)
 
     def RenderLayers(self, cameraMat, projMat, viewport, nearFar, out=None, out_ptr=None, pitch_bytes=0, depth=None, depth_ptr=None,
                      depth_pitch_bytes=0, occluder=None, occluder_ptr=None, occluder_pitch_bytes=0):
@@ -327,26 +357,14 @@ class SplatRenderer:
         msplat_render_depth / msplat_render_occluded / msplat_render.  The depth plane may BE the occluder plane (the same array,
         or the same pointer and pitch): a depth attachment read and written in place.
         Host output returns the image, or (image, depth) when a depth plane was asked for; device output returns None."""
-        c, p, v, nf = self._args.load(cameraMat, projMat, viewport, nearFar)
-        if out_ptr is not None:
-            if (depth is not None and depth is not False) or occluder is not None:
-                raise ValueError("the planes live in the colour's memory space: pass depth_ptr= / occluder_ptr= with out_ptr=")
-            _capi.check(self._ctx, self._lib.msplat_render_layers(self._ctx, c, p, v, nf, C.c_void_p(out_ptr), pitch_bytes,
-                                                                  C.c_void_p(depth_ptr), depth_pitch_bytes, C.c_void_p(occluder_ptr),
-                                                                  occluder_pitch_bytes, 1))
-            return None
-        if depth_ptr is not None or occluder_ptr is not None:
-            raise ValueError("the planes live in the colour's memory space: pass depth= / occluder= with host output")
-        out = _host_frame(self._fb_format, self._args.vp, out, self._load)
-        H, W = out.shape[:2]
-        if depth is False:
-            depth = None
-        if depth is True:
-            depth = np.empty((H, W), np.float32)
-        d = self._host_plane("depth=", depth, H, W).ctypes.data if depth is not None else None
-        o = self._host_plane("occluder=", occluder, H, W).ctypes.data if occluder is not None else None
-        _capi.check(self._ctx, self._lib.msplat_render_layers(self._ctx, c, p, v, nf, out.ctypes.data, 0, d, 0, o, 0, 0))
-        return out if depth is None else (out, depth)
+        f = self._args.load(cameraMat, projMat, viewport, nearFar)
+
+        def call(rgba, pitch, d, o, dev):
+            return self._lib.msplat_render_layers(self._ctx, *f, C.c_void_p(rgba), pitch, C.c_void_p(d), depth_pitch_bytes if dev else 0,
+                                                  C.c_void_p(o), occluder_pitch_bytes if dev else 0, dev)
+
+        return self._render_one(call, out, out_ptr, pitch_bytes, None if depth is False else depth, depth_ptr, occluder, occluder_ptr,
+                                self._host_plane, _LIVES["planes"])
 
     def RenderStereoLayers(self, cameraMats, projMats, viewport, nearFar, out_ptrs=None, pitch_bytes=0, depth_ptrs=None,
                            depth_pitch_bytes=0, occluder_ptrs=None, occluder_pitch_bytes=0, depth=False, occluders=None):
@@ -356,34 +374,13 @@ class SplatRenderer:
         Without out_ptrs host arrays are used, view by view: occluders = a pair of (H, W) float32 arrays or None, depth = True to
         have the depth planes allocated (or a pair of arrays to fill); returns [image0, image1], or ([image0, image1], [depth0,
         depth1]) when depth planes were asked for.  Not in target mode "load" (as for RenderStereo)."""
-        a0, a1 = self._args, getattr(self, "_args1", None)
-        if a1 is None:
-            a1 = self._args1 = _FrameArgs()
-        c0, p0, v, nf = a0.load(cameraMats[0], projMats[0], viewport, nearFar)
-        c1, p1, _, _ = a1.load(cameraMats[1], projMats[1], viewport, nearFar)
-        fn = self._lib.msplat_render_stereo_layers
-        if out_ptrs is not None:
-            if (depth is not None and depth is not False) or occluders is not None:
-                raise ValueError("the planes live in the colour's memory space: pass depth_ptrs= / occluder_ptrs= with out_ptrs=")
-            d0, d1 = depth_ptrs if depth_ptrs is not None else (None, None)
-            o0, o1 = occluder_ptrs if occluder_ptrs is not None else (None, None)
-            _capi.check(self._ctx, fn(self._ctx, c0, p0, c1, p1, v, nf, C.c_void_p(out_ptrs[0]), C.c_void_p(out_ptrs[1]), pitch_bytes,
-                                      C.c_void_p(d0), C.c_void_p(d1), depth_pitch_bytes, C.c_void_p(o0), C.c_void_p(o1),
-                                      occluder_pitch_bytes, 1))
-            return None
-        if depth_ptrs is not None or occluder_ptrs is not None:
-            raise ValueError("the planes live in the colour's memory space: pass depth= / occluders= with host output")
-        outs = [_host_frame(self._fb_format, a0.vp, None, self._load), _host_frame(self._fb_format, a0.vp, None, self._load)]
-        H, W = outs[0].shape[:2]
-        if depth is False:
-            depth = None
-        if depth is True:
-            depth = [np.empty((H, W), np.float32), np.empty((H, W), np.float32)]
-        d = [self._host_plane("depth=", z, H, W).ctypes.data for z in depth] if depth is not None else [None, None]
-        o = [self._host_plane("occluders=", z, H, W).ctypes.data for z in occluders] if occluders is not None else [None, None]
-        _capi.check(self._ctx, fn(self._ctx, c0, p0, c1, p1, v, nf, outs[0].ctypes.data, outs[1].ctypes.data, 0, d[0], d[1], 0, o[0], o[1],
-                                  0, 0))
-        return outs if depth is None else (outs, list(depth))
+        def call(f, rgba0, rgba1, pitch, d, o, dev):
+            return self._lib.msplat_render_stereo_layers(self._ctx, *f, C.c_void_p(rgba0), C.c_void_p(rgba1), pitch, C.c_void_p(d[0]),
+                                                         C.c_void_p(d[1]), depth_pitch_bytes if dev else 0, C.c_void_p(o[0]),
+                                                         C.c_void_p(o[1]), occluder_pitch_bytes if dev else 0, dev)
+
+        return self._render_two(call, cameraMats, projMats, viewport, nearFar, out_ptrs, pitch_bytes, None if depth is False else depth,
+                                depth_ptrs, occluders, occluder_ptrs)
 
     # -- extensions -------------------------------------------------------------------------
     def set_band(self, row_mod, row_rem, band_cull=False):

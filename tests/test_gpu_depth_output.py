@@ -335,7 +335,7 @@ def test_refused_combinations_say_why_and_leave_the_context_usable():
     for pitch in (4 * W - 4, 4 * W + 2, 3):
         with pytest.raises(MsplatError) as e:
             r.Render(*view, out_ptr=fb.data_ptr(), pitch_bytes=W * 16, depth_ptr=zb.data_ptr(), depth_pitch_bytes=pitch)
-        assert e.value.code == _capi.ERR_INVALID_ARG and "pitch" in r.last_error()
+        assert e.value.code == _capi.ERR_INVALID_ARG and "pitch" in r.last_error() and "msplat_render_depth" in r.last_error()
     r.Render(*view, out_ptr=fb.data_ptr(), pitch_bytes=W * 16, depth_ptr=zb.data_ptr(), depth_pitch_bytes=4 * W + 32)
     r.synchronize()
     np.testing.assert_array_equal(zb.cpu().numpy()[:, :W], want_z)

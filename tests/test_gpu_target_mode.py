@@ -408,7 +408,7 @@ def test_refused_combinations_say_why():
         r.set_target_mode(mode)
         with pytest.raises(MsplatError) as e:
             r.Render(*view, out=np.zeros((H, W, 4), np.float32))
-        assert e.value.code == _capi.ERR_UNSUPPORTED and "probe" in r.last_error()
+        assert e.value.code == _capi.ERR_UNSUPPORTED and "probe" in r.last_error() and r.last_error().startswith("msplat_render: ")
     # a bad mode
     L = _capi.lib()
     r = make_renderer(cloud)
