@@ -63,6 +63,24 @@ struct CloudStore {
     }
 };
 
+inline uint32_t* words(const Buf& b) { return (uint32_t*)b.p; }
+
+// The tables of the 8-bit radix passes (msplat_sort.hip.h), each with the numbers its kernels are launched with.
+// HistTable: chunk-major histogram rows, uint32[256 * stride].  GroupTable (the scan-free path): per-group sums, one row of 256 per
+// 32 chunks, behind `sup` rows of supergroup sums; `rows` of them in all (alloc_group_table)
+struct HistTable { Buf buf; uint32_t stride = 0; };
+struct GroupTable { Buf buf; uint32_t rows = 0, sup = 0; };
+
+// The wide-digit 3-pass sort (r3, msplat_sort.hip.h ws_*): whether the uploaded cloud gets it and in what shape (plan_wide_sort), the
+// histogram rows of up to 2048 digits per chunk, one group table per pass
+struct WideSort {
+    bool on = true;             // off: the four 8-bit passes (MSPLAT_SORT=lsd8, no lane-ordered LDS atomics, a refused LDS request)
+    uint32_t items = 8;         // keys per thread of pass 0: 8 or 16
+    uint32_t threads = 512;     // 256 (4 waves, 40 / 56 KB of LDS) for contexts that share the GPU with other frames
+    uint32_t gshift = 4, gsum_words = 0;       // groups of 1 << gshift chunk rows; words of each group table
+    Buf hist, gsum[3];
+};
+
 // clouds of at least this many splats are stored in Morton order (msplat_config.spatial_order = AUTO): below it a pass-0
 // chunk is a large part of the cloud and there is nothing to skip
 constexpr uint64_t kSpatialMinSplats = 1ull << 18;
@@ -150,24 +168,18 @@ struct msplat_ctx {
     hipEvent_t join_ev = nullptr;        // msplat_stream_wait
     // sort state
     Buf keyA, keyB, valA, valB;   // uint32[N]; final sorted result in keyA/valA
-    Buf hist;       // uint32[256 * hist_stride]
-    uint32_t hist_stride = 0;
-    // scan-free path (msplat_sort.hip.h, radix_upsweep): per-group histogram sums, one row of 256 per 32 chunks
-    Buf gsumS[2];   // sort passes alternate between the two
-    Buf gsumB1, gsumB2;     // binning: column pass / row pass
-    uint32_t gsumS_rows = 0, gsumB1_rows = 0, gsumB2_rows = 0;
-    uint32_t gsupS = 0, gsupB1 = 0, gsupB2 = 0;     // supergroup rows at the head of each table (the group rows follow)
-    // wide-digit 3-pass sort (r3, msplat_sort.hip.h ws_*): histogram rows of up to 2048 digits per chunk, one group
-    // table per pass, one visibility bit per splat, the visible set's minimum key per frame parity (counters, kCntMinKey)
-    Buf wsHist, wsGsum[3], vmask;
+    HistTable hist;
+    // scan-free path (msplat_sort.hip.h, radix_upsweep)
+    GroupTable gsumS[2];    // sort passes alternate between the two: same rows, same sup (prepare_cloud_buffers)
+    GroupTable gsumB1, gsumB2;      // binning: column pass / row pass
+    // the wide sort, one visibility bit per splat, the visible set's minimum key per frame parity (counters, kCntMinKey)
+    WideSort ws;
+    bool wide_sort_cfg = true;  // what the context asked for; ws.on = what the uploaded cloud gets (plan_wide_sort)
+    Buf vmask;
     Buf live_list, live_cnt;    // live bounding boxes of the latest Sort that ran box_cull_kernel (spatially ordered clouds)
     int spatial_mode = 0;       // msplat_config.spatial_order: 0 auto, 1 always, 2 never
     bool last_sort_listed = false;   // the latest Sort's pass 0 walked the listed boxes only
     FrameParams last_sort_fp{};
-    uint32_t ws_items = 8, ws_gshift = 4, ws_gsum_words = 0;
-    uint32_t ws_threads = 512;  // 256 (4 waves, 40 / 56 KB of LDS) for contexts that share the GPU with other frames
-    bool wide_sort = true;      // MSPLAT_SORT=lsd8 (or no lane-ordered LDS atomics): the four 8-bit passes
-    bool wide_sort_cfg = true;  // what the context asked for; wide_sort = what the uploaded cloud gets (alloc_cloud_buffers)
     uint32_t sort_parity = 0;
     bool tables_dirty = false;  // a launch failed: clear every self-cleaning table before the next frame
     // per-bin pair counts taken by the row pass's upsweep (r3): list offsets + work order (no kernel of their own)
@@ -198,12 +210,10 @@ struct msplat_ctx {
     Buf tile_start; // uint32[65537]
     Buf tile_order; // uint32[65536] bins by descending list length, then uint32[65536] = 0, 1, 2, ... (the order used when persistent
                     // waves pull the items dynamically: measured, the heaviest-first order buys nothing there)
-    Buf hist1;      // uint32[256 * hist1_stride]
-    uint32_t hist1_stride = 0;
+    HistTable hist1;      // column pass
     Buf pairsA, pairsB;   // uint32[pair_cap]
     uint64_t pair_cap = 0;
-    Buf hist2;      // uint32[256 * hist2_stride]
-    uint32_t hist2_stride = 0;
+    HistTable hist2;      // row pass
     Buf fb;         // internal framebuffer for host-output renders
     Buf fbz;        // ... and their depth plane (msplat_render_depth): float[W * H]
     Buf fbo;        // ... and the caller's occluder plane (msplat_render_occluded), staged once per call: float[W * H]
@@ -348,14 +358,8 @@ template <int V0, int... Vs, class F> inline void with_int(int v, F&& f)
     else with_int<Vs...>(v, f);
 }
 
-// keys per thread of the 8-bit radix passes (msplat_common.hip.h, kSortItems)
-template <class F> inline void with_sort_items(bool large, F&& f)
-{
-    with_int<kSortItemsLarge, kSortItems>(large ? kSortItemsLarge : kSortItems, f);
-}
-
 // The (keys per thread, threads) forms of the wide sort's kernels: the ONE list behind sort_impl's dispatch (with_ws_shape) and
-// msplat_create's dynamic-LDS requests.  ws_items is 8 or 16 and ws_threads kWsThreads or kWsThreadsSmall (prepare_cloud_buffers).
+// msplat_create's dynamic-LDS requests.  ws.items is 8 or 16 and ws.threads kWsThreads or kWsThreadsSmall (plan_wide_sort).
 template <class F> inline void for_each_ws_shape(F&& f)
 {
     f(int_t<8>{}, int_t<kWsThreads>{});
@@ -368,7 +372,109 @@ template <class F> inline void with_ws_shape(uint32_t items, uint32_t threads, F
     for_each_ws_shape([&](auto I, auto T) { if (items == (uint32_t)I.value && threads == (uint32_t)T.value) f(I, T); });
 }
 
-// host matrix helpers (implemented in msplat_host.cpp)
+// exclusive scan of a chunk-major histogram table along the chunks.  The element count is only known on the device,
+// so the variant is picked from the cloud size: up to 2 M splats (a few thousand chunk rows at most) the 16-workgroup
+// version, beyond that one workgroup per digit.
+void launch_scan(hipStream_t s, bool small, const HistTable& hist, const uint32_t* d_n, uint32_t n_static, uint32_t n_cap, uint32_t chunk,
+                 uint32_t* totals)
+{
+    if (small)
+        hipLaunchKernelGGL(radix_scan_small, dim3(kScanSmallBlocks), dim3(kThreads), 0, s, words(hist.buf), d_n, n_static, n_cap, chunk, totals);
+    else
+        hipLaunchKernelGGL(radix_scan, dim3(256), dim3(kThreads), 0, s, words(hist.buf), hist.stride, d_n, n_static, n_cap, chunk, totals);
+}
+
+// ---- The arguments of a sort pass, by name.  A member's initialiser is what a pass without that feature passes; a call site states
+// what its pass has, and launch_radix_* / launch_ws_* spell the kernels' positional lists (msplat_sort.hip.h), once each.
+struct PassIO {                                 // what both kinds of pass read and write
+    const uint32_t *keys_in = nullptr, *vals_in = nullptr;
+    const float4* pos = nullptr;                // pass 0: the keys come from the positions
+    const uint32_t* d_n = nullptr;              // the element count on the device; nullptr: n_static
+    uint32_t n_static = 0, n_cap = 0;
+    uint32_t *keys_out = nullptr, *vals_out = nullptr, *d_count_out = nullptr;
+    const FrameParams* fp = nullptr;
+    LiveBoxes lb{nullptr, nullptr, 0u, 0u};     // pass 0 over the listed live boxes (list_live_boxes)
+    // the sort's ping-pong buffers: (keyA, valA) -> (keyB, valB), or back
+    void buffers(const msplat_ctx* c, bool from_b)
+    {
+        keys_in = words(from_b ? c->keyB : c->keyA);   vals_in = words(from_b ? c->valB : c->valA);
+        keys_out = words(from_b ? c->keyA : c->keyB);  vals_out = words(from_b ? c->valA : c->valB);
+    }
+};
+
+// one 8-bit pass, radix_upsweep + radix_downsweep
+struct RadixPass : PassIO {
+    int shift = 0;
+    const HistTable* hist = nullptr;
+    uint32_t* totals = nullptr;                 // digit totals: radix_scan*'s, or (totals_out) the scan-free downsweep's own
+    // scan-free (`fused`): the upsweep accumulates into gsum and the downsweep reads it; gsum's sup travels either way.  gsum_zero: the
+    // table the upsweep clears for its successor pass
+    const GroupTable *gsum = nullptr, *gsum_zero = nullptr;
+    bool fused = false;
+    // MODE_PAIR, the binning's row pass: column totals in; row totals, bin counts, list offsets, work order and queue heads out
+    const uint32_t* col_totals = nullptr;
+    uint32_t *totals_out = nullptr, *bincnt = nullptr, *tile_start = nullptr, *tile_order = nullptr, *queue = nullptr;
+    int ntiles = 0, do_order = 0;
+};
+
+template <int MODE, int ITEMS, bool BAND>
+void launch_radix_upsweep(hipStream_t s, int grid, const RadixPass& a)
+{
+    hipLaunchKernelGGL((radix_upsweep<MODE, ITEMS, BAND>), dim3(grid), dim3(kThreads), 0, s, a.keys_in, a.pos, a.d_n, a.n_static, a.n_cap,
+                       a.shift, words(a.hist->buf), a.hist->stride, a.fused ? words(a.gsum->buf) : nullptr,
+                       a.gsum_zero ? words(a.gsum_zero->buf) : nullptr, a.gsum_zero ? a.gsum_zero->rows : 0u, *a.fp, a.col_totals, a.bincnt,
+                       a.gsum ? a.gsum->sup : 0u, a.lb);
+}
+template <int MODE, bool HAS_VALUES, bool ATOMIC_RANK, int ITEMS, bool BAND>
+void launch_radix_downsweep(hipStream_t s, int grid, const RadixPass& a)
+{
+    hipLaunchKernelGGL((radix_downsweep<MODE, HAS_VALUES, ATOMIC_RANK, ITEMS, BAND>), dim3(grid), dim3(kThreads), 0, s, a.keys_in, a.vals_in,
+                       a.pos, a.d_n, a.n_static, a.n_cap, a.shift, (const uint32_t*)words(a.hist->buf), a.hist->stride,
+                       (const uint32_t*)a.totals, a.keys_out, a.vals_out, a.d_count_out, a.col_totals,
+                       a.fused ? (const uint32_t*)words(a.gsum->buf) : nullptr, a.totals_out, *a.fp, a.bincnt, a.tile_start, a.tile_order,
+                       a.queue, a.ntiles, a.do_order, a.gsum ? a.gsum->sup : 0u, a.lb);
+}
+
+// one digit of the sort's 8-bit passes over `grid` chunks: upsweep, the scan unless the pass is scan-free, downsweep.  large: the chunks
+// of clouds beyond 2 M splats (keys per thread: msplat_common.hip.h, kSortItems)
+template <class Mode, class Band>
+void issue_radix_pass(msplat_ctx* ctx, Mode, Band, bool large, int grid, const RadixPass& a)
+{
+    with_int<kSortItemsLarge, kSortItems>(large ? kSortItemsLarge : kSortItems, [&](auto IT) {
+        launch_radix_upsweep<Mode::value, IT.value, Band::value>(ctx->stream, grid, a);
+        if (!a.fused) launch_scan(ctx->stream, !large, *a.hist, a.d_n, a.n_static, a.n_cap, (uint32_t)kThreads * IT.value, a.totals);
+        with_flag(ctx->atomic_rank, [&](auto AR) {
+            launch_radix_downsweep<Mode::value, true, AR.value, IT.value, Band::value>(ctx->stream, grid, a);
+        });
+    });
+}
+
+// one pass of the wide sort, ws_upsweep + ws_downsweep.  The tables, their group shift and size are the context's WideSort's: pass p
+// accumulates into gsum[p % 3] and clears its predecessor's
+struct WsPass : PassIO {
+    int pass = 0;
+    // pass 0: the upsweep leaves the keys in raw_keys with one visibility bit per splat; the downsweep reads both (raw_keys as its keys_in)
+    uint32_t* raw_keys = nullptr;
+    unsigned long long* vmask = nullptr;
+    uint32_t *minkey_cur = nullptr, *minkey_next = nullptr;
+};
+
+template <int CULL, int ITEMS, int THREADS>
+void launch_ws_upsweep(hipStream_t s, int grid, const WideSort& w, const WsPass& a)
+{
+    hipLaunchKernelGGL((ws_upsweep<CULL, ITEMS, THREADS>), dim3(grid), dim3(THREADS), 0, s, a.keys_in, a.pos, a.raw_keys, a.vmask, a.d_n,
+                       a.n_static, a.n_cap, a.pass, a.minkey_cur, a.minkey_next, words(w.hist), words(w.gsum[a.pass % 3]), (int)w.gshift,
+                       words(w.gsum[(a.pass + 2) % 3]), w.gsum_words, *a.fp, a.lb);
+}
+template <bool CULL, int ITEMS, int THREADS>
+void launch_ws_downsweep(hipStream_t s, int grid, const WideSort& w, const WsPass& a)
+{
+    hipLaunchKernelGGL((ws_downsweep<CULL, ITEMS, THREADS>), dim3(grid), dim3(THREADS), ws_downsweep_lds(ITEMS, THREADS), s,
+                       CULL ? (const uint32_t*)a.raw_keys : a.keys_in, a.vals_in, (const unsigned long long*)a.vmask, a.d_n, a.n_static,
+                       a.n_cap, a.pass, (const uint32_t*)a.minkey_cur, (const uint32_t*)words(w.hist),
+                       (const uint32_t*)words(w.gsum[a.pass % 3]), (int)w.gshift, a.keys_out, a.vals_out, a.d_count_out, a.lb);
+}
+
 }  // namespace
 
 extern "C" {
@@ -494,14 +600,13 @@ int msplat_create(msplat_ctx** out, const msplat_config* cfg)
         ctx->atomic_rank = (hbad == 0) && c.rank_mode != MSPLAT_RANK_BALLOT;
         ctx->scan_free = getenv("MSPLAT_SCAN_KERNELS") == nullptr;
         // frames in flight: kernels that co-schedule well (msplat.h); AUTO and any stale padding value = one frame at a time
-        ctx->wide_sort = true;
-        ctx->ws_threads = c.frame_mode == MSPLAT_FRAMES_IN_FLIGHT ? (uint32_t)kWsThreadsSmall : (uint32_t)kWsThreads;
-        if (const char* sk = getenv("MSPLAT_SORT")) ctx->wide_sort = std::string(sk) != "lsd8";
+        ctx->ws.threads = c.frame_mode == MSPLAT_FRAMES_IN_FLIGHT ? (uint32_t)kWsThreadsSmall : (uint32_t)kWsThreads;
+        if (const char* sk = getenv("MSPLAT_SORT")) ctx->wide_sort_cfg = std::string(sk) != "lsd8";
         // debug switch: fewer workgroups than chunks, so that the chunk loops of the sort's and the binning's kernels take several turns
         if (const char* gc = getenv("MSPLAT_GRID_CAP")) ctx->grid_cap = (uint32_t)std::min(std::max(atol(gc), 1L), (long)kGridCap);
-        if (!ctx->atomic_rank) ctx->wide_sort = false;       // the wide kernels rank with lane-ordered LDS atomics only
+        if (!ctx->atomic_rank) ctx->wide_sort_cfg = false;       // the wide kernels rank with lane-ordered LDS atomics only
         ctx->spatial_mode = c.spatial_order;
-        if (ctx->wide_sort) {
+        if (ctx->wide_sort_cfg) {
             // ws_downsweep needs 72 / 104 KB of dynamic LDS with 512 threads (40 / 56 KB with 256).  The attribute belongs to
             // the function ON A DEVICE (a kernel object per device): it is requested once per device, with that device current
             // (a process-wide flag left devices 1.. of a msplat_group without it)
@@ -518,9 +623,8 @@ int msplat_create(msplat_ctx** out, const msplat_config* cfg)
                 });
                 return ok ? 1 : -1;
             }();
-            if (lds_state[dslot] < 0) { (void)hipGetLastError(); ctx->wide_sort = false; }
+            if (lds_state[dslot] < 0) { (void)hipGetLastError(); ctx->wide_sort_cfg = false; }
         }
-        ctx->wide_sort_cfg = ctx->wide_sort;
     }
     if (rc != MSPLAT_OK) {
         std::string msg = ctx->err;
@@ -773,20 +877,6 @@ int msplat_wait_event(msplat_ctx* ctx, void* event)
     return MSPLAT_OK;
 }
 
-// exclusive scan of a chunk-major histogram table along the chunks.  The element count is only known on the device,
-// so the variant is picked from the cloud size: up to 2 M splats (a few thousand chunk rows at most) the 16-workgroup
-// version, beyond that one workgroup per digit.
-static void launch_scan(hipStream_t s, bool small, uint32_t* hist, uint32_t hist_stride, const uint32_t* d_n,
-                        uint32_t n_static, uint32_t n_cap, uint32_t chunk, uint32_t* totals)
-{
-    if (small)
-        hipLaunchKernelGGL(radix_scan_small, dim3(kScanSmallBlocks), dim3(kThreads), 0, s, hist, d_n, n_static, n_cap, chunk,
-                           totals);
-    else
-        hipLaunchKernelGGL(radix_scan, dim3(256), dim3(kThreads), 0, s, hist, hist_stride, d_n, n_static, n_cap, chunk,
-                           totals);
-}
-
 #include "msplat_upload.hip.inc"
 
 #include "msplat_bands.hip.inc"
@@ -858,6 +948,14 @@ static int clear_frame_tables(msplat_ctx* ctx)
     return MSPLAT_OK;
 }
 
+// box_cull_kernel over the store's boxes, for list_live_boxes and msplat_debug_get_cull_boxes; returns its workgroups
+static uint32_t launch_box_cull(msplat_ctx* ctx, const CloudStore* st, const FrameParams& fp, uint32_t* list, uint32_t* cnt)
+{
+    const uint32_t wgs = div_up(st->nboxes, kBoxGroup);
+    hipLaunchKernelGGL(box_cull_kernel, dim3(wgs), dim3(kBoxGroup), 0, ctx->stream, (const CullBox*)st->boxes.p, st->nboxes, fp, list, cnt);
+    return wgs;
+}
+
 // Chunk-level cull (msplat_common.hip.h, box_live): for a spatially ordered cloud of which an EARLIER frame saw less than 70 %
 // (host-mapped V, read without synchronising; 0 = no frame yet) Sort starts with box_cull_kernel and pass 0 walks the listed
 // live boxes only.  Either form gives the same visible set, keys and order; the choice only matters for speed: the extra launch
@@ -870,12 +968,9 @@ static LiveBoxes list_live_boxes(msplat_ctx* ctx, const FrameParams& fp, uint32_
     const CloudStore* st = ctx->store.get();
     if (!st || !st->reordered || !st->boxes.p || ctx->point_mode) return lb;
     if (last_V == 0u || (uint64_t)last_V * 10u >= ctx->N * 7u) return lb;
-    const uint32_t wgs = div_up(st->nboxes, kBoxGroup);
-    hipLaunchKernelGGL(box_cull_kernel, dim3(wgs), dim3(kBoxGroup), 0, ctx->stream, (const CullBox*)st->boxes.p, st->nboxes, fp,
-                       (uint32_t*)ctx->live_list.p, (uint32_t*)ctx->live_cnt.p);
     lb.list = (const uint32_t*)ctx->live_list.p;
     lb.cnt = (const uint32_t*)ctx->live_cnt.p;
-    lb.wgs = wgs;
+    lb.wgs = launch_box_cull(ctx, st, fp, (uint32_t*)ctx->live_list.p, (uint32_t*)ctx->live_cnt.p);
     ctx->last_sort_listed = true;
     return lb;
 }
@@ -1000,23 +1095,89 @@ static int sort_impl(msplat_ctx* ctx, const float cameraMat[16], const float pro
     return with_pending_overflow(ctx, [&] { return issue_sort(ctx, fp); });     // the sort itself is still performed
 }
 
+// three passes of 10 + (8..11) + (8..11) key bits (msplat_sort.hip.h, ws_*): 6 launches.
+// pass 0: positions -> raw keys + visibility bits in keyB / vmask -> (keyA, valA); pass 1: A -> B; pass 2: B -> A
+static void issue_wide_sort(msplat_ctx* ctx, const FrameParams& fp)
+{
+    hipStream_t s = ctx->stream;
+    const WideSort& w = ctx->ws;
+    const uint32_t N = (uint32_t)ctx->N;
+    uint32_t* counters = words(ctx->counters);
+    // Passes 1 and 2 see only the V splats that survived the cull.  With 8192-key chunks and V << N (a band-culled rank of a
+    // multi-GPU frame keeps 17 %, a camera inside a scene 40 %) they would run on ~100 workgroups: they take 4096-key chunks
+    // when an EARLIER frame's V (host-mapped word, read without synchronising) was below 2 M.  Any choice is correct at any V.
+    const uint32_t last_V = host_word(ctx, kHostV);
+    const uint32_t items12 = (w.items == 16u && last_V != 0u && (uint64_t)last_V + (last_V >> 2) <= (2u << 20)) ? 8u : w.items;
+    WsPass a;               // what the three passes share
+    a.n_cap = N;  a.fp = &fp;
+    a.minkey_cur = counters + kCntMinKey + (ctx->sort_parity & 1u);
+    a.minkey_next = counters + kCntMinKey + ((ctx->sort_parity ^ 1u) & 1u);
+    ctx->sort_parity ^= 1u;
+    WsPass p0 = a;
+    p0.pos = (const float4*)ctx->pos4.p;  p0.raw_keys = words(ctx->keyB);  p0.vmask = (unsigned long long*)ctx->vmask.p;  p0.n_static = N;
+    p0.keys_out = words(ctx->keyA);  p0.vals_out = words(ctx->valA);  p0.d_count_out = counters + kCntV;
+    p0.lb = list_live_boxes(ctx, fp, last_V);       // (launches box_cull_kernel when the view is a partial one)
+    // pass 0 over listed boxes: fewer chunks than the cloud has, so 4096-key chunks keep the CUs covered (as for passes 1, 2)
+    uint32_t items = p0.lb.list != nullptr ? 8u : w.items;
+    int wgrid = grid_for(div_up(N, w.threads * items), ctx->grid_cap);
+    auto upsweep = [&](auto CULL, const WsPass& p) {
+        // The upsweeps have no order to keep.  One frame at a time and 4096-key chunks (up to 2 M splats): twice the threads per
+        // chunk, half the keys per thread -- 241 workgroups of 16 waves instead of 8 at 1 M: sort 57.4 -> 55.7 us.  Not at 6 M
+        // (158 -> 166 us) and not for frames in flight (-0.5 %): EXPERIMENTS.md, "The upsweeps keep no order".
+        if (items == 8u && w.threads == (uint32_t)kWsThreads)
+            launch_ws_upsweep<CULL.value, 4, 2 * kWsThreads>(s, wgrid, w, p);
+        else
+            with_ws_shape(items, w.threads, [&](auto I, auto T) { launch_ws_upsweep<CULL.value, I.value, T.value>(s, wgrid, w, p); });
+    };
+    auto downsweep = [&](auto CULL, const WsPass& p) {
+        with_ws_shape(items, w.threads, [&](auto I, auto T) { launch_ws_downsweep<CULL.value, I.value, T.value>(s, wgrid, w, p); });
+    };
+    with_int<2, 1>(fp.band_cull ? 2 : 1, [&](auto CULL) { upsweep(CULL, p0); });
+    downsweep(flag_t<true>{}, p0);
+    items = items12;
+    wgrid = grid_for(div_up(N, w.threads * items), ctx->grid_cap);
+    a.d_n = counters + kCntV;
+    for (a.pass = 1; a.pass < 3; ++a.pass) {
+        a.buffers(ctx, a.pass == 2);
+        upsweep(int_t<0>{}, a);
+        downsweep(flag_t<false>{}, a);
+    }
+}
+
+// the four 8-bit passes (MSPLAT_SORT=lsd8): scan-free, 2 launches each, while the chunk table is small, else upsweep + scan + downsweep
+static void issue_lsd8_sort(msplat_ctx* ctx, const FrameParams& fp)
+{
+    const uint32_t N = (uint32_t)ctx->N;
+    uint32_t* d_V = words(ctx->counters) + kCntV;
+    // chunk size by cloud size (msplat_common.hip.h, kSortItems): 2048 keys up to 2 M splats, 4096 beyond
+    const bool large = ctx->N > (2u << 20);
+    const uint32_t nchunks = div_up(N, (uint32_t)kThreads * (large ? kSortItemsLarge : kSortItems));
+    const int grid = grid_for(nchunks, ctx->grid_cap);
+    RadixPass a;            // what the four passes share
+    a.n_cap = N;  a.fp = &fp;
+    a.hist = &ctx->hist;  a.totals = words(ctx->totals);  a.fused = ctx->scan_free && nchunks <= kFusedMaxChunks;
+    // pass 0: cull + key fused into the first radix pass (presort_compute.glsl + byte 0 of the sort)
+    RadixPass p0 = a;
+    p0.pos = (const float4*)ctx->pos4.p;  p0.n_static = N;
+    p0.keys_out = words(ctx->keyB);  p0.vals_out = words(ctx->valB);  p0.d_count_out = d_V;
+    p0.gsum = &ctx->gsumS[0];  p0.gsum_zero = &ctx->gsumS[1];       // (gsum_zero always, scan-free or not: keeps both tables clean)
+    p0.lb = list_live_boxes(ctx, fp, host_word(ctx, kHostV));
+    // (r6: frames without the band-restricted cull -- every single-GPU frame -- run instantiations that leave its code out)
+    with_flag(fp.band_cull != 0, [&](auto BAND) { issue_radix_pass(ctx, int_t<MODE_CULL>{}, BAND, large, grid, p0); });
+    // passes 1..3 on the V survivors (V stays on the device; splatrenderer.cpp:195-204's readback is gone)
+    a.d_n = d_V;
+    for (int pass = 1; pass < 4; ++pass) {
+        a.buffers(ctx, pass & 1);
+        a.shift = pass * 8;
+        a.gsum = &ctx->gsumS[pass & 1];  a.gsum_zero = &ctx->gsumS[(pass + 1) & 1];
+        issue_radix_pass(ctx, int_t<MODE_KEYS>{}, flag_t<true>{}, large, grid, a);
+    }
+}
+
 static int issue_sort(msplat_ctx* ctx, const FrameParams& fp)
 {
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    const uint32_t N = (uint32_t)ctx->N;
-    uint32_t* counters = (uint32_t*)ctx->counters.p;
-    uint32_t* d_V = counters + kCntV;
-    uint32_t* hist = (uint32_t*)ctx->hist.p;
-    uint32_t* totals = (uint32_t*)ctx->totals.p;
-    const float4* pos = (const float4*)ctx->pos4.p;
-    uint32_t *kA = (uint32_t*)ctx->keyA.p, *kB = (uint32_t*)ctx->keyB.p;
-    uint32_t *vA = (uint32_t*)ctx->valA.p, *vB = (uint32_t*)ctx->valB.p;
-    // chunk size by cloud size (msplat_common.hip.h, kSortItems): 2048 keys up to 2 M splats, 4096 beyond
-    const bool large = ctx->N > (2u << 20);
-    const uint32_t chunk = (uint32_t)kThreads * (large ? kSortItemsLarge : kSortItems);
-    const int grid = grid_for(div_up(N, chunk), ctx->grid_cap);
-
     if (ctx->tables_dirty) {
         int rc = clear_frame_tables(ctx);
         if (rc) return rc;
@@ -1024,108 +1185,9 @@ static int issue_sort(msplat_ctx* ctx, const FrameParams& fp)
     const bool timed = ctx->ev_ok && (ctx->sort_calls++ % ctx->timing_stride) == 0;
     const int tset = (int)(ctx->sort_sets % msplat_ctx::kEvSets);
     if (timed) HIP_TRY(ctx, hipEventRecord(ctx->ev[tset][kEvSortBegin], s));
-    const bool wide = ctx->wide_sort;
-    if (wide) {
-        // three passes of 10 + (8..11) + (8..11) key bits (msplat_sort.hip.h, ws_*): 6 launches.
-        // pass 0: positions -> raw keys + visibility bits in keyB / vmask -> (keyA, valA); pass 1: A -> B; pass 2: B -> A
-        uint32_t* mk_cur = counters + kCntMinKey + (ctx->sort_parity & 1u);
-        uint32_t* mk_next = counters + kCntMinKey + ((ctx->sort_parity ^ 1u) & 1u);
-        ctx->sort_parity ^= 1u;
-        uint32_t* whist = (uint32_t*)ctx->wsHist.p;
-        unsigned long long* vm = (unsigned long long*)ctx->vmask.p;
-        const int gsh = (int)ctx->ws_gshift;
-        const uint32_t gw = ctx->ws_gsum_words;
-        auto gt = [&](int pass) { return (uint32_t*)ctx->wsGsum[(pass + 3) % 3].p; };
-        // Passes 1 and 2 see only the V splats that survived the cull.  With 8192-key chunks and V << N (a band-culled rank of a
-        // multi-GPU frame keeps 17 %, a camera inside a scene 40 %) they would run on ~100 workgroups: they take 4096-key chunks
-        // when an EARLIER frame's V (host-mapped word, read without synchronising) was below 2 M.  Any choice is correct at any V.
-        const uint32_t last_V = host_word(ctx, kHostV);
-        const uint32_t items0 = ctx->ws_items;
-        const uint32_t items12 = (items0 == 16u && last_V != 0u && (uint64_t)last_V + (last_V >> 2) <= (2u << 20)) ? 8u : items0;
-        const LiveBoxes lb = list_live_boxes(ctx, fp, last_V);       // (launches box_cull_kernel when the view is a partial one)
-        // pass 0 over listed boxes: fewer chunks than the cloud has, so 4096-key chunks keep the CUs covered (as for passes 1, 2)
-        uint32_t items = lb.list != nullptr ? 8u : items0;
-        int wgrid = grid_for(div_up(N, ctx->ws_threads * items), ctx->grid_cap);
-        const uint32_t* dV = d_V;
-        auto upsweep = [&](auto CULL, const auto&... args) {
-            // The upsweeps have no order to keep.  One frame at a time and 4096-key chunks (up to 2 M splats): twice the threads per
-            // chunk, half the keys per thread -- 241 workgroups of 16 waves instead of 8 at 1 M: sort 57.4 -> 55.7 us.  Not at 6 M
-            // (158 -> 166 us) and not for frames in flight (-0.5 %): EXPERIMENTS.md, "The upsweeps keep no order".
-            if (items == 8u && ctx->ws_threads == (uint32_t)kWsThreads)
-                hipLaunchKernelGGL((ws_upsweep<CULL.value, 4, 2 * kWsThreads>), dim3(wgrid), dim3(2 * kWsThreads), 0, s, args...);
-            else
-                with_ws_shape(items, ctx->ws_threads, [&](auto I, auto T) {
-                    hipLaunchKernelGGL((ws_upsweep<CULL.value, I.value, T.value>), dim3(wgrid), dim3(T.value), 0, s, args...);
-                });
-        };
-        auto downsweep = [&](auto CULL, const auto&... args) {
-            with_ws_shape(items, ctx->ws_threads, [&](auto I, auto T) {
-                hipLaunchKernelGGL((ws_downsweep<CULL.value, I.value, T.value>), dim3(wgrid), dim3(T.value),
-                                   ws_downsweep_lds(I.value, T.value), s, args...);
-            });
-        };
-        with_int<2, 1>(fp.band_cull ? 2 : 1, [&](auto CULL) {
-            upsweep(CULL, (const uint32_t*)nullptr, pos, kB, vm, (const uint32_t*)nullptr, N, N, 0, mk_cur,
-                    mk_next, whist, gt(0), gsh, gt(-1), gw, fp, lb);
-        });
-        downsweep(flag_t<true>{}, (const uint32_t*)kB, (const uint32_t*)nullptr, (const unsigned long long*)vm,
-                  (const uint32_t*)nullptr, N, N, 0, (const uint32_t*)mk_cur, (const uint32_t*)whist, (const uint32_t*)gt(0), gsh, kA, vA,
-                  d_V, lb);
-        items = items12;
-        wgrid = grid_for(div_up(N, ctx->ws_threads * items), ctx->grid_cap);
-        for (int pass = 1; pass < 3; ++pass) {
-            uint32_t *kin = pass == 1 ? kA : kB, *vin = pass == 1 ? vA : vB, *kout = pass == 1 ? kB : kA, *vout = pass == 1 ? vB : vA;
-            upsweep(int_t<0>{}, (const uint32_t*)kin, (const float4*)nullptr, (uint32_t*)nullptr,
-                    (unsigned long long*)nullptr, dV, 0u, N, pass, mk_cur, mk_next, whist, gt(pass), gsh, gt(pass - 1), gw, fp);
-            downsweep(flag_t<false>{}, (const uint32_t*)kin, (const uint32_t*)vin, (const unsigned long long*)nullptr, dV,
-                      0u, N, pass, (const uint32_t*)mk_cur, (const uint32_t*)whist, (const uint32_t*)gt(pass), gsh, kout, vout, (uint32_t*)nullptr);
-        }
-    } else {
-        // scan-free passes (2 launches each) while the chunk table is small, else upsweep + scan + downsweep
-        const bool fused = ctx->scan_free && div_up(N, chunk) <= kFusedMaxChunks;
-        auto gacc = [&](int pass) { return fused ? (uint32_t*)ctx->gsumS[pass & 1].p : nullptr; };
-        auto gzero = [&](int pass) { return (uint32_t*)ctx->gsumS[(pass + 1) & 1].p; };      // always: keeps both tables clean
-        auto upsweep = [&](auto MODE, auto BAND, const auto&... args) {
-            with_sort_items(large, [&](auto IT) {
-                hipLaunchKernelGGL((radix_upsweep<MODE.value, IT.value, BAND.value>), dim3(grid), dim3(kThreads), 0, s, args...);
-            });
-        };
-        auto downsweep = [&](auto MODE, auto BAND, const auto&... args) {
-            with_sort_items(large, [&](auto IT) {
-                with_flag(ctx->atomic_rank, [&](auto AR) {
-                    hipLaunchKernelGGL((radix_downsweep<MODE.value, true, AR.value, IT.value, BAND.value>), dim3(grid), dim3(kThreads), 0, s,
-                                       args...);
-                });
-            });
-        };
-        // pass 0: cull + key fused into the first radix pass (presort_compute.glsl + byte 0 of the sort)
-        const LiveBoxes lb = list_live_boxes(ctx, fp, host_word(ctx, kHostV));
-        // (r6: frames without the band-restricted cull -- every single-GPU frame -- run instantiations that leave its code out)
-        with_flag(fp.band_cull != 0, [&](auto BAND) {
-            upsweep(int_t<MODE_CULL>{}, BAND, (const uint32_t*)nullptr, pos, (const uint32_t*)nullptr, N, N, 0, hist, ctx->hist_stride, gacc(0),
-                    gzero(0), ctx->gsumS_rows, fp, (const uint32_t*)nullptr, (uint32_t*)nullptr, ctx->gsupS, lb);
-            if (!fused) launch_scan(s, !large, hist, ctx->hist_stride, nullptr, N, N, chunk, totals);
-            downsweep(int_t<MODE_CULL>{}, BAND, (const uint32_t*)nullptr, (const uint32_t*)nullptr, pos, (const uint32_t*)nullptr, N, N, 0,
-                      (const uint32_t*)hist, ctx->hist_stride, (const uint32_t*)totals, kB, vB, d_V, (const uint32_t*)nullptr,
-                      (const uint32_t*)gacc(0), (uint32_t*)nullptr, fp, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr,
-                      (uint32_t*)nullptr, 0, 0, ctx->gsupS, lb);
-        });
-        // passes 1..3 on the V survivors (V stays on the device; splatrenderer.cpp:195-204's readback is gone)
-        for (int pass = 1; pass < 4; ++pass) {
-            uint32_t* kin = (pass & 1) ? kB : kA;
-            uint32_t* vin = (pass & 1) ? vB : vA;
-            uint32_t* kout = (pass & 1) ? kA : kB;
-            uint32_t* vout = (pass & 1) ? vA : vB;
-            upsweep(int_t<MODE_KEYS>{}, flag_t<true>{}, (const uint32_t*)kin, (const float4*)nullptr, (const uint32_t*)d_V, 0u, N, pass * 8, hist,
-                    ctx->hist_stride, gacc(pass), gzero(pass), ctx->gsumS_rows, fp, (const uint32_t*)nullptr, (uint32_t*)nullptr,
-                    ctx->gsupS);
-            if (!fused) launch_scan(s, !large, hist, ctx->hist_stride, d_V, 0u, N, chunk, totals);
-            downsweep(int_t<MODE_KEYS>{}, flag_t<true>{}, (const uint32_t*)kin, (const uint32_t*)vin, (const float4*)nullptr, (const uint32_t*)d_V, 0u, N,
-                      pass * 8, (const uint32_t*)hist, ctx->hist_stride, (const uint32_t*)totals, kout, vout, (uint32_t*)nullptr,
-                      (const uint32_t*)nullptr, (const uint32_t*)gacc(pass), (uint32_t*)nullptr, fp, (uint32_t*)nullptr,
-                      (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, 0, 0, ctx->gsupS);
-        }
-    }
+    const bool wide = ctx->ws.on;
+    if (wide) issue_wide_sort(ctx, fp);
+    else issue_lsd8_sort(ctx, fp);
     if (timed) {
         HIP_TRY(ctx, hipEventRecord(ctx->ev[tset][kEvSortEnd], s));
         ctx->sort_sets++;
@@ -1136,7 +1198,7 @@ static int issue_sort(msplat_ctx* ctx, const FrameParams& fp)
         if (!wide) return fail(ctx, MSPLAT_ERR_HIP, "msplat_sort: a kernel launch failed");
         // e.g. the dynamic-LDS request was not honoured on this device: later frames take the four 8-bit passes, which
         // need no opt-in (this frame is lost; the tables are restored before the next one)
-        ctx->wide_sort = ctx->wide_sort_cfg = false;
+        ctx->ws.on = ctx->wide_sort_cfg = false;
         return fail(ctx, MSPLAT_ERR_HIP, "msplat_sort: a kernel launch of the three-pass sort failed (%s); the context falls back "
                     "to the 8-bit passes from the next frame on", hipGetErrorString(le));
     }
@@ -1287,9 +1349,8 @@ static void issue_binning(RenderChain& rc, int keep_overflow, int occ_pass)
     const bool fused1 = ctx->scan_free && div_up(N, bchunk) <= kFusedMaxChunks;
     const uint32_t last_D = host_word(ctx, kHostD);
     const bool fused2 = ctx->scan_free && last_D != 0u && div_up((uint64_t)last_D + (last_D >> 2), kPairChunk) <= kFusedMaxChunks &&
-                        div_up(cap, kPairChunk) <= ctx->hist2_stride;                  // (the tables hold every chunk the capacity allows)
-    uint32_t* gB1 = (uint32_t*)ctx->gsumB1.p;
-    uint32_t* gB2 = (uint32_t*)ctx->gsumB2.p;
+                        div_up(cap, kPairChunk) <= ctx->hist2.stride;                  // (the tables hold every chunk the capacity allows)
+    uint32_t *gB1 = words(ctx->gsumB1.buf), *gB2 = words(ctx->gsumB2.buf);
     // column pass: groups of 8 consecutive chunks share an XCD (xcd_grouped): the seams between the runs neighbouring chunks write
     // merge in that XCD's L2.  Measured r4 (serial binning, groups of 0 / 2 / 4 / 8 / 16 / 32): 6 M / 4096^2 328 / 320 / 316 / 315 /
     // 315 / 313 us, scene-like 6 M 201 / 194 / 194 / 195, 1 M unchanged (57); the fully XCD-contiguous mapping of r3 was slower.
@@ -1297,18 +1358,18 @@ static void issue_binning(RenderChain& rc, int keep_overflow, int occ_pass)
     const bool small = ctx->N <= (2u << 20);      // (launch_scan)
     // (bin1_upsweep also clears the row pass's group table: its consumer, the previous frame's row downsweep, is long done)
     hipLaunchKernelGGL(bin1_upsweep<kBinChunk>, dim3(g1), dim3(kThreads), 0, s, (const uint32_t*)ctx->rect.p, d_V,
-                       (uint32_t*)ctx->hist1.p, ctx->hist1_stride, d_overflow, fused1 ? gB1 : nullptr, gB2,
-                       ctx->gsumB2_rows, hv_cur, hv_next, (uint8_t*)ctx->heavy_flag.p, heavy_slots, ctx->gsupB1,
+                       words(ctx->hist1.buf), ctx->hist1.stride, d_overflow, fused1 ? gB1 : nullptr, gB2,
+                       ctx->gsumB2.rows, hv_cur, hv_next, (uint8_t*)ctx->heavy_flag.p, heavy_slots, ctx->gsumB1.sup,
                        keep_overflow, d_first);
     if (!fused1)
-        launch_scan(s, small, (uint32_t*)ctx->hist1.p, ctx->hist1_stride, d_V, 0u, N, bchunk, totals1);
+        launch_scan(s, small, ctx->hist1, d_V, 0u, N, bchunk, totals1);
     with_flag(ctx->atomic_rank, [&](auto AR) {
         hipLaunchKernelGGL((bin1_downsweep<AR.value, kBinChunk>), dim3(g1 + nhelp), dim3(kThreads), 0, s,
-                           (const uint32_t*)ctx->rect.p, d_V, (const uint32_t*)ctx->hist1.p, ctx->hist1_stride,
+                           (const uint32_t*)ctx->rect.p, d_V, (const uint32_t*)words(ctx->hist1.buf), ctx->hist1.stride,
                            (const uint32_t*)totals1, (uint32_t*)ctx->pairsA.p, cap, d_D, d_overflow, ctx->d_flags,
                            async_overflow_flag ? 1 : 0, fused1 ? (const uint32_t*)gB1 : nullptr, fused1 ? totals1 : nullptr,
                            xcdg, (const uint32_t*)hv_cur, (const uint8_t*)ctx->heavy_flag.p,
-                           (uint32_t)nhelp, fp.tiles_x, ctx->gsupB1, (const uint32_t*)d_Vsort,
+                           (uint32_t)nhelp, fp.tiles_x, ctx->gsumB1.sup, (const uint32_t*)d_Vsort,
                            (keep_overflow && ctx->d_flags) ? ctx->d_flags + kHostPass2Pairs : (uint32_t*)nullptr, ctx->two_pass.seq, d_first);
     });
     // pass 2: stable partition by tile row (one generic radix pass on the top byte); words become (tx<<24)|rank
@@ -1324,22 +1385,18 @@ static void issue_binning(RenderChain& rc, int keep_overflow, int occ_pass)
     // counts into the list offsets (+ the heaviest-first order when it is wanted).  (r3-r5: contexts with frames in flight
     // searched the offsets in the partitioned array with a kernel of their own, 1 % faster then; equal in r6 under the CU halves
     // -- 6290 / 6298, 2478-2514 / 2485-2494, 1363-1403 / 1384-1403 frames/s at 1 M, 6 M, 6 M / 4096^2 -- and removed: one launch less.)
-    uint32_t* bincnt = (uint32_t*)ctx->bincnt.p;
     const int g2 = grid_for(div_up(cap, kPairChunk), ctx->grid_cap);
-    hipLaunchKernelGGL(radix_upsweep<MODE_PAIR>, dim3(g2), dim3(kThreads), 0, s, (const uint32_t*)ctx->pairsA.p,
-                       nullptr, d_D, 0u, cap, 24, (uint32_t*)ctx->hist2.p, ctx->hist2_stride, fused2 ? gB2 : nullptr, gB1,
-                       ctx->gsumB1_rows, fp, (const uint32_t*)totals1, bincnt, ctx->gsupB2);
+    RadixPass a;
+    a.keys_in = (const uint32_t*)ctx->pairsA.p;  a.keys_out = (uint32_t*)ctx->pairsB.p;
+    a.d_n = d_D;  a.n_cap = cap;  a.shift = 24;  a.fp = &fp;
+    a.hist = &ctx->hist2;  a.totals = totals2;  a.totals_out = fused2 ? totals2 : nullptr;
+    a.gsum = &ctx->gsumB2;  a.gsum_zero = &ctx->gsumB1;  a.fused = fused2;
+    a.col_totals = totals1;  a.bincnt = (uint32_t*)ctx->bincnt.p;  a.queue = d_queue;
+    a.tile_start = (uint32_t*)ctx->tile_start.p;  a.tile_order = (uint32_t*)ctx->tile_order.p;  a.ntiles = ntiles;  a.do_order = (ordered ? 1 : 0) | 2;
+    launch_radix_upsweep<MODE_PAIR, kSortItems, true>(s, g2, a);
     if (!fused2)
-        launch_scan(s, small, (uint32_t*)ctx->hist2.p, ctx->hist2_stride, d_D, 0u, cap, (uint32_t)kPairChunk, totals2);
-    const int g2d = g2 + 1;
-    with_flag(ctx->atomic_rank, [&](auto AR) {
-        hipLaunchKernelGGL((radix_downsweep<MODE_PAIR, false, AR.value>), dim3(g2d), dim3(kThreads), 0, s,
-                           (const uint32_t*)ctx->pairsA.p, nullptr, nullptr, d_D, 0u, cap, 24,
-                           (const uint32_t*)ctx->hist2.p, ctx->hist2_stride, (const uint32_t*)totals2,
-                           (uint32_t*)ctx->pairsB.p, nullptr, nullptr, (const uint32_t*)totals1,
-                           fused2 ? (const uint32_t*)gB2 : nullptr, fused2 ? totals2 : nullptr, fp, bincnt,
-                           (uint32_t*)ctx->tile_start.p, (uint32_t*)ctx->tile_order.p, d_queue, ntiles, (ordered ? 1 : 0) | 2, ctx->gsupB2);
-    });
+        launch_scan(s, small, ctx->hist2, d_D, 0u, cap, (uint32_t)kPairChunk, totals2);
+    with_flag(ctx->atomic_rank, [&](auto AR) { launch_radix_downsweep<MODE_PAIR, false, AR.value, kSortItems, true>(s, g2 + 1, a); });
     rc.ordered = ordered;
     rc.comp_items = comp_items;
     rc.comp_pool = comp_pool;
@@ -1753,9 +1810,9 @@ static int ensure_stereo_ranks(msplat_ctx* ctx)
     if ((rc = buf_alloc(ctx, ctx->rect, need * 4))) return rc;
     if ((rc = buf_alloc(ctx, ctx->heavy_flag, (size_t)div_up(need, kBinChunk) + 64))) return rc;
     HIP_TRY(ctx, hipMemsetAsync(ctx->heavy_flag.p, 0, ctx->heavy_flag.bytes, ctx->stream));
-    ctx->hist1_stride = std::max(1u, div_up(need, kBinChunk));
-    if ((rc = buf_alloc(ctx, ctx->hist1, (size_t)256 * ctx->hist1_stride * 4))) return rc;
-    if ((rc = alloc_group_table(ctx, ctx->gsumB1, ctx->gsumB1_rows, ctx->hist1_stride, ctx->gsupB1))) return rc;
+    ctx->hist1.stride = std::max(1u, div_up(need, kBinChunk));
+    if ((rc = buf_alloc(ctx, ctx->hist1.buf, (size_t)256 * ctx->hist1.stride * 4))) return rc;
+    if ((rc = alloc_group_table(ctx, ctx->gsumB1, ctx->hist1.stride))) return rc;
     ctx->rank_cap = need;
     return MSPLAT_OK;
 }

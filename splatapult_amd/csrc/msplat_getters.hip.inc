@@ -98,8 +98,7 @@ int msplat_debug_get_cull_boxes(msplat_ctx* ctx, uint32_t* live, uint32_t* total
     int rc = buf_alloc(ctx, list, (size_t)wgs * kBoxGroup * 4);
     if (!rc) rc = buf_alloc(ctx, cnt, 256 * 4);
     if (!rc) {
-        hipLaunchKernelGGL(box_cull_kernel, dim3(wgs), dim3(kBoxGroup), 0, ctx->stream, (const CullBox*)st->boxes.p, st->nboxes,
-                           ctx->last_sort_fp, (uint32_t*)list.p, (uint32_t*)cnt.p);
+        launch_box_cull(ctx, st, ctx->last_sort_fp, (uint32_t*)list.p, (uint32_t*)cnt.p);
         uint32_t h[256];
         hipError_t e = hipMemcpyAsync(h, cnt.p, (size_t)wgs * 4, hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);

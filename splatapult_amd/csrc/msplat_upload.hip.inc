@@ -1,17 +1,23 @@
 // msplat_upload.hip.inc -- SplatRenderer::Init: per-cloud buffers, the spatial storage order, cloud / PLY / point uploads, the sprite, download
 // (textually part of msplat_device.hip: included inside its extern "C" block, after struct msplat_ctx and the helpers; r6 split, VERDICT r5 item 7)
 
-// group table for `nchunks` chunk rows, zero-filled (the stream is idle whenever buffers are (re)allocated)
-static int alloc_group_table(msplat_ctx* ctx, Buf& b, uint32_t& rows, uint64_t nchunks, uint32_t& sup)
+// a table the frame's kernels keep clean, zero-filled (the stream is idle whenever buffers are (re)allocated)
+static int alloc_frame_table(msplat_ctx* ctx, Buf& b, size_t bytes)
 {
-    sup = (uint32_t)((nchunks >> kSuperShift) + 2);                      // supergroup rows first, then the group rows
-    rows = (uint32_t)(sup + (nchunks >> kGroupShift) + 2);
-    int rc = buf_alloc(ctx, b, (size_t)rows * 256 * sizeof(uint32_t));
+    int rc = buf_alloc(ctx, b, bytes);
     if (rc) return rc;
-    rows = (uint32_t)(b.bytes / (256 * sizeof(uint32_t)));
     b.frame_table = true;
     HIP_TRY(ctx, hipMemsetAsync(b.p, 0, b.bytes, ctx->stream));
     return MSPLAT_OK;
+}
+
+// group table for `nchunks` chunk rows
+static int alloc_group_table(msplat_ctx* ctx, GroupTable& t, uint64_t nchunks)
+{
+    t.sup = (uint32_t)((nchunks >> kSuperShift) + 2);                    // supergroup rows first, then the group rows
+    int rc = alloc_frame_table(ctx, t.buf, (size_t)(t.sup + (nchunks >> kGroupShift) + 2) * 256 * sizeof(uint32_t));
+    t.rows = (uint32_t)(t.buf.bytes / (256 * sizeof(uint32_t)));
+    return rc;
 }
 
 static int ensure_pair_capacity(msplat_ctx* ctx, uint64_t cap)
@@ -22,13 +28,42 @@ static int ensure_pair_capacity(msplat_ctx* ctx, uint64_t cap)
     if (rc) return rc;
     rc = buf_alloc(ctx, ctx->pairsB, cap * sizeof(uint32_t));
     if (rc) return rc;
-    ctx->hist2_stride = div_up(cap, kPairChunk);
-    rc = buf_alloc(ctx, ctx->hist2, (size_t)256 * ctx->hist2_stride * sizeof(uint32_t));
+    ctx->hist2.stride = div_up(cap, kPairChunk);
+    rc = buf_alloc(ctx, ctx->hist2.buf, (size_t)256 * ctx->hist2.stride * sizeof(uint32_t));
     if (rc) return rc;
-    rc = alloc_group_table(ctx, ctx->gsumB2, ctx->gsumB2_rows, ctx->hist2_stride, ctx->gsupB2);
+    rc = alloc_group_table(ctx, ctx->gsumB2, ctx->hist2.stride);
     if (rc) return rc;
     ctx->pair_cap = cap;
     return MSPLAT_OK;
+}
+
+// What a cloud's size and the context's frame mode decide about the wide sort -- whether it runs, its threads, keys per thread and
+// group shift -- and its tables, sized by that
+static int plan_wide_sort(msplat_ctx* ctx, uint64_t n)
+{
+    WideSort& w = ctx->ws;
+    // the three wide passes at every size.  (r3-r5: contexts with frames in flight took the four 8-bit passes beyond 2 M splats --
+    // 6 M: 1616 against 1497 frames/s then.  Since the 16-key variants lost their spills (r6) the three passes win there too, with
+    // two frames per half of the CUs: 6 M / 1080p 2384-2435 -> 2464-2473 frames/s, 6 M / 4096^2 1324-1331 -> 1381-1398; the scene-like
+    // 6 M cloud -1 %: EXPERIMENTS.md.  MSPLAT_SORT=lsd8 still selects the 8-bit passes.)
+    w.on = ctx->wide_sort_cfg;
+    // frames in flight: the sort's 256-thread form (4096-key chunks of 4 waves find slots between other frames' workgroups) up to
+    // 2 M splats, its 512-thread form beyond (r6: 6 M / 1080p 2478-2514 -> 2572-2591 frames/s, 6 M / 4096^2 unchanged; at 1 M the
+    // 512-thread form loses 2 %: EXPERIMENTS.md)
+    if (ctx->cfg.frame_mode == MSPLAT_FRAMES_IN_FLIGHT) w.threads = n > (2u << 20) ? (uint32_t)kWsThreads : (uint32_t)kWsThreadsSmall;
+    if (!w.on) return MSPLAT_OK;
+    // 4096-key chunks up to 2 M splats, 8192 beyond; groups of 16 chunk rows while
+    // there are at most 512 rows, else of 32 (a downsweep sums <= nchunks / G + G - 1 rows)
+    w.items = n > (2u << 20) ? 16u : 8u;
+    // (the tables are sized for 8 keys per thread: passes 1 and 2 drop to that when few splats survive the cull, issue_wide_sort)
+    const uint32_t nch = std::max(1u, div_up(n, (uint64_t)w.threads * 8u));
+    w.gshift = nch <= 512u ? 4u : 5u;
+    w.gsum_words = (uint32_t)(((nch >> w.gshift) + 2) * kWsMaxBins);
+    int rc = buf_alloc(ctx, w.hist, (size_t)nch * kWsMaxBins * 4);
+    for (auto& g : w.gsum)
+        if (!rc) rc = alloc_frame_table(ctx, g, (size_t)w.gsum_words * 4);
+    if (!rc) rc = buf_alloc(ctx, ctx->vmask, (size_t)div_up(std::max<uint64_t>(n, 1), 64) * 8 + 64);
+    return rc;
 }
 
 // (re)allocates every per-cloud device buffer for n splats; leaves the context without a cloud.
@@ -90,38 +125,13 @@ static int prepare_cloud_buffers(msplat_ctx* ctx, uint64_t n, bool full_sh, cons
     if ((rc = buf_alloc(ctx, ctx->keyB, alloc_n * 4))) return rc;
     if ((rc = buf_alloc(ctx, ctx->valA, alloc_n * 4))) return rc;
     if ((rc = buf_alloc(ctx, ctx->valB, alloc_n * 4))) return rc;
-    ctx->hist_stride = std::max(1u, div_up(n, kSortChunk));
-    if ((rc = buf_alloc(ctx, ctx->hist, (size_t)256 * ctx->hist_stride * 4))) return rc;
-    uint32_t rows_s0 = 0;
-    if ((rc = alloc_group_table(ctx, ctx->gsumS[0], rows_s0, ctx->hist_stride, ctx->gsupS))) return rc;
-    if ((rc = alloc_group_table(ctx, ctx->gsumS[1], ctx->gsumS_rows, ctx->hist_stride, ctx->gsupS))) return rc;
-    ctx->gsumS_rows = std::min(ctx->gsumS_rows, rows_s0);
-    // the three wide passes at every size.  (r3-r5: contexts with frames in flight took the four 8-bit passes beyond 2 M splats --
-    // 6 M: 1616 against 1497 frames/s then.  Since the 16-key variants lost their spills (r6) the three passes win there too, with
-    // two frames per half of the CUs: 6 M / 1080p 2384-2435 -> 2464-2473 frames/s, 6 M / 4096^2 1324-1331 -> 1381-1398; the scene-like
-    // 6 M cloud -1 %: EXPERIMENTS.md.  MSPLAT_SORT=lsd8 still selects the 8-bit passes.)
-    ctx->wide_sort = ctx->wide_sort_cfg;
-    // frames in flight: the sort's 256-thread form (4096-key chunks of 4 waves find slots between other frames' workgroups) up to
-    // 2 M splats, its 512-thread form beyond (r6: 6 M / 1080p 2478-2514 -> 2572-2591 frames/s, 6 M / 4096^2 unchanged; at 1 M the
-    // 512-thread form loses 2 %: EXPERIMENTS.md)
-    if (ctx->cfg.frame_mode == MSPLAT_FRAMES_IN_FLIGHT) ctx->ws_threads = n > (2u << 20) ? (uint32_t)kWsThreads : (uint32_t)kWsThreadsSmall;
-    if (ctx->wide_sort) {
-        // 4096-key chunks up to 2 M splats, 8192 beyond; groups of 16 chunk rows while
-        // there are at most 512 rows, else of 32 (a downsweep sums <= nchunks / G + G - 1 rows)
-        ctx->ws_items = n > (2u << 20) ? 16u : 8u;
-        // (the tables are sized for 8 keys per thread: passes 1 and 2 drop to that when few splats survive the cull, below)
-        const uint32_t nch = std::max(1u, div_up(n, (uint64_t)ctx->ws_threads * 8u));
-        ctx->ws_gshift = nch <= 512u ? 4u : 5u;
-        if ((rc = buf_alloc(ctx, ctx->wsHist, (size_t)nch * kWsMaxBins * 4))) return rc;
-        const size_t gwords = (size_t)((nch >> ctx->ws_gshift) + 2) * kWsMaxBins;
-        for (auto& g : ctx->wsGsum) {
-            if ((rc = buf_alloc(ctx, g, gwords * 4))) return rc;
-            g.frame_table = true;
-            HIP_TRY(ctx, hipMemsetAsync(g.p, 0, g.bytes, ctx->stream));
-        }
-        ctx->ws_gsum_words = (uint32_t)gwords;
-        if ((rc = buf_alloc(ctx, ctx->vmask, (size_t)div_up(alloc_n, 64) * 8 + 64))) return rc;
-    }
+    ctx->hist.stride = std::max(1u, div_up(n, kSortChunk));
+    if ((rc = buf_alloc(ctx, ctx->hist.buf, (size_t)256 * ctx->hist.stride * 4))) return rc;
+    // the sort's pair: every pass clears one table while it fills the other, so both are launched with the smaller row count
+    for (auto& g : ctx->gsumS)
+        if ((rc = alloc_group_table(ctx, g, ctx->hist.stride))) return rc;
+    ctx->gsumS[0].rows = ctx->gsumS[1].rows = std::min(ctx->gsumS[0].rows, ctx->gsumS[1].rows);
+    if ((rc = plan_wide_sort(ctx, n))) return rc;
     if ((rc = buf_alloc(ctx, ctx->live_list, ((size_t)div_up(div_up(alloc_n, kBoxSplats), kBoxGroup) * kBoxGroup + 16) * 4))) return rc;
     if ((rc = buf_alloc(ctx, ctx->live_cnt, 256 * 4))) return rc;
     ctx->rank_cap = alloc_n;
@@ -129,14 +139,12 @@ static int prepare_cloud_buffers(msplat_ctx* ctx, uint64_t n, bool full_sh, cons
     if ((rc = buf_alloc(ctx, ctx->rect, alloc_n * 4))) return rc;
     if (ctx->depth_bits != 0 && (rc = buf_alloc(ctx, ctx->zq, alloc_n * 4))) return rc;
     // (column pass: 1024-rank chunks; 2048 measured r3 at 6 M: binning 183 -> 191 us at 1080p, 459 -> 453 us at 4096^2)
-    if ((rc = buf_alloc(ctx, ctx->heavy, (size_t)2 * (1 + kHeavyCap) * 4))) return rc;
-    ctx->heavy.frame_table = true;
-    HIP_TRY(ctx, hipMemsetAsync(ctx->heavy.p, 0, ctx->heavy.bytes, ctx->stream));
+    if ((rc = alloc_frame_table(ctx, ctx->heavy, (size_t)2 * (1 + kHeavyCap) * 4))) return rc;
     if ((rc = buf_alloc(ctx, ctx->heavy_flag, (size_t)div_up(alloc_n, kBinChunk) + 64))) return rc;
     HIP_TRY(ctx, hipMemsetAsync(ctx->heavy_flag.p, 0, ctx->heavy_flag.bytes, ctx->stream));
-    ctx->hist1_stride = std::max(1u, div_up(n, kBinChunk));
-    if ((rc = buf_alloc(ctx, ctx->hist1, (size_t)256 * ctx->hist1_stride * 4))) return rc;
-    if ((rc = alloc_group_table(ctx, ctx->gsumB1, ctx->gsumB1_rows, ctx->hist1_stride, ctx->gsupB1))) return rc;
+    ctx->hist1.stride = std::max(1u, div_up(n, kBinChunk));
+    if ((rc = buf_alloc(ctx, ctx->hist1.buf, (size_t)256 * ctx->hist1.stride * 4))) return rc;
+    if ((rc = alloc_group_table(ctx, ctx->gsumB1, ctx->hist1.stride))) return rc;
     uint64_t cap = ctx->cfg.pair_capacity ? ctx->cfg.pair_capacity
                                           : std::max<uint64_t>(1ull << 22, std::min<uint64_t>(32 * n, 1ull << 30));
     return ensure_pair_capacity(ctx, cap);
@@ -166,7 +174,7 @@ static int spatial_reorder(msplat_ctx* ctx)
         return MSPLAT_OK;
     }
     double* acc = (double*)ctx->totals1.p;          // 1 KB, idle outside a render
-    uint32_t *kA = (uint32_t*)ctx->keyA.p, *kB = (uint32_t*)ctx->keyB.p, *vA = (uint32_t*)ctx->valA.p, *vB = (uint32_t*)ctx->valB.p;
+    uint32_t *kA = words(ctx->keyA), *vA = words(ctx->valA);
     const float4* pos = (const float4*)st.pos4.p;
     const uint32_t mrows = std::min(div_up(N, kThreads), 1024u);
     void* mpart = nullptr;
@@ -180,26 +188,16 @@ static int spatial_reorder(msplat_ctx* ctx)
     hipLaunchKernelGGL(cloud_moments_finish, dim3(1), dim3(kThreads), 0, s, (const double*)mpart, mrows, acc);
     hipLaunchKernelGGL(morton_kernel, dim3(div_up(N, kThreads)), dim3(kThreads), 0, s, pos, N, (const double*)acc, kA, vA);
     const bool large = n64 > (2u << 20);
-    const uint32_t chunk = (uint32_t)kThreads * (large ? kSortItemsLarge : kSortItems);
-    const int grid = grid_for(div_up(N, chunk), ctx->grid_cap);
+    const int grid = grid_for(div_up(N, (uint32_t)kThreads * (large ? kSortItemsLarge : kSortItems)), ctx->grid_cap);
     FrameParams fp0;
     std::memset(&fp0, 0, sizeof(fp0));
-    uint32_t* hist = (uint32_t*)ctx->hist.p;
-    uint32_t* totals = (uint32_t*)ctx->totals.p;
+    RadixPass a;            // a static n, the scanned form, no group table touched
+    a.n_static = a.n_cap = N;  a.fp = &fp0;
+    a.hist = &ctx->hist;  a.totals = words(ctx->totals);
     for (int pass = 0; pass < 4; ++pass) {          // A -> B -> A -> B -> A
-        uint32_t *kin = (pass & 1) ? kB : kA, *vin = (pass & 1) ? vB : vA, *kout = (pass & 1) ? kA : kB, *vout = (pass & 1) ? vA : vB;
-        with_sort_items(large, [&](auto IT) {
-            hipLaunchKernelGGL((radix_upsweep<MODE_KEYS, IT.value>), dim3(grid), dim3(kThreads), 0, s, (const uint32_t*)kin,
-                               (const float4*)nullptr, (const uint32_t*)nullptr, N, N, pass * 8, hist, ctx->hist_stride, (uint32_t*)nullptr,
-                               (uint32_t*)nullptr, 0u, fp0);
-            launch_scan(s, !large, hist, ctx->hist_stride, nullptr, N, N, chunk, totals);
-            with_flag(ctx->atomic_rank, [&](auto AR) {
-                hipLaunchKernelGGL((radix_downsweep<MODE_KEYS, true, AR.value, IT.value>), dim3(grid), dim3(kThreads), 0, s,
-                                   (const uint32_t*)kin, (const uint32_t*)vin, (const float4*)nullptr, (const uint32_t*)nullptr, N, N, pass * 8,
-                                   (const uint32_t*)hist, ctx->hist_stride, (const uint32_t*)totals, kout, vout, (uint32_t*)nullptr,
-                                   (const uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr, fp0);
-            });
-        });
+        a.buffers(ctx, pass & 1);
+        a.shift = pass * 8;
+        issue_radix_pass(ctx, int_t<MODE_KEYS>{}, flag_t<true>{}, large, grid, a);
     }
     hipLaunchKernelGGL(gather_cloud_kernel, dim3(2048), dim3(kThreads), 0, s, (const uint32_t*)vA, N, F4, pos,
                        (const float4*)st.recs.p, (float4*)npos, (float4*)nrec);
@@ -265,7 +263,6 @@ int msplat_upload_cloud(msplat_ctx* ctx, const void* aos, uint64_t n, uint32_t s
                                       off->cov3_col0, off->cov3_col1, off->cov3_col2};
     const uint32_t src_off_full[9] = {off->r_sh1, off->r_sh2, off->r_sh3, off->g_sh1, off->g_sh2, off->g_sh3,
                                       off->b_sh1, off->b_sh2, off->b_sh3};
-    const uint32_t max_need = ctx->full_sh ? 16 : 12;
     for (int k = 0; k < 7; ++k)
         if (src_off_base[k] + (k < 4 ? 16u : 12u) > stride_bytes)
             return fail(ctx, MSPLAT_ERR_INVALID_ARG, "attribute offset %u beyond stride %u", src_off_base[k], stride_bytes);
@@ -273,7 +270,6 @@ int msplat_upload_cloud(msplat_ctx* ctx, const void* aos, uint64_t n, uint32_t s
         for (int k = 0; k < 9; ++k)
             if (src_off_full[k] + 16u > stride_bytes)
                 return fail(ctx, MSPLAT_ERR_INVALID_ARG, "attribute offset %u beyond stride %u", src_off_full[k], stride_bytes);
-    (void)max_need;
     const uint8_t* src = static_cast<const uint8_t*>(aos);
     for (uint64_t base = 0; base < n; base += chunk) {
         const size_t cnt = (size_t)std::min<uint64_t>(chunk, n - base);
