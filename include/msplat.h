@@ -70,9 +70,7 @@ typedef struct msplat_config {
 /* Byte offsets of the attributes inside one AoS record: the BinaryAttribute offsets SplatRenderer::BuildVertexArrayObject binds
  * (splatrenderer.cpp:345-391; gaussiancloud.cpp:633-657).  r_sh1 .. b_sh3 are ignored unless full_sh. */
 typedef struct msplat_attr_offsets {
-    uint32_t pos_with_alpha, r_sh0, g_sh0, b_sh0;
-    uint32_t cov3_col0, cov3_col1, cov3_col2;
-    uint32_t r_sh1, r_sh2, r_sh3, g_sh1, g_sh2, g_sh3, b_sh1, b_sh2, b_sh3;
+    uint32_t pos_with_alpha, r_sh0, g_sh0, b_sh0, cov3_col0, cov3_col1, cov3_col2, r_sh1, r_sh2, r_sh3, g_sh1, g_sh2, g_sh3, b_sh1, b_sh2, b_sh3;
 } msplat_attr_offsets;
 typedef struct msplat_stats {
     uint64_t num_splats;       /* N */
@@ -104,15 +102,19 @@ int msplat_tile_size(void);                             /* edge of the square sc
 int msplat_upload_cloud(msplat_ctx* ctx, const void* aos, uint64_t n, uint32_t stride_bytes, const msplat_attr_offsets* off, int full_sh);
 /* GPU ingest (SURVEY.md 8f-1): GaussianCloud::ImportPly's per-vertex math (gaussiancloud.cpp:254-361) as a HIP kernel over the raw PLY vertex block.
  * Byte offsets of the float properties in one vertex; -1 = absent (reads as 0, like BinaryAttribute::Read); without all of f_rest, or full_sh == 0: SH degree 0 (:188-205). */
-typedef struct msplat_ply_layout {
-    uint32_t vertex_size;
-    int32_t x, y, z, f_dc[3];
-    int32_t f_rest[45];
-    int32_t opacity, scale[3], rot[4];
-} msplat_ply_layout;
+typedef struct msplat_ply_layout { uint32_t vertex_size; int32_t x, y, z, f_dc[3], f_rest[45], opacity, scale[3], rot[4]; } msplat_ply_layout;
 int msplat_upload_ply_vertices(msplat_ctx* ctx, const void* vertices, uint64_t n, const msplat_ply_layout* layout, int full_sh);
 /* Ply::Parse (ply.cpp:72-87) on the host + the ingest kernel: GaussianCloud::ImportPly + SplatRenderer::Init in one call */
 int msplat_upload_ply(msplat_ctx* ctx, const char* path, int import_full_sh);
+/* ---- uploads from DEVICE memory (INTEGRATION.md 18): a trainer's tensors, a streamed or decompressed cloud.  `off` / `layout` are host structs; every d_* pointer is memory of the context's device.  The source is read on the context's stream and
+ * the call returns after that stream has drained, as the host uploads do: on return the caller may overwrite or free it.  Whatever produced the source must have completed before the call, or the context's stream must have been made to wait for it (msplat_wait_event).
+ * Refused before anything is launched or copied -- MSPLAT_ERR_INVALID_ARG: a NULL pointer with n > 0, d_aos / d_vertices off a 16-byte or an attribute array off a 4-byte boundary, a pointer hipPointerGetAttributes does not report as device memory of the context's
+ * device (host memory, another device's), stride / offset / layout errors as the host calls; MSPLAT_ERR_UNSUPPORTED: stride_bytes > 1024, n > 2^24.  The f_rest failures (SH_FP16: |c| >= 65520, SH_Q8: non-finite) are the host routes'; after any failure the context holds no cloud.
+ * An unattached context that uploads the same or a smaller n again, same full_sh and storage, allocates nothing.  Out of scope: the device group (a replicated cloud needs peer copies), point clouds, updates of a sub-range, skipping the stream drain. */
+int msplat_upload_cloud_device(msplat_ctx* ctx, const void* d_aos, uint64_t n, uint32_t stride_bytes, const msplat_attr_offsets* off, int full_sh);   /* = msplat_upload_cloud of the same bytes: records, footprint bounds, storage kind and order, cull boxes, bit for bit */
+int msplat_upload_ply_vertices_device(msplat_ctx* ctx, const void* d_vertices, uint64_t n, const msplat_ply_layout* layout, int full_sh);   /* = msplat_upload_ply_vertices, bit for bit: the same kernel launch without the staging copy */
+/* = msplat_cloud_from_attributes + msplat_upload_gaussian_cloud on its arrays (f_rest n x 45 in PLY order f_rest_0..44, rot as w x y z; d_f_rest == NULL or full_sh == 0: SH degree 0); bit for bit msplat_upload_ply_vertices of the same values packed into one vertex block */
+int msplat_upload_attributes_device(msplat_ctx* ctx, uint64_t n, const float* d_xyz, const float* d_f_dc, const float* d_f_rest, const float* d_opacity, const float* d_log_scale, const float* d_rot, int full_sh);
 /* the device cloud in the reference's interleaved layout (100 B / 244 B records), upload numbering */
 int msplat_download_cloud(msplat_ctx* ctx, void* aos_out, uint64_t cap_bytes);
 /* f_rest storage of the context's NEXT splat upload, any route (INTEGRATION.md 12).  SH_FP16: IEEE fp16, nearest even, 160 / 96-B
@@ -175,8 +177,7 @@ int msplat_get_fb_format(const msplat_ctx* ctx);                    /* MSPLAT_FB
 int msplat_set_band(msplat_ctx* ctx, int32_t row_mod, int32_t row_rem);
 int msplat_set_band_layout(msplat_ctx* ctx, int32_t first_row, int32_t row_count, int32_t block, int32_t stride);
 /* the standard layouts (MSPLAT_BANDS_*) for rank `rank` of `world` over rows_full bin rows; host arithmetic only */
-int msplat_band_plan(int32_t kind, int32_t rows_full, int32_t world, int32_t rank, int32_t block_rows, int32_t* first_row,
-                     int32_t* row_count, int32_t* block, int32_t* stride);
+int msplat_band_plan(int32_t kind, int32_t rows_full, int32_t world, int32_t rank, int32_t block_rows, int32_t* first_row, int32_t* row_count, int32_t* block, int32_t* stride);
 /* MSPLAT_BANDS_ROOT_WEIGHTED: contiguous bands, rank 0 (the gather's root: sends nothing) weighted `block_rows` PERCENT of another rank;
  * msplat_band_root_weight picks the percentage from a linear cost model (INTEGRATION.md 5); _plan_weighted: rows ~ weights[], bounds[world + 1] */
 int msplat_band_plan_weighted(int32_t rows_full, int32_t world, const float* weights, int32_t* bounds_out);
@@ -249,8 +250,7 @@ msplat_cloud* msplat_cloud_create(int import_full_sh);          /* GaussianCloud
 void msplat_cloud_destroy(msplat_cloud* c);
 int msplat_cloud_import_ply(msplat_cloud* c, const char* path); /* GaussianCloud::ImportPly (gaussiancloud.cpp:138-365) */
 /* ImportPly's per-vertex math (gaussiancloud.cpp:254-361) on raw attribute arrays (synthetic scenes); f_rest may be NULL */
-int msplat_cloud_from_attributes(msplat_cloud* c, uint64_t n, const float* xyz, const float* f_dc, const float* f_rest,
-                                 const float* opacity, const float* log_scale, const float* rot);
+int msplat_cloud_from_attributes(msplat_cloud* c, uint64_t n, const float* xyz, const float* f_dc, const float* f_rest, const float* opacity, const float* log_scale, const float* rot);
 int msplat_cloud_export_ply(msplat_cloud* c, const char* path); /* ExportPly / InitDebugCloud / PruneSplats */
 int msplat_cloud_init_debug(msplat_cloud* c);                   /*   (gaussiancloud.cpp:367-626) */
 int msplat_cloud_prune(msplat_cloud* c, const float origin[3], uint32_t keep);
@@ -283,8 +283,7 @@ void msplat_points_init_debug(msplat_points* p);
 uint64_t msplat_points_num(const msplat_points* p);
 uint32_t msplat_points_stride(const msplat_points* p);          /* 32: position.xyzw, color.rgba */
 const void* msplat_points_data(const msplat_points* p);
-int msplat_upload_points(msplat_ctx* ctx, const void* aos, uint64_t n, uint32_t stride_bytes, uint32_t position_offset,
-                         uint32_t color_offset);                /* PointRenderer::Init's buffers (pointrenderer.cpp:95-110) */
+int msplat_upload_points(msplat_ctx* ctx, const void* aos, uint64_t n, uint32_t stride_bytes, uint32_t position_offset, uint32_t color_offset);   /* PointRenderer::Init's buffers (pointrenderer.cpp:95-110) */
 int msplat_upload_point_cloud(msplat_ctx* ctx, const msplat_points* p);
 /* the sprite (texture/sphere.png, pointrenderer.cpp:54-64): RGBA8, top row first (Image::Load's flip + premultiplication, mip chain); NULL = built-in sphere */
 int msplat_set_point_sprite(msplat_ctx* ctx, const uint8_t* rgba8, uint32_t width, uint32_t height);

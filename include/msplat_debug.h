@@ -79,6 +79,11 @@ int msplat_debug_cu_partition(msplat_ctx* ctx, uint32_t* mask8);
  * Returns the number of non-finite f_rest values (an upload fails when it is not 0), or MSPLAT_ERR_INVALID_ARG for a NULL ---- */
 int msplat_debug_sh_q8_round(const float rec_in[61], float rec_out[61], float steps_out[3], int8_t codes_out[45]);
 
+/* ---- the upload kernel alone: milliseconds between two stream events around the context's latest ingest_kernel / repack_kernel /
+ * ingest_attributes_kernel launch (msplat_upload_ply_vertices[_device], msplat_upload_cloud_device, msplat_upload_attributes_device)
+ * on a context created with enable_timing > 0; *ms = -1 when there is none.  tools/device_upload_timing.py ---- */
+int msplat_debug_upload_kernel_ms(msplat_ctx* ctx, float* ms);
+
 #ifdef __cplusplus
 }
 #endif

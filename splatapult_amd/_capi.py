@@ -91,6 +91,10 @@ SYMBOLS = [
     ("msplat_upload_cloud", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(AttrOffsets), C.c_int]),
     ("msplat_upload_ply_vertices", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(PlyLayout), C.c_int]),
     ("msplat_upload_ply", C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
+    ("msplat_upload_cloud_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(AttrOffsets), C.c_int]),
+    ("msplat_upload_ply_vertices_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(PlyLayout), C.c_int]),
+    ("msplat_upload_attributes_device", C.c_int, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 6 + [C.c_int]),
+    ("msplat_debug_upload_kernel_ms", C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     ("msplat_download_cloud", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
     ("msplat_set_band", C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     ("msplat_set_band_cull", C.c_int, [C.c_void_p, C.c_int]),

@@ -1,5 +1,6 @@
-// msplat_cloud.hip.h -- upload-time kernels: GPU PLY ingest (GaussianCloud::ImportPly's per-vertex math) and the spatial storage order
-// (moments, Morton codes, gather, cull boxes)
+// msplat_cloud.hip.h -- upload-time kernels: GPU PLY ingest (GaussianCloud::ImportPly's per-vertex math) from a vertex block or from
+// attribute arrays, the repack of interleaved records that are on the device, and the spatial storage order (moments, Morton codes,
+// gather, cull boxes)
 // (one of the parts of msplat_kernels.hip.h)
 #pragma once
 
@@ -27,52 +28,55 @@ struct PlyLayout {             // mirrors msplat_ply_layout (include/msplat.h)
     int32_t rot[4];
 };
 
+// One record out of the wave's hands: the FP32 record floats f[] (padded, reference float order) -> pos4[i] and recs[i].
 // STORAGE = kStorageShFp16 / kStorageShQ8: the records are written compact (msplat_common.hip.h: sh16_pack / sh8_pack); *n_over
 // counts the f_rest values beyond the fp16 range / the non-finite ones (the upload then fails)
-template <bool FULL_SH, int STORAGE = kStorageFp32>
-__global__ __launch_bounds__(64) void ingest_kernel(const char* __restrict__ raw, uint64_t n, PlyLayout L,
-                                                    float4* __restrict__ pos4, float4* __restrict__ recs,
-                                                    uint32_t* __restrict__ n_over)
+template <bool FULL_SH, int STORAGE>
+__device__ __forceinline__ void store_record(const float* f, uint64_t i, float4* __restrict__ pos4, float4* __restrict__ recs,
+                                             uint32_t* __restrict__ n_over)
 {
-    extern __shared__ __attribute__((aligned(16))) char s_raw[];
     constexpr int F4 = FULL_SH ? 16 : 8;
-    const int lane = threadIdx.x;
-    const uint32_t vs = L.vertex_size;
-    const uint64_t v0 = (uint64_t)blockIdx.x * 64u;
-    const uint64_t byte0 = v0 * vs;
-    const uint64_t total = n * (uint64_t)vs;
-    const uint32_t span = (uint32_t)min((uint64_t)64u * vs, total - byte0);      // multiple of 4
-    for (uint32_t off = lane * 16u; off < span; off += 64u * 16u) {
-        if (off + 16u <= span) {
-            *reinterpret_cast<float4*>(s_raw + off) = *reinterpret_cast<const float4*>(raw + byte0 + off);
-        } else {
-            for (uint32_t o = off; o < span; o += 4u)
-                *reinterpret_cast<float*>(s_raw + o) = *reinterpret_cast<const float*>(raw + byte0 + o);
-        }
+    pos4[i] = make_float4(f[0], f[1], f[2], footprint_bound(&f[16], f[3]));      // .w: world-space footprint bound for the band cull
+    if constexpr (STORAGE != kStorageFp32) {
+        constexpr int CF4 = cloud_f4(STORAGE, FULL_SH);
+        uint32_t w[CF4 * 4];
+        uint32_t over;
+        if constexpr (STORAGE == kStorageShQ8) over = sh8_pack<FULL_SH>(f, w); else over = sh16_pack<FULL_SH>(f, w);
+        if (over) atomicAdd(n_over, over);
+#pragma unroll
+        for (int k = 0; k < CF4; ++k)
+            recs[i * CF4 + k] = make_float4(__uint_as_float(w[4 * k]), __uint_as_float(w[4 * k + 1]), __uint_as_float(w[4 * k + 2]),
+                                            __uint_as_float(w[4 * k + 3]));
+    } else {
+#pragma unroll
+        for (int k = 0; k < F4; ++k) recs[i * F4 + k] = make_float4(f[4 * k], f[4 * k + 1], f[4 * k + 2], f[4 * k + 3]);
     }
-    __syncthreads();
-    const uint64_t i = v0 + lane;
-    if (i >= n) return;
-    const char* v = s_raw + (size_t)lane * vs;
-    auto rd = [&](int32_t off) -> float { return off >= 0 ? *reinterpret_cast<const float*>(v + off) : 0.0f; };
+}
 
+// ImportPly's per-vertex math on vertex i, behind both ingest kernels.  `rd` hands out the vertex's properties by name:
+// rd.pos(c), rd.f_dc(c), rd.f_rest(k) (PLY order f_rest_0..44; asked for with FULL_SH only), rd.opacity(), rd.scale(c), rd.rot(c) (w x y z)
+template <bool FULL_SH, int STORAGE, class Reader>
+__device__ __forceinline__ void ingest_vertex(const Reader& rd, uint64_t i, float4* __restrict__ pos4, float4* __restrict__ recs,
+                                              uint32_t* __restrict__ n_over)
+{
+    constexpr int F4 = FULL_SH ? 16 : 8;
     float f[F4 * 4];
 #pragma unroll
     for (int k = 0; k < F4 * 4; ++k) f[k] = 0.0f;
-    f[0] = rd(L.x); f[1] = rd(L.y); f[2] = rd(L.z);
-    f[3] = 1.0f / (1.0f + expf(-rd(L.opacity)));
+    f[0] = rd.pos(0); f[1] = rd.pos(1); f[2] = rd.pos(2);
+    f[3] = 1.0f / (1.0f + expf(-rd.opacity()));
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-        f[4 + 4 * c] = rd(L.f_dc[c]);
+        f[4 + 4 * c] = rd.f_dc(c);
         if constexpr (FULL_SH) {
 #pragma unroll
-            for (int k = 1; k < 4; ++k) f[4 + 4 * c + k] = rd(L.f_rest[c * 15 + k - 1]);
+            for (int k = 1; k < 4; ++k) f[4 + 4 * c + k] = rd.f_rest(c * 15 + k - 1);
 #pragma unroll
-            for (int k = 4; k < 16; ++k) f[25 + 12 * c + (k - 4)] = rd(L.f_rest[c * 15 + k - 1]);
+            for (int k = 4; k < 16; ++k) f[25 + 12 * c + (k - 4)] = rd.f_rest(c * 15 + k - 1);
         }
     }
-    const float s0 = expf(rd(L.scale[0])), s1 = expf(rd(L.scale[1])), s2 = expf(rd(L.scale[2]));
-    float w = rd(L.rot[0]), x = rd(L.rot[1]), y = rd(L.rot[2]), z = rd(L.rot[3]);
+    const float s0 = expf(rd.scale(0)), s1 = expf(rd.scale(1)), s2 = expf(rd.scale(2));
+    float w = rd.rot(0), x = rd.rot(1), y = rd.rot(2), z = rd.rot(3);
     const float len = sqrtf((w * w + x * x) + (y * y + z * z));
     if (len <= 0.0f) { w = 1.0f; x = 0.0f; y = 0.0f; z = 0.0f; }
     else { const float inv = 1.0f / len; w *= inv; x *= inv; y *= inv; z *= inv; }
@@ -98,21 +102,154 @@ __global__ __launch_bounds__(64) void ingest_kernel(const char* __restrict__ raw
             s = s + B[2 * 3 + r] * R[2 * 3 + c];
             f[16 + c * 3 + r] = s;
         }
-    pos4[i] = make_float4(f[0], f[1], f[2], footprint_bound(&f[16], f[3]));      // .w: world-space footprint bound for the band cull
-    if constexpr (STORAGE != kStorageFp32) {
-        constexpr int CF4 = cloud_f4(STORAGE, FULL_SH);
-        uint32_t w[CF4 * 4];
-        uint32_t over;
-        if constexpr (STORAGE == kStorageShQ8) over = sh8_pack<FULL_SH>(f, w); else over = sh16_pack<FULL_SH>(f, w);
-        if (over) atomicAdd(n_over, over);
+    store_record<FULL_SH, STORAGE>(f, i, pos4, recs, n_over);
+}
+
+// the wave's span of `span` bytes (a multiple of 4; src 16-byte aligned) into LDS with coalesced 16-byte loads; the sub-16-byte
+// tail of the last block goes word by word
+__device__ __forceinline__ void stage_span(char* __restrict__ dst, const char* __restrict__ src, uint32_t span, int lane)
+{
+    for (uint32_t off = lane * 16u; off < span; off += 64u * 16u) {
+        if (off + 16u <= span) {
+            *reinterpret_cast<float4*>(dst + off) = *reinterpret_cast<const float4*>(src + off);
+        } else {
+            for (uint32_t o = off; o < span; o += 4u)
+                *reinterpret_cast<float*>(dst + o) = *reinterpret_cast<const float*>(src + o);
+        }
+    }
+}
+
+struct PlyVertexReader {       // one vertex of the block in LDS; an absent property (offset -1) reads as 0, like BinaryAttribute::Read
+    const char* v;
+    const PlyLayout& L;
+    __device__ __forceinline__ float rd(int32_t off) const { return off >= 0 ? *reinterpret_cast<const float*>(v + off) : 0.0f; }
+    __device__ __forceinline__ float pos(int c) const { return rd(c == 0 ? L.x : (c == 1 ? L.y : L.z)); }
+    __device__ __forceinline__ float f_dc(int c) const { return rd(L.f_dc[c]); }
+    __device__ __forceinline__ float f_rest(int k) const { return rd(L.f_rest[k]); }
+    __device__ __forceinline__ float opacity() const { return rd(L.opacity); }
+    __device__ __forceinline__ float scale(int c) const { return rd(L.scale[c]); }
+    __device__ __forceinline__ float rot(int c) const { return rd(L.rot[c]); }
+};
+
+template <bool FULL_SH, int STORAGE = kStorageFp32>
+__global__ __launch_bounds__(64) void ingest_kernel(const char* __restrict__ raw, uint64_t n, PlyLayout L,
+                                                    float4* __restrict__ pos4, float4* __restrict__ recs,
+                                                    uint32_t* __restrict__ n_over)
+{
+    extern __shared__ __attribute__((aligned(16))) char s_raw[];
+    const int lane = threadIdx.x;
+    const uint32_t vs = L.vertex_size;
+    const uint64_t v0 = (uint64_t)blockIdx.x * 64u;
+    const uint64_t byte0 = v0 * vs;
+    const uint64_t total = n * (uint64_t)vs;
+    const uint32_t span = (uint32_t)min((uint64_t)64u * vs, total - byte0);      // multiple of 4
+    stage_span(s_raw, raw + byte0, span, lane);
+    __syncthreads();
+    const uint64_t i = v0 + lane;
+    if (i >= n) return;
+    ingest_vertex<FULL_SH, STORAGE>(PlyVertexReader{s_raw + (size_t)lane * vs, L}, i, pos4, recs, n_over);
+}
+
+// The same record from six attribute arrays in device memory (msplat_upload_attributes_device; the arrays of
+// msplat_cloud_from_attributes).  Only 4-byte alignment is assumed.  One wave per 64 splats: xyz, f_dc, opacity, scale and rot are
+// 14 floats a splat, read by the lane that owns it (a wave's loads cover one contiguous run per array); the 64 x 45 floats of f_rest
+// are one contiguous 11.25-KB run, staged through LDS with one dword per lane and step (256 B per load instruction), and read back
+// at a stride of 45 words -- odd, so the 64 lanes hit 64 different banks.
+struct AttrArrays {
+    const float* xyz; const float* f_dc; const float* f_rest; const float* opacity; const float* log_scale; const float* rot;
+};
+
+struct AttrReader {
+    const AttrArrays& A;
+    uint64_t i;
+    const float* rest;         // the splat's 45 floats in LDS (FULL_SH only)
+    __device__ __forceinline__ float pos(int c) const { return A.xyz[i * 3 + c]; }
+    __device__ __forceinline__ float f_dc(int c) const { return A.f_dc[i * 3 + c]; }
+    __device__ __forceinline__ float f_rest(int k) const { return rest[k]; }
+    __device__ __forceinline__ float opacity() const { return A.opacity[i]; }
+    __device__ __forceinline__ float scale(int c) const { return A.log_scale[i * 3 + c]; }
+    __device__ __forceinline__ float rot(int c) const { return A.rot[i * 4 + c]; }
+};
+
+template <bool FULL_SH, int STORAGE = kStorageFp32>
+__global__ __launch_bounds__(64) void ingest_attributes_kernel(AttrArrays A, uint64_t n, float4* __restrict__ pos4,
+                                                               float4* __restrict__ recs, uint32_t* __restrict__ n_over)
+{
+    __shared__ float s_rest[FULL_SH ? 64 * 45 : 1];
+    const int lane = threadIdx.x;
+    const uint64_t v0 = (uint64_t)blockIdx.x * 64u;
+    if constexpr (FULL_SH) {
+        const uint32_t words = (uint32_t)min((uint64_t)64u, n - v0) * 45u;
+        const float* src = A.f_rest + v0 * 45u;
+        for (uint32_t o = lane; o < words; o += 64u) s_rest[o] = src[o];
+        __syncthreads();
+    }
+    const uint64_t i = v0 + lane;
+    if (i >= n) return;
+    ingest_vertex<FULL_SH, STORAGE>(AttrReader{A, i, s_rest + (FULL_SH ? lane * 45 : 0)}, i, pos4, recs, n_over);
+}
+
+// Interleaved records in device memory (msplat_upload_cloud_device): n records of `stride` bytes (a multiple of 4, base 16-byte
+// aligned) with the attributes at the byte offsets of msplat_attr_offsets -> pos4 + the padded (or compact) records, the host
+// loop of msplat_upload_cloud field by field.  The ingest kernel's shape: one wave per 64 records, their span copied into dynamic
+// LDS (64 * stride bytes), each lane then picks its attributes out of its own record.
+struct AttrOffsets {           // mirrors msplat_attr_offsets (include/msplat.h)
+    uint32_t pos_with_alpha, r_sh0, g_sh0, b_sh0;
+    uint32_t cov3_col0, cov3_col1, cov3_col2;
+    uint32_t sh_full[9];       // r_sh1 r_sh2 r_sh3 g_sh1 .. b_sh3
+};
+
+template <bool FULL_SH, int STORAGE = kStorageFp32>
+__global__ __launch_bounds__(64) void repack_kernel(const char* __restrict__ aos, uint64_t n, uint32_t stride, AttrOffsets O,
+                                                    float4* __restrict__ pos4, float4* __restrict__ recs,
+                                                    uint32_t* __restrict__ n_over)
+{
+    extern __shared__ __attribute__((aligned(16))) char s_raw[];
+    constexpr int F4 = FULL_SH ? 16 : 8;
+    const int lane = threadIdx.x;
+    const uint64_t v0 = (uint64_t)blockIdx.x * 64u;
+    const uint64_t byte0 = v0 * stride;
+    const uint32_t span = (uint32_t)min((uint64_t)64u * stride, n * (uint64_t)stride - byte0);      // multiple of 4
+    stage_span(s_raw, aos + byte0, span, lane);
+    __syncthreads();
+    const uint64_t i = v0 + lane;
+    if (i >= n) return;
+    const uint32_t* r = reinterpret_cast<const uint32_t*>(s_raw + (size_t)lane * stride);
+    // cnt floats from byte offset off of the record, bits untouched.  The host's memcpy takes any offset: one that is no multiple
+    // of 4 (uniform over the wave) is put together from neighbouring words -- off + 4 cnt < stride then, so word cnt is the record's
+    auto put = [&](float* d, uint32_t off, int cnt) {
+        const uint32_t* w = r + (off >> 2);
+        const uint32_t sh = off & 3u;
+        if (sh == 0u) {
 #pragma unroll
-        for (int k = 0; k < CF4; ++k)
-            recs[i * CF4 + k] = make_float4(__uint_as_float(w[4 * k]), __uint_as_float(w[4 * k + 1]), __uint_as_float(w[4 * k + 2]),
-                                            __uint_as_float(w[4 * k + 3]));
+            for (int k = 0; k < cnt; ++k) d[k] = __uint_as_float(w[k]);
+        } else {
+            uint32_t lo = w[0];
+#pragma unroll
+            for (int k = 0; k < cnt; ++k) {
+                const uint32_t hi = w[k + 1];
+                d[k] = __uint_as_float(__builtin_amdgcn_alignbyte(hi, lo, sh));
+                lo = hi;
+            }
+        }
+    };
+    float f[F4 * 4];
+    put(f + 0, O.pos_with_alpha, 4);
+    put(f + 4, O.r_sh0, 4);
+    put(f + 8, O.g_sh0, 4);
+    put(f + 12, O.b_sh0, 4);
+    put(f + 16, O.cov3_col0, 3);
+    put(f + 19, O.cov3_col1, 3);
+    put(f + 22, O.cov3_col2, 3);
+    if constexpr (FULL_SH) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) put(f + 25 + 4 * k, O.sh_full[k], 4);
+        f[61] = f[62] = f[63] = 0.0f;
     } else {
 #pragma unroll
-        for (int k = 0; k < F4; ++k) recs[i * F4 + k] = make_float4(f[4 * k], f[4 * k + 1], f[4 * k + 2], f[4 * k + 3]);
+        for (int k = 25; k < 32; ++k) f[k] = 0.0f;
     }
+    store_record<FULL_SH, STORAGE>(f, i, pos4, recs, n_over);
 }
 
 // ------------------------------------------------------------------------------------------

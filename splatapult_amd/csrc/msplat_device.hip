@@ -166,6 +166,8 @@ struct msplat_ctx {
     Buf pos4;       // view: float4[N]  (x, y, z, bound)  -- the reference's posVec (splatrenderer.cpp:106-111)
     Buf recs;       // view: padded AoS, 16 (full SH) or 8 float4 per splat, reference float offsets preserved
     hipEvent_t join_ev = nullptr;        // msplat_stream_wait
+    Buf upload_over;                     // uint32: the f_rest failures an upload kernel counted (the uploads from device memory)
+    float upload_kernel_ms = -1.0f;      // the latest upload kernel alone, with enable_timing (msplat_debug_upload_kernel_ms)
     // sort state
     Buf keyA, keyB, valA, valB;   // uint32[N]; final sorted result in keyA/valA
     HistTable hist;

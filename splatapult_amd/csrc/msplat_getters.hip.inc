@@ -367,3 +367,10 @@ int msplat_debug_cu_partition(msplat_ctx* ctx, uint32_t* mask8)
     }
     return ctx->cu_partition;
 }
+
+int msplat_debug_upload_kernel_ms(msplat_ctx* ctx, float* ms)
+{
+    if (!ctx || !ms) return fail(ctx, MSPLAT_ERR_INVALID_ARG, "msplat_debug_upload_kernel_ms: NULL argument");
+    *ms = ctx->upload_kernel_ms;      // (run_ingest has drained the stream)
+    return MSPLAT_OK;
+}

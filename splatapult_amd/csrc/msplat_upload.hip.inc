@@ -66,12 +66,20 @@ static int plan_wide_sort(msplat_ctx* ctx, uint64_t n)
     return rc;
 }
 
+// (host arithmetic: the uploads from device memory refuse the count before their first HIP call)
+static int check_splat_count(msplat_ctx* ctx, uint64_t n)
+{
+    if (n > (1ull << 24))
+        return fail(ctx, MSPLAT_ERR_UNSUPPORTED, "%llu splats > 2^24 (rank field is 24 bit)", (unsigned long long)n);
+    return MSPLAT_OK;
+}
+
 // (re)allocates every per-cloud device buffer for n splats; leaves the context without a cloud.
 // `share` != null: use that store's cloud instead of allocating one (msplat_attach_cloud).
 static int prepare_cloud_buffers(msplat_ctx* ctx, uint64_t n, bool full_sh, const std::shared_ptr<CloudStore>& share)
 {
-    if (n > (1ull << 24))
-        return fail(ctx, MSPLAT_ERR_UNSUPPORTED, "%llu splats > 2^24 (rank field is 24 bit)", (unsigned long long)n);
+    int rc_n = check_splat_count(ctx, n);
+    if (rc_n) return rc_n;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     ctx->has_cloud = false;
@@ -313,14 +321,51 @@ int msplat_upload_cloud(msplat_ctx* ctx, const void* aos, uint64_t n, uint32_t s
 }
 
 
-// GPU ingest: GaussianCloud::ImportPly's per-vertex math (gaussiancloud.cpp:254-361) as a HIP kernel over
-// the raw PLY vertex block -- SURVEY.md 8f-1.  `vertices` is host memory (n * layout->vertex_size bytes).
-int msplat_upload_ply_vertices(msplat_ctx* ctx, const void* vertices, uint64_t n, const msplat_ply_layout* layout,
-                               int full_sh)
+// ---- GPU ingest (SURVEY.md 8f-1): the upload kernels of msplat_cloud.hip.h, each run around one counter ------------------
+// The launch every ingest route shares.  `e`: what the route's own staging copy (if any) returned; launch(SH, ST) issues the
+// route's kernel for the store's <full SH, storage> pair with d_over as its counter.  Returns after the stream has drained; the
+// f_rest failures are msplat_upload_cloud's, in its words, under the route's name.  (enable_timing: the kernel alone between two
+// stream events, msplat_debug_upload_kernel_ms.)
+extern "C++" {      // (a template)
+template <class Launch>
+static int run_ingest(msplat_ctx* ctx, const char* who, uint32_t* d_over, hipError_t e, Launch&& launch)
 {
-    drain_async(ctx);
-    if (!ctx) return fail(nullptr, MSPLAT_ERR_INVALID_ARG, "ctx is NULL");
-    if ((!vertices && n) || !layout) return fail(ctx, MSPLAT_ERR_INVALID_ARG, "msplat_upload_ply_vertices: NULL argument");
+    uint32_t n_over = 0;
+    const bool sh8 = ctx->cloud_storage == kStorageShQ8, counted = sh8 || ctx->cloud_storage == kStorageShFp16;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    const bool timed = ctx->cfg.enable_timing > 0 && hipEventCreate(&ev[0]) == hipSuccess && hipEventCreate(&ev[1]) == hipSuccess;
+    ctx->upload_kernel_ms = -1.0f;
+    if (e == hipSuccess) e = hipMemsetAsync(d_over, 0, 4, ctx->stream);
+    if (e == hipSuccess) {
+        if (timed) (void)hipEventRecord(ev[0], ctx->stream);
+        with_flag(ctx->full_sh, [&](auto SH) {
+            with_int<kStorageShQ8, kStorageShFp16, kStorageFp32>(ctx->cloud_storage, [&](auto ST) {
+                if constexpr (ST.value == kStorageShQ8 && !SH.value) return;      // (no such store: prepare_cloud_buffers)
+                else launch(SH, ST);
+            });
+        });
+        e = hipGetLastError();
+        if (timed) (void)hipEventRecord(ev[1], ctx->stream);
+    }
+    if (e == hipSuccess && counted) e = hipMemcpyAsync(&n_over, d_over, 4, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e == hipSuccess && timed && hipEventElapsedTime(&ctx->upload_kernel_ms, ev[0], ev[1]) != hipSuccess) ctx->upload_kernel_ms = -1.0f;
+    for (hipEvent_t v : ev)
+        if (v) (void)hipEventDestroy(v);
+    if (e != hipSuccess) return fail(ctx, MSPLAT_ERR_HIP, "GPU ingest failed: %s", hipGetErrorString(e));
+    if (n_over && sh8)
+        return fail(ctx, MSPLAT_ERR_UNSUPPORTED, "%s: %u f_rest values are not finite: MSPLAT_STORAGE_SH_Q8 cannot quantise them", who,
+                    n_over);
+    if (n_over)
+        return fail(ctx, MSPLAT_ERR_UNSUPPORTED, "%s: %u f_rest values are beyond the fp16 range (|c| >= 65520) of "
+                    "MSPLAT_STORAGE_SH_FP16", who, n_over);
+    return MSPLAT_OK;
+}
+}  // extern "C++"
+
+// what both vertex routes check of a layout; full: every f_rest property is there and the caller wants it
+static int check_ply_layout(msplat_ctx* ctx, const msplat_ply_layout* layout, int full_sh, bool& full)
+{
     const uint32_t vs = layout->vertex_size;
     if (vs == 0 || vs % 4 != 0 || vs > 1024)
         return fail(ctx, MSPLAT_ERR_UNSUPPORTED, "vertex size %u must be a multiple of 4 in (0, 1024]", vs);
@@ -332,44 +377,190 @@ int msplat_upload_ply_vertices(msplat_ctx* ctx, const void* vertices, uint64_t n
             return fail(ctx, MSPLAT_ERR_INVALID_ARG, "property offset %d outside / misaligned in a %u-byte vertex", offs[k], vs);
     bool has_rest = true;
     for (int k = 0; k < 45; ++k) has_rest = has_rest && layout->f_rest[k] >= 0;
-    const bool full = full_sh != 0 && has_rest;      // f_rest is optional (gaussiancloud.cpp:188-205)
-    ctx->point_mode = false;
-    int rc = prepare_cloud_buffers(ctx, n, full, nullptr);
+    full = full_sh != 0 && has_rest;      // f_rest is optional (gaussiancloud.cpp:188-205)
+    return MSPLAT_OK;
+}
+
+// ingest_kernel over a vertex block that is on the device (d_raw: 16-byte aligned), into the prepared store
+static int ingest_vertices(msplat_ctx* ctx, const char* who, const void* d_raw, uint64_t n, const msplat_ply_layout* layout,
+                           uint32_t* d_over, hipError_t staged)
+{
+    const int grid = (int)div_up(n, 64);
+    const size_t lds = (size_t)64 * layout->vertex_size + 16;
+    PlyLayout kl;
+    static_assert(sizeof(PlyLayout) == sizeof(msplat_ply_layout), "layout mirror out of sync");
+    std::memcpy(&kl, layout, sizeof(kl));
+    return run_ingest(ctx, who, d_over, staged, [&](auto SH, auto ST) {
+        hipLaunchKernelGGL((ingest_kernel<SH.value, ST.value>), dim3(grid), dim3(64), lds, ctx->stream, (const char*)d_raw, n, kl,
+                           (float4*)ctx->pos4.p, (float4*)ctx->recs.p, d_over);
+    });
+}
+
+// GaussianCloud::ImportPly's per-vertex math (gaussiancloud.cpp:254-361) as a HIP kernel over the raw PLY vertex block.
+// `vertices` is host memory (n * layout->vertex_size bytes).
+int msplat_upload_ply_vertices(msplat_ctx* ctx, const void* vertices, uint64_t n, const msplat_ply_layout* layout,
+                               int full_sh)
+{
+    drain_async(ctx);
+    if (!ctx) return fail(nullptr, MSPLAT_ERR_INVALID_ARG, "ctx is NULL");
+    if ((!vertices && n) || !layout) return fail(ctx, MSPLAT_ERR_INVALID_ARG, "msplat_upload_ply_vertices: NULL argument");
+    bool full = false;
+    int rc = check_ply_layout(ctx, layout, full_sh, full);
     if (rc) return rc;
+    const uint32_t vs = layout->vertex_size;
+    ctx->point_mode = false;
+    if ((rc = prepare_cloud_buffers(ctx, n, full, nullptr))) return rc;
     if (n) {
         Buf raw;
         if ((rc = buf_alloc(ctx, raw, (size_t)n * vs + 16))) return rc;
         uint32_t* d_over = reinterpret_cast<uint32_t*>((char*)raw.p + (size_t)n * vs);      // (vs is a multiple of 4)
-        uint32_t n_over = 0;
-        const bool sh8 = ctx->cloud_storage == kStorageShQ8, counted = sh8 || ctx->cloud_storage == kStorageShFp16;
-        hipError_t e = hipMemcpyAsync(raw.p, vertices, (size_t)n * vs, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(d_over, 0, 4, ctx->stream);
-        if (e == hipSuccess) {
-            const int grid = (int)div_up(n, 64);
-            const size_t lds = (size_t)64 * vs + 16;
-            PlyLayout kl;
-            static_assert(sizeof(PlyLayout) == sizeof(msplat_ply_layout), "layout mirror out of sync");
-            std::memcpy(&kl, layout, sizeof(kl));
-            with_flag(full, [&](auto SH) {
-                with_int<kStorageShQ8, kStorageShFp16, kStorageFp32>(ctx->cloud_storage, [&](auto ST) {
-                    if constexpr (ST.value == kStorageShQ8 && !SH.value) return;      // (no such store: prepare_cloud_buffers)
-                    else
-                        hipLaunchKernelGGL((ingest_kernel<SH.value, ST.value>), dim3(grid), dim3(64), lds, ctx->stream, (const char*)raw.p, n,
-                                           kl, (float4*)ctx->pos4.p, (float4*)ctx->recs.p, d_over);
-                });
-            });
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess && counted) e = hipMemcpyAsync(&n_over, d_over, 4, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        rc = ingest_vertices(ctx, "msplat_upload_ply_vertices", raw.p, n, layout, d_over,
+                             hipMemcpyAsync(raw.p, vertices, (size_t)n * vs, hipMemcpyHostToDevice, ctx->stream));
         buf_free(ctx, raw);
-        if (e != hipSuccess) return fail(ctx, MSPLAT_ERR_HIP, "GPU ingest failed: %s", hipGetErrorString(e));
-        if (n_over && sh8)
-            return fail(ctx, MSPLAT_ERR_UNSUPPORTED, "msplat_upload_ply_vertices: %u f_rest values are not finite: "
-                        "MSPLAT_STORAGE_SH_Q8 cannot quantise them", n_over);
-        if (n_over)
-            return fail(ctx, MSPLAT_ERR_UNSUPPORTED, "msplat_upload_ply_vertices: %u f_rest values are beyond the fp16 range "
-                        "(|c| >= 65520) of MSPLAT_STORAGE_SH_FP16", n_over);
+        if (rc) return rc;
+    }
+    if ((rc = spatial_reorder(ctx))) return rc;
+    ctx->has_cloud = true;
+    return MSPLAT_OK;
+}
+
+// ---- uploads from device memory: msplat_upload_cloud / _ply_vertices / msplat_cloud_from_attributes with the source on the
+// context's device.  Every refusal comes before anything is launched or copied, and the pointer query is the first HIP call of
+// each route: a host address that reached a kernel would fault the GPU.
+// `p` .. p + bytes - 1 must be device memory of the context's device as hipPointerGetAttributes reports it (both ends are
+// asked), inside one allocation where the runtime can name its range.  A failed query leaves a sticky error: cleared.
+static int check_device_source(msplat_ctx* ctx, const char* who, const char* what, const void* p, uint64_t bytes)
+{
+    const char* ends[2] = {static_cast<const char*>(p), static_cast<const char*>(p) + (bytes - 1)};
+    for (const char* q : ends) {
+        hipPointerAttribute_t at;
+        std::memset(&at, 0, sizeof(at));
+        const hipError_t e = hipPointerGetAttributes(&at, q);
+        if (e != hipSuccess) (void)hipGetLastError();
+        if (e != hipSuccess || at.type != hipMemoryTypeDevice || at.device != ctx->device)
+            return fail(ctx, MSPLAT_ERR_INVALID_ARG, "%s: %s (%p, %llu bytes) is not device memory of device %d", who, what, p,
+                        (unsigned long long)bytes, ctx->device);
+    }
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, const_cast<void*>(p)) != hipSuccess) {
+        (void)hipGetLastError();
+        return MSPLAT_OK;
+    }
+    if (ends[1] >= static_cast<const char*>(base) + size)
+        return fail(ctx, MSPLAT_ERR_INVALID_ARG, "%s: %s (%p, %llu bytes) runs past the end of its allocation", who, what, p,
+                    (unsigned long long)bytes);
+    return MSPLAT_OK;
+}
+
+// the 4-byte counter of run_ingest for the routes that stage nothing (kept: a re-upload allocates nothing)
+static int ingest_counter(msplat_ctx* ctx, uint32_t*& d_over)
+{
+    int rc = buf_alloc(ctx, ctx->upload_over, 16);
+    d_over = words(ctx->upload_over);
+    return rc;
+}
+
+// msplat_upload_cloud with the records in device memory: repack_kernel instead of the host loop, the same context afterwards
+int msplat_upload_cloud_device(msplat_ctx* ctx, const void* d_aos, uint64_t n, uint32_t stride_bytes,
+                               const msplat_attr_offsets* off, int full_sh)
+{
+    static const char* who = "msplat_upload_cloud_device";
+    drain_async(ctx);
+    if (!ctx) return fail(nullptr, MSPLAT_ERR_INVALID_ARG, "ctx is NULL");
+    if ((!d_aos && n) || !off) return fail(ctx, MSPLAT_ERR_INVALID_ARG, "%s: NULL argument", who);
+    if (reinterpret_cast<uintptr_t>(d_aos) % 16 != 0) return fail(ctx, MSPLAT_ERR_INVALID_ARG, "%s: d_aos must be 16-byte aligned", who);
+    if (stride_bytes % 4 != 0) return fail(ctx, MSPLAT_ERR_INVALID_ARG, "stride must be a multiple of 4");
+    if (stride_bytes > 1024) return fail(ctx, MSPLAT_ERR_UNSUPPORTED, "%s: stride %u > 1024 bytes", who, stride_bytes);
+    int rc = check_splat_count(ctx, n);
+    if (rc) return rc;
+    AttrOffsets ko;
+    static_assert(sizeof(AttrOffsets) == sizeof(msplat_attr_offsets), "offsets mirror out of sync");
+    std::memcpy(&ko, off, sizeof(ko));
+    const uint32_t* o = &ko.pos_with_alpha;
+    for (int k = 0; k < (full_sh ? 16 : 7); ++k)
+        if ((uint64_t)o[k] + (k < 4 || k >= 7 ? 16u : 12u) > stride_bytes)
+            return fail(ctx, MSPLAT_ERR_INVALID_ARG, "attribute offset %u beyond stride %u", o[k], stride_bytes);
+    if (n && (rc = check_device_source(ctx, who, "d_aos", d_aos, n * stride_bytes))) return rc;
+    ctx->point_mode = false;
+    if ((rc = prepare_cloud_buffers(ctx, n, full_sh != 0, nullptr))) return rc;
+    if (n) {
+        uint32_t* d_over = nullptr;
+        if ((rc = ingest_counter(ctx, d_over))) return rc;
+        const int grid = (int)div_up(n, 64);
+        const size_t lds = (size_t)64 * stride_bytes;      // <= 64 KB
+        rc = run_ingest(ctx, who, d_over, hipSuccess, [&](auto SH, auto ST) {
+            hipLaunchKernelGGL((repack_kernel<SH.value, ST.value>), dim3(grid), dim3(64), lds, ctx->stream, (const char*)d_aos, n,
+                               stride_bytes, ko, (float4*)ctx->pos4.p, (float4*)ctx->recs.p, d_over);
+        });
+        if (rc) return rc;
+    }
+    if ((rc = spatial_reorder(ctx))) return rc;
+    ctx->has_cloud = true;
+    return MSPLAT_OK;
+}
+
+// msplat_upload_ply_vertices with the vertex block in device memory: the same ingest_kernel launch, no staging copy
+int msplat_upload_ply_vertices_device(msplat_ctx* ctx, const void* d_vertices, uint64_t n, const msplat_ply_layout* layout,
+                                      int full_sh)
+{
+    static const char* who = "msplat_upload_ply_vertices_device";
+    drain_async(ctx);
+    if (!ctx) return fail(nullptr, MSPLAT_ERR_INVALID_ARG, "ctx is NULL");
+    if ((!d_vertices && n) || !layout) return fail(ctx, MSPLAT_ERR_INVALID_ARG, "%s: NULL argument", who);
+    if (reinterpret_cast<uintptr_t>(d_vertices) % 16 != 0)
+        return fail(ctx, MSPLAT_ERR_INVALID_ARG, "%s: d_vertices must be 16-byte aligned", who);
+    bool full = false;
+    int rc = check_ply_layout(ctx, layout, full_sh, full);
+    if (rc) return rc;
+    if ((rc = check_splat_count(ctx, n))) return rc;
+    if (n && (rc = check_device_source(ctx, who, "d_vertices", d_vertices, n * layout->vertex_size))) return rc;
+    ctx->point_mode = false;
+    if ((rc = prepare_cloud_buffers(ctx, n, full, nullptr))) return rc;
+    if (n) {
+        uint32_t* d_over = nullptr;
+        if ((rc = ingest_counter(ctx, d_over))) return rc;
+        if ((rc = ingest_vertices(ctx, who, d_vertices, n, layout, d_over, hipSuccess))) return rc;
+    }
+    if ((rc = spatial_reorder(ctx))) return rc;
+    ctx->has_cloud = true;
+    return MSPLAT_OK;
+}
+
+// msplat_cloud_from_attributes + msplat_upload_gaussian_cloud with the six arrays in device memory: ingest_attributes_kernel,
+// the vertex routes' math (one device function) on the same values
+int msplat_upload_attributes_device(msplat_ctx* ctx, uint64_t n, const float* d_xyz, const float* d_f_dc, const float* d_f_rest,
+                                    const float* d_opacity, const float* d_log_scale, const float* d_rot, int full_sh)
+{
+    static const char* who = "msplat_upload_attributes_device";
+    drain_async(ctx);
+    if (!ctx) return fail(nullptr, MSPLAT_ERR_INVALID_ARG, "ctx is NULL");
+    const bool full = full_sh != 0 && d_f_rest != nullptr;      // f_rest is optional, as in msplat_cloud_from_attributes
+    struct { const char* name; const float* p; uint32_t floats; } src[6] = {
+        {"d_xyz", d_xyz, 3}, {"d_f_dc", d_f_dc, 3}, {"d_f_rest", full ? d_f_rest : nullptr, 45},
+        {"d_opacity", d_opacity, 1}, {"d_log_scale", d_log_scale, 3}, {"d_rot", d_rot, 4}};
+    for (int k = 0; k < 6; ++k) {
+        if (k == 2 && !full) continue;
+        if (!src[k].p && n) return fail(ctx, MSPLAT_ERR_INVALID_ARG, "%s: %s is NULL", who, src[k].name);
+        if (reinterpret_cast<uintptr_t>(src[k].p) % 4 != 0)
+            return fail(ctx, MSPLAT_ERR_INVALID_ARG, "%s: %s must be 4-byte aligned", who, src[k].name);
+    }
+    int rc = check_splat_count(ctx, n);
+    if (rc) return rc;
+    for (int k = 0; k < 6 && n; ++k)
+        if (src[k].p && (rc = check_device_source(ctx, who, src[k].name, src[k].p, n * src[k].floats * 4))) return rc;
+    ctx->point_mode = false;
+    if ((rc = prepare_cloud_buffers(ctx, n, full, nullptr))) return rc;
+    if (n) {
+        uint32_t* d_over = nullptr;
+        if ((rc = ingest_counter(ctx, d_over))) return rc;
+        const AttrArrays arr{d_xyz, d_f_dc, full ? d_f_rest : nullptr, d_opacity, d_log_scale, d_rot};
+        const int grid = (int)div_up(n, 64);
+        rc = run_ingest(ctx, who, d_over, hipSuccess, [&](auto SH, auto ST) {
+            hipLaunchKernelGGL((ingest_attributes_kernel<SH.value, ST.value>), dim3(grid), dim3(64), 0, ctx->stream, arr, n,
+                               (float4*)ctx->pos4.p, (float4*)ctx->recs.p, d_over);
+        });
+        if (rc) return rc;
     }
     if ((rc = spatial_reorder(ctx))) return rc;
     ctx->has_cloud = true;

@@ -126,32 +126,7 @@ public:
         cfg.struct_size = sizeof(cfg);
         cfg.srgb = isFramebufferSRGBEnabledIn ? 1 : 0;
         if (groupDevices.size() > 1) return InitGroup(*gaussianCloud);
-        msplat_config c = cfg;
-        if (framesInFlight > 1) {
-            c.stream = nullptr;
-            c.compositor_waves = 1280;       // frames share the CUs (measured r3: 768 .. 2048, DESIGN.md 5)
-            c.frame_mode = MSPLAT_FRAMES_IN_FLIGHT;   // kernels that co-schedule well with other frames' kernels (+2-3 %)
-            c.async_submit = 1;                       // a worker thread per context issues its launches (msplat.h)
-        }
-        // r6: an even number >= 4 of frames in flight: the contexts' streams alternate between the even and the odd CU positions of
-        // every XCD -- two frames per half of the CUs instead of four on all of them (+3-5 %, DESIGN.md 5)
-        const bool halves = framesInFlight >= 4 && framesInFlight % 2 == 0 && cfg.cu_partition == MSPLAT_CU_ALL;
-        for (int k = 0; k < framesInFlight; ++k) {
-            msplat_ctx* h = nullptr;
-            if (halves) c.cu_partition = MSPLAT_CU_EVEN + (k & 1);
-            if (msplat_create(&h, &c) != MSPLAT_OK) {
-                std::fprintf(stderr, "[msplat][E] %s\n", msplat_last_error(nullptr));
-                DestroyContexts();
-                return false;
-            }
-            ctxs.push_back(h);
-        }
-        ctx = ctxs[0];
-        cur = framesInFlight - 1;            // the first Sort lands on context 0
-        if (msplat_set_cloud_storage(ctx, cloudStorage) != MSPLAT_OK) {      // (attached contexts render ctxs[0]'s storage)
-            std::fprintf(stderr, "[msplat][E] %s\n", msplat_last_error(ctx));
-            return false;
-        }
+        if (!CreateContexts()) return false;
         msplat_attr_offsets off{};
         off.pos_with_alpha = (uint32_t)gaussianCloud->GetPosWithAlphaAttrib().offset;
         off.r_sh0 = (uint32_t)gaussianCloud->GetR_SH0Attrib().offset;
@@ -176,12 +151,26 @@ public:
             std::fprintf(stderr, "[msplat][E] %s\n", msplat_last_error(ctx));
             return false;
         }
-        for (size_t k = 1; k < ctxs.size(); ++k)
-            if (msplat_attach_cloud(ctxs[k], ctxs[0]) != MSPLAT_OK) {
-                std::fprintf(stderr, "[msplat][E] %s\n", msplat_last_error(ctxs[k]));
-                return false;
-            }
-        return true;
+        return AttachContexts();
+    }
+
+    // Init from a cloud that is already in device memory (msplat_upload_cloud_device / msplat_upload_attributes_device):
+    // contexts as Init creates them -- SetFramesInFlight and SetCloudStorage are honoured -- and the cloud read from the caller's
+    // device memory on context 0's stream; on return the source may be overwritten or freed.  Whatever produced it must have
+    // completed.  Not with ConfigureDevices of more than one device (a replicated cloud needs peer copies): false after logging.
+    bool InitDevice(const void* dRecords, uint64_t n, uint32_t strideBytes, const msplat_attr_offsets& off, bool fullSH,
+                    bool isFramebufferSRGBEnabledIn)
+    {
+        return InitDeviceWith("InitDevice", isFramebufferSRGBEnabledIn,
+                              [&] { return msplat_upload_cloud_device(ctx, dRecords, n, strideBytes, &off, fullSH ? 1 : 0); });
+    }
+    // the arrays of msplat_cloud_from_attributes in device memory; dFRest may be NULL (SH degree 0)
+    bool InitDeviceAttributes(uint64_t n, const float* dXyz, const float* dFDc, const float* dFRest, const float* dOpacity,
+                              const float* dLogScale, const float* dRot, bool fullSH, bool isFramebufferSRGBEnabledIn)
+    {
+        return InitDeviceWith("InitDeviceAttributes", isFramebufferSRGBEnabledIn, [&] {
+            return msplat_upload_attributes_device(ctx, n, dXyz, dFDc, dFRest, dOpacity, dLogScale, dRot, fullSH ? 1 : 0);
+        });
     }
 
     // splatrenderer.cpp:153-312
@@ -368,6 +357,68 @@ public:
     uint32_t numBlocksPerWorkgroup = 1024;   // accepted and ignored (splatrenderer.h:39)
 
 protected:
+    // one context per frame in flight, the storage kind set on context 0 (cfg.struct_size / srgb are the caller's)
+    bool CreateContexts()
+    {
+        msplat_config c = cfg;
+        if (framesInFlight > 1) {
+            c.stream = nullptr;
+            c.compositor_waves = 1280;       // frames share the CUs (measured r3: 768 .. 2048, DESIGN.md 5)
+            c.frame_mode = MSPLAT_FRAMES_IN_FLIGHT;   // kernels that co-schedule well with other frames' kernels (+2-3 %)
+            c.async_submit = 1;                       // a worker thread per context issues its launches (msplat.h)
+        }
+        // r6: an even number >= 4 of frames in flight: the contexts' streams alternate between the even and the odd CU positions of
+        // every XCD -- two frames per half of the CUs instead of four on all of them (+3-5 %, DESIGN.md 5)
+        const bool halves = framesInFlight >= 4 && framesInFlight % 2 == 0 && cfg.cu_partition == MSPLAT_CU_ALL;
+        for (int k = 0; k < framesInFlight; ++k) {
+            msplat_ctx* h = nullptr;
+            if (halves) c.cu_partition = MSPLAT_CU_EVEN + (k & 1);
+            if (msplat_create(&h, &c) != MSPLAT_OK) {
+                std::fprintf(stderr, "[msplat][E] %s\n", msplat_last_error(nullptr));
+                DestroyContexts();
+                return false;
+            }
+            ctxs.push_back(h);
+        }
+        ctx = ctxs[0];
+        cur = framesInFlight - 1;            // the first Sort lands on context 0
+        if (msplat_set_cloud_storage(ctx, cloudStorage) != MSPLAT_OK) {      // (attached contexts render ctxs[0]'s storage)
+            std::fprintf(stderr, "[msplat][E] %s\n", msplat_last_error(ctx));
+            return false;
+        }
+        return true;
+    }
+
+    // every other context of the rotation renders context 0's cloud
+    bool AttachContexts()
+    {
+        for (size_t k = 1; k < ctxs.size(); ++k)
+            if (msplat_attach_cloud(ctxs[k], ctxs[0]) != MSPLAT_OK) {
+                std::fprintf(stderr, "[msplat][E] %s\n", msplat_last_error(ctxs[k]));
+                return false;
+            }
+        return true;
+    }
+
+    template <class Upload>
+    bool InitDeviceWith(const char* name, bool srgb, Upload upload)
+    {
+        DestroyContexts();
+        cfg.struct_size = sizeof(cfg);
+        cfg.srgb = srgb ? 1 : 0;
+        if (groupDevices.size() > 1) {
+            std::fprintf(stderr, "[msplat][E] %s: a device group takes no cloud from device memory (the replicated cloud needs peer "
+                         "copies): Init from host memory, or ConfigureDevices with one device\n", name);
+            return false;
+        }
+        if (!CreateContexts()) return false;
+        if (upload() != MSPLAT_OK) {
+            std::fprintf(stderr, "[msplat][E] %s: %s\n", name, msplat_last_error(ctx));
+            return false;
+        }
+        return AttachContexts();
+    }
+
     bool InitGroup(GaussianCloud& cloud)
     {
         std::vector<int32_t> devs(groupDevices.begin(), groupDevices.end());

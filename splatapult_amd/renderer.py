@@ -57,6 +57,36 @@ def _aos_upload(cloud):
     return aos, (aos.ctypes.data, aos.shape[0], aos.shape[1] * 4, C.byref(off), 1 if aos.shape[1] == 61 else 0)
 
 
+def _tensor_upload(xyz, f_dc, f_rest, opacity, log_scale, rot, full_sh):
+    """six device tensors (duck-typed: data_ptr(), is_contiguous(), dtype, shape, device) -> the arguments of
+    msplat_upload_attributes_device after the handle.  ValueError for anything but contiguous float32 of the right shape.  The
+    current stream of a torch tensor's device is synchronised: what produced the tensors has then completed."""
+    n = int(xyz.shape[0])
+    want = {"xyz": (xyz, [(n, 3)]), "f_dc": (f_dc, [(n, 3)]), "f_rest": (f_rest, [(n, 45), (n, 3, 15)]),
+            "opacity": (opacity, [(n,), (n, 1)]), "log_scale": (log_scale, [(n, 3)]), "rot": (rot, [(n, 4)])}
+    for name, (t, shapes) in want.items():
+        if t is None and name == "f_rest":
+            continue
+        if str(t.dtype).split(".")[-1] != "float32":
+            raise ValueError("%s must be float32, not %s" % (name, t.dtype))
+        if tuple(int(s) for s in t.shape) not in shapes:
+            raise ValueError("%s must have shape %s, not %s" % (name, " or ".join(str(s) for s in shapes), tuple(t.shape)))
+        if not t.is_contiguous():
+            raise ValueError("%s must be contiguous (pass %s.contiguous())" % (name, name))
+        if getattr(t.device, "type", "cuda") not in ("cuda", "hip"):
+            raise ValueError("%s must live in device memory, not on %s" % (name, t.device))
+    ptrs = {name: None if t is None else int(t.data_ptr()) for name, (t, _) in want.items()}
+    import sys
+    torch = sys.modules.get("torch")
+    for t in (xyz, f_dc, f_rest, opacity, log_scale, rot):
+        if torch is not None and isinstance(t, torch.Tensor):
+            torch.cuda.current_stream(t.device).synchronize()
+            break
+    full = bool(full_sh) and ptrs["f_rest"] is not None
+    return (n, C.c_void_p(ptrs["xyz"]), C.c_void_p(ptrs["f_dc"]), C.c_void_p(ptrs["f_rest"] if full else None),
+            C.c_void_p(ptrs["opacity"]), C.c_void_p(ptrs["log_scale"]), C.c_void_p(ptrs["rot"]), 1 if full else 0)
+
+
 def _target_mode(name):
     """set_target_mode argument -> MSPLAT_TARGET_*"""
     if name not in _capi.TARGET_MODES:
@@ -221,6 +251,49 @@ class SplatRenderer:
             self._err = self._lib.msplat_last_error(self._ctx).decode() or "PLY open/parse failure"
             return False
         self._n = self.stats()["num_splats"]
+        return self._attach_all()
+
+    # -- clouds that are already in device memory (msplat_upload_*_device) ---------
+    def InitFromDevice(self, ptr, n, stride_bytes, offsets, full_sh, isFramebufferSRGBEnabled=False):
+        """Init from n interleaved records of stride_bytes in device memory (msplat_upload_cloud_device): ptr = device pointer (int,
+        16-byte aligned), offsets = _capi.AttrOffsets or the 16 byte offsets in its field order.  The same context as Init with the
+        same bytes in host memory.  The records must be complete when this is called (it does not know their producer's stream);
+        on return they may be overwritten or freed."""
+        return self._create(isFramebufferSRGBEnabled) and self.UpdateFromDevice(ptr, n, stride_bytes, offsets, full_sh)
+
+    def InitFromTensors(self, xyz, f_dc, f_rest, opacity, log_scale, rot, full_sh=True, isFramebufferSRGBEnabled=False):
+        """Init from a trainer's parameter tensors on this renderer's device (msplat_upload_attributes_device): GaussianCloud
+        .FromAttributes' arrays -- xyz (N, 3), f_dc (N, 3), f_rest (N, 45) in PLY order or (N, 3, 15) or None, opacity (N,) or
+        (N, 1), log_scale (N, 3), rot (N, 4) as w x y z -- float32 and contiguous, else ValueError.  Tensors are duck-typed
+        (data_ptr(), is_contiguous(), dtype, shape, device); the current stream of torch tensors' device is synchronised first.
+        f_rest=None or full_sh=False: SH degree 0."""
+        args = _tensor_upload(xyz, f_dc, f_rest, opacity, log_scale, rot, full_sh)      # (refused before a context exists)
+        return self._create(isFramebufferSRGBEnabled) and self._upload_device(self._lib.msplat_upload_attributes_device, args)
+
+    def UpdateFromDevice(self, ptr, n, stride_bytes, offsets, full_sh):
+        """InitFromDevice into the contexts that exist: the cloud goes into context 0, the others are attached again, nothing is
+        re-created (a single context re-uses its store for the same or a smaller n).  Every frame in flight is finished first."""
+        off = offsets if isinstance(offsets, _capi.AttrOffsets) else _capi.AttrOffsets(*[int(o) for o in offsets])
+        return self._upload_device(self._lib.msplat_upload_cloud_device,
+                                   (C.c_void_p(int(ptr)), int(n), int(stride_bytes), C.byref(off), 1 if full_sh else 0))
+
+    def UpdateFromTensors(self, xyz, f_dc, f_rest, opacity, log_scale, rot, full_sh=True):
+        """InitFromTensors into the contexts that exist -- the loop of a viewer that follows a training run: UpdateFromTensors,
+        Sort, Render per step"""
+        return self._upload_device(self._lib.msplat_upload_attributes_device,
+                                   _tensor_upload(xyz, f_dc, f_rest, opacity, log_scale, rot, full_sh))
+
+    def _upload_device(self, fn, args):
+        if not self._ctxs:
+            self._err = "no context: InitFromDevice / InitFromTensors (or Init) first"
+            return False
+        own = self._ctx = self._ctxs[0]
+        self._cur = self._depth - 1          # the next Sort lands on context 0, as after Init
+        rc = fn(own, *args)
+        if rc != _capi.OK:
+            self._err = self._lib.msplat_last_error(own).decode()
+            return False
+        self._n = int(args[1] if fn is self._lib.msplat_upload_cloud_device else args[0])
         return self._attach_all()
 
     def download_cloud(self, full_sh):
