@@ -77,7 +77,7 @@ def u32_digest(a):
 
 # ---- PointRenderer: shader/point_{vert,geom,frag}.glsl + the sprite texture, on llvmpipe ----
 def point_sprite(size=64):
-    from tests.test_points import smooth_sprite
+    from tests.render_cases import smooth_sprite
     return smooth_sprite(size, size, seed=9)          # 2^k x 2^k: every mip reduction is an exact 2x2 box in any GL
 
 

@@ -53,7 +53,7 @@ def frame(aos, full_sh, cam, proj, W, H, **kw):
 
 def make_8f4():
     """SURVEY 8f-4 fixtures: depth-buffer emulation (second-eye case) and the point-cloud renderer"""
-    from tests.test_points import smooth_sprite
+    from tests.render_cases import smooth_sprite
     g = np.load(os.path.join(HERE, "synth_sh3.npz"))
     aos = orc.build_cloud(g["in_xyz"], g["in_f_dc"], g["in_f_rest"], g["in_opacity"], g["in_log_scale"], g["in_rot"], True)
     W, H = int(g["W"]), int(g["H"])

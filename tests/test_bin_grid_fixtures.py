@@ -2,57 +2,15 @@
 reach the 8-bit limit of the bin grid.  Oracle only -- if a seed or a helper changes so that the GPU tests stop reaching bin
 index 255, this fails without a GPU.
 
-A splat's bin rectangle is taken from the oracle's projection exactly as _check_projection (tests/test_gpu_parity.py) bounds the
+A splat's bin rectangle is taken from the oracle's projection exactly as _check_projection (tests/gpu_harness.py) bounds the
 library's from below: the pixels with w > 1/256 lie within rho sqrt(cov) of the centre, clipped to the viewport, divided by
 the 32-px bin."""
-import functools
-
 import numpy as np
 import pytest
 
 from oracle import oracle as orc
-from tests import scenes
-from tests.test_gpu_parity import TIGHT, check_image
-
-BIN = 32      # msplat_tile_size(): the bin edge in pixels (asserted against the library by the GPU module)
-
-# name -> (W, H, yaw, n, seed, hard): the five inputs of the GPU module's strip tests
-STRIPS = {
-    "wide_synth": (8192, 64, 0.0, 40000, 5, False),
-    "tall_synth": (64, 8192, 0.0, 40000, 6, False),
-    "wide_hard": (8192, 64, 0.1, 20000, 7, True),
-    "tall_hard": (64, 8192, 0.0, 20000, 8, True),
-    "ragged_hard": (8191, 33, 0.0, 20000, 9, True),
-}
-
-
-@functools.lru_cache(maxsize=None)
-def strip_cloud(name):
-    W, H, yaw, n, seed, hard = STRIPS[name]
-    return scenes.cloud_from_attrs(scenes.strip_attrs(n, seed, W, H, hard))
-
-
-def strip_case(name):
-    """(cloud, W, H, view) of a named strip"""
-    W, H, yaw = STRIPS[name][:3]
-    return strip_cloud(name), W, H, scenes.strip_view(W, H, yaw)
-
-
-def oracle_rects(sp, W, H):
-    """(drawn, tx0, ty0, tx1, ty1) per sorted splat from the oracle's projection: drawn = some pixel centre of the viewport lies
-    inside the w > 1/256 footprint's bounding box"""
-    alpha = sp["alpha"].astype(np.float64)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        rho2 = 2.0 * np.log(256.0 * alpha)
-    vis = (sp["reject"] == 0) & (rho2 > 0)
-    ex = np.sqrt(np.maximum(rho2, 0) * sp["cov"][:, 0])
-    ey = np.sqrt(np.maximum(rho2, 0) * sp["cov"][:, 3])
-    x0 = np.ceil(sp["px"] - ex - 0.5); x1 = np.floor(sp["px"] + ex - 0.5)
-    y0 = np.ceil(sp["py"] - ey - 0.5); y1 = np.floor(sp["py"] + ey - 0.5)
-    drawn = vis & (x1 >= 0) & (y1 >= 0) & (x0 <= W - 1) & (y0 <= H - 1) & (x0 <= x1) & (y0 <= y1)
-    c = lambda v, hi: (np.clip(np.nan_to_num(v), 0, hi - 1) // BIN).astype(np.int64)
-    return drawn, c(x0, W), c(y0, H), c(x1, W), c(y1, H)
-
+from tests.checks import TIGHT, check_image
+from tests.render_cases import BIN, STRIPS, oracle_rects, strip_case
 
 @pytest.mark.parametrize("name", sorted(STRIPS))
 def test_the_strips_reach_bin_255_and_the_tiled_renderer_meets_the_caps(name):

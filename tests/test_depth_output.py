@@ -1,11 +1,11 @@
 """CPU side of msplat_render_depth: the entry point is exported and bound, refuses a NULL context without touching a device, and the
-oracle recipe the GPU tests compare against (tests/test_gpu_depth_output.py imports depth_layers from here) is pinned by a numpy
-restatement of the definition
+oracle recipe the GPU tests compare against (tests/render_cases.depth_layers) is pinned by a numpy restatement of the
+definition
 
     depth = sum_i T_i w_i z_i + T * 1.0,      z_i = 0.5 ndc.z + 0.5,  T_i = prod_{j nearer} (1 - w_j),  T = the product over all
 
 on a handful of hand-placed splats.  The recipe never changes the oracle: window depth is composited as one more colour (the blend
-is linear in colour) and the white frame gives 1 - T, as tests/test_gpu_target_mode.py does for MSPLAT_TARGET_LOAD."""
+is linear in colour) and the white frame gives 1 - T, as tests/render_cases.oracle_layers does for MSPLAT_TARGET_LOAD."""
 import inspect
 import os
 import re
@@ -14,28 +14,9 @@ import numpy as np
 
 from oracle import oracle as orc
 from splatapult_amd import MsplatError, SplatRenderer, SplatRendererGroup, _capi, camera
+from tests.render_cases import depth_layers, hand_placed
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def depth_layers(splats, W, H, nthreads=16):
-    """The reference depth plane of orc.project'ed splats in draw order (orc.render_frame(..., want_splats=True)["splats"]):
-    D_ref = the oracle's composite of the splats recoloured with their window depth, T_ref = 1 - its composite of the splats
-    recoloured white; the plane is D_ref + T_ref.  Also: z_w per splat, the coverage 1 - T_ref and both threshold-flip budgets."""
-    zw = np.float32(0.5) * splats["ndc"][:, 2] + np.float32(0.5)        # project_kernel's arithmetic: an exact product, one rounded sum
-    assert zw.dtype == np.float32
-    coloured = splats.copy()
-    coloured["rgb"] = zw[:, None]
-    D, bud_d = orc.composite_flip(coloured, W, H, nthreads=nthreads)
-    white = splats.copy()
-    white["rgb"] = 1.0
-    cover, bud_w = orc.composite_flip(white, W, H, nthreads=nthreads)
-    T = 1.0 - cover[..., 0].astype(np.float64)
-    out = dict(zw=zw, plane=D[..., 0].astype(np.float64) + T, T=T, cover=cover[..., 0].astype(np.float64),
-               bud_d=bud_d.astype(np.float64), bud_w=bud_w.astype(np.float64))
-    for a in out.values():
-        a.setflags(write=False)
-    return out
 
 
 def test_the_entry_point_is_declared_exported_and_bound():
@@ -71,25 +52,6 @@ def test_the_group_refuses_a_depth_plane_before_it_touches_a_device():
             assert e.code == _capi.ERR_UNSUPPORTED and "depth" in str(e)
         else:
             raise AssertionError("the group took %s" % sorted(kw))
-
-
-def hand_placed():
-    """eight splats in front of a camera at z = 4 looking down -Z: overlapping footprints at distinct depths, one opaque, one faint,
-    one off to the side that overlaps nothing; near / far = 1 / 8 so that z_w covers most of [0.625, 1]"""
-    xyz = np.array([[0.0, 0.0, 1.6], [0.15, 0.05, 0.8], [-0.2, 0.1, 0.0], [0.1, -0.15, -1.0], [0.0, 0.0, -2.5],
-                    [0.9, 0.5, 0.5], [-0.1, 0.0, 1.2], [0.3, 0.2, -3.4]], np.float32)
-    n = xyz.shape[0]
-    f_dc = np.linspace(-1.0, 1.0, n * 3, dtype=np.float32).reshape(n, 3)
-    opacity = np.array([0.5, 2.0, -1.0, 30.0, 1.0, 0.0, -4.5, 3.0], np.float32)            # logits: alpha 0.01 .. 1
-    log_scale = np.log(np.array([[0.12, 0.2, 0.1], [0.3, 0.1, 0.1], [0.25, 0.25, 0.25], [0.4, 0.2, 0.1], [0.8, 0.6, 0.3],
-                                 [0.1, 0.1, 0.1], [0.5, 0.05, 0.1], [1.0, 1.0, 0.2]], np.float32))
-    rot = np.array([[1, 0, 0, 0], [0.9, 0.1, 0.3, 0.2], [1, 0, 0, 0], [0.7, 0.0, 0.0, 0.7], [1, 0, 0, 0], [1, 0, 0, 0],
-                    [0.6, 0.5, 0.4, 0.3], [1, 0, 0, 0]], np.float32)
-    rot /= np.linalg.norm(rot, axis=1, keepdims=True)
-    aos = orc.build_cloud(xyz, f_dc, None, opacity, log_scale, rot, False)
-    W, H, zn, zf = 96, 64, 1.0, 8.0
-    view = (camera.pose((0.0, 0.0, 4.0)), camera.perspective(camera.FOVY, W / H, zn, zf), [0, 0, W, H], [zn, zf])
-    return aos, W, H, view
 
 
 def test_the_oracle_recipe_is_the_definition():

@@ -153,9 +153,9 @@ def test_decode_tables_agree_and_round_trip():
 
 
 def test_the_sparse_scene_exercises_both_clamps_every_code_and_few_boundaries():
-    """fixture honesty: what the GPU tests assume about the "sparse" scene of tests/test_gpu_target_mode.py, on the CPU oracle"""
+    """fixture honesty: what the GPU tests assume about the "sparse" scene of tests/render_cases.py, on the CPU oracle"""
     from oracle import oracle as orc
-    from tests.test_gpu_target_mode import view_of
+    from tests.render_cases import view_of
     cloud, W, H, (cam, proj, vp, nf) = view_of("sparse")
     assert (W, H) == (517, 293)
     rgb = orc.render_frame(cloud.as_array(), True, cam, proj, vp, nf, nthreads=8)["image"][..., :3].astype(np.float32)

@@ -9,8 +9,8 @@ scenes.strip_attrs, whose reach is asserted on the CPU by tests/test_bin_grid_fi
 4160 x 4160 (130 x 130 bins: both coordinates above 127 at once, bin ids up to 16899) and 8192 x 3008 / 3040 (the largest
 summed-area table and the first viewport beyond it).
 
-References: the CPU oracle through check_image / check_fp16_image / _check_projection / _expected_tile_lists of
-tests/test_gpu_parity.py with their caps unchanged, the depth oracle and tolerance of tests/test_gpu_depth_output.py, the point
+References: the CPU oracle through check_image / check_fp16_image (tests/checks.py) and _check_projection / _expected_tile_lists
+(tests/gpu_harness.py) with their caps unchanged, the depth oracle and tolerance of tests/test_gpu_depth_output.py, the point
 oracle at the tolerance of test_point_renderer_matches_oracle; every other comparison is bit for bit.  Which regime ran (own waves /
 persistent waves, one chain / two renders, one pass / two passes) is read from the library's taps and asserted, never assumed.
 
@@ -29,10 +29,10 @@ import pytest
 from oracle import oracle as orc
 from splatapult_amd import MsplatError, _capi, camera, synthetic
 from tests import scenes
-from tests.test_bin_grid_fixtures import BIN, STRIPS, strip_case
-from tests.test_gpu_compositor_queue import SENTINEL, Target, frame, no_sentinel, same_bits, tap
-from tests.test_gpu_parity import (_check_projection, _expected_tile_lists, bin_px, check_fp16_image, check_image, make_renderer,
-                                   oracle_frame, random_points)
+from tests.checks import T_EPS, assert_is_a_plane, check_fp16_image, check_image, check_plane, same_bits
+from tests.gpu_harness import (QUEUE_SENTINEL as SENTINEL, _check_projection, _expected_tile_lists, bin_edge, bin_px, device_frame, make_renderer,
+                               no_sentinel, oracle_frame, stereo_frame, tap)
+from tests.render_cases import BIN, NP_DTYPES, STRIPS, const_dst, depth_layers, random_dst, random_points, smooth_sprite, strip_case
 
 pytestmark = pytest.mark.gpu
 
@@ -174,7 +174,7 @@ def test_short_pool_frames_equal_the_own_wave_frames(name):
             r.set_depth_test(depth_bits)
             r.Sort(*view)
             for rep in range(2):
-                img = frame(r, view)
+                img = device_frame(r, view, None, None, call=r.Render, **bin_edge())
                 assert tap(r, pool, kind=kind, items=STRIP_ITEMS) == (pool is not None)
                 no_sentinel(img)
                 if want is None:
@@ -220,7 +220,7 @@ def test_forced_two_passes_equal_one_pass(W, H, seed):
     for what, cloud, view in (("dense", dense_strip_cloud(W, H, seed), scenes.strip_view(W, H)), ("hard", hard[0], hard[3])):
         a = make_renderer(cloud, two_pass=_capi.TWO_PASS_OFF)
         a.Sort(*view)
-        want = frame(a, view)
+        want = device_frame(a, view, None, None, call=a.Render, **bin_edge())
         no_sentinel(want)
         assert a.two_pass_state()[0] == 0 and a.two_pass_info() is None
         dropped = []
@@ -228,7 +228,7 @@ def test_forced_two_passes_equal_one_pass(W, H, seed):
             b = make_renderer(cloud, two_pass=_capi.TWO_PASS_ON)
             b.two_pass_state(share)
             b.Sort(*view)
-            img = frame(b, view)
+            img = device_frame(b, view, None, None, call=b.Render, **bin_edge())
             same_bits(img, want, "%s %dx%d share %g" % (what, W, H, share))
             assert b.two_pass_state(share)[0] == 1
             info = b.two_pass_info()
@@ -256,7 +256,7 @@ def test_row_bands_reassemble_the_strip_bit_for_bit(name):
     R = (H + BIN - 1) // BIN
     base = make_renderer(cloud)
     base.Sort(*view)
-    want = frame(base, view)
+    want = device_frame(base, view, None, None, call=base.Render, **bin_edge())
     no_sentinel(want)
     for kind, k, G in BAND_LAYOUTS[name]:
         for cull in (False, True):
@@ -269,7 +269,7 @@ def test_row_bands_reassemble_the_strip_bit_for_bit(name):
                 mine = _capi.band_rows(*lay, rows_full=R)
                 rb.Sort(*view)
                 vs.append(rb.sort_count())
-                part = frame(rb, view)
+                part = device_frame(rb, view, None, None, call=rb.Render, **bin_edge())
                 rows = np.isin(np.arange(H) // BIN, mine)
                 assert (part[~rows] == SENTINEL).all() and not (covered & rows).any()
                 assert rb.stats()["tiles_y"] == len(mine)
@@ -286,7 +286,6 @@ def test_row_bands_reassemble_the_strip_bit_for_bit(name):
 def test_target_modes_on_a_pitched_target(name):
     """the identities of tests/test_gpu_target_mode.py::test_identities_between_the_modes (device_pitched_fp32), also on the thin
     strip cloud, most of whose pixels stay translucent"""
-    from tests.test_gpu_target_mode import SENTINEL as PAD, const_dst, random_dst, render_device
     if name.endswith("hard"):
         r, W, H, view = sorted_strip(name)
     else:
@@ -295,11 +294,7 @@ def test_target_modes_on_a_pitched_target(name):
         r = make_renderer(thin_strip_cloud(W, H, seed))
         r.Sort(*view)
 
-    def run(mode, dst):
-        img, padding = render_device(r, view, mode, dst)
-        assert (padding == PAD).all(), "mode %s wrote into the padding of a pitched target" % mode
-        return img
-
+    run = lambda mode, dst: device_frame(r, view, mode, dst, call=r.Render)         # (asserts that the padding keeps its bytes)
     zeros, opaque = const_dst(H, W, (0, 0, 0, 0)), const_dst(H, W, (0, 0, 0, 1))
     junk = random_dst(H, W, 5)
     clear = run("clear", junk)
@@ -317,7 +312,6 @@ def test_target_modes_on_a_pitched_target(name):
 
 @functools.lru_cache(maxsize=None)
 def strip_depth_layers(name):
-    from tests.test_depth_output import depth_layers
     _, W, H, _ = strip_case(name)
     return depth_layers(strip_oracle(name)["splats"], W, H, nthreads=16)
 
@@ -325,10 +319,9 @@ def strip_depth_layers(name):
 @pytest.mark.parametrize("name", ["wide_hard", "tall_hard"])
 def test_depth_plane(name):
     """msplat_render_depth: the colour of msplat_render bit for bit; the plane against the depth oracle, check_plane's tolerance"""
-    from tests.test_gpu_depth_output import T_EPS, assert_is_a_plane, check_plane
     r, W, H, view = sorted_strip(name)
-    plain = frame(r, view)
-    img, z = frame(r, view, depth=True)
+    plain = device_frame(r, view, None, None, call=r.Render, **bin_edge())
+    img, z = device_frame(r, view, None, None, call=r.Render, depth=True, **bin_edge())
     same_bits(img, plain, "%s: the colour of a depth frame" % name)
     no_sentinel(z)
     assert_is_a_plane(z)
@@ -357,7 +350,7 @@ def test_stereo_at_the_limit_of_the_chain(H, batched):
         r.Sort(eyes[0], proj, vp, nf)
         want = []
         for e in range(2):
-            want.append(frame(r, (eyes[0], proj, vp, nf), fmt, render_cam=eyes[e]))
+            want.append(device_frame(r, (eyes[0], proj, vp, nf), None, None, call=r.Render, render_cam=eyes[e], **bin_edge(dtype=NP_DTYPES[fmt])))
             assert not tap(r, None, items=one_view)
             no_sentinel(want[-1])
         assert not np.array_equal(want[0], want[1])
@@ -366,14 +359,12 @@ def test_stereo_at_the_limit_of_the_chain(H, batched):
         rs = make_renderer(cloud, fb_format=fmt)
         rs.Sort(eyes[0], proj, vp, nf)
         for rep in range(2):
-            tg = [Target(W, H, fmt), Target(W, H, fmt)]
-            rs.RenderStereo(eyes, [proj, proj], vp, nf, out_ptrs=[t.ptr for t in tg], pitch_bytes=tg[0].pitch)
-            rs.synchronize()
+            imgs = stereo_frame(rs, eyes, [proj, proj], vp, nf, None, None, call=rs.RenderStereo, **bin_edge(dtype=NP_DTYPES[fmt]))
             launch = rs.compositor_launch()
             assert launch[0] == (2 * one_view if batched else one_view) and launch[1] == launch[0], launch
             assert rs.stats()["tiles_y"] == (2 * rows if batched else rows)
             for e in range(2):
-                same_bits(tg[e].image(), want[e], "64x%d %s frame %d eye %d" % (H, fmt, rep, e))
+                same_bits(imgs[e], want[e], "64x%d %s frame %d eye %d" % (H, fmt, rep, e))
         print("64x%d %s: %s, compositor launch %s, tiles_y %d" % (H, fmt, "one chain" if batched else "two renders", launch, rs.stats()["tiles_y"]))
         assert rs.verify_order() == (0, 0)
         r.close(); rs.close()
@@ -528,7 +519,6 @@ def test_points_on_the_strips(W, H):
     of test_point_renderer_matches_oracle -- and below one pixel on the wide one, where only the draw order (exact) and the
     short-pool frame (equal to the own-wave frame, as on the tall strip) are asserted"""
     from splatapult_amd import PointRenderer
-    from tests.test_points import smooth_sprite
     pts, tex = strip_points(W, H), smooth_sprite(64, 48, seed=2)
     view = cam, proj, vp, nf = scenes.strip_view(W, H)
     ref = orc.points_frame(pts, tex, cam, proj, vp, nf, srgb=False, depth_bits=0)
@@ -542,7 +532,7 @@ def test_points_on_the_strips(W, H):
         r = PointRenderer(device=0, compositor_waves=pool)
         assert r.Init(pts, False, sprite=tex), r.last_error()
         for rep in range(2):
-            img = frame(r, view)
+            img = device_frame(r, view, None, None, call=r.Render, **bin_edge())
             assert tap(r, pool, kind=2, items=STRIP_ITEMS) == (pool is not None)
             no_sentinel(img)
             if want is None:

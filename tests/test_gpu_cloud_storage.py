@@ -13,13 +13,15 @@ import pytest
 from splatapult_amd import SplatRenderer, _capi, camera, synthetic
 from splatapult_amd.renderer import SplatRendererGroup
 from tests import scenes
+from tests.checks import bits, same_bits
+from tests.gpu_harness import assert_same_lists, sorted_frame
+from tests.render_cases import AOS_OFF, ply_layout, sh_basis_bounds
 
 pytestmark = pytest.mark.gpu
 
 # f_rest columns of the reference record (61 floats: pos+alpha, r/g/b_sh0 = DC + band 1, Sigma, r/g/b_sh1..3 = bands 2-3);
 # a degree-1 record (25 floats) has the first nine
 REST = [5, 6, 7, 9, 10, 11, 13, 14, 15] + list(range(25, 61))
-AOS_OFF = (0, 16, 32, 48, 64, 76, 88, 100, 116, 132, 148, 164, 180, 196, 212, 228)
 
 
 def round16(aos):
@@ -29,10 +31,6 @@ def round16(aos):
     with np.errstate(over="ignore", invalid="ignore"):
         out[:, cols] = out[:, cols].astype(np.float16).astype(np.float32)
     return out
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint16 if a.dtype == np.float16 else np.uint32)
 
 
 def cfg2_view(W=1920, H=1080, yaw=0.3):
@@ -57,26 +55,6 @@ def cloud(key):
     return _CLOUDS[key]
 
 
-def frame(r, view):
-    r.Sort(*view)
-    img = r.Render(*view)
-    st = r.stats()
-    return dict(img=img, keys=r.sorted_keys(), idx=r.sorted_indices(), V=r.sort_count(), drawn=st["drawn"], pairs=st["pairs"])
-
-
-def assert_same_lists(a, b):
-    assert a["V"] == b["V"]
-    np.testing.assert_array_equal(a["keys"], b["keys"])
-    np.testing.assert_array_equal(a["idx"], b["idx"])
-    assert (a["drawn"], a["pairs"]) == (b["drawn"], b["pairs"])
-
-
-def assert_bit_identical(img16, img_r):
-    assert img16.dtype == img_r.dtype and img16.shape == img_r.shape
-    diff = bits(img16) != bits(img_r)
-    assert not diff.any(), "%d of %d pixel words differ" % (int(diff.sum()), diff.size)
-
-
 def three_renders(aos, view, make, prepare=None):
     """(SH_FP16 of C, FP32 of round16(C), FP32 of C) frames with renderers from make(cloud_storage=...)"""
     out = []
@@ -86,7 +64,7 @@ def three_renders(aos, view, make, prepare=None):
         assert r.cloud_storage() == storage
         if prepare:
             prepare(r)
-        out.append(frame(r, view))
+        out.append(sorted_frame(r, view))
         r.close()
     return out
 
@@ -97,7 +75,7 @@ def three_renders(aos, view, make, prepare=None):
 def test_sh16_renders_the_fp32_frame_of_the_rounded_cloud(key, spatial):
     f16, fr, f32 = three_renders(cloud(key), cfg2_view(), lambda **kw: SplatRenderer(device=0, spatial_order=spatial, **kw))
     assert f16["V"] > 1000
-    assert_bit_identical(f16["img"], fr["img"])
+    same_bits(f16["img"], fr["img"])
     assert_same_lists(f16, f32)
 
 
@@ -105,7 +83,7 @@ def test_sh16_renders_the_fp32_frame_of_the_rounded_cloud(key, spatial):
 def test_sh16_bit_identity_on_an_rgba16f_target(key):
     f16, fr, f32 = three_renders(cloud(key), cfg2_view(), lambda **kw: SplatRenderer(device=0, fb_format="fp16", **kw))
     assert f16["img"].dtype == np.float16
-    assert_bit_identical(f16["img"], fr["img"])
+    same_bits(f16["img"], fr["img"])
     assert_same_lists(f16, f32)
 
 
@@ -116,14 +94,14 @@ def test_sh16_bit_identity_with_two_passes_on_6m():
         r = SplatRenderer(device=0, two_pass=_capi.TWO_PASS_ON, cloud_storage=storage)
         assert r.Init(a, False, False), r.last_error()
         r.two_pass_state(0.15)            # pin the first pass's share: both passes run
-        f = frame(r, view)
+        f = sorted_frame(r, view)
         f["tp"] = r.two_pass_info()
         out.append(f)
         r.close()
     _CLOUDS.pop("cfg3")
     f16, fr, f32 = out
     assert f16["tp"] is not None and fr["tp"] is not None, "the frame did not run in two passes"
-    assert_bit_identical(f16["img"], fr["img"])
+    same_bits(f16["img"], fr["img"])
     # (with two passes, drawn / pairs describe the second pass: they too must match the FP32 frame of C)
     assert_same_lists(f16, f32)
 
@@ -142,7 +120,7 @@ def test_sh16_bit_identity_stereo_both_eyes(key):
         outs.append(r.RenderStereo(cams, [proj, proj], vp, scenes.NF))
         r.close()
     for eye in range(2):
-        assert_bit_identical(outs[0][eye], outs[1][eye])
+        same_bits(outs[0][eye], outs[1][eye])
 
 
 def test_sh16_bit_identity_four_frames_in_flight():
@@ -162,7 +140,7 @@ def test_sh16_bit_identity_four_frames_in_flight():
         frames[storage] = got
         r.close()
     for k in range(len(views)):
-        assert_bit_identical(frames["sh_fp16"][k][0], frames["fp32"][k][0])
+        same_bits(frames["sh_fp16"][k][0], frames["fp32"][k][0])
         np.testing.assert_array_equal(frames["sh_fp16"][k][1], frames["fp32 of C"][k][1])
         np.testing.assert_array_equal(frames["sh_fp16"][k][2], frames["fp32 of C"][k][2])
 
@@ -171,7 +149,7 @@ def test_sh16_bit_identity_banded_context():
     def prepare(r):
         r.set_band_layout(1, 0, 3, 4, band_cull=True)       # blocks of 3 bin rows from row 1, every 4th block
     f16, fr, f32 = three_renders(cloud("cfg2"), cfg2_view(), lambda **kw: SplatRenderer(device=0, **kw), prepare)
-    assert_bit_identical(f16["img"], fr["img"])
+    same_bits(f16["img"], fr["img"])
     assert_same_lists(f16, f32)
 
 
@@ -186,7 +164,7 @@ def test_sh16_bit_identity_one_device_group():
         g.Sort(*view)
         imgs.append(g.Render(*view))
         g.close()
-    assert_bit_identical(imgs[0], imgs[1])
+    same_bits(imgs[0], imgs[1])
 
 
 # ---- 2. rounding ---------------------------------------------------------------------------------------------------------
@@ -207,23 +185,6 @@ def assert_equal_records(got, want):
     gn, wn = np.isnan(got), np.isnan(want)
     np.testing.assert_array_equal(gn, wn)
     np.testing.assert_array_equal(bits(np.where(gn, 0, got).astype(np.float32)), bits(np.where(wn, 0, want).astype(np.float32)))
-
-
-def ply_layout(full_sh=True):
-    """msplat_ply_layout of synthetic.write_ply's 62-float vertex"""
-    L = _capi.PlyLayout()
-    L.vertex_size = 62 * 4
-    L.x, L.y, L.z = 0, 4, 8
-    for i in range(3):
-        L.f_dc[i] = 24 + 4 * i
-    for i in range(45):
-        L.f_rest[i] = 36 + 4 * i
-    L.opacity = 216
-    for i in range(3):
-        L.scale[i] = 220 + 4 * i
-    for i in range(4):
-        L.rot[i] = 232 + 4 * i
-    return L
 
 
 def download(r, full_sh=True):
@@ -330,7 +291,7 @@ def test_storage_switches_on_one_context():
     for storage in ("fp32", "sh_fp16"):
         r = SplatRenderer(device=0, cloud_storage=storage)
         assert r.Init(aos, False, False), r.last_error()
-        fresh[storage] = frame(r, view)
+        fresh[storage] = sorted_frame(r, view)
         r.close()
     r = SplatRenderer(device=0)
     assert r.Init(aos, False, False), r.last_error()
@@ -341,8 +302,8 @@ def test_storage_switches_on_one_context():
         _capi.check(r._ctx, r._lib.msplat_set_cloud_storage(r._ctx, kind))
         _capi.check(r._ctx, r._lib.msplat_upload_cloud(r._ctx, aos.ctypes.data, n, 61 * 4, C.byref(off), 1))
         assert r.cloud_storage() == storage
-        f = frame(r, view)
-        assert_bit_identical(f["img"], fresh[storage]["img"])
+        f = sorted_frame(r, view)
+        same_bits(f["img"], fresh[storage]["img"])
         assert_same_lists(f, fresh[storage])
         seen.append(r.stats()["device_bytes"])
     assert seen[0] - seen[1] == n * 96, (seen, n)
@@ -353,20 +314,6 @@ def test_storage_switches_on_one_context():
 
 
 # ---- 5. magnitude --------------------------------------------------------------------------------------------------------
-def sh_basis_bounds():
-    """beta_k = max over unit v of |b_k(v)| for project_block's 16 basis functions (dense sphere sampling, 1e-3 margin)"""
-    th = np.linspace(0.0, np.pi, 1201)[:, None]
-    ph = np.linspace(0.0, 2 * np.pi, 2401)[None, :]
-    vx, vy, vz = np.sin(th) * np.cos(ph), np.sin(th) * np.sin(ph), np.cos(th) * np.ones_like(ph)
-    k1, k2, k3, k4 = 0.4886025119029199, 1.0925484305920792, 0.31539156525252005, 0.5462742152960396
-    k5, k6, k7, k8, k9 = 0.5900435899266435, 2.8906114426405543, 0.4570457994644658, 0.37317633259011546, 1.4453057213202771
-    b = [np.full_like(vx, 0.28209479177387814), -k1 * vy, k1 * vz, -k1 * vx,
-         k2 * vy * vx, -k2 * vy * vz, k3 * (3 * vz * vz - 1), -k2 * vx * vz, k4 * (vx * vx - vy * vy),
-         -k5 * vy * (3 * vx * vx - vy * vy), k6 * vy * vx * vz, -k7 * vy * (5 * vz * vz - 1), k8 * vz * (5 * vz * vz - 3),
-         -k7 * vx * (5 * vz * vz - 1), k9 * vz * (vx * vx - vy * vy), -k5 * vx * (vx * vx - 3 * vy * vy)]
-    return np.array([np.abs(x).max() for x in b]) * 1.001
-
-
 def colour_bound(aos):
     beta = sh_basis_bounds()
     d = np.abs(aos - round16(aos)).astype(np.float64)
@@ -389,7 +336,7 @@ def test_sh16_pixels_stay_within_the_sh_bound(cfg):
         for storage in ("sh_fp16", "fp32"):
             r = SplatRenderer(device=0, cloud_storage=storage)
             assert r.Init(aos, False, False), r.last_error()
-            imgs.append([frame(r, view)["img"]])
+            imgs.append([sorted_frame(r, view)["img"]])
             r.close()
     else:
         W, H = 2016, 2240
@@ -431,5 +378,5 @@ def test_point_clouds_ignore_the_storage_setting():
         assert r.cloud_storage() == "fp32"
         imgs.append((r.Render(*view), r.sorted_indices()))
         r.close()
-    assert_bit_identical(imgs[0][0], imgs[1][0])
+    same_bits(imgs[0][0], imgs[1][0])
     np.testing.assert_array_equal(imgs[0][1], imgs[1][1])

@@ -15,17 +15,15 @@ import pytest
 from splatapult_amd import SplatRenderer, _capi, camera, synthetic
 from splatapult_amd.renderer import SplatRendererGroup
 from tests import scenes
+from tests.checks import bits, same_bits
+from tests.gpu_harness import assert_same_lists, sorted_frame
+from tests.render_cases import AOS_OFF, ply_layout, sh_basis_bounds
 from tests.sh_q8_rule import PLY_OF_REST, REST, deq, special_rest
 
 pytestmark = pytest.mark.gpu
 
-AOS_OFF = (0, 16, 32, 48, 64, 76, 88, 100, 116, 132, 148, 164, 180, 196, 212, 228)
 KEEP = [c for c in range(61) if c not in REST]
 Q8 = _capi.STORAGE_SH_Q8
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint16 if a.dtype == np.float16 else np.uint32)
 
 
 def view(yaw=0.3):
@@ -47,26 +45,6 @@ def cloud(key):
     return _CLOUDS[key]
 
 
-def frame(r, v):
-    r.Sort(*v)
-    img = r.Render(*v)
-    st = r.stats()
-    return dict(img=img, keys=r.sorted_keys(), idx=r.sorted_indices(), V=r.sort_count(), drawn=st["drawn"], pairs=st["pairs"])
-
-
-def assert_same_lists(a, b):
-    assert a["V"] == b["V"]
-    np.testing.assert_array_equal(a["keys"], b["keys"])
-    np.testing.assert_array_equal(a["idx"], b["idx"])
-    assert (a["drawn"], a["pairs"]) == (b["drawn"], b["pairs"])
-
-
-def assert_bit_identical(a, b):
-    assert a.dtype == b.dtype and a.shape == b.shape
-    diff = bits(a) != bits(b)
-    assert not diff.any(), "%d of %d pixel words differ" % (int(diff.sum()), diff.size)
-
-
 def three_renders(key, v, make, prepare=None):
     """(SH_Q8 of C, FP32 of deq(C), FP32 of C) frames with renderers from make(cloud_storage=...)"""
     aos, d = cloud(key)
@@ -77,7 +55,7 @@ def three_renders(key, v, make, prepare=None):
         assert r.cloud_storage() == storage
         if prepare:
             prepare(r)
-        out.append(frame(r, v))
+        out.append(sorted_frame(r, v))
         r.close()
     return out
 
@@ -90,7 +68,7 @@ def test_q8_renders_the_fp32_frame_of_the_dequantised_cloud(key, spatial):
     assert fq["V"] > 1000
     if key == "small":
         assert fq["V"] % 64 != 0          # the last wave block of the projection is partly filled
-    assert_bit_identical(fq["img"], fd["img"])
+    same_bits(fq["img"], fd["img"])
     assert_same_lists(fq, f32)
     assert (bits(fq["img"]) != bits(f32["img"])).any()       # (the quantisation is visible: the frames can differ at all)
 
@@ -98,7 +76,7 @@ def test_q8_renders_the_fp32_frame_of_the_dequantised_cloud(key, spatial):
 def test_q8_bit_identity_on_an_rgba16f_target():
     fq, fd, f32 = three_renders("reordered", view(), lambda **kw: SplatRenderer(device=0, fb_format="fp16", **kw))
     assert fq["img"].dtype == np.float16 and fq["V"] > 1000
-    assert_bit_identical(fq["img"], fd["img"])
+    same_bits(fq["img"], fd["img"])
     assert_same_lists(fq, f32)
 
 
@@ -120,7 +98,7 @@ def test_q8_bit_identity_stereo_both_eyes():
         r.close()
     for eye in range(2):
         assert outs[0][eye].dtype == np.float16
-        assert_bit_identical(outs[0][eye], outs[1][eye])
+        same_bits(outs[0][eye], outs[1][eye])
 
 
 def test_q8_bit_identity_four_frames_in_flight():
@@ -142,7 +120,7 @@ def test_q8_bit_identity_four_frames_in_flight():
         r.close()
     for k in range(len(views)):
         assert frames["q8"][k][3] > 1000
-        assert_bit_identical(frames["q8"][k][0], frames["deq"][k][0])
+        same_bits(frames["q8"][k][0], frames["deq"][k][0])
         np.testing.assert_array_equal(frames["q8"][k][1], frames["c"][k][1])
         np.testing.assert_array_equal(frames["q8"][k][2], frames["c"][k][2])
 
@@ -152,7 +130,7 @@ def test_q8_bit_identity_banded_context():
         r.set_band_layout(1, 0, 3, 4, band_cull=True)       # blocks of 3 bin rows from row 1, every 4th block
     fq, fd, f32 = three_renders("reordered", view(), lambda **kw: SplatRenderer(device=0, **kw), prepare)
     assert fq["V"] > 1000
-    assert_bit_identical(fq["img"], fd["img"])
+    same_bits(fq["img"], fd["img"])
     assert_same_lists(fq, f32)
 
 
@@ -167,7 +145,7 @@ def test_q8_bit_identity_one_device_group():
         assert g.sort_count(0) > 1000
         imgs.append(g.Render(*view()))
         g.close()
-    assert_bit_identical(imgs[0], imgs[1])
+    same_bits(imgs[0], imgs[1])
 
 
 def test_q8_bit_identity_with_two_passes():
@@ -179,7 +157,7 @@ def test_q8_bit_identity_with_two_passes():
         r = SplatRenderer(device=0, two_pass=_capi.TWO_PASS_ON, cloud_storage=storage)
         assert r.Init(a, False, False), r.last_error()
         r.two_pass_state(0.15)            # pin the first pass's share
-        f = frame(r, view())
+        f = sorted_frame(r, view())
         f["tp"] = r.two_pass_info()
         out.append(f)
         r.close()
@@ -189,7 +167,7 @@ def test_q8_bit_identity_with_two_passes():
     assert 0 < fq["tp"]["splats_pass1"] < fq["V"], fq["tp"]
     assert fq["tp"] == f32["tp"]          # the passes split the frame like FP32 storage of C
     assert fq["V"] > 1000
-    assert_bit_identical(fq["img"], fd["img"])
+    same_bits(fq["img"], fd["img"])
     # (with two passes, drawn / pairs describe the second pass: they too must match the FP32 frame of C)
     assert_same_lists(fq, f32)
 
@@ -209,23 +187,6 @@ def special_attrs(n=4096):
         tail[k, k % 45] = vals[k // 45]
     a["f_rest"] = fr
     return a
-
-
-def ply_layout():
-    """msplat_ply_layout of synthetic.write_ply's 62-float vertex"""
-    L = _capi.PlyLayout()
-    L.vertex_size = 62 * 4
-    L.x, L.y, L.z = 0, 4, 8
-    for i in range(3):
-        L.f_dc[i] = 24 + 4 * i
-    for i in range(45):
-        L.f_rest[i] = 36 + 4 * i
-    L.opacity = 216
-    for i in range(3):
-        L.scale[i] = 220 + 4 * i
-    for i in range(4):
-        L.rot[i] = 232 + 4 * i
-    return L
 
 
 def assert_equal_records(got, want):
@@ -319,14 +280,14 @@ def test_q8_degree1_cloud_is_stored_fp32():
         r = SplatRenderer(device=0, cloud_storage=storage)
         assert r.Init(aos, False, False), r.last_error()
         assert r.cloud_storage() == "fp32"
-        f = frame(r, view())
+        f = sorted_frame(r, view())
         f["bytes"] = r.stats()["device_bytes"]
         f["dl"] = r.download_cloud(False)
         got.append(f)
         r.close()
     assert got[0]["V"] > 1000
     assert got[0]["bytes"] == got[1]["bytes"]
-    assert_bit_identical(got[0]["img"], got[1]["img"])
+    same_bits(got[0]["img"], got[1]["img"])
     assert_same_lists(got[0], got[1])
     np.testing.assert_array_equal(bits(got[0]["dl"]), bits(aos))
 
@@ -339,7 +300,7 @@ def test_storage_switches_on_one_context_through_q8():
     for storage in ("fp32", "sh_q8", "sh_fp16"):
         r = SplatRenderer(device=0, cloud_storage=storage)
         assert r.Init(aos, False, False), r.last_error()
-        fresh[storage] = frame(r, view())
+        fresh[storage] = sorted_frame(r, view())
         r.close()
     r = SplatRenderer(device=0)
     assert r.Init(aos, False, False), r.last_error()
@@ -349,8 +310,8 @@ def test_storage_switches_on_one_context_through_q8():
         _capi.check(r._ctx, r._lib.msplat_set_cloud_storage(r._ctx, _capi.CLOUD_STORAGE_NAMES[storage]))
         _capi.check(r._ctx, r._lib.msplat_upload_cloud(r._ctx, aos.ctypes.data, n, 61 * 4, C.byref(off), 1))
         assert r.cloud_storage() == storage
-        f = frame(r, view())
-        assert_bit_identical(f["img"], fresh[storage]["img"])
+        f = sorted_frame(r, view())
+        same_bits(f["img"], fresh[storage]["img"])
         assert_same_lists(f, fresh[storage])
         seen.setdefault(storage, []).append(r.stats()["device_bytes"])
     assert seen["fp32"][0] - seen["sh_q8"][0] == 128 * n, (seen, n)
@@ -376,24 +337,10 @@ def test_point_renderer_reports_fp32_with_kind_3():
         assert r.cloud_storage() == "fp32"
         imgs.append(r.Render(*v))
         r.close()
-    assert_bit_identical(imgs[0], imgs[1])
+    same_bits(imgs[0], imgs[1])
 
 
 # ---- 7. colour bound -----------------------------------------------------------------------------------------------------
-def sh_basis_bounds():
-    """beta_k = max over unit v of |b_k(v)| for project_block's 16 basis functions (dense sphere sampling, 1e-3 margin)"""
-    th = np.linspace(0.0, np.pi, 1201)[:, None]
-    ph = np.linspace(0.0, 2 * np.pi, 2401)[None, :]
-    vx, vy, vz = np.sin(th) * np.cos(ph), np.sin(th) * np.sin(ph), np.cos(th) * np.ones_like(ph)
-    k1, k2, k3, k4 = 0.4886025119029199, 1.0925484305920792, 0.31539156525252005, 0.5462742152960396
-    k5, k6, k7, k8, k9 = 0.5900435899266435, 2.8906114426405543, 0.4570457994644658, 0.37317633259011546, 1.4453057213202771
-    b = [np.full_like(vx, 0.28209479177387814), -k1 * vy, k1 * vz, -k1 * vx,
-         k2 * vy * vx, -k2 * vy * vz, k3 * (3 * vz * vz - 1), -k2 * vx * vz, k4 * (vx * vx - vy * vy),
-         -k5 * vy * (3 * vx * vx - vy * vy), k6 * vy * vx * vz, -k7 * vy * (5 * vz * vz - 1), k8 * vz * (5 * vz * vz - 3),
-         -k7 * vx * (5 * vz * vz - 1), k9 * vz * (vx * vx - vy * vy), -k5 * vx * (vx * vx - 3 * vy * vy)]
-    return np.array([np.abs(x).max() for x in b]) * 1.001
-
-
 def colour_bound(aos, d):
     """max over splats and channels of sum_k beta_k |c_k - deq(c)_k|: a pixel is a convex combination of splat colours (and
     the background), each of which moves by at most its own sum"""
@@ -415,7 +362,7 @@ def test_q8_pixels_stay_within_the_sh_bound():
     for storage in ("sh_q8", "fp32"):
         r = SplatRenderer(device=0, cloud_storage=storage)
         assert r.Init(aos, False, False), r.last_error()
-        f = frame(r, view())
+        f = sorted_frame(r, view())
         assert f["V"] > 1000
         imgs.append(f["img"].astype(np.float64))
         r.close()

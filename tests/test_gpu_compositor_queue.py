@@ -27,30 +27,17 @@ import pytest
 from oracle import oracle as orc
 from splatapult_amd import camera
 from tests import scenes
-from tests.test_gpu_parity import bin_px, check_image, make_renderer, oracle_frame, random_points
+from tests.checks import bits, check_image, same_bits
+from tests.gpu_harness import (MIN_POOL, QUEUE_SENTINEL as SENTINEL, Pitched, bin_edge, bin_px, device_frame, items_of, make_renderer, no_sentinel,
+                               oracle_frame, pools_of, stereo_frame, tap)
+from tests.render_cases import NP_DTYPES, random_points, smooth_sprite
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = -7.0
 # viewport -> why: 308 items = 288 on the XCD mapping + a 20-item tail, ragged right and top tiles; 128 items, no tail; 24 items: fewer
 # than 32 and than the minimum pool; 1144 items, the ragged case of test_compositor_both_targets_probe_and_work_counters
 VIEWPORTS = [(333, 211), (256, 128), (96, 64), (701, 397)]
 ORACLE_VIEWPORTS = [(333, 211), (701, 397)]
-MIN_POOL = 64                     # msplat_create raises a smaller compositor_waves to this
-
-
-def items_of(W, H, views=1):
-    T = bin_px()
-    return 4 * ((W + T - 1) // T) * ((H + T - 1) // T) * views
-
-
-def pools_of(items, short=False):
-    """64: the minimum; 100: no multiple of 32, the shards' static shares differ; items - 1: exactly one wave pulls once; 1280 (what
-    contexts with frames in flight use) where it is below the item count.  short: the 64 / 100 cases only"""
-    pools = [64, 100] if short else [64, 100, items - 1, 1280]
-    return [p for i, p in enumerate(pools) if i < 2 or MIN_POOL < p < items]
-
-
 @functools.lru_cache(maxsize=None)
 def the_cloud():
     return scenes.synth_cloud(30000, 7101, log_scale_mean=-3.0)      # long lists that vary a lot per tile
@@ -66,82 +53,11 @@ def oracle_of(W, H):
     return oracle_frame(the_cloud().as_array(), True, cam, proj, vp, nf)
 
 
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint16 if a.dtype == np.float16 else np.uint32)
-
-
-def same_bits(got, want, what=""):
-    assert got.dtype == want.dtype and got.shape == want.shape
-    diff = bits(got) != bits(want)
-    assert not diff.any(), "%s: %d value(s) differ, first at %s" % (what, diff.sum(), tuple(np.argwhere(diff)[0]))
-
-
-class Target:
-    """a device render target one bin wider and taller than the viewport (rows of `pitch` bytes), holding the sentinel or `fill`"""
-
-    def __init__(self, W, H, fmt="fp32", fill=None, plane=False):
-        import torch
-        T = bin_px()
-        self.W, self.H = W, H
-        dt = torch.float16 if fmt == "fp16" else torch.float32
-        dev = torch.device("cuda", 0)
-        shape = (H + T, W + T) if plane else (H + T, W + T, 4)
-        if fill is None:
-            self.t = torch.full(shape, SENTINEL, dtype=dt, device=dev)
-        else:
-            assert fill.shape == shape
-            self.t = torch.from_numpy(fill).to(device=dev, dtype=dt)
-        self.before = self.t.cpu().numpy().copy()               # (also: the fill has finished before the renderer's stream starts)
-        torch.cuda.synchronize()
-        self.ptr, self.pitch = self.t.data_ptr(), self.t.stride(0) * self.t.element_size()
-
-    def image(self):
-        """the viewport's pixels, after checking that the padding kept its bits"""
-        import torch
-        torch.cuda.synchronize()
-        a, H, W = self.t.cpu().numpy(), self.H, self.W
-        same_bits(a[H:], self.before[H:], "rows above the viewport")
-        same_bits(a[:H, W:], self.before[:H, W:], "columns right of the viewport")
-        return np.ascontiguousarray(a[:H, :W])
-
-
-def frame(r, view, fmt="fp32", fill=None, render_cam=None, depth=False):
-    """one Render of the latest Sort into a fresh device target (sentinel, or `fill`); with depth: (colour, plane)"""
-    cam, proj, vp, nf = view
-    tgt = Target(vp[2], vp[3], fmt, fill)
-    kw = {}
-    if depth:
-        zt = Target(vp[2], vp[3], plane=True)
-        kw = dict(depth_ptr=zt.ptr, depth_pitch_bytes=zt.pitch)
-    r.Render(cam if render_cam is None else render_cam, proj, vp, nf, out_ptr=tgt.ptr, pitch_bytes=tgt.pitch, **kw)
-    r.synchronize()
-    return (tgt.image(), zt.image()) if depth else tgt.image()
-
-
-def tap(r, pool, kind=0, items=None):
-    """checks what the library reports about the context's latest compositor launch against the schedule its pool (None: the default)
-    must give; True when the launch ran persistent waves (grid < items)"""
-    n, grid, ordered, k = r.compositor_launch()
-    assert k == kind, (k, kind)
-    if items is not None:
-        assert n == items, (n, items)
-    want = n if pool is None else min(n, max(pool, MIN_POOL))
-    assert grid == want, "items %d, pool %s: grid %d, expected %d" % (n, pool, grid, want)
-    persistent = grid < n
-    # persistent waves of the splat compositor walk the bins in storage order; everything else heaviest-first
-    assert ordered == (0 if kind == 0 and persistent else 1), (n, grid, ordered, k)
-    return persistent
-
-
 def random_target(W, H, fmt, seed):
     """a destination that is neither zero nor constant, in the target's format"""
     T = bin_px()
     a = np.random.default_rng(seed).random((H + T, W + T, 4), np.float32)
     return a.astype(np.float16) if fmt == "fp16" else a
-
-
-def no_sentinel(img):
-    assert not (img == SENTINEL).any(), "%d value(s) still hold the sentinel" % (img == SENTINEL).sum()
 
 
 # ------------------------------------------------------------------------------------------------
@@ -160,7 +76,7 @@ def test_every_pool_renders_the_own_wave_frame(W, H):
     want = []
     for v in views:
         base.Sort(*v)
-        want.append(frame(base, v))
+        want.append(device_frame(base, v, None, None, call=base.Render, **bin_edge()))
         assert not tap(base, None, items=items)
         no_sentinel(want[-1])
         assert (want[-1][..., :3] != 0).any()
@@ -169,14 +85,14 @@ def test_every_pool_renders_the_own_wave_frame(W, H):
         r = make_renderer(cloud, compositor_waves=pool)
         r.Sort(*views[0])
         for rep in range(3):
-            img = frame(r, views[0])
+            img = device_frame(r, views[0], None, None, call=r.Render, **bin_edge())
             assert tap(r, pool, items=items) == (items > MIN_POOL)
             same_bits(img, want[0], "%dx%d pool %d frame %d" % (W, H, pool, rep))
         if pool == 64 and (W, H) in ORACLE_VIEWPORTS:
             ref = oracle_of(W, H)
             check_image(img, ref["image"], budget=ref["budget"])
         r.Sort(*views[1])
-        img = frame(r, views[1])
+        img = device_frame(r, views[1], None, None, call=r.Render, **bin_edge())
         assert tap(r, pool, items=items) == (items > MIN_POOL)
         same_bits(img, want[1], "%dx%d pool %d after a new Sort" % (W, H, pool))
         assert r.verify_order() == (0, 0)
@@ -191,11 +107,11 @@ def test_target_formats_and_modes_on_a_short_pool(fmt, mode):
     cloud = the_cloud()
     for W, H in VIEWPORTS:
         items, v = items_of(W, H), view_of(W, H)
-        fill = random_target(W, H, fmt, 11 * W + H) if mode == "load" else None
+        fill = random_target(W, H, fmt, 11 * W + H) if mode == "load" else SENTINEL
         base = make_renderer(cloud, fb_format=fmt)
         base.set_target_mode(mode)
         base.Sort(*v)
-        want = frame(base, v, fmt, fill)
+        want = device_frame(base, v, None, None, call=base.Render, **bin_edge(fill=fill, dtype=NP_DTYPES[fmt]))
         assert not tap(base, None, items=items)
         no_sentinel(want)
         if mode == "load":
@@ -205,7 +121,7 @@ def test_target_formats_and_modes_on_a_short_pool(fmt, mode):
             r.set_target_mode(mode)
             r.Sort(*v)
             for rep in range(2):
-                img = frame(r, v, fmt, fill)
+                img = device_frame(r, v, None, None, call=r.Render, **bin_edge(fill=fill, dtype=NP_DTYPES[fmt]))
                 assert tap(r, pool, items=items) == (items > MIN_POOL)
                 same_bits(img, want, "%s %s %dx%d pool %d frame %d" % (fmt, mode, W, H, pool, rep))
             r.close()
@@ -219,7 +135,7 @@ def test_depth_output_on_a_short_pool():
         items, v = items_of(W, H), view_of(W, H)
         base = make_renderer(cloud)
         base.Sort(*v)
-        want, zwant = frame(base, v, depth=True)
+        want, zwant = device_frame(base, v, None, None, call=base.Render, depth=True, **bin_edge())
         assert not tap(base, None, items=items)
         no_sentinel(want)
         no_sentinel(zwant)
@@ -228,7 +144,7 @@ def test_depth_output_on_a_short_pool():
             r = make_renderer(cloud, compositor_waves=pool)
             r.Sort(*v)
             for rep in range(2):
-                img, z = frame(r, v, depth=True)
+                img, z = device_frame(r, v, None, None, call=r.Render, depth=True, **bin_edge())
                 assert tap(r, pool, items=items) == (items > MIN_POOL)
                 same_bits(img, want, "colour %dx%d pool %d frame %d" % (W, H, pool, rep))
                 same_bits(z, zwant, "depth plane %dx%d pool %d frame %d" % (W, H, pool, rep))
@@ -248,7 +164,7 @@ def test_both_eyes_in_one_chain_on_a_short_pool():
         base.Sort(eyes[0], proj, vp, nf)
         want = []
         for e in range(2):
-            want.append(frame(base, (eyes[0], proj, vp, nf), render_cam=eyes[e]))
+            want.append(device_frame(base, (eyes[0], proj, vp, nf), None, None, call=base.Render, render_cam=eyes[e], **bin_edge()))
             assert not tap(base, None, items=items // 2)
             no_sentinel(want[-1])
         assert not np.array_equal(want[0], want[1])
@@ -256,12 +172,10 @@ def test_both_eyes_in_one_chain_on_a_short_pool():
             r = make_renderer(cloud, compositor_waves=pool)
             r.Sort(eyes[0], proj, vp, nf)
             for rep in range(2):
-                tg = [Target(W, H), Target(W, H)]
-                r.RenderStereo(eyes, [proj, proj], vp, nf, out_ptrs=[t.ptr for t in tg], pitch_bytes=tg[0].pitch)
-                r.synchronize()
+                imgs = stereo_frame(r, eyes, [proj, proj], vp, nf, None, None, call=r.RenderStereo, **bin_edge())
                 assert tap(r, pool, items=items) == (items > MIN_POOL)
                 for e in range(2):
-                    same_bits(tg[e].image(), want[e], "%dx%d pool %d frame %d eye %d" % (W, H, pool, rep, e))
+                    same_bits(imgs[e], want[e], "%dx%d pool %d frame %d eye %d" % (W, H, pool, rep, e))
             r.close()
         base.close()
 
@@ -277,7 +191,7 @@ def test_row_bands_on_a_short_pool():
         rows_full, tiles_x = (H + T - 1) // T, (W + T - 1) // T
         base = make_renderer(cloud)
         base.Sort(*v)
-        want = frame(base, v)
+        want = device_frame(base, v, None, None, call=base.Render, **bin_edge())
         assert not tap(base, None, items=items_of(W, H))
         for pool in pools_of(items_of(W, H), short=True):
             got = np.full_like(want, SENTINEL)
@@ -287,7 +201,7 @@ def test_row_bands_on_a_short_pool():
                 lay = r.set_band_plan("block", rows_full, 3, g, block_rows=2)
                 mine = _capi.band_rows(*lay, rows_full=rows_full)
                 r.Sort(*v)
-                part = frame(r, v)
+                part = device_frame(r, v, None, None, call=r.Render, **bin_edge())
                 rows = np.isin(np.arange(H) // T, mine)
                 assert (part[~rows] == SENTINEL).all()               # a rank writes its own rows only
                 got[rows] = part[rows]
@@ -310,7 +224,7 @@ def test_two_pass_frames_on_a_short_pool(share):
         items, v = items_of(W, H), view_of(W, H)
         base = make_renderer(cloud)
         base.Sort(*v)
-        want = frame(base, v)
+        want = device_frame(base, v, None, None, call=base.Render, **bin_edge())
         assert not tap(base, None, items=items)
         assert base.two_pass_state()[0] == 0
         for pool in pools_of(items, short=True):
@@ -318,7 +232,7 @@ def test_two_pass_frames_on_a_short_pool(share):
             r.two_pass_state(share)
             r.Sort(*v)
             for rep in range(2):
-                img = frame(r, v)
+                img = device_frame(r, v, None, None, call=r.Render, **bin_edge())
                 assert tap(r, pool, items=items) == (items > MIN_POOL)
                 same_bits(img, want, "share %g %dx%d pool %d frame %d" % (share, W, H, pool, rep))
             assert r.two_pass_state()[0] > 0                         # both OCC passes ran on the short pool
@@ -336,18 +250,18 @@ def test_frames_in_flight_with_an_explicit_small_pool():
         want = []
         for v in views:
             base.Sort(*v)
-            want.append(frame(base, v))
+            want.append(device_frame(base, v, None, None, call=base.Render, **bin_edge()))
             assert not tap(base, None, items=items)
         for pool in pools_of(items, short=True):
             r = make_renderer(cloud, frames_in_flight=3, compositor_waves=pool)
-            tg = [Target(W, H) for _ in views]
+            tg = [Pitched(H, W, np.float32, SENTINEL, pad=bin_px(), rows=bin_px()) for _ in views]
             for k, (cam, proj, vp, nf) in enumerate(views):
                 r.Sort(cam, proj, vp, nf)
                 r.Render(cam, proj, vp, nf, out_ptr=tg[k].ptr, pitch_bytes=tg[k].pitch)
             r.synchronize()
             assert tap(r, pool, items=items) == (items > MIN_POOL)
             for k in range(len(views)):
-                same_bits(tg[k].image(), want[k], "%dx%d pool %d frame %d" % (W, H, pool, k))
+                same_bits(tg[k].read("frame %d" % k), want[k], "%dx%d pool %d frame %d" % (W, H, pool, k))
             r.close()
         base.close()
 
@@ -377,9 +291,9 @@ def test_probe_counts_the_same_work_on_a_short_pool():
         for pool in (None, 64):
             r = make_renderer(cloud, compositor_waves=pool)
             r.Sort(*v)
-            img = frame(r, v)
+            img = device_frame(r, v, None, None, call=r.Render, **bin_edge())
             r.set_tile_probe(True)
-            same_bits(frame(r, v), img, "%dx%d pool %s: the probe changed pixels" % (W, H, pool))
+            same_bits(device_frame(r, v, None, None, call=r.Render, **bin_edge()), img, "%dx%d pool %s: the probe changed pixels" % (W, H, pool))
             persistent = tap(r, pool, items=items)
             assert persistent == (pool is not None and items > MIN_POOL)
             work[pool] = (r.composite_work(), img)
@@ -418,7 +332,7 @@ def test_draw_order_compositor_on_a_short_pool(depth_bits, rop, mode):
         cam, proj, vp, nf = view_of(W, H)
         v = (cam, proj, vp, nf)
         eye1 = camera.translate_local(cam, dx=0.064)
-        fill = random_target(W, H, "fp32", 13 * W + H) if mode == "load" else None
+        fill = random_target(W, H, "fp32", 13 * W + H) if mode == "load" else SENTINEL
         want = None
         for pool in (None, 64):
             r = make_renderer(cloud, compositor_waves=pool)
@@ -427,7 +341,7 @@ def test_draw_order_compositor_on_a_short_pool(depth_bits, rop, mode):
             r.set_target_mode(mode)
             r.Sort(*v)
             for rep in range(2):
-                img = frame(r, v, fill=fill, render_cam=eye1)
+                img = device_frame(r, v, None, None, call=r.Render, render_cam=eye1, **bin_edge(fill=fill))
                 assert tap(r, pool, kind=1, items=items) == (pool is not None)
                 no_sentinel(img)
                 if want is None:
@@ -441,7 +355,6 @@ def test_point_compositor_on_a_short_pool():
     """the scene of test_point_renderer_matches_oracle (srgb off, z = 5) with and without the depth test, pool 64 against the default
     pool; the depth-tested pool-64 frame also against the oracle with that test's tolerance"""
     from splatapult_amd import PointRenderer
-    from tests.test_points import smooth_sprite
     pts = random_points(6000, 111)
     tex = smooth_sprite(64, 48, seed=2)
     W, H = 640, 360
@@ -454,7 +367,7 @@ def test_point_compositor_on_a_short_pool():
             assert r.Init(pts, False, sprite=tex), r.last_error()
             r.set_depth_test(depth_bits)
             for rep in range(2):
-                img = frame(r, v)                                    # (PointRenderer.Render sorts, then draws)
+                img = device_frame(r, v, None, None, call=r.Render, **bin_edge())      # (PointRenderer.Render sorts, then draws)
                 assert tap(r, pool, kind=2, items=items) == (pool is not None)
                 no_sentinel(img)
                 if want is None:
@@ -485,13 +398,13 @@ def test_timed_context_renders_the_same_pixels_and_reports_its_stages(pool):
     items, v = items_of(W, H), view_of(W, H)
     base = make_renderer(cloud)
     base.Sort(*v)
-    want = frame(base, v)
+    want = device_frame(base, v, None, None, call=base.Render, **bin_edge())
     assert not tap(base, None, items=items)
     base.close()
     r = make_renderer(cloud, enable_timing=True, compositor_waves=pool)
     for rep in range(3):
         r.Sort(*v)
-        img = frame(r, v)
+        img = device_frame(r, v, None, None, call=r.Render, **bin_edge())
         assert tap(r, pool, items=items) == (pool is not None)
         same_bits(img, want, "timed context, pool %s, frame %d" % (pool, rep))
     t = _capi.Timings()

@@ -3,84 +3,26 @@
     depth = sum_i T_i w_i z_i + T * 1.0,      z_i = 0.5 ndc.z + 0.5 (window depth),  T = the transmittance where the walk stopped
 
 -- the splats' expected window depth blended over GL's clear depth 1.0: MSPLAT_TARGET_LOAD's formula with colour z and dst = 1.
-Checked here: identities that need no oracle (bit for bit), the unchanged oracle (tests/test_depth_output.py: depth_layers, pinned
-there by a numpy restatement), every execution shape against the plain single-pass depth frame (bit for bit), and the refusals.
+Checked here: identities that need no oracle (bit for bit), the unchanged oracle (tests/render_cases.depth_layers, pinned by a
+numpy restatement in tests/test_depth_output.py), every execution shape against the plain single-pass depth frame (bit for bit),
+and the refusals.
 
-Tolerance against the oracle, derived as tests/test_gpu_target_mode.py derives LOAD's with |dst| = 1: both oracle frames (D_ref, the
-splats coloured with z_w <= 1, and the white frame 1 - T_ref) carry the suite's TIGHT bound, and early termination leaves T below
-t_eps instead of at its limit, so  |err| <= 2 TIGHT + t_eps;  check_image's frac / mean conditions are scaled the same way, and a
-pixel above the bound has to be explained by the threshold-flip budgets of BOTH frames (budget_D + budget_white * 1)."""
-import functools
-
+Tolerance against the oracle (tests/checks.check_plane), derived as tests/test_gpu_target_mode.py derives LOAD's with |dst| = 1:
+both oracle frames (D_ref, the splats coloured with z_w <= 1, and the white frame 1 - T_ref) carry the suite's TIGHT bound, and
+early termination leaves T below t_eps instead of at its limit, so  |err| <= 2 TIGHT + t_eps;  check_image's frac / mean
+conditions are scaled the same way, and a pixel above the bound has to be explained by the threshold-flip budgets of BOTH frames
+(budget_D + budget_white * 1)."""
 import numpy as np
 import pytest
 
 from oracle import oracle as orc
-from splatapult_amd import MsplatError, _capi, camera
+from splatapult_amd import MsplatError, _capi
 from tests import scenes
-from tests.test_depth_output import depth_layers
-from tests.test_gpu_parity import TIGHT, make_renderer
-from tests.test_gpu_target_mode import SENTINEL, T_EPS, random_dst, render_host, scene, view_of
+from tests.checks import T_EPS, TIGHT, assert_is_a_plane, check_plane
+from tests.gpu_harness import SENTINEL, device_frame, host_frame, make_renderer
+from tests.render_cases import MODES, case, depth_layers, junk_plane, oracle_plane, random_dst, scene, view_of
 
 pytestmark = pytest.mark.gpu
-
-MODES = ("clear", "load", "premultiplied")
-
-
-def spread_view():
-    """the "hard" scene between near / far planes that hug it: z_w of what the pixels see runs from the near cull (0.625) to the
-    far plane instead of crowding towards 1 (chosen on the CPU with the oracle; test_depth_matches_the_oracle asserts the spread)"""
-    cloud, W, H, _ = scene("hard")
-    zn, zf = 5.02, 6.33
-    return cloud, W, H, (camera.pose((0.0, 0.0, 5.75), 0.524, 0.037), camera.perspective(camera.FOVY, W / H, zn, zf), [0, 0, W, H], [zn, zf])
-
-
-def case(name):
-    return spread_view() if name == "spread" else view_of(name)
-
-
-def render_depth_host(r, view, mode="clear", dst=None, plane=None):
-    """one host-output Render with a depth plane in `mode`: (image, plane); dst: what the colour array holds before"""
-    cam, proj, vp, nf = view
-    r.set_target_mode(mode)
-    out = None if dst is None else np.ascontiguousarray(dst).copy()
-    img, z = r.Render(cam, proj, vp, nf, out=out, depth=True if plane is None else plane)
-    assert z.dtype == np.float32 and z.shape == img.shape[:2]
-    return img, z
-
-
-def render_depth_device(r, view, mode, dst, pad=24, zpad=8, zfill=None):
-    """one device-output Render into pitched targets: (image, plane), both paddings checked against the sentinel they start as;
-    zfill: what the plane's pixels hold before (default: the sentinel too)"""
-    import torch
-    cam, proj, vp, nf = view
-    H, W = dst.shape[:2]
-    tdt = torch.float16 if dst.dtype == np.float16 else torch.float32
-    fb = torch.full((H, W + pad, 4), SENTINEL, dtype=tdt, device="cuda:0")
-    fb[:, :W] = torch.from_numpy(np.ascontiguousarray(dst)).to("cuda:0")
-    zb = torch.full((H, W + zpad), SENTINEL, dtype=torch.float32, device="cuda:0")
-    if zfill is not None:
-        zb[:, :W] = torch.from_numpy(np.ascontiguousarray(zfill)).to("cuda:0")
-    torch.cuda.synchronize()
-    r.set_target_mode(mode)
-    r.Render(cam, proj, vp, nf, out_ptr=fb.data_ptr(), pitch_bytes=(W + pad) * 4 * fb.element_size(), depth_ptr=zb.data_ptr(),
-             depth_pitch_bytes=(W + zpad) * 4)
-    r.synchronize()
-    got, z = fb.cpu().numpy(), zb.cpu().numpy()
-    assert (got[:, W:] == SENTINEL).all() and (z[:, W:] == SENTINEL).all(), "mode %s wrote into the padding of a pitched target" % mode
-    return got[:, :W].copy(), z[:, :W].copy()
-
-
-def junk_plane(H, W, seed):
-    """what a caller's plane may hold: NaN, infinities, huge and negative values"""
-    z = (np.random.default_rng(seed).standard_normal((H, W)) * 1e6).astype(np.float32)
-    z[::2, ::3] = np.nan
-    z[1::4, 1::5] = np.inf
-    return z
-
-
-def assert_is_a_plane(z):
-    assert np.isfinite(z).all() and (z >= 0.0).all() and (z <= 1.0).all(), (np.nanmin(z), np.nanmax(z))
 
 
 # ------------------------------------------------------------------------------------------------
@@ -97,18 +39,18 @@ def test_identities(name, fmt):
     dst = random_dst(H, W, 5, dt)
     planes = []
     for mode in MODES:
-        plain = render_host(r, view, mode, dst)
-        img, z = render_depth_host(r, view, mode, dst, plane=junk_plane(H, W, 6))
+        plain = host_frame(r, view, mode, dst, call=r.Render)
+        img, z = host_frame(r, view, mode, dst, call=r.Render, depth=junk_plane(H, W, 6))
         np.testing.assert_array_equal(img, plain, err_msg="%s: the colour of a depth frame differs from msplat_render's" % mode)
         assert_is_a_plane(z)                                 # ... and nothing of the junk is left
-        dimg, dz = render_depth_device(r, view, mode, dst, zfill=junk_plane(H, W, 7))
+        dimg, dz = device_frame(r, view, mode, dst, call=r.Render, depth=True, dpad=8, zfill=junk_plane(H, W, 7))
         np.testing.assert_array_equal(dimg, plain)
         np.testing.assert_array_equal(dz, z, err_msg="%s: device output differs from host output" % mode)
-        np.testing.assert_array_equal(render_host(r, view, mode, dst), plain)      # and a plain Render after it is still the plain Render
+        np.testing.assert_array_equal(host_frame(r, view, mode, dst, call=r.Render), plain)      # and a plain Render after it is still the plain Render
         planes.append(z)
     np.testing.assert_array_equal(planes[1], planes[0], err_msg="the plane depends on the target mode")
     np.testing.assert_array_equal(planes[2], planes[0], err_msg="the plane depends on the target mode")
-    pre = render_host(r, view, "premultiplied")
+    pre = host_frame(r, view, "premultiplied", call=r.Render)
     empty = pre[..., 3] == 0
     assert (planes[0][empty] == 1.0).all(), "a pixel no splat reaches must read exactly 1.0"
     assert empty.mean() >= 0.01 or name != "sparse"           # the sparse scene has such pixels
@@ -118,31 +60,6 @@ def test_identities(name, fmt):
 # ------------------------------------------------------------------------------------------------
 # 2. against the unchanged oracle
 # ------------------------------------------------------------------------------------------------
-
-@functools.lru_cache(maxsize=None)
-def oracle_plane(name):
-    cloud, W, H, (cam, proj, vp, nf) = case(name)
-    ref = orc.render_frame(cloud.as_array(), True, cam, proj, vp, nf, nthreads=16, want_image=False, want_splats=True)
-    L = dict(depth_layers(ref["splats"], W, H, nthreads=16))
-    L["V"] = ref["V"]
-    L["visible"] = ref["splats"]["reject"] == 0
-    return L
-
-
-def check_plane(z, L, t_eps, max_abs=TIGHT, mean_abs=1e-4, frac=0.999, tol=1e-4):
-    """z against D_ref + T_ref: check_over of tests/test_gpu_target_mode.py with |dst| = 1"""
-    err = np.abs(z.astype(np.float64) - L["plane"])
-    print("check_plane: max |err| %.3g, mean %.3g, t_eps %g" % (err.max(), err.mean(), t_eps))
-    within = (err <= tol * 2.0 + t_eps).mean()
-    assert within >= frac, "only %.5f of values within the scaled %g (max %.3g)" % (within, tol, err.max())
-    assert err.mean() <= mean_abs * 2.0 + t_eps, "mean |err| %.3g" % err.mean()
-    bound = max_abs * 2.0 + t_eps
-    over = err > bound
-    if over.any():
-        bad = over & (err > bound + L["bud_d"] + L["bud_w"])
-        assert not bad.any(), "%d value(s) above the bound not explained by a w ~ 1/256 flip (max %.3g)" % (bad.sum(), err[bad].max())
-        print("check_plane: %d value(s) above the bound, all within the two frames' threshold-flip budgets" % over.sum())
-
 
 @pytest.mark.parametrize("t_eps", [-1.0, 0.0])
 @pytest.mark.parametrize("name", ["sparse", "dense", "spread"])
@@ -159,7 +76,7 @@ def test_depth_matches_the_oracle(name, t_eps):
     r = make_renderer(cloud, t_epsilon=t_eps)
     r.Sort(*view)
     assert r.sort_count() == L["V"]
-    img, z = render_depth_host(r, view)
+    img, z = host_frame(r, view, "clear", call=r.Render, depth=True)
     assert_is_a_plane(z)
     check_plane(z, L, T_EPS if t_eps < 0 else t_eps)
     assert (z[L["cover"] == 0.0] == 1.0).all()
@@ -184,11 +101,11 @@ def test_two_pass_frames_equal_the_single_pass(share):
         a.Sort(*view); b.Sort(*view)
         dst = random_dst(H, W, 21)
         for mode in ("clear", "load"):
-            ia, za = render_depth_host(a, view, mode, dst)
-            ib, zb = render_depth_host(b, view, mode, dst, plane=junk_plane(H, W, 22))
+            ia, za = host_frame(a, view, mode, dst, call=a.Render, depth=True)
+            ib, zb = host_frame(b, view, mode, dst, call=b.Render, depth=junk_plane(H, W, 22))
             np.testing.assert_array_equal(ib, ia)
             np.testing.assert_array_equal(zb, za, err_msg="%s %s share %g" % (name, mode, share))
-            np.testing.assert_array_equal(ia, render_host(a, view, mode, dst))
+            np.testing.assert_array_equal(ia, host_frame(a, view, mode, dst, call=a.Render))
         assert b.two_pass_state(share)[0] == 2 and a.two_pass_state()[0] == 0
         info = b.two_pass_info()
         print("two-pass, %s share %g: %s" % (name, share, info))
@@ -202,8 +119,8 @@ def test_fp16_two_pass_device_output():
     a.Sort(*view); b.Sort(*view)
     dst = random_dst(H, W, 23, np.float16)
     for mode in MODES:
-        ia, za = render_depth_device(a, view, mode, dst)
-        ib, zb = render_depth_device(b, view, mode, dst)
+        ia, za = device_frame(a, view, mode, dst, call=a.Render, depth=True, dpad=8)
+        ib, zb = device_frame(b, view, mode, dst, call=b.Render, depth=True, dpad=8)
         np.testing.assert_array_equal(ib, ia)
         np.testing.assert_array_equal(zb, za)
     assert b.two_pass_state(0.2)[0] == 3
@@ -216,10 +133,10 @@ def test_a_viewport_smaller_than_a_bin():
     r = make_renderer(cloud)
     r.Sort(*view)
     plain = r.Render(*view)
-    img, z = render_depth_host(r, view, plane=junk_plane(H, W, 31))
+    img, z = host_frame(r, view, "clear", call=r.Render, depth=junk_plane(H, W, 31))
     np.testing.assert_array_equal(img, plain)
     assert_is_a_plane(z)
-    dimg, dz = render_depth_device(r, view, "clear", np.zeros((H, W, 4), np.float32))
+    dimg, dz = device_frame(r, view, "clear", np.zeros((H, W, 4), np.float32), call=r.Render, depth=True, dpad=8)
     np.testing.assert_array_equal(dimg, plain)
     np.testing.assert_array_equal(dz, z)
     ref = orc.render_frame(cloud.as_array(), True, cam, proj, vp, nf, nthreads=4, want_image=False, want_splats=True)
@@ -233,7 +150,8 @@ def test_a_frame_with_nothing_visible_is_all_ones():
     r.Sort(*view)
     assert r.sort_count() == 0
     plain = r.Render(*view)
-    for got in (render_depth_host(r, view, plane=junk_plane(H, W, 32)), render_depth_device(r, view, "clear", random_dst(H, W, 33))):
+    for got in (host_frame(r, view, "clear", call=r.Render, depth=junk_plane(H, W, 32)),
+                device_frame(r, view, "clear", random_dst(H, W, 33), call=r.Render, depth=True, dpad=8)):
         np.testing.assert_array_equal(got[0], plain)
         assert (got[1] == 1.0).all()
 
@@ -253,9 +171,10 @@ def test_a_banded_context_writes_its_own_rows_only():
     band.Sort(*view)
     dst = random_dst(H, W, 51)
     for mode in ("clear", "load"):
-        want_img, want_z = render_depth_host(plain, view, mode, dst)
+        want_img, want_z = host_frame(plain, view, mode, dst, call=plain.Render, depth=True)
         sentinel = np.full((H, W), SENTINEL, np.float32)
-        for img, z in (render_depth_host(band, view, mode, dst, plane=sentinel.copy()), render_depth_device(band, view, mode, dst)):
+        for img, z in (host_frame(band, view, mode, dst, call=band.Render, depth=sentinel.copy()),
+                       device_frame(band, view, mode, dst, call=band.Render, depth=True, dpad=8)):
             np.testing.assert_array_equal(img[owned], want_img[owned])
             np.testing.assert_array_equal(z[owned], want_z[owned])
             assert (z[~owned] == SENTINEL).all(), "mode %s: the depth plane's rows of another band were touched" % mode
@@ -278,7 +197,7 @@ def test_frames_in_flight_and_queued_calls_equal_one_context(shape):
     fly.synchronize()
     for k, view in enumerate(views):
         one.Sort(*view)
-        img, z = render_depth_host(one, view)
+        img, z = host_frame(one, view, "clear", call=one.Render, depth=True)
         np.testing.assert_array_equal(fbs[k].cpu().numpy(), img, err_msg="frame %d" % k)
         np.testing.assert_array_equal(zbs[k].cpu().numpy(), z, err_msg="frame %d" % k)
 
@@ -291,12 +210,12 @@ def test_host_output_survives_a_pair_buffer_overflow():
     view = scenes.default_view(W, H, z=4.0)
     r = make_renderer(cloud)                                # automatic capacity
     r.Sort(*view)
-    img, z = render_depth_host(r, view, plane=junk_plane(H, W, 71))      # the context's first render
+    img, z = host_frame(r, view, "clear", call=r.Render, depth=junk_plane(H, W, 71))      # the context's first render
     st = r.stats()
     assert st["pairs"] > (1 << 22) and st["pair_capacity"] >= st["pairs"], st      # it did overflow, and grew
     calm = make_renderer(cloud, pair_capacity=int(st["pairs"]) + 4096)               # never overflows
     calm.Sort(*view)
-    cimg, cz = render_depth_host(calm, view)
+    cimg, cz = host_frame(calm, view, "clear", call=calm.Render, depth=True)
     np.testing.assert_array_equal(img, cimg)
     np.testing.assert_array_equal(z, cz)
     assert_is_a_plane(z)
@@ -312,7 +231,7 @@ def test_refused_combinations_say_why_and_leave_the_context_usable():
     r = make_renderer(cloud)
     r.Sort(*view)
     plain = r.Render(*view)
-    want_z = render_depth_host(r, view)[1]
+    want_z = host_frame(r, view, "clear", call=r.Render, depth=True)[1]
     switches = [("msplat_set_depth_test", lambda on: r.set_depth_test(24 if on else 0)),
                 ("msplat_set_target_emulation", lambda on: r.set_target_emulation("rgba8" if on else None)),
                 ("probe", lambda on: r.set_tile_probe(on))]
@@ -325,7 +244,7 @@ def test_refused_combinations_say_why_and_leave_the_context_usable():
         assert (z == SENTINEL).all()
         r.Render(*view)                                     # the plain Render of that configuration still works
         switch(False)
-        img, z = render_depth_host(r, view)
+        img, z = host_frame(r, view, "clear", call=r.Render, depth=True)
         np.testing.assert_array_equal(img, plain)
         np.testing.assert_array_equal(z, want_z)
     # a bad pitch

@@ -12,7 +12,8 @@ import pytest
 
 from splatapult_amd import SplatRenderer, _capi, synthetic
 from tests import scenes
-from tests.test_gpu_cloud_storage import ply_layout
+from tests.checks import same_bits
+from tests.render_cases import ply_layout
 
 pytestmark = pytest.mark.gpu
 
@@ -35,10 +36,6 @@ def ptr(t):
 
 def u32(a):
     return np.ascontiguousarray(a).view(np.uint32)
-
-
-def same(a, b, msg):
-    assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes(), msg
 
 
 @functools.lru_cache(maxsize=None)
@@ -115,7 +112,7 @@ def observe(r, full_sh, view=VIEW):
 def same_observations(a, b, msg):
     assert a["storage"] == b["storage"], msg
     for k in ("cloud", "keys", "indices", "frame"):
-        same(a[k], b[k], "%s: %s differs" % (msg, k))
+        same_bits(a[k], b[k], "%s: %s differs" % (msg, k))
 
 
 # ---- 1. records, device against host ----------------------------------------------------------------------------------------
@@ -134,7 +131,7 @@ def test_device_records_equal_host_records(full_sh, storage, kind):
         assert n < 1000 or len(a["keys"]) > n // 2
         same_observations(a, b, "n = %d" % n)
         if storage == "fp32" and n:
-            same(a["cloud"], u32(cloud_array(bool(full_sh))[:n]), "the FP32 download is the upload, bit for bit")
+            same_bits(a["cloud"], u32(cloud_array(bool(full_sh))[:n]), "the FP32 download is the upload, bit for bit")
     host.close(), devr.close()
 
 
@@ -154,11 +151,11 @@ def test_spatial_order_and_band_cull_are_equal_between_the_routes(storage):
         r.Sort(*VIEW)
         seen.append((order, got, r.sort_count(), r.sorted_indices()))
         r.close()
-    same(seen[0][0], seen[1][0], "msplat_get_storage_order differs")
+    same_bits(seen[0][0], seen[1][0], "msplat_get_storage_order differs")
     same_observations(seen[0][1], seen[1][1], "spatial order on")
     assert 0 < seen[0][2] < len(seen[0][1]["keys"]), "the band cull dropped nothing: it observes no footprint bound here"
     assert seen[0][2] == seen[1][2], "sort_count under the band cull differs: %d host, %d device" % (seen[0][2], seen[1][2])
-    same(seen[0][3], seen[1][3], "the band's sorted indices differ")
+    same_bits(seen[0][3], seen[1][3], "the band's sorted indices differ")
 
 
 def test_frames_in_flight_render_the_host_route_frame():
@@ -179,7 +176,7 @@ def test_frames_in_flight_render_the_host_route_frame():
         fly.Render(*VIEW, out_ptr=fbs[k].data_ptr(), pitch_bytes=256 * 16)
     fly.synchronize()
     for k in range(2):
-        same(u32(fbs[k].cpu().numpy()), want, "context %d" % k)
+        same_bits(u32(fbs[k].cpu().numpy()), want, "context %d" % k)
     fly.close(), one.close()
 
 
@@ -397,7 +394,7 @@ def test_refusals_come_before_any_read():
     # none of them left a cloud, and the context is usable
     assert lib.msplat_sort(h, *r._args.load(*VIEW)) == _capi.ERR_NO_CLOUD
     assert upload_records(r, pack_records(cloud_array(True)[:1000], stride, off), off, 1, True) == _capi.OK, r.last_error()
-    same(observe(r, True)["frame"], good_frame(), "the upload after the refusals")
+    same_bits(observe(r, True)["frame"], good_frame(), "the upload after the refusals")
     r.close()
 
 
@@ -411,7 +408,7 @@ def test_the_source_may_be_overwritten_and_freed_on_return():
     r._n = 1000
     t.view(-1)[:] = 0xFF            # every float a NaN
     del t
-    same(observe(r, True)["frame"], good_frame(), "the frame after the source was overwritten and dropped")
+    same_bits(observe(r, True)["frame"], good_frame(), "the frame after the source was overwritten and dropped")
     r.close()
 
 
@@ -437,7 +434,7 @@ def test_the_viewer_loop_updates_one_renderer_in_place():
         assert ok, r.last_error()
         del t
         r.Sort(*VIEW)
-        same(u32(r.Render(*VIEW)), host_frame_of(a, n), "update %d (n = %d)" % (step, n))
+        same_bits(u32(r.Render(*VIEW)), host_frame_of(a, n), "update %d (n = %d)" % (step, n))
         bytes_after.append(r.stats()["device_bytes"])
     assert bytes_after[0] == bytes_after[2], "a re-upload of the same n allocated: %s" % bytes_after[:3]
     assert bytes_after[3] == bytes_after[2], "a smaller cloud re-uses the store"

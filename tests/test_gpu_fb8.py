@@ -4,16 +4,14 @@ Only the compositors' final store (and MSPLAT_TARGET_LOAD's destination read) kn
 MSPLAT_FB_RGBA32F context, bit for bit.  So every check here is the rule of tests/fb8_rule.py applied to the fp32 context's frame of
 the same Sort -- RGBA8 byte for byte; SRGB8_ALPHA8 alpha byte for byte and r g b within 0.5 + 2^-10 of a code of the float64
 encode -- or, for the execution shapes, the plain 8-bit frame byte for byte.  Scenes and helpers are those of
-tests/test_gpu_target_mode.py and tests/test_gpu_parity.py."""
-import functools
-
+tests/render_cases.py and tests/gpu_harness.py."""
 import numpy as np
 import pytest
 
 from splatapult_amd import MsplatError, SplatRenderer, SplatRendererGroup, _capi, camera
 from tests import fb8_rule, scenes
-from tests.test_gpu_parity import bin_px, make_renderer
-from tests.test_gpu_target_mode import render_host, view_of
+from tests.gpu_harness import bin_px, device_frame, fp32_frame, host_frame, make_renderer, sorted_renderer
+from tests.render_cases import const_dst, random_bytes, view_of
 
 pytestmark = pytest.mark.gpu
 
@@ -25,55 +23,12 @@ def is_srgb(fmt):
     return fmt == "srgb8"
 
 
-def random_bytes(H, W, seed):
-    return np.random.default_rng(seed).integers(0, 256, (H, W, 4), dtype=np.uint8)
-
-
-def const_bytes(H, W, rgba):
-    return np.broadcast_to(np.asarray(rgba, np.uint8), (H, W, 4)).copy()
-
-
-def render_device8(r, view, mode, dst, pad=24):
-    """one device-output Render into a uint8 target whose rows are `pad` pixels wider than the image and hold SENTINEL there:
-    returns (image, padding after)"""
-    import torch
-    cam, proj, vp, nf = view
-    H, W = dst.shape[:2]
-    fb = torch.full((H, W + pad, 4), SENTINEL, dtype=torch.uint8, device="cuda:0")
-    fb[:, :W] = torch.from_numpy(np.ascontiguousarray(dst)).to("cuda:0")
-    torch.cuda.synchronize()
-    r.set_target_mode(mode)
-    r.Render(cam, proj, vp, nf, out_ptr=fb.data_ptr(), pitch_bytes=(W + pad) * 4)
-    r.synchronize()
-    got = fb.cpu().numpy()
-    return got[:, :W].copy(), got[:, W:].copy()
-
-
-@functools.lru_cache(maxsize=None)
-def fp32_frame(name, mode):
-    """the fp32 context's CLEAR / PREMULTIPLIED frame of a scene's view, computed once and left unchanged"""
-    cloud, W, H, view = view_of(name)
-    r = make_renderer(cloud)
-    r.Sort(*view)
-    img = render_host(r, view, mode)
-    img.setflags(write=False)
-    r.close()
-    return img
-
-
 def fp32_load(name, dst):
     """the fp32 context's LOAD frame over the float destination dst"""
     cloud, W, H, view = view_of(name)
     r = make_renderer(cloud)
     r.Sort(*view)
-    return render_host(r, view, "load", dst)
-
-
-def sorted_renderer(name, fmt, **kw):
-    cloud, W, H, view = view_of(name)
-    r = make_renderer(cloud, fb_format=fmt, **kw)
-    r.Sort(*view)
-    return r, W, H, view
+    return host_frame(r, view, "load", dst, call=r.Render)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -88,13 +43,12 @@ def test_the_store_is_the_rule_applied_to_the_fp32_frame(name, fmt):
     x = fp32_frame(name, "clear")
     if name == "sparse":                                    # the scene that reaches both clamps (tests/test_fb8.py, on the oracle)
         assert (x[..., :3] > 1).any() and (x[..., :3] < 0).any() and (x[..., :3] == 0).any()
-    host = render_host(r, view, "clear")
+    host = host_frame(r, view, "clear", call=r.Render)
     assert host.dtype == np.uint8 and host.shape == (H, W, 4)
     fb8_rule.check_frame(host, x, is_srgb(fmt), "%s host" % name)
-    dev, padding = render_device8(r, view, "clear", random_bytes(H, W, 1))
+    dev = device_frame(r, view, "clear", random_bytes(H, W, 1), call=r.Render, fill=SENTINEL)          # (asserts that the padding keeps its bytes)
     fb8_rule.check_frame(dev, x, is_srgb(fmt), "%s device" % name)
     np.testing.assert_array_equal(dev, host)
-    assert (padding == SENTINEL).all(), "the store wrote into the padding of a pitched target"
     assert (host[..., 3] == 255).all()                      # CLEAR's alpha
 
 
@@ -108,26 +62,25 @@ def test_target_modes(name, fmt):
     r, W, H, view = sorted_renderer(name, fmt)
     srgb = is_srgb(fmt)
     junk = random_bytes(H, W, 5)
-    clear = render_host(r, view, "clear", junk)
-    pre = render_host(r, view, "premultiplied", junk)
+    clear = host_frame(r, view, "clear", junk, call=r.Render)
+    pre = host_frame(r, view, "premultiplied", junk, call=r.Render)
     xpre = fp32_frame(name, "premultiplied")
     fb8_rule.check_frame(pre, xpre, srgb, "%s premultiplied" % name)
     np.testing.assert_array_equal(pre[..., :3], clear[..., :3])
     # LOAD over random bytes: the fp32 LOAD frame over the decoded destination
     dst = random_bytes(H, W, 6)
     xload = fp32_load(name, fb8_rule.decode(dst, srgb))
-    for got, padding in ((render_host(r, view, "load", dst), None), render_device8(r, view, "load", dst)):
+    for got in (host_frame(r, view, "load", dst, call=r.Render), device_frame(r, view, "load", dst, call=r.Render, fill=SENTINEL)):
         fb8_rule.check_frame(got, xload, srgb, "%s load" % name)
-        assert padding is None or (padding == SENTINEL).all()
         if name == "sparse":
             # a pixel no splat reaches keeps its four bytes (the fp32 PREMULTIPLIED alpha is 1 - T: exactly 0 where T == 1)
             untouched = xpre[..., 3] == 0
             assert untouched.mean() >= 0.01
             assert (got[untouched] == dst[untouched]).all(), "%d untouched pixel(s) changed" % (got[untouched] != dst[untouched]).any(axis=-1).sum()
             assert (got[~untouched] != dst[~untouched]).any()
-    np.testing.assert_array_equal(render_host(r, view, "load", const_bytes(H, W, (0, 0, 0, 0))), pre)
-    np.testing.assert_array_equal(render_host(r, view, "load", const_bytes(H, W, (0, 0, 0, 255))), clear)
-    np.testing.assert_array_equal(render_host(r, view, "clear", junk), clear)      # and back
+    np.testing.assert_array_equal(host_frame(r, view, "load", const_dst(H, W, (0, 0, 0, 0), np.uint8), call=r.Render), pre)
+    np.testing.assert_array_equal(host_frame(r, view, "load", const_dst(H, W, (0, 0, 0, 255), np.uint8), call=r.Render), clear)
+    np.testing.assert_array_equal(host_frame(r, view, "clear", junk, call=r.Render), clear)      # and back
 
 
 # ------------------------------------------------------------------------------------------------
@@ -145,9 +98,9 @@ def test_two_pass_frames_and_the_persistent_wave_queue(fmt):
     for r in (a, b, q):
         r.Sort(*view)
     for mode in ("clear", "load", "premultiplied"):
-        want = render_host(a, view, mode, dst)
-        np.testing.assert_array_equal(render_host(b, view, mode, dst), want, err_msg="two passes, " + mode)
-        np.testing.assert_array_equal(render_host(q, view, mode, dst), want, err_msg="64 persistent waves, " + mode)
+        want = host_frame(a, view, mode, dst, call=a.Render)
+        np.testing.assert_array_equal(host_frame(b, view, mode, dst, call=b.Render), want, err_msg="two passes, " + mode)
+        np.testing.assert_array_equal(host_frame(q, view, mode, dst, call=q.Render), want, err_msg="64 persistent waves, " + mode)
     assert b.two_pass_state(0.3)[0] == 3 and a.two_pass_state()[0] == 0
     items, grid = q.compositor_launch()[:2]
     assert grid == 64 < items, (items, grid)                 # persistent waves on the work queue
@@ -166,7 +119,7 @@ def test_render_stereo_equals_two_renders(fmt):
     r.Sort(eyes[0], projs[0], vp, nf)
     dsts = [random_bytes(H, W, 31), random_bytes(H, W, 32)]
     for mode in ("clear", "load"):
-        want = [render_device8(r, (eyes[k], projs[k], vp, nf), mode, dsts[k], pad=0)[0] for k in range(2)]
+        want = [device_frame(r, (eyes[k], projs[k], vp, nf), mode, dsts[k], call=r.Render, fill=SENTINEL, pad=0) for k in range(2)]
         fbs = [torch.from_numpy(dsts[k].copy()).to("cuda:0") for k in range(2)]
         torch.cuda.synchronize()
         r.RenderStereo(eyes, projs, vp, nf, out_ptrs=[f.data_ptr() for f in fbs], pitch_bytes=W * 4)
@@ -179,7 +132,7 @@ def test_render_stereo_equals_two_renders(fmt):
     outs = r.RenderStereo(eyes, projs, vp, nf)
     for k in range(2):
         assert outs[k].dtype == np.uint8
-        np.testing.assert_array_equal(outs[k], render_host(r, (eyes[k], projs[k], vp, nf), "clear"))
+        np.testing.assert_array_equal(outs[k], host_frame(r, (eyes[k], projs[k], vp, nf), "clear", call=r.Render))
 
 
 @pytest.mark.parametrize("fmt", FORMATS)
@@ -200,7 +153,7 @@ def test_four_frames_in_flight_equal_one_context(fmt):
         fly.synchronize()
         for k, view in enumerate(views):
             one.Sort(*view)
-            np.testing.assert_array_equal(fbs[k].cpu().numpy(), render_host(one, view, mode, dsts[k]), err_msg="%s frame %d" % (mode, k))
+            np.testing.assert_array_equal(fbs[k].cpu().numpy(), host_frame(one, view, mode, dsts[k], call=one.Render), err_msg="%s frame %d" % (mode, k))
 
 
 @pytest.mark.parametrize("fmt", FORMATS)
@@ -216,19 +169,18 @@ def test_a_banded_context_writes_its_own_rows_only(fmt):
     band = make_renderer(cloud, fb_format=fmt)
     band.set_band_layout(first, count, block, stride)
     band.Sort(*view)
-    for mode, dst in (("clear", const_bytes(H, W, (SENTINEL,) * 4)), ("load", random_bytes(H, W, 51))):
-        want = render_host(plain, view, mode, dst)
-        for got, padding in ((render_host(band, view, mode, dst), None), render_device8(band, view, mode, dst)):
+    for mode, dst in (("clear", const_dst(H, W, (SENTINEL,) * 4, np.uint8)), ("load", random_bytes(H, W, 51))):
+        want = host_frame(plain, view, mode, dst, call=plain.Render)
+        for got in (host_frame(band, view, mode, dst, call=band.Render), device_frame(band, view, mode, dst, call=band.Render, fill=SENTINEL)):
             np.testing.assert_array_equal(got[owned], want[owned])
             assert got[~owned].tobytes() == dst[~owned].tobytes(), "mode %s touched rows of another band" % mode
-            assert padding is None or (padding == SENTINEL).all()
 
 
 @pytest.mark.parametrize("fmt", FORMATS)
 def test_bands_of_every_kind_reassemble_the_unbanded_frame(fmt):
     plain, W, H, view = sorted_renderer("sparse", fmt)
     cloud = view_of("sparse")[0]
-    full = render_host(plain, view, "clear")
+    full = host_frame(plain, view, "clear", call=plain.Render)
     T = bin_px()
     rows_full = (H + T - 1) // T
     for kind, k, world, cull in (("contiguous", 1, 3, False), ("interleaved", 1, 4, True), ("block", 2, 3, True), ("weighted", 300, 3, False)):
@@ -253,7 +205,7 @@ def test_render_depth_colour_is_the_plain_frame_and_the_plane_is_the_fp32_one(fm
     f32.Sort(*view)
     _, zwant = f32.Render(*view, depth=True)
     assert zwant.dtype == np.float32 and (zwant < 1).any()
-    plain = render_host(r, view, "clear")
+    plain = host_frame(r, view, "clear", call=r.Render)
     img, z = r.Render(*view, depth=True)
     np.testing.assert_array_equal(img, plain)
     assert z.dtype == np.float32 and (z.view(np.uint32) == zwant.view(np.uint32)).all()
@@ -277,18 +229,18 @@ def test_depth_test_and_target_emulation():
     f32 = make_renderer(cloud)
     f32.set_depth_test(24)
     f32.Sort(*view)
-    x = render_host(f32, view, "clear")
-    xpre = render_host(f32, view, "premultiplied")
+    x = host_frame(f32, view, "clear", call=f32.Render)
+    xpre = host_frame(f32, view, "premultiplied", call=f32.Render)
     for fmt in FORMATS:
         r = make_renderer(cloud, fb_format=fmt)
         r.set_depth_test(24)
         r.Sort(*view)
-        fb8_rule.check_frame(render_host(r, view, "clear"), x, is_srgb(fmt), "depth test")
-        pre = render_host(r, view, "premultiplied")
+        fb8_rule.check_frame(host_frame(r, view, "clear", call=r.Render), x, is_srgb(fmt), "depth test")
+        pre = host_frame(r, view, "premultiplied", call=r.Render)
         fb8_rule.check_frame(pre, xpre, is_srgb(fmt), "depth test, premultiplied")
         dst = random_bytes(H, W, 61)
-        got = render_host(r, view, "load", dst)
-        fb8_rule.check_frame(got, render_host(f32, view, "load", fb8_rule.decode(dst, is_srgb(fmt))), is_srgb(fmt), "depth test, load")
+        got = host_frame(r, view, "load", dst, call=r.Render)
+        fb8_rule.check_frame(got, host_frame(f32, view, "load", fb8_rule.decode(dst, is_srgb(fmt)), call=f32.Render), is_srgb(fmt), "depth test, load")
         untouched = xpre[..., 3] == 0
         assert untouched.any() and (got[untouched] == dst[untouched]).all()
     # MSPLAT_ROP_RGBA8 on an RGBA8 context: the reference's default window, bytes included -- the emulated values already are codes
@@ -301,10 +253,10 @@ def test_depth_test_and_target_emulation():
         r.set_target_emulation("rgba8")
         r.Sort(*view)
         f32.Sort(*view)
-        emu = render_host(f32, view, "clear")
+        emu = host_frame(f32, view, "clear", call=f32.Render)
         codes = emu * np.float32(255.0)
         assert (codes == np.rint(codes)).all() and codes.min() >= 0 and codes.max() <= 255
-        np.testing.assert_array_equal(render_host(r, view, "clear"), codes.astype(np.uint8))
+        np.testing.assert_array_equal(host_frame(r, view, "clear", call=r.Render), codes.astype(np.uint8))
         f32.set_target_emulation(None)
 
 
@@ -373,8 +325,8 @@ def test_device_group_reproduces_the_single_context_frame(fmt, monkeypatch):
     cam, proj, vp, nf = view
     r = make_renderer(cloud, fb_format=fmt)
     r.Sort(*view)
-    full = render_host(r, view, "clear")
-    pre = render_host(r, view, "premultiplied")
+    full = host_frame(r, view, "clear", call=r.Render)
+    pre = host_frame(r, view, "premultiplied", call=r.Render)
     for devices, layout, k, exchanges in (([0], "contiguous", 1, ("peer", "copy", "rccl")), ([0, 0], "interleaved", 1, ("peer", "copy")),
                                           ([0, 0, 0], "block", 2, ("peer", "copy"))):
         for exchange in exchanges:                           # (RCCL refuses a device listed twice)
@@ -432,7 +384,7 @@ def test_refusals_say_why():
         assert e.value.code == _capi.ERR_UNSUPPORTED and "MSPLAT_FB_SRGB8_ALPHA8" in s.last_error() and "linear" in s.last_error().lower()
     s.set_target_emulation(None)                             # MSPLAT_ROP_NONE is no emulation
     s.Sort(*view)
-    fb8_rule.check_frame(render_host(s, view, "clear"), fp32_frame("hard", "clear"), True, "after the refusal")
+    fb8_rule.check_frame(host_frame(s, view, "clear", call=s.Render), fp32_frame("hard", "clear"), True, "after the refusal")
     # everything else is allowed: the fp16 emulation into an RGBA8 target
     u = make_renderer(cloud, fb_format="rgba8")
     u.set_target_emulation("fp16")
@@ -440,4 +392,4 @@ def test_refusals_say_why():
     f32 = make_renderer(cloud)
     f32.set_target_emulation("fp16")
     f32.Sort(*view)
-    fb8_rule.check_frame(render_host(u, view, "clear"), render_host(f32, view, "clear"), False, "fp16 emulation into rgba8")
+    fb8_rule.check_frame(host_frame(u, view, "clear", call=u.Render), host_frame(f32, view, "clear", call=f32.Render), False, "fp16 emulation into rgba8")

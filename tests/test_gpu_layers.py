@@ -5,87 +5,28 @@
 -- the expected window depth of the splats that pass GL_LESS, blended over what the depth attachment holds -- for one view and for
 both eyes of one Sort in one chain of launches.  Checked here: the degradations (a NULL plane gives the call without it, bit for
 bit), the combined frame (colour = msplat_render_occluded's bit for bit; the plane against the unchanged oracle,
-tests/test_layers.layers_reference through tests/test_gpu_depth_output.check_plane with its bounds unchanged -- 2 TIGHT + t_eps
+tests/render_cases.layers_reference through tests/checks.check_plane with its bounds unchanged -- 2 TIGHT + t_eps
 carries over because 0 <= d0 <= 1; the exact partition; d0 where nothing is seen; in place), every execution shape against the
 plain combined frame (bit for bit), the stereo chain and its fallbacks against one msplat_render_layers per eye (bit for bit), and
 the refusals.  The planes of the oracle and partition tests keep every level 2^-20 away from every drawn splat's z_w (asserted on
 the CPU in tests/test_occluded.py and tests/test_layers.py)."""
 import ctypes as C
-import functools
 
 import numpy as np
 import pytest
 
-from splatapult_amd import MsplatError, _capi, camera
+from splatapult_amd import MsplatError, _capi
 from tests import scenes
-from tests.test_gpu_depth_output import check_plane, render_depth_host
-from tests.test_gpu_occluded import (MODES, NP_DTYPES, PAD_COLOUR, dst_for, empty_frame, four_levels, mixed_plane, occluded_device,
-                                     occluded_host, subset_renderer)
-from tests.test_gpu_parity import make_renderer
-from tests.test_gpu_target_mode import SENTINEL, T_EPS, random_dst, render_host, scene, view_of
-from tests.test_layers import SMALL_VIEWPORTS, d0_of, layers_reference, small_viewport_case
-from tests.test_occluded import scene_splats
+from tests.checks import T_EPS, check_plane, same_bits
+from tests.gpu_harness import (JUNK, PAD_COLOUR, SENTINEL, device_frame, host_frame, make_renderer, mixed_plane, stereo_frame,
+                               subset_renderer)
+from tests.render_cases import (MODES, NP_DTYPES, SMALL_VIEWPORTS, d0_of, dst_for, empty_frame, four_levels, random_dst, reference_plane,
+                                scene, scene_splats, small_viewport_case, stereo_eyes, view_of)
 
 pytestmark = pytest.mark.gpu
 
-
-def layers_host(r, view, mode, plane, dst=None, depth=True):
-    """one host-output RenderLayers in `mode`: (image, depth plane); dst: what the colour array holds before; depth: True, or the
-    array to fill (the occluder's own array: in place)"""
-    cam, proj, vp, nf = view
-    r.set_target_mode(mode)
-    keep = None if plane is None or plane is depth else plane.copy()
-    out = None if dst is None else np.ascontiguousarray(dst).copy()
-    img, z = r.RenderLayers(cam, proj, vp, nf, out=out, depth=depth, occluder=plane)
-    assert keep is None or plane.tobytes() == keep.tobytes(), "the occluder plane is read-only"
-    assert z.dtype == np.float32 and z.shape == img.shape[:2]
-    return img, z
-
-
-def junk_rows(H, W, pad, value):
-    """a pitched float32 plane whose pixels hold `value` (array or scalar) and whose padding holds NaN / 0 junk"""
-    z = np.zeros((H, W + pad), np.float32)
-    z[:, W::2] = np.nan
-    z[:, :W] = value
-    return z
-
-
-def layers_device(r, view, mode, dst, plane, pad=24, zpad=8, dpad=12, in_place=False, depth=True):
-    """one device-output RenderLayers into a pitched colour target, from a pitched occluder plane (None: none) whose padding holds
-    junk, into a pitched depth plane that starts as the sentinel (in_place: into the occluder's own memory); returns (image,
-    depth plane or None) after checking that no padding changed and that a separate occluder plane did not change"""
-    import torch
-    cam, proj, vp, nf = view
-    H, W = dst.shape[:2]
-    fb = torch.full((H, W + pad, 4), PAD_COLOUR, dtype=getattr(torch, np.dtype(dst.dtype).name), device="cuda:0")
-    fb[:, :W] = torch.from_numpy(np.ascontiguousarray(dst)).to("cuda:0")
-    ohost = junk_rows(H, W, zpad, plane) if plane is not None else None
-    ob = torch.from_numpy(ohost).to("cuda:0") if plane is not None else None
-    if in_place:
-        db, dhost, dpad = ob, ohost, zpad
-    else:
-        dhost = junk_rows(H, W, dpad, SENTINEL)
-        db = torch.from_numpy(dhost).to("cuda:0") if depth else None
-    torch.cuda.synchronize()
-    r.set_target_mode(mode)
-    r.RenderLayers(cam, proj, vp, nf, out_ptr=fb.data_ptr(), pitch_bytes=(W + pad) * 4 * fb.element_size(),
-                   depth_ptr=db.data_ptr() if db is not None else None, depth_pitch_bytes=(W + dpad) * 4,
-                   occluder_ptr=ob.data_ptr() if ob is not None else None, occluder_pitch_bytes=(W + zpad) * 4)
-    r.synchronize()
-    got = fb.cpu().numpy()
-    assert (got[:, W:] == PAD_COLOUR).all(), "mode %s wrote into the padding of a pitched target" % mode
-    z = None
-    if db is not None:
-        z = db.cpu().numpy()
-        assert z[:, W:].tobytes() == dhost[:, W:].tobytes(), "mode %s wrote into the padding of the depth plane" % mode
-        z = z[:, :W].copy()
-    if ob is not None and not in_place:
-        assert ob.cpu().numpy().tobytes() == ohost.tobytes(), "the occluder plane is read-only"
-    return got[:, :W].copy(), z
-
-
-def same(a, b, msg=""):
-    assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes(), msg or "the arrays differ"
+# the device targets of this module: the colour's padding holds PAD_COLOUR, the depth plane's (like the occluder's) NaN / 0 junk
+PITCHED = dict(fill=PAD_COLOUR, dfill=JUNK)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -101,38 +42,40 @@ def test_a_missing_plane_gives_the_call_without_it(fmt):
     dst = dst_for(fmt, H, W, 5)
     cam, proj, vp, nf = view
     for mode in MODES:
-        plain = render_host(r, view, mode, dst)
+        plain = host_frame(r, view, mode, dst, call=r.Render)
         # neither plane: msplat_render
         r.set_target_mode(mode)
-        same(r.RenderLayers(cam, proj, vp, nf, out=dst.copy()), plain, "%s: no planes, host" % mode)
-        same(layers_device(r, view, mode, dst, None, depth=False)[0], plain, "%s: no planes, device" % mode)
+        same_bits(r.RenderLayers(cam, proj, vp, nf, out=dst.copy()), plain, "%s: no planes, host" % mode)
+        same_bits(device_frame(r, view, mode, dst, call=r.RenderLayers, **PITCHED), plain, "%s: no planes, device" % mode)
         # depth only: msplat_render_depth
         r.set_target_mode(mode)
         want_img, want_z = r.Render(cam, proj, vp, nf, out=dst.copy(), depth=True)
-        same(want_img, plain)
-        img, z = layers_host(r, view, mode, None, dst)
-        same(img, want_img, "%s: depth only, host" % mode); same(z, want_z, "%s: depth only, host plane" % mode)
-        img, z = layers_device(r, view, mode, dst, None)
-        same(img, want_img, "%s: depth only, device" % mode); same(z, want_z, "%s: depth only, device plane" % mode)
+        same_bits(want_img, plain)
+        img, z = host_frame(r, view, mode, dst, call=r.RenderLayers, depth=True)
+        same_bits(img, want_img, "%s: depth only, host" % mode); same_bits(z, want_z, "%s: depth only, host plane" % mode)
+        img, z = device_frame(r, view, mode, dst, call=r.RenderLayers, depth=True, **PITCHED)
+        same_bits(img, want_img, "%s: depth only, device" % mode); same_bits(z, want_z, "%s: depth only, device plane" % mode)
         # occluder only: msplat_render_occluded
-        want = occluded_host(r, view, mode, plane, dst)
+        want = host_frame(r, view, mode, dst, call=r.Render, occluder=plane)
         r.set_target_mode(mode)
-        same(r.RenderLayers(cam, proj, vp, nf, out=dst.copy(), occluder=plane), want, "%s: occluder only, host" % mode)
-        same(layers_device(r, view, mode, dst, plane, depth=False)[0], want, "%s: occluder only, device" % mode)
-        same(occluded_device(r, view, mode, dst, plane), want)
+        same_bits(r.RenderLayers(cam, proj, vp, nf, out=dst.copy(), occluder=plane), want, "%s: occluder only, host" % mode)
+        same_bits(device_frame(r, view, mode, dst, call=r.RenderLayers, occluder=plane, **PITCHED), want, "%s: occluder only, device" % mode)
+        same_bits(device_frame(r, view, mode, dst, call=r.Render, occluder=plane, fill=PAD_COLOUR), want)
         assert not np.array_equal(want, plain)
         # an open plane with a depth output: msplat_render's colour, msplat_render_depth's plane
         for level in (np.inf, 2.0):
             op = np.full((H, W), level, np.float32)
-            for img, z in (layers_host(r, view, mode, op, dst), layers_device(r, view, mode, dst, op)):
-                same(img, plain, "%s: open plane %g" % (mode, level)); same(z, want_z, "%s: open plane %g, depth" % (mode, level))
+            for img, z in (host_frame(r, view, mode, dst, call=r.RenderLayers, depth=True, occluder=op),
+                           device_frame(r, view, mode, dst, call=r.RenderLayers, depth=True, occluder=op, **PITCHED)):
+                same_bits(img, plain, "%s: open plane %g" % (mode, level)); same_bits(z, want_z, "%s: open plane %g, depth" % (mode, level))
         # a closed plane: the empty frame and a depth plane of exactly 0
         for level in (0.0, -1.0, np.nan):
             cl = np.full((H, W), level, np.float32)
-            for img, z in (layers_host(r, view, mode, cl, dst), layers_device(r, view, mode, dst, cl)):
-                same(img, np.ascontiguousarray(empty_frame(mode, dst)), "%s: closed plane %g" % (mode, level))
-                same(z, np.zeros((H, W), np.float32), "%s: closed plane %g, depth" % (mode, level))
-        same(render_host(r, view, mode, dst), plain)              # a plain Render afterwards is the plain Render
+            for img, z in (host_frame(r, view, mode, dst, call=r.RenderLayers, depth=True, occluder=cl),
+                           device_frame(r, view, mode, dst, call=r.RenderLayers, depth=True, occluder=cl, **PITCHED)):
+                same_bits(img, np.ascontiguousarray(empty_frame(mode, dst)), "%s: closed plane %g" % (mode, level))
+                same_bits(z, np.zeros((H, W), np.float32), "%s: closed plane %g, depth" % (mode, level))
+        same_bits(host_frame(r, view, mode, dst, call=r.Render), plain)              # a plain Render afterwards is the plain Render
 
 
 # ------------------------------------------------------------------------------------------------
@@ -148,27 +91,21 @@ def test_the_colour_is_the_occluded_frames_and_the_plane_ignores_the_target(fmt)
     dst = dst_for(fmt, H, W, 7)
     planes = []
     for mode in MODES:
-        want = occluded_host(r, view, mode, plane, dst)
-        img, z = layers_host(r, view, mode, plane, dst)
-        same(img, want, "%s host" % mode)
-        dimg, dz = layers_device(r, view, mode, dst, plane)
-        same(dimg, want, "%s device" % mode); same(dz, z, "%s: device plane differs from host plane" % mode)
+        want = host_frame(r, view, mode, dst, call=r.Render, occluder=plane)
+        img, z = host_frame(r, view, mode, dst, call=r.RenderLayers, depth=True, occluder=plane)
+        same_bits(img, want, "%s host" % mode)
+        dimg, dz = device_frame(r, view, mode, dst, call=r.RenderLayers, depth=True, occluder=plane, **PITCHED)
+        same_bits(dimg, want, "%s device" % mode); same_bits(dz, z, "%s: device plane differs from host plane" % mode)
         assert np.isfinite(z).all() and z.min() >= 0.0 and z.max() <= 1.0
         planes.append(z)
-    same(planes[1], planes[0], "the plane depends on the target mode"); same(planes[2], planes[0], "the plane depends on the target mode")
+    same_bits(planes[1], planes[0], "the plane depends on the target mode"); same_bits(planes[2], planes[0], "the plane depends on the target mode")
     # where no surviving splat reaches a pixel the plane holds d0 exactly
     if fmt == "fp32":
-        untouched = occluded_host(r, view, "premultiplied", plane)[..., 3] == 0
+        untouched = host_frame(r, view, "premultiplied", call=r.Render, occluder=plane)[..., 3] == 0
         assert untouched.mean() > 0.01 and (~untouched).mean() > 0.01
-        same(planes[0][untouched], d0_of(plane)[untouched], "a pixel no surviving splat reaches must read d0")
-        _, plain_z = render_depth_host(r, view)
+        same_bits(planes[0][untouched], d0_of(plane)[untouched], "a pixel no surviving splat reaches must read d0")
+        _, plain_z = host_frame(r, view, "clear", call=r.Render, depth=True)
         assert not np.array_equal(planes[0], plain_z)            # the occluder matters to the plane
-
-
-@functools.lru_cache(maxsize=None)
-def reference_plane(name):
-    _, W, H, _ = view_of(name)
-    return layers_reference(scene_splats(name)[0], four_levels(name)[0].copy(), W, H)
 
 
 @pytest.mark.parametrize("t_eps", [-1.0, 0.0])
@@ -181,11 +118,11 @@ def test_the_plane_matches_the_oracle(name, t_eps):
     r.Sort(*view)
     assert r.sort_count() == scene_splats(name)[1]
     eps = T_EPS if t_eps < 0 else t_eps
-    img, z = layers_host(r, view, "clear", plane)
-    same(img, occluded_host(r, view, "clear", plane))
+    img, z = host_frame(r, view, "clear", call=r.RenderLayers, depth=True, occluder=plane)
+    same_bits(img, host_frame(r, view, "clear", call=r.Render, occluder=plane))
     check_plane(z, L, eps)
-    _, dz = layers_device(r, view, "load", random_dst(H, W, 11), plane)
-    same(dz, z)
+    _, dz = device_frame(r, view, "load", random_dst(H, W, 11), call=r.RenderLayers, depth=True, occluder=plane, **PITCHED)
+    same_bits(dz, z)
 
 
 @pytest.mark.parametrize("name", ["hard", "dense"])
@@ -199,7 +136,7 @@ def test_each_region_of_the_plane_is_that_of_the_splats_in_front_of_its_level(na
     exact = make_renderer(cloud, t_epsilon=0.0)
     exact.Sort(*view)
     assert exact.sort_count() == V
-    img0, z0 = layers_host(exact, view, "clear", plane)
+    img0, z0 = host_frame(exact, view, "clear", call=exact.RenderLayers, depth=True, occluder=plane)
     if name == "dense":
         assert np.diff(exact.debug_tile_lists(want_pairs=False)[0].astype(np.int64)).max() > 128      # lists longer than two batches
     for v in levels:
@@ -207,11 +144,11 @@ def test_each_region_of_the_plane_is_that_of_the_splats_in_front_of_its_level(na
         sub, n = subset_renderer(name, splats, v, t_epsilon=0.0)
         assert 0 < n < V
         sub.Sort(*view)
-        img, z = layers_host(sub, view, "clear", plane)
+        img, z = host_frame(sub, view, "clear", call=sub.RenderLayers, depth=True, occluder=plane)
         sub.close()
-        same(z0[region], z[region], "level %.9g: the plane" % v)
-        same(img0[region], img[region], "level %.9g: the colour" % v)
-    _, zplain = render_depth_host(exact, view)
+        same_bits(z0[region], z[region], "level %.9g: the plane" % v)
+        same_bits(img0[region], img[region], "level %.9g: the colour" % v)
+    _, zplain = host_frame(exact, view, "clear", call=exact.Render, depth=True)
     changed = int((z0 != zplain).sum())
     print("%s: %d value(s) of the plane differ from msplat_render_depth's" % (name, changed))
     # (inside the dense cloud the nearest fifth of the splats leaves T below an ulp of the plane everywhere: there the test is about
@@ -227,13 +164,13 @@ def test_in_place_equals_separate_buffers(name):
     plane = mixed_plane(r, view)
     dst = random_dst(H, W, 13)
     for mode in MODES:
-        img, z = layers_host(r, view, mode, plane, dst)
+        img, z = host_frame(r, view, mode, dst, call=r.RenderLayers, depth=True, occluder=plane)
         attachment = plane.copy()
-        himg, hz = layers_host(r, view, mode, attachment, dst, depth=attachment)
+        himg, hz = host_frame(r, view, mode, dst, call=r.RenderLayers, depth=attachment, occluder=attachment)
         assert hz is attachment
-        same(himg, img, "%s host in place" % mode); same(hz, z, "%s host in place, plane" % mode)
-        dimg, dz = layers_device(r, view, mode, dst, plane, in_place=True)
-        same(dimg, img, "%s device in place" % mode); same(dz, z, "%s device in place, plane" % mode)
+        same_bits(himg, img, "%s host in place" % mode); same_bits(hz, z, "%s host in place, plane" % mode)
+        dimg, dz = device_frame(r, view, mode, dst, call=r.RenderLayers, depth=True, occluder=plane, **PITCHED, in_place=True)
+        same_bits(dimg, img, "%s device in place" % mode); same_bits(dz, z, "%s device in place, plane" % mode)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -251,10 +188,11 @@ def test_two_pass_frames_equal_the_single_pass(share):
     dst = random_dst(H, W, 21)
     before = b.two_pass_state(share)[0]
     for mode in MODES:
-        img, z = layers_host(a, view, mode, plane, dst)
-        for got, gz in (layers_host(b, view, mode, plane, dst), layers_device(b, view, mode, dst, plane),
-                        layers_device(b, view, mode, dst, plane, in_place=True)):
-            same(got, img, mode); same(gz, z, mode)
+        img, z = host_frame(a, view, mode, dst, call=a.RenderLayers, depth=True, occluder=plane)
+        for got, gz in (host_frame(b, view, mode, dst, call=b.RenderLayers, depth=True, occluder=plane),
+                        device_frame(b, view, mode, dst, call=b.RenderLayers, depth=True, occluder=plane, **PITCHED),
+                        device_frame(b, view, mode, dst, call=b.RenderLayers, depth=True, occluder=plane, **PITCHED, in_place=True)):
+            same_bits(got, img, mode); same_bits(gz, z, mode)
     assert b.two_pass_state(share)[0] == before + 9 and a.two_pass_state()[0] == 0
     print("two-pass, share %g: %s" % (share, b.two_pass_info()))
     a.close(); b.close()
@@ -265,9 +203,9 @@ def test_two_pass_frames_equal_the_single_pass(share):
     a.Sort(*view); b.Sort(*view)
     dst = random_dst(H, W, 22, np.float16)
     for mode in MODES:
-        img, z = layers_device(a, view, mode, dst, plane)
-        got, gz = layers_device(b, view, mode, dst, plane)
-        same(got, img, "fp16 " + mode); same(gz, z, "fp16 " + mode)
+        img, z = device_frame(a, view, mode, dst, call=a.RenderLayers, depth=True, occluder=plane, **PITCHED)
+        got, gz = device_frame(b, view, mode, dst, call=b.RenderLayers, depth=True, occluder=plane, **PITCHED)
+        same_bits(got, img, "fp16 " + mode); same_bits(gz, z, "fp16 " + mode)
     assert b.two_pass_state(share)[0] == 3
 
 
@@ -279,7 +217,7 @@ def test_three_bands_write_their_own_rows_of_both_planes():
     plain.Sort(*view)
     plane = mixed_plane(plain, view)
     dst = random_dst(H, W, 51)
-    want = {mode: layers_host(plain, view, mode, plane, dst) for mode in MODES}
+    want = {mode: host_frame(plain, view, mode, dst, call=plain.RenderLayers, depth=True, occluder=plane) for mode in MODES}
     covered = np.zeros(H, bool)
     for rank in range(3):
         band = make_renderer(cloud)
@@ -293,10 +231,10 @@ def test_three_bands_write_their_own_rows_of_both_planes():
         for mode in MODES:
             img, z = want[mode]
             hz = np.full((H, W), SENTINEL, np.float32)
-            himg, _ = layers_host(band, view, mode, foreign, dst, depth=hz)
-            dimg, dz = layers_device(band, view, mode, dst, foreign)
+            himg, _ = host_frame(band, view, mode, dst, call=band.RenderLayers, depth=hz, occluder=foreign)
+            dimg, dz = device_frame(band, view, mode, dst, call=band.RenderLayers, depth=True, occluder=foreign, **PITCHED)
             for gi, gz in ((himg, hz), (dimg, dz)):
-                same(gi[owned], img[owned], "%s rank %d" % (mode, rank)); same(gz[owned], z[owned], "%s rank %d: plane" % (mode, rank))
+                same_bits(gi[owned], img[owned], "%s rank %d" % (mode, rank)); same_bits(gz[owned], z[owned], "%s rank %d: plane" % (mode, rank))
                 assert gi[~owned].tobytes() == dst[~owned].tobytes(), "mode %s touched colour rows of another band" % mode
                 assert (gz[~owned] == SENTINEL).all(), "mode %s touched depth rows of another band" % mode
         band.close()
@@ -329,9 +267,9 @@ def test_frames_in_flight_and_queued_calls_equal_one_context(shape):
         fly.synchronize()
         for k, view in enumerate(views):
             one.Sort(*view)
-            img, z = layers_host(one, view, mode, planes[k], dsts[k])
-            same(fbs[k].cpu().numpy(), img, "%s frame %d" % (mode, k))
-            same((obs[k] if k % 2 else dbs[k]).cpu().numpy(), z, "%s frame %d: plane" % (mode, k))
+            img, z = host_frame(one, view, mode, dsts[k], call=one.RenderLayers, depth=True, occluder=planes[k])
+            same_bits(fbs[k].cpu().numpy(), img, "%s frame %d" % (mode, k))
+            same_bits((obs[k] if k % 2 else dbs[k]).cpu().numpy(), z, "%s frame %d: plane" % (mode, k))
 
 
 def test_persistent_waves_on_the_work_queue_equal_one_wave_per_item():
@@ -342,9 +280,9 @@ def test_persistent_waves_on_the_work_queue_equal_one_wave_per_item():
     plane = mixed_plane(a, view)
     dst = random_dst(H, W, 61)
     for mode in MODES:
-        img, z = layers_host(a, view, mode, plane, dst)
-        got, gz = layers_host(b, view, mode, plane, dst)
-        same(got, img, mode); same(gz, z, mode)
+        img, z = host_frame(a, view, mode, dst, call=a.RenderLayers, depth=True, occluder=plane)
+        got, gz = host_frame(b, view, mode, dst, call=b.RenderLayers, depth=True, occluder=plane)
+        same_bits(got, img, mode); same_bits(gz, z, mode)
     items, grid = b.compositor_launch()[:2]
     assert grid == 64 and items > grid                       # the work-queue regime
 
@@ -360,15 +298,16 @@ def test_small_viewports(W, H):
     r.Sort(*view)
     dst = random_dst(H, W, 25)
     for mode in MODES:
-        img, z = layers_host(r, view, mode, plane, dst)
-        same(img, occluded_host(r, view, mode, plane, dst), mode)
-        for got, gz in (layers_device(r, view, mode, dst, plane), layers_device(r, view, mode, dst, plane, in_place=True)):
-            same(got, img, mode); same(gz, z, mode)
-    _, z = layers_host(r, view, "clear", plane)
+        img, z = host_frame(r, view, mode, dst, call=r.RenderLayers, depth=True, occluder=plane)
+        same_bits(img, host_frame(r, view, mode, dst, call=r.Render, occluder=plane), mode)
+        for got, gz in (device_frame(r, view, mode, dst, call=r.RenderLayers, depth=True, occluder=plane, **PITCHED),
+                        device_frame(r, view, mode, dst, call=r.RenderLayers, depth=True, occluder=plane, **PITCHED, in_place=True)):
+            same_bits(got, img, mode); same_bits(gz, z, mode)
+    _, z = host_frame(r, view, "clear", call=r.RenderLayers, depth=True, occluder=plane)
     for v in levels:
         sub, n = subset_renderer(cloud, splats, v, t_epsilon=0.0)
         sub.Sort(*view)
-        same(z[plane == v], layers_host(sub, view, "clear", plane)[1][plane == v], "level %.9g" % v)
+        same_bits(z[plane == v], host_frame(sub, view, "clear", call=sub.RenderLayers, depth=True, occluder=plane)[1][plane == v], "level %.9g" % v)
         sub.close()
 
 
@@ -384,14 +323,14 @@ def test_host_output_survives_a_pair_buffer_overflow():
     r = make_renderer(cloud)                                # automatic capacity
     r.Sort(*view)
     attachment = plane.copy()
-    got, gz = layers_host(r, view, "load", attachment, dst, depth=attachment)        # the context's first render
+    got, gz = host_frame(r, view, "load", dst, call=r.RenderLayers, depth=attachment, occluder=attachment)        # the context's first render
     st = r.stats()
     assert st["pairs"] > (1 << 22) and st["pair_capacity"] >= st["pairs"], st      # it did overflow, and grew
     calm = make_renderer(cloud, pair_capacity=int(st["pairs"]) + 4096)               # never overflows
     calm.Sort(*view)
-    img, z = layers_host(calm, view, "load", plane, dst)
-    same(got, img); same(gz, z)
-    same(img, occluded_host(calm, view, "load", plane, dst))
+    img, z = host_frame(calm, view, "load", dst, call=calm.RenderLayers, depth=True, occluder=plane)
+    same_bits(got, img); same_bits(gz, z)
+    same_bits(img, host_frame(calm, view, "load", dst, call=calm.Render, occluder=plane))
     assert not np.array_equal(z, plane) and (z < plane).any()              # splats in front of the attachment were blended into it
 
 
@@ -400,12 +339,6 @@ def test_host_output_survives_a_pair_buffer_overflow():
 # ------------------------------------------------------------------------------------------------
 
 COMBOS = [(True, False), (False, True), (True, True)]         # (depth, occluder)
-
-
-def stereo_eyes(W, H):
-    """two eyes as tests/test_gpu_target_mode.test_render_stereo_equals_two_renders builds them"""
-    proj = camera.perspective(camera.FOVY, W / H)
-    return [camera.pose((-0.1, 0.0, 6.0), 0.65), camera.pose((0.1, 0.0, 6.0), 0.75)], proj, [0, 0, W, H], scenes.NF
 
 
 def eye_planes(r, cams, proj, vp, nf, swapped):
@@ -417,56 +350,23 @@ def eye_planes(r, cams, proj, vp, nf, swapped):
     return [mixed[0], closed] if swapped else [closed, mixed[1]]
 
 
-def stereo_device(r, cams, proj, vp, nf, mode, dsts, planes, depth, pad=24, zpad=8, dpad=12, in_place=False):
-    """one device-output RenderStereoLayers into pitched targets; returns ([image0, image1], [plane0, plane1] or None) after the
-    padding and read-only checks of layers_device"""
-    import torch
-    H, W = dsts[0].shape[:2]
-    tdt = getattr(torch, np.dtype(dsts[0].dtype).name)
-    fbs, ohosts, obs, dhosts, dbs = [], [], [], [], []
-    for e in range(2):
-        fb = torch.full((H, W + pad, 4), PAD_COLOUR, dtype=tdt, device="cuda:0")
-        fb[:, :W] = torch.from_numpy(np.ascontiguousarray(dsts[e])).to("cuda:0")
-        fbs.append(fb)
-        if planes is not None:
-            ohosts.append(junk_rows(H, W, zpad, planes[e]))
-            obs.append(torch.from_numpy(ohosts[e]).to("cuda:0"))
-        if depth and not in_place:
-            dhosts.append(junk_rows(H, W, dpad, SENTINEL))
-            dbs.append(torch.from_numpy(dhosts[e]).to("cuda:0"))
-    if in_place:
-        dbs, dhosts, dpad = obs, ohosts, zpad
-    torch.cuda.synchronize()
-    r.set_target_mode(mode)
-    r.RenderStereoLayers(cams, [proj, proj], vp, nf, out_ptrs=[f.data_ptr() for f in fbs], pitch_bytes=(W + pad) * 4 * fbs[0].element_size(),
-                         depth_ptrs=[d.data_ptr() for d in dbs] if depth else None, depth_pitch_bytes=(W + dpad) * 4,
-                         occluder_ptrs=[o.data_ptr() for o in obs] if planes is not None else None, occluder_pitch_bytes=(W + zpad) * 4)
-    r.synchronize()
-    imgs, zs = [], []
-    for e in range(2):
-        got = fbs[e].cpu().numpy()
-        assert (got[:, W:] == PAD_COLOUR).all(), "eye %d: wrote into the padding of a pitched target" % e
-        imgs.append(got[:, :W].copy())
-        if depth:
-            z = dbs[e].cpu().numpy()
-            assert z[:, W:].tobytes() == dhosts[e][:, W:].tobytes(), "eye %d: wrote into the padding of the depth plane" % e
-            zs.append(z[:, :W].copy())
-        if planes is not None and not in_place:
-            assert obs[e].cpu().numpy().tobytes() == ohosts[e].tobytes(), "eye %d: the occluder plane is read-only" % e
-    return imgs, (zs if depth else None)
+def with_planes(got, depth):
+    """(images, planes or None) of what a frame of both eyes returned"""
+    return got if depth else (got, None)
 
 
 def per_eye(r, cams, proj, vp, nf, mode, dsts, planes, depth):
     """the same frame as one device-output RenderLayers per eye"""
-    out = [layers_device(r, (cams[e], proj, vp, nf), mode, dsts[e], planes[e] if planes is not None else None, depth=depth) for e in range(2)]
-    return [o[0] for o in out], ([o[1] for o in out] if depth else None)
+    out = [device_frame(r, (cams[e], proj, vp, nf), mode, dsts[e], call=r.RenderLayers, depth=depth,
+                        occluder=planes[e] if planes is not None else None, **PITCHED) for e in range(2)]
+    return ([o[0] for o in out], [o[1] for o in out]) if depth else (out, None)
 
 
 def assert_eyes(got, want, msg):
     for e in range(2):
-        same(got[0][e], want[0][e], "%s: eye %d colour" % (msg, e))
+        same_bits(got[0][e], want[0][e], "%s: eye %d colour" % (msg, e))
         if want[1] is not None:
-            same(got[1][e], want[1][e], "%s: eye %d plane" % (msg, e))
+            same_bits(got[1][e], want[1][e], "%s: eye %d plane" % (msg, e))
 
 
 @pytest.mark.parametrize("fmt", ["fp32", "fp16"])
@@ -484,17 +384,18 @@ def test_stereo_layers_in_one_chain_equal_one_call_per_eye(depth, occluder, fmt)
         for mode in MODES:                                   # LOAD: over random destinations
             want = per_eye(r, cams, proj, vp, nf, mode, dsts, planes, depth)
             mono_items = r.compositor_launch()[0]
-            got = stereo_device(r, cams, proj, vp, nf, mode, dsts, planes, depth)
+            got = with_planes(stereo_frame(r, cams, [proj, proj], vp, nf, mode, dsts, call=r.RenderStereoLayers, depth=depth, occluders=planes, **PITCHED), depth)
             assert r.compositor_launch()[0] == 2 * mono_items, "the single chain did not run"
             assert_eyes(got, want, "%s swapped %d" % (mode, swapped))
             if depth and occluder:
-                assert_eyes(stereo_device(r, cams, proj, vp, nf, mode, dsts, planes, depth, in_place=True), want, "%s in place" % mode)
+                got = stereo_frame(r, cams, [proj, proj], vp, nf, mode, dsts, call=r.RenderStereoLayers, depth=depth, occluders=planes, **PITCHED, in_place=True)
+                assert_eyes(with_planes(got, depth), want, "%s in place" % mode)
         assert not np.array_equal(want[0][0], want[0][1])
         if depth:
             assert not np.array_equal(want[1][0], want[1][1])
     # a mono frame on the same context afterwards is unaffected
-    same(layers_device(r, (cams[1], proj, vp, nf), "clear", dsts[1], planes[1] if occluder else None, depth=depth)[0],
-         per_eye(r, cams, proj, vp, nf, "clear", dsts, planes, depth)[0][1])
+    mono = device_frame(r, (cams[1], proj, vp, nf), "clear", dsts[1], call=r.RenderLayers, depth=depth, occluder=planes[1] if occluder else None, **PITCHED)
+    same_bits(mono[0] if depth else mono, per_eye(r, cams, proj, vp, nf, "clear", dsts, planes, depth)[0][1])
 
 
 @pytest.mark.parametrize("depth, occluder", COMBOS)
@@ -510,7 +411,8 @@ def test_stereo_layers_on_the_work_queue_and_in_flight(depth, occluder):
     # persistent waves on the work queue
     q = make_renderer(cloud, compositor_waves=64)
     q.Sort(cams[0], proj, vp, nf)
-    assert_eyes(stereo_device(q, cams, proj, vp, nf, "load", dsts, planes, depth), want, "compositor_waves=64")
+    got = stereo_frame(q, cams, [proj, proj], vp, nf, "load", dsts, call=q.RenderStereoLayers, depth=depth, occluders=planes, **PITCHED)
+    assert_eyes(with_planes(got, depth), want, "compositor_waves=64")
     items, grid = q.compositor_launch()[:2]
     assert grid == 64 and items > grid and items == 2 * one.compositor_launch()[0]
     # four contexts in flight: six frames, each with its own targets
@@ -544,8 +446,7 @@ def test_stereo_layers_fall_back_view_by_view(depth, occluder):
     mono_items = r.compositor_launch()[0]
     # host arrays
     r.set_target_mode("clear")
-    got = r.RenderStereoLayers(cams, [proj, proj], vp, nf, depth=depth, occluders=planes)
-    got = got if depth else (got, None)
+    got = with_planes(r.RenderStereoLayers(cams, [proj, proj], vp, nf, depth=depth, occluders=planes), depth)
     assert_eyes(got, want, "host arrays")
     assert r.compositor_launch()[0] == mono_items
     # a banded context: owned rows of each eye
@@ -554,12 +455,12 @@ def test_stereo_layers_fall_back_view_by_view(depth, occluder):
     band.set_band(2, 1)
     band.Sort(cams[0], proj, vp, nf)
     owned = np.arange(H) // T % 2 == 1
-    gi, gz = stereo_device(band, cams, proj, vp, nf, "clear", dsts, planes, depth)
+    gi, gz = with_planes(stereo_frame(band, cams, [proj, proj], vp, nf, "clear", dsts, call=band.RenderStereoLayers, depth=depth, occluders=planes, **PITCHED), depth)
     for e in range(2):
-        same(gi[e][owned], want[0][e][owned], "banded: eye %d" % e)
+        same_bits(gi[e][owned], want[0][e][owned], "banded: eye %d" % e)
         assert gi[e][~owned].tobytes() == dsts[e][~owned].tobytes()
         if depth:
-            same(gz[e][owned], want[1][e][owned], "banded: eye %d plane" % e)
+            same_bits(gz[e][owned], want[1][e][owned], "banded: eye %d plane" % e)
             assert (gz[e][~owned] == SENTINEL).all()
     assert band.compositor_launch()[0] < 2 * mono_items
 
@@ -576,7 +477,8 @@ def test_stereo_layers_beyond_128_bin_rows_go_view_by_view(depth, occluder):
     want = per_eye(r, cams, proj, vp, nf, "load", dsts, planes, depth)
     mono_items = r.compositor_launch()[0]
     assert mono_items == 4 * 2 * 129
-    assert_eyes(stereo_device(r, cams, proj, vp, nf, "load", dsts, planes, depth), want, "64 x 4128")
+    got = stereo_frame(r, cams, [proj, proj], vp, nf, "load", dsts, call=r.RenderStereoLayers, depth=depth, occluders=planes, **PITCHED)
+    assert_eyes(with_planes(got, depth), want, "64 x 4128")
     assert r.compositor_launch()[0] == mono_items            # two renders, not one chain
 
 
@@ -594,7 +496,7 @@ def test_refused_combinations_say_why_and_leave_the_context_usable():
     r.Sort(*view)
     plain = r.Render(*view)
     plane = mixed_plane(r, view)
-    want = layers_host(r, view, "clear", plane)
+    want = host_frame(r, view, "clear", call=r.RenderLayers, depth=True, occluder=plane)
     fbs = [torch.full((H, W, 4), SENTINEL, dtype=torch.float32, device="cuda:0") for _ in range(2)]
     zbs = [torch.full((H, W + 8), SENTINEL, dtype=torch.float32, device="cuda:0") for _ in range(2)]
     obs = [torch.from_numpy(plane).to("cuda:0") for _ in range(2)]
@@ -624,9 +526,9 @@ def test_refused_combinations_say_why_and_leave_the_context_usable():
             assert untouched()
         r.RenderLayers(*view)                               # without planes it is the plain Render of that configuration: it works
         switch(False)
-        same(r.Render(*view), plain)
-        got = layers_host(r, view, "clear", plane)
-        same(got[0], want[0]); same(got[1], want[1])
+        same_bits(r.Render(*view), plain)
+        got = host_frame(r, view, "clear", call=r.RenderLayers, depth=True, occluder=plane)
+        same_bits(got[0], want[0]); same_bits(got[1], want[1])
     # half-given pairs of stereo planes
     for kw in (dict(depth_ptrs=[zbs[0].data_ptr(), None]), dict(depth_ptrs=[None, zbs[1].data_ptr()]), dict(occluder_ptrs=[obs[0].data_ptr(), None]),
                dict(occluder_ptrs=[None, obs[1].data_ptr()]), dict(depth_ptrs=ptrs(zbs), occluder_ptrs=[None, obs[1].data_ptr()])):
@@ -659,9 +561,9 @@ def test_refused_combinations_say_why_and_leave_the_context_usable():
     r.RenderLayers(*view, out_ptr=fbs[0].data_ptr(), pitch_bytes=W * 16, depth_ptr=zbs[0].data_ptr(), depth_pitch_bytes=(W + 8) * 4,
                    occluder_ptr=obs[0].data_ptr())
     r.synchronize()
-    same(fbs[0].cpu().numpy(), want[0]); same(zbs[0].cpu().numpy()[:, :W].copy(), want[1])
+    same_bits(fbs[0].cpu().numpy(), want[0]); same_bits(zbs[0].cpu().numpy()[:, :W].copy(), want[1])
     assert (zbs[0].cpu().numpy()[:, W:] == SENTINEL).all()
-    same(r.Render(*view), plain)
+    same_bits(r.Render(*view), plain)
 
 
 def test_point_clouds_have_no_layers_frame():
@@ -704,5 +606,5 @@ def test_the_group_has_no_layers_frame():
     with pytest.raises(MsplatError) as e:
         g.RenderLayers(*view, depth=True, occluder=np.ones((H, W), np.float32))
     assert e.value.code == _capi.ERR_UNSUPPORTED
-    same(g.Render(*view), want)
+    same_bits(g.Render(*view), want)
     g.close()

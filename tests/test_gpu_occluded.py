@@ -3,109 +3,24 @@
 Per pixel p the frame is msplat_render's with every splat i with !(z_i < plane[p]) absent at p.  Checked here:
   planes that hide nothing / everything (bit for bit against msplat_render / the empty frame), the exact partition (a region of
   one level equals msplat_render of a context that holds only the splats in front of it, bit for bit at t_epsilon = 0), the
-  unchanged oracle (tests/test_occluded.occluded_reference through tests/test_gpu_target_mode.check_over, its bounds unchanged),
+  unchanged oracle (tests/render_cases.occluded_reference through tests/checks.check_over, its bounds unchanged),
   the tie rule on a splat whose z_w is exact, every execution shape against the plain occluded frame (bit for bit), refusals.
 
 The planes of the partition and oracle tests keep every level 2^-20 away from every drawn splat's z_w (asserted on the CPU in
 tests/test_occluded.py): the GPU's z_w may differ from the oracle's in the last bits."""
-import functools
-
 import numpy as np
 import pytest
 
 from oracle import oracle as orc
 from splatapult_amd import MsplatError, _capi, camera
 from tests import scenes
-from tests.test_depth_output import hand_placed
-from tests.test_gpu_parity import make_renderer
-from tests.test_gpu_target_mode import T_EPS, check_over, const_dst, random_dst, render_host, scene, view_of
-from tests.test_occluded import (assert_plane_is_testable, choose_levels, definition_f64, four_level_plane, hand_placed_ramp,
-                                 hand_placed_splats, occluded_reference, scene_splats, window_depth)
+from tests.checks import T_EPS, check_over
+from tests.gpu_harness import PAD_COLOUR, device_frame, host_frame, make_renderer, mixed_plane, subset_renderer
+from tests.render_cases import (MODES, assert_plane_is_testable, choose_levels, const_dst, definition_f64, dst_for, empty_frame, four_levels,
+                                hand_placed, hand_placed_ramp, hand_placed_splats, occluded_reference, random_dst, reference_layers, scene,
+                                scene_splats, view_of)
 
 pytestmark = pytest.mark.gpu
-
-MODES = ("clear", "load", "premultiplied")
-NP_DTYPES = {"fp32": np.float32, "fp16": np.float16, "rgba8": np.uint8, "srgb8": np.uint8}
-PAD_COLOUR = 77               # what the padding of a pitched colour target holds (exact in every format)
-
-
-def dst_for(fmt, H, W, seed):
-    """finite destination pixels in the format's host dtype"""
-    if NP_DTYPES[fmt] == np.uint8:
-        return np.random.default_rng(seed).integers(0, 256, (H, W, 4)).astype(np.uint8)
-    return random_dst(H, W, seed, NP_DTYPES[fmt])
-
-
-def occluded_host(r, view, mode, plane, dst=None):
-    """one host-output occluded Render in `mode`; dst: what the array holds before (LOAD's destination)"""
-    cam, proj, vp, nf = view
-    r.set_target_mode(mode)
-    keep = plane.copy()
-    if dst is None:
-        out = r.Render(cam, proj, vp, nf, occluder=plane)
-    else:
-        out = np.ascontiguousarray(dst).copy()
-        r.Render(cam, proj, vp, nf, out=out, occluder=plane)
-    assert plane.tobytes() == keep.tobytes(), "the occluder plane is read-only"
-    return out
-
-
-def occluded_device(r, view, mode, dst, plane, pad=24, zpad=8):
-    """one device-output occluded Render into a pitched colour target, from a pitched plane whose padding holds NaN and 0 junk;
-    returns the image after checking that neither padding nor the plane changed"""
-    import torch
-    cam, proj, vp, nf = view
-    H, W = dst.shape[:2]
-    fb = torch.full((H, W + pad, 4), PAD_COLOUR, dtype=getattr(torch, np.dtype(dst.dtype).name), device="cuda:0")
-    fb[:, :W] = torch.from_numpy(np.ascontiguousarray(dst)).to("cuda:0")
-    zhost = np.zeros((H, W + zpad), np.float32)
-    zhost[:, W::2] = np.nan
-    zhost[:, :W] = plane
-    zb = torch.from_numpy(zhost).to("cuda:0")
-    torch.cuda.synchronize()
-    r.set_target_mode(mode)
-    r.Render(cam, proj, vp, nf, out_ptr=fb.data_ptr(), pitch_bytes=(W + pad) * 4 * fb.element_size(), occluder_ptr=zb.data_ptr(),
-             occluder_pitch_bytes=(W + zpad) * 4)
-    r.synchronize()
-    got = fb.cpu().numpy()
-    assert (got[:, W:] == PAD_COLOUR).all(), "mode %s wrote into the padding of a pitched target" % mode
-    assert zb.cpu().numpy().tobytes() == zhost.tobytes(), "the occluder plane is read-only"
-    return got[:, :W].copy()
-
-
-def mixed_plane(r, view, seed=0):
-    """a plane with everything in it, for the bit-for-bit comparisons between execution shapes: four levels from the quantiles of
-    the frame's own depth output (one call's output is another's input), that depth plane itself in one quadrant (varies per
-    pixel), a NaN block, a +inf block and a closed (0.0) block"""
-    r.set_target_mode("clear")
-    _, z = r.Render(*view, depth=True)
-    H, W = z.shape
-    hit = z[z < 1.0]
-    levels = np.quantile(hit, [0.2, 0.4, 0.6, 0.8]).astype(np.float32) if hit.size else np.full(4, 0.5, np.float32)
-    plane = np.empty((H, W), np.float32)
-    plane[:H // 2, :W // 2], plane[:H // 2, W // 2:], plane[H // 2:, :W // 2] = levels[0], levels[2], levels[3]
-    plane[H // 2:, W // 2:] = z[H // 2:, W // 2:]
-    plane[H // 3:H // 3 + 9, W // 5:W // 5 + 21] = np.nan
-    plane[H // 4:H // 4 + 7, W // 2 - 10:W // 2 + 13] = np.inf
-    plane[2 * H // 3:2 * H // 3 + 5, W // 3:W // 3 + 40] = 0.0
-    plane[::7, ::5] = levels[1]
-    return plane
-
-
-def subset_renderer(name_or_cloud, splats, level, **kw):
-    """a context that holds only the splats with (the oracle's) z_w < level, in the upload order of the full cloud"""
-    cloud = scene(name_or_cloud)[0] if isinstance(name_or_cloud, str) else name_or_cloud
-    aos = cloud.as_array() if hasattr(cloud, "as_array") else cloud
-    keep = np.sort(splats["index"][window_depth(splats) < level])
-    return make_renderer(np.ascontiguousarray(aos[keep]), **kw), keep.shape[0]
-
-
-def empty_frame(mode, dst):
-    """what a Render with nothing visible leaves in `mode` over dst (any format's host dtype)"""
-    if mode == "load":
-        return dst
-    one = 255 if dst.dtype == np.uint8 else 1
-    return np.broadcast_to(np.array([0, 0, 0, one if mode == "clear" else 0], dst.dtype), dst.shape)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -120,12 +35,12 @@ def test_an_open_plane_gives_the_plain_frame(name, fmt):
     r.Sort(*view)
     dst = dst_for(fmt, H, W, 5)
     for mode in MODES:
-        want = render_host(r, view, mode, dst)
+        want = host_frame(r, view, mode, dst, call=r.Render)
         for level in (np.inf, 2.0):
             plane = np.full((H, W), level, np.float32)
-            np.testing.assert_array_equal(occluded_host(r, view, mode, plane, dst), want, err_msg="%s host %g" % (mode, level))
-            np.testing.assert_array_equal(occluded_device(r, view, mode, dst, plane), want, err_msg="%s device %g" % (mode, level))
-        np.testing.assert_array_equal(render_host(r, view, mode, dst), want)        # a plain Render afterwards is the plain Render
+            np.testing.assert_array_equal(host_frame(r, view, mode, dst, call=r.Render, occluder=plane), want, err_msg="%s host %g" % (mode, level))
+            np.testing.assert_array_equal(device_frame(r, view, mode, dst, call=r.Render, occluder=plane, fill=PAD_COLOUR), want, err_msg="%s device %g" % (mode, level))
+        np.testing.assert_array_equal(host_frame(r, view, mode, dst, call=r.Render), want)        # a plain Render afterwards is the plain Render
 
 
 @pytest.mark.parametrize("fmt", ["fp32", "fp16", "rgba8", "srgb8"])
@@ -134,30 +49,18 @@ def test_a_closed_plane_gives_the_empty_frame(fmt):
     r = make_renderer(cloud, fb_format=fmt)
     r.Sort(*view)
     dst = dst_for(fmt, H, W, 6)
-    assert not np.array_equal(render_host(r, view, "clear", dst), empty_frame("clear", dst))      # the view is not empty
+    assert not np.array_equal(host_frame(r, view, "clear", dst, call=r.Render), empty_frame("clear", dst))      # the view is not empty
     for mode in MODES:
         for level in (0.0, -1.0, np.nan):
             plane = np.full((H, W), level, np.float32)
             want = empty_frame(mode, dst)
-            assert occluded_host(r, view, mode, plane, dst).tobytes() == np.ascontiguousarray(want).tobytes(), (mode, level)
-            assert occluded_device(r, view, mode, dst, plane).tobytes() == np.ascontiguousarray(want).tobytes(), (mode, level)
+            assert host_frame(r, view, mode, dst, call=r.Render, occluder=plane).tobytes() == np.ascontiguousarray(want).tobytes(), (mode, level)
+            assert device_frame(r, view, mode, dst, call=r.Render, occluder=plane, fill=PAD_COLOUR).tobytes() == np.ascontiguousarray(want).tobytes(), (mode, level)
 
 
 # ------------------------------------------------------------------------------------------------
 # 3. exact partition
 # ------------------------------------------------------------------------------------------------
-
-@functools.lru_cache(maxsize=None)
-def four_levels(name):
-    """(plane, levels) of a scene's view: the four-level plane whose levels tests/test_occluded.py found testable"""
-    _, W, H, _ = view_of(name)
-    splats, _ = scene_splats(name)
-    levels = choose_levels(splats)
-    plane = four_level_plane(levels, W, H)
-    assert_plane_is_testable(splats, plane)
-    plane.setflags(write=False)
-    return plane, levels
-
 
 @pytest.mark.parametrize("name", ["hard", "dense"])
 def test_each_region_is_the_frame_of_the_splats_in_front_of_its_level(name):
@@ -169,9 +72,9 @@ def test_each_region_is_the_frame_of_the_splats_in_front_of_its_level(name):
     early = make_renderer(cloud)
     exact.Sort(*view); early.Sort(*view)
     assert exact.sort_count() == V
-    got0 = occluded_host(exact, view, "clear", plane)
-    got1 = occluded_host(early, view, "clear", plane)
-    plain = render_host(exact, view, "clear")
+    got0 = host_frame(exact, view, "clear", call=exact.Render, occluder=plane)
+    got1 = host_frame(early, view, "clear", call=early.Render, occluder=plane)
+    plain = host_frame(exact, view, "clear", call=exact.Render)
     if name == "dense":
         assert np.diff(exact.debug_tile_lists(want_pairs=False)[0].astype(np.int64)).max() > 128      # lists longer than two batches
     for v in levels:
@@ -179,7 +82,7 @@ def test_each_region_is_the_frame_of_the_splats_in_front_of_its_level(name):
         sub, n = subset_renderer(name, splats, v, t_epsilon=0.0)
         assert 0 < n < V
         sub.Sort(*view)
-        want = render_host(sub, view, "clear")
+        want = host_frame(sub, view, "clear", call=sub.Render)
         sub.close()
         # default t_epsilon: the walk stops at a batch boundary with T < t_epsilon left, the exact one goes on
         err = np.abs(got1[region].astype(np.float64) - want[region]).max()
@@ -197,12 +100,6 @@ def test_each_region_is_the_frame_of_the_splats_in_front_of_its_level(name):
 # 4. against the unchanged oracle
 # ------------------------------------------------------------------------------------------------
 
-@functools.lru_cache(maxsize=None)
-def reference_layers(name):
-    _, W, H, _ = view_of(name)
-    return occluded_reference(scene_splats(name)[0], four_levels(name)[0].copy(), W, H)
-
-
 @pytest.mark.parametrize("t_eps", [-1.0, 0.0])
 @pytest.mark.parametrize("name", ["sparse", "dense"])
 def test_the_occluded_frame_matches_the_oracle(name, t_eps):
@@ -214,10 +111,10 @@ def test_the_occluded_frame_matches_the_oracle(name, t_eps):
     assert r.sort_count() == scene_splats(name)[1]
     eps = T_EPS if t_eps < 0 else t_eps
     opaque = const_dst(H, W, (0, 0, 0, 1))                  # CLEAR is the blend over (0, 0, 0, 1)
-    check_over(occluded_host(r, view, "clear", plane), L, opaque, eps)
+    check_over(host_frame(r, view, "clear", call=r.Render, occluder=plane), L, opaque, eps)
     dst = random_dst(H, W, 11)
-    check_over(occluded_host(r, view, "load", plane, dst), L, dst, eps)
-    check_over(occluded_host(r, view, "premultiplied", plane), L, np.zeros((H, W, 4), np.float32), eps)
+    check_over(host_frame(r, view, "load", dst, call=r.Render, occluder=plane), L, dst, eps)
+    check_over(host_frame(r, view, "premultiplied", call=r.Render, occluder=plane), L, np.zeros((H, W, 4), np.float32), eps)
 
 
 @pytest.mark.parametrize("t_eps", [-1.0, 0.0])
@@ -232,11 +129,11 @@ def test_a_ramp_plane_matches_the_definition(t_eps):
     r.Sort(*view)
     assert r.sort_count() == splats.shape[0]
     eps = T_EPS if t_eps < 0 else t_eps
-    check_over(occluded_host(r, view, "clear", ramp), L, const_dst(H, W, (0, 0, 0, 1)), eps)
+    check_over(host_frame(r, view, "clear", call=r.Render, occluder=ramp), L, const_dst(H, W, (0, 0, 0, 1)), eps)
     dst = random_dst(H, W, 12)
-    check_over(occluded_host(r, view, "load", ramp, dst), L, dst, eps)
-    check_over(occluded_host(r, view, "premultiplied", ramp), L, np.zeros((H, W, 4), np.float32), eps)
-    assert np.abs(occluded_host(r, view, "clear", ramp) - render_host(r, view, "clear")).max() > 0.05      # the ramp hides something
+    check_over(host_frame(r, view, "load", dst, call=r.Render, occluder=ramp), L, dst, eps)
+    check_over(host_frame(r, view, "premultiplied", call=r.Render, occluder=ramp), L, np.zeros((H, W, 4), np.float32), eps)
+    assert np.abs(host_frame(r, view, "clear", call=r.Render, occluder=ramp) - host_frame(r, view, "clear", call=r.Render)).max() > 0.05      # the ramp hides something
 
 
 # ------------------------------------------------------------------------------------------------
@@ -258,14 +155,14 @@ def test_a_splat_at_the_planes_depth_is_hidden(z, zw, drawn):
                           np.array([3.0], np.float32), np.log(np.full((1, 3), 0.2, np.float32)), np.array([[1, 0, 0, 0]], np.float32), False)
     r = make_renderer(aos)
     r.Sort(*view)
-    plain = render_host(r, view, "clear")
+    plain = host_frame(r, view, "clear", call=r.Render)
     empty = empty_frame("clear", plain)
     assert (not np.array_equal(plain, empty)) == drawn
     level = np.float32(zw)
-    np.testing.assert_array_equal(occluded_host(r, view, "clear", np.full((H, W), level, np.float32)), empty)
-    np.testing.assert_array_equal(occluded_host(r, view, "clear", np.full((H, W), np.nextafter(level, np.float32(1)), np.float32)), plain)
+    np.testing.assert_array_equal(host_frame(r, view, "clear", call=r.Render, occluder=np.full((H, W), level, np.float32)), empty)
+    np.testing.assert_array_equal(host_frame(r, view, "clear", call=r.Render, occluder=np.full((H, W), np.nextafter(level, np.float32(1)), np.float32)), plain)
     if drawn:
-        np.testing.assert_array_equal(occluded_host(r, view, "clear", np.full((H, W), np.nextafter(level, np.float32(0)), np.float32)), empty)
+        np.testing.assert_array_equal(host_frame(r, view, "clear", call=r.Render, occluder=np.full((H, W), np.nextafter(level, np.float32(0)), np.float32)), empty)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -283,11 +180,11 @@ def test_two_pass_frames_equal_the_single_pass(share):
     dst = random_dst(H, W, 21)
     before = b.two_pass_state(share)[0]
     for mode in MODES:
-        want = occluded_host(a, view, mode, plane, dst)
-        np.testing.assert_array_equal(occluded_host(b, view, mode, plane, dst), want)
-        np.testing.assert_array_equal(occluded_device(b, view, mode, dst, plane), want)
+        want = host_frame(a, view, mode, dst, call=a.Render, occluder=plane)
+        np.testing.assert_array_equal(host_frame(b, view, mode, dst, call=b.Render, occluder=plane), want)
+        np.testing.assert_array_equal(device_frame(b, view, mode, dst, call=b.Render, occluder=plane, fill=PAD_COLOUR), want)
     assert b.two_pass_state(share)[0] == before + 6 and a.two_pass_state()[0] == 0
-    assert not np.array_equal(occluded_host(a, view, "clear", plane), render_host(a, view, "clear"))
+    assert not np.array_equal(host_frame(a, view, "clear", call=a.Render, occluder=plane), host_frame(a, view, "clear", call=a.Render))
     print("two-pass, share %g: %s" % (share, b.two_pass_info()))
 
 
@@ -305,14 +202,15 @@ def test_small_viewports(W, H):
     assert_plane_is_testable(splats, plane)
     r = make_renderer(cloud, t_epsilon=0.0)
     r.Sort(*view)
-    got = occluded_host(r, view, "clear", plane)
+    got = host_frame(r, view, "clear", call=r.Render, occluder=plane)
     dst = random_dst(H, W, 25)
     for mode in MODES:
-        np.testing.assert_array_equal(occluded_device(r, view, mode, dst, plane), occluded_host(r, view, mode, plane, dst))
+        np.testing.assert_array_equal(device_frame(r, view, mode, dst, call=r.Render, occluder=plane, fill=PAD_COLOUR),
+                                      host_frame(r, view, mode, dst, call=r.Render, occluder=plane))
     for v in levels:
         sub, n = subset_renderer(cloud, splats, v, t_epsilon=0.0)
         sub.Sort(*view)
-        np.testing.assert_array_equal(got[plane == v], render_host(sub, view, "clear")[plane == v])
+        np.testing.assert_array_equal(got[plane == v], host_frame(sub, view, "clear", call=sub.Render)[plane == v])
         sub.close()
 
 
@@ -334,9 +232,10 @@ def test_a_banded_context_reads_and_writes_its_own_rows_only():
     foreign[~owned] = np.nan                                # the other bands' rows of the plane: not this context's to read
     dst = random_dst(H, W, 51)
     for mode in MODES:
-        want = occluded_host(plain, view, mode, plane, dst)
-        assert not np.array_equal(want[owned], render_host(plain, view, mode, dst)[owned])
-        for got in (occluded_host(band, view, mode, foreign, dst), occluded_device(band, view, mode, dst, foreign)):
+        want = host_frame(plain, view, mode, dst, call=plain.Render, occluder=plane)
+        assert not np.array_equal(want[owned], host_frame(plain, view, mode, dst, call=plain.Render)[owned])
+        for got in (host_frame(band, view, mode, dst, call=band.Render, occluder=foreign),
+                    device_frame(band, view, mode, dst, call=band.Render, occluder=foreign, fill=PAD_COLOUR)):
             np.testing.assert_array_equal(got[owned], want[owned])
             assert got[~owned].tobytes() == dst[~owned].tobytes(), "mode %s touched rows of another band" % mode
 
@@ -364,7 +263,8 @@ def test_frames_in_flight_and_queued_calls_equal_one_context(shape):
         fly.synchronize()
         for k, view in enumerate(views):
             one.Sort(*view)
-            np.testing.assert_array_equal(fbs[k].cpu().numpy(), occluded_host(one, view, mode, planes[k], dsts[k]), err_msg="%s frame %d" % (mode, k))
+            np.testing.assert_array_equal(fbs[k].cpu().numpy(), host_frame(one, view, mode, dsts[k], call=one.Render, occluder=planes[k]),
+                                          err_msg="%s frame %d" % (mode, k))
 
 
 def test_persistent_waves_on_the_work_queue_equal_one_wave_per_item():
@@ -375,7 +275,7 @@ def test_persistent_waves_on_the_work_queue_equal_one_wave_per_item():
     plane = mixed_plane(a, view)
     dst = random_dst(H, W, 61)
     for mode in MODES:
-        np.testing.assert_array_equal(occluded_host(b, view, mode, plane, dst), occluded_host(a, view, mode, plane, dst))
+        np.testing.assert_array_equal(host_frame(b, view, mode, dst, call=b.Render, occluder=plane), host_frame(a, view, mode, dst, call=a.Render, occluder=plane))
     items, grid = b.compositor_launch()[:2]
     assert grid == 64 and items > grid                       # the work-queue regime
 
@@ -393,13 +293,13 @@ def test_host_output_survives_a_pair_buffer_overflow():
     dst = random_dst(H, W, 71)
     r = make_renderer(cloud)                                # automatic capacity
     r.Sort(*view)
-    got = occluded_host(r, view, "load", plane, dst)        # the context's first render
+    got = host_frame(r, view, "load", dst, call=r.Render, occluder=plane)        # the context's first render
     st = r.stats()
     assert st["pairs"] > (1 << 22) and st["pair_capacity"] >= st["pairs"], st      # it did overflow, and grew
     calm = make_renderer(cloud, pair_capacity=int(st["pairs"]) + 4096)               # never overflows
     calm.Sort(*view)
-    np.testing.assert_array_equal(got, occluded_host(calm, view, "load", plane, dst))
-    assert not np.array_equal(got, render_host(calm, view, "load", dst)) and not np.array_equal(got, dst)      # some hidden, some shown
+    np.testing.assert_array_equal(got, host_frame(calm, view, "load", dst, call=calm.Render, occluder=plane))
+    assert not np.array_equal(got, host_frame(calm, view, "load", dst, call=calm.Render)) and not np.array_equal(got, dst)      # some hidden, some shown
 
 
 # ------------------------------------------------------------------------------------------------
@@ -413,7 +313,7 @@ def test_refused_combinations_say_why_and_leave_the_context_usable():
     r.Sort(*view)
     plain = r.Render(*view)
     plane = mixed_plane(r, view)
-    want = occluded_host(r, view, "clear", plane)
+    want = host_frame(r, view, "clear", call=r.Render, occluder=plane)
     switches = [("msplat_set_depth_test", lambda on: r.set_depth_test(24 if on else 0)),
                 ("msplat_set_target_emulation", lambda on: r.set_target_emulation("rgba8" if on else None)),
                 ("probe", lambda on: r.set_tile_probe(on))]
@@ -427,7 +327,7 @@ def test_refused_combinations_say_why_and_leave_the_context_usable():
         r.Render(*view)                                     # the plain Render of that configuration still works
         switch(False)
         np.testing.assert_array_equal(r.Render(*view), plain)
-        np.testing.assert_array_equal(occluded_host(r, view, "clear", plane), want)
+        np.testing.assert_array_equal(host_frame(r, view, "clear", call=r.Render, occluder=plane), want)
     # a depth output and an occluder plane in one frame
     for kw in (dict(depth=True, occluder=plane), dict(depth=np.zeros((H, W), np.float32), occluder=plane), dict(out_ptr=1, depth_ptr=1, occluder_ptr=1)):
         with pytest.raises(MsplatError) as e:

@@ -14,6 +14,7 @@ Tolerances, stated once:
      Early termination adds <= t_eps * |c| (t_eps = 2^-14).
   alpha channel ............................................ == 1 exactly
   fp16 framebuffer ......................................... vs fp32 oracle: 2e-3 + 1 fp16 ulp
+The comparators are tests/checks.py's, the renderer and oracle helpers tests/gpu_harness.py's.
 """
 import os
 
@@ -23,106 +24,12 @@ import pytest
 from oracle import oracle as orc
 from splatapult_amd import SplatRenderer, camera
 from tests import scenes
+from tests.checks import TIGHT, check_fp16_image, check_image
+from tests.gpu_harness import _check_projection, _expected_tile_lists, bin_px, make_renderer, oracle_frame, run_frame, storage_aos
+from tests.render_cases import _covariance_by_rodrigues, random_points, smooth_sprite
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-KK = -0.5 * 1.4426950408889634
-
-
-def bin_px():
-    from splatapult_amd import _capi
-    return _capi.lib().msplat_tile_size()
-
-
-def make_renderer(cloud, srgb=False, **kw):
-    r = SplatRenderer(device=0, **kw)
-    assert r.Init(cloud, srgb, False), r.last_error()
-    return r
-
-
-TIGHT = 5e-3          # max abs per channel
-# SURVEY 8c states rel 1e-5 for conic and colour: asserted as stated, relative to max(|x|, floor) because conic entries and SH
-# colours pass through zero.  Measured on the MI355X (r4, every _check_projection call of the suite, 176 k splats): worst relative
-# error 0 -- project_kernel evaluates the oracle's operation order without contraction, so these values are bit-identical.
-CONIC_RTOL, CONIC_FLOOR = 1e-5, 1e-3
-RGB_RTOL, RGB_FLOOR = 1e-5, 1e-3
-WORST = {"conic": 0.0, "rgb": 0.0}
-
-
-def check_image(img, ref, max_abs=TIGHT, mean_abs=1e-4, frac=0.999, tol=1e-4, budget=None):
-    """budget: per-pixel threshold-flip allowance from orc.composite_flip (None = plain max_abs bound)"""
-    assert img.shape == ref.shape
-    d = np.abs(img.astype(np.float64) - ref.astype(np.float64))
-    rgb = d[..., :3]
-    assert np.isfinite(img).all()
-    within = (rgb <= tol).mean()
-    assert within >= frac, "only %.5f of values within %g (max %.3g)" % (within, tol, rgb.max())
-    assert rgb.mean() <= mean_abs, "mean |diff| %.3g" % rgb.mean()
-    worst = rgb.max(axis=-1)
-    over = worst > max_abs
-    if over.any():
-        assert budget is not None, "max |diff| %.3g in %d pixel(s), no threshold-flip budget given" % (worst.max(), over.sum())
-        unexplained = over & (worst > max_abs + budget.astype(np.float64))
-        assert not unexplained.any(), "%d pixel(s) above %g not explained by a w ~ 1/256 flip (max %.3g, budget there %.3g)" % (
-            unexplained.sum(), max_abs, worst[unexplained].max(), budget[unexplained].max())
-        print("check_image: %d pixel(s) above %g, all within the oracle's threshold-flip budget (max %.3g)"
-              % (over.sum(), max_abs, worst.max()))
-    assert (img[..., 3] == 1.0).all()              # the kernels write alpha = 1 exactly (app.cpp:158-160: cleared to 1, blended to 1)
-
-
-def check_fp16_image(img, ref, budget):
-    """RGBA16F target against the fp32 oracle: 2e-3 + 1 fp16 ulp (the target is rounded once; the reference's
-    ROP rounds after every blend), threshold flips explained like in check_image"""
-    assert img.dtype == np.float16
-    ulp = np.abs(ref[..., :3]) * 2.0 ** -10
-    d = np.abs(img[..., :3].astype(np.float32) - ref[..., :3])
-    assert (d <= 2e-3 + ulp + budget[..., None]).all(), "max excess %.3g" % (d - 2e-3 - ulp - budget[..., None]).max()
-    assert (d <= 2e-3 + ulp).mean() > 0.999
-    assert (img[..., 3] == 1).all()
-
-
-_STORAGE_CACHE = {}
-
-
-def storage_aos(r, aos):
-    """(the cloud in the renderer's STORAGE order, the permutation slot -> upload index or None).  Large clouds are stored in
-    Morton order (msplat_config.spatial_order) and splats with EQUAL depth keys are drawn in ascending storage slot: the
-    reference's tie order is undefined (atomic slots, presort_compute.glsl:50); ours is reproduced by feeding the oracle the
-    cloud in that order.  Everything the renderer reports is in upload numbering, so oracle indices are mapped with order[idx]."""
-    order = r.storage_order()
-    if order is None:
-        return aos, None
-    key = (aos.shape, float(aos[0, 0]), float(aos[-1, 5]), float(aos[aos.shape[0] // 2, 17]), int(order[:97].sum()), int(order[-97:].sum()))
-    hit = _STORAGE_CACHE.get("last")
-    if hit is None or hit[0] != key:
-        _STORAGE_CACHE["last"] = hit = (key, np.ascontiguousarray(aos[order]))
-    return hit[1], order
-
-
-def oracle_frame(aos, full_sh, cam, proj, vp, nf, render_cam=None, render_proj=None, srgb=False, nthreads=16,
-                 row0=0, row1=None, r=None):
-    """oracle Sort + Render with the per-pixel threshold-flip budget: dict(V, image, budget, splats, sorted_*).
-    r: the renderer whose storage order the oracle is to follow (storage_aos); sorted_idx comes back in upload numbering"""
-    order = None
-    if r is not None:
-        aos, order = storage_aos(r, aos)
-    ref = orc.render_frame(aos, full_sh, cam, proj, vp, nf, render_cam=render_cam, render_proj=render_proj, srgb=srgb,
-                           nthreads=nthreads, want_image=False, want_splats=True)
-    if order is not None:
-        ref["sorted_idx"] = order[ref["sorted_idx"]]
-    W, H = int(vp[2]), int(vp[3])
-    ref["image"], ref["budget"] = orc.composite_flip(ref["splats"], W, H, nthreads=nthreads, row0=row0, row1=row1)
-    return ref
-
-
-def run_frame(cloud, view, full_sh=True, srgb=False, **kw):
-    cam, proj, vp, nf = view
-    r = make_renderer(cloud, srgb=srgb, **kw)
-    r.Sort(cam, proj, vp, nf)
-    img = r.Render(cam, proj, vp, nf)
-    ref = oracle_frame(cloud.as_array(), full_sh, cam, proj, vp, nf, srgb=srgb, r=r)
-    return r, img, ref
 
 
 # ------------------------------------------------------------------------------------------------
@@ -179,55 +86,6 @@ def test_sort_everything_culled_and_empty_cloud():
 # stage 2: projection
 # ------------------------------------------------------------------------------------------------
 
-def _check_projection(r, ref, W, H):
-    rec, rect = r.debug_projected()
-    sp = ref["splats"]
-    assert rec.shape[0] == sp.shape[0]
-    tx0, ty0, tx1, ty1 = rect & 255, (rect >> 8) & 255, (rect >> 16) & 255, rect >> 24
-    drawn = tx0 <= tx1
-    # a drawn splat is never one the geometry stage rejected
-    assert not (drawn & (sp["reject"] != 0)).any()
-    ok = sp["reject"] == 0
-    np.testing.assert_allclose(rec[ok, 0], sp["px"][ok], atol=1e-3, rtol=0)
-    np.testing.assert_allclose(rec[ok, 1], sp["py"][ok], atol=1e-3, rtol=0)
-    inv = sp["inv"][ok]
-    exp_conic = np.stack([KK * inv[:, 0], KK * (inv[:, 1] + inv[:, 2]), KK * inv[:, 3]], axis=1)
-    # worst relative error over the splats (|x| below the absolute floor counts from the floor): printed (-rP shows it), so the
-    # tolerance below is a measured one, not a guess
-    def rel(a, b, floor):
-        a, b = a.astype(np.float64), b.astype(np.float64)
-        return float((np.abs(a - b) / np.maximum(np.abs(b), floor)).max()) if a.size else 0.0
-    rc, rg = rel(rec[ok, 2:5], exp_conic, CONIC_FLOOR), rel(rec[ok, 6:9], sp["rgb"][ok], RGB_FLOOR)
-    WORST["conic"], WORST["rgb"] = max(WORST["conic"], rc), max(WORST["rgb"], rg)
-    print("projection parity: worst rel conic %.3g, colour %.3g over %d splats (suite so far: %.3g / %.3g)"
-          % (rc, rg, int(ok.sum()), WORST["conic"], WORST["rgb"]))
-    assert rc <= CONIC_RTOL, "conic rel error %.3g > %g" % (rc, CONIC_RTOL)
-    assert rg <= RGB_RTOL, "colour rel error %.3g > %g" % (rg, RGB_RTOL)
-    np.testing.assert_array_equal(rec[ok, 9], sp["alpha"][ok])
-    # footprint: every pixel with w > 1/256 lies within rho*sqrt(cov_xx) of the centre
-    alpha = sp["alpha"].astype(np.float64)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        rho2 = 2.0 * np.log(256.0 * alpha)
-    vis = ok & (rho2 > 0)
-    ex = np.sqrt(np.maximum(rho2, 0) * sp["cov"][:, 0])
-    ey = np.sqrt(np.maximum(rho2, 0) * sp["cov"][:, 3])
-    x0 = np.ceil(sp["px"] - ex - 0.5); x1 = np.floor(sp["px"] + ex - 0.5)
-    y0 = np.ceil(sp["py"] - ey - 0.5); y1 = np.floor(sp["py"] + ey - 0.5)
-    onscreen = vis & (x1 >= 0) & (y1 >= 0) & (x0 <= W - 1) & (y0 <= H - 1) & (x0 <= x1) & (y0 <= y1)
-    # anything the oracle can light up must be drawn ...
-    assert drawn[onscreen].all()
-    B = bin_px()
-    xs0 = np.clip(x0, 0, W - 1) // B; xs1 = np.clip(x1, 0, W - 1) // B
-    ys0 = np.clip(y0, 0, H - 1) // B; ys1 = np.clip(y1, 0, H - 1) // B
-    m = onscreen
-    assert (tx0[m] <= xs0[m]).all() and (tx1[m] >= xs1[m]).all()
-    assert (ty0[m] <= ys0[m]).all() and (ty1[m] >= ys1[m]).all()
-    # ... and the rectangle is tight to within one tile
-    assert (xs0[m] - tx0[m] <= 1).all() and (tx1[m] - xs1[m] <= 1).all()
-    assert (ys0[m] - ty0[m] <= 1).all() and (ty1[m] - ys1[m] <= 1).all()
-    return rect
-
-
 @pytest.mark.parametrize("full_sh", [True, False])
 def test_projection_matches_oracle(full_sh):
     cloud = scenes.synth_cloud(6000, 21, full_sh=full_sh, log_scale_mean=-3.2)
@@ -248,18 +106,6 @@ def test_projection_hard_cases():
 # ------------------------------------------------------------------------------------------------
 # stage 3: tile lists (binning must reproduce the draw order inside every tile, exactly)
 # ------------------------------------------------------------------------------------------------
-
-def _expected_tile_lists(rect, tiles_x, tiles_y):
-    lists = [[] for _ in range(tiles_x * tiles_y)]
-    for rank, rc in enumerate(rect.tolist()):
-        tx0, ty0, tx1, ty1 = rc & 255, (rc >> 8) & 255, (rc >> 16) & 255, rc >> 24
-        if tx0 > tx1:
-            continue
-        for ty in range(ty0, ty1 + 1):
-            for tx in range(tx0, tx1 + 1):
-                lists[ty * tiles_x + tx].append(rank)
-    return lists
-
 
 @pytest.mark.parametrize("W,H", [(640, 360), (333, 211), (16, 16)])
 def test_tile_lists_exact(W, H):
@@ -442,20 +288,9 @@ def test_render_target_emulation_matches_oracle(rop, depth_bits, fb):
 # point-cloud renderer: PointRenderer::Render = presort + sort + textured sprites
 # ------------------------------------------------------------------------------------------------
 
-def random_points(n, seed):
-    rng = np.random.default_rng(seed)
-    pts = np.zeros((n, 8), np.float32)
-    pts[:, :3] = rng.normal(0, 1.2, size=(n, 3))
-    pts[:, 3] = 1.0
-    pts[:, 4:7] = rng.integers(0, 256, size=(n, 3)).astype(np.float32) / np.float32(255.0)
-    pts[:, 7] = 1.0
-    return pts
-
-
 @pytest.mark.parametrize("srgb,depth_bits,z", [(False, 0, 5.0), (True, 0, 5.0), (False, 24, 5.0), (False, 0, 1.5)])
 def test_point_renderer_matches_oracle(srgb, depth_bits, z):
     from splatapult_amd import PointRenderer
-    from tests.test_points import smooth_sprite
     pts = random_points(6000, 111)
     tex = smooth_sprite(64, 48, seed=2)                     # not square, not 2^k x 2^k all the way down
     W, H = 640, 360
@@ -1256,7 +1091,6 @@ def test_cpp_point_renderer_shim_matches_python(tmp_path):
     from PIL import Image
     from splatapult_amd import PointCloud, PointRenderer, _capi
     from tests.conftest import ROOT
-    from tests.test_points import smooth_sprite
     exe = str(tmp_path / "example_points")
     libdir = os.path.dirname(_capi.LIB_PATH)
     subprocess.run(["g++", "-std=c++17", "-I", ROOT, "-I", os.path.join(ROOT, "splatapult_amd", "host"),
@@ -1321,9 +1155,8 @@ def test_gpu_ingest_matches_host_import(tmp_path, n, full_sh):
 
 def test_gpu_ingest_covariance_by_rodrigues_rotation(tmp_path):
     """VERDICT r4 item 7c on the device: ingest_kernel's R S S^T R^T for random non-normalised quaternions against the property
-    Sigma = sum_i s_i^2 (R e_i)(R e_i)^T with R e_i from Rodrigues' formula in float64 (tests/test_host.py) -- no shared formula"""
+    Sigma = sum_i s_i^2 (R e_i)(R e_i)^T with R e_i from Rodrigues' formula in float64 (tests/render_cases.py) -- no shared formula"""
     from splatapult_amd import synthetic
-    from tests.test_host import _covariance_by_rodrigues
     rng = np.random.default_rng(78)
     n = 5000
     a = synthetic.generate(n, seed=6, full_sh=True)

@@ -39,7 +39,8 @@ from oracle import oracle as orc
 from splatapult_amd import SplatRenderer, _capi
 from tests import scenes
 from tests import sort_limit_cases as slc
-from tests.test_gpu_parity import _check_projection, _expected_tile_lists, check_image, oracle_frame
+from tests.checks import check_image
+from tests.gpu_harness import _check_projection, _expected_tile_lists, oracle_frame
 
 pytestmark = pytest.mark.gpu
 

@@ -7,81 +7,22 @@ PREMULTIPLIED (C, 1 - T), LOAD (fma(T, dst.rgb, C), fma(T, dst.a - 1, 1)).  Chec
   draw-order (depth-test) compositor, a host-output frame whose pair buffer has to grow, and the refused combinations.
 
 Tolerance against the oracle, derived: both oracle frames (C_ref and the white frame 1 - T_ref) carry the suite's TIGHT bound
-(tests/test_gpu_parity.py), early termination leaves T below t_eps instead of at its limit, and the alpha channel is the same
+(tests/checks.py), early termination leaves T below t_eps instead of at its limit, and the alpha channel is the same
 blend with "colour" 1 - T, so for all four channels  |err| <= TIGHT (1 + |dst|) + t_eps |dst|;  check_image's frac / mean
 conditions are scaled the same way, and a pixel above the bound has to be explained by the threshold-flip budgets of BOTH frames
-(budget_C + budget_white |dst|), as check_image does for one."""
-import functools
-
+(budget_C + budget_white |dst|), as check_image does for one: tests/checks.check_over.  The oracle recipe is
+tests/render_cases.oracle_layers."""
 import numpy as np
 import pytest
 
 from oracle import oracle as orc
 from splatapult_amd import MsplatError, SplatRenderer, SplatRendererGroup, _capi, camera
 from tests import scenes
-from tests.test_gpu_parity import TIGHT, check_image, make_renderer
+from tests.checks import T_EPS, TIGHT, check_image, check_over
+from tests.gpu_harness import device_frame, host_frame, make_renderer
+from tests.render_cases import const_dst, oracle_layers, random_dst, scene, view_of
 
 pytestmark = pytest.mark.gpu
-
-T_EPS = 1.0 / 16384.0           # msplat_config.t_epsilon's default
-
-
-@functools.lru_cache(maxsize=None)
-def scene(name):
-    """(cloud, W, H, view kwargs): ragged edge tiles and many empty tiles / the nasty attributes / saturated tiles and early exit"""
-    if name == "sparse":
-        return scenes.synth_cloud(20000, 302, log_scale_mean=-4.2), 517, 293, dict(z=7.0)
-    if name == "hard":
-        return scenes.cloud_from_attrs(scenes.hard_attrs(6000, 17)), 400, 300, dict(z=6.0, yaw=0.7)
-    if name == "dense":
-        return scenes.synth_cloud(120000, 301, log_scale_mean=-2.6), 640, 360, dict(z=0.8, yaw=2.0)
-    raise KeyError(name)
-
-
-def view_of(name, **over):
-    cloud, W, H, kw = scene(name)
-    return cloud, W, H, scenes.default_view(W, H, **dict(kw, **over))
-
-
-def random_dst(H, W, seed, dtype=np.float32, lo=0.0, hi=2.0):
-    """finite destination pixels, alpha included"""
-    return np.random.default_rng(seed).uniform(lo, hi, (H, W, 4)).astype(np.float32).astype(dtype)
-
-
-def const_dst(H, W, rgba, dtype=np.float32):
-    return np.broadcast_to(np.asarray(rgba, np.float32), (H, W, 4)).astype(dtype)
-
-
-def render_host(r, view, mode, dst=None):
-    """one host-output Render in `mode`; dst: what the array holds before (LOAD's destination)"""
-    cam, proj, vp, nf = view
-    r.set_target_mode(mode)
-    if dst is None:
-        return r.Render(cam, proj, vp, nf)
-    out = np.ascontiguousarray(dst).copy()
-    r.Render(cam, proj, vp, nf, out=out)
-    return out
-
-
-SENTINEL = -123.0
-
-
-def render_device(r, view, mode, dst, pad=24):
-    """one device-output Render into a target whose rows are `pad` pixels wider than the image: returns (image, padding after);
-    the padding starts as SENTINEL"""
-    import torch
-    cam, proj, vp, nf = view
-    H, W = dst.shape[:2]
-    tdt = torch.float16 if dst.dtype == np.float16 else torch.float32
-    fb = torch.full((H, W + pad, 4), SENTINEL, dtype=tdt, device="cuda:0")
-    fb[:, :W] = torch.from_numpy(np.ascontiguousarray(dst)).to("cuda:0")
-    torch.cuda.synchronize()
-    r.set_target_mode(mode)
-    r.Render(cam, proj, vp, nf, out_ptr=fb.data_ptr(), pitch_bytes=(W + pad) * 4 * fb.element_size())
-    r.synchronize()
-    got = fb.cpu().numpy()
-    return got[:, :W].copy(), got[:, W:].copy()
-
 
 # ------------------------------------------------------------------------------------------------
 # 1. identities that need no oracle
@@ -97,12 +38,9 @@ def test_identities_between_the_modes(name, target):
     r.Sort(*view)
     zeros, opaque = const_dst(H, W, (0, 0, 0, 0), dt), const_dst(H, W, (0, 0, 0, 1), dt)
     if target.startswith("host"):
-        run = lambda mode, dst: render_host(r, view, mode, dst)
+        run = lambda mode, dst: host_frame(r, view, mode, dst, call=r.Render)
     else:
-        def run(mode, dst):
-            img, padding = render_device(r, view, mode, dst)
-            assert (padding == SENTINEL).all(), "mode %s wrote into the padding of a pitched target" % mode
-            return img
+        run = lambda mode, dst: device_frame(r, view, mode, dst, call=r.Render)         # (asserts that the padding keeps its bytes)
     junk = random_dst(H, W, 5, dt)                     # CLEAR and PREMULTIPLIED read nothing: what the target held does not matter
     clear = run("clear", junk)
     pre = run("premultiplied", junk)
@@ -121,45 +59,6 @@ def test_identities_between_the_modes(name, target):
 # 2. / 3. against the unchanged oracle
 # ------------------------------------------------------------------------------------------------
 
-@functools.lru_cache(maxsize=None)
-def oracle_layers(name):
-    """C_ref (with alpha 1 - T_ref), T_ref and the two threshold-flip budgets of a scene's view, computed once"""
-    cloud, W, H, view = view_of(name)
-    cam, proj, vp, nf = view
-    ref = orc.render_frame(cloud.as_array(), True, cam, proj, vp, nf, nthreads=16, want_image=False, want_splats=True)
-    splats = ref["splats"]                                  # orc.project of the sorted splats
-    C_ref, bud_c = orc.composite_flip(splats, W, H, nthreads=16)
-    white = splats.copy()
-    white["rgb"] = 1.0
-    cover, bud_w = orc.composite_flip(white, W, H, nthreads=16)
-    T_ref = 1.0 - cover[..., 0].astype(np.float64)
-    layer = C_ref.astype(np.float64)
-    layer[..., 3] = cover[..., 0]                           # 1 - T_ref
-    for a in (layer, T_ref, bud_c, bud_w, cover):
-        a.setflags(write=False)
-    return dict(V=ref["V"], layer=layer, T=T_ref, bud_c=bud_c.astype(np.float64), bud_w=bud_w.astype(np.float64), cover=cover)
-
-
-def check_over(img, L, dst, t_eps, max_abs=TIGHT, mean_abs=1e-4, frac=0.999, tol=1e-4):
-    """img against layer + T_ref dst on all four channels; check_image's three conditions, each scaled by (1 + |dst|) plus
-    t_eps |dst| for the transmittance the early exit leaves"""
-    d64 = np.abs(dst.astype(np.float64))
-    want = L["layer"] + L["T"][..., None] * dst.astype(np.float64)
-    err = np.abs(img.astype(np.float64) - want)
-    assert np.isfinite(img).all()
-    print("check_over: max |err| %.3g, mean %.3g, t_eps %g" % (err.max(), err.mean(), t_eps))
-    within = (err <= tol * (1.0 + d64) + t_eps * d64).mean()
-    assert within >= frac, "only %.5f of values within the scaled %g (max %.3g)" % (within, tol, err.max())
-    assert err.mean() <= mean_abs * (1.0 + d64.mean()) + t_eps * d64.mean(), "mean |err| %.3g" % err.mean()
-    bound = max_abs * (1.0 + d64) + t_eps * d64
-    over = err > bound
-    if over.any():
-        flips = L["bud_c"][..., None] + L["bud_w"][..., None] * d64
-        bad = over & (err > bound + flips)
-        assert not bad.any(), "%d value(s) above the bound not explained by a w ~ 1/256 flip (max %.3g)" % (bad.sum(), err[bad].max())
-        print("check_over: %d value(s) above the bound, all within the two frames' threshold-flip budgets" % over.sum())
-
-
 @pytest.mark.parametrize("t_eps", [-1.0, 0.0])
 @pytest.mark.parametrize("name", ["sparse", "dense"])
 def test_load_and_premultiplied_match_the_oracle(name, t_eps):
@@ -170,9 +69,9 @@ def test_load_and_premultiplied_match_the_oracle(name, t_eps):
     assert r.sort_count() == L["V"]
     eps = T_EPS if t_eps < 0 else t_eps
     dst = random_dst(H, W, 11)
-    check_over(render_host(r, view, "load", dst), L, dst, eps)
+    check_over(host_frame(r, view, "load", dst, call=r.Render), L, dst, eps)
     zero = np.zeros((H, W, 4), np.float32)
-    pre = render_host(r, view, "premultiplied")
+    pre = host_frame(r, view, "premultiplied", call=r.Render)
     check_over(pre, L, zero, eps)                            # |err| <= TIGHT: alpha against 1 - T_ref, colour against C_ref
     if name == "dense":
         assert (pre[..., 3] > 1.0 - 2.0 * T_EPS).mean() > 0.5      # the early exit was taken: saturated pixels
@@ -191,7 +90,7 @@ def test_load_leaves_pixels_no_splat_reaches_bit_for_bit():
     odd = np.array([-0.0, 1e-40, -3e-39, np.finfo(np.float32).max, np.finfo(np.float32).tiny], np.float32)
     dst[::3, ::2] = odd[np.random.default_rng(13).integers(0, odd.size, dst[::3, ::2].shape)]
     assert (untouched[::3, ::2]).any()
-    for got in (render_host(r, view, "load", dst), render_device(r, view, "load", dst)[0]):
+    for got in (host_frame(r, view, "load", dst, call=r.Render), device_frame(r, view, "load", dst, call=r.Render)):
         seen = untouched & (got.view(np.uint32) == dst.view(np.uint32)).all(axis=-1)
         assert seen.sum() == untouched.sum(), "%d untouched pixel(s) changed" % (untouched.sum() - seen.sum())
         assert seen.mean() >= 0.01
@@ -212,7 +111,7 @@ def test_two_pass_frames_equal_the_single_pass(share):
     a.Sort(*view); b.Sort(*view)
     dst = random_dst(H, W, 21)
     for mode in ("load", "premultiplied"):
-        np.testing.assert_array_equal(render_host(b, view, mode, dst), render_host(a, view, mode, dst))
+        np.testing.assert_array_equal(host_frame(b, view, mode, dst, call=b.Render), host_frame(a, view, mode, dst, call=a.Render))
     assert b.two_pass_state(share)[0] == 2 and a.two_pass_state()[0] == 0
     print("two-pass, share %g: %s" % (share, b.two_pass_info()))
 
@@ -229,7 +128,7 @@ def test_render_stereo_equals_two_renders(fmt):
     r = make_renderer(cloud, fb_format=fmt)
     r.Sort(cams[0], proj, vp, nf)
     for mode in ("load", "premultiplied"):
-        want = [render_device(r, (cams[k], proj, vp, nf), mode, dsts[k], pad=0)[0] for k in range(2)]
+        want = [device_frame(r, (cams[k], proj, vp, nf), mode, dsts[k], call=r.Render, pad=0) for k in range(2)]
         fbs = [torch.from_numpy(dsts[k].copy()).to("cuda:0") for k in range(2)]
         torch.cuda.synchronize()
         r.RenderStereo(cams, [proj, proj], vp, nf, out_ptrs=[f.data_ptr() for f in fbs], pitch_bytes=W * 4 * fbs[0].element_size())
@@ -250,7 +149,7 @@ def test_host_output_stereo_goes_view_by_view_over_each_array():
     dsts = [random_dst(H, W, 33), random_dst(H, W, 34)]
     r = make_renderer(cloud)
     r.Sort(cams[0], proj, vp, nf)
-    want = [render_host(r, (cams[k], proj, vp, nf), "load", dsts[k]) for k in range(2)]
+    want = [host_frame(r, (cams[k], proj, vp, nf), "load", dsts[k], call=r.Render) for k in range(2)]
     with pytest.raises(ValueError):
         r.RenderStereo(cams, [proj, proj], vp, nf)
     fp = C.POINTER(C.c_float)
@@ -280,7 +179,7 @@ def test_four_frames_in_flight_equal_one_context():
         fly.synchronize()
         for k, view in enumerate(views):
             one.Sort(*view)
-            np.testing.assert_array_equal(fbs[k].cpu().numpy(), render_host(one, view, mode, dsts[k]), err_msg="%s frame %d" % (mode, k))
+            np.testing.assert_array_equal(fbs[k].cpu().numpy(), host_frame(one, view, mode, dsts[k], call=one.Render), err_msg="%s frame %d" % (mode, k))
 
 
 def test_a_banded_context_reads_and_writes_its_own_rows_only():
@@ -298,18 +197,17 @@ def test_a_banded_context_reads_and_writes_its_own_rows_only():
     band.Sort(*view)
     dst = random_dst(H, W, 51)
     for mode in ("load", "premultiplied"):
-        want = render_host(plain, view, mode, dst)
-        for got, padding in ((render_host(band, view, mode, dst), None), render_device(band, view, mode, dst)):
+        want = host_frame(plain, view, mode, dst, call=plain.Render)
+        for got in (host_frame(band, view, mode, dst, call=band.Render), device_frame(band, view, mode, dst, call=band.Render)):
             np.testing.assert_array_equal(got[owned], want[owned])
             assert got[~owned].tobytes() == dst[~owned].tobytes(), "mode %s touched rows of another band" % mode
-            assert padding is None or (padding == SENTINEL).all()
 
 
 def test_a_one_device_group_takes_premultiplied_and_refuses_load():
     cloud, W, H, view = view_of("hard")
     r = make_renderer(cloud)
     r.Sort(*view)
-    want = render_host(r, view, "premultiplied")
+    want = host_frame(r, view, "premultiplied", call=r.Render)
     g = SplatRendererGroup([0])
     assert g.Init(cloud), g.last_error()
     g.set_target_mode("premultiplied")
@@ -351,15 +249,15 @@ def test_depth_test_path_blends_over_the_target():
         check_image(opaque, np.concatenate([want_rgb, np.ones_like(want_rgb[..., :1])], axis=-1))
         assert np.abs(img[..., 3].astype(np.float64) - want_a).max() <= TIGHT
 
-    check(render_host(r, view, "load", dst), want, cover + (1.0 - cover) * dst[..., 3].astype(np.float64))
-    pre = render_host(r, view, "premultiplied")
+    check(host_frame(r, view, "load", dst, call=r.Render), want, cover + (1.0 - cover) * dst[..., 3].astype(np.float64))
+    pre = host_frame(r, view, "premultiplied", call=r.Render)
     check(pre, C_ref[..., :3], cover)
-    clear = render_host(r, view, "clear")
+    clear = host_frame(r, view, "clear", call=r.Render)
     np.testing.assert_array_equal(pre[..., :3], clear[..., :3])
     assert (clear[..., 3] == 1).all()
-    np.testing.assert_array_equal(render_host(r, view, "load", const_dst(H, W, (0, 0, 0, 0))), pre)
+    np.testing.assert_array_equal(host_frame(r, view, "load", const_dst(H, W, (0, 0, 0, 0)), call=r.Render), pre)
     # an opaque target stays exactly opaque (w + fl(1 - w) rounds to 1 for every w in [0, 1]), the colours are CLEAR's
-    np.testing.assert_array_equal(render_host(r, view, "load", const_dst(H, W, (0, 0, 0, 1))), clear)
+    np.testing.assert_array_equal(host_frame(r, view, "load", const_dst(H, W, (0, 0, 0, 1)), call=r.Render), clear)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -374,12 +272,12 @@ def test_host_output_load_render_survives_a_pair_buffer_overflow():
     dst = random_dst(H, W, 71)
     r = make_renderer(cloud)                                # automatic capacity
     r.Sort(*view)
-    got = render_host(r, view, "load", dst)                 # the context's first render
+    got = host_frame(r, view, "load", dst, call=r.Render)                 # the context's first render
     st = r.stats()
     assert st["pairs"] > (1 << 22) and st["pair_capacity"] >= st["pairs"], st      # it did overflow, and grew
     calm = make_renderer(cloud, pair_capacity=int(st["pairs"]) + 4096)               # never overflows
     calm.Sort(*view)
-    np.testing.assert_array_equal(got, render_host(calm, view, "load", dst))
+    np.testing.assert_array_equal(got, host_frame(calm, view, "load", dst, call=calm.Render))
     assert calm.stats()["pair_capacity"] == int(st["pairs"]) + 4096
 
 

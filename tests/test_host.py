@@ -13,6 +13,7 @@ from splatapult_amd import GaussianCloud, _capi, camera, synthetic
 from tests import ref_ply_cases
 from tests.golden.make_golden import PLY_NAMES
 from tests.ref_ply_cases import ref_read
+from tests.render_cases import _covariance_by_rodrigues
 
 import ctypes as C
 
@@ -225,25 +226,6 @@ def test_host_library_is_clean_under_asan_ubsan(tmp_path):
     tail = (p.stdout + p.stderr)[-3000:]
     assert p.returncode == 0, tail
     assert "0 failed expectation(s)" in p.stdout and "ERROR: AddressSanitizer" not in tail and "runtime error" not in tail
-
-
-def _covariance_by_rodrigues(rot, log_scale):
-    """Sigma = sum_i s_i^2 (R e_i)(R e_i)^T with R e_i from Rodrigues' rotation formula about the quaternion's axis, in float64 --
-    no quaternion-to-matrix closed form, no matrix products: independent of the restatements of glm's mat3_cast it checks"""
-    q = np.asarray(rot, np.float64)
-    q = q / np.linalg.norm(q, axis=1, keepdims=True)                 # glm::normalize (gaussiancloud.cpp:88-89); rot = (w, x, y, z)
-    w, v = q[:, 0], q[:, 1:]
-    sin_half = np.linalg.norm(v, axis=1)
-    angle = 2.0 * np.arctan2(sin_half, w)
-    axis = v / np.maximum(sin_half, 1e-300)[:, None]
-    s2 = np.exp(np.asarray(log_scale, np.float64)) ** 2              # scale = exp(log_scale) (gaussiancloud.cpp:254-361)
-    sigma = np.zeros((q.shape[0], 3, 3))
-    for i in range(3):
-        e = np.zeros((q.shape[0], 3)); e[:, i] = 1.0
-        c, s = np.cos(angle)[:, None], np.sin(angle)[:, None]
-        re = e * c + np.cross(axis, e) * s + axis * (axis * e).sum(1, keepdims=True) * (1.0 - c)
-        sigma += s2[:, i, None, None] * re[:, :, None] * re[:, None, :]
-    return sigma
 
 
 def test_covariance_of_random_quaternions_by_rodrigues_rotation():

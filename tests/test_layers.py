@@ -1,100 +1,25 @@
 """CPU side of msplat_render_layers / msplat_render_stereo_layers: the entry points are declared, exported and bound, refuse a NULL
 context without touching a device, the group refuses, and the oracle recipe the GPU tests compare the combined depth plane against
-(tests/test_gpu_layers.py imports layers_reference from here) is pinned by a float64 restatement of the definition:
+(tests/render_cases.layers_reference) is pinned by a float64 restatement of the definition:
 
     depth[p] = min(fma(T, d0, sum_{i: z_i < o} T_i w_i z_i), 1),   o = occluder[p],  d0 = o > 0 ? (o > 1 ? 1 : o) : 0  (NaN -> 0)
 
 -- the expected window depth of the splats that pass GL_LESS against the plane, blended over what the depth attachment holds.
-The recipe never changes the oracle: per level v of a plane with a few distinct values, tests/test_depth_output.depth_layers of the
+The recipe never changes the oracle: per level v of a plane with a few distinct values, tests/render_cases.depth_layers of the
 splats with z_w < v gives D and T, and the region of v reads D + T * d0(v).  The conditions the GPU tests lean on (every level well
 away from every drawn splat's z_w) are asserted here, where they can fail without a GPU."""
-import functools
 import inspect
 import os
 import re
 
 import numpy as np
 
-from oracle import oracle as orc
 from splatapult_amd import MsplatError, SplatRenderer, SplatRendererGroup, _capi, camera
-from tests import scenes
-from tests.test_depth_output import depth_layers, hand_placed
-from tests.test_gpu_target_mode import scene          # (importing the module needs no GPU: the scenes are built on the host)
-from tests.test_occluded import (assert_plane_is_testable, choose_levels, definition_f64, four_level_plane, hand_placed_ramp,
-                                 hand_placed_splats, window_depth)
+from tests.render_cases import (SMALL_VIEWPORTS, assert_plane_is_testable, blocks_plane, choose_levels, d0_of, definition_depth_f64,
+                                definition_f64, depth_layers, four_level_plane, hand_placed, hand_placed_ramp, hand_placed_splats,
+                                layers_reference, small_viewport_case, window_depth)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def d0_of(plane):
-    """what the depth attachment holds, as the depth plane's destination: the 8-bit targets' clamp rule, NaN -> 0 (float32 in and out)"""
-    o = np.asarray(plane, np.float32)
-    with np.errstate(invalid="ignore"):
-        return np.where(o > 0, np.where(o > 1, np.float32(1), o), np.float32(0)).astype(np.float32)
-
-
-def layers_reference(splats, plane, W, H, nthreads=16):
-    """The reference depth plane of orc.project'ed splats in draw order behind `plane` (few distinct values), in the form
-    tests/test_gpu_depth_output.check_plane takes: plane = D_ref + T_ref * d0 per region, T, and the two threshold-flip budgets
-    (the white frame's scaled by d0 <= 1, like |dst| in tests/test_gpu_target_mode.check_over)."""
-    assert plane.shape == (H, W) and plane.dtype == np.float32
-    zw = window_depth(splats)
-    d0 = d0_of(plane).astype(np.float64)
-    out_plane, T = d0.copy(), np.ones((H, W))                    # (a NaN hides everything: the region keeps d0 = 0, T 1)
-    bud_d, bud_w = np.zeros((H, W)), np.zeros((H, W))
-    for v in np.unique(plane[~np.isnan(plane)]):
-        region = plane == v
-        front = splats[zw < v]                                   # draw order kept
-        if front.shape[0] == 0:
-            continue
-        L = depth_layers(front, W, H, nthreads=nthreads)
-        D = L["plane"] - L["T"]                                  # depth_layers hands out D + T
-        out_plane[region] = D[region] + L["T"][region] * d0[region]
-        T[region] = L["T"][region]
-        bud_d[region], bud_w[region] = L["bud_d"][region], L["bud_w"][region] * d0[region]
-    out = dict(plane=out_plane, T=T, bud_d=bud_d, bud_w=bud_w, d0=d0)
-    for a in out.values():
-        a.setflags(write=False)
-    return out
-
-
-def definition_depth_f64(splats, plane, W, H):
-    """the definition of the combined depth plane, in float64: tests/test_occluded.definition_f64's walk with the window depth as
-    the colour, over d0.  Returns (depth, T)."""
-    z = splats.copy()
-    z["rgb"] = window_depth(splats)[:, None]
-    layer, T = definition_f64(z, plane, W, H)
-    return np.minimum(layer[..., 0] + T * d0_of(plane).astype(np.float64), 1.0), T
-
-
-def blocks_plane(levels, W, H):
-    """the four-level plane with a NaN, a 0, a +inf and a 2.0 block in it: d0 = 0, 0, 1, 1"""
-    plane = four_level_plane(levels, W, H)
-    plane[4:12, 6:30] = np.nan
-    plane[30:41, 10:22] = 0.0
-    plane[25:52, 50:70] = np.inf
-    plane[2:20, 60:90] = 2.0
-    return plane
-
-
-SMALL_VIEWPORTS = [(70, 45), (33, 17), (16, 16)]      # no multiples of 16 / smaller than a bin / a single tile
-
-
-@functools.lru_cache(maxsize=None)
-def small_viewport_case(W, H):
-    """the "sparse" cloud in a small viewport behind a plane of two levels, left and right of the middle column: (cloud, view,
-    the oracle's splats, plane, levels); the levels are testable (asserted here, on the CPU)"""
-    cloud = scene("sparse")[0]
-    view = cam, proj, vp, nf = scenes.default_view(W, H, z=7.0)
-    ref = orc.render_frame(cloud.as_array(), True, cam, proj, vp, nf, nthreads=4, want_image=False, want_splats=True)
-    splats = ref["splats"]
-    levels = choose_levels(splats, (0.3, 0.7))
-    plane = np.empty((H, W), np.float32)
-    plane[:, :W // 2], plane[:, W // 2:] = levels[0], levels[1]
-    assert_plane_is_testable(splats, plane)
-    splats.setflags(write=False)
-    plane.setflags(write=False)
-    return cloud, view, splats, plane, levels
 
 
 # ------------------------------------------------------------------------------------------------
@@ -189,7 +114,7 @@ def test_the_oracle_recipe_is_the_definition():
     for plane in (blocks, ramp):
         L = layers_reference(splats, plane, W, H, nthreads=4)
         depth, T = definition_depth_f64(splats, plane, W, H)
-        # tests/test_depth_output's tolerance: float32 against float64 over at most eight blends of values <= 1, and a fragment
+        # tests/test_depth_output.py's tolerance: float32 against float64 over at most eight blends of values <= 1, and a fragment
         # within 1e-4 of the discard threshold may fall on either side: the oracle's own flip budgets cover that
         tol = 8 * 4 * 2.0 ** -24 + L["bud_d"] + L["bud_w"]
         assert (np.abs(L["T"] - T) <= tol).all(), np.abs(L["T"] - T).max()

@@ -10,6 +10,7 @@ import pytest
 from oracle import oracle as orc
 from splatapult_amd import PointCloud, camera
 from tests import scenes
+from tests.render_cases import smooth_sprite
 
 
 def write_point_ply(path, xyz, rgb, doubles=False, with_color=True, extra=True):
@@ -141,19 +142,6 @@ def test_png_reader_roundtrips_the_library_writer(tmp_path):
     camera.write_image(p, img)
     exp = (np.clip(img[::-1], 0, 1) * 255.0 + 0.5).astype(np.uint8)
     np.testing.assert_array_equal(camera.read_image(p), exp)
-
-
-def smooth_sprite(w, h, seed=0):
-    rng = np.random.default_rng(seed)
-    yy, xx = np.mgrid[0:h, 0:w]
-    d = np.hypot((xx + 0.5) / w * 2 - 1, (yy + 0.5) / h * 2 - 1)
-    t = np.zeros((h, w, 4), np.float64)
-    t[..., 0] = 0.5 + 0.5 * np.sin(xx * 0.3)
-    t[..., 1] = (yy + 0.5) / h                       # vertical gradient: catches a missing row flip
-    t[..., 2] = 0.5 + 0.5 * np.cos(d * 5)
-    t[..., 3] = np.clip((1 - d) * 6, 0, 1)
-    t[..., :3] = np.clip(t[..., :3] + rng.normal(0, 0.02, size=(h, w, 3)), 0, 1)
-    return (t * 255 + 0.5).astype(np.uint8)
 
 
 def test_oracle_sprite_chain_and_single_point_geometry():

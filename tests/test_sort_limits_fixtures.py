@@ -10,7 +10,7 @@ import pytest
 
 from oracle import oracle as orc
 from tests import sort_limit_cases as slc
-from tests.test_gpu_parity import TIGHT, check_image
+from tests.checks import TIGHT, check_image
 
 
 def digit_range(p, B):
