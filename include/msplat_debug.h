@@ -64,6 +64,16 @@ int msplat_get_composite_work(msplat_ctx* ctx, msplat_composite_work* out);
  * pass's item count, the unfinished bins, exists on the device only; its grid is chosen the same way) ---- */
 int msplat_debug_get_compositor_launch(msplat_ctx* ctx, uint32_t out[4]);
 
+/* ---- the order in which persistent compositor waves walk the bins (grid < items above, unordered): slot s of the table holds a bin,
+ * and the slots of one residue class mod 8 -- the bins one XCD composites -- form compact blocks of bins, so that the bins a
+ * splat covers share an L2.  msplat_debug_bin_order: the table for a grid of tiles_x x rows bins (1 .. 256 each) as the host computes
+ * it with the compiled-in block shape, a permutation of 0 .. tiles_x * rows - 1 (no context, no device).
+ * msplat_debug_get_bin_order: the tiles_x * tiles_y words the context's latest compositor launch walked, read back from the device --
+ * that table for persistent waves, the heaviest-first order when every item had its own wave, 0, 1, 2, ... (storage order) for the persistent
+ * waves of a probed context, whose probe slot i stays storage-order item i.  After a two-pass Render: the first pass's ---- */
+int msplat_debug_bin_order(int32_t tiles_x, int32_t rows, uint32_t* out);
+int msplat_debug_get_bin_order(msplat_ctx* ctx, uint32_t* out, uint32_t cap);
+
 /* ---- msplat_band_exchange on ONE rank (tests on a one-GPU box): the runs of bin rows that rank `rank` of `world` owns travel
  * from src to dst through ncclSend / ncclRecv to the calling rank itself (`comm` = a 1-rank communicator) ---- */
 int msplat_debug_band_exchange_loopback(msplat_ctx* ctx, void* comm, int32_t kind, int32_t block_rows, int32_t world, int32_t rank,

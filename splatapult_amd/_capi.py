@@ -174,6 +174,8 @@ SYMBOLS = [
     ("msplat_get_two_pass_info", C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     ("msplat_get_composite_work", C.c_int, [C.c_void_p, C.POINTER(CompositeWork)]),
     ("msplat_debug_get_compositor_launch", C.c_int, [C.c_void_p, _U32P]),
+    ("msplat_debug_bin_order", C.c_int, [C.c_int32, C.c_int32, _U32P]),
+    ("msplat_debug_get_bin_order", C.c_int, [C.c_void_p, _U32P, C.c_uint32]),
     ("msplat_cloud_create", C.c_void_p, [C.c_int]),
     ("msplat_cloud_destroy", None, [C.c_void_p]),
     ("msplat_cloud_import_ply", C.c_int, [C.c_void_p, C.c_char_p]),

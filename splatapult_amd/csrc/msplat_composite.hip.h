@@ -15,7 +15,8 @@ namespace msplat {
 // in shard i % 32, a workgroup pulls from the shard of its index and, when that one is drained, from up to two
 // neighbours (checked with a plain load first, so drained shards are not hammered by the exiting waves).
 // Where the items are numbered heaviest-first (every item on its own wave) every shard hands out its
-// share heaviest-first too; persistent waves otherwise walk the bins in storage order (`tile_order` + 65536).  The first item
+// share heaviest-first too; persistent waves otherwise walk the bins in the XCD-local order of msplat_bin_order.h (`tile_order` +
+// 2 * 65536; a probed frame: storage order, `tile_order` + 65536).  The first item
 // of every workgroup is static (its own index): queue[s] counts only the items of shard s taken dynamically.
 __device__ __forceinline__ uint32_t queue_next(uint32_t* __restrict__ queue, uint32_t nitems)
 {
@@ -35,7 +36,7 @@ __device__ __forceinline__ uint32_t queue_next(uint32_t* __restrict__ queue, uin
     return 0xFFFFFFFFu;
 }
 
-// 0, 1, 2, ...: the bin order persistent compositor waves use (filled once, at msplat_create)
+// 0, 1, 2, ...: storage order, the bin order of a probed frame's persistent compositor waves (filled once, at msplat_create)
 __global__ __launch_bounds__(kThreads) void iota_kernel(uint32_t* __restrict__ dst)
 {
     dst[blockIdx.x * kThreads + threadIdx.x] = blockIdx.x * kThreads + threadIdx.x;
@@ -156,7 +157,9 @@ __global__ __launch_bounds__(kCompThreads, comp_occ(OCC, TWO_VIEWS, DEPTH, ZTEST
     // The four tiles of a bin walk the SAME list, and workgroup b runs on XCD b % 8 (each XCD has its own L2): inside every
     // group of 32 items the quadrants of one bin are the items r, r + 8, r + 16, r + 24, i.e. on one XCD, as the first
     // (static) item of a wave and -- shard = item % 32, home shard = workgroup % 32 -- as a pulled one.  Three of the four
-    // waves then find the list words and records in their XCD's L2 instead of fetching them from HBM again.
+    // waves then find the list words and records in their XCD's L2 instead of fetching them from HBM again.  XCD x therefore composites
+    // the slots with slot % 8 == x, in ascending order, and `order` (msplat_bin_order.h) gives each such class compact blocks of bins:
+    // the bins a splat covers meet its record in one L2.
     uint32_t slot = tpos >> 2, quadrant = tpos & 3u;
     if (tpos < (ntiles & ~31u)) {
         slot = (tpos >> 5) * 8u + (tpos & 7u);

@@ -28,6 +28,7 @@
 #include "../../include/msplat.h"
 #include "../../include/msplat_debug.h"
 #include "../host/two_pass_controller.hpp"
+#include "msplat_bin_order.h"
 
 using namespace msplat;
 
@@ -210,8 +211,13 @@ struct msplat_ctx {
     Buf sprite;
     SpriteParams sprite_params{};
     Buf tile_start; // uint32[65537]
-    Buf tile_order; // uint32[65536] bins by descending list length, then uint32[65536] = 0, 1, 2, ... (the order used when persistent
-                    // waves pull the items dynamically: measured, the heaviest-first order buys nothing there)
+    Buf tile_order; // uint32[65536] bins by descending list length, then uint32[65536] = 0, 1, 2, ... (storage order), then uint32[65536]
+                    // = the XCD-local order persistent waves walk (msplat_bin_order.h), built for bin_order_tx x bin_order_rows bins
+    int bin_order_tx = 0, bin_order_rows = 0;     // 0 x 0: none yet
+    uint32_t* bin_order_host = nullptr;      // pinned: what the latest upload of that table reads ...
+    hipEvent_t bin_order_ev = nullptr;       // ... and the event behind it
+    const uint32_t* comp_order = nullptr;    // msplat_debug_get_bin_order: the table of the latest compositor launch and its bins
+    uint32_t comp_order_bins = 0;
     HistTable hist1;      // column pass
     Buf pairsA, pairsB;   // uint32[pair_cap]
     uint64_t pair_cap = 0;
@@ -576,7 +582,7 @@ int msplat_create(msplat_ctx** out, const msplat_config* cfg)
     if (rc == MSPLAT_OK) rc = buf_alloc(ctx, ctx->tile_start, (65536 + 1024 + 16) * sizeof(uint32_t));
     if (rc == MSPLAT_OK) rc = buf_alloc(ctx, ctx->bincnt, (65536 + 1024 + 16) * sizeof(uint32_t));
     if (rc == MSPLAT_OK && hipMemsetAsync(ctx->bincnt.p, 0, ctx->bincnt.bytes, ctx->stream) != hipSuccess) rc = MSPLAT_ERR_HIP;
-    if (rc == MSPLAT_OK) rc = buf_alloc(ctx, ctx->tile_order, 2 * 65536 * sizeof(uint32_t));
+    if (rc == MSPLAT_OK) rc = buf_alloc(ctx, ctx->tile_order, 3 * 65536 * sizeof(uint32_t));
 
     if (c.compositor_waves > 0) { ctx->comp_waves = std::max(64, (int)c.compositor_waves); ctx->comp_waves_auto = false; }
     if (rc == MSPLAT_OK) {
@@ -670,6 +676,8 @@ void msplat_destroy(msplat_ctx* ctx)
     ctx->store.reset();
     if (ctx->join_ev) (void)hipEventDestroy(ctx->join_ev);
     if (ctx->h_flags) (void)hipHostFree(ctx->h_flags);
+    if (ctx->bin_order_host) (void)hipHostFree(ctx->bin_order_host);
+    if (ctx->bin_order_ev) (void)hipEventDestroy(ctx->bin_order_ev);
     for (Buf* b : ctx->bufs) buf_free(ctx, *b);
     if (ctx->ev_ok)
         for (auto& set : ctx->ev)
@@ -1377,7 +1385,7 @@ static void issue_binning(RenderChain& rc, int keep_overflow, int occ_pass)
     // pass 2: stable partition by tile row (one generic radix pass on the top byte); words become (tx<<24)|rank
     // The heaviest-first order of the bins only pays when every work item has its own wave (the hardware then starts the
     // waves in item order: 83 -> 97 us without it at config 2); persistent waves that pull items from the queue balance
-    // themselves: they walk the bins in storage order (`tile_order` + 65536 holds 0, 1, 2, ...).
+    // themselves: they walk the bins in the XCD-local order (ensure_bin_order).
     const bool wave_comp = !draw_order_frame(ctx);
     const uint32_t comp_items = (uint32_t)ntiles * 4u;
     // (every item on its own wave up to 20 k items, 40 k for two views in one chain: BASELINE configs[4] has 2 x 17.6 k)
@@ -1402,6 +1410,28 @@ static void issue_binning(RenderChain& rc, int keep_overflow, int occ_pass)
     rc.ordered = ordered;
     rc.comp_items = comp_items;
     rc.comp_pool = comp_pool;
+}
+
+// The XCD-local bin order (msplat_bin_order.h) for a grid of tiles_x x rows bins -- rows as the compositor indexes them: stacked for two
+// views in one chain, owned virtual rows for a banded context -- at tile_order + 2 * 65536.  Built on the host and uploaded on the
+// context's stream only when the geometry differs from the table's: a steady-state frame issues nothing.
+static int ensure_bin_order(msplat_ctx* ctx, int tiles_x, int rows, hipStream_t s)
+{
+    if (ctx->bin_order_tx == tiles_x && ctx->bin_order_rows == rows) return MSPLAT_OK;
+    if (!ctx->bin_order_host) {
+        HIP_TRY(ctx, hipHostMalloc((void**)&ctx->bin_order_host, 65536 * sizeof(uint32_t), hipHostMallocDefault));
+        HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->bin_order_ev, hipEventDisableTiming));
+    } else {
+        HIP_TRY(ctx, hipEventSynchronize(ctx->bin_order_ev));      // the upload before this one has read the host copy (long ago)
+    }
+    bin_order_xcd(tiles_x, rows, kBinBlockW, kBinBlockH, ctx->bin_order_host);
+    ctx->bin_order_tx = ctx->bin_order_rows = 0;
+    HIP_TRY(ctx, hipMemcpyAsync((uint32_t*)ctx->tile_order.p + 2 * 65536, ctx->bin_order_host, (size_t)tiles_x * rows * sizeof(uint32_t),
+                                hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipEventRecord(ctx->bin_order_ev, s));
+    ctx->bin_order_tx = tiles_x;
+    ctx->bin_order_rows = rows;
+    return MSPLAT_OK;
 }
 
 // fragment stage + blend over the bin lists: the splat compositor (front to back), the draw-order compositor of the emulations,
@@ -1434,6 +1464,8 @@ static int issue_compositor(RenderChain& rc, int occ_pass, int ev_c0, int ev_c1)
         ctx->comp_launch[1] = draw_order ? (uint32_t)cgrid : std::min(comp_items, comp_pool);
         ctx->comp_launch[2] = ordered ? 1u : 0u;
         ctx->comp_launch[3] = ctx->point_mode ? 2u : draw_order ? 1u : 0u;
+        ctx->comp_order = (const uint32_t*)ctx->tile_order.p;      // (the splat compositor names its table below)
+        ctx->comp_order_bins = (uint32_t)ntiles;
     }
     // (frames in flight: serialising the compositor launches of the contexts sharing a cloud with an event
     //  gate was measured r1 -- no gain over letting the hardware queues interleave them, dropped)
@@ -1470,9 +1502,17 @@ static int issue_compositor(RenderChain& rc, int occ_pass, int ev_c0, int ev_c1)
         const uint32_t* ts = (const uint32_t*)ctx->tile_start.p;
         const uint32_t* pb = (const uint32_t*)ctx->pairsB.p;
         const float4* r2 = (const float4*)ctx->rec2d.p;
-        const uint32_t* ord = occ_pass == 2 ? (const uint32_t*)ctx->occ_unf.p : (const uint32_t*)ctx->tile_order.p + (ordered ? 0 : 65536);
+        // persistent waves walk the XCD-local order; a probed frame walks storage order, so that probe slot i stays storage-order item i
+        const bool xcd_order = !ordered && occ_pass != 2 && !probe;
+        if (xcd_order) {
+            const int rc_order = ensure_bin_order(ctx, fp.tiles_x, fp.tiles_y, s);
+            if (rc_order != MSPLAT_OK) return rc_order;
+        }
+        const uint32_t* ord = occ_pass == 2 ? (const uint32_t*)ctx->occ_unf.p
+                                            : (const uint32_t*)ctx->tile_order.p + (ordered ? 0 : xcd_order ? 2 * 65536 : 65536);
+        if (occ_pass != 2) { ctx->comp_order = ord; ctx->comp_order_bins = (uint32_t)ntiles; }
         // wave issue priority by item number where the items are numbered heaviest-first (every item on its own wave); none for
-        // persistent waves that walk the bins in storage order (r3, 4 frames in flight: none / by item number / by list length
+        // persistent waves, whose items are not numbered by weight (r3, in storage order, 4 frames in flight: none / by item number / by list length
         // = 5.82 / 5.76 / 5.79 k frames/s, i.e. no effect there)
         const int prio_mode = ordered ? 1 : 0;
         const int grid = (int)std::min<uint32_t>(comp_items, comp_pool);

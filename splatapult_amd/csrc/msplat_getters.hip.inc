@@ -332,6 +332,28 @@ int msplat_debug_get_compositor_launch(msplat_ctx* ctx, uint32_t out[4])
     return MSPLAT_OK;
 }
 
+// the order[slot] -> bin table the context's latest compositor launch walked (the first pass's of a two-pass frame), read back from
+// the device: tiles_x * tiles_y words
+int msplat_debug_get_bin_order(msplat_ctx* ctx, uint32_t* out, uint32_t cap)
+{
+    drain_async(ctx);
+    if (!ctx || !out) return fail(ctx, MSPLAT_ERR_INVALID_ARG, "NULL argument");
+    if (!ctx->has_render || !ctx->comp_order) return fail(ctx, MSPLAT_ERR_NO_SORT, "no render yet");
+    if (cap < ctx->comp_order_bins) return fail(ctx, MSPLAT_ERR_INVALID_ARG, "capacity %u < %u bins", cap, ctx->comp_order_bins);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    HIP_TRY(ctx, hipMemcpy(out, ctx->comp_order, (size_t)ctx->comp_order_bins * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return MSPLAT_OK;
+}
+
+// bin_order_xcd with the compiled-in block shape, on the host (no context, no device)
+int msplat_debug_bin_order(int32_t tiles_x, int32_t rows, uint32_t* out)
+{
+    if (!out || tiles_x < 1 || rows < 1 || tiles_x > 256 || rows > 256) return MSPLAT_ERR_INVALID_ARG;
+    bin_order_xcd(tiles_x, rows, kBinBlockW, kBinBlockH, out);
+    return MSPLAT_OK;
+}
+
 int msplat_debug_get_tile_lists(msplat_ctx* ctx, uint32_t* tile_start, uint32_t tile_cap,
                                 uint32_t* pairs, uint64_t pair_cap)
 {

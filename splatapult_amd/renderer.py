@@ -627,6 +627,13 @@ class SplatRenderer:
         _capi.check(self._ctx, self._lib.msplat_debug_get_compositor_launch(self._ctx, out))
         return tuple(int(v) for v in out)
 
+    def bin_order(self):
+        """the order[slot] -> bin table the current context's latest compositor launch walked, read back from the device
+        (msplat_debug_get_bin_order): one word per bin"""
+        out = np.zeros(max(self.compositor_launch()[0] // 4, 1), np.uint32)
+        _capi.check(self._ctx, self._lib.msplat_debug_get_bin_order(self._ctx, out.ctypes.data_as(C.POINTER(C.c_uint32)), out.shape[0]))
+        return out
+
     def two_pass_state(self, share=0.0):
         """(two-pass Renders so far, share of the visible splats the next one puts into its first pass) summed / taken over the
         contexts; share > 0 pins the share (msplat_debug_two_pass), 0 leaves it to the feedback loop"""
