@@ -1,14 +1,7 @@
 /*
- * msplat.h -- C ABI of libmsplat.so, the MI355X-native (gfx950 / CDNA4, HIP) replacement for the reference's
- * SplatRenderer::Sort()/Render() hot path.  This header is what an integrator binds; parity-test taps, probes and experiment
- * switches are in msplat_debug.h; the reasoning behind every default is in INTEGRATION.md (Appendix A) and DESIGN.md.
- *
- * The reference's seam is the C++ class SplatRenderer (src/splatrenderer.h:23-67) fed by GaussianCloud (src/gaussiancloud.h:17-91);
- * every entry point names the reference interface it replaces; splatapult_amd/host/msplat_host.hpp re-creates that class surface.
- *
- * Conventions (the reference's): matrices are float[16], column-major like glm; cameraMat = camera-to-world; viewport =
- * (x, y, W, H); nearFar = (near, far).  Functions return 0 (MSPLAT_OK) or a negative MSPLAT_ERR_* and never throw.  A context
- * is not thread-safe (the reference's single GL thread).  No torch / framework / HIP types cross this boundary.
+ * msplat.h -- C ABI of libmsplat.so, the MI355X-native (gfx950 / CDNA4, HIP) replacement for the reference's SplatRenderer::Sort()/Render() hot path.  This header is what an integrator binds; parity-test taps, probes and experiment switches are in msplat_debug.h; the reasoning behind every default is in INTEGRATION.md (Appendix A) and DESIGN.md.
+ * The reference's seam is the C++ class SplatRenderer (src/splatrenderer.h:23-67) fed by GaussianCloud (src/gaussiancloud.h:17-91); every entry point names the reference interface it replaces; splatapult_amd/host/msplat_host.hpp re-creates that class surface.
+ * Conventions (the reference's): matrices are float[16], column-major like glm; cameraMat = camera-to-world; viewport = (x, y, W, H); nearFar = (near, far).  Functions return 0 (MSPLAT_OK) or a negative MSPLAT_ERR_* and never throw.  A context is not thread-safe (the reference's single GL thread).  No torch / framework / HIP types cross this boundary.
  */
 #ifndef MSPLAT_H
 #define MSPLAT_H
@@ -132,6 +125,16 @@ int msplat_get_cloud_storage(const msplat_ctx* ctx);
  * radix sort; the sorted index list stays context state for the following renders.  Asynchronous: the reference's 4-byte
  * readback stall (splatrenderer.cpp:195-204) is not reproduced. */
 int msplat_sort(msplat_ctx* ctx, const float cameraMat[16], const float projMat[16], const float viewport[4], const float nearFar[2]);
+/* ---- per-splat visibility (INTEGRATION.md 19): hide splats without another upload.  For the context's FOLLOWING msplat_sort calls splat i (upload numbering) takes part iff mask(i) && crop(i); a hidden splat is exactly a splat the presort cull rejected: not in sort_count, sorted keys or indices, never projected, binned or composited.  Visible splats keep their keys, their relative order (ties by storage slot) and their upload indices.  msplat_render* draws the latest Sort: a change shows at the next Sort.  With nothing set a Sort launches and reads what it always did.
+ * Mask: n bytes, one per splat, nonzero = visible (a bool array); n must be the cloud's N (else MSPLAT_ERR_INVALID_ARG); NULL = no mask.  Crop: M = worldToCrop (column-major, affine: M[3], M[7], M[11], M[15] are not read) and a shape.  Per splat centre (x, y, z), every operation rounded to fp32, no fused multiply-add, in this order:
+ *   qx = ((M[0] x + M[4] y) + M[8] z) + M[12];  qy = ((M[1] x + M[5] y) + M[9] z) + M[13];  qz = ((M[2] x + M[6] y) + M[10] z) + M[14];  BOX: inside = |qx| <= 1 && |qy| <= 1 && |qz| <= 1;  SPHERE: inside = (qx qx + qy qy) + qz qz <= 1
+ * (a centre on the surface is inside; a NaN makes every comparison false).  crop(i) = inside, with MSPLAT_CROP_INVERT or-ed in = !inside.  Per context (frames in flight: set it on every context of the rotation), ordered with the context's frames on its stream: no drain, no race with frames in flight.  Any upload or msplat_attach_cloud drops the mask (the numbering is new) and keeps the crop, evaluated on the new positions.
+ * Costs one kernel at the next Sort after a change, 16 B (+ 1 B mask) per splat per context, 4 B per splat of a cloud stored in Morton order.  MSPLAT_ERR_UNSUPPORTED: the context holds a point cloud (it stays usable); _NO_CLOUD: a mask before the upload (a crop may come first); _INVALID_ARG: NULL context, unknown shape, non-finite M (rows 0-2), d_visible not memory of the context's device -- all before anything is launched or copied.  Out of scope: the device group, sub-range updates, bit-packed masks. */
+enum { MSPLAT_CROP_NONE = 0, MSPLAT_CROP_BOX = 1, MSPLAT_CROP_SPHERE = 2, MSPLAT_CROP_INVERT = 0x100 };
+int msplat_set_visibility(msplat_ctx* ctx, const uint8_t* visible, uint64_t n);             /* host memory; copied before return (waits at most for the PREVIOUS mask's copy) */
+int msplat_set_visibility_device(msplat_ctx* ctx, const uint8_t* d_visible, uint64_t n);    /* device memory of the context's device; asynchronous on the context's stream, never waits: the source stays valid until that work has run (msplat_synchronize / msplat_stream_wait) */
+int msplat_set_crop(msplat_ctx* ctx, const float worldToCrop[16], int32_t shape);           /* NULL or MSPLAT_CROP_NONE: no crop */
+int msplat_get_visibility(msplat_ctx* ctx, int32_t* has_mask, int32_t* crop_shape, uint64_t* hidden);   /* hidden: splats the latest Sort's plane hides (synchronises); any out pointer may be NULL */
 /* ---- SplatRenderer::Render (splatrenderer.cpp:315-343) plus the GL pipeline behind its glDrawElements: splat_vert / _geom / _frag.glsl and
  * the blend / clear state of app.cpp:144-164.  Writes W x H RGBA (float, half or 4 bytes), row 0 = GL bottom row, alpha = 1 (msplat_set_target_mode: or
  * over the target's contents).  out_is_device != 0: `rgba` is device memory, the call is asynchronous on the stream; else host memory, the
@@ -161,7 +164,6 @@ int msplat_render_stereo(msplat_ctx* ctx, const float cameraMat0[16], const floa
 int msplat_render_stereo_layers(msplat_ctx* ctx, const float cameraMat0[16], const float projMat0[16], const float cameraMat1[16], const float projMat1[16], const float viewport[4], const float nearFar[2], void* rgba0, void* rgba1, uint64_t pitch_bytes, float* depth0, float* depth1, uint64_t depth_pitch_bytes, const float* occluder0, const float* occluder1, uint64_t occluder_pitch_bytes, int out_is_device);
 /* blocks until everything queued on the context (and issued by its worker thread) has finished */
 int msplat_synchronize(msplat_ctx* ctx);
-
 /* ---- frames in flight.  The reference queues successive frames on one GL command stream and the driver overlaps them; here the overlap is
  * explicit: one context per frame in flight (own stream and per-frame buffers), the cloud uploaded into the first and attached to the others, frame k
  * on context k % depth.  Bit-identical to a single context.  The shims rotate (SetFramesInFlight).  Start with GPU_MAX_HW_QUEUES=8 (INTEGRATION.md 6). */
@@ -292,7 +294,6 @@ void msplat_mat4_inverse(const float m[16], float out[16]);
 void msplat_mat4_mul(const float a[16], const float b[16], float out[16]);
 void msplat_perspective(float fovy, float aspect, float zn, float zf, float out[16]);
 void msplat_create_projection(float tanL, float tanR, float tanU, float tanD, float zn, float zf, float out[16]);
-
 #ifdef __cplusplus
 }
 #endif

@@ -25,7 +25,8 @@ int msplat_debug_get_tile_lists(msplat_ctx* ctx, uint32_t* tile_start, uint32_t 
  * which msplat_create probes but the hardware does not document (msplat_config.rank_mode = MSPLAT_RANK_BALLOT selects the ballot path) */
 int msplat_debug_verify_order(msplat_ctx* ctx, uint32_t* key_violations, uint32_t* list_violations);
 /* chunk-level cull for the latest Sort's camera: live / all bounding boxes (of 256 stored splats; 0 / 0 for a cloud in upload
- * order); *listed (may be NULL) = 1 when that Sort's first pass walked only the listed live boxes */
+ * order); *listed (may be NULL) = 1 when that Sort's first pass walked only the listed live boxes.  The boxes are the ones that Sort
+ * used: under msplat_set_visibility / msplat_set_crop the context's own, built over the visible splats */
 int msplat_debug_get_cull_boxes(msplat_ctx* ctx, uint32_t* live, uint32_t* total, int* listed);
 
 /* ---- two-pass frames (msplat_config.two_pass) ---- */

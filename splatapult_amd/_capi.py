@@ -30,6 +30,9 @@ CLOUD_STORAGE_NAMES = {**CLOUD_STORAGES, "sh_q8": STORAGE_SH_Q8}  # every name t
 # msplat_set_target_mode: overwrite with (C, 1); blend over the target's contents; write the layer (C, 1 - T)
 TARGET_CLEAR, TARGET_LOAD, TARGET_PREMULTIPLIED = 0, 1, 2
 TARGET_MODES = {"clear": TARGET_CLEAR, "load": TARGET_LOAD, "premultiplied": TARGET_PREMULTIPLIED}
+# msplat_set_crop: the shape, MSPLAT_CROP_INVERT or-ed in
+CROP_NONE, CROP_BOX, CROP_SPHERE, CROP_INVERT = 0, 1, 2, 0x100
+CROP_SHAPES = {"box": CROP_BOX, "sphere": CROP_SPHERE}
 # "weighted": contiguous bands, rank 0 (the gather's root) weighted block_rows PERCENT of another rank (msplat.h)
 BAND_KINDS = {"contiguous": BANDS_CONTIGUOUS, "interleaved": BANDS_INTERLEAVED, "block": BANDS_BLOCK_INTERLEAVED,
               "weighted": BANDS_ROOT_WEIGHTED}
@@ -162,6 +165,10 @@ SYMBOLS = [
     ("msplat_get_sorted_indices", C.c_int, [C.c_void_p, _U32P, C.c_uint32]),
     ("msplat_get_sorted_keys", C.c_int, [C.c_void_p, _U32P, C.c_uint32]),
     ("msplat_get_storage_order", C.c_int, [C.c_void_p, _U32P, C.c_uint64, C.POINTER(C.c_int)]),
+    ("msplat_set_visibility", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
+    ("msplat_set_visibility_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
+    ("msplat_set_crop", C.c_int, [C.c_void_p, _F16, C.c_int32]),
+    ("msplat_get_visibility", C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]),
     ("msplat_debug_get_cull_boxes", C.c_int, [C.c_void_p, _U32P, _U32P, C.POINTER(C.c_int)]),
     ("msplat_get_stats", C.c_int, [C.c_void_p, C.POINTER(Stats)]),
     ("msplat_get_timings", C.c_int, [C.c_void_p, C.POINTER(Timings)]),

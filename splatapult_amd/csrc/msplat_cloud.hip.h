@@ -407,4 +407,84 @@ __global__ __launch_bounds__(kThreads) void cull_boxes_kernel(const float4* __re
     }
 }
 
+// ---- per-splat visibility (msplat_set_visibility / msplat_set_crop, include/msplat.h).  A hidden splat is a splat pass 0 of the
+// sort rejects: the context's Sort reads a COPY of the position plane in which a hidden splat's x is a quiet NaN -- every comparison
+// of cull_key is then false -- and cull boxes built over the visible splats only.  Nothing else in the frame knows.
+constexpr int kCropBox = 1, kCropSphere = 2, kCropShapeMask = 0xFF, kCropInvert = 0x100;      // MSPLAT_CROP_*
+struct VisibilityArgs {
+    const float4* pos;          // the store's plane (storage order)
+    const uint8_t* mask;        // one byte per splat in UPLOAD numbering, nonzero = visible; nullptr: no mask
+    const uint32_t* order;      // slot -> upload index of a reordered store; nullptr: the store is in upload order
+    uint32_t n;
+    int shape;                  // MSPLAT_CROP_BOX / _SPHERE, | MSPLAT_CROP_INVERT; 0: no crop
+    float m[16];                // world -> crop space, column-major; row 3 is not read
+    float4* vis_pos;            // out: pos with x = NaN where hidden
+    CullBox* boxes;             // out: one box per kBoxSplats slots over the visible finite centres; hi.w (read by no kernel) = the
+                                // box's hidden splats, as a float: msplat_get_visibility sums them
+};
+
+// the crop rule of msplat.h, in cull_key's operation order (fp32, no contraction); false for a NaN centre with either shape
+__device__ __forceinline__ bool crop_inside(const float4 p, const float* m, int shape)
+{
+    const float qx = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(m[0], p.x), __fmul_rn(m[4], p.y)), __fmul_rn(m[8], p.z)), m[12]);
+    const float qy = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(m[1], p.x), __fmul_rn(m[5], p.y)), __fmul_rn(m[9], p.z)), m[13]);
+    const float qz = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(m[2], p.x), __fmul_rn(m[6], p.y)), __fmul_rn(m[10], p.z)), m[14]);
+    if ((shape & kCropShapeMask) == kCropSphere)
+        return __fadd_rn(__fadd_rn(__fmul_rn(qx, qx), __fmul_rn(qy, qy)), __fmul_rn(qz, qz)) <= 1.0f;
+    return fabsf(qx) <= 1.0f && fabsf(qy) <= 1.0f && fabsf(qz) <= 1.0f;
+}
+
+// one workgroup per box, one lane per stored slot: 16 + 16 + 1 (+ 4) bytes per splat, coalesced but for the mask bytes of a
+// reordered store (Morton neighbours: scattered over upload numbers).  The hidden count stays per box: one atomicAdd per workgroup
+// on ONE counter was measured first and was the kernel -- 23 k same-address atomics at 6 M splats, 255-280 us against 50-80 us
+// without them (EXPERIMENTS.md, round 21)
+__global__ __launch_bounds__(kThreads) void visibility_kernel(const VisibilityArgs a)
+{
+    static_assert(kBoxSplats == kThreads, "one lane per slot of a box");
+    __shared__ float s_red[7][kThreads / 64];
+    __shared__ uint32_t s_hid[kThreads / 64];
+    float r[7] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY, 0.0f};
+    const uint32_t slot = blockIdx.x * kBoxSplats + threadIdx.x;
+    bool hide = false;
+    if (slot < a.n) {
+        float4 p = a.pos[slot];
+        bool vis = true;
+        if (a.mask) vis = a.mask[a.order ? a.order[slot] : slot] != 0;
+        if (a.shape != 0) vis = vis && (crop_inside(p, a.m, a.shape) != ((a.shape & kCropInvert) != 0));
+        hide = !vis;
+        if (vis && isfinite(p.x) && isfinite(p.y) && isfinite(p.z)) {
+            r[0] = p.x; r[1] = p.y; r[2] = p.z; r[3] = p.x; r[4] = p.y; r[5] = p.z;
+            if (p.w > 0.0f) r[6] = p.w;                                     // (as cull_boxes_kernel: NaN never wins)
+        }
+        if (hide) p.x = __uint_as_float(0x7FC00000u);
+        a.vis_pos[slot] = p;
+    }
+    const uint32_t hid = (uint32_t)__popcll(__ballot(hide));
+    if ((threadIdx.x & 63) == 0) s_hid[threadIdx.x >> 6] = hid;
+    // the box: cull_boxes_kernel's reduction (written again, not shared: that kernel's registers stay as they were)
+#pragma unroll
+    for (int k = 0; k < 7; ++k) {
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) {
+            const float o = __shfl_xor(r[k], d, 64);
+            r[k] = k < 3 ? fminf(r[k], o) : fmaxf(r[k], o);
+        }
+        if ((threadIdx.x & 63) == 0) s_red[k][threadIdx.x >> 6] = r[k];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t h = s_hid[0];
+#pragma unroll
+        for (int w = 1; w < kThreads / 64; ++w) {
+            h += s_hid[w];
+#pragma unroll
+            for (int k = 0; k < 7; ++k) r[k] = k < 3 ? fminf(r[k], s_red[k][w]) : fmaxf(r[k], s_red[k][w]);
+        }
+        CullBox b;
+        b.lo = make_float4(r[0], r[1], r[2], r[6]);
+        b.hi = make_float4(r[3], r[4], r[5], (float)h);        // (h <= 256: exact)
+        a.boxes[blockIdx.x] = b;
+    }
+}
+
 }  // namespace msplat

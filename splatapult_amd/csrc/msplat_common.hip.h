@@ -655,7 +655,7 @@ constexpr int kBoxSplats = 256;          // stored splats per bounding box (four
 constexpr int kBoxGroup = 256;           // boxes per workgroup of box_cull_kernel = entries per segment of the live list
 struct CullBox {                         // 32 bytes
     float4 lo;                           // min x, y, z of the finite positions; .w = max footprint bound (pos4.w) of the box
-    float4 hi;                           // max x, y, z; .w unused.  lo.x > hi.x: no finite position in the box
+    float4 hi;                           // max x, y, z; .w read by no kernel (visibility_kernel: the box's hidden splats).  lo.x > hi.x: no finite position in the box
 };
 
 __device__ __forceinline__ bool box_live(const CullBox& b, const FrameParams& fp)

@@ -55,12 +55,17 @@ struct CloudStore {
     std::vector<uint32_t> order_host;
     Buf boxes;
     uint32_t nboxes = 0;
+    // order_host on the device, for visibility_kernel: a mask speaks upload numbering.  Made by the first mask set on a reordered
+    // store (ensure_order_dev), under mu: the contexts that share the store may belong to different threads
+    Buf order_dev;
+    std::mutex mu;
     ~CloudStore()
     {
         (void)hipSetDevice(device);
         if (pos4.p) (void)hipFree(pos4.p);
         if (recs.p) (void)hipFree(recs.p);
         if (boxes.p) (void)hipFree(boxes.p);
+        if (order_dev.p) (void)hipFree(order_dev.p);
     }
 };
 
@@ -183,6 +188,19 @@ struct msplat_ctx {
     int spatial_mode = 0;       // msplat_config.spatial_order: 0 auto, 1 always, 2 never
     bool last_sort_listed = false;   // the latest Sort's pass 0 walked the listed boxes only
     FrameParams last_sort_fp{};
+    // per-splat visibility (msplat_set_visibility / msplat_set_crop; msplat_cloud.hip.h, visibility_kernel): the position plane and
+    // the cull boxes the context's Sorts read INSTEAD of the store's while a mask or a crop is set.  Allocated by the set calls (and
+    // by an upload / attach under a crop), never by a Sort
+    Buf vis_pos4, vis_boxes;    // float4[N]: x = NaN where hidden; CullBox[N / kBoxSplats] over the visible splats
+    Buf vis_mask;               // uint8[N], upload numbering: the caller's mask, copied on the stream
+    bool has_mask = false;
+    int crop_shape = 0;         // MSPLAT_CROP_*; 0: no crop
+    float crop_mat[16]{};
+    bool vis_dirty = false;     // the plane is older than the mask, the crop or the cloud: the next Sort starts with visibility_kernel
+    bool vis_sorted = false;    // the latest Sort read the context's plane and boxes
+    uint8_t* vis_stage = nullptr;       // pinned: what the latest host mask's copy reads ...
+    size_t vis_stage_bytes = 0;
+    hipEvent_t vis_stage_ev = nullptr;  // ... and the event behind that copy
     uint32_t sort_parity = 0;
     bool tables_dirty = false;  // a launch failed: clear every self-cleaning table before the next frame
     // per-bin pair counts taken by the row pass's upsweep (r3): list offsets + work order (no kernel of their own)
@@ -678,6 +696,8 @@ void msplat_destroy(msplat_ctx* ctx)
     if (ctx->h_flags) (void)hipHostFree(ctx->h_flags);
     if (ctx->bin_order_host) (void)hipHostFree(ctx->bin_order_host);
     if (ctx->bin_order_ev) (void)hipEventDestroy(ctx->bin_order_ev);
+    if (ctx->vis_stage) (void)hipHostFree(ctx->vis_stage);
+    if (ctx->vis_stage_ev) (void)hipEventDestroy(ctx->vis_stage_ev);
     for (Buf* b : ctx->bufs) buf_free(ctx, *b);
     if (ctx->ev_ok)
         for (auto& set : ctx->ev)
@@ -958,11 +978,15 @@ static int clear_frame_tables(msplat_ctx* ctx)
     return MSPLAT_OK;
 }
 
-// box_cull_kernel over the store's boxes, for list_live_boxes and msplat_debug_get_cull_boxes; returns its workgroups
-static uint32_t launch_box_cull(msplat_ctx* ctx, const CloudStore* st, const FrameParams& fp, uint32_t* list, uint32_t* cnt)
+#include "msplat_visibility.hip.inc"
+
+// box_cull_kernel over the store's boxes or (vis) the context's own, for list_live_boxes and msplat_debug_get_cull_boxes; returns
+// its workgroups
+static uint32_t launch_box_cull(msplat_ctx* ctx, const CloudStore* st, bool vis, const FrameParams& fp, uint32_t* list, uint32_t* cnt)
 {
     const uint32_t wgs = div_up(st->nboxes, kBoxGroup);
-    hipLaunchKernelGGL(box_cull_kernel, dim3(wgs), dim3(kBoxGroup), 0, ctx->stream, (const CullBox*)st->boxes.p, st->nboxes, fp, list, cnt);
+    hipLaunchKernelGGL(box_cull_kernel, dim3(wgs), dim3(kBoxGroup), 0, ctx->stream, (const CullBox*)(vis ? ctx->vis_boxes.p : st->boxes.p),
+                       st->nboxes, fp, list, cnt);
     return wgs;
 }
 
@@ -980,7 +1004,7 @@ static LiveBoxes list_live_boxes(msplat_ctx* ctx, const FrameParams& fp, uint32_
     if (last_V == 0u || (uint64_t)last_V * 10u >= ctx->N * 7u) return lb;
     lb.list = (const uint32_t*)ctx->live_list.p;
     lb.cnt = (const uint32_t*)ctx->live_cnt.p;
-    lb.wgs = launch_box_cull(ctx, st, fp, (uint32_t*)ctx->live_list.p, (uint32_t*)ctx->live_cnt.p);
+    lb.wgs = launch_box_cull(ctx, st, vis_active(ctx), fp, (uint32_t*)ctx->live_list.p, (uint32_t*)ctx->live_cnt.p);
     ctx->last_sort_listed = true;
     return lb;
 }
@@ -1124,7 +1148,7 @@ static void issue_wide_sort(msplat_ctx* ctx, const FrameParams& fp)
     a.minkey_next = counters + kCntMinKey + ((ctx->sort_parity ^ 1u) & 1u);
     ctx->sort_parity ^= 1u;
     WsPass p0 = a;
-    p0.pos = (const float4*)ctx->pos4.p;  p0.raw_keys = words(ctx->keyB);  p0.vmask = (unsigned long long*)ctx->vmask.p;  p0.n_static = N;
+    p0.pos = sort_positions(ctx);  p0.raw_keys = words(ctx->keyB);  p0.vmask = (unsigned long long*)ctx->vmask.p;  p0.n_static = N;
     p0.keys_out = words(ctx->keyA);  p0.vals_out = words(ctx->valA);  p0.d_count_out = counters + kCntV;
     p0.lb = list_live_boxes(ctx, fp, last_V);       // (launches box_cull_kernel when the view is a partial one)
     // pass 0 over listed boxes: fewer chunks than the cloud has, so 4096-key chunks keep the CUs covered (as for passes 1, 2)
@@ -1168,7 +1192,7 @@ static void issue_lsd8_sort(msplat_ctx* ctx, const FrameParams& fp)
     a.hist = &ctx->hist;  a.totals = words(ctx->totals);  a.fused = ctx->scan_free && nchunks <= kFusedMaxChunks;
     // pass 0: cull + key fused into the first radix pass (presort_compute.glsl + byte 0 of the sort)
     RadixPass p0 = a;
-    p0.pos = (const float4*)ctx->pos4.p;  p0.n_static = N;
+    p0.pos = sort_positions(ctx);  p0.n_static = N;
     p0.keys_out = words(ctx->keyB);  p0.vals_out = words(ctx->valB);  p0.d_count_out = d_V;
     p0.gsum = &ctx->gsumS[0];  p0.gsum_zero = &ctx->gsumS[1];       // (gsum_zero always, scan-free or not: keeps both tables clean)
     p0.lb = list_live_boxes(ctx, fp, host_word(ctx, kHostV));
@@ -1195,6 +1219,9 @@ static int issue_sort(msplat_ctx* ctx, const FrameParams& fp)
     const bool timed = ctx->ev_ok && (ctx->sort_calls++ % ctx->timing_stride) == 0;
     const int tset = (int)(ctx->sort_sets % msplat_ctx::kEvSets);
     if (timed) HIP_TRY(ctx, hipEventRecord(ctx->ev[tset][kEvSortBegin], s));
+    // a mask or a crop: pass 0 and the box cull read the context's plane and boxes, rebuilt first when something changed
+    ctx->vis_sorted = vis_active(ctx);
+    if (ctx->vis_sorted && ctx->vis_dirty) launch_visibility(ctx);
     const bool wide = ctx->ws.on;
     if (wide) issue_wide_sort(ctx, fp);
     else issue_lsd8_sort(ctx, fp);
@@ -1204,7 +1231,7 @@ static int issue_sort(msplat_ctx* ctx, const FrameParams& fp)
     }
     const hipError_t le = hipGetLastError();
     if (le != hipSuccess) {
-        ctx->tables_dirty = true;
+        ctx->tables_dirty = ctx->vis_dirty = true;
         if (!wide) return fail(ctx, MSPLAT_ERR_HIP, "msplat_sort: a kernel launch failed");
         // e.g. the dynamic-LDS request was not honoured on this device: later frames take the four 8-bit passes, which
         // need no opt-in (this frame is lost; the tables are restored before the next one)
@@ -1561,7 +1588,9 @@ static void issue_occlusion_gate(RenderChain& rc)
     uint32_t *d_Vsort = rc.d_Vsort, *d_D = rc.d_D, *occ = rc.occ;
     hipLaunchKernelGGL(occ_mask_kernel, dim3(1), dim3(kOccMaskThreads), 0, s, (const uint32_t*)ctx->occ_fin.p, fp.tiles_x, fp.tiles_y,
                        (uint16_t*)ctx->occ_mask.p, occ, (const uint32_t*)d_Vsort, (uint32_t*)ctx->occ_unf.p);
-    // spatially ordered cloud: whole boxes of 256 stored splats are dropped before any centre is fetched
+    // spatially ordered cloud: whole boxes of 256 stored splats are dropped before any centre is fetched.  (The STORE's boxes and
+    // plane, also under a mask or a crop: its boxes hold the visible splats' too, a superset and so conservative, and the ranks the
+    // gate looks up are visible splats, whose positions the context's plane keeps bit for bit.)
     const uint32_t nboxes = (ctx->store && ctx->store->reordered && ctx->store->boxes.p) ? ctx->store->nboxes : 0u;
     const uint32_t boxwords = ((nboxes + (uint32_t)kThreads - 1u) / (uint32_t)kThreads) * ((uint32_t)kThreads / 32u);
     const bool use_boxes = nboxes != 0u && boxwords <= 2048u && ctx->occ_boxdead.p != nullptr;

@@ -82,7 +82,8 @@ int msplat_get_storage_order(msplat_ctx* ctx, uint32_t* dst, uint64_t cap, int* 
 }
 
 // chunk-level cull, for the latest Sort's camera: bounding boxes box_live keeps / boxes in the cloud (0 / 0 for a cloud in upload
-// order); *listed = 1 when that Sort's pass 0 walked the listed boxes only.  Runs box_cull_kernel on demand; synchronises.
+// order); *listed = 1 when that Sort's pass 0 walked the listed boxes only.  Runs box_cull_kernel on demand, over the boxes that Sort
+// used: the context's own under a mask or a crop (msplat_set_visibility), else the store's; synchronises.
 int msplat_debug_get_cull_boxes(msplat_ctx* ctx, uint32_t* live, uint32_t* total, int* listed)
 {
     drain_async(ctx);
@@ -98,7 +99,7 @@ int msplat_debug_get_cull_boxes(msplat_ctx* ctx, uint32_t* live, uint32_t* total
     int rc = buf_alloc(ctx, list, (size_t)wgs * kBoxGroup * 4);
     if (!rc) rc = buf_alloc(ctx, cnt, 256 * 4);
     if (!rc) {
-        launch_box_cull(ctx, st, ctx->last_sort_fp, (uint32_t*)list.p, (uint32_t*)cnt.p);
+        launch_box_cull(ctx, st, ctx->vis_sorted, ctx->last_sort_fp, (uint32_t*)list.p, (uint32_t*)cnt.p);
         uint32_t h[256];
         hipError_t e = hipMemcpyAsync(h, cnt.p, (size_t)wgs * 4, hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);

@@ -74,6 +74,15 @@ static int check_splat_count(msplat_ctx* ctx, uint64_t n)
     return MSPLAT_OK;
 }
 
+// the plane and the boxes a context with a mask or a crop sorts from, for the N it holds
+static int vis_alloc(msplat_ctx* ctx)
+{
+    const size_t n = std::max<uint64_t>(ctx->N, 1);
+    int rc = buf_alloc(ctx, ctx->vis_pos4, n * sizeof(float4));
+    if (!rc) rc = buf_alloc(ctx, ctx->vis_boxes, (size_t)div_up(n, kBoxSplats) * sizeof(CullBox));
+    return rc;
+}
+
 // (re)allocates every per-cloud device buffer for n splats; leaves the context without a cloud.
 // `share` != null: use that store's cloud instead of allocating one (msplat_attach_cloud).
 static int prepare_cloud_buffers(msplat_ctx* ctx, uint64_t n, bool full_sh, const std::shared_ptr<CloudStore>& share)
@@ -87,6 +96,18 @@ static int prepare_cloud_buffers(msplat_ctx* ctx, uint64_t n, bool full_sh, cons
     ctx->has_render = false;
     ctx->N = n;
     ctx->full_sh = full_sh;
+    // visibility: a mask speaks the old cloud's numbering and goes; a crop is world space and stays, evaluated on the new positions
+    // by the next Sort (the stream is idle: the buffers may be freed)
+    ctx->has_mask = ctx->vis_sorted = false;
+    buf_free(ctx, ctx->vis_mask);
+    if (ctx->crop_shape != 0 && !ctx->point_mode) {
+        int rc_v = vis_alloc(ctx);
+        if (rc_v) return rc_v;
+        ctx->vis_dirty = true;
+    } else {
+        buf_free(ctx, ctx->vis_pos4);
+        buf_free(ctx, ctx->vis_boxes);
+    }
     // the storage kind belongs to the store: attached contexts render the owner's, point clouds are always FP32, and so is a
     // degree-1 cloud asked to be SH_Q8 (its FP32 record is one 128-B line already)
     int storage = share ? share->storage : (ctx->point_mode ? kStorageFp32 : ctx->storage_cfg);
@@ -123,6 +144,7 @@ static int prepare_cloud_buffers(msplat_ctx* ctx, uint64_t n, bool full_sh, cons
         // a fresh upload starts in upload order (spatial_reorder runs once the cloud is on the device)
         ctx->store->reordered = false;
         ctx->store->order_host.clear();
+        if (ctx->store->order_dev.p) { (void)hipFree(ctx->store->order_dev.p); ctx->store->order_dev = Buf{}; }
         if (ctx->store->boxes.p) { (void)hipFree(ctx->store->boxes.p); ctx->store->boxes = Buf{}; }
         ctx->store->nboxes = 0;
     }

@@ -3,7 +3,7 @@
 // Sort + Render into an explicit RGBA32F framebuffer, dumped as a binary PPM-like float file.
 //
 //   g++ -std=c++17 -I. splatapult_amd/host/example_render.cpp -Lsplatapult_amd/lib -lmsplat -o example_render
-//   ./example_render scene.ply out.f32 [width height] [--nosh] [--frames-in-flight N] [--devices 0,1,2,...] [--over-gradient] [--depth out_depth.f32] [--srgb8 out.png]
+//   ./example_render scene.ply out.f32 [width height] [--nosh] [--frames-in-flight N] [--devices 0,1,2,...] [--over-gradient] [--depth out_depth.f32] [--srgb8 out.png] [--crop-sphere cx cy cz r]
 // With --frames-in-flight N the same frame is issued N + 1 times round-robin over N contexts that share the cloud
 // (SplatRenderer::SetFramesInFlight); the last one is written.  With --devices the frame's bin rows are dealt to the
 // listed GPUs (SplatRenderer::ConfigureDevices, msplat_group_*): same pixels.  With --over-gradient the target is first filled with
@@ -13,6 +13,8 @@
 // depth 1.0, row 0 = bottom), written to the named file; one device only.
 // With --srgb8 the target is an MSPLAT_FB_SRGB8_ALPHA8 one -- the reference's sRGB window: 4 bytes per pixel, encoded by the compositor's
 // final store -- and the PNG is written from those bytes (WritePNG), with no float frame in between; out.f32 is then not written.
+// With --crop-sphere only the splats whose centre lies in the sphere of radius r around (cx, cy, cz) are drawn (SplatRenderer::SetCrop,
+// MSPLAT_CROP_SPHERE): the cloud is uploaded whole, the Sort and everything behind it work on what the crop keeps.  One device only.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -36,7 +38,10 @@ int main(int argc, char** argv)
     const char* depthPath = nullptr;
     const char* srgb8Path = nullptr;
     std::vector<int> devices;
+    float cropSphere[4] = {0.0f, 0.0f, 0.0f, 0.0f};       // centre, radius; radius 0: no crop
     for (int i = 3; i < argc; ++i) {
+        if (!std::strcmp(argv[i], "--crop-sphere") && i + 4 < argc)
+            for (int k = 0; k < 4; ++k) cropSphere[k] = (float)std::atof(argv[i + 1 + k]);
         nosh = nosh || !std::strcmp(argv[i], "--nosh");
         overGradient = overGradient || !std::strcmp(argv[i], "--over-gradient");
         if (!std::strcmp(argv[i], "--frames-in-flight") && i + 1 < argc) inFlight = std::atoi(argv[i + 1]);
@@ -58,6 +63,13 @@ int main(int argc, char** argv)
     if (srgb8Path) renderer.Configure(/*device*/0, MSPLAT_FB_SRGB8_ALPHA8);
     if (devices.size() > 1) renderer.ConfigureDevices(devices, MSPLAT_BANDS_BLOCK_INTERLEAVED, 2);
     if (!renderer.Init(cloud, /*isFramebufferSRGBEnabled=*/false, /*useRgcSortOverride=*/false)) return 1;
+
+    if (cropSphere[3] > 0.0f) {
+        // world -> crop space: the sphere becomes the unit sphere, q = (p - c) / r
+        const float s = 1.0f / cropSphere[3];
+        const float worldToCrop[16] = {s, 0, 0, 0, 0, s, 0, 0, 0, 0, s, 0, -cropSphere[0] * s, -cropSphere[1] * s, -cropSphere[2] * s, 1};
+        if (!renderer.SetCrop(worldToCrop, MSPLAT_CROP_SPHERE)) return 1;
+    }
 
     // app.cpp:73-75,1039-1042: camera at the identity pose pulled back along +Z, 45 degree fovy
     msplat::mat4 cameraMat{}, projMat{};

@@ -322,6 +322,27 @@ public:
         return true;
     }
 
+    // per-splat visibility (msplat_set_visibility / msplat_set_crop; after Init, on every context of the rotation): for the following
+    // Sorts splat i (upload numbering) takes part iff visible[i] != 0 and the crop keeps it; nullptr = no mask.  An upload drops the
+    // mask and keeps the crop.  A device group has no visibility (out of scope): false.
+    bool SetVisibility(const uint8_t* visible, size_t n) { return SetMask(visible, n, false); }
+    // the mask in memory of the renderer's device: read asynchronously on each context's stream, valid until Synchronize()
+    bool SetVisibilityDevice(const uint8_t* d_visible, size_t n) { return SetMask(d_visible, n, true); }
+    // crop volume: worldToCrop (column-major, affine) and MSPLAT_CROP_BOX / _SPHERE, | MSPLAT_CROP_INVERT; nullptr or MSPLAT_CROP_NONE = none
+    bool SetCrop(const float* worldToCrop, int shape)
+    {
+        if (group) {
+            std::fprintf(stderr, "[msplat][E] SetCrop: a device group has no per-splat visibility\n");
+            return false;
+        }
+        for (msplat_ctx* h : ctxs)
+            if (msplat_set_crop(h, worldToCrop, shape) != MSPLAT_OK) {
+                std::fprintf(stderr, "[msplat][E] SetCrop: %s\n", msplat_last_error(h));
+                return false;
+            }
+        return true;
+    }
+
     // blocks until every frame in flight has finished
     // (also where a pair-buffer overflow of an earlier device-target Render is reported, see msplat_render)
     void Synchronize()
@@ -455,6 +476,21 @@ protected:
             std::fprintf(stderr, "[msplat][E] %s\n", msplat_group_last_error(group));
             return false;
         }
+        return true;
+    }
+
+    // SetVisibility / SetVisibilityDevice: the mask on every context of the rotation
+    bool SetMask(const uint8_t* mask, size_t n, bool onDevice)
+    {
+        if (group) {
+            std::fprintf(stderr, "[msplat][E] SetVisibility: a device group has no per-splat visibility\n");
+            return false;
+        }
+        for (msplat_ctx* h : ctxs)
+            if ((onDevice ? msplat_set_visibility_device(h, mask, n) : msplat_set_visibility(h, mask, n)) != MSPLAT_OK) {
+                std::fprintf(stderr, "[msplat][E] SetVisibility: %s\n", msplat_last_error(h));
+                return false;
+            }
         return true;
     }
 

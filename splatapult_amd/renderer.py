@@ -501,6 +501,66 @@ class SplatRenderer:
         k = self._lib.msplat_get_target_mode(self._ctx) if self._ctx else -1
         return {v: n for n, v in _capi.TARGET_MODES.items()}.get(k)
 
+    # -- per-splat visibility (msplat_set_visibility / msplat_set_crop) ---------------
+    def SetVisibility(self, mask=None):
+        """Hide splats without another upload: for the following Sorts splat i (upload numbering) takes part iff mask[i] (and the
+        crop keeps it).  mask: N values, numpy bool / uint8 (nonzero = visible; copied before the call returns), or an object with
+        data_ptr() that lives on the device -- a torch bool / uint8 tensor on this renderer's device, read asynchronously on each
+        context's stream: keep it alive and unchanged until synchronize() -- or None for no mask.  Set on every context of the
+        frames-in-flight rotation; a Render shows it after the next Sort.  An upload (Init*, Update*) drops the mask.
+        ValueError for a wrong length or dtype, before the library is called."""
+        if mask is None:
+            args, fn = (None, 0), self._lib.msplat_set_visibility
+        elif hasattr(mask, "data_ptr"):
+            if str(mask.dtype).split(".")[-1] not in ("bool", "uint8"):
+                raise ValueError("the mask must be bool or uint8, not %s" % mask.dtype)
+            if tuple(int(s) for s in mask.shape) != (self._n,):
+                raise ValueError("the mask must have shape (%d,), one value per splat, not %s" % (self._n, tuple(mask.shape)))
+            if not mask.is_contiguous():
+                raise ValueError("the mask must be contiguous (pass mask.contiguous())")
+            if getattr(mask.device, "type", "cuda") not in ("cuda", "hip"):
+                raise ValueError("a mask with data_ptr() must live in device memory, not on %s (pass mask.numpy())" % mask.device)
+            import sys
+            torch = sys.modules.get("torch")
+            if torch is not None and isinstance(mask, torch.Tensor):
+                torch.cuda.current_stream(mask.device).synchronize()       # what produced the tensor has completed
+            args, fn = (C.c_void_p(int(mask.data_ptr())), self._n), self._lib.msplat_set_visibility_device
+        else:
+            if not isinstance(mask, np.ndarray) or mask.dtype not in (np.bool_, np.uint8):
+                raise ValueError("the mask must be a numpy bool / uint8 array, a device tensor or None, not %s %s"
+                                 % (type(mask).__name__, getattr(mask, "dtype", "")))
+            if mask.shape != (self._n,):
+                raise ValueError("the mask must have shape (%d,), one value per splat, not %s" % (self._n, mask.shape))
+            mask = np.ascontiguousarray(mask)
+            args, fn = (mask.ctypes.data, self._n), self._lib.msplat_set_visibility
+        if not self._ctxs:
+            raise _capi.MsplatError(_capi.ERR_NO_CLOUD, "SetVisibility: no cloud (Init first)")
+        for h in self._ctxs:
+            _capi.check(h, fn(h, *args))
+
+    def SetCrop(self, worldToCrop=None, shape="box", invert=False):
+        """Crop volume for the following Sorts, on every context: worldToCrop = 16 floats, column-major, world -> crop space (affine),
+        shape "box" (|q| <= 1 per axis) or "sphere" (|q|^2 <= 1) in crop space, invert = keep what is OUTSIDE.  None = no crop.
+        A centre on the surface is inside; the exact fp32 rule is msplat.h's.  An upload keeps the crop."""
+        if worldToCrop is None:
+            m, code = None, _capi.CROP_NONE
+        else:
+            if shape not in _capi.CROP_SHAPES:
+                raise ValueError("shape must be one of %s (got %r)" % (sorted(_capi.CROP_SHAPES), shape))
+            m = np.ascontiguousarray(_FrameArgs._flat(worldToCrop, 16))
+            code = _capi.CROP_SHAPES[shape] | (_capi.CROP_INVERT if invert else 0)
+        for h in self._ctxs:
+            _capi.check(h, self._lib.msplat_set_crop(h, None if m is None else m.ctypes.data_as(C.POINTER(C.c_float)), code))
+
+    def visibility(self):
+        """dict(has_mask, crop, hidden) of the current context (msplat_get_visibility): crop = None or (shape, invert); hidden =
+        splats the latest Sort's mask and crop hid (synchronises)"""
+        a, b, h = C.c_int32(), C.c_int32(), C.c_uint64()
+        _capi.check(self._ctx, self._lib.msplat_get_visibility(self._ctx, C.byref(a), C.byref(b), C.byref(h)))
+        names = {v: n for n, v in _capi.CROP_SHAPES.items()}
+        crop = None if b.value == _capi.CROP_NONE else (names[b.value & ~_capi.CROP_INVERT], bool(b.value & _capi.CROP_INVERT))
+        return dict(has_mask=bool(a.value), crop=crop, hidden=int(h.value))
+
     def synchronize(self):
         """blocks until every frame in flight has been issued (async_submit) AND has finished on the GPU"""
         for h in self._ctxs:
