@@ -117,8 +117,7 @@ int msplat_download_cloud(msplat_ctx* ctx, void* aos_out, uint64_t cap_bytes);
  * r g b together), fp32: m = max |c|; step = m / 127 (0, codes 0, when m < 2^-64); code = clamp(rint(c / step), -127, 127), halves to even;
  * stored c' = (float)code * step: |c - c'| <= (1/2 + 2^-16) step.  Pixels = FP32 of the cloud of c', which the download returns; a second
  * Q8 round may move c' once more; a non-finite f_rest value fails the upload (MSPLAT_ERR_UNSUPPORTED, no cloud). */
-enum { MSPLAT_STORAGE_FP32 = 0, MSPLAT_STORAGE_SH_FP16 = 1 };
-enum { MSPLAT_STORAGE_SH_Q8 = 3 };
+enum { MSPLAT_STORAGE_SH_Q8 = 3 }; enum { MSPLAT_STORAGE_FP32 = 0, MSPLAT_STORAGE_SH_FP16 = 1 };
 int msplat_set_cloud_storage(msplat_ctx* ctx, int32_t storage);
 int msplat_get_cloud_storage(const msplat_ctx* ctx);
 /* ---- SplatRenderer::Sort (splatrenderer.cpp:153-312): cull + depth key (presort_compute.glsl:31-57), stable ascending 32-bit
@@ -162,6 +161,11 @@ int msplat_render_layers(msplat_ctx* ctx, const float cameraMat[16], const float
 int msplat_render_stereo(msplat_ctx* ctx, const float cameraMat0[16], const float projMat0[16], const float cameraMat1[16], const float projMat1[16], const float viewport[4], const float nearFar[2], void* rgba0, void* rgba1, uint64_t pitch_bytes, int out_is_device);
 /* msplat_render_stereo with msplat_render_layers' planes per eye; the pitch of each kind is shared by the eyes.  depth0 / depth1 are both given or both NULL, and so are occluder0 / occluder1 (else MSPLAT_ERR_INVALID_ARG); all NULL = msplat_render_stereo.  One chain where msplat_render_stereo runs as one (device output, no bands, <= 2^23 splats, <= 128 bin rows per view), else view by view; either way each eye's colour and depth are bit for bit msplat_render_layers' with that eye's matrices after the same Sort. */
 int msplat_render_stereo_layers(msplat_ctx* ctx, const float cameraMat0[16], const float projMat0[16], const float cameraMat1[16], const float projMat1[16], const float viewport[4], const float nearFar[2], void* rgba0, void* rgba1, uint64_t pitch_bytes, float* depth0, float* depth1, uint64_t depth_pitch_bytes, const float* occluder0, const float* occluder1, uint64_t occluder_pitch_bytes, int out_is_device);
+/* ---- which splat each pixel shows (INTEGRATION.md 20): the read half of msplat_set_visibility -- click, brush and lasso on the device.  Over the splats of the latest Sort (hidden ones are not in it), walked near to far at pixel centre p: w_i(p) = alpha times the Gaussian, 0 where splat_frag.glsl:37-40 discards (w <= 1/256); T_i = prod_{j in front of i}(1 - w_j); c_i = T_i w_i.  ids[p] = upload index (the numbering of msplat_get_sorted_indices, also for a cloud stored in Morton order) of the splat with the largest c_i, the nearest of equals; MSPLAT_ID_NONE where no splat has w_i(p) > 0.  id_depth[p] (NULL: no plane) = that splat's window depth 0.5 ndc.z + 0.5, the per-splat value msplat_render_depth blends and msplat_render_occluded tests; exactly 1.0 at MSPLAT_ID_NONE.  The walk ends only where no later splat can win (T <= best): the planes do not depend on t_epsilon, compositor_waves, frame_mode, two_pass, the fb format or the target mode.  window = x0, y0, w, h in viewport pixels, row 0 = GL bottom; NULL = the whole viewport.  Both planes are w x h OF THE WINDOW, 4-byte elements, in one memory space; a pitch of 0 = tight rows, else >= 4 w and a multiple of 4; padding bytes are not written; a window's planes equal that rectangle of the whole viewport's, bit for bit.  Host output returns after the copy and grows the pair buffer like msplat_render; device output is asynchronous on the stream, queued under async_submit, and reports pair overflow as a device-output msplat_render does.  The frame is a plain one-pass frame's projection and binning plus one kernel over the 16 x 16 tiles the window touches; it is never a two-pass frame and leaves msplat_get_two_pass_info and msplat_get_timings as they were.
+ * Refused before anything is launched -- _INVALID_ARG: NULL ids, a window with w or h <= 0 or not inside the viewport, a bad pitch; _NO_CLOUD / _NO_SORT as msplat_render; _UNSUPPORTED (the context stays usable): a point cloud, msplat_set_depth_test, a target emulation, the tile probe, a banded context.  Out of scope: the device group, two views in one chain, an occluder plane for the id walk.  msplat_mark_ids: device memory only (pointers checked as msplat_set_visibility_device checks its own); for every pixel of the w x h plane d_ids whose d_region byte is nonzero (NULL: every pixel; region pitch 0 = w) and whose id is not MSPLAT_ID_NONE: d_mask[id] = value.  n must be the cloud's N (else _INVALID_ARG); an id >= n is skipped, never stored through.  Asynchronous on the context's stream, so ordered behind the id frame that wrote the plane.  value = 0 on a mask of ones, handed to msplat_set_visibility_device, hides what was brushed; value = 1 on zeros is a selection. */
+#define MSPLAT_ID_NONE 0xFFFFFFFFu
+int msplat_render_ids(msplat_ctx* ctx, const float cameraMat[16], const float projMat[16], const float viewport[4], const float nearFar[2], const int32_t window[4], uint32_t* ids, uint64_t ids_pitch_bytes, float* id_depth, uint64_t id_depth_pitch_bytes, int out_is_device);
+int msplat_mark_ids(msplat_ctx* ctx, const uint32_t* d_ids, uint64_t ids_pitch_bytes, uint32_t w, uint32_t h, const uint8_t* d_region, uint64_t region_pitch_bytes, uint8_t* d_mask, uint64_t n, uint8_t value);
 /* blocks until everything queued on the context (and issued by its worker thread) has finished */
 int msplat_synchronize(msplat_ctx* ctx);
 /* ---- frames in flight.  The reference queues successive frames on one GL command stream and the driver overlaps them; here the overlap is
@@ -172,7 +176,6 @@ int msplat_stream_wait(msplat_ctx* ctx, void* stream);              /* `stream` 
 int msplat_wait_event(msplat_ctx* ctx, void* event);                /* the context's stream waits for `event` (hipEvent_t) */
 void* msplat_get_stream(msplat_ctx* ctx);                           /* the hipStream_t the context launches on */
 int msplat_get_fb_format(const msplat_ctx* ctx);                    /* MSPLAT_FB_* the context was created with (-1: NULL) */
-
 /* ---- rows of the screen on several GPUs (SURVEY.md 8e; no reference counterpart).  The context owns blocks of `block` consecutive bin rows
  * (msplat_tile_size() pixels; row 0 = GL bottom) starting at first_row, first_row + stride, ..., at most row_count rows (0 = all).  msplat_render
  * is always handed the full image; only owned rows are written (and read), bit-identical to the unbanded frame.  msplat_set_band(mod, rem) = interleaved single rows. */
@@ -194,9 +197,7 @@ int msplat_set_band_cull(msplat_ctx* ctx, int enable);
  * flags: MSPLAT_EXCHANGE_WIRE_FP16 (RGBA32F targets only): rows cross the link as RGBA16F -- half the bytes; the gathered rows
  * then differ from the owners' by one fp16 rounding, |d| <= 2^-11 |value| (values beyond 65504 become inf), root's own rows not. */
 enum { MSPLAT_EXCHANGE_WIRE_FP16 = 1 };
-int msplat_band_exchange(msplat_ctx* ctx, void* comm, int32_t rank, int32_t world, int32_t root, int32_t kind, int32_t block_rows,
-                         void* rgba, uint64_t pitch_bytes, int32_t width, int32_t height, int32_t flags);
-
+int msplat_band_exchange(msplat_ctx* ctx, void* comm, int32_t rank, int32_t world, int32_t root, int32_t kind, int32_t block_rows, void* rgba, uint64_t pitch_bytes, int32_t width, int32_t height, int32_t flags);
 /* ---- several GPUs, ONE process: the reference's shape, a single-threaded host calling Sort / Render (app.cpp:1067-1068).  One context per
  * listed device, replicated cloud, bin rows partitioned (default MSPLAT_BANDS_CONTIGUOUS).  The only exchange is the row gather into `rgba` on
  * devices[0]: peer stores from the other devices' compositors (default; no staging), RCCL send / recv (msplat_group_set_exchange), or a 2-D copy
@@ -219,8 +220,7 @@ int msplat_group_set_target_mode(msplat_group* g, int32_t mode);
 int msplat_group_set_layout(msplat_group* g, int32_t kind, int32_t block_rows);
 int msplat_group_set_band_cull(msplat_group* g, int enable);
 int msplat_group_sort(msplat_group* g, const float cameraMat[16], const float projMat[16], const float viewport[4], const float nearFar[2]);
-int msplat_group_render(msplat_group* g, const float cameraMat[16], const float projMat[16], const float viewport[4],
-                        const float nearFar[2], void* rgba, uint64_t pitch_bytes, int out_is_device);
+int msplat_group_render(msplat_group* g, const float cameraMat[16], const float projMat[16], const float viewport[4], const float nearFar[2], void* rgba, uint64_t pitch_bytes, int out_is_device);
 int msplat_group_synchronize(msplat_group* g);
 /* ---- results of the latest Sort / Render (these synchronise) ---- */
 int msplat_sort_count(msplat_ctx* ctx, uint32_t* v);            /* sortCount (splatrenderer.cpp:198-199) */

@@ -243,6 +243,7 @@ struct msplat_ctx {
     Buf fb;         // internal framebuffer for host-output renders
     Buf fbz;        // ... and their depth plane (msplat_render_depth): float[W * H]
     Buf fbo;        // ... and the caller's occluder plane (msplat_render_occluded), staged once per call: float[W * H]
+    Buf fb_ids, fb_idz;   // the planes of a host-output id frame (msplat_render_ids): uint32 / float[w * h] of its window
     Buf probe;      // uint32[8 * work items] compositor probe (msplat_set_tile_probe)
     bool probe_on = false;
     // device-output renders never synchronise: a pair-buffer overflow is left in host-mapped memory by the
@@ -1297,6 +1298,7 @@ struct RenderChain {
     // the compositor's schedule, decided where the bins are ordered (issue_binning) and used by issue_compositor
     bool ordered = true;
     uint32_t comp_items = 0, comp_pool = 0;
+    bool want_zw = false;        // an id frame: z_w per rank although the chain has no planes
 };
 
 // vertex + geometry stage.  mode: PROJ_PLAIN / PROJ_TWO_VIEWS (chosen from the chain), PROJ_PASS1 or PROJ_LISTED (two-pass frames)
@@ -1315,7 +1317,7 @@ static void issue_projection(RenderChain& rc, int mode, float occ_frac)
     }
     ProjParams pp = proj_params(fp);
     uint32_t* zq = (mode != PROJ_LISTED && ctx->depth_bits) ? (uint32_t*)ctx->zq.p : nullptr;
-    if (rc.planes.any()) {
+    if (rc.planes.any() || rc.want_zw) {
         // a depth frame, or one tested against an occluder plane: every projection of the frame leaves z_w = (float)(0.5 ndc.z + 0.5)
         // per rank -- quantise_depth's 32-bit form is that float's bits (one product by 0.5, exact, and one rounded sum)
         pp.depth_bits = 32;
@@ -1954,6 +1956,8 @@ int msplat_render_stereo_layers(msplat_ctx* ctx, const float cameraMat0[16], con
     return submit_render_stereo(ctx, "msplat_render_stereo_layers", cameraMat0, projMat0, cameraMat1, projMat1, viewport, nearFar, rgba0, rgba1,
                                 pitch_bytes, out_is_device, {{depth0, depth1}, {occluder0, occluder1}, depth_pitch_bytes, occluder_pitch_bytes});
 }
+
+#include "msplat_ids.hip.inc"
 
 #include "msplat_getters.hip.inc"
 

@@ -1,10 +1,11 @@
-// msplat_kernels.hip.h -- hand-written CDNA4 (gfx950, wave64) kernels of the splat hot path, in eight parts.
+// msplat_kernels.hip.h -- hand-written CDNA4 (gfx950, wave64) kernels of the splat hot path, in nine parts.
 //
 // Replaces (not ports) the reference's GL pipeline:
 //   shader/presort_compute.glsl + shader/multi_radixsort*.glsl  -> msplat_sort.hip.h      radix_* / ws_* (cull fused in pass 0)
 //   shader/splat_vert.glsl + shader/splat_geom.glsl             -> msplat_project.hip.h   project_kernel
 //   GL rasteriser + shader/splat_frag.glsl + ROP blend          -> msplat_binning.hip.h   bin1_* (+ radix_*<MODE_PAIR>)
 //                                                                  msplat_composite.hip.h composite_kernel, composite_depth_kernel
+//   which splat a pixel shows (no reference part)               -> msplat_ids.hip.h       composite_ids_kernel, mark_ids_kernel
 //   GaussianCloud::ImportPly's per-vertex math, storage order   -> msplat_cloud.hip.h     ingest_kernel, morton / gather / cull boxes
 //   shader/point_*.glsl                                         -> msplat_points.hip.h
 //   two-pass frame with occlusion feedback (no reference part)  -> msplat_occlusion.hip.h
@@ -20,5 +21,6 @@
 #include "msplat_project.hip.h"
 #include "msplat_binning.hip.h"
 #include "msplat_composite.hip.h"
+#include "msplat_ids.hip.h"
 #include "msplat_points.hip.h"
 #include "msplat_occlusion.hip.h"

@@ -3,7 +3,7 @@
 // Sort + Render into an explicit RGBA32F framebuffer, dumped as a binary PPM-like float file.
 //
 //   g++ -std=c++17 -I. splatapult_amd/host/example_render.cpp -Lsplatapult_amd/lib -lmsplat -o example_render
-//   ./example_render scene.ply out.f32 [width height] [--nosh] [--frames-in-flight N] [--devices 0,1,2,...] [--over-gradient] [--depth out_depth.f32] [--srgb8 out.png] [--crop-sphere cx cy cz r]
+//   ./example_render scene.ply out.f32 [width height] [--nosh] [--frames-in-flight N] [--devices 0,1,2,...] [--over-gradient] [--depth out_depth.f32] [--srgb8 out.png] [--crop-sphere cx cy cz r] [--pick X,Y]
 // With --frames-in-flight N the same frame is issued N + 1 times round-robin over N contexts that share the cloud
 // (SplatRenderer::SetFramesInFlight); the last one is written.  With --devices the frame's bin rows are dealt to the
 // listed GPUs (SplatRenderer::ConfigureDevices, msplat_group_*): same pixels.  With --over-gradient the target is first filled with
@@ -15,6 +15,8 @@
 // final store -- and the PNG is written from those bytes (WritePNG), with no float frame in between; out.f32 is then not written.
 // With --crop-sphere only the splats whose centre lies in the sphere of radius r around (cx, cy, cz) are drawn (SplatRenderer::SetCrop,
 // MSPLAT_CROP_SPHERE): the cloud is uploaded whole, the Sort and everything behind it work on what the crop keeps.  One device only.
+// With --pick X,Y the splat that contributes most to pixel (X, Y) (row 0 = bottom) and its window depth are printed (SplatRenderer::Pick,
+// msplat_render_ids through a 1 x 1 window).  One device only.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -35,6 +37,7 @@ int main(int argc, char** argv)
     bool nosh = false, overGradient = false;
     if (argc >= 5 && argv[3][0] != '-') { W = std::atoi(argv[3]); H = std::atoi(argv[4]); }
     int inFlight = 1;
+    int pickX = -1, pickY = -1;      // --pick: print the splat under this pixel (row 0 = bottom) and its window depth
     const char* depthPath = nullptr;
     const char* srgb8Path = nullptr;
     std::vector<int> devices;
@@ -46,6 +49,7 @@ int main(int argc, char** argv)
         overGradient = overGradient || !std::strcmp(argv[i], "--over-gradient");
         if (!std::strcmp(argv[i], "--frames-in-flight") && i + 1 < argc) inFlight = std::atoi(argv[i + 1]);
         if (!std::strcmp(argv[i], "--depth") && i + 1 < argc) depthPath = argv[i + 1];
+        if (!std::strcmp(argv[i], "--pick") && i + 1 < argc && std::sscanf(argv[i + 1], "%d,%d", &pickX, &pickY) != 2) pickX = pickY = -1;
         if (!std::strcmp(argv[i], "--srgb8") && i + 1 < argc) srgb8Path = argv[i + 1];
         if (!std::strcmp(argv[i], "--devices") && i + 1 < argc)
             for (const char* p = argv[i + 1]; *p;) {
@@ -108,6 +112,13 @@ int main(int argc, char** argv)
         else renderer.Render(cameraMat, projMat, viewport, nearFar);
     }
     renderer.Synchronize();
+    if (pickX >= 0 && pickY >= 0) {
+        uint32_t index = MSPLAT_ID_NONE;
+        float zw = 1.0f;
+        if (!renderer.Pick(cameraMat, projMat, viewport, nearFar, pickX, pickY, &index, &zw)) return 1;
+        if (index == MSPLAT_ID_NONE) std::printf("pick (%d, %d): no splat, z_w %.9g\n", pickX, pickY, zw);
+        else std::printf("pick (%d, %d): splat %u, z_w %.9g\n", pickX, pickY, index, zw);
+    }
 
     FILE* f = std::fopen(argv[2], "wb");
     if (!f) return 1;

@@ -343,6 +343,48 @@ public:
         return true;
     }
 
+    // Which splat each pixel shows (msplat_render_ids): per pixel of window = {x0, y0, w, h} (viewport pixels, row 0 = GL bottom; nullptr =
+    // the whole viewport) the upload index of the splat of the latest Sort that contributes most to it, MSPLAT_ID_NONE where none
+    // reaches; idDepth (may be nullptr) = that splat's window depth, 1.0 at MSPLAT_ID_NONE.  Both planes are w x h of the WINDOW, rows
+    // of their pitch (0 = tight), in host or device memory alike (isDevicePointer).  Needs no render target.  A device group has no id frame.
+    template <class Mat4, class Vec4, class Vec2>
+    bool RenderIds(const Mat4& cameraMat, const Mat4& projMat, const Vec4& viewport, const Vec2& nearFar, const int32_t* window, uint32_t* ids,
+                   uint64_t idsPitchBytes = 0, float* idDepth = nullptr, uint64_t idDepthPitchBytes = 0, bool isDevicePointer = false)
+    {
+        static_assert(sizeof(Mat4) == 64 && sizeof(Vec4) == 16 && sizeof(Vec2) == 8, "glm-compatible layout expected");
+        if (group || !ctx) {
+            std::fprintf(stderr, "[msplat][E] RenderIds: %s\n", group ? "a device group has no id frame" : "no cloud (Init first)");
+            return false;
+        }
+        const int rc = msplat_render_ids(ctx, F(cameraMat), F(projMat), F(viewport), F(nearFar), window, ids, idsPitchBytes, idDepth,
+                                         idDepthPitchBytes, isDevicePointer ? 1 : 0);
+        if (rc != MSPLAT_OK) std::fprintf(stderr, "[msplat][%c] RenderIds: %s\n", Level(rc), msplat_last_error(ctx));
+        return rc == MSPLAT_OK || rc == MSPLAT_ERR_PAIR_OVERFLOW_EARLIER;
+    }
+    // the splat under pixel (x, y) of the viewport: RenderIds through a 1 x 1 window.  *index = MSPLAT_ID_NONE, *zw = 1.0 where none reaches
+    template <class Mat4, class Vec4, class Vec2>
+    bool Pick(const Mat4& cameraMat, const Mat4& projMat, const Vec4& viewport, const Vec2& nearFar, int x, int y, uint32_t* index, float* zw = nullptr)
+    {
+        const int32_t window[4] = {x, y, 1, 1};
+        return RenderIds(cameraMat, projMat, viewport, nearFar, window, index, 0, zw, 0, false);
+    }
+    // d_mask[id] = value for every pixel of the w x h id plane d_ids that d_region selects (nonzero byte; nullptr = every pixel) and whose
+    // id is a splat (msplat_mark_ids).  Device memory only; d_mask: one byte per splat, what SetVisibilityDevice takes.  Asynchronous on
+    // the stream of the latest Sort's context, behind the RenderIds that wrote the plane.
+    bool MarkIds(const uint32_t* d_ids, uint64_t idsPitchBytes, uint32_t w, uint32_t h, uint8_t* d_mask, size_t n, uint8_t value,
+                 const uint8_t* d_region = nullptr, uint64_t regionPitchBytes = 0)
+    {
+        if (group || !ctx) {
+            std::fprintf(stderr, "[msplat][E] MarkIds: %s\n", group ? "a device group has no per-splat visibility" : "no cloud (Init first)");
+            return false;
+        }
+        if (msplat_mark_ids(ctx, d_ids, idsPitchBytes, w, h, d_region, regionPitchBytes, d_mask, n, value) != MSPLAT_OK) {
+            std::fprintf(stderr, "[msplat][E] MarkIds: %s\n", msplat_last_error(ctx));
+            return false;
+        }
+        return true;
+    }
+
     // blocks until every frame in flight has finished
     // (also where a pair-buffer overflow of an earlier device-target Render is reported, see msplat_render)
     void Synchronize()

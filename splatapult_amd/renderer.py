@@ -561,6 +561,80 @@ class SplatRenderer:
         crop = None if b.value == _capi.CROP_NONE else (names[b.value & ~_capi.CROP_INVERT], bool(b.value & _capi.CROP_INVERT))
         return dict(has_mask=bool(a.value), crop=crop, hidden=int(h.value))
 
+    # -- which splat each pixel shows (msplat_render_ids / msplat_mark_ids) -----------
+    def RenderIds(self, cameraMat, projMat, viewport, nearFar, window=None, out=None, out_ptr=None, pitch_bytes=0, depth=False,
+                  depth_ptr=None, depth_pitch_bytes=0):
+        """Per pixel the upload index of the splat of the latest Sort that contributes most to it (ID_NONE = 0xFFFFFFFF where no
+        splat reaches), over window = (x0, y0, w, h) in viewport pixels, row 0 = GL bottom; None = the whole viewport.
+        out=None -> returns a new (h, w) uint32 array; out=ndarray -> filled in place; depth=True (or an (h, w) float32 array) ->
+        returns (ids, depth), depth = that splat's window depth, 1.0 at ID_NONE.  out_ptr=int -> device memory, rows of pitch_bytes
+        (0 = tight), asynchronous on the stream, returns None; depth_ptr=int (rows of depth_pitch_bytes) goes with out_ptr.
+        ValueError for a window, array or pitch that cannot be right, before the library is called."""
+        f = self._args.load(cameraMat, projMat, viewport, nearFar)
+        W, H = int(self._args.vp[2]), int(self._args.vp[3])
+        if window is None:
+            win, (w, h) = None, (W, H)
+        else:
+            if len(window) != 4 or any(int(v) != v for v in window):
+                raise ValueError("window must be four integers (x0, y0, w, h), not %r" % (window,))
+            x0, y0, w, h = (int(v) for v in window)
+            if w <= 0 or h <= 0 or x0 < 0 or y0 < 0 or x0 + w > W or y0 + h > H:
+                raise ValueError("window %r is empty or not inside the %d x %d viewport" % (tuple(window), W, H))
+            win = (C.c_int32 * 4)(x0, y0, w, h)
+        for name, pitch in (("pitch_bytes", pitch_bytes), ("depth_pitch_bytes", depth_pitch_bytes)):
+            if pitch and (pitch < 4 * w or pitch % 4):
+                raise ValueError("%s must be 0 (tight rows) or at least %d and a multiple of 4, not %d" % (name, 4 * w, pitch))
+        if out_ptr is not None:
+            if out is not None or (depth is not None and depth is not False):
+                raise ValueError("the planes live in one memory space: pass depth_ptr= with out_ptr=")
+            _capi.check(self._ctx, self._lib.msplat_render_ids(self._ctx, *f, win, C.c_void_p(out_ptr), pitch_bytes,
+                                                               C.c_void_p(depth_ptr) if depth_ptr is not None else None, depth_pitch_bytes, 1))
+            return None
+        if depth_ptr is not None:
+            raise ValueError("the planes live in one memory space: pass depth= with host output")
+        if pitch_bytes or depth_pitch_bytes:
+            raise ValueError("host arrays have tight rows: pitch_bytes / depth_pitch_bytes go with out_ptr=")
+        if out is None:
+            out = np.empty((h, w), np.uint32)
+        elif not isinstance(out, np.ndarray) or out.dtype != np.uint32 or out.shape != (h, w) or not out.flags["C_CONTIGUOUS"]:
+            raise ValueError("out= takes a C-contiguous uint32 array of shape (%d, %d)" % (h, w))
+        if depth is False:
+            depth = None
+        if depth is True:
+            depth = np.empty((h, w), np.float32)
+        d = self._host_plane("depth=", depth, h, w).ctypes.data if depth is not None else None
+        _capi.check(self._ctx, self._lib.msplat_render_ids(self._ctx, *f, win, out.ctypes.data, 0, d, 0, 0))
+        return out if depth is None else (out, depth)
+
+    def Pick(self, cameraMat, projMat, viewport, nearFar, x, y):
+        """(index, z_w) of the splat pixel (x, y) of the viewport shows (row 0 = GL bottom): RenderIds through a 1 x 1 window.
+        index is None, and z_w 1.0, where no splat reaches."""
+        ids, z = self.RenderIds(cameraMat, projMat, viewport, nearFar, window=(x, y, 1, 1), depth=True)
+        i = int(ids[0, 0])
+        return (None if i == _capi.ID_NONE else i), float(z[0, 0])
+
+    def MarkIds(self, ids_ptr, pitch_bytes, w, h, mask_ptr, value, region_ptr=None, region_pitch_bytes=0):
+        """mask[id] = value for every pixel of the w x h id plane at device pointer ids_ptr (rows of pitch_bytes, 0 = tight) that
+        the byte plane region_ptr selects (nonzero; None = every pixel; rows of region_pitch_bytes, 0 = w) and whose id is a
+        splat.  mask_ptr: N bytes of device memory -- what SetVisibility takes.  Asynchronous on the current context's stream,
+        behind the RenderIds(out_ptr=) that wrote the plane."""
+        w, h, value = int(w), int(h), int(value)
+        if w < 0 or h < 0:
+            raise ValueError("w and h must not be negative (got %d x %d)" % (w, h))
+        if not 0 <= value <= 255:
+            raise ValueError("value is one byte, 0..255 (got %d)" % value)
+        if pitch_bytes and (pitch_bytes < 4 * w or pitch_bytes % 4):
+            raise ValueError("pitch_bytes must be 0 (tight rows) or at least %d and a multiple of 4, not %d" % (4 * w, pitch_bytes))
+        if region_ptr is not None and region_pitch_bytes and region_pitch_bytes < w:
+            raise ValueError("region_pitch_bytes must be 0 (tight rows) or at least %d, not %d" % (w, region_pitch_bytes))
+        if not ids_ptr or not mask_ptr:
+            raise ValueError("ids_ptr and mask_ptr are device pointers, not %r / %r" % (ids_ptr, mask_ptr))
+        if not self._ctx:
+            raise _capi.MsplatError(_capi.ERR_NO_CLOUD, "MarkIds: no cloud (Init first)")
+        _capi.check(self._ctx, self._lib.msplat_mark_ids(self._ctx, C.c_void_p(int(ids_ptr)), pitch_bytes, w, h,
+                                                         C.c_void_p(int(region_ptr)) if region_ptr is not None else None,
+                                                         region_pitch_bytes, C.c_void_p(int(mask_ptr)), self._n, value))
+
     def synchronize(self):
         """blocks until every frame in flight has been issued (async_submit) AND has finished on the GPU"""
         for h in self._ctxs:
