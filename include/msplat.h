@@ -117,9 +117,7 @@ int msplat_download_cloud(msplat_ctx* ctx, void* aos_out, uint64_t cap_bytes);
  * r g b together), fp32: m = max |c|; step = m / 127 (0, codes 0, when m < 2^-64); code = clamp(rint(c / step), -127, 127), halves to even;
  * stored c' = (float)code * step: |c - c'| <= (1/2 + 2^-16) step.  Pixels = FP32 of the cloud of c', which the download returns; a second
  * Q8 round may move c' once more; a non-finite f_rest value fails the upload (MSPLAT_ERR_UNSUPPORTED, no cloud). */
-enum { MSPLAT_STORAGE_SH_Q8 = 3 }; enum { MSPLAT_STORAGE_FP32 = 0, MSPLAT_STORAGE_SH_FP16 = 1 };
-int msplat_set_cloud_storage(msplat_ctx* ctx, int32_t storage);
-int msplat_get_cloud_storage(const msplat_ctx* ctx);
+enum { MSPLAT_STORAGE_SH_Q8 = 3 }; enum { MSPLAT_STORAGE_FP32 = 0, MSPLAT_STORAGE_SH_FP16 = 1 }; int msplat_set_cloud_storage(msplat_ctx* ctx, int32_t storage); int msplat_get_cloud_storage(const msplat_ctx* ctx);
 /* ---- SplatRenderer::Sort (splatrenderer.cpp:153-312): cull + depth key (presort_compute.glsl:31-57), stable ascending 32-bit
  * radix sort; the sorted index list stays context state for the following renders.  Asynchronous: the reference's 4-byte
  * readback stall (splatrenderer.cpp:195-204) is not reproduced. */
@@ -164,8 +162,10 @@ int msplat_render_stereo_layers(msplat_ctx* ctx, const float cameraMat0[16], con
 /* ---- which splat each pixel shows (INTEGRATION.md 20): the read half of msplat_set_visibility -- click, brush and lasso on the device.  Over the splats of the latest Sort (hidden ones are not in it), walked near to far at pixel centre p: w_i(p) = alpha times the Gaussian, 0 where splat_frag.glsl:37-40 discards (w <= 1/256); T_i = prod_{j in front of i}(1 - w_j); c_i = T_i w_i.  ids[p] = upload index (the numbering of msplat_get_sorted_indices, also for a cloud stored in Morton order) of the splat with the largest c_i, the nearest of equals; MSPLAT_ID_NONE where no splat has w_i(p) > 0.  id_depth[p] (NULL: no plane) = that splat's window depth 0.5 ndc.z + 0.5, the per-splat value msplat_render_depth blends and msplat_render_occluded tests; exactly 1.0 at MSPLAT_ID_NONE.  The walk ends only where no later splat can win (T <= best): the planes do not depend on t_epsilon, compositor_waves, frame_mode, two_pass, the fb format or the target mode.  window = x0, y0, w, h in viewport pixels, row 0 = GL bottom; NULL = the whole viewport.  Both planes are w x h OF THE WINDOW, 4-byte elements, in one memory space; a pitch of 0 = tight rows, else >= 4 w and a multiple of 4; padding bytes are not written; a window's planes equal that rectangle of the whole viewport's, bit for bit.  Host output returns after the copy and grows the pair buffer like msplat_render; device output is asynchronous on the stream, queued under async_submit, and reports pair overflow as a device-output msplat_render does.  The frame is a plain one-pass frame's projection and binning plus one kernel over the 16 x 16 tiles the window touches; it is never a two-pass frame and leaves msplat_get_two_pass_info and msplat_get_timings as they were.
  * Refused before anything is launched -- _INVALID_ARG: NULL ids, a window with w or h <= 0 or not inside the viewport, a bad pitch; _NO_CLOUD / _NO_SORT as msplat_render; _UNSUPPORTED (the context stays usable): a point cloud, msplat_set_depth_test, a target emulation, the tile probe, a banded context.  Out of scope: the device group, two views in one chain, an occluder plane for the id walk.  msplat_mark_ids: device memory only (pointers checked as msplat_set_visibility_device checks its own); for every pixel of the w x h plane d_ids whose d_region byte is nonzero (NULL: every pixel; region pitch 0 = w) and whose id is not MSPLAT_ID_NONE: d_mask[id] = value.  n must be the cloud's N (else _INVALID_ARG); an id >= n is skipped, never stored through.  Asynchronous on the context's stream, so ordered behind the id frame that wrote the plane.  value = 0 on a mask of ones, handed to msplat_set_visibility_device, hides what was brushed; value = 1 on zeros is a selection. */
 #define MSPLAT_ID_NONE 0xFFFFFFFFu
-int msplat_render_ids(msplat_ctx* ctx, const float cameraMat[16], const float projMat[16], const float viewport[4], const float nearFar[2], const int32_t window[4], uint32_t* ids, uint64_t ids_pitch_bytes, float* id_depth, uint64_t id_depth_pitch_bytes, int out_is_device);
-int msplat_mark_ids(msplat_ctx* ctx, const uint32_t* d_ids, uint64_t ids_pitch_bytes, uint32_t w, uint32_t h, const uint8_t* d_region, uint64_t region_pitch_bytes, uint8_t* d_mask, uint64_t n, uint8_t value);
+int msplat_render_ids(msplat_ctx* ctx, const float cameraMat[16], const float projMat[16], const float viewport[4], const float nearFar[2], const int32_t window[4], uint32_t* ids, uint64_t ids_pitch_bytes, float* id_depth, uint64_t id_depth_pitch_bytes, int out_is_device); int msplat_mark_ids(msplat_ctx* ctx, const uint32_t* d_ids, uint64_t ids_pitch_bytes, uint32_t w, uint32_t h, const uint8_t* d_region, uint64_t region_pitch_bytes, uint8_t* d_mask, uint64_t n, uint8_t value);
+/* ---- how much of the frame each splat contributes (INTEGRATION.md 21): the scatter half of msplat_render_ids -- select through a lasso, prune by importance, find floaters.  Over the splats of the latest Sort, walked near to far at pixel centre p, with w_i(p), T_i and c_i = T_i w_i exactly msplat_render_ids' (w = 0 where splat_frag.glsl:37-40 discards): q_i(p) = (uint32) rint(c_i(p) * 2^23), the multiply fp32 and exact, rounding to nearest, ties to even; MSPLAT_SCORE_ONE is one fully covered pixel.  For every splat i in upload numbering (the numbering of msplat_get_sorted_indices, also for a cloud stored in Morton order): score[i] += sum_p q_i(p); pixels[i] += #{p : q_i(p) >= 1} (NULL: none), p over the pixels of window (x0, y0, w, h in viewport pixels, row 0 = GL bottom; NULL = the whole viewport) whose d_region byte is nonzero (NULL: all; a w x h byte plane of the WINDOW, region pitch 0 = w, as msplat_mark_ids takes it).  The arrays are accumulated into, not overwritten: the caller zeroes them, one call per camera sums over views.  A pixel is finished when T <= 2^-24 (every later c <= T, so c * 2^23 <= 0.5 and q = 0): the sums do not depend on t_epsilon, compositor_waves, frame_mode, two_pass, the fb format, the target mode or how pixels are grouped; they are integers, so the order of the additions does not matter, and a window's scores plus its complement's equal the whole viewport's exactly.  A 16 x 16 tile adds at most 256 * 2^23 = 2^31 at once, an 8192^2 frame at most 2^49 per call.  Device memory only (pointers checked as msplat_mark_ids checks its own; d_score 8-byte, d_pixels 4-byte aligned); n must be the cloud's N (else _INVALID_ARG).  Asynchronous on the context's stream, queued under async_submit; pair overflow is reported as for a device-output msplat_render and, as with MSPLAT_TARGET_LOAD, the call is not idempotent: after MSPLAT_ERR_PAIR_OVERFLOW[_EARLIER] the caller zeroes the arrays and runs it again.  Refused before anything is launched -- _INVALID_ARG: NULL d_score, an empty window or one not inside the viewport, region pitch < w; _NO_CLOUD / _NO_SORT as msplat_render_ids; _UNSUPPORTED (the context stays usable): a point cloud, msplat_set_depth_test, a target emulation, the tile probe, a banded context.  Never a two-pass frame; msplat_get_two_pass_info and msplat_get_timings stay as they were.  Out of scope: the device group, host-memory arrays, two views in one chain, an occluder plane for the score walk.  msplat_mark_scores: for every i < n, MSPLAT_SCORE_BELOW: d_score[i] < threshold, MSPLAT_SCORE_AT_LEAST: d_score[i] >= threshold sets d_mask[i] = value; other bytes are untouched.  Checks as msplat_mark_ids (n == N, device pointers, a point cloud refused); asynchronous on the stream, so ordered behind the score frames that wrote d_score.  BELOW with value = 0 on a mask of ones, handed to msplat_set_visibility_device, prunes; AT_LEAST with value = 1 on zeros selects. */
+#define MSPLAT_SCORE_ONE 8388608u
+enum { MSPLAT_SCORE_BELOW = 0, MSPLAT_SCORE_AT_LEAST = 1 }; int msplat_render_scores(msplat_ctx* ctx, const float cameraMat[16], const float projMat[16], const float viewport[4], const float nearFar[2], const int32_t window[4], const uint8_t* d_region, uint64_t region_pitch_bytes, uint64_t* d_score, uint32_t* d_pixels, uint64_t n); int msplat_mark_scores(msplat_ctx* ctx, const uint64_t* d_score, uint64_t n, int32_t op, uint64_t threshold, uint8_t* d_mask, uint8_t value);
 /* blocks until everything queued on the context (and issued by its worker thread) has finished */
 int msplat_synchronize(msplat_ctx* ctx);
 /* ---- frames in flight.  The reference queues successive frames on one GL command stream and the driver overlaps them; here the overlap is

@@ -33,6 +33,9 @@ TARGET_MODES = {"clear": TARGET_CLEAR, "load": TARGET_LOAD, "premultiplied": TAR
 # msplat_set_crop: the shape, MSPLAT_CROP_INVERT or-ed in
 CROP_NONE, CROP_BOX, CROP_SPHERE, CROP_INVERT = 0, 1, 2, 0x100
 ID_NONE = 0xFFFFFFFF          # MSPLAT_ID_NONE: a pixel of an id plane (msplat_render_ids) no splat reaches
+SCORE_ONE = 8388608           # MSPLAT_SCORE_ONE: what one fully covered pixel adds to a splat's score (msplat_render_scores)
+SCORE_BELOW, SCORE_AT_LEAST = 0, 1   # msplat_mark_scores: the compare
+SCORE_OPS = {"below": SCORE_BELOW, "at_least": SCORE_AT_LEAST}
 CROP_SHAPES = {"box": CROP_BOX, "sphere": CROP_SPHERE}
 # "weighted": contiguous bands, rank 0 (the gather's root) weighted block_rows PERCENT of another rank (msplat.h)
 BAND_KINDS = {"contiguous": BANDS_CONTIGUOUS, "interleaved": BANDS_INTERLEAVED, "block": BANDS_BLOCK_INTERLEAVED,
@@ -145,6 +148,9 @@ SYMBOLS = [
                                     C.c_int]),
     ("msplat_mark_ids", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
                                   C.c_uint8]),
+    ("msplat_render_scores", C.c_int, [C.c_void_p, _F16, _F16, _F16, _F16, C.POINTER(C.c_int32), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                       C.c_uint64]),
+    ("msplat_mark_scores", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_uint64, C.c_void_p, C.c_uint8]),
     ("msplat_synchronize", C.c_int, [C.c_void_p]),
     ("msplat_read_image", C.c_int, [C.c_char_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     ("msplat_points_create", C.c_void_p, [C.c_int]),

@@ -1958,6 +1958,7 @@ int msplat_render_stereo_layers(msplat_ctx* ctx, const float cameraMat0[16], con
 }
 
 #include "msplat_ids.hip.inc"
+#include "msplat_scores.hip.inc"
 
 #include "msplat_getters.hip.inc"
 

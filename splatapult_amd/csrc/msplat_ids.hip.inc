@@ -14,33 +14,52 @@ struct IdsTarget {               // the planes of one id frame, both in one memo
     size_t depth_pitch;
 };
 
-// window: x0, y0, w, h in viewport pixels (checked)
-static int launch_ids(msplat_ctx* ctx, const FrameParams& fp, const int32_t window[4], const IdsTarget& out, bool async_overflow_flag)
+// What the id frame and the score frame launch before their own kernel, and what that kernel walks
+struct WalkChain {
+    IdsParams p;
+    uint32_t items;              // the 16x16 tiles the window touches
+    uint32_t grid;               // waves: one per item, or the context's pool of persistent waves
+    const uint32_t* order;       // storage slot -> upload index; NULL for a cloud stored in upload order
+};
+
+// a plain one-pass frame's projection and binning (want_zw: plus z_w per rank); window: x0, y0, w, h in viewport pixels (checked)
+static int issue_walk_chain(msplat_ctx* ctx, const FrameParams& fp, const int32_t window[4], bool want_zw, bool async_overflow_flag,
+                            WalkChain& wc)
 {
-    hipStream_t s = ctx->stream;
     uint32_t* counters = (uint32_t*)ctx->counters.p;
     const uint32_t N = (uint32_t)ctx->N;
-    RenderChain rc{ctx, fp, s, false, N, counters + kCntV, counters + kCntD, counters + kCntOverflow, (uint32_t*)ctx->queue.p,
+    RenderChain rc{ctx, fp, ctx->stream, false, N, counters + kCntV, counters + kCntD, counters + kCntOverflow, (uint32_t*)ctx->queue.p,
                    counters + kCntV, (uint32_t*)ctx->occ.p, fp.tiles_x * fp.tiles_y, (uint32_t)ctx->pair_cap,
                    false, 0, (int)std::max(1u, div_up(N, kProjThreads)), nullptr, nullptr, 0, async_overflow_flag, FramePlanes{}};
-    rc.want_zw = true;           // z_w per rank, as for a frame with planes
-    int arc = buf_alloc(ctx, ctx->zq, std::max<uint64_t>(std::max(ctx->rank_cap, ctx->N), 1) * 4);
-    if (arc) return arc;
+    rc.want_zw = want_zw;        // z_w per rank, as for a frame with planes
+    if (want_zw) {
+        int arc = buf_alloc(ctx, ctx->zq, std::max<uint64_t>(std::max(ctx->rank_cap, ctx->N), 1) * 4);
+        if (arc) return arc;
+    }
     issue_projection(rc, PROJ_PLAIN, 0.0f);
     issue_binning(rc, 0, 0);
-    IdsParams p;
+    IdsParams& p = wc.p;
     p.tiles_x = fp.tiles_x;
     p.x0 = window[0]; p.y0 = window[1]; p.x1 = window[0] + window[2]; p.y1 = window[1] + window[3];
     p.tile_x0 = p.x0 / kTile; p.tile_y0 = p.y0 / kTile;
     p.tiles_w = (p.x1 - 1) / kTile - p.tile_x0 + 1;
-    const uint32_t items = (uint32_t)p.tiles_w * (uint32_t)((p.y1 - 1) / kTile - p.tile_y0 + 1);
+    wc.items = (uint32_t)p.tiles_w * (uint32_t)((p.y1 - 1) / kTile - p.tile_y0 + 1);
     // every item on its own wave where the compositor would do the same, else the context's pool of persistent waves and the queue
-    const uint32_t pool = (ctx->comp_waves_auto && items <= 20480u) ? items : (uint32_t)ctx->comp_waves;
-    const uint32_t* order = (ctx->store && ctx->store->reordered) ? (const uint32_t*)ctx->store->order_dev.p : nullptr;
+    const uint32_t pool = (ctx->comp_waves_auto && wc.items <= 20480u) ? wc.items : (uint32_t)ctx->comp_waves;
+    wc.grid = std::min(wc.items, pool);
+    wc.order = (ctx->store && ctx->store->reordered) ? (const uint32_t*)ctx->store->order_dev.p : nullptr;
+    return MSPLAT_OK;
+}
+
+static int launch_ids(msplat_ctx* ctx, const FrameParams& fp, const int32_t window[4], const IdsTarget& out, bool async_overflow_flag)
+{
+    WalkChain wc;
+    int arc = issue_walk_chain(ctx, fp, window, true, async_overflow_flag, wc);
+    if (arc) return arc;
     if (fp.tiles_x * fp.tiles_y > 0)
-        hipLaunchKernelGGL(composite_ids_kernel, dim3(std::min(items, pool)), dim3(kCompThreads), 0, s, (const uint32_t*)ctx->tile_start.p,
+        hipLaunchKernelGGL(composite_ids_kernel, dim3(wc.grid), dim3(kCompThreads), 0, ctx->stream, (const uint32_t*)ctx->tile_start.p,
                            (const uint32_t*)ctx->pairsB.p, (const float4*)ctx->rec2d.p, (const float*)ctx->zq.p, (const uint32_t*)ctx->valA.p,
-                           order, p, (uint32_t)ctx->pair_cap, (uint32_t*)ctx->queue.p, items, out.ids, out.ids_pitch, out.depth,
+                           wc.order, wc.p, (uint32_t)ctx->pair_cap, (uint32_t*)ctx->queue.p, wc.items, out.ids, out.ids_pitch, out.depth,
                            out.depth_pitch);
     if (hipGetLastError() != hipSuccess) {
         ctx->tables_dirty = true;
@@ -88,6 +107,25 @@ static int ids_pitch(msplat_ctx* ctx, const char* who, const char* what, uint64_
 
 struct IdsWindow { bool given; int32_t v[4]; };
 
+// What the frames that walk the lists themselves (the id frame, the score frame: `walk` names it) refuse after begin_frame, and
+// their window: not given = the whole viewport; else x0, y0, w, h, not empty and inside the viewport
+static int walk_frame_window(msplat_ctx* ctx, const char* who, const char* walk, const FrameParams& fp, IdsWindow& win)
+{
+    char why[160] = "";
+    if (ctx->point_mode) std::snprintf(why, sizeof(why), "the context holds a point cloud (the sprite pipeline has no %s walk)", walk);
+    else if (ctx->depth_bits != 0) std::snprintf(why, sizeof(why), "msplat_set_depth_test is on (the %s walk is front to back, without a depth buffer)", walk);
+    else if (ctx->rop != MSPLAT_ROP_NONE) std::snprintf(why, sizeof(why), "msplat_set_target_emulation is not MSPLAT_ROP_NONE (the %s walk blends in fp32)", walk);
+    else if (ctx->probe_on) std::snprintf(why, sizeof(why), "the tile probe (msplat_set_tile_probe) has no %s walk", walk);
+    else if (ctx->banded) std::snprintf(why, sizeof(why), "the context is banded (msplat_set_band / msplat_set_band_layout): the %s frame covers whole windows", walk);
+    if (why[0]) return fail(ctx, MSPLAT_ERR_UNSUPPORTED, "%s: %s", who, why);
+    if (!win.given) { win.v[0] = 0; win.v[1] = 0; win.v[2] = fp.width; win.v[3] = fp.height; }
+    const int32_t* w = win.v;
+    if (w[2] <= 0 || w[3] <= 0 || w[0] < 0 || w[1] < 0 || (int64_t)w[0] + w[2] > fp.width || (int64_t)w[1] + w[3] > fp.height)
+        return fail(ctx, MSPLAT_ERR_INVALID_ARG, "%s: window (%d, %d, %d, %d) is empty or not inside the %d x %d viewport", who, w[0], w[1],
+                    w[2], w[3], fp.width, fp.height);
+    return MSPLAT_OK;
+}
+
 static int ids_impl(msplat_ctx* ctx, const float cameraMat[16], const float projMat[16], const float viewport[4], const float nearFar[2],
                     IdsWindow win, uint32_t* ids, uint64_t ids_pitch_bytes, float* id_depth, uint64_t depth_pitch_bytes, int out_is_device)
 {
@@ -95,17 +133,8 @@ static int ids_impl(msplat_ctx* ctx, const float cameraMat[16], const float proj
     FrameParams fp;
     int rc = begin_frame(ctx, who, true, ids ? nullptr : "ids is NULL", cameraMat, projMat, viewport, nearFar, fp);
     if (rc) return rc;
-    const char* why = ctx->point_mode ? "the context holds a point cloud (the sprite pipeline has no id walk)"
-                      : ctx->depth_bits != 0 ? "msplat_set_depth_test is on (the id walk is front to back, without a depth buffer)"
-                      : ctx->rop != MSPLAT_ROP_NONE ? "msplat_set_target_emulation is not MSPLAT_ROP_NONE (the id walk blends in fp32)"
-                      : ctx->probe_on ? "the tile probe (msplat_set_tile_probe) has no id walk"
-                      : ctx->banded ? "the context is banded (msplat_set_band / msplat_set_band_layout): an id frame covers whole windows" : nullptr;
-    if (why) return fail(ctx, MSPLAT_ERR_UNSUPPORTED, "%s: %s", who, why);
-    if (!win.given) { win.v[0] = 0; win.v[1] = 0; win.v[2] = fp.width; win.v[3] = fp.height; }
+    if ((rc = walk_frame_window(ctx, who, "id", fp, win))) return rc;
     const int32_t* w = win.v;
-    if (w[2] <= 0 || w[3] <= 0 || w[0] < 0 || w[1] < 0 || (int64_t)w[0] + w[2] > fp.width || (int64_t)w[1] + w[3] > fp.height)
-        return fail(ctx, MSPLAT_ERR_INVALID_ARG, "%s: window (%d, %d, %d, %d) is empty or not inside the %d x %d viewport", who, w[0], w[1],
-                    w[2], w[3], fp.width, fp.height);
     if ((rc = ids_pitch(ctx, who, "ids", ids_pitch_bytes, (uint64_t)w[2]))) return rc;
     if (id_depth && (rc = ids_pitch(ctx, who, "id_depth", depth_pitch_bytes, (uint64_t)w[2]))) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));

@@ -1,4 +1,4 @@
-// msplat_kernels.hip.h -- hand-written CDNA4 (gfx950, wave64) kernels of the splat hot path, in nine parts.
+// msplat_kernels.hip.h -- hand-written CDNA4 (gfx950, wave64) kernels of the splat hot path, in ten parts.
 //
 // Replaces (not ports) the reference's GL pipeline:
 //   shader/presort_compute.glsl + shader/multi_radixsort*.glsl  -> msplat_sort.hip.h      radix_* / ws_* (cull fused in pass 0)
@@ -6,6 +6,7 @@
 //   GL rasteriser + shader/splat_frag.glsl + ROP blend          -> msplat_binning.hip.h   bin1_* (+ radix_*<MODE_PAIR>)
 //                                                                  msplat_composite.hip.h composite_kernel, composite_depth_kernel
 //   which splat a pixel shows (no reference part)               -> msplat_ids.hip.h       composite_ids_kernel, mark_ids_kernel
+//   what each splat contributes (no reference part)             -> msplat_scores.hip.h    composite_scores_kernel, mark_scores_kernel
 //   GaussianCloud::ImportPly's per-vertex math, storage order   -> msplat_cloud.hip.h     ingest_kernel, morton / gather / cull boxes
 //   shader/point_*.glsl                                         -> msplat_points.hip.h
 //   two-pass frame with occlusion feedback (no reference part)  -> msplat_occlusion.hip.h
@@ -22,5 +23,6 @@
 #include "msplat_binning.hip.h"
 #include "msplat_composite.hip.h"
 #include "msplat_ids.hip.h"
+#include "msplat_scores.hip.h"
 #include "msplat_points.hip.h"
 #include "msplat_occlusion.hip.h"

@@ -3,7 +3,7 @@
 // Sort + Render into an explicit RGBA32F framebuffer, dumped as a binary PPM-like float file.
 //
 //   g++ -std=c++17 -I. splatapult_amd/host/example_render.cpp -Lsplatapult_amd/lib -lmsplat -o example_render
-//   ./example_render scene.ply out.f32 [width height] [--nosh] [--frames-in-flight N] [--devices 0,1,2,...] [--over-gradient] [--depth out_depth.f32] [--srgb8 out.png] [--crop-sphere cx cy cz r] [--pick X,Y]
+//   ./example_render scene.ply out.f32 [width height] [--nosh] [--frames-in-flight N] [--devices 0,1,2,...] [--over-gradient] [--depth out_depth.f32] [--srgb8 out.png] [--crop-sphere cx cy cz r] [--pick X,Y] [--min-score S]
 // With --frames-in-flight N the same frame is issued N + 1 times round-robin over N contexts that share the cloud
 // (SplatRenderer::SetFramesInFlight); the last one is written.  With --devices the frame's bin rows are dealt to the
 // listed GPUs (SplatRenderer::ConfigureDevices, msplat_group_*): same pixels.  With --over-gradient the target is first filled with
@@ -17,15 +17,37 @@
 // MSPLAT_CROP_SPHERE): the cloud is uploaded whole, the Sort and everything behind it work on what the crop keeps.  One device only.
 // With --pick X,Y the splat that contributes most to pixel (X, Y) (row 0 = bottom) and its window depth are printed (SplatRenderer::Pick,
 // msplat_render_ids through a 1 x 1 window).  One device only.
+// With --min-score S the rendered view is scored (SplatRenderer::RenderScores), every splat that contributes less than S fully covered
+// pixels to it is hidden (MarkScores below S * MSPLAT_SCORE_ONE into a mask of ones, SetVisibilityDevice), and the frame is sorted and
+// rendered again: what is written is the pruned view; the number of hidden splats is printed.  One device, one frame in flight.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <dlfcn.h>
 #include <memory>
 #include <vector>
 
 #include "msplat_host.hpp"
 #include "scene_config.hpp"
+
+// device memory without the HIP headers: four calls of the runtime libmsplat.so already brought into the process
+struct DeviceMemory {
+    int (*alloc)(void**, size_t) = nullptr;
+    int (*fill)(void*, int, size_t) = nullptr;
+    int (*release)(void*) = nullptr;
+    int (*wait)() = nullptr;
+    bool Load()
+    {
+        void* hip = dlopen("libamdhip64.so", RTLD_NOW | RTLD_GLOBAL);
+        if (!hip) return false;
+        alloc = reinterpret_cast<int (*)(void**, size_t)>(dlsym(hip, "hipMalloc"));
+        fill = reinterpret_cast<int (*)(void*, int, size_t)>(dlsym(hip, "hipMemset"));
+        release = reinterpret_cast<int (*)(void*)>(dlsym(hip, "hipFree"));
+        wait = reinterpret_cast<int (*)()>(dlsym(hip, "hipDeviceSynchronize"));
+        return alloc && fill && release && wait;
+    }
+};
 
 int main(int argc, char** argv)
 {
@@ -38,6 +60,7 @@ int main(int argc, char** argv)
     if (argc >= 5 && argv[3][0] != '-') { W = std::atoi(argv[3]); H = std::atoi(argv[4]); }
     int inFlight = 1;
     int pickX = -1, pickY = -1;      // --pick: print the splat under this pixel (row 0 = bottom) and its window depth
+    double minScore = -1.0;          // --min-score: hide the splats that contribute less than this many pixels, render again
     const char* depthPath = nullptr;
     const char* srgb8Path = nullptr;
     std::vector<int> devices;
@@ -51,6 +74,7 @@ int main(int argc, char** argv)
         if (!std::strcmp(argv[i], "--depth") && i + 1 < argc) depthPath = argv[i + 1];
         if (!std::strcmp(argv[i], "--pick") && i + 1 < argc && std::sscanf(argv[i + 1], "%d,%d", &pickX, &pickY) != 2) pickX = pickY = -1;
         if (!std::strcmp(argv[i], "--srgb8") && i + 1 < argc) srgb8Path = argv[i + 1];
+        if (!std::strcmp(argv[i], "--min-score") && i + 1 < argc) minScore = std::atof(argv[i + 1]);
         if (!std::strcmp(argv[i], "--devices") && i + 1 < argc)
             for (const char* p = argv[i + 1]; *p;) {
                 devices.push_back(std::atoi(p));
@@ -118,6 +142,27 @@ int main(int argc, char** argv)
         if (!renderer.Pick(cameraMat, projMat, viewport, nearFar, pickX, pickY, &index, &zw)) return 1;
         if (index == MSPLAT_ID_NONE) std::printf("pick (%d, %d): no splat, z_w %.9g\n", pickX, pickY, zw);
         else std::printf("pick (%d, %d): splat %u, z_w %.9g\n", pickX, pickY, index, zw);
+    }
+    if (minScore >= 0.0 && inFlight == 1 && devices.size() <= 1) {
+        const size_t n = cloud->GetNumGaussians();
+        DeviceMemory dm;
+        void *score = nullptr, *mask = nullptr;
+        if (!dm.Load() || dm.alloc(&score, n * 8) != 0 || dm.alloc(&mask, n) != 0) return 1;
+        if (dm.fill(score, 0, n * 8) != 0 || dm.fill(mask, 1, n) != 0 || dm.wait() != 0) return 1;      // filled before the context's stream starts
+        if (!renderer.RenderScores(cameraMat, projMat, viewport, nearFar, nullptr, static_cast<uint64_t*>(score), n)) return 1;
+        if (!renderer.MarkScores(static_cast<const uint64_t*>(score), n, MSPLAT_SCORE_BELOW, (uint64_t)(minScore * (double)MSPLAT_SCORE_ONE),
+                                 static_cast<uint8_t*>(mask), 0))
+            return 1;
+        if (!renderer.SetVisibilityDevice(static_cast<const uint8_t*>(mask), n)) return 1;
+        renderer.Sort(cameraMat, projMat, viewport, nearFar);
+        if (depthPath) renderer.RenderWithDepth(cameraMat, projMat, viewport, nearFar, depth.data());
+        else renderer.Render(cameraMat, projMat, viewport, nearFar);
+        renderer.Synchronize();
+        uint64_t hidden = 0;
+        if (msplat_get_visibility(renderer.GetContext(), nullptr, nullptr, &hidden) != MSPLAT_OK) return 1;
+        std::printf("min score %g: %llu of %zu splats hidden\n", minScore, (unsigned long long)hidden, n);
+        dm.release(score);
+        dm.release(mask);
     }
 
     FILE* f = std::fopen(argv[2], "wb");

@@ -384,6 +384,39 @@ public:
         }
         return true;
     }
+    // How much of the frame each splat contributes (msplat_render_scores): d_score[i] += the sum over the pixels of window (nullptr = the
+    // whole viewport) that d_region selects (nonzero byte of a w x h plane of the window; nullptr = all) of rint(T_i w_i 2^23), i in upload
+    // numbering; MSPLAT_SCORE_ONE is one fully covered pixel; d_pixels (may be nullptr) += the number of those pixels with a nonzero term.
+    // Device memory only, n = the cloud's splats; the arrays are accumulated into: zero them first, call once per camera to sum over views.
+    // Asynchronous on the stream of the latest Sort's context.  A device group has no score frame.
+    template <class Mat4, class Vec4, class Vec2>
+    bool RenderScores(const Mat4& cameraMat, const Mat4& projMat, const Vec4& viewport, const Vec2& nearFar, const int32_t* window,
+                      uint64_t* d_score, size_t n, uint32_t* d_pixels = nullptr, const uint8_t* d_region = nullptr, uint64_t regionPitchBytes = 0)
+    {
+        static_assert(sizeof(Mat4) == 64 && sizeof(Vec4) == 16 && sizeof(Vec2) == 8, "glm-compatible layout expected");
+        if (group || !ctx) {
+            std::fprintf(stderr, "[msplat][E] RenderScores: %s\n", group ? "a device group has no score frame" : "no cloud (Init first)");
+            return false;
+        }
+        const int rc = msplat_render_scores(ctx, F(cameraMat), F(projMat), F(viewport), F(nearFar), window, d_region, regionPitchBytes, d_score,
+                                            d_pixels, n);
+        if (rc != MSPLAT_OK) std::fprintf(stderr, "[msplat][%c] RenderScores: %s\n", Level(rc), msplat_last_error(ctx));
+        return rc == MSPLAT_OK || rc == MSPLAT_ERR_PAIR_OVERFLOW_EARLIER;
+    }
+    // d_mask[i] = value for every splat with d_score[i] < threshold (op = MSPLAT_SCORE_BELOW) or >= threshold (MSPLAT_SCORE_AT_LEAST)
+    // (msplat_mark_scores); other bytes stay.  Device memory only; asynchronous on the stream, behind the RenderScores that wrote d_score.
+    bool MarkScores(const uint64_t* d_score, size_t n, int32_t op, uint64_t threshold, uint8_t* d_mask, uint8_t value)
+    {
+        if (group || !ctx) {
+            std::fprintf(stderr, "[msplat][E] MarkScores: %s\n", group ? "a device group has no per-splat visibility" : "no cloud (Init first)");
+            return false;
+        }
+        if (msplat_mark_scores(ctx, d_score, n, op, threshold, d_mask, value) != MSPLAT_OK) {
+            std::fprintf(stderr, "[msplat][E] MarkScores: %s\n", msplat_last_error(ctx));
+            return false;
+        }
+        return true;
+    }
 
     // blocks until every frame in flight has finished
     // (also where a pair-buffer overflow of an earlier device-target Render is reported, see msplat_render)

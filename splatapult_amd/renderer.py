@@ -635,6 +635,107 @@ class SplatRenderer:
                                                          C.c_void_p(int(region_ptr)) if region_ptr is not None else None,
                                                          region_pitch_bytes, C.c_void_p(int(mask_ptr)), self._n, value))
 
+    # -- how much of the frame each splat contributes (msplat_render_scores / msplat_mark_scores) --
+    def _device_vector(self, name, t, dtype):
+        """a contiguous torch tensor of N values of `dtype` on this renderer's device (ValueError otherwise)"""
+        import torch
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != (self._n,) or not t.is_contiguous():
+            raise ValueError("%s must be a contiguous torch %s tensor of shape (%d,)" % (name, str(dtype).split(".")[-1], self._n))
+        if t.device.type != "cuda" or (t.device.index or 0) != self._device:
+            raise ValueError("%s must live on device %d, not on %s" % (name, self._device, t.device))
+        return t
+
+    def RenderScores(self, cameraMat, projMat, viewport, nearFar, window=None, region=None, score=None, pixels=False):
+        """Per splat of the cloud (upload numbering) what it contributes to the view: score[i] += the sum over the pixels of
+        window = (x0, y0, w, h) (viewport pixels, row 0 = GL bottom; None = the whole viewport) of rint(T_i w_i 2^23), over the
+        splats of the latest Sort; _capi.SCORE_ONE is one fully covered pixel.  region: an (h, w) uint8 / bool plane of the WINDOW,
+        nonzero = the pixel counts -- a torch tensor on this renderer's device (rows may be strided) or a numpy array; None = all.
+        Returns a torch int64 tensor on the renderer's device (the values stay below 2^63), or (score, hits) with pixels=True
+        (or an int32 tensor): hits[i] += the number of those pixels with a nonzero term.  score=None allocates zeroed tensors,
+        waits for the frame and runs it once more from fresh zeros if the pair buffer overflowed; a given score (int64) / pixels
+        (int32) tensor is accumulated into -- one call per camera sums over views -- asynchronously on the context's stream,
+        which torch's current stream is made to wait for.  ValueError for arguments that cannot be right, before the library is
+        called."""
+        import torch
+        f = self._args.load(cameraMat, projMat, viewport, nearFar)
+        W, H = int(self._args.vp[2]), int(self._args.vp[3])
+        if window is None:
+            win, (w, h) = None, (W, H)
+        else:
+            if len(window) != 4 or any(int(v) != v for v in window):
+                raise ValueError("window must be four integers (x0, y0, w, h), not %r" % (window,))
+            x0, y0, w, h = (int(v) for v in window)
+            if w <= 0 or h <= 0 or x0 < 0 or y0 < 0 or x0 + w > W or y0 + h > H:
+                raise ValueError("window %r is empty or not inside the %d x %d viewport" % (tuple(window), W, H))
+            win = (C.c_int32 * 4)(x0, y0, w, h)
+        dev = torch.device("cuda", self._device)
+        region_ptr, region_pitch = None, 0
+        if region is not None:
+            if isinstance(region, np.ndarray):
+                region = torch.from_numpy(np.ascontiguousarray(region)).to(dev)
+            if (not isinstance(region, torch.Tensor) or region.dtype not in (torch.uint8, torch.bool) or tuple(region.shape) != (h, w)
+                    or (w > 1 and region.stride(1) != 1) or (h > 1 and region.stride(0) < w)):
+                raise ValueError("region must be a uint8 / bool plane of shape (%d, %d) with unit column stride" % (h, w))
+            if region.device != dev:
+                raise ValueError("region must live on %s, not on %s" % (dev, region.device))
+            region_ptr, region_pitch = C.c_void_p(region.data_ptr()), (region.stride(0) if h > 1 else w)
+        own = score is None
+        if own and isinstance(pixels, torch.Tensor):
+            raise ValueError("a pixels tensor goes with a score tensor: both are accumulated into")
+        if not own:
+            self._device_vector("score", score, torch.int64)
+            if pixels is True:
+                raise ValueError("with a score tensor pass the int32 tensor to accumulate the hit counts into as pixels=")
+        hits = self._device_vector("pixels", pixels, torch.int32) if isinstance(pixels, torch.Tensor) else None
+        if not self._ctx:
+            raise _capi.MsplatError(_capi.ERR_NO_CLOUD, "RenderScores: no cloud (Init first)")
+
+        def issue():
+            torch.cuda.current_stream(dev).synchronize()                # what produced the tensors has completed
+            _capi.check(self._ctx, self._lib.msplat_render_scores(self._ctx, *f, win, region_ptr, region_pitch, C.c_void_p(score.data_ptr()),
+                                                                  C.c_void_p(hits.data_ptr()) if hits is not None else None, self._n))
+        if not own:
+            issue()
+            self.wait_on_stream(torch.cuda.current_stream(dev).cuda_stream)
+            return score if hits is None else (score, hits)
+        for attempt in range(2):
+            score = torch.zeros(self._n, dtype=torch.int64, device=dev)
+            hits = torch.zeros(self._n, dtype=torch.int32, device=dev) if pixels else None
+            issue()
+            try:
+                _capi.check(self._ctx, self._lib.msplat_synchronize(self._ctx))
+                break
+            except _capi.MsplatError as e:                              # this frame's overflow: the buffer has grown
+                if e.code != _capi.ERR_PAIR_OVERFLOW or attempt:
+                    raise
+        return score if hits is None else (score, hits)
+
+    def MarkScores(self, score, op, threshold, mask, value):
+        """mask[i] = value for every splat whose score[i] is below `threshold` (op "below") or at least it ("at_least"); other
+        bytes stay (msplat_mark_scores).  score: the int64 tensor RenderScores returns; mask: a torch uint8 / bool tensor of N
+        bytes on the same device -- what SetVisibility takes.  "below" with value 0 on a mask of ones prunes, "at_least" with
+        value 1 on zeros selects.  Asynchronous on the current context's stream, behind the score frames that wrote `score`;
+        torch's current stream is made to wait for it.  threshold: 0 .. 2^64 - 1."""
+        import torch
+        if op not in _capi.SCORE_OPS:
+            raise ValueError("op must be one of %s (got %r)" % (sorted(_capi.SCORE_OPS), op))
+        value, threshold = int(value), int(threshold)
+        if not 0 <= value <= 255:
+            raise ValueError("value is one byte, 0..255 (got %d)" % value)
+        if not 0 <= threshold < 2 ** 64:
+            raise ValueError("threshold is an unsigned 64-bit value (got %d)" % threshold)
+        if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.uint8, torch.bool):
+            raise ValueError("mask must be a torch uint8 / bool tensor")
+        self._device_vector("score", score, torch.int64)
+        self._device_vector("mask", mask, mask.dtype)
+        if not self._ctx:
+            raise _capi.MsplatError(_capi.ERR_NO_CLOUD, "MarkScores: no cloud (Init first)")
+        dev = torch.device("cuda", self._device)
+        torch.cuda.current_stream(dev).synchronize()
+        _capi.check(self._ctx, self._lib.msplat_mark_scores(self._ctx, C.c_void_p(score.data_ptr()), self._n, _capi.SCORE_OPS[op], threshold,
+                                                            C.c_void_p(mask.data_ptr()), value))
+        self.wait_on_stream(torch.cuda.current_stream(dev).cuda_stream)
+
     def synchronize(self):
         """blocks until every frame in flight has been issued (async_submit) AND has finished on the GPU"""
         for h in self._ctxs:
