@@ -131,7 +131,7 @@ enum { MSPLAT_CROP_NONE = 0, MSPLAT_CROP_BOX = 1, MSPLAT_CROP_SPHERE = 2, MSPLAT
 int msplat_set_visibility(msplat_ctx* ctx, const uint8_t* visible, uint64_t n);             /* host memory; copied before return (waits at most for the PREVIOUS mask's copy) */
 int msplat_set_visibility_device(msplat_ctx* ctx, const uint8_t* d_visible, uint64_t n);    /* device memory of the context's device; asynchronous on the context's stream, never waits: the source stays valid until that work has run (msplat_synchronize / msplat_stream_wait) */
 int msplat_set_crop(msplat_ctx* ctx, const float worldToCrop[16], int32_t shape);           /* NULL or MSPLAT_CROP_NONE: no crop */
-int msplat_get_visibility(msplat_ctx* ctx, int32_t* has_mask, int32_t* crop_shape, uint64_t* hidden);   /* hidden: splats the latest Sort's plane hides (synchronises); any out pointer may be NULL */
+int msplat_get_visibility(msplat_ctx* ctx, int32_t* has_mask, int32_t* crop_shape, uint64_t* hidden);   /* hidden: splats the latest Sort's plane hides (synchronises); any out pointer may be NULL */ /* ---- msplat_compact_cloud makes the mask and the crop permanent, on the device: it keeps splat i (upload numbering) iff mask(i) && crop(i), the rule above as the context's NEXT Sort would apply it (a NaN centre: kept by a mask alone, dropped by a crop, kept by an inverted crop), and renumbers the K kept splats 0..K-1 in ascending old upload index.  d_index_map (NULL: none; else N uint32 of device memory of the context's device, 4-byte aligned, checked as msplat_mark_ids checks its pointers): d_index_map[i] = new upload index of splat i, the exclusive prefix sum of the keep flags, or MSPLAT_ID_NONE where it was dropped.  n_kept_out (host, may be NULL) receives K.  pos4 and the stored records are copied bit for bit -- nothing is unpacked, re-rounded or re-quantised -- and the store keeps the storage kind and full_sh it had (msplat_set_cloud_storage still speaks of the next upload): msplat_download_cloud afterwards = the kept rows of msplat_download_cloud before, bit for bit, in every storage.  The context afterwards is what msplat_upload_cloud of the kept source rows, same storage and spatial_order, leaves: records, storage order (the spatial reorder runs on the compacted cloud: under AUTO it may enter or leave Morton storage where K crosses 2^18), cull boxes, the keys, indices and frames of every later Sort / Render, bit for bit; K == 0 is an upload of n = 0, K == N has the same postconditions and an identity map.  The mask is dropped (the numbering is new), the crop kept and evaluated on the new cloud at the next Sort; a render before that Sort returns MSPLAT_ERR_NO_SORT.  Synchronous like the uploads: drains async_submit work and the stream, returns after the stream has drained.  Never in place: the kept records are gathered into a fresh store (peak = old + new store, + the reorder's second copy of the new one); if that allocation fails: MSPLAT_ERR_HIP and the context renders what it rendered before; a failure after the swap leaves no cloud, as a failed upload does.  A store shared with attached contexts is not modified: this context gets a store of its own, the others render the old cloud until msplat_attach_cloud is called again.  Refused before anything is launched -- _INVALID_ARG: NULL ctx, a bad d_index_map; _NO_CLOUD; _UNSUPPORTED (the context stays usable): a point cloud.  Out of scope: the device group, a mask other than the context's own, a device-memory download of the records. */ int msplat_compact_cloud(msplat_ctx* ctx, uint32_t* d_index_map, uint64_t* n_kept_out);
 /* ---- SplatRenderer::Render (splatrenderer.cpp:315-343) plus the GL pipeline behind its glDrawElements: splat_vert / _geom / _frag.glsl and
  * the blend / clear state of app.cpp:144-164.  Writes W x H RGBA (float, half or 4 bytes), row 0 = GL bottom row, alpha = 1 (msplat_set_target_mode: or
  * over the target's contents).  out_is_device != 0: `rgba` is device memory, the call is asynchronous on the stream; else host memory, the

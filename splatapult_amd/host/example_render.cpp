@@ -3,7 +3,7 @@
 // Sort + Render into an explicit RGBA32F framebuffer, dumped as a binary PPM-like float file.
 //
 //   g++ -std=c++17 -I. splatapult_amd/host/example_render.cpp -Lsplatapult_amd/lib -lmsplat -o example_render
-//   ./example_render scene.ply out.f32 [width height] [--nosh] [--frames-in-flight N] [--devices 0,1,2,...] [--over-gradient] [--depth out_depth.f32] [--srgb8 out.png] [--crop-sphere cx cy cz r] [--pick X,Y] [--min-score S]
+//   ./example_render scene.ply out.f32 [width height] [--nosh] [--frames-in-flight N] [--devices 0,1,2,...] [--over-gradient] [--depth out_depth.f32] [--srgb8 out.png] [--crop-sphere cx cy cz r] [--pick X,Y] [--min-score S] [--compact]
 // With --frames-in-flight N the same frame is issued N + 1 times round-robin over N contexts that share the cloud
 // (SplatRenderer::SetFramesInFlight); the last one is written.  With --devices the frame's bin rows are dealt to the
 // listed GPUs (SplatRenderer::ConfigureDevices, msplat_group_*): same pixels.  With --over-gradient the target is first filled with
@@ -20,6 +20,9 @@
 // With --min-score S the rendered view is scored (SplatRenderer::RenderScores), every splat that contributes less than S fully covered
 // pixels to it is hidden (MarkScores below S * MSPLAT_SCORE_ONE into a mask of ones, SetVisibilityDevice), and the frame is sorted and
 // rendered again: what is written is the pruned view; the number of hidden splats is printed.  One device, one frame in flight.
+// With --compact, after --min-score / --crop-sphere, the hidden splats are dropped for good (SplatRenderer::CompactCloud,
+// msplat_compact_cloud: the kept records gathered into a new store on the device), the splat counts before and after are printed and
+// the frame is sorted and rendered once more from the smaller cloud: the same pixels.  One device only.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -56,7 +59,7 @@ int main(int argc, char** argv)
         return 2;
     }
     int W = 1024, H = 768;   // the reference's default window (sdl_main.cpp:92)
-    bool nosh = false, overGradient = false;
+    bool nosh = false, overGradient = false, compact = false;
     if (argc >= 5 && argv[3][0] != '-') { W = std::atoi(argv[3]); H = std::atoi(argv[4]); }
     int inFlight = 1;
     int pickX = -1, pickY = -1;      // --pick: print the splat under this pixel (row 0 = bottom) and its window depth
@@ -70,6 +73,7 @@ int main(int argc, char** argv)
             for (int k = 0; k < 4; ++k) cropSphere[k] = (float)std::atof(argv[i + 1 + k]);
         nosh = nosh || !std::strcmp(argv[i], "--nosh");
         overGradient = overGradient || !std::strcmp(argv[i], "--over-gradient");
+        compact = compact || !std::strcmp(argv[i], "--compact");
         if (!std::strcmp(argv[i], "--frames-in-flight") && i + 1 < argc) inFlight = std::atoi(argv[i + 1]);
         if (!std::strcmp(argv[i], "--depth") && i + 1 < argc) depthPath = argv[i + 1];
         if (!std::strcmp(argv[i], "--pick") && i + 1 < argc && std::sscanf(argv[i + 1], "%d,%d", &pickX, &pickY) != 2) pickX = pickY = -1;
@@ -163,6 +167,22 @@ int main(int argc, char** argv)
         std::printf("min score %g: %llu of %zu splats hidden\n", minScore, (unsigned long long)hidden, n);
         dm.release(score);
         dm.release(mask);
+    }
+
+    if (compact && devices.size() <= 1) {
+        uint64_t kept = 0;
+        if (!renderer.CompactCloud(nullptr, &kept)) return 1;
+        std::printf("compacted: %zu -> %llu splats\n", cloud->GetNumGaussians(), (unsigned long long)kept);
+        if (overGradient)
+            for (int y = 0; y < H; ++y)
+                for (int x = 0; x < W; ++x) {
+                    float* px = &fb[((size_t)y * W + x) * 4];
+                    px[0] = 0.1f; px[1] = 0.2f; px[2] = 0.2f + 0.6f * (float)y / (float)H; px[3] = 1.0f;
+                }
+        renderer.Sort(cameraMat, projMat, viewport, nearFar);
+        if (depthPath) renderer.RenderWithDepth(cameraMat, projMat, viewport, nearFar, depth.data());
+        else renderer.Render(cameraMat, projMat, viewport, nearFar);
+        renderer.Synchronize();
     }
 
     FILE* f = std::fopen(argv[2], "wb");

@@ -343,6 +343,27 @@ public:
         return true;
     }
 
+    // Makes the mask and the crop permanent, on the device (msplat_compact_cloud): the cloud becomes the K splats they let through,
+    // renumbered 0..K-1 in ascending old index, records copied bit for bit -- the renderer afterwards is one Init'ed with those rows.
+    // d_index_map (may be nullptr): the old N uint32 of device memory, [i] = new index of splat i or MSPLAT_ID_NONE.  Every frame in
+    // flight is finished first; context 0 is compacted, the others are attached again and the next Sort lands on context 0, as after
+    // InitDevice.  The masks of all contexts are gone, the crop stays; Sort before the next Render.  *kept (may be nullptr) = K.
+    bool CompactCloud(uint32_t* d_index_map = nullptr, uint64_t* kept = nullptr)
+    {
+        if (group || ctxs.empty()) {
+            std::fprintf(stderr, "[msplat][E] CompactCloud: %s\n", group ? "a device group has no per-splat visibility" : "no cloud (Init first)");
+            return false;
+        }
+        Synchronize();
+        ctx = ctxs[0];
+        cur = (int)ctxs.size() - 1;           // the next Sort lands on context 0
+        if (msplat_compact_cloud(ctx, d_index_map, kept) != MSPLAT_OK) {
+            std::fprintf(stderr, "[msplat][E] CompactCloud: %s\n", msplat_last_error(ctx));
+            return false;
+        }
+        return AttachContexts();
+    }
+
     // Which splat each pixel shows (msplat_render_ids): per pixel of window = {x0, y0, w, h} (viewport pixels, row 0 = GL bottom; nullptr =
     // the whole viewport) the upload index of the splat of the latest Sort that contributes most to it, MSPLAT_ID_NONE where none
     // reaches; idDepth (may be nullptr) = that splat's window depth, 1.0 at MSPLAT_ID_NONE.  Both planes are w x h of the WINDOW, rows

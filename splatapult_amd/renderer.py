@@ -561,6 +561,32 @@ class SplatRenderer:
         crop = None if b.value == _capi.CROP_NONE else (names[b.value & ~_capi.CROP_INVERT], bool(b.value & _capi.CROP_INVERT))
         return dict(has_mask=bool(a.value), crop=crop, hidden=int(h.value))
 
+    def CompactCloud(self, index_map=False):
+        """Make the mask and the crop permanent, on the device (msplat_compact_cloud): the cloud becomes the K
+        splats SetVisibility's mask and SetCrop's volume let through, renumbered 0..K-1 in ascending old index, their records
+        copied bit for bit -- the renderer afterwards is one that was Init'ed with those rows.  Every frame in flight is finished
+        first; context 0 (it holds the mask SetVisibility set on every context) is compacted, the others are attached again and
+        the next Sort lands on context 0, as after Init.  The masks of all contexts are gone, the crop stays; Sort before the
+        next Render.  Returns K, or with index_map=True (K, map): a torch int32 tensor of the old N on this renderer's device,
+        map[i] = new index of splat i, -1 where it was dropped -- what the caller's per-splat arrays follow."""
+        if not self._ctxs:
+            raise _capi.MsplatError(_capi.ERR_NO_CLOUD, "CompactCloud: no cloud (Init first)")
+        self.synchronize()
+        own = self._ctxs[0]
+        m = None
+        if index_map:
+            import torch
+            m = torch.empty(max(self._n, 1), dtype=torch.int32, device=torch.device("cuda", self._device))
+            torch.cuda.current_stream(m.device).synchronize()
+        k = C.c_uint64()
+        _capi.check(own, self._lib.msplat_compact_cloud(own, C.c_void_p(m.data_ptr()) if m is not None else None, C.byref(k)))
+        n_old, self._n = self._n, int(k.value)
+        self._ctx = own
+        self._cur = self._depth - 1          # the next Sort lands on context 0, as after Init
+        if not self._attach_all():
+            raise _capi.MsplatError(_capi.ERR_HIP, "CompactCloud: attaching the compacted cloud failed: " + self._err)
+        return (self._n, m[:n_old]) if index_map else self._n
+
     # -- which splat each pixel shows (msplat_render_ids / msplat_mark_ids, INTEGRATION.md 20) -----------
     def RenderIds(self, cameraMat, projMat, viewport, nearFar, window=None, out=None, out_ptr=None, pitch_bytes=0, depth=False,
                   depth_ptr=None, depth_pitch_bytes=0):
