@@ -1,4 +1,4 @@
-// msplat_kernels.hip.h -- hand-written CDNA4 (gfx950, wave64) kernels of the splat hot path, in eleven parts.
+// msplat_kernels.hip.h -- hand-written CDNA4 (gfx950, wave64) kernels of the splat hot path, in twelve parts.
 //
 // Replaces (not ports) the reference's GL pipeline:
 //   shader/presort_compute.glsl + shader/multi_radixsort*.glsl  -> msplat_sort.hip.h      radix_* / ws_* (cull fused in pass 0)
@@ -9,6 +9,7 @@
 //   what each splat contributes (no reference part)             -> msplat_scores.hip.h    composite_scores_kernel, mark_scores_kernel
 //   GaussianCloud::ImportPly's per-vertex math, storage order   -> msplat_cloud.hip.h     ingest_kernel, morton / gather / cull boxes
 //   a mask or crop made permanent (no reference part)          -> msplat_compact.hip.h   compact_* (flags, count, offsets, index, gather)
+//   splats moved, rotated, scaled in the store (no ref. part)   -> msplat_transform.hip.h transform_kernel
 //   shader/point_*.glsl                                         -> msplat_points.hip.h
 //   two-pass frame with occlusion feedback (no reference part)  -> msplat_occlusion.hip.h
 //   shared constants, FrameParams, cull_key, box_live           -> msplat_common.hip.h
@@ -21,6 +22,7 @@
 #include "msplat_sort.hip.h"
 #include "msplat_cloud.hip.h"
 #include "msplat_compact.hip.h"
+#include "msplat_transform.hip.h"
 #include "msplat_project.hip.h"
 #include "msplat_binning.hip.h"
 #include "msplat_composite.hip.h"

@@ -795,3 +795,98 @@ void msplat_create_projection(float tanL, float tanR, float tanU, float tanD, fl
 }
 
 }  // extern "C"
+
+// ---- msplat_sh_rotation: how the SH coefficients of bands 1..3 follow a rotation of the splat (msplat_transform_cloud) ----
+namespace {
+
+// b[1..15] of splat_vert.glsl:51-105 at direction v, its signs and order: out[0..2] band 1, [3..7] band 2, [8..14] band 3
+void sh_basis(const double v[3], double out[15])
+{
+    const double x = v[0], y = v[1], z = v[2], x2 = x * x, y2 = y * y, z2 = z * z;
+    const double k1 = 0.4886025119029199, k2 = 1.0925484305920792, k3 = 0.31539156525252005, k4 = 0.5462742152960396;
+    const double k5 = 0.5900435899266435, k6 = 2.8906114426405543, k7 = 0.4570457994644658, k8 = 0.37317633259011546, k9 = 1.4453057213202771;
+    out[0] = -k1 * y;  out[1] = k1 * z;  out[2] = -k1 * x;
+    out[3] = k2 * y * x;  out[4] = -k2 * y * z;  out[5] = k3 * (3.0 * z2 - 1.0);  out[6] = -k2 * x * z;  out[7] = k4 * (x2 - y2);
+    out[8] = -k5 * y * (3.0 * x2 - y2);  out[9] = k6 * y * x * z;  out[10] = -k7 * y * (5.0 * z2 - 1.0);  out[11] = k8 * z * (5.0 * z2 - 3.0);
+    out[12] = -k7 * x * (5.0 * z2 - 1.0);  out[13] = k9 * z * (x2 - y2);  out[14] = -k5 * x * (x2 - 3.0 * y2);
+}
+
+constexpr int kShDirs = 64;      // sample directions of the fit: a Fibonacci spiral, 9 times the 7 unknowns of a row of band 3
+
+// The band's matrix from its defining identity b(Q^T v)^T = b(v)^T D over the sample directions, as the least-squares solution of
+// B D = B' (B[k][i] = b_i(v_k), B'[k][j] = b_j(Q^T v_k)): the normal equations (B^T B) D = B^T B', NB x NB, by Gauss-Jordan
+// elimination with partial pivoting.  B^T B is close to kShDirs / (4 pi) times the identity.  Row-major, rounded once to fp32; an
+// entry below 1e-12 -- the elimination's own rounding, where the exact entry is 0 -- is stored as 0, so that a quarter turn about
+// z gives the signed permutation it is.
+void sh_fit_band(const double (*b)[15], const double (*bq)[15], int first, int nb, float* out)
+{
+    double G[7][14];
+    for (int i = 0; i < nb; ++i)
+        for (int j = 0; j < nb; ++j) {
+            double g = 0.0, h = 0.0;
+            for (int k = 0; k < kShDirs; ++k) {
+                g += b[k][first + i] * b[k][first + j];
+                h += b[k][first + i] * bq[k][first + j];
+            }
+            G[i][j] = g;
+            G[i][nb + j] = h;
+        }
+    for (int c = 0; c < nb; ++c) {
+        int p = c;
+        for (int r = c + 1; r < nb; ++r)
+            if (std::fabs(G[r][c]) > std::fabs(G[p][c])) p = r;
+        for (int j = 0; j < 2 * nb; ++j) std::swap(G[c][j], G[p][j]);
+        const double inv = 1.0 / G[c][c];
+        for (int j = 0; j < 2 * nb; ++j) G[c][j] *= inv;
+        for (int r = 0; r < nb; ++r) {
+            if (r == c) continue;
+            const double t = G[r][c];
+            for (int j = 0; j < 2 * nb; ++j) G[r][j] -= t * G[c][j];
+        }
+    }
+    for (int i = 0; i < nb; ++i)
+        for (int j = 0; j < nb; ++j) {
+            const double d = G[i][nb + j];
+            out[i * nb + j] = std::fabs(d) < 1e-12 ? 0.0f : (float)d;
+        }
+}
+
+}  // namespace
+
+extern "C" int msplat_sh_rotation(const float M[16], float d1[9], float d2[25], float d3[49], float* scale_out)
+{
+    if (!M) return MSPLAT_ERR_INVALID_ARG;
+    double A[3][3];      // A[k][r] = M[4 k + r]: column k, row r
+    for (int k = 0; k < 3; ++k)
+        for (int r = 0; r < 3; ++r) {
+            if (!std::isfinite(M[4 * k + r]) || !std::isfinite(M[12 + r])) return MSPLAT_ERR_INVALID_ARG;
+            A[k][r] = M[4 * k + r];
+        }
+    const double det = A[0][0] * (A[1][1] * A[2][2] - A[2][1] * A[1][2]) - A[1][0] * (A[0][1] * A[2][2] - A[2][1] * A[0][2]) +
+                       A[2][0] * (A[0][1] * A[1][2] - A[1][1] * A[0][2]);
+    if (!(det > 0.0)) return MSPLAT_ERR_UNSUPPORTED;
+    const double s = std::cbrt(det);
+    if (!(s > 0.0) || !std::isfinite(s)) return MSPLAT_ERR_UNSUPPORTED;
+    double Q[3][3];
+    for (int k = 0; k < 3; ++k)
+        for (int r = 0; r < 3; ++r) Q[k][r] = A[k][r] / s;
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {      // (Q^T Q)(i, j) = column i . column j
+            const double g = Q[i][0] * Q[j][0] + Q[i][1] * Q[j][1] + Q[i][2] * Q[j][2];
+            if (!(std::fabs(g - (i == j ? 1.0 : 0.0)) <= 1e-4)) return MSPLAT_ERR_UNSUPPORTED;
+        }
+    double b[kShDirs][15], bq[kShDirs][15];
+    for (int k = 0; k < kShDirs; ++k) {
+        const double z = 1.0 - (2.0 * k + 1.0) / kShDirs, rad = std::sqrt(1.0 - z * z), phi = k * 2.399963229728653;      // pi (3 - sqrt 5)
+        const double v[3] = {rad * std::cos(phi), rad * std::sin(phi), z};
+        double w[3];      // Q^T v
+        for (int i = 0; i < 3; ++i) w[i] = Q[i][0] * v[0] + Q[i][1] * v[1] + Q[i][2] * v[2];
+        sh_basis(v, b[k]);
+        sh_basis(w, bq[k]);
+    }
+    if (d1) sh_fit_band(b, bq, 0, 3, d1);
+    if (d2) sh_fit_band(b, bq, 3, 5, d2);
+    if (d3) sh_fit_band(b, bq, 8, 7, d3);
+    if (scale_out) *scale_out = (float)s;
+    return MSPLAT_OK;
+}

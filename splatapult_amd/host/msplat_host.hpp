@@ -364,6 +364,31 @@ public:
         return AttachContexts();
     }
 
+    // Moves, rotates and scales splats on the device (msplat_transform_cloud): every splat i with d_select[i] != 0 (n bytes of device
+    // memory; nullptr: every splat) gets centre M x, covariance A S A^T and, unless keepSH, SH bands 1..3 rotated by msplat_sh_rotation(M);
+    // the others are copied bit for bit.  Without keepSH M must be a rotation times a uniform positive scale.  Every frame in flight is
+    // finished first; context 0 is transformed and keeps its mask (the numbering does not change), the others are attached again, which
+    // drops THEIR masks: with frames in flight call SetVisibility[Device] again afterwards.  The crop stays; Sort before the next Render.
+    template <class Mat4>
+    bool TransformCloud(const Mat4& M, const uint8_t* d_select = nullptr, bool keepSH = false)
+    {
+        static_assert(sizeof(Mat4) == 64, "glm-compatible layout expected");
+        if (group || ctxs.empty()) {
+            std::fprintf(stderr, "[msplat][E] TransformCloud: %s\n", group ? "a device group has no cloud editing" : "no cloud (Init first)");
+            return false;
+        }
+        Synchronize();
+        ctx = ctxs[0];
+        cur = (int)ctxs.size() - 1;           // the next Sort lands on context 0
+        msplat_stats st;
+        if (msplat_get_stats(ctx, &st) != MSPLAT_OK ||
+            msplat_transform_cloud(ctx, F(M), d_select, st.num_splats, keepSH ? MSPLAT_TRANSFORM_KEEP_SH : 0) != MSPLAT_OK) {
+            std::fprintf(stderr, "[msplat][E] TransformCloud: %s\n", msplat_last_error(ctx));
+            return false;
+        }
+        return AttachContexts();
+    }
+
     // Which splat each pixel shows (msplat_render_ids): per pixel of window = {x0, y0, w, h} (viewport pixels, row 0 = GL bottom; nullptr =
     // the whole viewport) the upload index of the splat of the latest Sort that contributes most to it, MSPLAT_ID_NONE where none
     // reaches; idDepth (may be nullptr) = that splat's window depth, 1.0 at MSPLAT_ID_NONE.  Both planes are w x h of the WINDOW, rows

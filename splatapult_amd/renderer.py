@@ -508,6 +508,8 @@ class SplatRenderer:
         data_ptr() that lives on the device -- a torch bool / uint8 tensor on this renderer's device, read asynchronously on each
         context's stream: keep it alive and unchanged until synchronize() -- or None for no mask.  Set on every context of the
         frames-in-flight rotation; a Render shows it after the next Sort.  An upload (Init*, Update*) drops the mask.
+        The argument is remembered: TransformCloud keeps the mask and hands it to the contexts it attaches again, so a
+        device-tensor mask must still hold the mask at that point.
         ValueError for a wrong length or dtype, before the library is called."""
         if mask is None:
             args, fn = (None, 0), self._lib.msplat_set_visibility
@@ -537,6 +539,7 @@ class SplatRenderer:
             raise _capi.MsplatError(_capi.ERR_NO_CLOUD, "SetVisibility: no cloud (Init first)")
         for h in self._ctxs:
             _capi.check(h, fn(h, *args))
+        self._vis_arg = mask                 # (TransformCloud hands it to the contexts it attaches again)
 
     def SetCrop(self, worldToCrop=None, shape="box", invert=False):
         """Crop volume for the following Sorts, on every context: worldToCrop = 16 floats, column-major, world -> crop space (affine),
@@ -586,6 +589,59 @@ class SplatRenderer:
         if not self._attach_all():
             raise _capi.MsplatError(_capi.ERR_HIP, "CompactCloud: attaching the compacted cloud failed: " + self._err)
         return (self._n, m[:n_old]) if index_map else self._n
+
+    def TransformCloud(self, M, select=None, keep_sh=False):
+        """Move, rotate and scale splats on the device (msplat_transform_cloud): every splat i with select[i]
+        (None: every splat) gets centre M x, covariance A S A^T (A = M's upper 3x3) and, unless keep_sh, SH bands 1..3 rotated by
+        msplat_sh_rotation(M); the others are copied bit for bit.  M: 16 floats, column-major; without keep_sh it must be a rotation
+        times a uniform positive scale (MsplatError ERR_UNSUPPORTED else).  select: N values, numpy bool / uint8 (staged to the
+        device through torch) or a torch bool / uint8 tensor on this renderer's device -- SetVisibility's checks, ValueError before
+        the library is called.  The renderer afterwards is one that was Init'ed with those rows, except that the numbering, and
+        with it the mask, stays: every frame in flight is finished first; context 0 is transformed, the others are attached again
+        (attaching drops their masks) and are handed SetVisibility's last argument again -- a device-tensor mask must still hold
+        the mask at that point.  The crop stays; Sort before the next Render."""
+        if not self._ctxs:
+            raise _capi.MsplatError(_capi.ERR_NO_CLOUD, "TransformCloud: no cloud (Init first)")
+        m = np.ascontiguousarray(_FrameArgs._flat(M, 16))
+        sel = None
+        if select is not None:
+            if not hasattr(select, "data_ptr"):
+                if not isinstance(select, np.ndarray) or select.dtype not in (np.bool_, np.uint8):
+                    raise ValueError("select must be a numpy bool / uint8 array, a device tensor or None, not %s %s"
+                                     % (type(select).__name__, getattr(select, "dtype", "")))
+                if select.shape != (self._n,):
+                    raise ValueError("select must have shape (%d,), one value per splat, not %s" % (self._n, select.shape))
+                import torch
+                select = torch.from_numpy(np.ascontiguousarray(select).view(np.uint8)).to(torch.device("cuda", self._device))
+            if str(select.dtype).split(".")[-1] not in ("bool", "uint8"):
+                raise ValueError("select must be bool or uint8, not %s" % select.dtype)
+            if tuple(int(s) for s in select.shape) != (self._n,):
+                raise ValueError("select must have shape (%d,), one value per splat, not %s" % (self._n, tuple(select.shape)))
+            if not select.is_contiguous():
+                raise ValueError("select must be contiguous (pass select.contiguous())")
+            if getattr(select.device, "type", "cuda") not in ("cuda", "hip"):
+                raise ValueError("a select with data_ptr() must live in device memory, not on %s (pass select.numpy())" % select.device)
+            import sys
+            torch = sys.modules.get("torch")
+            if torch is not None and isinstance(select, torch.Tensor):
+                torch.cuda.current_stream(select.device).synchronize()     # what produced the tensor has completed
+            sel = C.c_void_p(int(select.data_ptr())) if self._n else None
+        self.synchronize()
+        own = self._ctxs[0]
+        masked = C.c_int32()
+        _capi.check(own, self._lib.msplat_get_visibility(own, C.byref(masked), None, None))
+        _capi.check(own, self._lib.msplat_transform_cloud(own, m.ctypes.data_as(C.POINTER(C.c_float)), sel, self._n,
+                                                          _capi.TRANSFORM_KEEP_SH if keep_sh else 0))
+        self._ctx = own
+        self._cur = self._depth - 1          # the next Sort lands on context 0, as after Init
+        if not self._attach_all():
+            raise _capi.MsplatError(_capi.ERR_HIP, "TransformCloud: attaching the transformed cloud failed: " + self._err)
+        if masked.value and len(self._ctxs) > 1 and getattr(self, "_vis_arg", None) is not None:
+            ctxs, self._ctxs = self._ctxs, self._ctxs[1:]
+            try:
+                self.SetVisibility(self._vis_arg)
+            finally:
+                self._ctxs = ctxs
 
     # -- which splat each pixel shows (msplat_render_ids / msplat_mark_ids, INTEGRATION.md 20) -----------
     def RenderIds(self, cameraMat, projMat, viewport, nearFar, window=None, out=None, out_ptr=None, pitch_bytes=0, depth=False,
