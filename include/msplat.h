@@ -131,7 +131,7 @@ enum { MSPLAT_CROP_NONE = 0, MSPLAT_CROP_BOX = 1, MSPLAT_CROP_SPHERE = 2, MSPLAT
 int msplat_set_visibility(msplat_ctx* ctx, const uint8_t* visible, uint64_t n);             /* host memory; copied before return (waits at most for the PREVIOUS mask's copy) */
 int msplat_set_visibility_device(msplat_ctx* ctx, const uint8_t* d_visible, uint64_t n);    /* device memory of the context's device; asynchronous on the context's stream, never waits: the source stays valid until that work has run (msplat_synchronize / msplat_stream_wait) */
 int msplat_set_crop(msplat_ctx* ctx, const float worldToCrop[16], int32_t shape);           /* NULL or MSPLAT_CROP_NONE: no crop */
-int msplat_get_visibility(msplat_ctx* ctx, int32_t* has_mask, int32_t* crop_shape, uint64_t* hidden);   /* hidden: splats the latest Sort's plane hides (synchronises); any out pointer may be NULL */ /* ---- msplat_compact_cloud (INTEGRATION.md 22) makes the mask and the crop permanent, on the device: it keeps splat i (upload numbering) iff mask(i) && crop(i), the rule above as the context's NEXT Sort would apply it (a NaN centre: kept by a mask alone, dropped by a crop, kept by an inverted crop), and renumbers the K kept splats 0..K-1 in ascending old upload index.  d_index_map (NULL: none; else N uint32 of device memory of the context's device, 4-byte aligned, checked as msplat_mark_ids checks its pointers): d_index_map[i] = new upload index of splat i, the exclusive prefix sum of the keep flags, or MSPLAT_ID_NONE where it was dropped.  n_kept_out (host, may be NULL) receives K.  pos4 and the stored records are copied bit for bit -- nothing is unpacked, re-rounded or re-quantised -- and the store keeps the storage kind and full_sh it had (msplat_set_cloud_storage still speaks of the next upload): msplat_download_cloud afterwards = the kept rows of msplat_download_cloud before, bit for bit, in every storage.  The context afterwards is what msplat_upload_cloud of the kept source rows, same storage and spatial_order, leaves: records, storage order (the spatial reorder runs on the compacted cloud: under AUTO it may enter or leave Morton storage where K crosses 2^18), cull boxes, the keys, indices and frames of every later Sort / Render, bit for bit; K == 0 is an upload of n = 0, K == N has the same postconditions and an identity map.  The mask is dropped (the numbering is new), the crop kept and evaluated on the new cloud at the next Sort; a render before that Sort returns MSPLAT_ERR_NO_SORT.  Synchronous like the uploads: drains async_submit work and the stream, returns after the stream has drained.  Never in place: the kept records are gathered into a fresh store (peak = old + new store, + the reorder's second copy of the new one); if that allocation fails: MSPLAT_ERR_HIP and the context renders what it rendered before; a failure after the swap leaves no cloud, as a failed upload does.  A store shared with attached contexts is not modified: this context gets a store of its own, the others render the old cloud until msplat_attach_cloud is called again.  Refused before anything is launched -- _INVALID_ARG: NULL ctx, a bad d_index_map; _NO_CLOUD; _UNSUPPORTED (the context stays usable): a point cloud.  Out of scope: the device group, a mask other than the context's own, a device-memory download of the records. */ int msplat_compact_cloud(msplat_ctx* ctx, uint32_t* d_index_map, uint64_t* n_kept_out); /* ---- msplat_transform_cloud (INTEGRATION.md 23) moves, rotates and scales splats on the device: every splat i (upload numbering) with d_select == NULL or d_select[i] != 0 (n bytes of device memory of the context's device, checked as msplat_mark_ids checks its pointers; n must be the cloud's N) is transformed by M (column-major; A[k][r] = M[4k + r] its upper 3x3; row 3 is not read), the others are copied.  The record is decoded to its FP32 floats (SH_FP16 / SH_Q8: the values msplat_download_cloud returns); then, every operation rounded to fp32, left to right, no fused multiply-add:  centre x' = ((M[0] x + M[4] y) + M[8] z) + M[12], y' and z' likewise (the crop's form);  covariance S[c][r] (column c, row r): T[c][r] = (A[0][r] S[c][0] + A[1][r] S[c][1]) + A[2][r] S[c][2], S'[c][r] = (T[0][r] A[0][c] + T[1][r] A[1][c]) + T[2][r] A[2][c] -- A S A^T, all nine entries, nothing symmetrised; a scale arrives through A, alpha is untouched;  SH, per channel, unless MSPLAT_TRANSFORM_KEEP_SH: band 1 = coefficients 1..3, band 2 = 4..8, band 3 = 9..15 (bands 2 and 3: full-SH clouds), sh'[k] = (..(D[k][0] sh[0] + D[k][1] sh[1]) + ..) + D[k][last] sh[last] over the band, D exactly what msplat_sh_rotation(M) returns; the DC term is untouched;  the footprint bound is recomputed from S'.  A transformed record is encoded again in the store's own kind (SH_Q8 is quantised again); an unselected splat's position and stored record are copied bit for bit, nothing unpacked: msplat_download_cloud afterwards = msplat_download_cloud before on those rows, bit for bit, in every storage.  An identity M is not a bit-for-bit no-op for -0 and inf (-0 + 0 = +0, 0 * inf = NaN).  The context afterwards is what msplat_upload_cloud of those rows, same storage, full_sh and spatial_order, leaves -- records, storage order (the spatial reorder runs on the moved cloud), cull boxes, the keys, indices and frames of every later Sort / Render, bit for bit -- except that the numbering has not changed, so the MASK IS KEPT; the crop is kept too and evaluated on the new centres at the next Sort; a render before that Sort returns MSPLAT_ERR_NO_SORT.  Never in place: the rows go into a fresh store (peak = old + new store, + the reorder's second copy); a store shared with attached contexts is not modified: this context gets a store of its own, the others render the old cloud until msplat_attach_cloud is called again.  Synchronous like the uploads: drains async_submit work and the stream.  Refused before anything is launched -- _UNSUPPORTED: M is not a rotation times a uniform positive scale (msplat_sh_rotation's gate) and KEEP_SH is not set, whatever the cloud's SH hold; with KEEP_SH any M with finite rows 0-2 is taken (shear, mirror, non-uniform scale) and the SH stay as they are; a point cloud (the context stays usable); _INVALID_ARG: NULL ctx, NULL M, a non-finite M (rows 0-2), unknown flag bits, a bad d_select, n != N; _NO_CLOUD.  After the kernel has run -- MSPLAT_ERR_HIP: the new store could not be allocated; _UNSUPPORTED: a transformed f_rest value is beyond SH_FP16's range (|c| >= 65520) or not finite under SH_Q8 -- the context renders what it rendered before; a failure after the swap leaves no cloud, as a failed upload does.  Out of scope: the device group, host-memory selections, mirrored SH (improper rotations), a per-splat matrix, merging two clouds. */ enum { MSPLAT_TRANSFORM_KEEP_SH = 1 }; int msplat_transform_cloud(msplat_ctx* ctx, const float M[16], const uint8_t* d_select, uint64_t n, int32_t flags);
+int msplat_get_visibility(msplat_ctx* ctx, int32_t* has_mask, int32_t* crop_shape, uint64_t* hidden);   /* hidden: splats the latest Sort's plane hides (synchronises); any out pointer may be NULL */ /* ---- msplat_compact_cloud (INTEGRATION.md 22) makes the mask and the crop permanent, on the device: it keeps splat i (upload numbering) iff mask(i) && crop(i), the rule above as the context's NEXT Sort would apply it (a NaN centre: kept by a mask alone, dropped by a crop, kept by an inverted crop), and renumbers the K kept splats 0..K-1 in ascending old upload index.  d_index_map (NULL: none; else N uint32 of device memory of the context's device, 4-byte aligned, checked as msplat_mark_ids checks its pointers): d_index_map[i] = new upload index of splat i, the exclusive prefix sum of the keep flags, or MSPLAT_ID_NONE where it was dropped.  n_kept_out (host, may be NULL) receives K.  pos4 and the stored records are copied bit for bit -- nothing is unpacked, re-rounded or re-quantised -- and the store keeps the storage kind and full_sh it had (msplat_set_cloud_storage still speaks of the next upload): msplat_download_cloud afterwards = the kept rows of msplat_download_cloud before, bit for bit, in every storage.  The context afterwards is what msplat_upload_cloud of the kept source rows, same storage and spatial_order, leaves: records, storage order (the spatial reorder runs on the compacted cloud: under AUTO it may enter or leave Morton storage where K crosses 2^18), cull boxes, the keys, indices and frames of every later Sort / Render, bit for bit; K == 0 is an upload of n = 0, K == N has the same postconditions and an identity map.  The mask is dropped (the numbering is new), the crop kept and evaluated on the new cloud at the next Sort; a render before that Sort returns MSPLAT_ERR_NO_SORT.  Synchronous like the uploads: drains async_submit work and the stream, returns after the stream has drained.  Never in place: the kept records are gathered into a fresh store (peak = old + new store, + the reorder's second copy of the new one); if that allocation fails: MSPLAT_ERR_HIP and the context renders what it rendered before; a failure after the swap leaves no cloud, as a failed upload does.  A store shared with attached contexts is not modified: this context gets a store of its own, the others render the old cloud until msplat_attach_cloud is called again.  Refused before anything is launched -- _INVALID_ARG: NULL ctx, a bad d_index_map; _NO_CLOUD; _UNSUPPORTED (the context stays usable): a point cloud.  Out of scope: the device group, a mask other than the context's own, a device-memory download of the records. */ int msplat_compact_cloud(msplat_ctx* ctx, uint32_t* d_index_map, uint64_t* n_kept_out); /* ---- msplat_transform_cloud (INTEGRATION.md 23) moves, rotates and scales splats on the device: every splat i (upload numbering) with d_select == NULL or d_select[i] != 0 (n bytes of device memory of the context's device, checked as msplat_mark_ids checks its pointers; n must be the cloud's N) is transformed by M (column-major; A[k][r] = M[4k + r] its upper 3x3; row 3 is not read), the others are copied.  The record is decoded to its FP32 floats (SH_FP16 / SH_Q8: the values msplat_download_cloud returns); then, every operation rounded to fp32, left to right, no fused multiply-add:  centre x' = ((M[0] x + M[4] y) + M[8] z) + M[12], y' and z' likewise (the crop's form);  covariance S[c][r] (column c, row r): T[c][r] = (A[0][r] S[c][0] + A[1][r] S[c][1]) + A[2][r] S[c][2], S'[c][r] = (T[0][r] A[0][c] + T[1][r] A[1][c]) + T[2][r] A[2][c] -- A S A^T, all nine entries, nothing symmetrised; a scale arrives through A, alpha is untouched;  SH, per channel, unless MSPLAT_TRANSFORM_KEEP_SH: band 1 = coefficients 1..3, band 2 = 4..8, band 3 = 9..15 (bands 2 and 3: full-SH clouds), sh'[k] = (..(D[k][0] sh[0] + D[k][1] sh[1]) + ..) + D[k][last] sh[last] over the band, D exactly what msplat_sh_rotation(M) returns; the DC term is untouched;  the footprint bound is recomputed from S'.  A transformed record is encoded again in the store's own kind (SH_Q8 is quantised again); an unselected splat's position and stored record are copied bit for bit, nothing unpacked: msplat_download_cloud afterwards = msplat_download_cloud before on those rows, bit for bit, in every storage.  An identity M is not a bit-for-bit no-op for -0 and inf (-0 + 0 = +0, 0 * inf = NaN).  The context afterwards is what msplat_upload_cloud of those rows, same storage, full_sh and spatial_order, leaves -- records, storage order (the spatial reorder runs on the moved cloud), cull boxes, the keys, indices and frames of every later Sort / Render, bit for bit -- except that the numbering has not changed, so the MASK IS KEPT; the crop is kept too and evaluated on the new centres at the next Sort; a render before that Sort returns MSPLAT_ERR_NO_SORT.  Never in place: the rows go into a fresh store (peak = old + new store, + the reorder's second copy); a store shared with attached contexts is not modified: this context gets a store of its own, the others render the old cloud until msplat_attach_cloud is called again.  Synchronous like the uploads: drains async_submit work and the stream.  Refused before anything is launched -- _UNSUPPORTED: M is not a rotation times a uniform positive scale (msplat_sh_rotation's gate) and KEEP_SH is not set, whatever the cloud's SH hold; with KEEP_SH any M with finite rows 0-2 is taken (shear, mirror, non-uniform scale) and the SH stay as they are; a point cloud (the context stays usable); _INVALID_ARG: NULL ctx, NULL M, a non-finite M (rows 0-2), unknown flag bits, a bad d_select, n != N; _NO_CLOUD.  After the kernel has run -- MSPLAT_ERR_HIP: the new store could not be allocated; _UNSUPPORTED: a transformed f_rest value is beyond SH_FP16's range (|c| >= 65520) or not finite under SH_Q8 -- the context renders what it rendered before; a failure after the swap leaves no cloud, as a failed upload does.  Out of scope: the device group, host-memory selections, mirrored SH (improper rotations), a per-splat matrix, merging two clouds. */ enum { MSPLAT_TRANSFORM_KEEP_SH = 1 }; int msplat_transform_cloud(msplat_ctx* ctx, const float M[16], const uint8_t* d_select, uint64_t n, int32_t flags); /* ---- msplat_append_cloud (INTEGRATION.md 24) puts splats INTO a cloud, on the device: ctx holds a splat cloud of N splats, src one of Ns (either may be 0); splat i of src (upload numbering) is appended iff d_select == NULL or d_select[i] != 0 (n bytes of device memory of the context's device, checked as msplat_mark_ids checks its pointers; n must be Ns).  The K selected splats follow ctx's own in ascending source index: they get upload indices N .. N+K-1, the splats ctx had keep 0 .. N-1; src is only read.  d_index_map (NULL: none; else Ns uint32 of device memory, 4-byte aligned, checked as msplat_compact_cloud checks its map): d_index_map[i] = N + the exclusive prefix sum of the select flags, or MSPLAT_ID_NONE where splat i was not selected; written only by a call that succeeds.  n_added_out (host, may be NULL) receives K.  The store keeps ctx's storage kind and full_sh (msplat_set_cloud_storage still speaks of the next upload); src's full_sh must be ctx's.  ctx's own N positions and stored records are copied bit for bit, nothing unpacked; so are the appended rows, pos4 and record, of a source of the SAME storage kind -- an SH_Q8 object pasted into an SH_Q8 scene is not quantised a second time.  Appended rows of a source of ANOTHER kind are decoded to their FP32 record floats (the values msplat_download_cloud(src) returns) and encoded by the destination kind's pack routine exactly as an upload of those floats encodes them; their pos4 -- centre and footprint bound -- is copied: the bound depends on covariance and alpha only, and centre, alpha and covariance are fp32 in every storage kind (the 16-float head of an SH_FP16 / SH_Q8 record is bit for bit the FP32 values).  The context afterwards is what msplat_upload_cloud of those N+K rows, same storage, full_sh and spatial_order, leaves -- records, storage order (the spatial reorder runs on the merged cloud: under AUTO it may enter Morton storage where N+K reaches 2^18), cull boxes, the keys, indices and frames of every later Sort / Render, bit for bit -- except that the old numbering has not changed, so the MASK IS KEPT and extended by K visible bytes; the crop is kept too and evaluated on all N+K centres at the next Sort; a render before that Sort returns MSPLAT_ERR_NO_SORT.  Never in place: all rows go into a fresh store (peak = both old stores + the new one, + the reorder's second copy); a store shared with attached contexts is not modified: this context gets a store of its own, the others render the old cloud until msplat_attach_cloud is called again.  src == ctx is allowed and duplicates the selection; src may be an attached context; K == 0 has the same postconditions as any other K; an empty destination (an upload of n = 0) extracts the selection into a cloud of its own.  Synchronous like the uploads: drains the async_submit work and the streams of both contexts; the kernels run on ctx's stream.  Refused before anything is launched -- _INVALID_ARG: NULL ctx or src, contexts on different devices, n != Ns, a bad d_select or d_index_map; _NO_CLOUD: either context has none; _UNSUPPORTED (the contexts stay usable): a point cloud in either, different full_sh.  After the count, with nothing allocated and the context unchanged -- _UNSUPPORTED: N + K > 2^24.  After the kernels have run -- MSPLAT_ERR_HIP: the new store could not be allocated; _UNSUPPORTED: a converted f_rest value is beyond SH_FP16's range (|c| >= 65520) or not finite under SH_Q8 -- the context renders what it rendered before; a failure after the swap leaves no cloud, as a failed upload does.  Out of scope: the device group, host-memory selections, a matrix applied on the way (msplat_transform_cloud before or after, with the index map), SH degree conversion, a device-memory download. */ int msplat_append_cloud(msplat_ctx* ctx, msplat_ctx* src, const uint8_t* d_select, uint64_t n, uint32_t* d_index_map, uint64_t* n_added_out);
 /* ---- SplatRenderer::Render (splatrenderer.cpp:315-343) plus the GL pipeline behind its glDrawElements: splat_vert / _geom / _frag.glsl and
  * the blend / clear state of app.cpp:144-164.  Writes W x H RGBA (float, half or 4 bytes), row 0 = GL bottom row, alpha = 1 (msplat_set_target_mode: or
  * over the target's contents).  out_is_device != 0: `rgba` is device memory, the call is asynchronous on the stream; else host memory, the

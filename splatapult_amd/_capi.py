@@ -183,6 +183,7 @@ SYMBOLS = [
     ("msplat_get_visibility", C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]),
     ("msplat_compact_cloud", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
     ("msplat_transform_cloud", C.c_int, [C.c_void_p, _F16, C.c_void_p, C.c_uint64, C.c_int32]),
+    ("msplat_append_cloud", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64)]),
     ("msplat_sh_rotation", C.c_int, [_F16, _F16, _F16, _F16, _F16]),
     ("msplat_debug_get_cull_boxes", C.c_int, [C.c_void_p, _U32P, _U32P, C.POINTER(C.c_int)]),
     ("msplat_get_stats", C.c_int, [C.c_void_p, C.POINTER(Stats)]),

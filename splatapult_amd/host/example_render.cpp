@@ -3,7 +3,7 @@
 // Sort + Render into an explicit RGBA32F framebuffer, dumped as a binary PPM-like float file.
 //
 //   g++ -std=c++17 -I. splatapult_amd/host/example_render.cpp -Lsplatapult_amd/lib -lmsplat -o example_render
-//   ./example_render scene.ply out.f32 [width height] [--nosh] [--frames-in-flight N] [--devices 0,1,2,...] [--over-gradient] [--depth out_depth.f32] [--srgb8 out.png] [--crop-sphere cx cy cz r] [--pick X,Y] [--min-score S] [--compact]
+//   ./example_render scene.ply out.f32 [width height] [--nosh] [--frames-in-flight N] [--devices 0,1,2,...] [--over-gradient] [--depth out_depth.f32] [--srgb8 out.png] [--crop-sphere cx cy cz r] [--pick X,Y] [--min-score S] [--compact] [--append OTHER.ply]
 // With --frames-in-flight N the same frame is issued N + 1 times round-robin over N contexts that share the cloud
 // (SplatRenderer::SetFramesInFlight); the last one is written.  With --devices the frame's bin rows are dealt to the
 // listed GPUs (SplatRenderer::ConfigureDevices, msplat_group_*): same pixels.  With --over-gradient the target is first filled with
@@ -23,6 +23,9 @@
 // With --compact, after --min-score / --crop-sphere, the hidden splats are dropped for good (SplatRenderer::CompactCloud,
 // msplat_compact_cloud: the kept records gathered into a new store on the device), the splat counts before and after are printed and
 // the frame is sorted and rendered once more from the smaller cloud: the same pixels.  One device only.
+// With --append OTHER.ply a second renderer uploads that file and its splats are appended to the scene's before the frame
+// (SplatRenderer::AppendCloud, msplat_append_cloud: both stores' records gathered into a new one on the device); the counts are
+// printed.  OTHER.ply is read with the scene's SH degree.  One device only.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -66,6 +69,7 @@ int main(int argc, char** argv)
     double minScore = -1.0;          // --min-score: hide the splats that contribute less than this many pixels, render again
     const char* depthPath = nullptr;
     const char* srgb8Path = nullptr;
+    const char* appendPath = nullptr;
     std::vector<int> devices;
     float cropSphere[4] = {0.0f, 0.0f, 0.0f, 0.0f};       // centre, radius; radius 0: no crop
     for (int i = 3; i < argc; ++i) {
@@ -78,6 +82,7 @@ int main(int argc, char** argv)
         if (!std::strcmp(argv[i], "--depth") && i + 1 < argc) depthPath = argv[i + 1];
         if (!std::strcmp(argv[i], "--pick") && i + 1 < argc && std::sscanf(argv[i + 1], "%d,%d", &pickX, &pickY) != 2) pickX = pickY = -1;
         if (!std::strcmp(argv[i], "--srgb8") && i + 1 < argc) srgb8Path = argv[i + 1];
+        if (!std::strcmp(argv[i], "--append") && i + 1 < argc) appendPath = argv[i + 1];
         if (!std::strcmp(argv[i], "--min-score") && i + 1 < argc) minScore = std::atof(argv[i + 1]);
         if (!std::strcmp(argv[i], "--devices") && i + 1 < argc)
             for (const char* p = argv[i + 1]; *p;) {
@@ -95,6 +100,15 @@ int main(int argc, char** argv)
     if (srgb8Path) renderer.Configure(/*device*/0, MSPLAT_FB_SRGB8_ALPHA8);
     if (devices.size() > 1) renderer.ConfigureDevices(devices, MSPLAT_BANDS_BLOCK_INTERLEAVED, 2);
     if (!renderer.Init(cloud, /*isFramebufferSRGBEnabled=*/false, /*useRgcSortOverride=*/false)) return 1;
+
+    if (appendPath && devices.size() <= 1) {
+        auto other = std::make_shared<GaussianCloud>(GaussianCloud::Options{!nosh, false});
+        if (!other->ImportPly(appendPath)) return 1;
+        SplatRenderer second;
+        uint64_t added = 0;
+        if (!second.Init(other, false, false) || !renderer.AppendCloud(second, nullptr, nullptr, &added)) return 1;
+        std::printf("appended: %zu + %llu of %zu splats\n", cloud->GetNumGaussians(), (unsigned long long)added, other->GetNumGaussians());
+    }
 
     if (cropSphere[3] > 0.0f) {
         // world -> crop space: the sphere becomes the unit sphere, q = (p - c) / r

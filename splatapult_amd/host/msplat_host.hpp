@@ -389,6 +389,36 @@ public:
         return AttachContexts();
     }
 
+    // Puts splats into the cloud on the device (msplat_append_cloud): every splat i of src's cloud (another renderer on this device,
+    // or this one: a duplicate) with d_select[i] != 0 (one byte per splat of src in device memory; nullptr: every splat) is appended
+    // behind this renderer's own in ascending source index; the old splats keep their indices, the K new ones get N..N+K-1.  Rows are
+    // copied bit for bit where both clouds are stored alike and converted through their FP32 values where not.  d_index_map (may be
+    // nullptr): src's Ns uint32 of device memory, [i] = new index of source splat i or MSPLAT_ID_NONE; *added (may be nullptr) = K.
+    // Every frame in flight of both renderers is finished first; context 0 appends and keeps its mask, K visible bytes longer, the
+    // others are attached again, which drops THEIR masks: with frames in flight call SetVisibility[Device] again afterwards.  The crop
+    // stays; Sort before the next Render.
+    bool AppendCloud(SplatRenderer& src, const uint8_t* d_select = nullptr, uint32_t* d_index_map = nullptr, uint64_t* added = nullptr)
+    {
+        if (group || src.group || ctxs.empty() || src.ctxs.empty()) {
+            std::fprintf(stderr, "[msplat][E] AppendCloud: %s\n", group || src.group ? "a device group has no cloud editing" : "no cloud (Init first)");
+            return false;
+        }
+        Synchronize();
+        if (&src != this) src.Synchronize();
+        ctx = ctxs[0];
+        cur = (int)ctxs.size() - 1;           // the next Sort lands on context 0
+        msplat_stats st;
+        if (msplat_get_stats(src.ctxs[0], &st) != MSPLAT_OK) {
+            std::fprintf(stderr, "[msplat][E] AppendCloud: %s\n", msplat_last_error(src.ctxs[0]));
+            return false;
+        }
+        if (msplat_append_cloud(ctx, src.ctxs[0], d_select, st.num_splats, d_index_map, added) != MSPLAT_OK) {
+            std::fprintf(stderr, "[msplat][E] AppendCloud: %s\n", msplat_last_error(ctx));
+            return false;
+        }
+        return AttachContexts();
+    }
+
     // Which splat each pixel shows (msplat_render_ids): per pixel of window = {x0, y0, w, h} (viewport pixels, row 0 = GL bottom; nullptr =
     // the whole viewport) the upload index of the splat of the latest Sort that contributes most to it, MSPLAT_ID_NONE where none
     // reaches; idDepth (may be nullptr) = that splat's window depth, 1.0 at MSPLAT_ID_NONE.  Both planes are w x h of the WINDOW, rows

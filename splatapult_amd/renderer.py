@@ -590,6 +590,36 @@ class SplatRenderer:
             raise _capi.MsplatError(_capi.ERR_HIP, "CompactCloud: attaching the compacted cloud failed: " + self._err)
         return (self._n, m[:n_old]) if index_map else self._n
 
+    def _device_select(self, select, n):
+        """a select argument (None, numpy bool / uint8 -- staged to the device through torch -- or a torch bool / uint8 tensor on
+        this renderer's device) of n values as the c_void_p the library takes (None: every splat, or n == 0); SetVisibility's
+        checks, ValueError before the library is called.  The tensor is kept alive in self._select_arg until the next call."""
+        self._select_arg = None
+        if select is None:
+            return None
+        if not hasattr(select, "data_ptr"):
+            if not isinstance(select, np.ndarray) or select.dtype not in (np.bool_, np.uint8):
+                raise ValueError("select must be a numpy bool / uint8 array, a device tensor or None, not %s %s"
+                                 % (type(select).__name__, getattr(select, "dtype", "")))
+            if select.shape != (n,):
+                raise ValueError("select must have shape (%d,), one value per splat, not %s" % (n, select.shape))
+            import torch
+            select = torch.from_numpy(np.ascontiguousarray(select).view(np.uint8)).to(torch.device("cuda", self._device))
+        if str(select.dtype).split(".")[-1] not in ("bool", "uint8"):
+            raise ValueError("select must be bool or uint8, not %s" % select.dtype)
+        if tuple(int(s) for s in select.shape) != (n,):
+            raise ValueError("select must have shape (%d,), one value per splat, not %s" % (n, tuple(select.shape)))
+        if not select.is_contiguous():
+            raise ValueError("select must be contiguous (pass select.contiguous())")
+        if getattr(select.device, "type", "cuda") not in ("cuda", "hip"):
+            raise ValueError("a select with data_ptr() must live in device memory, not on %s (pass select.numpy())" % select.device)
+        import sys
+        torch = sys.modules.get("torch")
+        if torch is not None and isinstance(select, torch.Tensor):
+            torch.cuda.current_stream(select.device).synchronize()     # what produced the tensor has completed
+        self._select_arg = select
+        return C.c_void_p(int(select.data_ptr())) if n else None
+
     def TransformCloud(self, M, select=None, keep_sh=False):
         """Move, rotate and scale splats on the device (msplat_transform_cloud): every splat i with select[i]
         (None: every splat) gets centre M x, covariance A S A^T (A = M's upper 3x3) and, unless keep_sh, SH bands 1..3 rotated by
@@ -603,29 +633,7 @@ class SplatRenderer:
         if not self._ctxs:
             raise _capi.MsplatError(_capi.ERR_NO_CLOUD, "TransformCloud: no cloud (Init first)")
         m = np.ascontiguousarray(_FrameArgs._flat(M, 16))
-        sel = None
-        if select is not None:
-            if not hasattr(select, "data_ptr"):
-                if not isinstance(select, np.ndarray) or select.dtype not in (np.bool_, np.uint8):
-                    raise ValueError("select must be a numpy bool / uint8 array, a device tensor or None, not %s %s"
-                                     % (type(select).__name__, getattr(select, "dtype", "")))
-                if select.shape != (self._n,):
-                    raise ValueError("select must have shape (%d,), one value per splat, not %s" % (self._n, select.shape))
-                import torch
-                select = torch.from_numpy(np.ascontiguousarray(select).view(np.uint8)).to(torch.device("cuda", self._device))
-            if str(select.dtype).split(".")[-1] not in ("bool", "uint8"):
-                raise ValueError("select must be bool or uint8, not %s" % select.dtype)
-            if tuple(int(s) for s in select.shape) != (self._n,):
-                raise ValueError("select must have shape (%d,), one value per splat, not %s" % (self._n, tuple(select.shape)))
-            if not select.is_contiguous():
-                raise ValueError("select must be contiguous (pass select.contiguous())")
-            if getattr(select.device, "type", "cuda") not in ("cuda", "hip"):
-                raise ValueError("a select with data_ptr() must live in device memory, not on %s (pass select.numpy())" % select.device)
-            import sys
-            torch = sys.modules.get("torch")
-            if torch is not None and isinstance(select, torch.Tensor):
-                torch.cuda.current_stream(select.device).synchronize()     # what produced the tensor has completed
-            sel = C.c_void_p(int(select.data_ptr())) if self._n else None
+        sel = self._device_select(select, self._n)
         self.synchronize()
         own = self._ctxs[0]
         masked = C.c_int32()
@@ -642,6 +650,58 @@ class SplatRenderer:
                 self.SetVisibility(self._vis_arg)
             finally:
                 self._ctxs = ctxs
+
+    def AppendCloud(self, src, select=None, index_map=False):
+        """Put splats into the cloud on the device (msplat_append_cloud): every splat i of src -- another
+        SplatRenderer on this device, or this one: a duplicate -- with select[i] (None: every splat) is appended behind this
+        renderer's own, in ascending source index; the old splats keep their indices 0..N-1, the K new ones get N..N+K-1.  Rows are
+        copied bit for bit where both clouds are stored alike and converted through their FP32 values where not; the cloud keeps
+        its storage kind.  select: Ns values, as TransformCloud takes them.  The renderer afterwards is one that was Init'ed with
+        the N+K rows, except that the old numbering, and with it the mask, stays, K visible values longer: every frame in flight
+        of both renderers is finished first; context 0 appends, the others are attached again (attaching drops their masks) and
+        are handed SetVisibility's last argument, K visible values longer -- a device-tensor mask must still hold the mask.  The crop
+        stays; Sort before the next Render.  Returns (K, map): map = None, or with index_map=True a torch int32 tensor of Ns on
+        this renderer's device, map[i] = new index of source splat i, -1 where it was not selected."""
+        if not self._ctxs:
+            raise _capi.MsplatError(_capi.ERR_NO_CLOUD, "AppendCloud: no cloud (Init first; Init of 0 rows makes an empty one)")
+        if not isinstance(src, SplatRenderer) or not src._ctxs:
+            raise _capi.MsplatError(_capi.ERR_NO_CLOUD, "AppendCloud: src is not a SplatRenderer with a cloud")
+        ns = src._n
+        sel = self._device_select(select, ns)
+        self.synchronize()
+        if src is not self:
+            src.synchronize()
+        own = self._ctxs[0]
+        m = None
+        if index_map:
+            import torch
+            m = torch.empty(max(ns, 1), dtype=torch.int32, device=torch.device("cuda", self._device))
+            torch.cuda.current_stream(m.device).synchronize()
+        k, masked = C.c_uint64(), C.c_int32()
+        _capi.check(own, self._lib.msplat_get_visibility(own, C.byref(masked), None, None))
+        _capi.check(own, self._lib.msplat_append_cloud(own, src._ctxs[0], sel, ns, C.c_void_p(m.data_ptr()) if m is not None else None,
+                                                       C.byref(k)))
+        self._select_arg = None
+        self._n += int(k.value)
+        self._ctx = own
+        self._cur = self._depth - 1          # the next Sort lands on context 0, as after Init
+        if not self._attach_all():
+            raise _capi.MsplatError(_capi.ERR_HIP, "AppendCloud: attaching the merged cloud failed: " + self._err)
+        vis = getattr(self, "_vis_arg", None)
+        if masked.value and vis is not None:
+            if hasattr(vis, "data_ptr"):
+                import torch
+                vis = torch.cat([vis.to(torch.uint8), torch.ones(int(k.value), dtype=torch.uint8, device=vis.device)])
+            else:
+                vis = np.concatenate([vis.view(np.uint8), np.ones(int(k.value), np.uint8)])
+            ctxs, self._ctxs = self._ctxs, self._ctxs[1:]
+            try:
+                if self._ctxs:
+                    self.SetVisibility(vis)
+                self._vis_arg = vis
+            finally:
+                self._ctxs = ctxs
+        return int(k.value), (m[:ns] if index_map else None)
 
     # -- which splat each pixel shows (msplat_render_ids / msplat_mark_ids, INTEGRATION.md 20) -----------
     def RenderIds(self, cameraMat, projMat, viewport, nearFar, window=None, out=None, out_ptr=None, pitch_bytes=0, depth=False,
