@@ -29,6 +29,12 @@ int msplat_debug_verify_order(msplat_ctx* ctx, uint32_t* key_violations, uint32_
  * used: under msplat_set_visibility / msplat_set_crop the context's own, built over the visible splats */
 int msplat_debug_get_cull_boxes(msplat_ctx* ctx, uint32_t* live, uint32_t* total, int* listed);
 
+/* ---- the conservative culls (band cull per splat and per box, the two-pass gate) bound a splat's reach by
+ * |J_row|^2 * view_scale2 * rho^2 lambda_max(Sigma): view_scale2 as every frame computes it from viewMat = inverse(cameraMat)
+ * (msplat_mat4_inverse), an upper bound of the squared spectral norm of its upper-left 3x3, at most 1e-5 above it (relative).
+ * Host arithmetic: no context, no device ---- */
+int msplat_debug_view_scale2(const float viewMat[16], float* out);
+
 /* ---- two-pass frames (msplat_config.two_pass) ---- */
 /* share > 0 pins the share of the visible splats in the first pass (any value gives the same pixels), 0 hands it back to the
  * feedback loop.  two_pass_frames: Renders of the context that ran in two passes; share_now: what the next one would use */

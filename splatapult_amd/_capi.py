@@ -199,6 +199,7 @@ SYMBOLS = [
     ("msplat_debug_get_compositor_launch", C.c_int, [C.c_void_p, _U32P]),
     ("msplat_debug_bin_order", C.c_int, [C.c_int32, C.c_int32, _U32P]),
     ("msplat_debug_get_bin_order", C.c_int, [C.c_void_p, _U32P, C.c_uint32]),
+    ("msplat_debug_view_scale2", C.c_int, [_F16, _F16]),
     ("msplat_cloud_create", C.c_void_p, [C.c_int]),
     ("msplat_cloud_destroy", None, [C.c_void_p]),
     ("msplat_cloud_import_ply", C.c_int, [C.c_void_p, C.c_char_p]),

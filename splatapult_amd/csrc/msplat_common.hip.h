@@ -152,7 +152,7 @@ struct FrameParams {
     float band_inv_stride;      // 1 / band_stride: row numbers are below 256, so their quotients are taken in float (exact)
     int full_sh, srgb;
     int band_cull;              // multi-GPU only: Sort also drops splats that cannot reach an owned bin row
-    float view_scale2;          // largest squared column norm of mat3(view) (1 for a rigid camera)
+    float view_scale2;          // upper bound of sigma_max(mat3(view))^2, at most 1e-5 above it (view_scale2_of; 1 + 1e-6 for a rigid camera)
     int depth_bits;             // 0 = colour-only target (no depth test); 24 / 32 = emulated depth buffer
     int rop;                    // 0 = float accumulation; 1 = RGBA8, 2 = RGBA16F render-target rounding after every blend
     // Two views in ONE render chain (msplat_render_stereo, r4): the second view's matrices; its splats are the draw-order ranks
@@ -394,17 +394,11 @@ __device__ __forceinline__ uint32_t xcd_contiguous(uint32_t b, uint32_t n)
     return base + idx;
 }
 
-// World-space footprint bound of a splat, kept in pos4.w for the band-restricted cull: rho^2 * lambda_max(Sigma) with
-// rho^2 = 2 ln(256 alpha) (the fragment shader's discard radius) -- every projected variance M Sigma M^T is at most |M|^2 times
-// the largest eigenvalue.  (r1-r3 used trace(Sigma), 1.7x the radius of an isotropic splat: a rank of an 8-way row-sharded
-// frame then kept 17 % of the visible splats for 12.5 % of the rows.)  Closed form for a symmetric 3x3, in double, + 1e-5.
-// S = Sigma as stored: column-major 3x3 (S[3c + r]).  0 when alpha <= 1/256 (the splat can never pass the discard test).
-__host__ __device__ inline float footprint_bound(const float* S, float alpha)
+// Largest eigenvalue of the symmetric 3x3 with diagonal a00 a11 a22 and off-diagonal a01 a02 a12: the trigonometric closed form,
+// in double.  Junk in, junk out (NaN, or a value above the trace of a matrix that is not PSD): each caller orders the result
+// against its own fallback.
+__host__ __device__ inline double sym3_lambda_max(double a00, double a11, double a22, double a01, double a02, double a12)
 {
-    const float rho2 = 2.0f * logf(256.0f * alpha);
-    if (!(rho2 > 0.0f)) return 0.0f;
-    const double a00 = S[0], a11 = S[4], a22 = S[8];
-    const double a01 = 0.5 * ((double)S[1] + S[3]), a02 = 0.5 * ((double)S[2] + S[6]), a12 = 0.5 * ((double)S[5] + S[7]);
     const double tr = a00 + a11 + a22, q = tr / 3.0;
     const double p1 = a01 * a01 + a02 * a02 + a12 * a12;
     const double p2 = (a00 - q) * (a00 - q) + (a11 - q) * (a11 - q) + (a22 - q) * (a22 - q) + 2.0 * p1;
@@ -416,6 +410,44 @@ __host__ __device__ inline float footprint_bound(const float* S, float alpha)
         r = r < -1.0 ? -1.0 : (r > 1.0 ? 1.0 : r);
         lmax = q + 2.0 * p * cos(acos(r) / 3.0);
     }
+    return lmax;
+}
+
+// FrameParams::view_scale2: an upper bound of sigma_max(W)^2 for W = mat3(view), the factor by which the camera matrix can
+// stretch a world-space length -- |J_row W|^2 <= |J_row|^2 sigma_max(W)^2 holds for ANY W, so the culls built on it are sound for
+// every invertible camera matrix (scaled, squashed, sheared), not only rigid ones.  (The largest squared column norm of W, used
+// at first, is a LOWER bound of sigma_max^2 and equals it only for a rotation times a uniform scale: a camera squashed along one
+// axis lost visible splats to the band cull.)  Largest eigenvalue of W^T W in double; when the closed form's result is not
+// finite or not between the largest column norm^2 and the Frobenius norm^2 (it lies between them), the Frobenius norm^2: never
+// below sigma_max^2, NaN / inf for a matrix that holds one.  + 1e-6, which covers the rounding to float.  0 for W = 0.
+__host__ inline float view_scale2_of(const float view[16])
+{
+    double g[3][3], frob = 0.0, colmax = 0.0;                 // g = W^T W (view[4 c + r]: column c, row r)
+    for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b)
+            g[a][b] = (double)view[4 * a] * view[4 * b] + (double)view[4 * a + 1] * view[4 * b + 1] + (double)view[4 * a + 2] * view[4 * b + 2];
+    for (int a = 0; a < 3; ++a) {
+        frob += g[a][a];
+        colmax = g[a][a] > colmax ? g[a][a] : colmax;
+    }
+    double lmax = sym3_lambda_max(g[0][0], g[1][1], g[2][2], g[0][1], g[0][2], g[1][2]);
+    if (!(lmax >= colmax * (1.0 - 1e-9) && lmax <= frob * (1.0 + 1e-9))) lmax = frob;
+    return (float)(lmax * (1.0 + 1e-6));
+}
+
+// World-space footprint bound of a splat, kept in pos4.w for the band-restricted cull: rho^2 * lambda_max(Sigma) with
+// rho^2 = 2 ln(256 alpha) (the fragment shader's discard radius) -- every projected variance M Sigma M^T is at most |M|^2 times
+// the largest eigenvalue.  (r1-r3 used trace(Sigma), 1.7x the radius of an isotropic splat: a rank of an 8-way row-sharded
+// frame then kept 17 % of the visible splats for 12.5 % of the rows.)  Closed form for a symmetric 3x3, in double, + 1e-5.
+// S = Sigma as stored: column-major 3x3 (S[3c + r]).  0 when alpha <= 1/256 (the splat can never pass the discard test).
+__host__ __device__ inline float footprint_bound(const float* S, float alpha)
+{
+    const float rho2 = 2.0f * logf(256.0f * alpha);
+    if (!(rho2 > 0.0f)) return 0.0f;
+    const double a00 = S[0], a11 = S[4], a22 = S[8];
+    const double a01 = 0.5 * ((double)S[1] + S[3]), a02 = 0.5 * ((double)S[2] + S[6]), a12 = 0.5 * ((double)S[5] + S[7]);
+    const double tr = a00 + a11 + a22;
+    double lmax = sym3_lambda_max(a00, a11, a22, a01, a02, a12);
     if (!(lmax <= tr)) lmax = tr;                       // NaN / negative-eigenvalue junk: fall back to the trace (also a bound for PSD)
     if (!(lmax >= 0.0)) lmax = 0.0;
     // never 0 for a splat that can be drawn: a zero (or underflowing) covariance still has the 0.3-pixel low-pass footprint, and

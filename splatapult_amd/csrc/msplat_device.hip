@@ -958,10 +958,7 @@ static int make_frame_params(msplat_ctx* ctx, const float cameraMat[16], const f
     fp.rop = ctx->rop;
     fp.views = 1;
     fp.rows_view = rows_full;
-    fp.view_scale2 = 0.0f;
-    for (int c = 0; c < 3; ++c)
-        fp.view_scale2 = std::max(fp.view_scale2, fp.view[c * 4] * fp.view[c * 4] + fp.view[c * 4 + 1] * fp.view[c * 4 + 1] +
-                                                      fp.view[c * 4 + 2] * fp.view[c * 4 + 2]);
+    fp.view_scale2 = view_scale2_of(fp.view);
     return MSPLAT_OK;
 }
 

@@ -355,6 +355,14 @@ int msplat_debug_bin_order(int32_t tiles_x, int32_t rows, uint32_t* out)
     return MSPLAT_OK;
 }
 
+// FrameParams::view_scale2 as make_frame_params computes it from viewMat = inverse(cameraMat), on the host (no context, no device)
+int msplat_debug_view_scale2(const float viewMat[16], float* out)
+{
+    if (!viewMat || !out) return MSPLAT_ERR_INVALID_ARG;
+    *out = view_scale2_of(viewMat);
+    return MSPLAT_OK;
+}
+
 int msplat_debug_get_tile_lists(msplat_ctx* ctx, uint32_t* tile_start, uint32_t tile_cap,
                                 uint32_t* pairs, uint64_t pair_cap)
 {
