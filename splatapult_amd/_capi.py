@@ -104,6 +104,10 @@ SYMBOLS = [
     ("msplat_upload_attributes_device", C.c_int, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 6 + [C.c_int]),
     ("msplat_debug_upload_kernel_ms", C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     ("msplat_download_cloud", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
+    ("msplat_download_cloud_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
+    ("msplat_download_attributes_device", C.c_int, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 6),
+    ("msplat_download_ply_vertices_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(PlyLayout)]),
+    ("msplat_export_ply", C.c_int, [C.c_void_p, C.c_char_p]),
     ("msplat_set_band", C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     ("msplat_set_band_cull", C.c_int, [C.c_void_p, C.c_int]),
     ("msplat_set_band_layout", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),

@@ -3,7 +3,7 @@
 // Sort + Render into an explicit RGBA32F framebuffer, dumped as a binary PPM-like float file.
 //
 //   g++ -std=c++17 -I. splatapult_amd/host/example_render.cpp -Lsplatapult_amd/lib -lmsplat -o example_render
-//   ./example_render scene.ply out.f32 [width height] [--nosh] [--frames-in-flight N] [--devices 0,1,2,...] [--over-gradient] [--depth out_depth.f32] [--srgb8 out.png] [--crop-sphere cx cy cz r] [--pick X,Y] [--min-score S] [--compact] [--append OTHER.ply]
+//   ./example_render scene.ply out.f32 [width height] [--nosh] [--frames-in-flight N] [--devices 0,1,2,...] [--over-gradient] [--depth out_depth.f32] [--srgb8 out.png] [--crop-sphere cx cy cz r] [--pick X,Y] [--min-score S] [--compact] [--append OTHER.ply] [--save OUT.ply]
 // With --frames-in-flight N the same frame is issued N + 1 times round-robin over N contexts that share the cloud
 // (SplatRenderer::SetFramesInFlight); the last one is written.  With --devices the frame's bin rows are dealt to the
 // listed GPUs (SplatRenderer::ConfigureDevices, msplat_group_*): same pixels.  With --over-gradient the target is first filled with
@@ -26,6 +26,9 @@
 // With --append OTHER.ply a second renderer uploads that file and its splats are appended to the scene's before the frame
 // (SplatRenderer::AppendCloud, msplat_append_cloud: both stores' records gathered into a new one on the device); the counts are
 // printed.  OTHER.ply is read with the scene's SH degree.  One device only.
+// With --save OUT.ply the cloud as it is on the device after --append, --crop-sphere and --compact have run is written as a PLY
+// (SplatRenderer::ExportPly, msplat_export_ply: the per-splat math of GaussianCloud::ExportPly as a HIP kernel).  A crop that was not
+// made permanent with --compact is not applied: what is saved is the cloud.  One device only.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -70,6 +73,7 @@ int main(int argc, char** argv)
     const char* depthPath = nullptr;
     const char* srgb8Path = nullptr;
     const char* appendPath = nullptr;
+    const char* savePath = nullptr;
     std::vector<int> devices;
     float cropSphere[4] = {0.0f, 0.0f, 0.0f, 0.0f};       // centre, radius; radius 0: no crop
     for (int i = 3; i < argc; ++i) {
@@ -83,6 +87,7 @@ int main(int argc, char** argv)
         if (!std::strcmp(argv[i], "--pick") && i + 1 < argc && std::sscanf(argv[i + 1], "%d,%d", &pickX, &pickY) != 2) pickX = pickY = -1;
         if (!std::strcmp(argv[i], "--srgb8") && i + 1 < argc) srgb8Path = argv[i + 1];
         if (!std::strcmp(argv[i], "--append") && i + 1 < argc) appendPath = argv[i + 1];
+        if (!std::strcmp(argv[i], "--save") && i + 1 < argc) savePath = argv[i + 1];
         if (!std::strcmp(argv[i], "--min-score") && i + 1 < argc) minScore = std::atof(argv[i + 1]);
         if (!std::strcmp(argv[i], "--devices") && i + 1 < argc)
             for (const char* p = argv[i + 1]; *p;) {
@@ -197,6 +202,11 @@ int main(int argc, char** argv)
         if (depthPath) renderer.RenderWithDepth(cameraMat, projMat, viewport, nearFar, depth.data());
         else renderer.Render(cameraMat, projMat, viewport, nearFar);
         renderer.Synchronize();
+    }
+
+    if (savePath && devices.size() <= 1) {
+        if (!renderer.ExportPly(savePath)) return 1;
+        std::printf("saved the cloud on the device to %s\n", savePath);
     }
 
     FILE* f = std::fopen(argv[2], "wb");

@@ -419,6 +419,29 @@ public:
         return AttachContexts();
     }
 
+    // The cloud out of the device (msplat_export_ply, msplat_download_cloud_device, msplat_download_attributes_device): as it is on the
+    // device -- moved, pasted into, compacted --, upload numbering, the mask and the crop ignored; nothing of the renderer changes.
+    // ExportPly writes the PLY GaussianCloud::ExportPly writes; DownloadDevice N tight reference records (244 B with full SH, 100 B
+    // without) at d_aos (16-byte aligned, capBytes large): what InitDevice takes with the reference offsets; DownloadDeviceAttributes
+    // the six arrays InitDeviceAttributes takes (n = the cloud's N; d_f_rest may be nullptr).  A device group has no download.
+    bool ExportPly(const std::string& plyFilename) { return Download("ExportPly", [&](msplat_ctx* h) { return msplat_export_ply(h, plyFilename.c_str()); }); }
+    bool DownloadDevice(void* d_aos, uint64_t capBytes) { return Download("DownloadDevice", [&](msplat_ctx* h) { return msplat_download_cloud_device(h, d_aos, capBytes); }); }
+    bool DownloadDeviceAttributes(uint64_t n, float* d_xyz, float* d_f_dc, float* d_f_rest, float* d_opacity, float* d_log_scale, float* d_rot)
+    {
+        return Download("DownloadDeviceAttributes", [&](msplat_ctx* h) { return msplat_download_attributes_device(h, n, d_xyz, d_f_dc, d_f_rest, d_opacity, d_log_scale, d_rot); });
+    }
+    template <class Call>
+    bool Download(const char* who, Call&& call)
+    {
+        if (group || !ctx) {
+            std::fprintf(stderr, "[msplat][E] %s: %s\n", who, group ? "a device group has no download" : "no cloud (Init first)");
+            return false;
+        }
+        const int rc = call(ctx);
+        if (rc != MSPLAT_OK) std::fprintf(stderr, "[msplat][E] %s: %s\n", who, msplat_last_error(ctx));
+        return rc == MSPLAT_OK;
+    }
+
     // Which splat each pixel shows (msplat_render_ids): per pixel of window = {x0, y0, w, h} (viewport pixels, row 0 = GL bottom; nullptr =
     // the whole viewport) the upload index of the splat of the latest Sort that contributes most to it, MSPLAT_ID_NONE where none
     // reaches; idDepth (may be nullptr) = that splat's window depth, 1.0 at MSPLAT_ID_NONE.  Both planes are w x h of the WINDOW, rows

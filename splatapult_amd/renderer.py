@@ -302,6 +302,45 @@ class SplatRenderer:
         _capi.check(self._ctx, self._lib.msplat_download_cloud(self._ctx, out.ctypes.data, out.nbytes))
         return out[:self._n]
 
+    # -- the cloud out of the device (msplat_download_*_device, msplat_export_ply) --------
+    def _download(self, what, call):
+        """run call(ctx) -> code on the current context; False (and last_error) instead of an exception"""
+        if not self._ctx:
+            self._err = what + ": no context (Init first)"
+            return False
+        rc = call(self._ctx)
+        if rc != _capi.OK:
+            self._err = self._lib.msplat_last_error(self._ctx).decode()
+            return False
+        return True
+
+    def ExportPly(self, plyFilename):
+        """Write the cloud as it is on the device -- moved, pasted into, compacted -- as a PLY any 3DGS tool loads
+        (msplat_export_ply): GaussianCloud.ExportPly's header and per-splat values, upload numbering, the mask and the crop
+        ignored.  Returns False (see last_error()) on failure, like GaussianCloud.ExportPly."""
+        return self._download("ExportPly", lambda h: self._lib.msplat_export_ply(h, str(plyFilename).encode()))
+
+    def DownloadTensors(self, f_rest=True):
+        """The cloud as the six tensors InitFromTensors takes, on this renderer's device (msplat_download_attributes_device): a dict
+        xyz (N, 3), f_dc (N, 3), f_rest (N, 45) in PLY order (zeros for a cloud of SH degree 0; None with f_rest=False),
+        opacity (N,), log_scale (N, 3), rot (N, 4) as w x y z, float32.  Returns None (see last_error()) on failure."""
+        if not self._ctx:
+            self._err = "DownloadTensors: no context (Init first)"
+            return None
+        import torch
+        n, dev = self._n, torch.device("cuda", self._device)
+        shapes = dict(xyz=(n, 3), f_dc=(n, 3), f_rest=(n, 45), opacity=(n,), log_scale=(n, 3), rot=(n, 4))
+        t = {k: None if k == "f_rest" and not f_rest else torch.empty(s, dtype=torch.float32, device=dev) for k, s in shapes.items()}
+        torch.cuda.current_stream(dev).synchronize()
+        p = [C.c_void_p(t[k].data_ptr() if t[k] is not None and n else None) for k in shapes]
+        return t if self._download("DownloadTensors", lambda h: self._lib.msplat_download_attributes_device(h, n, *p)) else None
+
+    def DownloadDevice(self, ptr, cap_bytes):
+        """The cloud as N tight reference records (244 B with full SH, 100 B without: download_cloud's bytes) at the device pointer
+        ptr (int, 16-byte aligned, cap_bytes large; msplat_download_cloud_device) -- what InitFromDevice takes with the reference
+        offsets.  Returns False (see last_error()) on failure."""
+        return self._download("DownloadDevice", lambda h: self._lib.msplat_download_cloud_device(h, C.c_void_p(int(ptr) or None), int(cap_bytes)))
+
     def cloud_storage(self):
         """"fp32" / "sh_fp16" / "sh_q8": how the uploaded cloud is stored (msplat_get_cloud_storage); None without a cloud"""
         k = self._lib.msplat_get_cloud_storage(self._ctx) if self._ctx else -1
