@@ -71,6 +71,14 @@ int msplat_get_composite_work(msplat_ctx* ctx, msplat_composite_work* out);
  * pass's item count, the unfinished bins, exists on the device only; its grid is chosen the same way) ---- */
 int msplat_debug_get_compositor_launch(msplat_ctx* ctx, uint32_t out[4]);
 
+/* ---- the column pass's heavy chunks: what the context's latest binning chain (the second one of a two-pass Render) met and had.
+ * out[0] = chunks of 1024 draw-order ranks with MORE than 49152 (splat, bin) pairs, as bin1_upsweep counted them -- every such chunk,
+ * with or without a slot --, [1] = the helper slots its bin1_downsweep was launched with (min(128, 2 * an earlier frame's count + 8),
+ * 0 after a frame without heavy chunks): min(out[0], out[1]) chunks were split over 8 workgroups, the others ran unsplit.  Reads a
+ * host-mapped word and host bookkeeping after the usual synchronise: no device work.  tests/test_gpu_binning_limits.py proves with
+ * it which regime its frames ran in ---- */
+int msplat_debug_get_heavy_chunks(msplat_ctx* ctx, uint32_t out[2]);
+
 /* ---- the order in which persistent compositor waves walk the bins (grid < items above, unordered): slot s of the table holds a bin,
  * and the slots of one residue class mod 8 -- the bins one XCD composites -- form compact blocks of bins, so that the bins a
  * splat covers share an L2.  msplat_debug_bin_order: the table for a grid of tiles_x x rows bins (1 .. 256 each) as the host computes

@@ -201,6 +201,7 @@ SYMBOLS = [
     ("msplat_get_two_pass_info", C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     ("msplat_get_composite_work", C.c_int, [C.c_void_p, C.POINTER(CompositeWork)]),
     ("msplat_debug_get_compositor_launch", C.c_int, [C.c_void_p, _U32P]),
+    ("msplat_debug_get_heavy_chunks", C.c_int, [C.c_void_p, _U32P]),
     ("msplat_debug_bin_order", C.c_int, [C.c_int32, C.c_int32, _U32P]),
     ("msplat_debug_get_bin_order", C.c_int, [C.c_void_p, _U32P, C.c_uint32]),
     ("msplat_debug_view_scale2", C.c_int, [_F16, _F16]),

@@ -278,6 +278,7 @@ struct msplat_ctx {
     int two_pass_mode = MSPLAT_TWO_PASS_AUTO;
     TwoPassController two_pass;              // ... when to run one, and with what share in pass 1 (host/two_pass_controller.hpp)
     bool last_render_two_pass = false;
+    uint32_t heavy_slots_launched = 0;       // msplat_debug_get_heavy_chunks: helper slots of the latest bin1_downsweep launch
     uint32_t comp_launch[4] = {0, 0, 0, 0};  // msplat_debug_get_compositor_launch: items, grid, ordered, kernel kind of the latest compositor launch
     uint64_t frames_two_pass = 0;
 
@@ -1381,6 +1382,7 @@ static void issue_binning(RenderChain& rc, int keep_overflow, int occ_pass)
     const uint32_t last_heavy = host_word(ctx, kHostHeavyChunks);
     const uint32_t heavy_slots = last_heavy != 0u ? std::min<uint32_t>(kHeavyCap, 2u * last_heavy + 8u) : 0u;
     const int nhelp = (int)(heavy_slots * (kHeavyParts - 1u));
+    ctx->heavy_slots_launched = heavy_slots;
     // scan-free variants while the chunk tables are small; the row pass's size (D) is only known on the device, so
     // its choice uses the D of an EARLIER frame that the binning kernel left in host-mapped memory (0 = none yet);
     // either variant is correct at any size, the choice only matters for speed

@@ -333,6 +333,20 @@ int msplat_debug_get_compositor_launch(msplat_ctx* ctx, uint32_t out[4])
     return MSPLAT_OK;
 }
 
+// the heavy chunks of the context's latest column pass: how many chunks bin1_upsweep found over kHeavyPairs (the host-mapped word
+// bin1_downsweep leaves for the next frame's launch) and the helper slots issue_binning gave that downsweep
+int msplat_debug_get_heavy_chunks(msplat_ctx* ctx, uint32_t out[2])
+{
+    drain_async(ctx);
+    if (!ctx || !out) return fail(ctx, MSPLAT_ERR_INVALID_ARG, "NULL argument");
+    if (!ctx->has_render) return fail(ctx, MSPLAT_ERR_NO_SORT, "no render yet");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    out[0] = host_word(ctx, kHostHeavyChunks);
+    out[1] = ctx->heavy_slots_launched;
+    return MSPLAT_OK;
+}
+
 // the order[slot] -> bin table the context's latest compositor launch walked (the first pass's of a two-pass frame), read back from
 // the device: tiles_x * tiles_y words
 int msplat_debug_get_bin_order(msplat_ctx* ctx, uint32_t* out, uint32_t cap)

@@ -1043,6 +1043,13 @@ class SplatRenderer:
         _capi.check(self._ctx, self._lib.msplat_debug_get_compositor_launch(self._ctx, out))
         return tuple(int(v) for v in out)
 
+    def heavy_chunks(self):
+        """(chunks over the heavy threshold, helper slots) of the current context's latest column pass (msplat_debug_get_heavy_chunks):
+        min of the two were split over 8 workgroups; the second chain's numbers after a two-pass Render"""
+        out = (C.c_uint32 * 2)()
+        _capi.check(self._ctx, self._lib.msplat_debug_get_heavy_chunks(self._ctx, out))
+        return int(out[0]), int(out[1])
+
     def bin_order(self):
         """the order[slot] -> bin table the current context's latest compositor launch walked, read back from the device
         (msplat_debug_get_bin_order): one word per bin"""
