@@ -237,8 +237,8 @@ __global__ __launch_bounds__(kCompThreads, comp_occ(OCC, TWO_VIEWS, DEPTH, ZTEST
             }
         }
     }
-    // The exponent is evaluated as a polynomial in TILE-CENTRED pixel coordinates (|u|, |v| <= 7.5: no cancellation
-    // trouble): e(u, v) = c0 + c1 u + c2 v + c3 u^2 + c4 u v + c5 v^2, coefficients per staged record.  Per record and lane
+    // The exponent is evaluated as a polynomial in TILE-CENTRED pixel coordinates (|u|, |v| <= 7.5: no cancellation in u
+    // and v; c0 itself cancels far from the splat's centre and is compensated there, below): e(u, v) = c0 + c1 u + c2 v + c3 u^2 + c4 u v + c5 v^2, coefficients per staged record.  Per record and lane
     // that is 3 scalar FMAs for the u part plus 2 packed FMAs per strip pair -- the centre-relative form (dx, dy, base,
     // lin) needed 4 + 3: 162 instead of 186 VALU pipe cycles per record.
     const float xc = (float)(tx * kTile) + 0.5f * (float)kTile, yc = tile_y0 + 0.5f * (float)ROWS;
@@ -307,7 +307,26 @@ __global__ __launch_bounds__(kCompThreads, comp_occ(OCC, TWO_VIEWS, DEPTH, ZTEST
             const float Aa = qa * a, Bb = qb * b, Cb = qc * b, Ba = qb * a;
             const float c1 = __builtin_fmaf(-2.0f, Aa, -Bb);
             const float c2 = __builtin_fmaf(-2.0f, Cb, -Ba);
-            const float c0 = __builtin_fmaf(Aa + Bb, a, __builtin_fmaf(Cb, b, p1.y - kBias));   // the exponent bias rides on log2(alpha)
+            // c0 = (A a + B b) a + C b b + log2 alpha - 118 (the exponent bias rides on log2 alpha).  Its quadratic terms are as large as
+            // |A| a^2 and cancel for a long thin splat that crosses the tile far from its centre (a 45-degree needle of short variance
+            // 0.5 px^2 at 2000 px: terms of 1.4e6, an ulp of 0.125; plain float32 left 0.06 ... 0.2 of error in e, more than the 0.05
+            // slack of the test below and 6 % in w: DESIGN.md 4).  A batch that holds a record more than kFarCentre px from the tile's
+            // centre (wave-uniform: one ballot) therefore COMPENSATES the sum: every product and the two sums that cancel carry their
+            // exact float32 residue (fma(x, y, -xy); Knuth's two-sum), the residues are added at the end.  Nearer than that the terms
+            // stay below 1.2e5 (|A| <= 2.41: the 0.3 px^2 floor of the covariance) and the plain form is good to 8e-3.
+            constexpr float kFarCentre = 128.0f;
+            float c0 = __builtin_fmaf(Aa + Bb, a, __builtin_fmaf(Cb, b, p1.y - kBias));
+            if (__ballot(lane < (int)cnt && (fabsf(a) > kFarCentre || fabsf(b) > kFarCentre)) != 0ull) {
+                const float rAa = __builtin_fmaf(qa, a, -Aa), rBb = __builtin_fmaf(qb, b, -Bb), rCb = __builtin_fmaf(qc, b, -Cb);
+                const float s = Aa + Bb, sv = s - Aa;
+                const float rs = (Aa - (s - sv)) + (Bb - sv);                    // Aa + Bb = s + rs
+                const float p = s * a, q = Cb * b;
+                const float rp = __builtin_fmaf(s, a, -p), rq = __builtin_fmaf(Cb, b, -q);
+                const float t = p + q, tv = t - p;
+                const float rt = (p - (t - tv)) + (q - tv);                      // p + q = t + rt
+                const float tail = __builtin_fmaf((rs + rAa) + rBb, a, __builtin_fmaf(rCb, b, (rp + rq) + rt));
+                c0 = (t + (p1.y - kBias)) + tail;
+            }
             // y reach of the footprint against the strips that are still live (strip k: v in [4k - Vh, 4k + 3 - Vh])
             const float vlo = b - p2.w, vhi = b + p2.w;
             bool rel = lane < (int)cnt && vhi >= -Vh && vlo <= Vh;

@@ -1102,6 +1102,15 @@ class SplatRenderer:
             self._ctx, out.ctypes.data_as(C.POINTER(C.c_uint32)), out.shape[0]))
         return out[out[:, 7] > 0]
 
+    def debug_tile_probe_table(self):
+        """the probe's eight words per work item of the current context's latest probed render, row = work item (debug_tile_probe
+        drops the rows of the items that did not run, and with them the index); rows of items outside the image are zero"""
+        items = self.compositor_launch()[0]
+        out = np.zeros((max(items, 1), 8), np.uint32)
+        _capi.check(self._ctx, self._lib.msplat_debug_get_tile_probe8(
+            self._ctx, out.ctypes.data_as(C.POINTER(C.c_uint32)), out.shape[0]))
+        return out[:items]
+
     def debug_tile_lists(self, want_pairs=True):
         st = self.stats()
         nt = st["tiles_x"] * st["tiles_y"]
