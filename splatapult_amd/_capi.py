@@ -185,6 +185,10 @@ SYMBOLS = [
     ("msplat_set_visibility_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
     ("msplat_set_crop", C.c_int, [C.c_void_p, _F16, C.c_int32]),
     ("msplat_get_visibility", C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]),
+    ("msplat_set_overlay", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
+    ("msplat_set_overlay_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
+    ("msplat_set_overlay_palette", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
+    ("msplat_get_overlay", C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]),
     ("msplat_compact_cloud", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
     ("msplat_transform_cloud", C.c_int, [C.c_void_p, _F16, C.c_void_p, C.c_uint64, C.c_int32]),
     ("msplat_append_cloud", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64)]),

@@ -186,7 +186,9 @@ int msplat_append_cloud(msplat_ctx* ctx, msplat_ctx* src, const uint8_t* d_selec
     st->F4 = F4;
     // from here on an upload of N + K splats whose records are in place -- but for the mask: prepare_cloud_buffers frees the old one
     // (the stream is idle), the extended one takes its place
+    const OverlayKept ov = overlay_take(ctx);      // (the overlay's classes stay as well; overlay_restore extends them by K bytes of class 0)
     rc = prepare_cloud_buffers(ctx, total_n, full_sh, st);
+    ctx->ov_cls = ov.cls;
     if (ctx->store == st) ctx->device_bytes += need_pos + need_rec;
     if (rc) {
         buf_free(ctx, nmask);
@@ -202,6 +204,7 @@ int msplat_append_cloud(msplat_ctx* ctx, msplat_ctx* src, const uint8_t* d_selec
         ctx->has_mask = true;
         ctx->vis_dirty = true;
     }
+    if ((rc = overlay_restore(ctx, ov, N, K))) return rc;
     ctx->has_cloud = true;
     if (n_added_out) *n_added_out = K;
     return MSPLAT_OK;

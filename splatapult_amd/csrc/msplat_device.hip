@@ -201,6 +201,18 @@ struct msplat_ctx {
     uint8_t* vis_stage = nullptr;       // pinned: what the latest host mask's copy reads ...
     size_t vis_stage_bytes = 0;
     hipEvent_t vis_stage_ev = nullptr;  // ... and the event behind that copy
+    // render-time overlay (msplat_set_overlay* / msplat_set_overlay_palette; msplat_overlay.hip.h): a class byte per splat and a palette
+    // tint the projected records of the context's Renders.  Allocated by the set calls, never by a Render
+    Buf ov_cls;                 // uint8[N], upload numbering: the caller's classes, copied on the stream
+    Buf ov_slot;                // uint8[N], storage order (a store in Morton order only): overlay_classes_kernel, where overlay_dirty
+    Buf ov_pal;                 // float4[kOverlayEntries]: the palette, a = 0 beyond the caller's count
+    bool has_classes = false;
+    bool overlay_dirty = false; // ov_slot is older than the classes or the store's order: resolved by the next overlaid Render
+    uint32_t ov_count = 0;      // palette entries the caller set ...
+    bool ov_tints = false;      // ... and whether one of them has a != 0
+    uint8_t* ov_stage[2] = {nullptr, nullptr};       // pinned: what the latest host classes' / palette's copy reads ...
+    size_t ov_stage_bytes[2] = {0, 0};
+    hipEvent_t ov_stage_ev[2] = {nullptr, nullptr};  // ... and the events behind those copies
     uint32_t sort_parity = 0;
     bool tables_dirty = false;  // a launch failed: clear every self-cleaning table before the next frame
     // per-bin pair counts taken by the row pass's upsweep (r3): list offsets + work order (no kernel of their own)
@@ -700,6 +712,10 @@ void msplat_destroy(msplat_ctx* ctx)
     if (ctx->bin_order_ev) (void)hipEventDestroy(ctx->bin_order_ev);
     if (ctx->vis_stage) (void)hipHostFree(ctx->vis_stage);
     if (ctx->vis_stage_ev) (void)hipEventDestroy(ctx->vis_stage_ev);
+    for (int k = 0; k < 2; ++k) {
+        if (ctx->ov_stage[k]) (void)hipHostFree(ctx->ov_stage[k]);
+        if (ctx->ov_stage_ev[k]) (void)hipEventDestroy(ctx->ov_stage_ev[k]);
+    }
     for (Buf* b : ctx->bufs) buf_free(ctx, *b);
     if (ctx->ev_ok)
         for (auto& set : ctx->ev)
@@ -978,6 +994,7 @@ static int clear_frame_tables(msplat_ctx* ctx)
 }
 
 #include "msplat_visibility.hip.inc"
+#include "msplat_overlay.hip.inc"
 #include "msplat_compact.hip.inc"
 #include "msplat_transform.hip.inc"
 #include "msplat_append.hip.inc"
@@ -1253,7 +1270,8 @@ static bool occlusion_plan(msplat_ctx* ctx, const FrameParams& fp, bool stereo, 
 {
     const size_t nbins = (size_t)std::max(fp.tiles_x * fp.tiles_y, 0);
     // (scan_free: the chunk offset of pass 1's column pass exists in the scan-free form only; kOccSatMax: the table of unfinished bins)
-    const bool eligible = !stereo && !draw_order_frame(ctx) && !ctx->probe_on && ctx->scan_free &&
+    // (an overlaid frame is a one-pass frame: overlay_kernel tints the records of ONE projection over all ranks)
+    const bool eligible = !stereo && !draw_order_frame(ctx) && !ctx->probe_on && ctx->scan_free && !overlay_active(ctx) &&
                           nbins != 0 && (fp.tiles_x + 1) * (fp.tiles_y + 1) <= kOccSatMax;
     const TwoPassFrame frame{ctx->two_pass_mode, eligible, ctx->cfg.frame_mode == MSPLAT_FRAMES_IN_FLIGHT, ctx->N, host_word(ctx, kHostV), nbins};
     const TwoPassFeedback fb{host_word(ctx, kHostPass1Pairs), host_word(ctx, kHostUnfinishedBins), host_word(ctx, kHostPass2Pairs),
@@ -1301,6 +1319,7 @@ struct RenderChain {
     bool ordered = true;
     uint32_t comp_items = 0, comp_pool = 0;
     bool want_zw = false;        // an id frame: z_w per rank although the chain has no planes
+    bool overlay = false;        // a Render with an active overlay: overlay_kernel behind the projection (never an id or a score frame)
 };
 
 // vertex + geometry stage.  mode: PROJ_PLAIN / PROJ_TWO_VIEWS (chosen from the chain), PROJ_PASS1 or PROJ_LISTED (two-pass frames)
@@ -1351,6 +1370,7 @@ static void issue_projection(RenderChain& rc, int mode, float occ_frac)
         const ProjExtra ex{nullptr, nullptr, nullptr, 0.0f};
         project(int_t<PROJ_PLAIN>{}, pgrid, (const uint32_t*)d_Vsort, ex, ProjNoView1{0});
     }
+    if (rc.overlay) launch_overlay(ctx, s, (const uint32_t*)d_Vsort, rc.N, rc.stereo);      // (a one-pass frame: occlusion_plan)
 }
 
 // bin lists over the current rectangles: column pass (bin1_*), row pass (radix_*<MODE_PAIR>), list offsets + work order.
@@ -1644,6 +1664,7 @@ static int launch_render(msplat_ctx* ctx, const FrameParams& fp, void* d_out, vo
     const int tset = rc.tset = (int)(ctx->render_sets % msplat_ctx::kEvSets);
     if (timed) HIP_TRY(ctx, hipEventRecord(ctx->ev[tset][kEvRenderBegin], s));
     rc.occ = (uint32_t*)ctx->occ.p;              // (allocated by occlusion_plan with a context's first two-pass frame)
+    rc.overlay = overlay_active(ctx);
 
     // ---- the plain chain (also: both eyes in one chain, points, the emulations), or pass 1 of a two-pass frame ----
     issue_projection(rc, two_pass ? PROJ_PASS1 : PROJ_PLAIN, plan->frac);
@@ -1767,6 +1788,7 @@ static int render_frame(msplat_ctx* ctx, const FrameParams& fp, void* rgba, void
                         int out_is_device, const FramePlanes& pl)
 {
     int rc;
+    if ((rc = overlay_frame_checks(ctx))) return rc;
     ctx->last_fp = fp;
     if (ctx->tables_dirty && (rc = clear_frame_tables(ctx))) return rc;
     if (ctx->point_mode && !ctx->sprite.p && (rc = build_sprite(ctx, nullptr, 0, 0))) return rc;   // built-in sphere sprite

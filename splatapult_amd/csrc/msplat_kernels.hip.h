@@ -1,4 +1,4 @@
-// msplat_kernels.hip.h -- hand-written CDNA4 (gfx950, wave64) kernels of the splat hot path, in fourteen parts.
+// msplat_kernels.hip.h -- hand-written CDNA4 (gfx950, wave64) kernels of the splat hot path, in fifteen parts.
 //
 // Replaces (not ports) the reference's GL pipeline:
 //   shader/presort_compute.glsl + shader/multi_radixsort*.glsl  -> msplat_sort.hip.h      radix_* / ws_* (cull fused in pass 0)
@@ -7,6 +7,7 @@
 //                                                                  msplat_composite.hip.h composite_kernel, composite_depth_kernel
 //   which splat a pixel shows (no reference part)               -> msplat_ids.hip.h       composite_ids_kernel, mark_ids_kernel
 //   what each splat contributes (no reference part)             -> msplat_scores.hip.h    composite_scores_kernel, mark_scores_kernel
+//   splats tinted by class at render time (no reference part)   -> msplat_overlay.hip.h   overlay_kernel, overlay_classes_kernel
 //   GaussianCloud::ImportPly's per-vertex math, storage order   -> msplat_cloud.hip.h     ingest_kernel, morton / gather / cull boxes
 //   a mask or crop made permanent (no reference part)          -> msplat_compact.hip.h   compact_* (flags, count, offsets, index, gather)
 //   splats moved, rotated, scaled in the store (no ref. part)   -> msplat_transform.hip.h transform_kernel
@@ -32,5 +33,6 @@
 #include "msplat_composite.hip.h"
 #include "msplat_ids.hip.h"
 #include "msplat_scores.hip.h"
+#include "msplat_overlay.hip.h"
 #include "msplat_points.hip.h"
 #include "msplat_occlusion.hip.h"

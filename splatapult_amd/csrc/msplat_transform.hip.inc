@@ -111,8 +111,10 @@ int msplat_transform_cloud(msplat_ctx* ctx, const float M[16], const uint8_t* d_
     const bool had_mask = ctx->has_mask;
     const Buf mask = ctx->vis_mask;
     ctx->vis_mask = Buf{};
+    const OverlayKept ov = overlay_take(ctx);      // (the overlay's classes likewise: a dragged selection stays tinted)
     rc = prepare_cloud_buffers(ctx, N, full_sh, st);
     ctx->vis_mask = mask;
+    ctx->ov_cls = ov.cls;
     if (ctx->store == st) ctx->device_bytes += need_pos + need_rec;
     if (rc) return rc;
     if ((rc = spatial_reorder(ctx))) return rc;
@@ -121,6 +123,7 @@ int msplat_transform_cloud(msplat_ctx* ctx, const float M[16], const uint8_t* d_
         ctx->has_mask = true;
         ctx->vis_dirty = true;
     }
+    if ((rc = overlay_restore(ctx, ov, N, 0))) return rc;
     ctx->has_cloud = true;
     return MSPLAT_OK;
 }

@@ -100,6 +100,10 @@ static int prepare_cloud_buffers(msplat_ctx* ctx, uint64_t n, bool full_sh, cons
     // by the next Sort (the stream is idle: the buffers may be freed)
     ctx->has_mask = ctx->vis_sorted = false;
     buf_free(ctx, ctx->vis_mask);
+    // the overlay: the classes speak the old numbering too and go with the mask; the palette stays
+    ctx->has_classes = ctx->overlay_dirty = false;
+    buf_free(ctx, ctx->ov_cls);
+    buf_free(ctx, ctx->ov_slot);
     if (ctx->crop_shape != 0 && !ctx->point_mode) {
         int rc_v = vis_alloc(ctx);
         if (rc_v) return rc_v;

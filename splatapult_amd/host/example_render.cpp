@@ -3,7 +3,7 @@
 // Sort + Render into an explicit RGBA32F framebuffer, dumped as a binary PPM-like float file.
 //
 //   g++ -std=c++17 -I. splatapult_amd/host/example_render.cpp -Lsplatapult_amd/lib -lmsplat -o example_render
-//   ./example_render scene.ply out.f32 [width height] [--nosh] [--frames-in-flight N] [--devices 0,1,2,...] [--over-gradient] [--depth out_depth.f32] [--srgb8 out.png] [--crop-sphere cx cy cz r] [--pick X,Y] [--min-score S] [--compact] [--append OTHER.ply] [--save OUT.ply]
+//   ./example_render scene.ply out.f32 [width height] [--nosh] [--frames-in-flight N] [--devices 0,1,2,...] [--over-gradient] [--depth out_depth.f32] [--srgb8 out.png] [--crop-sphere cx cy cz r] [--pick X,Y] [--min-score S] [--highlight R,G,B,A] [--compact] [--append OTHER.ply] [--save OUT.ply]
 // With --frames-in-flight N the same frame is issued N + 1 times round-robin over N contexts that share the cloud
 // (SplatRenderer::SetFramesInFlight); the last one is written.  With --devices the frame's bin rows are dealt to the
 // listed GPUs (SplatRenderer::ConfigureDevices, msplat_group_*): same pixels.  With --over-gradient the target is first filled with
@@ -20,6 +20,9 @@
 // With --min-score S the rendered view is scored (SplatRenderer::RenderScores), every splat that contributes less than S fully covered
 // pixels to it is hidden (MarkScores below S * MSPLAT_SCORE_ONE into a mask of ones, SetVisibilityDevice), and the frame is sorted and
 // rendered again: what is written is the pruned view; the number of hidden splats is printed.  One device, one frame in flight.
+// With --highlight R,G,B,A (the record's colour space: linear values, A in [0, 1]) nothing is hidden: --min-score then TINTS the splats it
+// selects and --pick the picked splat (SplatRenderer::SetOverlayPalette + SetOverlayDevice / SetOverlay, msplat_set_overlay*: class 1 of a
+// two-entry palette) and the frame is rendered again -- without another Sort: the overlay changes the projected records, not the cloud.
 // With --compact, after --min-score / --crop-sphere, the hidden splats are dropped for good (SplatRenderer::CompactCloud,
 // msplat_compact_cloud: the kept records gathered into a new store on the device), the splat counts before and after are printed and
 // the frame is sorted and rendered once more from the smaller cloud: the same pixels.  One device only.
@@ -70,6 +73,7 @@ int main(int argc, char** argv)
     int inFlight = 1;
     int pickX = -1, pickY = -1;      // --pick: print the splat under this pixel (row 0 = bottom) and its window depth
     double minScore = -1.0;          // --min-score: hide the splats that contribute less than this many pixels, render again
+    float highlight[8] = {0, 0, 0, 0, 0, 0, 0, -1.0f};      // --highlight: palette entry 0 (no effect) and entry 1; A < 0: not given
     const char* depthPath = nullptr;
     const char* srgb8Path = nullptr;
     const char* appendPath = nullptr;
@@ -89,6 +93,9 @@ int main(int argc, char** argv)
         if (!std::strcmp(argv[i], "--append") && i + 1 < argc) appendPath = argv[i + 1];
         if (!std::strcmp(argv[i], "--save") && i + 1 < argc) savePath = argv[i + 1];
         if (!std::strcmp(argv[i], "--min-score") && i + 1 < argc) minScore = std::atof(argv[i + 1]);
+        if (!std::strcmp(argv[i], "--highlight") && i + 1 < argc &&
+            std::sscanf(argv[i + 1], "%f,%f,%f,%f", &highlight[4], &highlight[5], &highlight[6], &highlight[7]) != 4)
+            highlight[7] = -1.0f;
         if (!std::strcmp(argv[i], "--devices") && i + 1 < argc)
             for (const char* p = argv[i + 1]; *p;) {
                 devices.push_back(std::atoi(p));
@@ -159,31 +166,46 @@ int main(int argc, char** argv)
         else renderer.Render(cameraMat, projMat, viewport, nearFar);
     }
     renderer.Synchronize();
+    const bool tint = highlight[7] >= 0.0f && inFlight == 1 && devices.size() <= 1;
     if (pickX >= 0 && pickY >= 0) {
         uint32_t index = MSPLAT_ID_NONE;
         float zw = 1.0f;
         if (!renderer.Pick(cameraMat, projMat, viewport, nearFar, pickX, pickY, &index, &zw)) return 1;
         if (index == MSPLAT_ID_NONE) std::printf("pick (%d, %d): no splat, z_w %.9g\n", pickX, pickY, zw);
         else std::printf("pick (%d, %d): splat %u, z_w %.9g\n", pickX, pickY, index, zw);
+        if (tint && index != MSPLAT_ID_NONE && minScore < 0.0) {
+            std::vector<uint8_t> classes(cloud->GetNumGaussians(), 0);
+            if (index < classes.size()) classes[index] = 1;
+            if (!renderer.SetOverlayPalette(highlight, 2) || !renderer.SetOverlay(classes.data(), classes.size())) return 1;
+            if (depthPath) renderer.RenderWithDepth(cameraMat, projMat, viewport, nearFar, depth.data());      // the latest Sort: no new one
+            else renderer.Render(cameraMat, projMat, viewport, nearFar);
+            renderer.Synchronize();
+            std::printf("splat %u highlighted\n", index);
+        }
     }
     if (minScore >= 0.0 && inFlight == 1 && devices.size() <= 1) {
         const size_t n = cloud->GetNumGaussians();
         DeviceMemory dm;
         void *score = nullptr, *mask = nullptr;
         if (!dm.Load() || dm.alloc(&score, n * 8) != 0 || dm.alloc(&mask, n) != 0) return 1;
-        if (dm.fill(score, 0, n * 8) != 0 || dm.fill(mask, 1, n) != 0 || dm.wait() != 0) return 1;      // filled before the context's stream starts
+        if (dm.fill(score, 0, n * 8) != 0 || dm.fill(mask, tint ? 0 : 1, n) != 0 || dm.wait() != 0) return 1;      // filled before the context's stream starts
         if (!renderer.RenderScores(cameraMat, projMat, viewport, nearFar, nullptr, static_cast<uint64_t*>(score), n)) return 1;
         if (!renderer.MarkScores(static_cast<const uint64_t*>(score), n, MSPLAT_SCORE_BELOW, (uint64_t)(minScore * (double)MSPLAT_SCORE_ONE),
-                                 static_cast<uint8_t*>(mask), 0))
+                                 static_cast<uint8_t*>(mask), tint ? 1 : 0))
             return 1;
-        if (!renderer.SetVisibilityDevice(static_cast<const uint8_t*>(mask), n)) return 1;
-        renderer.Sort(cameraMat, projMat, viewport, nearFar);
+        // hidden (a mask of ones with zeros marked: the next Sort drops them), or shown: classes of zeros with ones marked, tinted by the
+        // palette's entry 1 at the next Render
+        if (tint ? !(renderer.SetOverlayPalette(highlight, 2) && renderer.SetOverlayDevice(static_cast<const uint8_t*>(mask), n))
+                 : !renderer.SetVisibilityDevice(static_cast<const uint8_t*>(mask), n))
+            return 1;
+        if (!tint) renderer.Sort(cameraMat, projMat, viewport, nearFar);
         if (depthPath) renderer.RenderWithDepth(cameraMat, projMat, viewport, nearFar, depth.data());
         else renderer.Render(cameraMat, projMat, viewport, nearFar);
         renderer.Synchronize();
         uint64_t hidden = 0;
         if (msplat_get_visibility(renderer.GetContext(), nullptr, nullptr, &hidden) != MSPLAT_OK) return 1;
-        std::printf("min score %g: %llu of %zu splats hidden\n", minScore, (unsigned long long)hidden, n);
+        if (tint) std::printf("min score %g: the splats below it are highlighted\n", minScore);
+        else std::printf("min score %g: %llu of %zu splats hidden\n", minScore, (unsigned long long)hidden, n);
         dm.release(score);
         dm.release(mask);
     }

@@ -328,6 +328,30 @@ public:
     bool SetVisibility(const uint8_t* visible, size_t n) { return SetMask(visible, n, false); }
     // the mask in memory of the renderer's device: read asynchronously on each context's stream, valid until Synchronize()
     bool SetVisibilityDevice(const uint8_t* d_visible, size_t n) { return SetMask(d_visible, n, true); }
+    // render-time overlay (msplat_set_overlay* / msplat_set_overlay_palette; on every context of the rotation): splat i (upload numbering)
+    // of class classes[i] = k is shown tinted by palette entry k = (h_r, h_g, h_b, a), lane by lane c' = (1 - a) c + a h; a class >= count
+    // or an entry with a == 0 has no effect; nullptr = no classes.  Shows at the next Render, no Sort needed.  Set the classes after Init;
+    // an upload and CompactCloud drop them, TransformCloud / AppendCloud keep context 0's and drop those of the contexts they attach again:
+    // with frames in flight call SetOverlay[Device] again afterwards.  A device group has no overlay (out of scope): false.
+    bool SetOverlay(const uint8_t* classes, size_t n) { return SetClasses(classes, n, false); }
+    // the classes in memory of the renderer's device (what MarkIds / MarkScores wrote): read asynchronously on each context's stream, valid until Synchronize()
+    bool SetOverlayDevice(const uint8_t* d_classes, size_t n) { return SetClasses(d_classes, n, true); }
+    // count <= 256 entries of 4 floats; nullptr or 0 = no palette.  May come before Init: it is kept and handed to every context created later
+    bool SetOverlayPalette(const float* rgba, uint32_t count)
+    {
+        if (group) {
+            std::fprintf(stderr, "[msplat][E] SetOverlayPalette: a device group has no overlay\n");
+            return false;
+        }
+        if (!rgba) count = 0;
+        for (msplat_ctx* h : ctxs)
+            if (msplat_set_overlay_palette(h, rgba, count) != MSPLAT_OK) {
+                std::fprintf(stderr, "[msplat][E] SetOverlayPalette: %s\n", msplat_last_error(h));
+                return false;
+            }
+        overlayPalette.assign(rgba, rgba + 4 * (size_t)count);
+        return true;
+    }
     // crop volume: worldToCrop (column-major, affine) and MSPLAT_CROP_BOX / _SPHERE, | MSPLAT_CROP_INVERT; nullptr or MSPLAT_CROP_NONE = none
     bool SetCrop(const float* worldToCrop, int shape)
     {
@@ -581,6 +605,11 @@ protected:
             std::fprintf(stderr, "[msplat][E] %s\n", msplat_last_error(ctx));
             return false;
         }
+        for (msplat_ctx* h : ctxs)           // the overlay's palette outlives the contexts (SetOverlayPalette)
+            if (!overlayPalette.empty() && msplat_set_overlay_palette(h, overlayPalette.data(), (uint32_t)(overlayPalette.size() / 4)) != MSPLAT_OK) {
+                std::fprintf(stderr, "[msplat][E] %s\n", msplat_last_error(h));
+                return false;
+            }
         return true;
     }
 
@@ -653,6 +682,21 @@ protected:
         return true;
     }
 
+    // SetOverlay / SetOverlayDevice: the classes on every context of the rotation
+    bool SetClasses(const uint8_t* classes, size_t n, bool onDevice)
+    {
+        if (group) {
+            std::fprintf(stderr, "[msplat][E] SetOverlay: a device group has no overlay\n");
+            return false;
+        }
+        for (msplat_ctx* h : ctxs)
+            if ((onDevice ? msplat_set_overlay_device(h, classes, n) : msplat_set_overlay(h, classes, n)) != MSPLAT_OK) {
+                std::fprintf(stderr, "[msplat][E] SetOverlay: %s\n", msplat_last_error(h));
+                return false;
+            }
+        return true;
+    }
+
     // SetVisibility / SetVisibilityDevice: the mask on every context of the rotation
     bool SetMask(const uint8_t* mask, size_t n, bool onDevice)
     {
@@ -709,6 +753,7 @@ protected:
     int cur = 0;
     int framesInFlight = 1;
     int cloudStorage = MSPLAT_STORAGE_FP32;
+    std::vector<float> overlayPalette;   // SetOverlayPalette's entries, for the contexts Init creates
     msplat_config cfg{sizeof(msplat_config), 0, MSPLAT_FB_RGBA32F, 0, -1.0f, 0, nullptr, 0, 0, 0, 0};
     void* target = nullptr;
     uint64_t targetPitch = 0;

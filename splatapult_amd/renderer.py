@@ -119,6 +119,9 @@ _LIVES = {"depth": ("the depth plane lives in the colour's memory space: pass de
                      "the planes live in the colour's memory space: pass depth= / occluder= with host output")}
 
 
+_KEEP = object()        # SetOverlay: an argument left out stays as it is
+
+
 class SplatRenderer:
     def __init__(self, device=0, fb_format="fp32", t_epsilon=-1.0, pair_capacity=0, stream=None,
                  enable_timing=False, frames_in_flight=1, rank_mode=_capi.RANK_AUTO, frame_mode=None,
@@ -163,6 +166,8 @@ class SplatRenderer:
         self._frame_mode = int(frame_mode) if frame_mode is not None else (_capi.FRAMES_IN_FLIGHT if self._depth > 1 else _capi.FRAMES_AUTO)
         self._n = 0
         self._load = False                     # set_target_mode("load"): a host Render needs the destination in out=
+        self._ov_arg = None                    # SetOverlay's classes, for the contexts TransformCloud / AppendCloud attach again
+        self._ov_palette = None                # ... and its palette, which new contexts (Init*) receive again
 
     def __del__(self):
         self.close()
@@ -232,6 +237,12 @@ class SplatRenderer:
                 self._err = self._lib.msplat_last_error(h).decode()
                 self.close()
                 return False
+        if self._ov_palette is not None:     # the overlay's palette outlives the contexts (SetOverlay)
+            for h in self._ctxs:
+                if self._lib.msplat_set_overlay_palette(h, self._ov_palette.ctypes.data, self._ov_palette.shape[0]) != _capi.OK:
+                    self._err = self._lib.msplat_last_error(h).decode()
+                    self.close()
+                    return False
         return True
 
     def _attach_all(self):
@@ -603,6 +614,88 @@ class SplatRenderer:
         crop = None if b.value == _capi.CROP_NONE else (names[b.value & ~_capi.CROP_INVERT], bool(b.value & _capi.CROP_INVERT))
         return dict(has_mask=bool(a.value), crop=crop, hidden=int(h.value))
 
+    # -- render-time overlay (msplat_set_overlay* / msplat_set_overlay_palette) -------
+    def SetOverlay(self, classes=_KEEP, palette=_KEEP):
+        """Tint splats by class at render time, without touching the cloud: splat i (upload numbering) of class classes[i] = k is
+        shown with each colour lane c of its projected record replaced by (1 - a) c + a h, (h_r, h_g, h_b, a) = palette[k]; a class
+        >= len(palette) or an entry with a == 0 has no effect; the exact fp32 rule is msplat.h's.  Shows at the next Render, no Sort
+        needed.  classes: N values, numpy uint8 / bool (copied before the call returns), or an object with data_ptr() that lives on
+        the device -- a torch uint8 / bool tensor on this renderer's device, e.g. the array MarkIds / MarkScores wrote, read
+        asynchronously on each context's stream: keep it alive and unchanged until synchronize() -- or None for no classes.
+        palette: (count, 4) floats, count <= 256, finite, a in [0, 1], or None for no palette.  An argument left out stays as it is.
+        Set on every context of the frames-in-flight rotation.  An upload (Init*, Update*) and CompactCloud drop the classes and keep
+        the palette (Init* hands it to the new contexts); TransformCloud and AppendCloud keep the classes and hand the remembered
+        argument to the contexts they attach again -- AppendCloud extended by K values of class 0 -- so a device-tensor argument must
+        still hold the classes at that point.  ValueError for a wrong length, shape or dtype, before the library is called."""
+        if palette is not _KEEP and palette is not None:
+            palette = np.ascontiguousarray(np.asarray(palette, dtype=np.float32))
+            if palette.ndim != 2 or palette.shape[1] != 4 or palette.shape[0] > 256:
+                raise ValueError("the palette must have shape (count, 4) with count <= 256, not %s" % (palette.shape,))
+            if not np.isfinite(palette).all() or (palette[:, 3] < 0).any() or (palette[:, 3] > 1).any():
+                raise ValueError("the palette must be finite with a in [0, 1]")
+        if classes is _KEEP:
+            args = fn = None
+        elif classes is None:
+            args, fn = (None, 0), self._lib.msplat_set_overlay
+        elif hasattr(classes, "data_ptr"):
+            if str(classes.dtype).split(".")[-1] not in ("bool", "uint8"):
+                raise ValueError("the classes must be uint8 or bool, not %s" % classes.dtype)
+            if tuple(int(s) for s in classes.shape) != (self._n,):
+                raise ValueError("the classes must have shape (%d,), one value per splat, not %s" % (self._n, tuple(classes.shape)))
+            if not classes.is_contiguous():
+                raise ValueError("the classes must be contiguous (pass classes.contiguous())")
+            if getattr(classes.device, "type", "cuda") not in ("cuda", "hip"):
+                raise ValueError("classes with data_ptr() must live in device memory, not on %s (pass classes.numpy())" % classes.device)
+            import sys
+            torch = sys.modules.get("torch")
+            if torch is not None and isinstance(classes, torch.Tensor):
+                torch.cuda.current_stream(classes.device).synchronize()    # what produced the tensor has completed
+            args, fn = (C.c_void_p(int(classes.data_ptr())), self._n), self._lib.msplat_set_overlay_device
+        else:
+            if not isinstance(classes, np.ndarray) or classes.dtype not in (np.bool_, np.uint8):
+                raise ValueError("the classes must be a numpy uint8 / bool array, a device tensor or None, not %s %s"
+                                 % (type(classes).__name__, getattr(classes, "dtype", "")))
+            if classes.shape != (self._n,):
+                raise ValueError("the classes must have shape (%d,), one value per splat, not %s" % (self._n, classes.shape))
+            classes = np.ascontiguousarray(classes)
+            args, fn = (classes.ctypes.data, self._n), self._lib.msplat_set_overlay
+        if fn is not None and classes is not None and not self._ctxs:
+            raise _capi.MsplatError(_capi.ERR_NO_CLOUD, "SetOverlay: no cloud (Init first)")
+        if palette is not _KEEP:
+            for h in self._ctxs:
+                _capi.check(h, self._lib.msplat_set_overlay_palette(h, None if palette is None else palette.ctypes.data,
+                                                                    0 if palette is None else palette.shape[0]))
+            self._ov_palette = palette
+        if fn is not None:
+            for h in self._ctxs:
+                _capi.check(h, fn(h, *args))
+            self._ov_arg = classes
+
+    def overlay(self):
+        """dict(has_classes, palette_count, active) of the current context (msplat_get_overlay)"""
+        a, b, c = C.c_int32(), C.c_uint32(), C.c_int32()
+        _capi.check(self._ctx, self._lib.msplat_get_overlay(self._ctx, C.byref(a), C.byref(b), C.byref(c)))
+        return dict(has_classes=bool(a.value), palette_count=int(b.value), active=bool(c.value))
+
+    def _overlay_again(self, classed, added=0):
+        """the contexts TransformCloud / AppendCloud attached again receive the remembered classes, `added` values of class 0 longer"""
+        ov = self._ov_arg
+        if not classed or ov is None:
+            return
+        if added:
+            if hasattr(ov, "data_ptr"):
+                import torch
+                ov = torch.cat([ov.to(torch.uint8), torch.zeros(added, dtype=torch.uint8, device=ov.device)])
+            else:
+                ov = np.concatenate([ov.view(np.uint8), np.zeros(added, np.uint8)])
+        ctxs, self._ctxs = self._ctxs, self._ctxs[1:]
+        try:
+            if self._ctxs:
+                self.SetOverlay(ov)
+            self._ov_arg = ov
+        finally:
+            self._ctxs = ctxs
+
     def CompactCloud(self, index_map=False):
         """Make the mask and the crop permanent, on the device (msplat_compact_cloud): the cloud becomes the K
         splats SetVisibility's mask and SetCrop's volume let through, renumbered 0..K-1 in ascending old index, their records
@@ -675,8 +768,9 @@ class SplatRenderer:
         sel = self._device_select(select, self._n)
         self.synchronize()
         own = self._ctxs[0]
-        masked = C.c_int32()
+        masked, classed = C.c_int32(), C.c_int32()
         _capi.check(own, self._lib.msplat_get_visibility(own, C.byref(masked), None, None))
+        _capi.check(own, self._lib.msplat_get_overlay(own, C.byref(classed), None, None))
         _capi.check(own, self._lib.msplat_transform_cloud(own, m.ctypes.data_as(C.POINTER(C.c_float)), sel, self._n,
                                                           _capi.TRANSFORM_KEEP_SH if keep_sh else 0))
         self._ctx = own
@@ -689,6 +783,7 @@ class SplatRenderer:
                 self.SetVisibility(self._vis_arg)
             finally:
                 self._ctxs = ctxs
+        self._overlay_again(classed.value)
 
     def AppendCloud(self, src, select=None, index_map=False):
         """Put splats into the cloud on the device (msplat_append_cloud): every splat i of src -- another
@@ -716,8 +811,9 @@ class SplatRenderer:
             import torch
             m = torch.empty(max(ns, 1), dtype=torch.int32, device=torch.device("cuda", self._device))
             torch.cuda.current_stream(m.device).synchronize()
-        k, masked = C.c_uint64(), C.c_int32()
+        k, masked, classed = C.c_uint64(), C.c_int32(), C.c_int32()
         _capi.check(own, self._lib.msplat_get_visibility(own, C.byref(masked), None, None))
+        _capi.check(own, self._lib.msplat_get_overlay(own, C.byref(classed), None, None))
         _capi.check(own, self._lib.msplat_append_cloud(own, src._ctxs[0], sel, ns, C.c_void_p(m.data_ptr()) if m is not None else None,
                                                        C.byref(k)))
         self._select_arg = None
@@ -740,6 +836,7 @@ class SplatRenderer:
                 self._vis_arg = vis
             finally:
                 self._ctxs = ctxs
+        self._overlay_again(classed.value, int(k.value))
         return int(k.value), (m[:ns] if index_map else None)
 
     # -- which splat each pixel shows (msplat_render_ids / msplat_mark_ids) -----------

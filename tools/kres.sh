@@ -2,7 +2,7 @@
 # usage: tools/kres.sh [name filter regex]: compiles msplat_device.hip for gfx950 with -Rpass-analysis=kernel-resource-usage and
 # prints VGPRs / SGPRs / spills / scratch / occupancy / LDS of the kernels whose demangled name matches (no GPU needed)
 cd "$(dirname "$0")/.."
-F=${1:-composite_kernel|project_kernel}
+F=${1:-composite_kernel|project_kernel|overlay_}
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -c -Rpass-analysis=kernel-resource-usage \
     splatapult_amd/csrc/msplat_device.hip -o /tmp/kres_dev.o 2> /tmp/kres.txt || { grep -E "error" -A5 /tmp/kres.txt | head -60; exit 1; }
 python3 - "$F" <<'PY'
