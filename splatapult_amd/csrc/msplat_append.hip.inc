@@ -2,12 +2,12 @@
 // context's own; kernels in msplat_append.hip.h, the scan in msplat_compact.hip.h
 // (textually part of msplat_device.hip: included inside its extern "C" block, after msplat_transform.hip.inc)
 //
-// The compaction's and the transform's shape: an upload whose source is two stores.  Flags, count, offsets and index rank the
-// selected source splats, the host reads K (and refuses N + K > 2^24 with nothing allocated), the context's own rows and the selected
-// source rows go into a FRESH store of N + K rows in upload order, the host reads the pack routines' counter, and from there on the
-// path is an upload's: prepare_cloud_buffers adopting that store, spatial_reorder, has_cloud.  Until the swap the context renders what
-// it rendered before, so every failure up to there leaves it alone.  The old numbering is a prefix of the new one: the mask is
-// carried across prepare_cloud_buffers, K visible bytes longer, and the visibility plane marked stale.
+// The compaction's and the transform's shape: an upload whose source is two stores.  The selection scan (msplat_edit.hip.inc) behind
+// append_flags_kernel ranks the selected source splats and gives the host K (N + K > 2^24 is refused with nothing allocated), the
+// context's own rows and the selected source rows go into a FreshStore of N + K rows in upload order, the host reads the pack
+// routines' counter, and fresh_adopt makes it the context's cloud; every failure up to there leaves the cloud alone.  The old
+// numbering is a prefix of the new one: the mask and the overlay's classes stay (KeptPlanes), K visible bytes / K bytes of class 0
+// longer, both built before the swap.
 
 int msplat_append_cloud(msplat_ctx* ctx, msplat_ctx* src, const uint8_t* d_select, uint64_t n, uint32_t* d_index_map, uint64_t* n_added_out)
 {
@@ -31,11 +31,7 @@ int msplat_append_cloud(msplat_ctx* ctx, msplat_ctx* src, const uint8_t* d_selec
         return fail(ctx, MSPLAT_ERR_INVALID_ARG, "%s: n = %llu for a source of %llu splats", who, (unsigned long long)n, (unsigned long long)Ns);
     int rc;
     if (d_select && Ns && (rc = check_device_source(ctx, who, "d_select", d_select, Ns))) return rc;
-    if (d_index_map) {
-        if ((uintptr_t)d_index_map % 4 != 0)
-            return fail(ctx, MSPLAT_ERR_INVALID_ARG, "%s: d_index_map (%p) is not 4-byte aligned", who, (const void*)d_index_map);
-        if (Ns && (rc = check_device_source(ctx, who, "d_index_map", d_index_map, Ns * 4))) return rc;
-    }
+    if ((rc = check_index_map(ctx, who, d_index_map, Ns))) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (src != ctx) HIP_TRY(ctx, hipStreamSynchronize(src->stream));
@@ -48,80 +44,46 @@ int msplat_append_cloud(msplat_ctx* ctx, msplat_ctx* src, const uint8_t* d_selec
     const bool full_sh = ctx->full_sh;
     hipStream_t s = ctx->stream;
 
-    // the scratch of one call: flags padded to whole chunks | chunk counts | K | the ranks
-    const uint32_t ns = (uint32_t)Ns, nchunks = div_up(Ns, kCompactChunk);
-    const size_t flag_bytes = (size_t)nchunks * kCompactChunk, count_off = flag_bytes, total_off = count_off + (size_t)nchunks * 4;
-    const size_t rank_off = (total_off + 4 + 15) & ~(size_t)15;
-    Buf tmp, nmask;
-    uint32_t K = 0;
-    const uint32_t* rank = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    const bool timed = ctx->cfg.enable_timing > 0 && hipEventCreate(&ev[0]) == hipSuccess && hipEventCreate(&ev[1]) == hipSuccess;
-    ctx->upload_kernel_ms = -1.0f;
-    auto done = [&](int code) {
-        for (hipEvent_t v : ev)
-            if (v) (void)hipEventDestroy(v);
-        ev[0] = ev[1] = nullptr;
-        buf_free(ctx, tmp);
-        return code;
-    };
+    KernelTimer timer(ctx);
+    SelectionScan sc(ctx);
+    const uint32_t ns = (uint32_t)Ns;
     if (Ns) {
-        if ((rc = buf_alloc(ctx, tmp, rank_off + (size_t)Ns * 4))) return done(rc);
-        uint8_t* flags = (uint8_t*)tmp.p;
-        uint32_t* counts = (uint32_t*)((char*)tmp.p + count_off);
-        uint32_t* total = (uint32_t*)((char*)tmp.p + total_off);
-        uint32_t* rank_out = (uint32_t*)((char*)tmp.p + rank_off);
-        rank = rank_out;
-        const int gchunks = grid_for(nchunks, ctx->grid_cap);
-        hipLaunchKernelGGL(append_flags_kernel, dim3(gchunks), dim3(kThreads), 0, s, d_select, ns, nchunks, flags);
-        hipLaunchKernelGGL(compact_count_kernel, dim3(gchunks), dim3(kThreads), 0, s, (const uint8_t*)flags, nchunks, counts);
-        hipLaunchKernelGGL(compact_offsets_kernel, dim3(1), dim3(kThreads), 0, s, counts, nchunks, total);
-        hipLaunchKernelGGL(compact_index_kernel, dim3(gchunks), dim3(kThreads), 0, s, (const uint8_t*)flags, (const uint32_t*)counts, ns,
-                           nchunks, rank_out);
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(&K, total, 4, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) return done(fail(ctx, MSPLAT_ERR_HIP, "%s: numbering the selected splats failed: %s", who, hipGetErrorString(e)));
+        if ((rc = scan_reserve(sc, Ns, nullptr))) return rc;
+        hipLaunchKernelGGL(append_flags_kernel, dim3(grid_for(sc.nchunks, ctx->grid_cap)), dim3(kThreads), 0, s, d_select, ns, sc.nchunks, sc.flags);
+        if ((rc = scan_number(sc, who, "selected", hipSuccess))) return rc;
     }
+    const uint32_t K = sc.K;
+    const uint32_t* rank = sc.rank;
     const uint64_t total_n = N + K;
     if (total_n > (1ull << 24))       // (check_splat_count's limit, before anything is allocated or the caller's map written)
-        return done(fail(ctx, MSPLAT_ERR_UNSUPPORTED, "%s: %llu + %u splats > 2^24 (rank field is 24 bit); the cloud is unchanged", who,
-                         (unsigned long long)N, K));
+        return fail(ctx, MSPLAT_ERR_UNSUPPORTED, "%s: %llu + %u splats > 2^24 (rank field is 24 bit); the cloud is unchanged", who,
+                    (unsigned long long)N, K);
 
-    // the new store, never an old allocation: until the swap below the context renders what it rendered before
-    const size_t alloc_n = std::max<uint64_t>(total_n, 1), need_pos = alloc_n * 16, need_rec = alloc_n * F4 * 16;
-    const bool had_mask = ctx->has_mask;
-    void *npos = nullptr, *nrec = nullptr, *d_over = nullptr;
+    FreshStore fs;
+    KeptPlanes kept(ctx);
     uint32_t n_over = 0;
-    hipError_t e = hipMalloc(&npos, need_pos);
-    if (e == hipSuccess) e = hipMalloc(&nrec, need_rec);
-    if (e == hipSuccess) e = hipMalloc(&d_over, 16);
-    if (e == hipSuccess) e = hipMemsetAsync(d_over, 0, 4, s);
-    if (e == hipSuccess && had_mask) {      // the mask of the merged cloud: the old bytes, then K visible ones
-        if (buf_alloc(ctx, nmask, alloc_n)) e = hipErrorOutOfMemory;
-        if (e == hipSuccess && N) e = hipMemcpyAsync(nmask.p, ctx->vis_mask.p, N, hipMemcpyDeviceToDevice, s);
-        if (e == hipSuccess && K) e = hipMemsetAsync((char*)nmask.p + N, 1, K, s);
-    }
+    hipError_t e = fresh_alloc(ctx, fs, total_n, F4, storage, true);
+    if (e == hipSuccess) e = kept_grow(kept, N, K);
     if (e == hipSuccess) {
-        if (timed) (void)hipEventRecord(ev[0], s);
+        float4 *npos = (float4*)fs.st->pos4.p, *nrec = (float4*)fs.st->recs.p;
+        timer.start(s);
         if (N)      // the context's own rows, storage order -> upload order
             hipLaunchKernelGGL(append_gather_kernel, dim3(grid_for(div_up(N * (uint64_t)F4, kThreads), ctx->grid_cap)), dim3(kThreads), 0, s,
                                (const uint32_t*)nullptr, old->reordered ? (const uint32_t*)old->order_dev.p : nullptr, (uint32_t)N, 0u, F4,
-                               (const float4*)old->pos4.p, (const float4*)old->recs.p, (float4*)npos, (float4*)nrec);
+                               (const float4*)old->pos4.p, (const float4*)old->recs.p, npos, nrec);
         const uint32_t* sorder = from->reordered ? (const uint32_t*)from->order_dev.p : nullptr;
         if (K && sstorage == storage) {
             hipLaunchKernelGGL(append_gather_kernel, dim3(grid_for(div_up(Ns * (uint64_t)sF4, kThreads), ctx->grid_cap)), dim3(kThreads), 0, s,
-                               rank, sorder, ns, (uint32_t)N, sF4, (const float4*)from->pos4.p, (const float4*)from->recs.p, (float4*)npos,
-                               (float4*)nrec);
+                               rank, sorder, ns, (uint32_t)N, sF4, (const float4*)from->pos4.p, (const float4*)from->recs.p, npos, nrec);
         } else if (K) {
             AppendConvertArgs a;
             a.pos_in = (const float4*)from->pos4.p;
             a.recs_in = (const float4*)from->recs.p;
             a.order = sorder;
             a.rank = rank;
-            a.pos_out = (float4*)npos;
-            a.recs_out = (float4*)nrec;
-            a.n_over = (uint32_t*)d_over;
+            a.pos_out = npos;
+            a.recs_out = nrec;
+            a.n_over = fs.d_over;
             a.n = ns;
             a.base = (uint32_t)N;
             const int grid = grid_for(div_up(Ns, 64), ctx->grid_cap);
@@ -136,35 +98,16 @@ int msplat_append_cloud(msplat_ctx* ctx, msplat_ctx* src, const uint8_t* d_selec
             });
         }
         e = hipGetLastError();
-        if (timed) (void)hipEventRecord(ev[1], s);
-        if (e == hipSuccess) e = hipMemcpyAsync(&n_over, d_over, 4, hipMemcpyDeviceToHost, s);
+        timer.stop(s);
+        if (e == hipSuccess) e = hipMemcpyAsync(&n_over, fs.d_over, 4, hipMemcpyDeviceToHost, s);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    // (the gathers and the conversion between two stream events: msplat_debug_upload_kernel_ms)
-    if (e == hipSuccess && total_n && timed && hipEventElapsedTime(&ctx->upload_kernel_ms, ev[0], ev[1]) != hipSuccess) ctx->upload_kernel_ms = -1.0f;
-    if (d_over) (void)hipFree(d_over);
-    std::shared_ptr<CloudStore> st;
-    if (e == hipSuccess && !n_over) {
-        try {      // the C ABI never throws
-            st = std::make_shared<CloudStore>();
-        } catch (const std::exception&) {
-            e = hipErrorOutOfMemory;
-        }
-    }
-    if (e != hipSuccess || n_over) {
+    if (e == hipSuccess && total_n) timer.read(ctx);      // (the gathers and the conversion between two stream events: msplat_debug_upload_kernel_ms)
+    if (e != hipSuccess) {
         (void)hipGetLastError();
-        if (npos) (void)hipFree(npos);
-        if (nrec) (void)hipFree(nrec);
-        buf_free(ctx, nmask);
-        done(MSPLAT_OK);
-        if (e != hipSuccess)
-            return fail(ctx, MSPLAT_ERR_HIP, "%s: the store of the merged cloud could not be made: %s", who, hipGetErrorString(e));
-        if (storage == kStorageShQ8)
-            return fail(ctx, MSPLAT_ERR_UNSUPPORTED, "%s: %u appended f_rest values are not finite: MSPLAT_STORAGE_SH_Q8 cannot quantise "
-                        "them; the cloud is unchanged", who, n_over);
-        return fail(ctx, MSPLAT_ERR_UNSUPPORTED, "%s: %u appended f_rest values are beyond the fp16 range (|c| >= 65520) of "
-                    "MSPLAT_STORAGE_SH_FP16; the cloud is unchanged", who, n_over);
+        return fail(ctx, MSPLAT_ERR_HIP, "%s: the store of the merged cloud could not be made: %s", who, hipGetErrorString(e));
     }
+    if (n_over) return f_rest_failure(ctx, who, storage, n_over, "appended ", "; the cloud is unchanged");
     // the caller's map last of all that is launched: a call that fails has written nothing of the caller's
     if (d_index_map && Ns) {
         hipLaunchKernelGGL(append_map_kernel, dim3(grid_for(div_up(Ns, kThreads), ctx->grid_cap)), dim3(kThreads), 0, s, rank, ns, (uint32_t)N,
@@ -173,39 +116,11 @@ int msplat_append_cloud(msplat_ctx* ctx, msplat_ctx* src, const uint8_t* d_selec
         if (e == hipSuccess) e = hipStreamSynchronize(s);
         if (e != hipSuccess) {
             (void)hipGetLastError();
-            (void)hipFree(npos); (void)hipFree(nrec);
-            buf_free(ctx, nmask);
-            return done(fail(ctx, MSPLAT_ERR_HIP, "%s: writing the index map failed: %s", who, hipGetErrorString(e)));
+            return fail(ctx, MSPLAT_ERR_HIP, "%s: writing the index map failed: %s", who, hipGetErrorString(e));
         }
     }
-    done(MSPLAT_OK);
-    st->device = ctx->device;
-    st->pos4.p = npos; st->pos4.bytes = need_pos;
-    st->recs.p = nrec; st->recs.bytes = need_rec;
-    st->storage = storage;
-    st->F4 = F4;
-    // from here on an upload of N + K splats whose records are in place -- but for the mask: prepare_cloud_buffers frees the old one
-    // (the stream is idle), the extended one takes its place
-    const OverlayKept ov = overlay_take(ctx);      // (the overlay's classes stay as well; overlay_restore extends them by K bytes of class 0)
-    rc = prepare_cloud_buffers(ctx, total_n, full_sh, st);
-    ctx->ov_cls = ov.cls;
-    if (ctx->store == st) ctx->device_bytes += need_pos + need_rec;
-    if (rc) {
-        buf_free(ctx, nmask);
-        return rc;
-    }
-    if (had_mask) {      // (a member of the context since the mask was set: msplat_destroy knows it)
-        ctx->vis_mask.p = nmask.p;
-        ctx->vis_mask.bytes = nmask.bytes;
-    }
-    if ((rc = spatial_reorder(ctx))) return rc;
-    if (had_mask) {         // the plane, the boxes and the new store's order on the device, as set_mask leaves them
-        if ((rc = vis_alloc(ctx)) || (rc = ensure_order_dev(ctx))) return rc;
-        ctx->has_mask = true;
-        ctx->vis_dirty = true;
-    }
-    if ((rc = overlay_restore(ctx, ov, N, K))) return rc;
-    ctx->has_cloud = true;
+    buf_free(ctx, sc.tmp);
+    if ((rc = fresh_adopt(ctx, fs, total_n, full_sh, &kept))) return rc;
     if (n_added_out) *n_added_out = K;
     return MSPLAT_OK;
 }

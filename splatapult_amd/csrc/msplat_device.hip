@@ -71,6 +71,14 @@ struct CloudStore {
 
 inline uint32_t* words(const Buf& b) { return (uint32_t*)b.p; }
 
+// A pinned host buffer that host bytes go through on their way to the device, and the event behind the latest copy out of it: the
+// buffer is written again only after that copy has left it (stage_reserve / stage_send / stage_copy, msplat_edit.hip.inc)
+struct StagingSlot {
+    void* host = nullptr;
+    size_t bytes = 0;
+    hipEvent_t ev = nullptr;
+};
+
 // The tables of the 8-bit radix passes (msplat_sort.hip.h), each with the numbers its kernels are launched with.
 // HistTable: chunk-major histogram rows, uint32[256 * stride].  GroupTable (the scan-free path): per-group sums, one row of 256 per
 // 32 chunks, behind `sup` rows of supergroup sums; `rows` of them in all (alloc_group_table)
@@ -198,9 +206,7 @@ struct msplat_ctx {
     float crop_mat[16]{};
     bool vis_dirty = false;     // the plane is older than the mask, the crop or the cloud: the next Sort starts with visibility_kernel
     bool vis_sorted = false;    // the latest Sort read the context's plane and boxes
-    uint8_t* vis_stage = nullptr;       // pinned: what the latest host mask's copy reads ...
-    size_t vis_stage_bytes = 0;
-    hipEvent_t vis_stage_ev = nullptr;  // ... and the event behind that copy
+    StagingSlot vis_stage;      // what the latest host mask's copy reads
     // render-time overlay (msplat_set_overlay* / msplat_set_overlay_palette; msplat_overlay.hip.h): a class byte per splat and a palette
     // tint the projected records of the context's Renders.  Allocated by the set calls, never by a Render
     Buf ov_cls;                 // uint8[N], upload numbering: the caller's classes, copied on the stream
@@ -210,9 +216,7 @@ struct msplat_ctx {
     bool overlay_dirty = false; // ov_slot is older than the classes or the store's order: resolved by the next overlaid Render
     uint32_t ov_count = 0;      // palette entries the caller set ...
     bool ov_tints = false;      // ... and whether one of them has a != 0
-    uint8_t* ov_stage[2] = {nullptr, nullptr};       // pinned: what the latest host classes' / palette's copy reads ...
-    size_t ov_stage_bytes[2] = {0, 0};
-    hipEvent_t ov_stage_ev[2] = {nullptr, nullptr};  // ... and the events behind those copies
+    StagingSlot ov_stage[2];    // what the latest host classes' / palette's copy reads
     uint32_t sort_parity = 0;
     bool tables_dirty = false;  // a launch failed: clear every self-cleaning table before the next frame
     // per-bin pair counts taken by the row pass's upsweep (r3): list offsets + work order (no kernel of their own)
@@ -244,8 +248,7 @@ struct msplat_ctx {
     Buf tile_order; // uint32[65536] bins by descending list length, then uint32[65536] = 0, 1, 2, ... (storage order), then uint32[65536]
                     // = the XCD-local order persistent waves walk (msplat_bin_order.h), built for bin_order_tx x bin_order_rows bins
     int bin_order_tx = 0, bin_order_rows = 0;     // 0 x 0: none yet
-    uint32_t* bin_order_host = nullptr;      // pinned: what the latest upload of that table reads ...
-    hipEvent_t bin_order_ev = nullptr;       // ... and the event behind it
+    StagingSlot bin_order_stage;             // what the latest upload of that table reads
     const uint32_t* comp_order = nullptr;    // msplat_debug_get_bin_order: the table of the latest compositor launch and its bins
     uint32_t comp_order_bins = 0;
     HistTable hist1;      // column pass
@@ -691,6 +694,8 @@ int msplat_create(msplat_ctx** out, const msplat_config* cfg)
     return MSPLAT_OK;
 }
 
+static void stage_free(StagingSlot& sl);      // (msplat_edit.hip.inc)
+
 void msplat_destroy(msplat_ctx* ctx)
 {
     if (!ctx) return;
@@ -708,14 +713,7 @@ void msplat_destroy(msplat_ctx* ctx)
     ctx->store.reset();
     if (ctx->join_ev) (void)hipEventDestroy(ctx->join_ev);
     if (ctx->h_flags) (void)hipHostFree(ctx->h_flags);
-    if (ctx->bin_order_host) (void)hipHostFree(ctx->bin_order_host);
-    if (ctx->bin_order_ev) (void)hipEventDestroy(ctx->bin_order_ev);
-    if (ctx->vis_stage) (void)hipHostFree(ctx->vis_stage);
-    if (ctx->vis_stage_ev) (void)hipEventDestroy(ctx->vis_stage_ev);
-    for (int k = 0; k < 2; ++k) {
-        if (ctx->ov_stage[k]) (void)hipHostFree(ctx->ov_stage[k]);
-        if (ctx->ov_stage_ev[k]) (void)hipEventDestroy(ctx->ov_stage_ev[k]);
-    }
+    for (StagingSlot* sl : {&ctx->bin_order_stage, &ctx->vis_stage, &ctx->ov_stage[0], &ctx->ov_stage[1]}) stage_free(*sl);
     for (Buf* b : ctx->bufs) buf_free(ctx, *b);
     if (ctx->ev_ok)
         for (auto& set : ctx->ev)
@@ -925,6 +923,7 @@ int msplat_wait_event(msplat_ctx* ctx, void* event)
     return MSPLAT_OK;
 }
 
+#include "msplat_edit.hip.inc"
 #include "msplat_upload.hip.inc"
 
 #include "msplat_bands.hip.inc"
@@ -1470,17 +1469,11 @@ static void issue_binning(RenderChain& rc, int keep_overflow, int occ_pass)
 static int ensure_bin_order(msplat_ctx* ctx, int tiles_x, int rows, hipStream_t s)
 {
     if (ctx->bin_order_tx == tiles_x && ctx->bin_order_rows == rows) return MSPLAT_OK;
-    if (!ctx->bin_order_host) {
-        HIP_TRY(ctx, hipHostMalloc((void**)&ctx->bin_order_host, 65536 * sizeof(uint32_t), hipHostMallocDefault));
-        HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->bin_order_ev, hipEventDisableTiming));
-    } else {
-        HIP_TRY(ctx, hipEventSynchronize(ctx->bin_order_ev));      // the upload before this one has read the host copy (long ago)
-    }
-    bin_order_xcd(tiles_x, rows, kBinBlockW, kBinBlockH, ctx->bin_order_host);
+    int rc = stage_reserve(ctx, ctx->bin_order_stage, 65536 * sizeof(uint32_t));      // (the upload before this one read it long ago)
+    if (rc) return rc;
+    bin_order_xcd(tiles_x, rows, kBinBlockW, kBinBlockH, (uint32_t*)ctx->bin_order_stage.host);
     ctx->bin_order_tx = ctx->bin_order_rows = 0;
-    HIP_TRY(ctx, hipMemcpyAsync((uint32_t*)ctx->tile_order.p + 2 * 65536, ctx->bin_order_host, (size_t)tiles_x * rows * sizeof(uint32_t),
-                                hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipEventRecord(ctx->bin_order_ev, s));
+    if ((rc = stage_send(ctx, ctx->bin_order_stage, (uint32_t*)ctx->tile_order.p + 2 * 65536, (size_t)tiles_x * rows * sizeof(uint32_t), s))) return rc;
     ctx->bin_order_tx = tiles_x;
     ctx->bin_order_rows = rows;
     return MSPLAT_OK;

@@ -12,10 +12,7 @@
 static int check_download(msplat_ctx* ctx, const char* who)
 {
     if (!ctx) return fail(nullptr, MSPLAT_ERR_INVALID_ARG, "%s: ctx is NULL", who);
-    if (ctx->has_cloud && ctx->point_mode)
-        return fail(ctx, MSPLAT_ERR_UNSUPPORTED, "%s: the context holds a point cloud (the call is for splat clouds)", who);
-    if (!ctx->has_cloud || !ctx->store) return fail(ctx, MSPLAT_ERR_NO_CLOUD, "%s: no cloud uploaded", who);
-    return MSPLAT_OK;
+    return require_splat_cloud(ctx, who, "the call is for splat clouds");
 }
 
 // a destination of `bytes` bytes: there, aligned, memory of the context's device
@@ -59,7 +56,7 @@ static void with_store_kind(msplat_ctx* ctx, Launch&& launch)
 }
 
 // The launch the three device routes share, N > 0: launch(SH, ST, inv) issues the route's kernel over all N rows.  Returns after the
-// stream has drained.  (enable_timing: the kernel alone between two stream events, msplat_debug_upload_kernel_ms.)
+// stream has drained.  (enable_timing: the kernel alone between two stream events, KernelTimer -> msplat_debug_upload_kernel_ms.)
 template <class Launch>
 static int run_download(msplat_ctx* ctx, const char* who, Launch&& launch)
 {
@@ -67,17 +64,13 @@ static int run_download(msplat_ctx* ctx, const char* who, Launch&& launch)
     Buf inv;
     int rc = download_inverse_order(ctx, who, inv);
     if (rc) return rc;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    const bool timed = ctx->cfg.enable_timing > 0 && hipEventCreate(&ev[0]) == hipSuccess && hipEventCreate(&ev[1]) == hipSuccess;
-    ctx->upload_kernel_ms = -1.0f;
-    if (timed) (void)hipEventRecord(ev[0], ctx->stream);
+    KernelTimer timer(ctx);
+    timer.start(ctx->stream);
     with_store_kind(ctx, [&](auto SH, auto ST) { launch(SH, ST, (const uint32_t*)inv.p); });
     hipError_t e = hipGetLastError();
-    if (timed) (void)hipEventRecord(ev[1], ctx->stream);
+    timer.stop(ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e == hipSuccess && timed && hipEventElapsedTime(&ctx->upload_kernel_ms, ev[0], ev[1]) != hipSuccess) ctx->upload_kernel_ms = -1.0f;
-    for (hipEvent_t v : ev)
-        if (v) (void)hipEventDestroy(v);
+    if (e == hipSuccess) timer.read(ctx);
     buf_free(ctx, inv);
     if (e != hipSuccess) return fail(ctx, MSPLAT_ERR_HIP, "%s failed: %s", who, hipGetErrorString(e));
     return MSPLAT_OK;

@@ -164,15 +164,13 @@ int msplat_mark_ids(msplat_ctx* ctx, const uint32_t* d_ids, uint64_t ids_pitch_b
     static const char* who = "msplat_mark_ids";
     drain_async(ctx);
     if (!ctx) return fail(nullptr, MSPLAT_ERR_INVALID_ARG, "ctx is NULL");
-    if (ctx->has_cloud && ctx->point_mode)
-        return fail(ctx, MSPLAT_ERR_UNSUPPORTED, "%s: the context holds a point cloud (visibility is for splat clouds)", who);
-    if (!ctx->has_cloud) return fail(ctx, MSPLAT_ERR_NO_CLOUD, "%s: no cloud uploaded (a mask is in the cloud's upload numbering)", who);
+    int rc;
+    if ((rc = require_splat_cloud(ctx, who, "visibility is for splat clouds", " (a mask is in the cloud's upload numbering)"))) return rc;
     if (n != ctx->N)
         return fail(ctx, MSPLAT_ERR_INVALID_ARG, "%s: %llu mask bytes for a cloud of %llu splats", who, (unsigned long long)n,
                     (unsigned long long)ctx->N);
     if (w == 0 || h == 0 || n == 0) return MSPLAT_OK;
     if (!d_ids || !d_mask) return fail(ctx, MSPLAT_ERR_INVALID_ARG, "%s: %s is NULL", who, d_ids ? "d_mask" : "d_ids");
-    int rc;
     if ((rc = ids_pitch(ctx, who, "ids", ids_pitch_bytes, w))) return rc;
     if (region_pitch_bytes == 0) region_pitch_bytes = w;
     if (d_region && region_pitch_bytes < w)

@@ -5,6 +5,8 @@
 // A class byte per splat (upload numbering) and a palette of up to 256 RGBA entries tint the colours project_kernel left in the
 // records, before the compositor reads them: the cloud, its Sort and its lists stay as they are, and a change shows at the next
 // Render.  With no classes, no palette or a palette of a == 0 only, nothing here runs and a Render launches what it always did.
+// The host routes stage through the context's slots (stage_copy) and the classes outlive a transform or an append as the mask does
+// (KeptPlanes): both in msplat_edit.hip.inc.
 
 // does a Render of the context tint its records?
 static bool overlay_active(const msplat_ctx* ctx) { return !ctx->point_mode && ctx->has_classes && ctx->ov_tints; }
@@ -36,25 +38,6 @@ static void launch_overlay(msplat_ctx* ctx, hipStream_t s, const uint32_t* d_V, 
                        (const float4*)ctx->ov_pal.p, (float*)ctx->rec2d.p, two_views ? 1u : 0u);
 }
 
-// `n` host bytes to device memory of the context's through pinned staging slot k (0 classes, 1 palette), as set_mask does it: the copy
-// is the stream's, the caller's array is free on return, and the slot is written again only after its previous copy has left it
-static int overlay_stage_copy(msplat_ctx* ctx, int k, void* dst, const void* src, size_t n)
-{
-    if (ctx->ov_stage_ev[k]) HIP_TRY(ctx, hipEventSynchronize(ctx->ov_stage_ev[k]));
-    else HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ov_stage_ev[k], hipEventDisableTiming));
-    if (ctx->ov_stage_bytes[k] < n) {
-        if (ctx->ov_stage[k]) (void)hipHostFree(ctx->ov_stage[k]);
-        ctx->ov_stage[k] = nullptr;
-        ctx->ov_stage_bytes[k] = 0;
-        HIP_TRY(ctx, hipHostMalloc((void**)&ctx->ov_stage[k], n, hipHostMallocDefault));
-        ctx->ov_stage_bytes[k] = n;
-    }
-    std::memcpy(ctx->ov_stage[k], src, n);
-    HIP_TRY(ctx, hipMemcpyAsync(dst, ctx->ov_stage[k], n, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipEventRecord(ctx->ov_stage_ev[k], ctx->stream));
-    return MSPLAT_OK;
-}
-
 // the slot array of a store in Morton order, and that store's order on the device
 static int overlay_slot_alloc(msplat_ctx* ctx)
 {
@@ -68,9 +51,8 @@ static int set_overlay_classes(msplat_ctx* ctx, const char* who, const uint8_t* 
 {
     drain_async(ctx);
     if (!ctx) return fail(nullptr, MSPLAT_ERR_INVALID_ARG, "ctx is NULL");
-    if (ctx->has_cloud && ctx->point_mode)
-        return fail(ctx, MSPLAT_ERR_UNSUPPORTED, "%s: the context holds a point cloud (the overlay is for splat clouds)", who);
-    if (!ctx->has_cloud) return fail(ctx, MSPLAT_ERR_NO_CLOUD, "%s: no cloud uploaded (classes are in the cloud's upload numbering)", who);
+    int rc;
+    if ((rc = require_splat_cloud(ctx, who, "the overlay is for splat clouds", " (classes are in the cloud's upload numbering)"))) return rc;
     if (!src) {                     // no classes
         ctx->has_classes = ctx->overlay_dirty = false;
         return MSPLAT_OK;
@@ -78,50 +60,14 @@ static int set_overlay_classes(msplat_ctx* ctx, const char* who, const uint8_t* 
     if (n != ctx->N)
         return fail(ctx, MSPLAT_ERR_INVALID_ARG, "%s: %llu class bytes for a cloud of %llu splats", who, (unsigned long long)n,
                     (unsigned long long)ctx->N);
-    int rc;
     if (on_device && n && (rc = check_device_source(ctx, who, "d_classes", src, n))) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if ((rc = buf_alloc(ctx, ctx->ov_cls, std::max<uint64_t>(n, 1))) || (rc = overlay_slot_alloc(ctx))) return rc;
     if (on_device) {
         if (n) HIP_TRY(ctx, hipMemcpyAsync(ctx->ov_cls.p, src, n, hipMemcpyDeviceToDevice, ctx->stream));
-    } else if (n && (rc = overlay_stage_copy(ctx, 0, ctx->ov_cls.p, src, n))) {
+    } else if (n && (rc = stage_copy(ctx, ctx->ov_stage[0], ctx->ov_cls.p, src, n))) {
         return rc;
     }
-    ctx->has_classes = true;
-    ctx->overlay_dirty = true;
-    return MSPLAT_OK;
-}
-
-// msplat_transform_cloud / msplat_append_cloud keep the classes -- the numbering is the old one -- through the upload tail that would
-// free them: taken out of prepare_cloud_buffers' hands (overlay_take), handed back, then made valid for the new store (overlay_restore)
-struct OverlayKept { bool had; Buf cls; };
-static OverlayKept overlay_take(msplat_ctx* ctx)
-{
-    const OverlayKept k{ctx->has_classes, ctx->ov_cls};
-    ctx->ov_cls = Buf{};
-    return k;
-}
-
-// n_old classes are in ctx->ov_cls again; the cloud now has n_old + added splats: `added` bytes of class 0 follow (the stream is idle)
-static int overlay_restore(msplat_ctx* ctx, const OverlayKept& k, uint64_t n_old, uint64_t added)
-{
-    if (!k.had) return MSPLAT_OK;
-    int rc;
-    if (ctx->ov_cls.bytes < n_old + added) {
-        const Buf old = ctx->ov_cls;
-        ctx->ov_cls = Buf{};
-        rc = buf_alloc(ctx, ctx->ov_cls, n_old + added);
-        hipError_t e = hipSuccess;
-        if (!rc && n_old) e = hipMemcpy(ctx->ov_cls.p, old.p, n_old, hipMemcpyDeviceToDevice);
-        if (old.p) {
-            (void)hipFree(old.p);
-            ctx->device_bytes -= old.bytes;
-        }
-        if (rc) return rc;
-        if (e != hipSuccess) return fail(ctx, MSPLAT_ERR_HIP, "copying the overlay's classes failed: %s", hipGetErrorString(e));
-    }
-    if (added) HIP_TRY(ctx, hipMemsetAsync((char*)ctx->ov_cls.p + n_old, 0, added, ctx->stream));
-    if ((rc = overlay_slot_alloc(ctx))) return rc;
     ctx->has_classes = true;
     ctx->overlay_dirty = true;
     return MSPLAT_OK;
@@ -159,7 +105,7 @@ int msplat_set_overlay_palette(msplat_ctx* ctx, const float* rgba, uint32_t coun
         std::memcpy(pal, rgba, (size_t)count * 16);
         HIP_TRY(ctx, hipSetDevice(ctx->device));
         int rc;
-        if ((rc = buf_alloc(ctx, ctx->ov_pal, sizeof(pal))) || (rc = overlay_stage_copy(ctx, 1, ctx->ov_pal.p, pal, sizeof(pal)))) return rc;
+        if ((rc = buf_alloc(ctx, ctx->ov_pal, sizeof(pal))) || (rc = stage_copy(ctx, ctx->ov_stage[1], ctx->ov_pal.p, pal, sizeof(pal)))) return rc;
     }
     ctx->ov_count = count;
     ctx->ov_tints = tints;

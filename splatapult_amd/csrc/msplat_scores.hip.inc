@@ -82,9 +82,8 @@ int msplat_mark_scores(msplat_ctx* ctx, const uint64_t* d_score, uint64_t n, int
     static const char* who = "msplat_mark_scores";
     drain_async(ctx);
     if (!ctx) return fail(nullptr, MSPLAT_ERR_INVALID_ARG, "ctx is NULL");
-    if (ctx->has_cloud && ctx->point_mode)
-        return fail(ctx, MSPLAT_ERR_UNSUPPORTED, "%s: the context holds a point cloud (visibility is for splat clouds)", who);
-    if (!ctx->has_cloud) return fail(ctx, MSPLAT_ERR_NO_CLOUD, "%s: no cloud uploaded (a mask is in the cloud's upload numbering)", who);
+    int rc;
+    if ((rc = require_splat_cloud(ctx, who, "visibility is for splat clouds", " (a mask is in the cloud's upload numbering)"))) return rc;
     if (n != ctx->N)
         return fail(ctx, MSPLAT_ERR_INVALID_ARG, "%s: %llu mask bytes for a cloud of %llu splats", who, (unsigned long long)n,
                     (unsigned long long)ctx->N);
@@ -93,7 +92,6 @@ int msplat_mark_scores(msplat_ctx* ctx, const uint64_t* d_score, uint64_t n, int
     if (n == 0) return MSPLAT_OK;
     if (!d_score || !d_mask) return fail(ctx, MSPLAT_ERR_INVALID_ARG, "%s: %s is NULL", who, d_score ? "d_mask" : "d_score");
     if ((uintptr_t)d_score % 8 != 0) return fail(ctx, MSPLAT_ERR_INVALID_ARG, "%s: d_score (%p) is not 8-byte aligned", who, (const void*)d_score);
-    int rc;
     if ((rc = check_device_source(ctx, who, "d_score", d_score, 8 * n))) return rc;
     if ((rc = check_device_source(ctx, who, "d_mask", d_mask, n))) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));

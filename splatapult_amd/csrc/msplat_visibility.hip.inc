@@ -4,7 +4,8 @@
 //
 // A hidden splat is a splat the presort cull rejects.  The context keeps a copy of the position plane with a NaN x where the mask
 // or the crop hides a splat, and cull boxes over the visible ones; its Sorts read those instead of the store's (sort_positions,
-// launch_box_cull).  With nothing set the pointers are the store's and nothing here runs.
+// launch_box_cull).  With nothing set the pointers are the store's and nothing here runs.  The front-door refusals, the pinned staging
+// slot of the host route and the rule by which the mask outlives a cloud edit (KeptPlanes) are msplat_edit.hip.inc's.
 
 // does the context sort from its own plane?  (a crop set before the upload of a POINT cloud stays set and is not applied)
 static bool vis_active(const msplat_ctx* ctx)
@@ -58,9 +59,8 @@ static int set_mask(msplat_ctx* ctx, const char* who, const uint8_t* src, uint64
 {
     drain_async(ctx);
     if (!ctx) return fail(nullptr, MSPLAT_ERR_INVALID_ARG, "ctx is NULL");
-    if (ctx->has_cloud && ctx->point_mode)
-        return fail(ctx, MSPLAT_ERR_UNSUPPORTED, "%s: the context holds a point cloud (visibility is for splat clouds)", who);
-    if (!ctx->has_cloud) return fail(ctx, MSPLAT_ERR_NO_CLOUD, "%s: no cloud uploaded (a mask is in the cloud's upload numbering)", who);
+    int rc;
+    if ((rc = require_splat_cloud(ctx, who, "visibility is for splat clouds", " (a mask is in the cloud's upload numbering)"))) return rc;
     if (!src) {                     // no mask
         ctx->vis_dirty = ctx->vis_dirty || ctx->has_mask;
         ctx->has_mask = false;
@@ -69,27 +69,13 @@ static int set_mask(msplat_ctx* ctx, const char* who, const uint8_t* src, uint64
     if (n != ctx->N)
         return fail(ctx, MSPLAT_ERR_INVALID_ARG, "%s: %llu mask bytes for a cloud of %llu splats", who, (unsigned long long)n,
                     (unsigned long long)ctx->N);
-    int rc;
     if (on_device && n && (rc = check_device_source(ctx, who, "d_visible", src, n))) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if ((rc = vis_alloc(ctx)) || (rc = buf_alloc(ctx, ctx->vis_mask, std::max<uint64_t>(n, 1))) || (rc = ensure_order_dev(ctx))) return rc;
     if (on_device) {
         if (n) HIP_TRY(ctx, hipMemcpyAsync(ctx->vis_mask.p, src, n, hipMemcpyDeviceToDevice, ctx->stream));
-    } else if (n) {
-        // through pinned memory of the context's, so that the copy is the stream's and the caller's array is free on return.  The
-        // staging buffer is written again only after the previous mask's copy has left it (an event: no drain of the frames behind it)
-        if (ctx->vis_stage_ev) HIP_TRY(ctx, hipEventSynchronize(ctx->vis_stage_ev));
-        else HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->vis_stage_ev, hipEventDisableTiming));
-        if (ctx->vis_stage_bytes < n) {
-            if (ctx->vis_stage) (void)hipHostFree(ctx->vis_stage);
-            ctx->vis_stage = nullptr;
-            ctx->vis_stage_bytes = 0;
-            HIP_TRY(ctx, hipHostMalloc((void**)&ctx->vis_stage, n, hipHostMallocDefault));
-            ctx->vis_stage_bytes = n;
-        }
-        std::memcpy(ctx->vis_stage, src, n);
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->vis_mask.p, ctx->vis_stage, n, hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipEventRecord(ctx->vis_stage_ev, ctx->stream));
+    } else if (n && (rc = stage_copy(ctx, ctx->vis_stage, ctx->vis_mask.p, src, n))) {      // (the caller's array is free on return)
+        return rc;
     }
     ctx->has_mask = true;
     ctx->vis_dirty = true;
@@ -115,16 +101,13 @@ int msplat_set_crop(msplat_ctx* ctx, const float worldToCrop[16], int32_t shape)
     if (shape != MSPLAT_CROP_NONE && base != MSPLAT_CROP_BOX && base != MSPLAT_CROP_SPHERE)
         return fail(ctx, MSPLAT_ERR_INVALID_ARG, "%s: shape must be MSPLAT_CROP_NONE, or MSPLAT_CROP_BOX / _SPHERE with or without "
                     "MSPLAT_CROP_INVERT (got 0x%x)", who, (unsigned)shape);
-    for (int k = 0; k < 16 && shape != MSPLAT_CROP_NONE; ++k)
-        if (k % 4 != 3 && !std::isfinite(worldToCrop[k]))       // (row 3 is not read)
-            return fail(ctx, MSPLAT_ERR_INVALID_ARG, "%s: worldToCrop[%d] is not finite", who, k);
+    int rc;
+    if (shape != MSPLAT_CROP_NONE && (rc = check_affine_finite(ctx, who, "worldToCrop", worldToCrop))) return rc;
     if (!ctx) return fail(nullptr, MSPLAT_ERR_INVALID_ARG, "ctx is NULL");
-    if (ctx->has_cloud && ctx->point_mode)
-        return fail(ctx, MSPLAT_ERR_UNSUPPORTED, "%s: the context holds a point cloud (visibility is for splat clouds)", who);
+    if (ctx->has_cloud && (rc = require_splat_cloud(ctx, who, "visibility is for splat clouds"))) return rc;      // (a crop may precede the cloud)
     if (shape != MSPLAT_CROP_NONE && ctx->has_cloud) {       // (before the upload: prepare_cloud_buffers allocates)
         HIP_TRY(ctx, hipSetDevice(ctx->device));
-        int rc = vis_alloc(ctx);
-        if (rc) return rc;
+        if ((rc = vis_alloc(ctx))) return rc;
     }
     ctx->vis_dirty = ctx->vis_dirty || shape != MSPLAT_CROP_NONE || ctx->crop_shape != 0;
     ctx->crop_shape = shape;
