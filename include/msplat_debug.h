@@ -110,7 +110,8 @@ int msplat_debug_sh_q8_round(const float rec_in[61], float rec_out[61], float st
  * msplat_compact_cloud: its span from the flags kernel to the end of the gather (the readback of K and the new store's allocation
  * included; -1 when nothing was kept).  tools/compact_timing.py.  After msplat_transform_cloud: transform_kernel alone (-1 for an
  * empty cloud).  tools/transform_timing.py.  After msplat_append_cloud: its gathers and append_convert_kernel, without the scan
- * (-1 for an empty result).  tools/append_timing.py ---- */
+ * (-1 for an empty result).  tools/append_timing.py.  After msplat_adjust_cloud: adjust_kernel alone (-1 for an empty cloud).
+ * tools/adjust_timing.py ---- */
 int msplat_debug_upload_kernel_ms(msplat_ctx* ctx, float* ms);
 
 #ifdef __cplusplus

@@ -33,6 +33,7 @@ TARGET_MODES = {"clear": TARGET_CLEAR, "load": TARGET_LOAD, "premultiplied": TAR
 # msplat_set_crop: the shape, MSPLAT_CROP_INVERT or-ed in
 CROP_NONE, CROP_BOX, CROP_SPHERE, CROP_INVERT = 0, 1, 2, 0x100
 TRANSFORM_KEEP_SH = 1            # msplat_transform_cloud's flag
+ADJUST_COLOUR, ADJUST_OPACITY = 1, 2   # msplat_adjust_cloud: which parts of the rule run
 ID_NONE = 0xFFFFFFFF          # MSPLAT_ID_NONE: a pixel of an id plane (msplat_render_ids) no splat reaches
 SCORE_ONE = 8388608           # MSPLAT_SCORE_ONE: what one fully covered pixel adds to a splat's score (msplat_render_scores)
 SCORE_BELOW, SCORE_AT_LEAST = 0, 1   # msplat_mark_scores: the compare
@@ -192,6 +193,7 @@ SYMBOLS = [
     ("msplat_compact_cloud", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
     ("msplat_transform_cloud", C.c_int, [C.c_void_p, _F16, C.c_void_p, C.c_uint64, C.c_int32]),
     ("msplat_append_cloud", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64)]),
+    ("msplat_adjust_cloud", C.c_int, [C.c_void_p, _F16, C.c_float, C.c_void_p, C.c_uint64, C.c_int32]),
     ("msplat_sh_rotation", C.c_int, [_F16, _F16, _F16, _F16, _F16]),
     ("msplat_debug_get_cull_boxes", C.c_int, [C.c_void_p, _U32P, _U32P, C.POINTER(C.c_int)]),
     ("msplat_get_stats", C.c_int, [C.c_void_p, C.POINTER(Stats)]),

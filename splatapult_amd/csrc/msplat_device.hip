@@ -997,6 +997,7 @@ static int clear_frame_tables(msplat_ctx* ctx)
 #include "msplat_compact.hip.inc"
 #include "msplat_transform.hip.inc"
 #include "msplat_append.hip.inc"
+#include "msplat_adjust.hip.inc"
 #include "msplat_download.hip.inc"
 
 // box_cull_kernel over the store's boxes or (vis) the context's own, for list_live_boxes and msplat_debug_get_cull_boxes; returns

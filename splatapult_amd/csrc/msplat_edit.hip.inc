@@ -2,7 +2,7 @@
 // f_rest failure, the kernel timing pair, the pinned staging slot, the selection scan, and the fresh store with the planes it keeps
 // (textually part of msplat_device.hip: included inside its extern "C" block, before msplat_upload.hip.inc -- run_ingest is the first user)
 //
-// A cloud edit (msplat_compact_cloud, msplat_transform_cloud, msplat_append_cloud) reads: refusals, sync, ensure_order_dev, its own
+// A cloud edit (msplat_compact_cloud, msplat_transform_cloud, msplat_append_cloud, msplat_adjust_cloud) reads: refusals, sync, ensure_order_dev, its own
 // kernels into a FreshStore, fresh_adopt.  A new edit writes its kernels and calls fresh_adopt; a new per-splat plane in upload
 // numbering joins KeptPlanes.
 
@@ -40,7 +40,7 @@ static int check_affine_finite(msplat_ctx* ctx, const char* who, const char* nam
     return MSPLAT_OK;
 }
 
-// what a store of compact SH refuses: n_over values the pack routines counted.  what: "" / "transformed " / "appended ";
+// what a store of compact SH refuses: n_over values the pack routines counted.  what: "" / "transformed " / "appended " / "adjusted ";
 // tail: "" / "; the cloud is unchanged"
 static int f_rest_failure(msplat_ctx* ctx, const char* who, int storage, uint64_t n_over, const char* what, const char* tail)
 {

@@ -1,4 +1,4 @@
-// msplat_kernels.hip.h -- hand-written CDNA4 (gfx950, wave64) kernels of the splat hot path, in fifteen parts.
+// msplat_kernels.hip.h -- hand-written CDNA4 (gfx950, wave64) kernels of the splat hot path, in sixteen parts.
 //
 // Replaces (not ports) the reference's GL pipeline:
 //   shader/presort_compute.glsl + shader/multi_radixsort*.glsl  -> msplat_sort.hip.h      radix_* / ws_* (cull fused in pass 0)
@@ -12,6 +12,7 @@
 //   a mask or crop made permanent (no reference part)          -> msplat_compact.hip.h   compact_* (flags, count, offsets, index, gather)
 //   splats moved, rotated, scaled in the store (no ref. part)   -> msplat_transform.hip.h transform_kernel
 //   splats of a second cloud appended (no reference part)       -> msplat_append.hip.h    append_* (flags, map, gather, convert)
+//   splats recoloured and faded in the store (no ref. part)     -> msplat_adjust.hip.h    adjust_kernel
 //   GaussianCloud::ExportPly's per-splat math, the way out     -> msplat_download.hip.h  unpack_kernel, egress_kernel
 //   shader/point_*.glsl                                         -> msplat_points.hip.h
 //   two-pass frame with occlusion feedback (no reference part)  -> msplat_occlusion.hip.h
@@ -27,6 +28,7 @@
 #include "msplat_compact.hip.h"
 #include "msplat_transform.hip.h"
 #include "msplat_append.hip.h"
+#include "msplat_adjust.hip.h"
 #include "msplat_download.hip.h"
 #include "msplat_project.hip.h"
 #include "msplat_binning.hip.h"

@@ -3,7 +3,7 @@
 // Sort + Render into an explicit RGBA32F framebuffer, dumped as a binary PPM-like float file.
 //
 //   g++ -std=c++17 -I. splatapult_amd/host/example_render.cpp -Lsplatapult_amd/lib -lmsplat -o example_render
-//   ./example_render scene.ply out.f32 [width height] [--nosh] [--frames-in-flight N] [--devices 0,1,2,...] [--over-gradient] [--depth out_depth.f32] [--srgb8 out.png] [--crop-sphere cx cy cz r] [--pick X,Y] [--min-score S] [--highlight R,G,B,A] [--compact] [--append OTHER.ply] [--save OUT.ply]
+//   ./example_render scene.ply out.f32 [width height] [--nosh] [--frames-in-flight N] [--devices 0,1,2,...] [--over-gradient] [--depth out_depth.f32] [--srgb8 out.png] [--crop-sphere cx cy cz r] [--pick X,Y] [--min-score S] [--highlight R,G,B,A] [--compact] [--append OTHER.ply] [--save OUT.ply] [--fade S] [--tint R,G,B,A]
 // With --frames-in-flight N the same frame is issued N + 1 times round-robin over N contexts that share the cloud
 // (SplatRenderer::SetFramesInFlight); the last one is written.  With --devices the frame's bin rows are dealt to the
 // listed GPUs (SplatRenderer::ConfigureDevices, msplat_group_*): same pixels.  With --over-gradient the target is first filled with
@@ -23,6 +23,11 @@
 // With --highlight R,G,B,A (the record's colour space: linear values, A in [0, 1]) nothing is hidden: --min-score then TINTS the splats it
 // selects and --pick the picked splat (SplatRenderer::SetOverlayPalette + SetOverlayDevice / SetOverlay, msplat_set_overlay*: class 1 of a
 // two-entry palette) and the frame is rendered again -- without another Sort: the overlay changes the projected records, not the cloud.
+// With --fade S every splat's opacity is multiplied by S (clamped to [0, 1]) and with --tint R,G,B,A every splat's colour is blended
+// towards R,G,B with weight A in every view direction -- col' = (1 - A) col + A (R, G, B) on the SH coefficients, the record's colour
+// space -- IN THE CLOUD (SplatRenderer::AdjustCloud, msplat_adjust_cloud), and the frame is sorted and rendered again; --save writes
+// the adjusted cloud.  With --min-score (and no --highlight) the splats it selects are not hidden but adjusted: floaters fade or
+// change colour, the rest of the cloud keeps its bits.  One device, one frame in flight.
 // With --compact, after --min-score / --crop-sphere, the hidden splats are dropped for good (SplatRenderer::CompactCloud,
 // msplat_compact_cloud: the kept records gathered into a new store on the device), the splat counts before and after are printed and
 // the frame is sorted and rendered once more from the smaller cloud: the same pixels.  One device only.
@@ -74,6 +79,8 @@ int main(int argc, char** argv)
     int pickX = -1, pickY = -1;      // --pick: print the splat under this pixel (row 0 = bottom) and its window depth
     double minScore = -1.0;          // --min-score: hide the splats that contribute less than this many pixels, render again
     float highlight[8] = {0, 0, 0, 0, 0, 0, 0, -1.0f};      // --highlight: palette entry 0 (no effect) and entry 1; A < 0: not given
+    float fade = -1.0f;              // --fade: the factor on alpha; < 0: not given
+    float tintTo[4] = {0, 0, 0, -1.0f};       // --tint: the colour and the weight; A < 0: not given
     const char* depthPath = nullptr;
     const char* srgb8Path = nullptr;
     const char* appendPath = nullptr;
@@ -96,6 +103,9 @@ int main(int argc, char** argv)
         if (!std::strcmp(argv[i], "--highlight") && i + 1 < argc &&
             std::sscanf(argv[i + 1], "%f,%f,%f,%f", &highlight[4], &highlight[5], &highlight[6], &highlight[7]) != 4)
             highlight[7] = -1.0f;
+        if (!std::strcmp(argv[i], "--fade") && i + 1 < argc) fade = (float)std::atof(argv[i + 1]);
+        if (!std::strcmp(argv[i], "--tint") && i + 1 < argc && std::sscanf(argv[i + 1], "%f,%f,%f,%f", &tintTo[0], &tintTo[1], &tintTo[2], &tintTo[3]) != 4)
+            tintTo[3] = -1.0f;
         if (!std::strcmp(argv[i], "--devices") && i + 1 < argc)
             for (const char* p = argv[i + 1]; *p;) {
                 devices.push_back(std::atoi(p));
@@ -167,6 +177,18 @@ int main(int argc, char** argv)
     }
     renderer.Synchronize();
     const bool tint = highlight[7] >= 0.0f && inFlight == 1 && devices.size() <= 1;
+    // --fade / --tint: the 3 x 4 map [G | o], column-major, G = (1 - A) I and o = A (R, G, B); d_select = nullptr: the whole cloud
+    const bool adjust = (fade >= 0.0f || tintTo[3] >= 0.0f) && inFlight == 1 && devices.size() <= 1;
+    auto adjustCloud = [&](const uint8_t* d_select) {
+        const float t = 1.0f - tintTo[3], a = tintTo[3];
+        const float map[12] = {t, 0, 0, 0, t, 0, 0, 0, t, a * tintTo[0], a * tintTo[1], a * tintTo[2]};
+        if (!renderer.AdjustCloud(tintTo[3] >= 0.0f ? map : nullptr, fade, d_select)) return false;
+        renderer.Sort(cameraMat, projMat, viewport, nearFar);
+        if (depthPath) renderer.RenderWithDepth(cameraMat, projMat, viewport, nearFar, depth.data());
+        else renderer.Render(cameraMat, projMat, viewport, nearFar);
+        renderer.Synchronize();
+        return true;
+    };
     if (pickX >= 0 && pickY >= 0) {
         uint32_t index = MSPLAT_ID_NONE;
         float zw = 1.0f;
@@ -188,26 +210,34 @@ int main(int argc, char** argv)
         DeviceMemory dm;
         void *score = nullptr, *mask = nullptr;
         if (!dm.Load() || dm.alloc(&score, n * 8) != 0 || dm.alloc(&mask, n) != 0) return 1;
-        if (dm.fill(score, 0, n * 8) != 0 || dm.fill(mask, tint ? 0 : 1, n) != 0 || dm.wait() != 0) return 1;      // filled before the context's stream starts
+        if (dm.fill(score, 0, n * 8) != 0 || dm.fill(mask, tint || adjust ? 0 : 1, n) != 0 || dm.wait() != 0) return 1;      // filled before the context's stream starts
         if (!renderer.RenderScores(cameraMat, projMat, viewport, nearFar, nullptr, static_cast<uint64_t*>(score), n)) return 1;
         if (!renderer.MarkScores(static_cast<const uint64_t*>(score), n, MSPLAT_SCORE_BELOW, (uint64_t)(minScore * (double)MSPLAT_SCORE_ONE),
-                                 static_cast<uint8_t*>(mask), tint ? 1 : 0))
+                                 static_cast<uint8_t*>(mask), tint || adjust ? 1 : 0))
             return 1;
-        // hidden (a mask of ones with zeros marked: the next Sort drops them), or shown: classes of zeros with ones marked, tinted by the
-        // palette's entry 1 at the next Render
-        if (tint ? !(renderer.SetOverlayPalette(highlight, 2) && renderer.SetOverlayDevice(static_cast<const uint8_t*>(mask), n))
-                 : !renderer.SetVisibilityDevice(static_cast<const uint8_t*>(mask), n))
-            return 1;
-        if (!tint) renderer.Sort(cameraMat, projMat, viewport, nearFar);
-        if (depthPath) renderer.RenderWithDepth(cameraMat, projMat, viewport, nearFar, depth.data());
-        else renderer.Render(cameraMat, projMat, viewport, nearFar);
-        renderer.Synchronize();
-        uint64_t hidden = 0;
-        if (msplat_get_visibility(renderer.GetContext(), nullptr, nullptr, &hidden) != MSPLAT_OK) return 1;
-        if (tint) std::printf("min score %g: the splats below it are highlighted\n", minScore);
-        else std::printf("min score %g: %llu of %zu splats hidden\n", minScore, (unsigned long long)hidden, n);
+        // adjusted in the cloud (--fade / --tint: nothing is hidden), hidden (a mask of ones with zeros marked: the next Sort drops them),
+        // or shown: classes of zeros with ones marked, tinted by the palette's entry 1 at the next Render
+        if (adjust && !tint) {
+            if (!adjustCloud(static_cast<const uint8_t*>(mask))) return 1;
+            std::printf("min score %g: the splats below it are adjusted (fade %g, tint weight %g)\n", minScore, fade, tintTo[3]);
+        } else {
+            if (tint ? !(renderer.SetOverlayPalette(highlight, 2) && renderer.SetOverlayDevice(static_cast<const uint8_t*>(mask), n))
+                     : !renderer.SetVisibilityDevice(static_cast<const uint8_t*>(mask), n))
+                return 1;
+            if (!tint) renderer.Sort(cameraMat, projMat, viewport, nearFar);
+            if (depthPath) renderer.RenderWithDepth(cameraMat, projMat, viewport, nearFar, depth.data());
+            else renderer.Render(cameraMat, projMat, viewport, nearFar);
+            renderer.Synchronize();
+            uint64_t hidden = 0;
+            if (msplat_get_visibility(renderer.GetContext(), nullptr, nullptr, &hidden) != MSPLAT_OK) return 1;
+            if (tint) std::printf("min score %g: the splats below it are highlighted\n", minScore);
+            else std::printf("min score %g: %llu of %zu splats hidden\n", minScore, (unsigned long long)hidden, n);
+        }
         dm.release(score);
         dm.release(mask);
+    } else if (adjust) {
+        if (!adjustCloud(nullptr)) return 1;
+        std::printf("adjusted: every splat (fade %g, tint weight %g)\n", fade, tintTo[3]);
     }
 
     if (compact && devices.size() <= 1) {

@@ -443,6 +443,31 @@ public:
         return AttachContexts();
     }
 
+    // Recolours and fades splats on the device (msplat_adjust_cloud): every splat i with d_select[i] != 0 (n bytes of device memory;
+    // nullptr: every splat) gets, with colour != nullptr, the affine map col' = G col + o of its colour in every view direction
+    // (12 floats, column-major: G's three columns, then o; applied to the SH coefficients, in the record's colour space) and, with
+    // opacityScale >= 0, alpha' = clamp(opacityScale * alpha, 0, 1); the others are copied bit for bit, and a part that is not asked
+    // for keeps its bits.  Every frame in flight is finished first; context 0 is adjusted and keeps its mask and overlay classes (the
+    // numbering does not change), the others are attached again, which drops THEIRS: with frames in flight call
+    // SetVisibility[Device] / SetOverlay[Device] again afterwards.  The crop stays; Sort before the next Render.
+    bool AdjustCloud(const float* colour, float opacityScale = -1.0f, const uint8_t* d_select = nullptr)
+    {
+        if (group || ctxs.empty()) {
+            std::fprintf(stderr, "[msplat][E] AdjustCloud: %s\n", group ? "a device group has no cloud editing" : "no cloud (Init first)");
+            return false;
+        }
+        Synchronize();
+        ctx = ctxs[0];
+        cur = (int)ctxs.size() - 1;           // the next Sort lands on context 0
+        const int32_t flags = (colour ? MSPLAT_ADJUST_COLOUR : 0) | (opacityScale >= 0.0f ? MSPLAT_ADJUST_OPACITY : 0);
+        msplat_stats st;
+        if (msplat_get_stats(ctx, &st) != MSPLAT_OK || msplat_adjust_cloud(ctx, colour, opacityScale, d_select, st.num_splats, flags) != MSPLAT_OK) {
+            std::fprintf(stderr, "[msplat][E] AdjustCloud: %s\n", msplat_last_error(ctx));
+            return false;
+        }
+        return AttachContexts();
+    }
+
     // The cloud out of the device (msplat_export_ply, msplat_download_cloud_device, msplat_download_attributes_device): as it is on the
     // device -- moved, pasted into, compacted --, upload numbering, the mask and the crop ignored; nothing of the renderer changes.
     // ExportPly writes the PLY GaussianCloud::ExportPly writes; DownloadDevice N tight reference records (244 B with full SH, 100 B

@@ -122,6 +122,24 @@ _LIVES = {"depth": ("the depth plane lives in the colour's memory space: pass de
 _KEEP = object()        # SetOverlay: an argument left out stays as it is
 
 
+def tint_matrix(rgb, a):
+    """The (3, 4) colour map [G | o] of AdjustCloud that blends every colour towards rgb with weight a: G = (1 - a) I, o = a rgb --
+    the overlay's rule t c + a h made permanent (in the record's colour space)."""
+    rgb = np.asarray(rgb, np.float64).reshape(-1)
+    if rgb.shape[0] != 3:
+        raise ValueError("rgb must be three values, not %d" % rgb.shape[0])
+    a = float(a)
+    return np.concatenate([(1.0 - a) * np.eye(3), (a * rgb)[:, None]], axis=1).astype(np.float32)
+
+
+def gain_matrix(gain, offset=0.0):
+    """The (3, 4) colour map [G | o] of AdjustCloud with G = diag(gain) and o = offset; each a scalar or one value per channel:
+    white balance, exposure, a lift."""
+    g = np.broadcast_to(np.asarray(gain, np.float64), (3,))
+    o = np.broadcast_to(np.asarray(offset, np.float64), (3,))
+    return np.concatenate([np.diag(g), o[:, None]], axis=1).astype(np.float32)
+
+
 class SplatRenderer:
     def __init__(self, device=0, fb_format="fp32", t_epsilon=-1.0, pair_capacity=0, stream=None,
                  enable_timing=False, frames_in_flight=1, rank_mode=_capi.RANK_AUTO, frame_mode=None,
@@ -166,7 +184,7 @@ class SplatRenderer:
         self._frame_mode = int(frame_mode) if frame_mode is not None else (_capi.FRAMES_IN_FLIGHT if self._depth > 1 else _capi.FRAMES_AUTO)
         self._n = 0
         self._load = False                     # set_target_mode("load"): a host Render needs the destination in out=
-        self._ov_arg = None                    # SetOverlay's classes, for the contexts TransformCloud / AppendCloud attach again
+        self._ov_arg = None                    # SetOverlay's classes, for the contexts TransformCloud / AppendCloud / AdjustCloud attach again
         self._ov_palette = None                # ... and its palette, which new contexts (Init*) receive again
 
     def __del__(self):
@@ -678,7 +696,7 @@ class SplatRenderer:
         return dict(has_classes=bool(a.value), palette_count=int(b.value), active=bool(c.value))
 
     def _overlay_again(self, classed, added=0):
-        """the contexts TransformCloud / AppendCloud attached again receive the remembered classes, `added` values of class 0 longer"""
+        """the contexts TransformCloud / AppendCloud / AdjustCloud attached again receive the remembered classes, `added` values of class 0 longer"""
         ov = self._ov_arg
         if not classed or ov is None:
             return
@@ -777,6 +795,55 @@ class SplatRenderer:
         self._cur = self._depth - 1          # the next Sort lands on context 0, as after Init
         if not self._attach_all():
             raise _capi.MsplatError(_capi.ERR_HIP, "TransformCloud: attaching the transformed cloud failed: " + self._err)
+        if masked.value and len(self._ctxs) > 1 and getattr(self, "_vis_arg", None) is not None:
+            ctxs, self._ctxs = self._ctxs, self._ctxs[1:]
+            try:
+                self.SetVisibility(self._vis_arg)
+            finally:
+                self._ctxs = ctxs
+        self._overlay_again(classed.value)
+
+    def AdjustCloud(self, colour=None, opacity=None, select=None):
+        """Recolour and fade splats on the device (msplat_adjust_cloud): every splat i with select[i] (None:
+        every splat) gets, with colour, the affine map col' = G col + o of its colour in every view direction -- applied to its SH
+        coefficients, in the record's colour space -- and, with opacity, alpha' = clamp(opacity * alpha, 0, 1) and the footprint
+        bound that goes with it; the others are copied bit for bit.  colour: a (3, 4) array-like in the row form [G | o]
+        (tint_matrix, gain_matrix); opacity: a finite factor >= 0.  An argument left None leaves its part of the record alone (a
+        fade never re-quantises an "sh_q8" cloud); both None is a ValueError.  select: N values, as TransformCloud takes them.
+        The renderer afterwards is one that was Init'ed with those rows, except that the numbering, and with it the mask and the
+        overlay's classes, stays: every frame in flight is finished first; context 0 is adjusted, the others are attached again
+        and are handed SetVisibility's and SetOverlay's last arguments again, exactly as after TransformCloud.  The crop stays;
+        Sort before the next Render."""
+        if colour is None and opacity is None:
+            raise ValueError("AdjustCloud: pass colour=, opacity= or both")
+        flags, c12, scale = 0, None, 1.0
+        if colour is not None:
+            g = np.asarray(colour, np.float32)
+            if g.shape != (3, 4):
+                raise ValueError("colour must have shape (3, 4), the rows of [G | o], not %s" % (g.shape,))
+            if not np.isfinite(g).all():
+                raise ValueError("colour must be finite")
+            c12 = np.ascontiguousarray(g.T.reshape(12))          # column-major: G's columns, then o
+            flags |= _capi.ADJUST_COLOUR
+        if opacity is not None:
+            scale = float(opacity)
+            if not np.isfinite(scale) or scale < 0.0:
+                raise ValueError("opacity must be a finite factor >= 0, not %r" % (opacity,))
+            flags |= _capi.ADJUST_OPACITY
+        if not self._ctxs:
+            raise _capi.MsplatError(_capi.ERR_NO_CLOUD, "AdjustCloud: no cloud (Init first)")
+        sel = self._device_select(select, self._n)
+        self.synchronize()
+        own = self._ctxs[0]
+        masked, classed = C.c_int32(), C.c_int32()
+        _capi.check(own, self._lib.msplat_get_visibility(own, C.byref(masked), None, None))
+        _capi.check(own, self._lib.msplat_get_overlay(own, C.byref(classed), None, None))
+        _capi.check(own, self._lib.msplat_adjust_cloud(own, c12.ctypes.data_as(C.POINTER(C.c_float)) if c12 is not None else None,
+                                                       C.c_float(scale), sel, self._n, flags))
+        self._ctx = own
+        self._cur = self._depth - 1          # the next Sort lands on context 0, as after Init
+        if not self._attach_all():
+            raise _capi.MsplatError(_capi.ERR_HIP, "AdjustCloud: attaching the adjusted cloud failed: " + self._err)
         if masked.value and len(self._ctxs) > 1 and getattr(self, "_vis_arg", None) is not None:
             ctxs, self._ctxs = self._ctxs, self._ctxs[1:]
             try:
