@@ -111,8 +111,13 @@ int msplat_debug_sh_q8_round(const float rec_in[61], float rec_out[61], float st
  * included; -1 when nothing was kept).  tools/compact_timing.py.  After msplat_transform_cloud: transform_kernel alone (-1 for an
  * empty cloud).  tools/transform_timing.py.  After msplat_append_cloud: its gathers and append_convert_kernel, without the scan
  * (-1 for an empty result).  tools/append_timing.py.  After msplat_adjust_cloud: adjust_kernel alone (-1 for an empty cloud).
- * tools/adjust_timing.py ---- */
+ * tools/adjust_timing.py.  After msplat_measure_cloud: its two kernels (-1 for an empty cloud).  tools/select_timing.py ---- */
 int msplat_debug_upload_kernel_ms(msplat_ctx* ctx, float* ms);
+
+/* ---- the store's position plane as the kernels read it: N x (x, y, z, footprint bound) in STORAGE order (msplat_get_storage_order
+ * maps a slot to its upload index), whatever the mask and the crop hide; cap_floats >= 4 N.  What msplat_mark_volume, msplat_mark_view
+ * and msplat_measure_cloud are functions of.  Synchronises ---- */
+int msplat_debug_get_positions(msplat_ctx* ctx, float* pos4_out, uint64_t cap_floats);
 
 #ifdef __cplusplus
 }

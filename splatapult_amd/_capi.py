@@ -83,6 +83,12 @@ class CompositeWork(C.Structure):
                  "pixel_evals", "batches", "clocks_sum", "clocks_max", "inner_clocks_sum", "useful_evals")]
 
 
+class CloudMeasure(C.Structure):
+    """msplat_cloud_measure (msplat_measure_cloud, msplat_measure_box)"""
+    _fields_ = [("struct_size", C.c_uint32), ("selected", C.c_uint64), ("finite", C.c_uint64), ("lo", C.c_float * 3), ("hi", C.c_float * 3),
+                ("reach2_max", C.c_float), ("sum", C.c_double * 3), ("sum2", C.c_double * 6)]
+
+
 class Timings(C.Structure):
     _fields_ = [("sort_total", C.c_float), ("render_total", C.c_float), ("project", C.c_float),
                 ("binning", C.c_float), ("composite", C.c_float), ("reserved", C.c_float * 3)]
@@ -157,6 +163,12 @@ SYMBOLS = [
     ("msplat_render_scores", C.c_int, [C.c_void_p, _F16, _F16, _F16, _F16, C.POINTER(C.c_int32), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                        C.c_uint64]),
     ("msplat_mark_scores", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_uint64, C.c_void_p, C.c_uint8]),
+    ("msplat_mark_volume", C.c_int, [C.c_void_p, _F16, C.c_int32, C.c_void_p, C.c_uint64, C.c_uint8]),
+    ("msplat_mark_view", C.c_int, [C.c_void_p, _F16, _F16, _F16, _F16, C.POINTER(C.c_int32), C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                                   C.c_uint8]),
+    ("msplat_measure_cloud", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(CloudMeasure)]),
+    ("msplat_measure_box", C.c_int, [C.POINTER(CloudMeasure), C.c_float, _F16]),
+    ("msplat_debug_get_positions", C.c_int, [C.c_void_p, _F16, C.c_uint64]),
     ("msplat_synchronize", C.c_int, [C.c_void_p]),
     ("msplat_read_image", C.c_int, [C.c_char_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     ("msplat_points_create", C.c_void_p, [C.c_int]),

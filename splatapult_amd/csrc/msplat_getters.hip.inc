@@ -419,3 +419,18 @@ int msplat_debug_upload_kernel_ms(msplat_ctx* ctx, float* ms)
     *ms = ctx->upload_kernel_ms;      // (run_ingest has drained the stream)
     return MSPLAT_OK;
 }
+
+int msplat_debug_get_positions(msplat_ctx* ctx, float* pos4_out, uint64_t cap_floats)
+{
+    drain_async(ctx);
+    if (!ctx || !pos4_out) return fail(ctx, MSPLAT_ERR_INVALID_ARG, "msplat_debug_get_positions: NULL argument");
+    if (!ctx->has_cloud) return fail(ctx, MSPLAT_ERR_NO_CLOUD, "msplat_debug_get_positions: no cloud uploaded");
+    if (cap_floats < 4 * ctx->N)
+        return fail(ctx, MSPLAT_ERR_INVALID_ARG, "msplat_debug_get_positions: capacity %llu < 4 x %llu floats", (unsigned long long)cap_floats,
+                    (unsigned long long)ctx->N);
+    if (ctx->N == 0) return MSPLAT_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipMemcpyAsync(pos4_out, ctx->pos4.p, ctx->N * 16, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return MSPLAT_OK;
+}

@@ -107,8 +107,19 @@ static int ids_pitch(msplat_ctx* ctx, const char* who, const char* what, uint64_
 
 struct IdsWindow { bool given; int32_t v[4]; };
 
+// a caller's window of a width x height viewport: not given = the whole viewport; else x0, y0, w, h, not empty and inside it
+static int frame_window(msplat_ctx* ctx, const char* who, int width, int height, IdsWindow& win)
+{
+    if (!win.given) { win.v[0] = 0; win.v[1] = 0; win.v[2] = width; win.v[3] = height; }
+    const int32_t* w = win.v;
+    if (w[2] <= 0 || w[3] <= 0 || w[0] < 0 || w[1] < 0 || (int64_t)w[0] + w[2] > width || (int64_t)w[1] + w[3] > height)
+        return fail(ctx, MSPLAT_ERR_INVALID_ARG, "%s: window (%d, %d, %d, %d) is empty or not inside the %d x %d viewport", who, w[0], w[1],
+                    w[2], w[3], width, height);
+    return MSPLAT_OK;
+}
+
 // What the frames that walk the lists themselves (the id frame, the score frame: `walk` names it) refuse after begin_frame, and
-// their window: not given = the whole viewport; else x0, y0, w, h, not empty and inside the viewport
+// their window (frame_window)
 static int walk_frame_window(msplat_ctx* ctx, const char* who, const char* walk, const FrameParams& fp, IdsWindow& win)
 {
     char why[160] = "";
@@ -118,12 +129,7 @@ static int walk_frame_window(msplat_ctx* ctx, const char* who, const char* walk,
     else if (ctx->probe_on) std::snprintf(why, sizeof(why), "the tile probe (msplat_set_tile_probe) has no %s walk", walk);
     else if (ctx->banded) std::snprintf(why, sizeof(why), "the context is banded (msplat_set_band / msplat_set_band_layout): the %s frame covers whole windows", walk);
     if (why[0]) return fail(ctx, MSPLAT_ERR_UNSUPPORTED, "%s: %s", who, why);
-    if (!win.given) { win.v[0] = 0; win.v[1] = 0; win.v[2] = fp.width; win.v[3] = fp.height; }
-    const int32_t* w = win.v;
-    if (w[2] <= 0 || w[3] <= 0 || w[0] < 0 || w[1] < 0 || (int64_t)w[0] + w[2] > fp.width || (int64_t)w[1] + w[3] > fp.height)
-        return fail(ctx, MSPLAT_ERR_INVALID_ARG, "%s: window (%d, %d, %d, %d) is empty or not inside the %d x %d viewport", who, w[0], w[1],
-                    w[2], w[3], fp.width, fp.height);
-    return MSPLAT_OK;
+    return frame_window(ctx, who, fp.width, fp.height, win);
 }
 
 static int ids_impl(msplat_ctx* ctx, const float cameraMat[16], const float projMat[16], const float viewport[4], const float nearFar[2],

@@ -1,4 +1,4 @@
-// msplat_kernels.hip.h -- hand-written CDNA4 (gfx950, wave64) kernels of the splat hot path, in sixteen parts.
+// msplat_kernels.hip.h -- hand-written CDNA4 (gfx950, wave64) kernels of the splat hot path, in seventeen parts.
 //
 // Replaces (not ports) the reference's GL pipeline:
 //   shader/presort_compute.glsl + shader/multi_radixsort*.glsl  -> msplat_sort.hip.h      radix_* / ws_* (cull fused in pass 0)
@@ -9,6 +9,7 @@
 //   what each splat contributes (no reference part)             -> msplat_scores.hip.h    composite_scores_kernel, mark_scores_kernel
 //   splats tinted by class at render time (no reference part)   -> msplat_overlay.hip.h   overlay_kernel, overlay_classes_kernel
 //   GaussianCloud::ImportPly's per-vertex math, storage order   -> msplat_cloud.hip.h     ingest_kernel, morton / gather / cull boxes
+//   splats selected by position, a selection measured (no ref.) -> msplat_select.hip.h    mark_volume_kernel, mark_view_kernel, measure_cloud_*
 //   a mask or crop made permanent (no reference part)          -> msplat_compact.hip.h   compact_* (flags, count, offsets, index, gather)
 //   splats moved, rotated, scaled in the store (no ref. part)   -> msplat_transform.hip.h transform_kernel
 //   splats of a second cloud appended (no reference part)       -> msplat_append.hip.h    append_* (flags, map, gather, convert)
@@ -25,6 +26,7 @@
 #include "msplat_common.hip.h"
 #include "msplat_sort.hip.h"
 #include "msplat_cloud.hip.h"
+#include "msplat_select.hip.h"
 #include "msplat_compact.hip.h"
 #include "msplat_transform.hip.h"
 #include "msplat_append.hip.h"

@@ -3,7 +3,7 @@
 // Sort + Render into an explicit RGBA32F framebuffer, dumped as a binary PPM-like float file.
 //
 //   g++ -std=c++17 -I. splatapult_amd/host/example_render.cpp -Lsplatapult_amd/lib -lmsplat -o example_render
-//   ./example_render scene.ply out.f32 [width height] [--nosh] [--frames-in-flight N] [--devices 0,1,2,...] [--over-gradient] [--depth out_depth.f32] [--srgb8 out.png] [--crop-sphere cx cy cz r] [--pick X,Y] [--min-score S] [--highlight R,G,B,A] [--compact] [--append OTHER.ply] [--save OUT.ply] [--fade S] [--tint R,G,B,A]
+//   ./example_render scene.ply out.f32 [width height] [--nosh] [--frames-in-flight N] [--devices 0,1,2,...] [--over-gradient] [--depth out_depth.f32] [--srgb8 out.png] [--crop-sphere cx cy cz r] [--pick X,Y] [--min-score S] [--highlight R,G,B,A] [--compact] [--append OTHER.ply] [--save OUT.ply] [--fade S] [--tint R,G,B,A] [--select-sphere CX,CY,CZ,R]
 // With --frames-in-flight N the same frame is issued N + 1 times round-robin over N contexts that share the cloud
 // (SplatRenderer::SetFramesInFlight); the last one is written.  With --devices the frame's bin rows are dealt to the
 // listed GPUs (SplatRenderer::ConfigureDevices, msplat_group_*): same pixels.  With --over-gradient the target is first filled with
@@ -28,6 +28,9 @@
 // space -- IN THE CLOUD (SplatRenderer::AdjustCloud, msplat_adjust_cloud), and the frame is sorted and rendered again; --save writes
 // the adjusted cloud.  With --min-score (and no --highlight) the splats it selects are not hidden but adjusted: floaters fade or
 // change colour, the rest of the cloud keeps its bits.  One device, one frame in flight.
+// With --select-sphere CX,CY,CZ,R every splat whose centre lies in that sphere is marked into a device mask (SplatRenderer::MarkVolume,
+// msplat_mark_volume: the crop's rule, hidden and occluded splats included) and the selection's count, box, centroid and reach are
+// printed (SplatRenderer::MeasureCloud); with --highlight the selection is tinted and the frame rendered again.  One device, one frame in flight.
 // With --compact, after --min-score / --crop-sphere, the hidden splats are dropped for good (SplatRenderer::CompactCloud,
 // msplat_compact_cloud: the kept records gathered into a new store on the device), the splat counts before and after are printed and
 // the frame is sorted and rendered once more from the smaller cloud: the same pixels.  One device only.
@@ -87,7 +90,11 @@ int main(int argc, char** argv)
     const char* savePath = nullptr;
     std::vector<int> devices;
     float cropSphere[4] = {0.0f, 0.0f, 0.0f, 0.0f};       // centre, radius; radius 0: no crop
+    float selectSphere[4] = {0.0f, 0.0f, 0.0f, 0.0f};     // --select-sphere: centre, radius; radius 0: not given
     for (int i = 3; i < argc; ++i) {
+        if (!std::strcmp(argv[i], "--select-sphere") && i + 1 < argc &&
+            std::sscanf(argv[i + 1], "%f,%f,%f,%f", &selectSphere[0], &selectSphere[1], &selectSphere[2], &selectSphere[3]) != 4)
+            selectSphere[3] = 0.0f;
         if (!std::strcmp(argv[i], "--crop-sphere") && i + 4 < argc)
             for (int k = 0; k < 4; ++k) cropSphere[k] = (float)std::atof(argv[i + 1 + k]);
         nosh = nosh || !std::strcmp(argv[i], "--nosh");
@@ -238,6 +245,33 @@ int main(int argc, char** argv)
     } else if (adjust) {
         if (!adjustCloud(nullptr)) return 1;
         std::printf("adjusted: every splat (fade %g, tint weight %g)\n", fade, tintTo[3]);
+    }
+
+    if (selectSphere[3] > 0.0f && inFlight == 1 && devices.size() <= 1) {
+        const size_t n = cloud->GetNumGaussians();
+        DeviceMemory dm;
+        void* mask = nullptr;
+        if (!dm.Load() || dm.alloc(&mask, n) != 0 || dm.fill(mask, 0, n) != 0 || dm.wait() != 0) return 1;
+        const float s = 1.0f / selectSphere[3];
+        const float worldToVolume[16] = {s, 0, 0, 0, 0, s, 0, 0, 0, 0, s, 0, -selectSphere[0] * s, -selectSphere[1] * s, -selectSphere[2] * s, 1};
+        msplat_cloud_measure m;
+        if (!renderer.MarkVolume(worldToVolume, MSPLAT_CROP_SPHERE, static_cast<uint8_t*>(mask), n, 1) ||
+            !renderer.MeasureCloud(static_cast<const uint8_t*>(mask), n, &m))
+            return 1;
+        std::printf("select sphere: %llu of %zu splats", (unsigned long long)m.selected, n);
+        if (m.finite)
+            std::printf(", box (%g, %g, %g) .. (%g, %g, %g), centroid (%g, %g, %g), reach %g", m.lo[0], m.lo[1], m.lo[2], m.hi[0], m.hi[1], m.hi[2],
+                        m.sum[0] / (double)m.finite, m.sum[1] / (double)m.finite, m.sum[2] / (double)m.finite, std::sqrt((double)m.reach2_max));
+        std::printf("\n");
+        if (tint) {              // the selection as class 1 of the two-entry palette: shown at the next Render, no Sort
+            if (!renderer.SetOverlayPalette(highlight, 2) || !renderer.SetOverlayDevice(static_cast<const uint8_t*>(mask), n)) return 1;
+            if (depthPath) renderer.RenderWithDepth(cameraMat, projMat, viewport, nearFar, depth.data());
+            else renderer.Render(cameraMat, projMat, viewport, nearFar);
+            renderer.Synchronize();
+            std::printf("the selection is highlighted\n");
+        }
+        renderer.Synchronize();
+        dm.release(mask);
     }
 
     if (compact && devices.size() <= 1) {

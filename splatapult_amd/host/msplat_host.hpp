@@ -565,6 +565,50 @@ public:
         }
         return true;
     }
+    // Selection by position (msplat_mark_volume, msplat_mark_view, msplat_measure_cloud): the cloud itself is tested, whatever a mask or
+    // a crop hides, in upload numbering; no Sort is needed.  Device memory only; the marks are asynchronous on the stream of the latest
+    // Sort's context, the measure returns after its copy.  A device group has none of them.
+    // MarkVolume: d_mask[i] = value where the centre satisfies SetCrop's rule for worldToVolume and shape (MSPLAT_CROP_BOX / _SPHERE,
+    // | MSPLAT_CROP_INVERT); other bytes stay.
+    bool MarkVolume(const float* worldToVolume, int32_t shape, uint8_t* d_mask, size_t n, uint8_t value)
+    {
+        return Select("MarkVolume", [&](msplat_ctx* h) { return msplat_mark_volume(h, worldToVolume, shape, d_mask, n, value); });
+    }
+    // MarkView, select through: d_mask[i] = value where the projected centre lies in front of the camera on a pixel of window (nullptr =
+    // the whole viewport) that d_region selects (nullptr = all; RenderScores' conventions), occluded splats included.
+    template <class Mat4, class Vec4, class Vec2>
+    bool MarkView(const Mat4& cameraMat, const Mat4& projMat, const Vec4& viewport, const Vec2& nearFar, const int32_t* window, uint8_t* d_mask,
+                  size_t n, uint8_t value, const uint8_t* d_region = nullptr, uint64_t regionPitchBytes = 0)
+    {
+        static_assert(sizeof(Mat4) == 64 && sizeof(Vec4) == 16 && sizeof(Vec2) == 8, "glm-compatible layout expected");
+        return Select("MarkView", [&](msplat_ctx* h) {
+            return msplat_mark_view(h, F(cameraMat), F(projMat), F(viewport), F(nearFar), window, d_region, regionPitchBytes, d_mask, n, value);
+        });
+    }
+    // MeasureCloud: count, box, largest footprint bound and moment sums of the splats d_select selects (nullptr: all) into *out.
+    // MeasureBox (host only): the axis-aligned worldToVolume whose box holds every measured centre, pad world units wider per side.
+    bool MeasureCloud(const uint8_t* d_select, size_t n, msplat_cloud_measure* out)
+    {
+        if (out) out->struct_size = sizeof(msplat_cloud_measure);
+        return Select("MeasureCloud", [&](msplat_ctx* h) { return msplat_measure_cloud(h, d_select, n, out); });
+    }
+    static bool MeasureBox(const msplat_cloud_measure& m, float pad, float worldToVolume[16])
+    {
+        if (msplat_measure_box(&m, pad, worldToVolume) == MSPLAT_OK) return true;
+        std::fprintf(stderr, "[msplat][E] MeasureBox: %s\n", msplat_last_error(nullptr));
+        return false;
+    }
+    template <class Call>
+    bool Select(const char* who, Call&& call)
+    {
+        if (group || !ctx) {
+            std::fprintf(stderr, "[msplat][E] %s: %s\n", who, group ? "a device group has no selection by position" : "no cloud (Init first)");
+            return false;
+        }
+        const int rc = call(ctx);
+        if (rc != MSPLAT_OK) std::fprintf(stderr, "[msplat][E] %s: %s\n", who, msplat_last_error(ctx));
+        return rc == MSPLAT_OK;
+    }
 
     // blocks until every frame in flight has finished
     // (also where a pair-buffer overflow of an earlier device-target Render is reported, see msplat_render)

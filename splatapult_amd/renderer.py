@@ -140,6 +140,19 @@ def gain_matrix(gain, offset=0.0):
     return np.concatenate([np.diag(g), o[:, None]], axis=1).astype(np.float32)
 
 
+def measure_box(measure, pad=0.0):
+    """The axis-aligned worldToVolume (float32[16], column-major) whose box holds every centre of a MeasureCloud result, widened by
+    pad >= 0 world units per side (msplat_measure_box): pass np.sqrt(measure["reach2_max"]) to include the splats' extent.  Feeds
+    MarkVolume and SetCrop.  Host arithmetic; MsplatError for a measure without a finite centre or a bad pad."""
+    m = _capi.CloudMeasure(struct_size=C.sizeof(_capi.CloudMeasure), selected=int(measure["selected"]), finite=int(measure["finite"]),
+                           reach2_max=float(measure.get("reach2_max", 0.0)))
+    for k in range(3):
+        m.lo[k], m.hi[k] = float(measure["lo"][k]), float(measure["hi"][k])
+    out = np.zeros(16, np.float32)
+    _capi.check(None, _capi.lib().msplat_measure_box(C.byref(m), C.c_float(float(pad)), out.ctypes.data_as(C.POINTER(C.c_float))))
+    return out
+
+
 class SplatRenderer:
     def __init__(self, device=0, fb_format="fp32", t_epsilon=-1.0, pair_capacity=0, stream=None,
                  enable_timing=False, frames_in_flight=1, rank_mode=_capi.RANK_AUTO, frame_mode=None,
@@ -990,19 +1003,11 @@ class SplatRenderer:
             raise ValueError("%s must live on device %d, not on %s" % (name, self._device, t.device))
         return t
 
-    def RenderScores(self, cameraMat, projMat, viewport, nearFar, window=None, region=None, score=None, pixels=False):
-        """Per splat of the cloud (upload numbering) what it contributes to the view: score[i] += the sum over the pixels of
-        window = (x0, y0, w, h) (viewport pixels, row 0 = GL bottom; None = the whole viewport) of rint(T_i w_i 2^23), over the
-        splats of the latest Sort; _capi.SCORE_ONE is one fully covered pixel.  region: an (h, w) uint8 / bool plane of the WINDOW,
-        nonzero = the pixel counts -- a torch tensor on this renderer's device (rows may be strided) or a numpy array; None = all.
-        Returns a torch int64 tensor on the renderer's device (the values stay below 2^63), or (score, hits) with pixels=True
-        (or an int32 tensor): hits[i] += the number of those pixels with a nonzero term.  score=None allocates zeroed tensors,
-        waits for the frame and runs it once more from fresh zeros if the pair buffer overflowed; a given score (int64) / pixels
-        (int32) tensor is accumulated into -- one call per camera sums over views -- asynchronously on the context's stream,
-        which torch's current stream is made to wait for.  ValueError for arguments that cannot be right, before the library is
-        called."""
+    def _window_and_region(self, window, region):
+        """the window and region arguments of RenderScores / MarkView for the viewport self._args holds, as the library takes them:
+        (c_int32[4] or None, the region tensor -- kept alive by the caller --, its pointer or None, its pitch).  ValueError for
+        arguments that cannot be right"""
         import torch
-        f = self._args.load(cameraMat, projMat, viewport, nearFar)
         W, H = int(self._args.vp[2]), int(self._args.vp[3])
         if window is None:
             win, (w, h) = None, (W, H)
@@ -1024,6 +1029,23 @@ class SplatRenderer:
             if region.device != dev:
                 raise ValueError("region must live on %s, not on %s" % (dev, region.device))
             region_ptr, region_pitch = C.c_void_p(region.data_ptr()), (region.stride(0) if h > 1 else w)
+        return win, region, region_ptr, region_pitch
+
+    def RenderScores(self, cameraMat, projMat, viewport, nearFar, window=None, region=None, score=None, pixels=False):
+        """Per splat of the cloud (upload numbering) what it contributes to the view: score[i] += the sum over the pixels of
+        window = (x0, y0, w, h) (viewport pixels, row 0 = GL bottom; None = the whole viewport) of rint(T_i w_i 2^23), over the
+        splats of the latest Sort; _capi.SCORE_ONE is one fully covered pixel.  region: an (h, w) uint8 / bool plane of the WINDOW,
+        nonzero = the pixel counts -- a torch tensor on this renderer's device (rows may be strided) or a numpy array; None = all.
+        Returns a torch int64 tensor on the renderer's device (the values stay below 2^63), or (score, hits) with pixels=True
+        (or an int32 tensor): hits[i] += the number of those pixels with a nonzero term.  score=None allocates zeroed tensors,
+        waits for the frame and runs it once more from fresh zeros if the pair buffer overflowed; a given score (int64) / pixels
+        (int32) tensor is accumulated into -- one call per camera sums over views -- asynchronously on the context's stream,
+        which torch's current stream is made to wait for.  ValueError for arguments that cannot be right, before the library is
+        called."""
+        import torch
+        f = self._args.load(cameraMat, projMat, viewport, nearFar)
+        dev = torch.device("cuda", self._device)
+        win, region, region_ptr, region_pitch = self._window_and_region(window, region)
         own = score is None
         if own and isinstance(pixels, torch.Tensor):
             raise ValueError("a pixels tensor goes with a score tensor: both are accumulated into")
@@ -1080,6 +1102,73 @@ class SplatRenderer:
         _capi.check(self._ctx, self._lib.msplat_mark_scores(self._ctx, C.c_void_p(score.data_ptr()), self._n, _capi.SCORE_OPS[op], threshold,
                                                             C.c_void_p(mask.data_ptr()), value))
         self.wait_on_stream(torch.cuda.current_stream(dev).cuda_stream)
+
+    # -- selection by position (msplat_mark_volume / msplat_mark_view / msplat_measure_cloud) --
+    def _mark_target(self, who, mask, value):
+        """MarkScores' checks of a mask tensor and a byte; torch's current stream has completed on return"""
+        import torch
+        value = int(value)
+        if not 0 <= value <= 255:
+            raise ValueError("value is one byte, 0..255 (got %d)" % value)
+        if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.uint8, torch.bool):
+            raise ValueError("mask must be a torch uint8 / bool tensor")
+        self._device_vector("mask", mask, mask.dtype)
+        if not self._ctx:
+            raise _capi.MsplatError(_capi.ERR_NO_CLOUD, "%s: no cloud (Init first)" % who)
+        torch.cuda.current_stream(torch.device("cuda", self._device)).synchronize()
+        return value
+
+    def MarkVolume(self, worldToVolume, mask, value, shape="box", invert=False):
+        """mask[i] = value for every splat whose centre lies in the volume (invert: outside it); other bytes stay
+        (msplat_mark_volume).  worldToVolume, shape, invert: exactly SetCrop's arguments and SetCrop's fp32 rule -- a centre on
+        the surface is inside, a NaN centre outside -- applied to the cloud itself: splats a mask or a crop hides are marked like
+        any other.  mask: a torch uint8 / bool tensor of N bytes on this renderer's device, what SetVisibility, SetOverlay and the
+        select= of the cloud edits take.  No Sort is needed.  Asynchronous on the current context's stream; torch's current
+        stream is made to wait for it."""
+        import torch
+        if shape not in _capi.CROP_SHAPES:
+            raise ValueError("shape must be one of %s (got %r)" % (sorted(_capi.CROP_SHAPES), shape))
+        m = np.ascontiguousarray(_FrameArgs._flat(worldToVolume, 16))
+        value = self._mark_target("MarkVolume", mask, value)
+        code = _capi.CROP_SHAPES[shape] | (_capi.CROP_INVERT if invert else 0)
+        _capi.check(self._ctx, self._lib.msplat_mark_volume(self._ctx, m.ctypes.data_as(C.POINTER(C.c_float)), code, C.c_void_p(mask.data_ptr()),
+                                                            self._n, value))
+        self.wait_on_stream(torch.cuda.current_stream(torch.device("cuda", self._device)).cuda_stream)
+
+    def MarkView(self, cameraMat, projMat, viewport, nearFar, mask, value, window=None, region=None):
+        """Select through: mask[i] = value for every splat in front of the camera whose projected CENTRE falls on a pixel of
+        window = (x0, y0, w, h) (viewport pixels, row 0 = GL bottom; None = the whole viewport) that region selects -- an (h, w)
+        uint8 / bool plane of the window as RenderScores takes it; None = all; other bytes stay (msplat_mark_view).  Occluded
+        splats are marked like visible ones: a rectangle or lasso takes the whole object, not its visible skin; intersect with a
+        RenderScores mask for the visible part.  The cloud itself is tested, whatever a mask or crop hides; no Sort is needed;
+        nearFar is not read.  Asynchronous on the current context's stream; torch's current stream is made to wait for it."""
+        import torch
+        f = self._args.load(cameraMat, projMat, viewport, nearFar)
+        win, region, region_ptr, region_pitch = self._window_and_region(window, region)
+        value = self._mark_target("MarkView", mask, value)
+        _capi.check(self._ctx, self._lib.msplat_mark_view(self._ctx, *f, win, region_ptr, region_pitch, C.c_void_p(mask.data_ptr()), self._n, value))
+        self.wait_on_stream(torch.cuda.current_stream(torch.device("cuda", self._device)).cuda_stream)
+
+    def MeasureCloud(self, select=None):
+        """Where a selection is (msplat_measure_cloud): a dict of selected, finite (ints), lo, hi (float32[3]), reach2_max
+        (float32), sum (float64[3]), sum2 (float64[6]: xx yy zz xy xz yz) over the splats with select[i] (None: all; N values as
+        TransformCloud takes them) -- finite and everything after it over the finite centres among them -- plus, derived here in
+        float64, mean (None when finite == 0) and covariance (3 x 3, the population covariance sum2 / finite - mean mean^T).  The
+        cloud itself is measured, whatever a mask or crop hides.  Synchronous."""
+        if not self._ctx:
+            raise _capi.MsplatError(_capi.ERR_NO_CLOUD, "MeasureCloud: no cloud (Init first)")
+        sel = self._device_select(select, self._n)
+        m = _capi.CloudMeasure(struct_size=C.sizeof(_capi.CloudMeasure))
+        _capi.check(self._ctx, self._lib.msplat_measure_cloud(self._ctx, sel, self._n, C.byref(m)))
+        out = dict(selected=int(m.selected), finite=int(m.finite), lo=np.array(m.lo, np.float32), hi=np.array(m.hi, np.float32),
+                   reach2_max=np.float32(m.reach2_max), sum=np.array(m.sum, np.float64), sum2=np.array(m.sum2, np.float64))
+        out["mean"] = out["covariance"] = None
+        if out["finite"]:
+            mean = out["sum"] / out["finite"]
+            xx, yy, zz, xy, xz, yz = out["sum2"] / out["finite"]
+            out["mean"] = mean
+            out["covariance"] = np.array([[xx, xy, xz], [xy, yy, yz], [xz, yz, zz]]) - np.outer(mean, mean)
+        return out
 
     def synchronize(self):
         """blocks until every frame in flight has been issued (async_submit) AND has finished on the GPU"""
@@ -1151,6 +1240,19 @@ class SplatRenderer:
         a, b, l = C.c_uint32(), C.c_uint32(), C.c_int()
         _capi.check(self._ctx, self._lib.msplat_debug_get_cull_boxes(self._ctx, C.byref(a), C.byref(b), C.byref(l)))
         return a.value, b.value, bool(l.value)
+
+    def debug_positions(self):
+        """the store's position plane as the kernels read it (msplat_debug_get_positions): (N, 4) float32 of x, y, z and the
+        footprint bound, in UPLOAD numbering (the storage order undone); synchronises"""
+        out = np.zeros((max(self._n, 1), 4), np.float32)
+        _capi.check(self._ctx, self._lib.msplat_debug_get_positions(self._ctx, out.ctypes.data_as(C.POINTER(C.c_float)), out.size))
+        out = out[:self._n]
+        order = self.storage_order()
+        if order is not None:
+            up = np.empty_like(out)
+            up[order] = out
+            out = up
+        return out
 
     def sorted_keys(self):
         out = np.empty(max(self._n, 1), np.uint32)
