@@ -111,7 +111,8 @@ int msplat_debug_sh_q8_round(const float rec_in[61], float rec_out[61], float st
  * included; -1 when nothing was kept).  tools/compact_timing.py.  After msplat_transform_cloud: transform_kernel alone (-1 for an
  * empty cloud).  tools/transform_timing.py.  After msplat_append_cloud: its gathers and append_convert_kernel, without the scan
  * (-1 for an empty result).  tools/append_timing.py.  After msplat_adjust_cloud: adjust_kernel alone (-1 for an empty cloud).
- * tools/adjust_timing.py.  After msplat_measure_cloud: its two kernels (-1 for an empty cloud).  tools/select_timing.py ---- */
+ * tools/adjust_timing.py.  After msplat_measure_cloud: its two kernels (-1 for an empty cloud).  tools/select_timing.py.  After
+ * msplat_histogram_values: its two kernels, without the clearing of the counts (-1 for an empty cloud).  tools/values_timing.py ---- */
 int msplat_debug_upload_kernel_ms(msplat_ctx* ctx, float* ms);
 
 /* ---- the store's position plane as the kernels read it: N x (x, y, z, footprint bound) in STORAGE order (msplat_get_storage_order

@@ -39,6 +39,12 @@ SCORE_ONE = 8388608           # MSPLAT_SCORE_ONE: what one fully covered pixel a
 SCORE_BELOW, SCORE_AT_LEAST = 0, 1   # msplat_mark_scores: the compare
 SCORE_OPS = {"below": SCORE_BELOW, "at_least": SCORE_AT_LEAST}
 CROP_SHAPES = {"box": CROP_BOX, "sphere": CROP_SPHERE}
+# msplat_cloud_values: what a splat is, one float per splat (MSPLAT_VALUE_*); msplat_mark_values: the side of the closed range
+VALUE_KINDS = {"x": 0, "y": 1, "z": 2, "reach2": 3, "distance2": 4, "alpha": 5, "red": 6, "green": 7, "blue": 8, "colour_dist2": 9,
+               "scale_min": 10, "scale_mid": 11, "scale_max": 12}
+VALUE_KINDS_WITH_PARAM = ("distance2", "colour_dist2")
+RANGE_INSIDE, RANGE_OUTSIDE = 0, 1
+VALUE_BINS_MAX = 4096
 # "weighted": contiguous bands, rank 0 (the gather's root) weighted block_rows PERCENT of another rank (msplat.h)
 BAND_KINDS = {"contiguous": BANDS_CONTIGUOUS, "interleaved": BANDS_INTERLEAVED, "block": BANDS_BLOCK_INTERLEAVED,
               "weighted": BANDS_ROOT_WEIGHTED}
@@ -87,6 +93,12 @@ class CloudMeasure(C.Structure):
     """msplat_cloud_measure (msplat_measure_cloud, msplat_measure_box)"""
     _fields_ = [("struct_size", C.c_uint32), ("selected", C.c_uint64), ("finite", C.c_uint64), ("lo", C.c_float * 3), ("hi", C.c_float * 3),
                 ("reach2_max", C.c_float), ("sum", C.c_double * 3), ("sum2", C.c_double * 6)]
+
+
+class ValueSummary(C.Structure):
+    """msplat_value_summary (msplat_histogram_values)"""
+    _fields_ = [("struct_size", C.c_uint32), ("selected", C.c_uint64), ("finite", C.c_uint64), ("nan", C.c_uint64), ("below", C.c_uint64),
+                ("above", C.c_uint64), ("vmin", C.c_float), ("vmax", C.c_float)]
 
 
 class Timings(C.Structure):
@@ -168,6 +180,10 @@ SYMBOLS = [
                                    C.c_uint8]),
     ("msplat_measure_cloud", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(CloudMeasure)]),
     ("msplat_measure_box", C.c_int, [C.POINTER(CloudMeasure), C.c_float, _F16]),
+    ("msplat_cloud_values", C.c_int, [C.c_void_p, C.c_int32, _F16, C.c_void_p, C.c_uint64]),
+    ("msplat_mark_values", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_float, C.c_float, C.c_int32, C.c_void_p, C.c_uint8]),
+    ("msplat_histogram_values", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_float, C.c_float, C.c_uint32, _U32P,
+                                          C.POINTER(ValueSummary)]),
     ("msplat_debug_get_positions", C.c_int, [C.c_void_p, _F16, C.c_uint64]),
     ("msplat_synchronize", C.c_int, [C.c_void_p]),
     ("msplat_read_image", C.c_int, [C.c_char_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),

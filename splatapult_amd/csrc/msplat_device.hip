@@ -218,6 +218,7 @@ struct msplat_ctx {
     bool ov_tints = false;      // ... and whether one of them has a != 0
     StagingSlot ov_stage[2];    // what the latest host classes' / palette's copy reads
     Buf measure_rows;           // msplat_measure_cloud's scratch (msplat_select.hip.h): MeasureRow[kGridCap] partials, then the total; first use
+    Buf value_hist;             // msplat_histogram_values' scratch (msplat_values.hip.h): uint32[4096] counts, ValueRow[kGridCap] partials, the total; first use
     uint32_t sort_parity = 0;
     bool tables_dirty = false;  // a launch failed: clear every self-cleaning table before the next frame
     // per-bin pair counts taken by the row pass's upsweep (r3): list offsets + work order (no kernel of their own)
@@ -1980,6 +1981,7 @@ int msplat_render_stereo_layers(msplat_ctx* ctx, const float cameraMat0[16], con
 #include "msplat_ids.hip.inc"
 #include "msplat_scores.hip.inc"
 #include "msplat_select.hip.inc"
+#include "msplat_values.hip.inc"
 
 #include "msplat_getters.hip.inc"
 

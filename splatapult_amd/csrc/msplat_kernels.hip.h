@@ -1,4 +1,4 @@
-// msplat_kernels.hip.h -- hand-written CDNA4 (gfx950, wave64) kernels of the splat hot path, in seventeen parts.
+// msplat_kernels.hip.h -- hand-written CDNA4 (gfx950, wave64) kernels of the splat hot path, in eighteen parts.
 //
 // Replaces (not ports) the reference's GL pipeline:
 //   shader/presort_compute.glsl + shader/multi_radixsort*.glsl  -> msplat_sort.hip.h      radix_* / ws_* (cull fused in pass 0)
@@ -10,6 +10,7 @@
 //   splats tinted by class at render time (no reference part)   -> msplat_overlay.hip.h   overlay_kernel, overlay_classes_kernel
 //   GaussianCloud::ImportPly's per-vertex math, storage order   -> msplat_cloud.hip.h     ingest_kernel, morton / gather / cull boxes
 //   splats selected by position, a selection measured (no ref.) -> msplat_select.hip.h    mark_volume_kernel, mark_view_kernel, measure_cloud_*
+//   splats selected by attribute: values, range, histogram      -> msplat_values.hip.h    cloud_values_kernel, mark_values_kernel, histogram_values_*
 //   a mask or crop made permanent (no reference part)          -> msplat_compact.hip.h   compact_* (flags, count, offsets, index, gather)
 //   splats moved, rotated, scaled in the store (no ref. part)   -> msplat_transform.hip.h transform_kernel
 //   splats of a second cloud appended (no reference part)       -> msplat_append.hip.h    append_* (flags, map, gather, convert)
@@ -32,6 +33,7 @@
 #include "msplat_append.hip.h"
 #include "msplat_adjust.hip.h"
 #include "msplat_download.hip.h"
+#include "msplat_values.hip.h"
 #include "msplat_project.hip.h"
 #include "msplat_binning.hip.h"
 #include "msplat_composite.hip.h"

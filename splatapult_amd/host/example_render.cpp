@@ -3,7 +3,7 @@
 // Sort + Render into an explicit RGBA32F framebuffer, dumped as a binary PPM-like float file.
 //
 //   g++ -std=c++17 -I. splatapult_amd/host/example_render.cpp -Lsplatapult_amd/lib -lmsplat -o example_render
-//   ./example_render scene.ply out.f32 [width height] [--nosh] [--frames-in-flight N] [--devices 0,1,2,...] [--over-gradient] [--depth out_depth.f32] [--srgb8 out.png] [--crop-sphere cx cy cz r] [--pick X,Y] [--min-score S] [--highlight R,G,B,A] [--compact] [--append OTHER.ply] [--save OUT.ply] [--fade S] [--tint R,G,B,A] [--select-sphere CX,CY,CZ,R]
+//   ./example_render scene.ply out.f32 [width height] [--nosh] [--frames-in-flight N] [--devices 0,1,2,...] [--over-gradient] [--depth out_depth.f32] [--srgb8 out.png] [--crop-sphere cx cy cz r] [--pick X,Y] [--min-score S] [--highlight R,G,B,A] [--compact] [--append OTHER.ply] [--save OUT.ply] [--fade S] [--tint R,G,B,A] [--select-sphere CX,CY,CZ,R] [--min-alpha T]
 // With --frames-in-flight N the same frame is issued N + 1 times round-robin over N contexts that share the cloud
 // (SplatRenderer::SetFramesInFlight); the last one is written.  With --devices the frame's bin rows are dealt to the
 // listed GPUs (SplatRenderer::ConfigureDevices, msplat_group_*): same pixels.  With --over-gradient the target is first filled with
@@ -31,6 +31,10 @@
 // With --select-sphere CX,CY,CZ,R every splat whose centre lies in that sphere is marked into a device mask (SplatRenderer::MarkVolume,
 // msplat_mark_volume: the crop's rule, hidden and occluded splats included) and the selection's count, box, centroid and reach are
 // printed (SplatRenderer::MeasureCloud); with --highlight the selection is tinted and the frame rendered again.  One device, one frame in flight.
+// With --min-alpha T a 16-bin histogram of every splat's longest axis (SplatRenderer::CloudValues with MSPLAT_VALUE_SCALE_MAX,
+// SplatRenderer::HistogramValues: first the range, then the counts) is printed, the splats with alpha below T are hidden
+// (MSPLAT_VALUE_ALPHA, SplatRenderer::MarkValues of 0 into a mask of ones, SetVisibilityDevice) and the frame is sorted and rendered
+// again.  One device, one frame in flight.
 // With --compact, after --min-score / --crop-sphere, the hidden splats are dropped for good (SplatRenderer::CompactCloud,
 // msplat_compact_cloud: the kept records gathered into a new store on the device), the splat counts before and after are printed and
 // the frame is sorted and rendered once more from the smaller cloud: the same pixels.  One device only.
@@ -91,6 +95,7 @@ int main(int argc, char** argv)
     std::vector<int> devices;
     float cropSphere[4] = {0.0f, 0.0f, 0.0f, 0.0f};       // centre, radius; radius 0: no crop
     float selectSphere[4] = {0.0f, 0.0f, 0.0f, 0.0f};     // --select-sphere: centre, radius; radius 0: not given
+    float minAlpha = -1.0f;          // --min-alpha: hide the splats whose alpha is below it; < 0: not given
     for (int i = 3; i < argc; ++i) {
         if (!std::strcmp(argv[i], "--select-sphere") && i + 1 < argc &&
             std::sscanf(argv[i + 1], "%f,%f,%f,%f", &selectSphere[0], &selectSphere[1], &selectSphere[2], &selectSphere[3]) != 4)
@@ -110,6 +115,7 @@ int main(int argc, char** argv)
         if (!std::strcmp(argv[i], "--highlight") && i + 1 < argc &&
             std::sscanf(argv[i + 1], "%f,%f,%f,%f", &highlight[4], &highlight[5], &highlight[6], &highlight[7]) != 4)
             highlight[7] = -1.0f;
+        if (!std::strcmp(argv[i], "--min-alpha") && i + 1 < argc) minAlpha = (float)std::atof(argv[i + 1]);
         if (!std::strcmp(argv[i], "--fade") && i + 1 < argc) fade = (float)std::atof(argv[i + 1]);
         if (!std::strcmp(argv[i], "--tint") && i + 1 < argc && std::sscanf(argv[i + 1], "%f,%f,%f,%f", &tintTo[0], &tintTo[1], &tintTo[2], &tintTo[3]) != 4)
             tintTo[3] = -1.0f;
@@ -271,6 +277,39 @@ int main(int argc, char** argv)
             std::printf("the selection is highlighted\n");
         }
         renderer.Synchronize();
+        dm.release(mask);
+    }
+
+    if (minAlpha >= 0.0f && inFlight == 1 && devices.size() <= 1) {
+        const size_t n = cloud->GetNumGaussians();
+        DeviceMemory dm;
+        void *values = nullptr, *mask = nullptr;
+        if (!dm.Load() || dm.alloc(&values, n * 4) != 0 || dm.alloc(&mask, n) != 0 || dm.fill(mask, 1, n) != 0 || dm.wait() != 0) return 1;
+        float* v = static_cast<float*>(values);
+        // the longest axis of every splat: the summary alone gives the range, a second call the 16 counts over it
+        // (the printed edges are vmin + (vmax - vmin) b / 16 in fp32, for reading only: a value is counted by the library's rule,
+        //  t = (v - lo) * scale, so a value within an ulp or two of a printed edge may sit in the neighbouring bin)
+        msplat_value_summary sum;
+        uint32_t counts[16] = {};
+        if (!renderer.CloudValues(MSPLAT_VALUE_SCALE_MAX, nullptr, v, n) || !renderer.HistogramValues(v, nullptr, n, 0.0f, 0.0f, 0, nullptr, &sum)) return 1;
+        std::printf("longest axis: %llu finite of %llu, %g .. %g (bin edges below are approximate)\n", (unsigned long long)sum.finite, (unsigned long long)sum.selected, sum.vmin, sum.vmax);
+        if (sum.finite && sum.vmin < sum.vmax && renderer.HistogramValues(v, nullptr, n, sum.vmin, sum.vmax, 16, counts, &sum))
+            for (int b = 0; b < 16; ++b)
+                std::printf("  [%10.4g, %10.4g%c %u\n", sum.vmin + (sum.vmax - sum.vmin) * (float)b / 16.0f,
+                            sum.vmin + (sum.vmax - sum.vmin) * (float)(b + 1) / 16.0f, b == 15 ? ']' : ')', counts[b]);
+        // alpha < T: outside [T, +inf] (a NaN alpha goes too)
+        if (!renderer.CloudValues(MSPLAT_VALUE_ALPHA, nullptr, v, n) ||
+            !renderer.MarkValues(v, n, minAlpha, INFINITY, MSPLAT_RANGE_OUTSIDE, static_cast<uint8_t*>(mask), 0) ||
+            !renderer.SetVisibilityDevice(static_cast<const uint8_t*>(mask), n))
+            return 1;
+        renderer.Sort(cameraMat, projMat, viewport, nearFar);
+        if (depthPath) renderer.RenderWithDepth(cameraMat, projMat, viewport, nearFar, depth.data());
+        else renderer.Render(cameraMat, projMat, viewport, nearFar);
+        renderer.Synchronize();
+        uint64_t hidden = 0;
+        if (msplat_get_visibility(renderer.GetContext(), nullptr, nullptr, &hidden) != MSPLAT_OK) return 1;
+        std::printf("min alpha %g: %llu of %zu splats hidden\n", minAlpha, (unsigned long long)hidden, n);
+        dm.release(values);
         dm.release(mask);
     }
 

@@ -598,11 +598,30 @@ public:
         std::fprintf(stderr, "[msplat][E] MeasureBox: %s\n", msplat_last_error(nullptr));
         return false;
     }
+    // Selection by attribute (msplat_cloud_values, msplat_mark_values, msplat_histogram_values): the same contract.
+    // CloudValues: d_values[i] = what splat i is (kind = MSPLAT_VALUE_*; param: the point of _DISTANCE2, the colour of _COLOUR_DIST2).
+    bool CloudValues(int32_t kind, const float* param, float* d_values, size_t n)
+    {
+        return Select("CloudValues", [&](msplat_ctx* h) { return msplat_cloud_values(h, kind, param, d_values, n); });
+    }
+    // MarkValues: d_mask[i] = value where lo <= d_values[i] <= hi (op = MSPLAT_RANGE_INSIDE) or where not (_OUTSIDE: NaN values too).
+    bool MarkValues(const float* d_values, size_t n, float lo, float hi, int32_t op, uint8_t* d_mask, uint8_t value)
+    {
+        return Select("MarkValues", [&](msplat_ctx* h) { return msplat_mark_values(h, d_values, n, lo, hi, op, d_mask, value); });
+    }
+    // HistogramValues: `bins` counts over [lo, hi] into counts (host memory) and the summary of the values d_select selects (nullptr:
+    // all) into *out; bins == 0: the summary alone.
+    bool HistogramValues(const float* d_values, const uint8_t* d_select, size_t n, float lo, float hi, uint32_t bins, uint32_t* counts,
+                         msplat_value_summary* out)
+    {
+        if (out) out->struct_size = sizeof(msplat_value_summary);
+        return Select("HistogramValues", [&](msplat_ctx* h) { return msplat_histogram_values(h, d_values, d_select, n, lo, hi, bins, counts, out); });
+    }
     template <class Call>
     bool Select(const char* who, Call&& call)
     {
         if (group || !ctx) {
-            std::fprintf(stderr, "[msplat][E] %s: %s\n", who, group ? "a device group has no selection by position" : "no cloud (Init first)");
+            std::fprintf(stderr, "[msplat][E] %s: %s\n", who, group ? "a device group has no selection by position or attribute" : "no cloud (Init first)");
             return false;
         }
         const int rc = call(ctx);

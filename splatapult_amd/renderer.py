@@ -1170,6 +1170,94 @@ class SplatRenderer:
             out["covariance"] = np.array([[xx, xy, xz], [xy, yy, yz], [xz, yz, zz]]) - np.outer(mean, mean)
         return out
 
+    # -- selection by attribute (msplat_cloud_values / msplat_mark_values / msplat_histogram_values) --
+    def CloudValues(self, kind, param=None, out=None):
+        """What every splat is, one float32 per splat in upload numbering (msplat_cloud_values).  kind: a name of
+        _capi.VALUE_KINDS ("x", "y", "z", "reach2", "distance2", "alpha", "red", "green", "blue", "colour_dist2", "scale_min",
+        "scale_mid", "scale_max") or its MSPLAT_VALUE_* number; param: three floats, the point of "distance2" or the colour of
+        "colour_dist2" (no other kind takes one).  out: a float32 tensor of N values on this renderer's device to write into
+        (None: a new one).  The cloud itself is read, whatever a mask or crop hides; no Sort is needed.  Asynchronous on the
+        current context's stream; torch's current stream is made to wait for it.  Returns the tensor."""
+        import torch
+        if isinstance(kind, str):
+            if kind not in _capi.VALUE_KINDS:
+                raise ValueError("kind must be one of %s (got %r)" % (sorted(_capi.VALUE_KINDS), kind))
+            code = _capi.VALUE_KINDS[kind]
+        else:
+            code = int(kind)
+            if code not in _capi.VALUE_KINDS.values():
+                raise ValueError("kind %r is not an MSPLAT_VALUE_* number" % (kind,))
+        needs = code in tuple(_capi.VALUE_KINDS[k] for k in _capi.VALUE_KINDS_WITH_PARAM)
+        if needs != (param is not None):
+            raise ValueError("param goes with the kinds %s and with no other" % (_capi.VALUE_KINDS_WITH_PARAM,))
+        p = None
+        if needs:
+            p = np.zeros(4, np.float32)
+            p[0:3] = np.asarray(param, np.float64).reshape(3)
+            if not np.isfinite(p).all():
+                raise ValueError("param must be three finite floats (got %r)" % (param,))
+        if not self._ctx:
+            raise _capi.MsplatError(_capi.ERR_NO_CLOUD, "CloudValues: no cloud (Init first)")
+        dev = torch.device("cuda", self._device)
+        if out is None:
+            out = torch.empty(self._n, dtype=torch.float32, device=dev)
+        else:
+            self._device_vector("out", out, torch.float32)
+        torch.cuda.current_stream(dev).synchronize()
+        _capi.check(self._ctx, self._lib.msplat_cloud_values(self._ctx, code, p.ctypes.data_as(C.POINTER(C.c_float)) if needs else None,
+                                                             C.c_void_p(out.data_ptr()), self._n))
+        self.wait_on_stream(torch.cuda.current_stream(dev).cuda_stream)
+        return out
+
+    def MarkValues(self, values, lo, hi, mask, value, outside=False):
+        """mask[i] = value for every splat whose values[i] lies in the closed range lo <= v <= hi (outside=True: for every other
+        one, NaN values included); other bytes stay (msplat_mark_values).  values: a float32 tensor of N values on this
+        renderer's device, what CloudValues returns; mask: a torch uint8 / bool tensor of N bytes, what SetVisibility and the
+        select= of the cloud edits take.  lo and hi may be infinite; lo > hi is an empty range.  Asynchronous on the current
+        context's stream; torch's current stream is made to wait for it."""
+        import torch
+        lo, hi = float(lo), float(hi)
+        if lo != lo or hi != hi:
+            raise ValueError("lo and hi must not be NaN (got %r, %r)" % (lo, hi))
+        self._device_vector("values", values, torch.float32)
+        value = self._mark_target("MarkValues", mask, value)
+        _capi.check(self._ctx, self._lib.msplat_mark_values(self._ctx, C.c_void_p(values.data_ptr()), self._n, lo, hi,
+                                                            _capi.RANGE_OUTSIDE if outside else _capi.RANGE_INSIDE, C.c_void_p(mask.data_ptr()), value))
+        self.wait_on_stream(torch.cuda.current_stream(torch.device("cuda", self._device)).cuda_stream)
+
+    def HistogramValues(self, values, bins=0, lo=None, hi=None, select=None):
+        """Histogram and summary of values[i] over the splats with select[i] (None: all; N values as TransformCloud takes them)
+        (msplat_histogram_values): a dict of selected, finite, nan, below, above (ints), vmin, vmax (float32: the extremes of the
+        finite values, +inf / -inf when there is none) and counts (numpy uint32[bins]).  bins=0 (lo, hi not given): the summary
+        alone, the first call of a range slider.  1 <= bins <= 4096: finite lo < hi; bin b counts the values with
+        b <= (v - lo) * bins / (hi - lo) < b + 1, v == hi in the last bin; below / above count the values outside [lo, hi],
+        infinities included.  Synchronous."""
+        import torch
+        bins = int(bins)
+        if not 0 <= bins <= _capi.VALUE_BINS_MAX:
+            raise ValueError("bins must be 0 .. %d (got %d)" % (_capi.VALUE_BINS_MAX, bins))
+        if bins == 0:
+            if lo is not None or hi is not None:
+                raise ValueError("lo and hi go with bins > 0")
+            lo = hi = 0.0
+        else:
+            if lo is None or hi is None:
+                raise ValueError("bins > 0 needs lo and hi")
+            lo, hi = float(lo), float(hi)
+            if not (np.isfinite(lo) and np.isfinite(hi) and lo < hi):
+                raise ValueError("lo and hi must be finite with lo < hi (got %r, %r)" % (lo, hi))
+        self._device_vector("values", values, torch.float32)
+        if not self._ctx:
+            raise _capi.MsplatError(_capi.ERR_NO_CLOUD, "HistogramValues: no cloud (Init first)")
+        sel = self._device_select(select, self._n)
+        torch.cuda.current_stream(torch.device("cuda", self._device)).synchronize()
+        counts = np.zeros(bins, np.uint32)
+        s = _capi.ValueSummary(struct_size=C.sizeof(_capi.ValueSummary))
+        _capi.check(self._ctx, self._lib.msplat_histogram_values(self._ctx, C.c_void_p(values.data_ptr()), sel, self._n, lo, hi, bins,
+                                                                 counts.ctypes.data_as(C.POINTER(C.c_uint32)) if bins else None, C.byref(s)))
+        return dict(selected=int(s.selected), finite=int(s.finite), nan=int(s.nan), below=int(s.below), above=int(s.above),
+                    vmin=np.float32(s.vmin), vmax=np.float32(s.vmax), counts=counts)
+
     def synchronize(self):
         """blocks until every frame in flight has been issued (async_submit) AND has finished on the GPU"""
         for h in self._ctxs:
