@@ -31,7 +31,7 @@ int msplat_append_cloud(msplat_ctx* ctx, msplat_ctx* src, const uint8_t* d_selec
         return fail(ctx, MSPLAT_ERR_INVALID_ARG, "%s: n = %llu for a source of %llu splats", who, (unsigned long long)n, (unsigned long long)Ns);
     int rc;
     if (d_select && Ns && (rc = check_device_source(ctx, who, "d_select", d_select, Ns))) return rc;
-    if ((rc = check_index_map(ctx, who, d_index_map, Ns))) return rc;
+    if (d_index_map && (rc = check_device_array(ctx, who, "d_index_map", d_index_map, 4, Ns))) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (src != ctx) HIP_TRY(ctx, hipStreamSynchronize(src->stream));

@@ -14,7 +14,7 @@ int msplat_compact_cloud(msplat_ctx* ctx, uint32_t* d_index_map, uint64_t* n_kep
     int rc;
     if ((rc = require_splat_cloud(ctx, who, "visibility is for splat clouds"))) return rc;
     const uint64_t N = ctx->N;
-    if ((rc = check_index_map(ctx, who, d_index_map, N))) return rc;
+    if (d_index_map && (rc = check_device_array(ctx, who, "d_index_map", d_index_map, 4, N))) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if ((rc = ensure_order_dev(ctx))) return rc;

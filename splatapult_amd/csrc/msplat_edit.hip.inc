@@ -23,12 +23,36 @@ static int require_splat_cloud(msplat_ctx* ctx, const char* who, const char* for
     return MSPLAT_OK;
 }
 
-// an optional d_index_map of n words: aligned, device memory of the context's device
-static int check_index_map(msplat_ctx* ctx, const char* who, const uint32_t* p, uint64_t n)
+// a caller's array `what`: aligned to its elements of elem_bytes bytes ...
+static int check_aligned(msplat_ctx* ctx, const char* who, const char* what, const void* p, unsigned elem_bytes)
 {
-    if (!p) return MSPLAT_OK;
-    if ((uintptr_t)p % 4 != 0) return fail(ctx, MSPLAT_ERR_INVALID_ARG, "%s: d_index_map (%p) is not 4-byte aligned", who, (const void*)p);
-    return n ? check_device_source(ctx, who, "d_index_map", p, n * 4) : MSPLAT_OK;
+    if ((uintptr_t)p % elem_bytes == 0) return MSPLAT_OK;
+    return fail(ctx, MSPLAT_ERR_INVALID_ARG, "%s: %s (%p) is not %u-byte aligned", who, what, p, elem_bytes);
+}
+
+// ... and `count` of them in device memory of the context's device (none: nothing to query).  A NULL p is the caller's to refuse or allow
+static int check_device_array(msplat_ctx* ctx, const char* who, const char* what, const void* p, unsigned elem_bytes, uint64_t count)
+{
+    const int rc = check_aligned(ctx, who, what, p, elem_bytes);
+    return rc || count == 0 ? rc : check_device_source(ctx, who, what, p, elem_bytes * count);
+}
+
+// n bytes, one per splat in upload numbering (a mask, a selection), for the cloud the context holds.  for_what: require_splat_cloud's
+static int check_splat_count(msplat_ctx* ctx, const char* who, const char* for_what, uint64_t n)
+{
+    const int rc = require_splat_cloud(ctx, who, for_what, " (a mask is in the cloud's upload numbering)");
+    if (rc || n == ctx->N) return rc;
+    return fail(ctx, MSPLAT_ERR_INVALID_ARG, "%s: %llu mask bytes for a cloud of %llu splats", who, (unsigned long long)n, (unsigned long long)ctx->N);
+}
+
+// what the selection calls refuse first: check_splat_count, then the bytes -- `what`, device memory (NULL allowed where `optional`).
+// (msplat_mark_ids, msplat_mark_scores and set_mask have checks of their own between the two, so their order is written out there)
+static int check_splat_bytes(msplat_ctx* ctx, const char* who, const char* what, const void* d_bytes, uint64_t n, bool optional)
+{
+    const int rc = check_splat_count(ctx, who, "selection is for splat clouds", n);
+    if (rc || n == 0 || (optional && !d_bytes)) return rc;
+    if (!d_bytes) return fail(ctx, MSPLAT_ERR_INVALID_ARG, "%s: %s is NULL", who, what);
+    return check_device_source(ctx, who, what, d_bytes, n);
 }
 
 // a column-major 4x4 affine matrix `name`: rows 0..2 finite
@@ -71,6 +95,38 @@ struct KernelTimer {
     void stop(hipStream_t s) { if (on) (void)hipEventRecord(ev[1], s); }
     void read(msplat_ctx* ctx) { if (on && hipEventElapsedTime(&ctx->upload_kernel_ms, ev[0], ev[1]) != hipSuccess) ctx->upload_kernel_ms = -1.0f; }
 };
+
+extern "C++" {      // (templates)
+// ---- a mark's launch: one lane per item (splat, pixel), asynchronous on the context's stream ------------------------------------------
+template <class Kernel, class... Args>
+static int launch_per_item(msplat_ctx* ctx, const char* who, uint64_t items, Kernel kernel, const Args&... args)
+{
+    hipLaunchKernelGGL(kernel, dim3(div_up(items, kThreads)), dim3(kThreads), 0, ctx->stream, args...);
+    if (hipGetLastError() != hipSuccess) return fail(ctx, MSPLAT_ERR_HIP, "%s: the kernel launch failed", who);
+    return MSPLAT_OK;
+}
+
+// ---- the host side of a row reduction (msplat_rows.hip.h) over n items: part holds kGridCap + 1 rows, the partials and the total -------
+// launch_partial(grid, part) issues the call's grid-stride kernel, rows_finish_kernel folds its `grid` rows, and `row` is the total
+// once the stream has drained; more_copies() issues what else the call copies out before that.  (KernelTimer: both kernels)
+template <class Row, class Partial, class Copies>
+static int reduce_rows(msplat_ctx* ctx, const char* who, Row* part, uint64_t n, Row& row, Partial&& launch_partial, Copies&& more_copies)
+{
+    Row* total = part + kGridCap;
+    const int grid = grid_for(div_up(n, kThreads), ctx->grid_cap);
+    KernelTimer timer(ctx);
+    timer.start(ctx->stream);
+    launch_partial(grid, part);
+    hipLaunchKernelGGL(rows_finish_kernel<Row>, dim3(1), dim3(kThreads), 0, ctx->stream, (const Row*)part, (uint32_t)grid, total);
+    timer.stop(ctx->stream);
+    if (hipGetLastError() != hipSuccess) return fail(ctx, MSPLAT_ERR_HIP, "%s: a kernel launch failed", who);
+    HIP_TRY(ctx, hipMemcpyAsync(&row, total, sizeof(Row), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, more_copies());
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    timer.read(ctx);
+    return MSPLAT_OK;
+}
+}  // extern "C++"
 
 // ---- the pinned staging slot (StagingSlot, msplat_device.hip): host bytes to the device on a stream of the context's, the caller's
 // array free on return and no drain of the frames queued before ------------------------------------------------------------------

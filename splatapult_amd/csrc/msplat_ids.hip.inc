@@ -105,6 +105,21 @@ static int ids_pitch(msplat_ctx* ctx, const char* who, const char* what, uint64_
     return MSPLAT_OK;
 }
 
+// an optional region plane, one byte per pixel of a w x h window: its pitch (0 = tight rows; read only with a region) ...
+static int region_pitch(msplat_ctx* ctx, const char* who, const uint8_t* d_region, uint64_t& pitch_bytes, uint64_t w)
+{
+    if (pitch_bytes == 0) pitch_bytes = w;
+    if (!d_region || pitch_bytes >= w) return MSPLAT_OK;
+    return fail(ctx, MSPLAT_ERR_INVALID_ARG, "%s: region pitch %llu too small for %llu pixels of 1 byte", who, (unsigned long long)pitch_bytes,
+                (unsigned long long)w);
+}
+
+// ... and its rows: device memory of the context's device.  (Two functions: every caller has checks of its own between them)
+static int check_region(msplat_ctx* ctx, const char* who, const uint8_t* d_region, uint64_t pitch_bytes, uint64_t w, uint64_t h)
+{
+    return d_region ? check_device_source(ctx, who, "d_region", d_region, (h - 1) * pitch_bytes + w) : MSPLAT_OK;
+}
+
 struct IdsWindow { bool given; int32_t v[4]; };
 
 // a caller's window of a width x height viewport: not given = the whole viewport; else x0, y0, w, h, not empty and inside it
@@ -171,24 +186,15 @@ int msplat_mark_ids(msplat_ctx* ctx, const uint32_t* d_ids, uint64_t ids_pitch_b
     drain_async(ctx);
     if (!ctx) return fail(nullptr, MSPLAT_ERR_INVALID_ARG, "ctx is NULL");
     int rc;
-    if ((rc = require_splat_cloud(ctx, who, "visibility is for splat clouds", " (a mask is in the cloud's upload numbering)"))) return rc;
-    if (n != ctx->N)
-        return fail(ctx, MSPLAT_ERR_INVALID_ARG, "%s: %llu mask bytes for a cloud of %llu splats", who, (unsigned long long)n,
-                    (unsigned long long)ctx->N);
+    if ((rc = check_splat_count(ctx, who, "visibility is for splat clouds", n))) return rc;
     if (w == 0 || h == 0 || n == 0) return MSPLAT_OK;
     if (!d_ids || !d_mask) return fail(ctx, MSPLAT_ERR_INVALID_ARG, "%s: %s is NULL", who, d_ids ? "d_mask" : "d_ids");
-    if ((rc = ids_pitch(ctx, who, "ids", ids_pitch_bytes, w))) return rc;
-    if (region_pitch_bytes == 0) region_pitch_bytes = w;
-    if (d_region && region_pitch_bytes < w)
-        return fail(ctx, MSPLAT_ERR_INVALID_ARG, "%s: region pitch %llu too small for %u pixels of 1 byte", who,
-                    (unsigned long long)region_pitch_bytes, w);
-    if ((uintptr_t)d_ids % 4 != 0) return fail(ctx, MSPLAT_ERR_INVALID_ARG, "%s: d_ids (%p) is not 4-byte aligned", who, (const void*)d_ids);
+    if ((rc = ids_pitch(ctx, who, "ids", ids_pitch_bytes, w)) || (rc = region_pitch(ctx, who, d_region, region_pitch_bytes, w))) return rc;
+    if ((rc = check_aligned(ctx, who, "d_ids", d_ids, 4))) return rc;      // (a pitched extent: not check_device_array's)
     if ((rc = check_device_source(ctx, who, "d_ids", d_ids, (uint64_t)(h - 1) * ids_pitch_bytes + 4ull * w))) return rc;
-    if (d_region && (rc = check_device_source(ctx, who, "d_region", d_region, (uint64_t)(h - 1) * region_pitch_bytes + w))) return rc;
+    if ((rc = check_region(ctx, who, d_region, region_pitch_bytes, w, h))) return rc;
     if ((rc = check_device_source(ctx, who, "d_mask", d_mask, n))) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipLaunchKernelGGL(mark_ids_kernel, dim3((uint32_t)div_up((uint64_t)w * h, (uint64_t)kThreads)), dim3(kThreads), 0, ctx->stream, d_ids,
-                       (size_t)ids_pitch_bytes, w, h, d_region, (size_t)region_pitch_bytes, d_mask, (uint32_t)n, value);
-    if (hipGetLastError() != hipSuccess) return fail(ctx, MSPLAT_ERR_HIP, "%s: the kernel launch failed", who);
-    return MSPLAT_OK;
+    return launch_per_item(ctx, who, (uint64_t)w * h, mark_ids_kernel, d_ids, (size_t)ids_pitch_bytes, w, h, d_region, (size_t)region_pitch_bytes,
+                           d_mask, (uint32_t)n, value);
 }

@@ -1,4 +1,4 @@
-// msplat_kernels.hip.h -- hand-written CDNA4 (gfx950, wave64) kernels of the splat hot path, in eighteen parts.
+// msplat_kernels.hip.h -- hand-written CDNA4 (gfx950, wave64) kernels of the splat hot path, in nineteen parts.
 //
 // Replaces (not ports) the reference's GL pipeline:
 //   shader/presort_compute.glsl + shader/multi_radixsort*.glsl  -> msplat_sort.hip.h      radix_* / ws_* (cull fused in pass 0)
@@ -9,8 +9,9 @@
 //   what each splat contributes (no reference part)             -> msplat_scores.hip.h    composite_scores_kernel, mark_scores_kernel
 //   splats tinted by class at render time (no reference part)   -> msplat_overlay.hip.h   overlay_kernel, overlay_classes_kernel
 //   GaussianCloud::ImportPly's per-vertex math, storage order   -> msplat_cloud.hip.h     ingest_kernel, morton / gather / cull boxes
-//   splats selected by position, a selection measured (no ref.) -> msplat_select.hip.h    mark_volume_kernel, mark_view_kernel, measure_cloud_*
-//   splats selected by attribute: values, range, histogram      -> msplat_values.hip.h    cloud_values_kernel, mark_values_kernel, histogram_values_*
+//   splats selected by position, a selection measured (no ref.) -> msplat_select.hip.h    mark_volume_kernel, mark_view_kernel, measure_cloud_kernel
+//   splats selected by attribute: values, range, histogram      -> msplat_values.hip.h    cloud_values_kernel, mark_values_kernel, histogram_values_kernel
+//   the row reduction both measures end with (no ref. part)     -> msplat_rows.hip.h      row_reduce_store, rows_finish_kernel
 //   a mask or crop made permanent (no reference part)          -> msplat_compact.hip.h   compact_* (flags, count, offsets, index, gather)
 //   splats moved, rotated, scaled in the store (no ref. part)   -> msplat_transform.hip.h transform_kernel
 //   splats of a second cloud appended (no reference part)       -> msplat_append.hip.h    append_* (flags, map, gather, convert)
@@ -27,6 +28,7 @@
 #include "msplat_common.hip.h"
 #include "msplat_sort.hip.h"
 #include "msplat_cloud.hip.h"
+#include "msplat_rows.hip.h"
 #include "msplat_select.hip.h"
 #include "msplat_compact.hip.h"
 #include "msplat_transform.hip.h"

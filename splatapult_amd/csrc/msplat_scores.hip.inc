@@ -48,14 +48,11 @@ static int scores_impl(msplat_ctx* ctx, const float cameraMat[16], const float p
     if (n != ctx->N)
         return fail(ctx, MSPLAT_ERR_INVALID_ARG, "%s: %llu scores for a cloud of %llu splats", who, (unsigned long long)n,
                     (unsigned long long)ctx->N);
-    if (region_pitch_bytes == 0) region_pitch_bytes = (uint64_t)w[2];
-    if (d_region && region_pitch_bytes < (uint64_t)w[2])
-        return fail(ctx, MSPLAT_ERR_INVALID_ARG, "%s: region pitch %llu too small for %d pixels of 1 byte", who,
-                    (unsigned long long)region_pitch_bytes, w[2]);
-    if ((uintptr_t)d_score % 8 != 0) return fail(ctx, MSPLAT_ERR_INVALID_ARG, "%s: d_score (%p) is not 8-byte aligned", who, (const void*)d_score);
-    if ((uintptr_t)d_pixels % 4 != 0) return fail(ctx, MSPLAT_ERR_INVALID_ARG, "%s: d_pixels (%p) is not 4-byte aligned", who, (const void*)d_pixels);
+    if ((rc = region_pitch(ctx, who, d_region, region_pitch_bytes, w[2]))) return rc;
+    // (both alignments before any pointer query, and before an empty cloud succeeds: not check_device_array's order)
+    if ((rc = check_aligned(ctx, who, "d_score", d_score, 8)) || (rc = check_aligned(ctx, who, "d_pixels", d_pixels, 4))) return rc;
     if (n == 0) return MSPLAT_OK;
-    if (d_region && (rc = check_device_source(ctx, who, "d_region", d_region, (uint64_t)(w[3] - 1) * region_pitch_bytes + (uint64_t)w[2]))) return rc;
+    if ((rc = check_region(ctx, who, d_region, region_pitch_bytes, w[2], w[3]))) return rc;
     if ((rc = check_device_source(ctx, who, "d_score", d_score, 8 * n))) return rc;
     if (d_pixels && (rc = check_device_source(ctx, who, "d_pixels", d_pixels, 4 * n))) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -83,20 +80,14 @@ int msplat_mark_scores(msplat_ctx* ctx, const uint64_t* d_score, uint64_t n, int
     drain_async(ctx);
     if (!ctx) return fail(nullptr, MSPLAT_ERR_INVALID_ARG, "ctx is NULL");
     int rc;
-    if ((rc = require_splat_cloud(ctx, who, "visibility is for splat clouds", " (a mask is in the cloud's upload numbering)"))) return rc;
-    if (n != ctx->N)
-        return fail(ctx, MSPLAT_ERR_INVALID_ARG, "%s: %llu mask bytes for a cloud of %llu splats", who, (unsigned long long)n,
-                    (unsigned long long)ctx->N);
+    if ((rc = check_splat_count(ctx, who, "visibility is for splat clouds", n))) return rc;
     if (op != MSPLAT_SCORE_BELOW && op != MSPLAT_SCORE_AT_LEAST)
         return fail(ctx, MSPLAT_ERR_INVALID_ARG, "%s: op %d is neither MSPLAT_SCORE_BELOW nor MSPLAT_SCORE_AT_LEAST", who, op);
     if (n == 0) return MSPLAT_OK;
     if (!d_score || !d_mask) return fail(ctx, MSPLAT_ERR_INVALID_ARG, "%s: %s is NULL", who, d_score ? "d_mask" : "d_score");
-    if ((uintptr_t)d_score % 8 != 0) return fail(ctx, MSPLAT_ERR_INVALID_ARG, "%s: d_score (%p) is not 8-byte aligned", who, (const void*)d_score);
-    if ((rc = check_device_source(ctx, who, "d_score", d_score, 8 * n))) return rc;
+    if ((rc = check_device_array(ctx, who, "d_score", d_score, 8, n))) return rc;
     if ((rc = check_device_source(ctx, who, "d_mask", d_mask, n))) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipLaunchKernelGGL(mark_scores_kernel, dim3(div_up((uint32_t)n, kThreads)), dim3(kThreads), 0, ctx->stream,
-                       (const unsigned long long*)d_score, (uint32_t)n, op == MSPLAT_SCORE_AT_LEAST, (unsigned long long)threshold, d_mask, value);
-    if (hipGetLastError() != hipSuccess) return fail(ctx, MSPLAT_ERR_HIP, "%s: the kernel launch failed", who);
-    return MSPLAT_OK;
+    return launch_per_item(ctx, who, n, mark_scores_kernel, (const unsigned long long*)d_score, (uint32_t)n, op == MSPLAT_SCORE_AT_LEAST,
+                           (unsigned long long)threshold, d_mask, value);
 }

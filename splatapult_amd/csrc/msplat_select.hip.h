@@ -2,10 +2,11 @@
 // three functions of the store's 16-byte position plane.  The marks write one byte per selected splat into the caller's mask in
 // UPLOAD numbering (a store in Morton order: through its slot -> upload table); the measure reads such a mask.  None of them is part
 // of a frame: no Sort is needed and nothing of the context changes.  (Included by msplat_kernels.hip.h after msplat_cloud.hip.h,
-// whose crop_inside is the rule of the volume mark.)
+// whose crop_inside is the rule of the volume mark, and msplat_rows.hip.h, whose row reduction the measure is.)
 #pragma once
 
 #include "msplat_cloud.hip.h"
+#include "msplat_rows.hip.h"
 
 namespace msplat {
 
@@ -66,62 +67,36 @@ __global__ __launch_bounds__(kThreads) void mark_view_kernel(const MarkViewArgs 
     a.mask[a.order ? a.order[slot] : slot] = a.value;
 }
 
-// ---- msplat_measure_cloud: count, AABB, largest footprint bound and the first and second moments of the selected centres.  Two
-// stages in the shape of cloud_moments_kernel / cloud_moments_finish: no atomics and a summation order fixed by the grid, so a call
-// repeated on a context returns the same bytes.  The counts, the box and the bound do not depend on any order.
+// ---- msplat_measure_cloud: count, AABB, largest footprint bound and the first and second moments of the selected centres.  A row
+// reduction (msplat_rows.hip.h): no atomics and a summation order fixed by the grid, so a call repeated on a context returns the
+// same bytes.  The counts, the box and the bound do not depend on any order.
 constexpr int kMeasureSums = 9;         // x y z, xx yy zz xy xz yz
 struct MeasureRow {                     // what a lane, a wave, a workgroup and the whole cloud accumulate
     double s[kMeasureSums];
     float lo[3], hi[3];
     float reach;
     uint32_t selected, finite;          // (a cloud holds at most 2^24 splats)
+
+    __host__ __device__ __forceinline__ void clear()
+    {
+#pragma unroll
+        for (int k = 0; k < kMeasureSums; ++k) s[k] = 0.0;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { lo[k] = INFINITY; hi[k] = -INFINITY; }
+        reach = 0.0f;
+        selected = finite = 0u;
+    }
+    __device__ __forceinline__ void merge(const MeasureRow& o)
+    {
+#pragma unroll
+        for (int k = 0; k < kMeasureSums; ++k) s[k] += o.s[k];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { lo[k] = fminf(lo[k], o.lo[k]); hi[k] = fmaxf(hi[k], o.hi[k]); }
+        reach = fmaxf(reach, o.reach);
+        selected += o.selected;
+        finite += o.finite;
+    }
 };
-
-__device__ __forceinline__ void measure_clear(MeasureRow& r)
-{
-#pragma unroll
-    for (int k = 0; k < kMeasureSums; ++k) r.s[k] = 0.0;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) { r.lo[k] = INFINITY; r.hi[k] = -INFINITY; }
-    r.reach = 0.0f;
-    r.selected = r.finite = 0u;
-}
-
-__device__ __forceinline__ void measure_merge(MeasureRow& r, const MeasureRow& o)
-{
-#pragma unroll
-    for (int k = 0; k < kMeasureSums; ++k) r.s[k] += o.s[k];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) { r.lo[k] = fminf(r.lo[k], o.lo[k]); r.hi[k] = fmaxf(r.hi[k], o.hi[k]); }
-    r.reach = fmaxf(r.reach, o.reach);
-    r.selected += o.selected;
-    r.finite += o.finite;
-}
-
-// every lane's row -> one row per workgroup: butterflies inside the wave, then the waves' rows in wave order through LDS
-__device__ __forceinline__ void measure_reduce_store(MeasureRow& r, MeasureRow* __restrict__ out)
-{
-    __shared__ MeasureRow s_w[kThreads / 64];
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        MeasureRow o;
-#pragma unroll
-        for (int k = 0; k < kMeasureSums; ++k) o.s[k] = __shfl_xor(r.s[k], d, 64);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) { o.lo[k] = __shfl_xor(r.lo[k], d, 64); o.hi[k] = __shfl_xor(r.hi[k], d, 64); }
-        o.reach = __shfl_xor(r.reach, d, 64);
-        o.selected = __shfl_xor(r.selected, d, 64);
-        o.finite = __shfl_xor(r.finite, d, 64);
-        measure_merge(r, o);
-    }
-    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = r;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        MeasureRow t = s_w[0];
-        for (int w = 1; w < kThreads / 64; ++w) measure_merge(t, s_w[w]);
-        *out = t;
-    }
-}
 
 // grid-stride over the stored slots; part: one row per workgroup
 __global__ __launch_bounds__(kThreads) void measure_cloud_kernel(const float4* __restrict__ pos, const uint32_t* __restrict__ order,
@@ -129,7 +104,7 @@ __global__ __launch_bounds__(kThreads) void measure_cloud_kernel(const float4* _
                                                                  MeasureRow* __restrict__ part /* [gridDim.x] */)
 {
     MeasureRow r;
-    measure_clear(r);
+    r.clear();
     for (uint32_t i = blockIdx.x * kThreads + threadIdx.x; i < n; i += gridDim.x * kThreads) {
         if (select && select[order ? order[i] : i] == 0) continue;
         const float4 p = pos[i];
@@ -145,17 +120,7 @@ __global__ __launch_bounds__(kThreads) void measure_cloud_kernel(const float4* _
             r.s[6] += x * y; r.s[7] += x * z; r.s[8] += y * z;
         }
     }
-    measure_reduce_store(r, part + blockIdx.x);
-}
-
-// one workgroup: the rows of the partial pass, in row order per lane, into *out
-__global__ __launch_bounds__(kThreads) void measure_cloud_finish(const MeasureRow* __restrict__ part, uint32_t rows,
-                                                                 MeasureRow* __restrict__ out)
-{
-    MeasureRow r;
-    measure_clear(r);
-    for (uint32_t k = threadIdx.x; k < rows; k += kThreads) measure_merge(r, part[k]);
-    measure_reduce_store(r, out);
+    row_reduce_store(r, part + blockIdx.x);
 }
 
 }  // namespace msplat

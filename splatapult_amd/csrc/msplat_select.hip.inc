@@ -7,19 +7,6 @@
 // numbering through the store's order table, need no Sort and leave the context, its frames and its timings alone.  The marks are
 // asynchronous on the context's stream like msplat_mark_scores; the measure returns after its 112-byte copy like msplat_get_visibility.
 
-// what the three calls refuse first, in msplat_mark_ids' order; bytes: the mask or selection (NULL allowed where `optional`)
-static int select_front_door(msplat_ctx* ctx, const char* who, const char* what, const void* d_bytes, uint64_t n, bool optional)
-{
-    int rc;
-    if ((rc = require_splat_cloud(ctx, who, "selection is for splat clouds", " (a mask is in the cloud's upload numbering)"))) return rc;
-    if (n != ctx->N)
-        return fail(ctx, MSPLAT_ERR_INVALID_ARG, "%s: %llu mask bytes for a cloud of %llu splats", who, (unsigned long long)n,
-                    (unsigned long long)ctx->N);
-    if (n == 0 || (optional && !d_bytes)) return MSPLAT_OK;
-    if (!d_bytes) return fail(ctx, MSPLAT_ERR_INVALID_ARG, "%s: %s is NULL", who, what);
-    return check_device_source(ctx, who, what, d_bytes, n);
-}
-
 int msplat_mark_volume(msplat_ctx* ctx, const float worldToVolume[16], int32_t shape, uint8_t* d_mask, uint64_t n, uint8_t value)
 {
     static const char* who = "msplat_mark_volume";
@@ -32,7 +19,7 @@ int msplat_mark_volume(msplat_ctx* ctx, const float worldToVolume[16], int32_t s
                     who, (unsigned)shape);
     int rc;
     if ((rc = check_affine_finite(ctx, who, "worldToVolume", worldToVolume))) return rc;
-    if ((rc = select_front_door(ctx, who, "d_mask", d_mask, n, false)) || n == 0) return rc;
+    if ((rc = check_splat_bytes(ctx, who, "d_mask", d_mask, n, false)) || n == 0) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if ((rc = ensure_order_dev(ctx))) return rc;
     MarkVolumeArgs a;
@@ -43,9 +30,7 @@ int msplat_mark_volume(msplat_ctx* ctx, const float worldToVolume[16], int32_t s
     std::memcpy(a.m, worldToVolume, sizeof(a.m));
     a.mask = d_mask;
     a.value = value;
-    hipLaunchKernelGGL(mark_volume_kernel, dim3(div_up(n, kThreads)), dim3(kThreads), 0, ctx->stream, a);
-    if (hipGetLastError() != hipSuccess) return fail(ctx, MSPLAT_ERR_HIP, "%s: the kernel launch failed", who);
-    return MSPLAT_OK;
+    return launch_per_item(ctx, who, n, mark_volume_kernel, a);
 }
 
 int msplat_mark_view(msplat_ctx* ctx, const float cameraMat[16], const float projMat[16], const float viewport[4], const float nearFar[2],
@@ -71,12 +56,9 @@ int msplat_mark_view(msplat_ctx* ctx, const float cameraMat[16], const float pro
     int rc;
     if ((rc = frame_window(ctx, who, width, height, win))) return rc;
     const int32_t* w = win.v;
-    if (region_pitch_bytes == 0) region_pitch_bytes = (uint64_t)w[2];
-    if (d_region && region_pitch_bytes < (uint64_t)w[2])
-        return fail(ctx, MSPLAT_ERR_INVALID_ARG, "%s: region pitch %llu too small for %d pixels of 1 byte", who,
-                    (unsigned long long)region_pitch_bytes, w[2]);
-    if ((rc = select_front_door(ctx, who, "d_mask", d_mask, n, false)) || n == 0) return rc;
-    if (d_region && (rc = check_device_source(ctx, who, "d_region", d_region, (uint64_t)(w[3] - 1) * region_pitch_bytes + (uint64_t)w[2]))) return rc;
+    if ((rc = region_pitch(ctx, who, d_region, region_pitch_bytes, w[2]))) return rc;
+    if ((rc = check_splat_bytes(ctx, who, "d_mask", d_mask, n, false)) || n == 0) return rc;
+    if ((rc = check_region(ctx, who, d_region, region_pitch_bytes, w[2], w[3]))) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if ((rc = ensure_order_dev(ctx))) return rc;
     a.pos = (const float4*)ctx->pos4.p;
@@ -87,9 +69,7 @@ int msplat_mark_view(msplat_ctx* ctx, const float cameraMat[16], const float pro
     a.region_pitch = (size_t)region_pitch_bytes;
     a.mask = d_mask;
     a.value = value;
-    hipLaunchKernelGGL(mark_view_kernel, dim3(div_up(n, kThreads)), dim3(kThreads), 0, ctx->stream, a);
-    if (hipGetLastError() != hipSuccess) return fail(ctx, MSPLAT_ERR_HIP, "%s: the kernel launch failed", who);
-    return MSPLAT_OK;
+    return launch_per_item(ctx, who, n, mark_view_kernel, a);
 }
 
 int msplat_measure_cloud(msplat_ctx* ctx, const uint8_t* d_select, uint64_t n, msplat_cloud_measure* out)
@@ -103,26 +83,17 @@ int msplat_measure_cloud(msplat_ctx* ctx, const uint8_t* d_select, uint64_t n, m
         return fail(ctx, MSPLAT_ERR_INVALID_ARG, "%s: struct_size %u ends before sum2 (sizeof(msplat_cloud_measure) is %zu)", who,
                     out->struct_size, sizeof(msplat_cloud_measure));
     int rc;
-    if ((rc = select_front_door(ctx, who, "d_select", d_select, n, true))) return rc;
+    if ((rc = check_splat_bytes(ctx, who, "d_select", d_select, n, true))) return rc;
     MeasureRow row;
-    std::memset(&row, 0, sizeof(row));
-    for (int k = 0; k < 3; ++k) { row.lo[k] = INFINITY; row.hi[k] = -INFINITY; }
+    row.clear();
     if (n != 0) {
         HIP_TRY(ctx, hipSetDevice(ctx->device));
         if ((rc = buf_alloc(ctx, ctx->measure_rows, ((size_t)kGridCap + 1) * sizeof(MeasureRow))) || (d_select && (rc = ensure_order_dev(ctx)))) return rc;
-        MeasureRow* part = (MeasureRow*)ctx->measure_rows.p;
-        MeasureRow* total = part + kGridCap;
-        const int grid = grid_for(div_up(n, kThreads), ctx->grid_cap);
-        KernelTimer timer(ctx);
-        timer.start(ctx->stream);
-        hipLaunchKernelGGL(measure_cloud_kernel, dim3(grid), dim3(kThreads), 0, ctx->stream, (const float4*)ctx->pos4.p,
-                           d_select && ctx->store->reordered ? (const uint32_t*)ctx->store->order_dev.p : nullptr, d_select, (uint32_t)n, part);
-        hipLaunchKernelGGL(measure_cloud_finish, dim3(1), dim3(kThreads), 0, ctx->stream, (const MeasureRow*)part, (uint32_t)grid, total);
-        timer.stop(ctx->stream);
-        if (hipGetLastError() != hipSuccess) return fail(ctx, MSPLAT_ERR_HIP, "%s: a kernel launch failed", who);
-        HIP_TRY(ctx, hipMemcpyAsync(&row, total, sizeof(row), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        timer.read(ctx);
+        const uint32_t* order = d_select && ctx->store->reordered ? (const uint32_t*)ctx->store->order_dev.p : nullptr;
+        rc = reduce_rows(ctx, who, (MeasureRow*)ctx->measure_rows.p, n, row, [&](int grid, MeasureRow* part) {
+            hipLaunchKernelGGL(measure_cloud_kernel, dim3(grid), dim3(kThreads), 0, ctx->stream, (const float4*)ctx->pos4.p, order, d_select, (uint32_t)n, part);
+        }, [] { return hipSuccess; });
+        if (rc) return rc;
     }
     out->selected = row.selected;
     out->finite = row.finite;

@@ -11,6 +11,7 @@
 #pragma once
 
 #include "msplat_download.hip.h"
+#include "msplat_rows.hip.h"
 
 #pragma clang fp contract(off)
 
@@ -103,48 +104,26 @@ __global__ __launch_bounds__(kThreads) void mark_values_kernel(const float* __re
     if ((v >= lo && v <= hi) != (outside != 0)) mask[i] = value;
 }
 
-// ---- msplat_histogram_values.  The counts are integers added with integer atomics, the minimum and maximum are reduced through
-// rows like the measure's (no floating-point atomic): nothing depends on the grid or on any order.
+// ---- msplat_histogram_values.  The counts are integers added with integer atomics, the minimum and maximum go through the row
+// reduction of msplat_rows.hip.h like the measure's (no floating-point atomic): nothing depends on the grid or on any order.
 struct ValueRow {                       // what a lane, a wave, a workgroup and the whole array accumulate
     uint32_t selected, finite, nan, below, above;
     float vmin, vmax;
     uint32_t pad;
+
+    __host__ __device__ __forceinline__ void clear()
+    {
+        selected = finite = nan = below = above = pad = 0u;
+        vmin = INFINITY;
+        vmax = -INFINITY;
+    }
+    __device__ __forceinline__ void merge(const ValueRow& o)
+    {
+        selected += o.selected; finite += o.finite; nan += o.nan; below += o.below; above += o.above;
+        vmin = fminf(vmin, o.vmin);
+        vmax = fmaxf(vmax, o.vmax);
+    }
 };
-
-__device__ __forceinline__ void value_row_clear(ValueRow& r)
-{
-    r.selected = r.finite = r.nan = r.below = r.above = r.pad = 0u;
-    r.vmin = INFINITY;
-    r.vmax = -INFINITY;
-}
-
-__device__ __forceinline__ void value_row_merge(ValueRow& r, const ValueRow& o)
-{
-    r.selected += o.selected; r.finite += o.finite; r.nan += o.nan; r.below += o.below; r.above += o.above;
-    r.vmin = fminf(r.vmin, o.vmin);
-    r.vmax = fmaxf(r.vmax, o.vmax);
-}
-
-// measure_reduce_store's shape: butterflies inside the wave, then the waves' rows through LDS
-__device__ __forceinline__ void value_row_reduce_store(ValueRow& r, ValueRow* __restrict__ out)
-{
-    __shared__ ValueRow s_w[kThreads / 64];
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        ValueRow o;
-        o.selected = __shfl_xor(r.selected, d, 64); o.finite = __shfl_xor(r.finite, d, 64); o.nan = __shfl_xor(r.nan, d, 64);
-        o.below = __shfl_xor(r.below, d, 64); o.above = __shfl_xor(r.above, d, 64);
-        o.vmin = __shfl_xor(r.vmin, d, 64); o.vmax = __shfl_xor(r.vmax, d, 64);
-        value_row_merge(r, o);
-    }
-    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = r;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        ValueRow t = s_w[0];
-        for (int w = 1; w < kThreads / 64; ++w) value_row_merge(t, s_w[w]);
-        *out = t;
-    }
-}
 
 // grid-stride over the values in turns of the whole workgroup (every wave stays whole: the ballots below count its 64 lanes).
 // bins > 0: s_bins is the workgroup's histogram (dynamic LDS, bins words), flushed into `counts` (zeroed by the host) where nonzero.
@@ -157,7 +136,7 @@ __global__ __launch_bounds__(kThreads) void histogram_values_kernel(const float*
     for (uint32_t b = threadIdx.x; b < bins; b += kThreads) s_bins[b] = 0u;
     __syncthreads();
     ValueRow r;
-    value_row_clear(r);
+    r.clear();
     const float fbins = (float)bins;
     for (uint32_t base = blockIdx.x * kThreads; base < n; base += gridDim.x * kThreads) {
         const uint32_t i = base + threadIdx.x;
@@ -203,16 +182,7 @@ __global__ __launch_bounds__(kThreads) void histogram_values_kernel(const float*
         const uint32_t c = s_bins[b];
         if (c) atomicAdd(&counts[b], c);
     }
-    value_row_reduce_store(r, part + blockIdx.x);
-}
-
-// one workgroup: the rows of the partial pass into *out
-__global__ __launch_bounds__(kThreads) void histogram_values_finish(const ValueRow* __restrict__ part, uint32_t rows, ValueRow* __restrict__ out)
-{
-    ValueRow r;
-    value_row_clear(r);
-    for (uint32_t k = threadIdx.x; k < rows; k += kThreads) value_row_merge(r, part[k]);
-    value_row_reduce_store(r, out);
+    row_reduce_store(r, part + blockIdx.x);
 }
 
 }  // namespace msplat

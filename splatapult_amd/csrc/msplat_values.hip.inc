@@ -1,7 +1,7 @@
 // msplat_values.hip.inc -- selection by attribute: msplat_cloud_values (one float per splat: a coordinate, alpha, the base colour, an
 // axis length ...), msplat_mark_values (such an array compared with a closed range into a mask) and msplat_histogram_values (its
 // histogram and summary); kernels in msplat_values.hip.h
-// (textually part of msplat_device.hip: included inside its extern "C" block, after msplat_select.hip.inc, whose front door it shares)
+// (textually part of msplat_device.hip: included inside its extern "C" block, after msplat_select.hip.inc)
 //
 // The split of the scores: one call produces a per-splat array, the others consume it.  Like the selection by position the calls read
 // the STORE (whatever the mask and the crop hide), speak upload numbering, need no Sort and leave the context, its frames and its
@@ -17,8 +17,7 @@ constexpr uint32_t kValueBinsMax = 4096;
 static int check_values(msplat_ctx* ctx, const char* who, const float* d_values, uint64_t n)
 {
     if (!d_values) return fail(ctx, MSPLAT_ERR_INVALID_ARG, "%s: d_values is NULL", who);
-    if ((uintptr_t)d_values % 4 != 0) return fail(ctx, MSPLAT_ERR_INVALID_ARG, "%s: d_values (%p) is not 4-byte aligned", who, (const void*)d_values);
-    return check_device_source(ctx, who, "d_values", d_values, 4 * n);
+    return check_device_array(ctx, who, "d_values", d_values, 4, n);
 }
 
 int msplat_cloud_values(msplat_ctx* ctx, int32_t kind, const float param[4], float* d_values, uint64_t n)
@@ -37,7 +36,7 @@ int msplat_cloud_values(msplat_ctx* ctx, int32_t kind, const float param[4], flo
         }
     }
     int rc;
-    if ((rc = select_front_door(ctx, who, "d_values", d_values, n, false)) || n == 0) return rc;
+    if ((rc = check_splat_bytes(ctx, who, "d_values", d_values, n, false)) || n == 0) return rc;
     if ((rc = check_values(ctx, who, d_values, n))) return rc;      // (the alignment, and all 4 n bytes)
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if ((rc = ensure_order_dev(ctx))) return rc;
@@ -76,13 +75,10 @@ int msplat_mark_values(msplat_ctx* ctx, const float* d_values, uint64_t n, float
         return fail(ctx, MSPLAT_ERR_INVALID_ARG, "%s: op %d is neither MSPLAT_RANGE_INSIDE nor MSPLAT_RANGE_OUTSIDE", who, op);
     if (lo != lo || hi != hi) return fail(ctx, MSPLAT_ERR_INVALID_ARG, "%s: %s is NaN", who, lo != lo ? "lo" : "hi");
     int rc;
-    if ((rc = select_front_door(ctx, who, "d_mask", d_mask, n, false)) || n == 0) return rc;
+    if ((rc = check_splat_bytes(ctx, who, "d_mask", d_mask, n, false)) || n == 0) return rc;
     if ((rc = check_values(ctx, who, d_values, n))) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipLaunchKernelGGL(mark_values_kernel, dim3(div_up(n, kThreads)), dim3(kThreads), 0, ctx->stream, d_values, (uint32_t)n, lo, hi,
-                       op == MSPLAT_RANGE_OUTSIDE ? 1 : 0, d_mask, value);
-    if (hipGetLastError() != hipSuccess) return fail(ctx, MSPLAT_ERR_HIP, "%s: the kernel launch failed", who);
-    return MSPLAT_OK;
+    return launch_per_item(ctx, who, n, mark_values_kernel, d_values, (uint32_t)n, lo, hi, op == MSPLAT_RANGE_OUTSIDE ? 1 : 0, d_mask, value);
 }
 
 int msplat_histogram_values(msplat_ctx* ctx, const float* d_values, const uint8_t* d_select, uint64_t n, float lo, float hi, uint32_t bins,
@@ -111,32 +107,21 @@ int msplat_histogram_values(msplat_ctx* ctx, const float* d_values, const uint8_
             return fail(ctx, MSPLAT_ERR_INVALID_ARG, "%s: bins / (hi - lo) = %g is not a normal fp32 number", who, (double)bins / ((double)hi - (double)lo));
     }
     int rc;
-    if ((rc = select_front_door(ctx, who, "d_select", d_select, n, true))) return rc;
+    if ((rc = check_splat_bytes(ctx, who, "d_select", d_select, n, true))) return rc;
     if (n != 0 && (rc = check_values(ctx, who, d_values, n))) return rc;
     ValueRow row;
-    std::memset(&row, 0, sizeof(row));
-    row.vmin = INFINITY;
-    row.vmax = -INFINITY;
+    row.clear();
     if (n != 0) {
         HIP_TRY(ctx, hipSetDevice(ctx->device));
         if ((rc = buf_alloc(ctx, ctx->value_hist, kScratch))) return rc;
-        uint32_t* d_counts = (uint32_t*)ctx->value_hist.p;
-        ValueRow* part = (ValueRow*)(d_counts + kValueBinsMax);
-        ValueRow* total = part + kGridCap;
-        const int grid = grid_for(div_up(n, kThreads), ctx->grid_cap);
+        uint32_t* d_counts = (uint32_t*)ctx->value_hist.p;                                    // counts first, then the rows
         hipStream_t s = ctx->stream;
-        if (bins) HIP_TRY(ctx, hipMemsetAsync(d_counts, 0, (size_t)bins * 4, s));
-        KernelTimer timer(ctx);
-        timer.start(s);
-        hipLaunchKernelGGL(histogram_values_kernel, dim3(grid), dim3(kThreads), (size_t)bins * 4, s, d_values, d_select, (uint32_t)n, lo, hi, scale,
-                           bins, d_counts, part);
-        hipLaunchKernelGGL(histogram_values_finish, dim3(1), dim3(kThreads), 0, s, (const ValueRow*)part, (uint32_t)grid, total);
-        timer.stop(s);
-        if (hipGetLastError() != hipSuccess) return fail(ctx, MSPLAT_ERR_HIP, "%s: a kernel launch failed", who);
-        HIP_TRY(ctx, hipMemcpyAsync(&row, total, sizeof(row), hipMemcpyDeviceToHost, s));
-        if (bins) HIP_TRY(ctx, hipMemcpyAsync(counts, d_counts, (size_t)bins * 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(ctx, hipStreamSynchronize(s));
-        timer.read(ctx);
+        if (bins) HIP_TRY(ctx, hipMemsetAsync(d_counts, 0, (size_t)bins * 4, s));             // (outside the timed pair)
+        rc = reduce_rows(ctx, who, (ValueRow*)(d_counts + kValueBinsMax), n, row, [&](int grid, ValueRow* part) {
+            hipLaunchKernelGGL(histogram_values_kernel, dim3(grid), dim3(kThreads), (size_t)bins * 4, s, d_values, d_select, (uint32_t)n, lo, hi, scale,
+                               bins, d_counts, part);
+        }, [&] { return bins ? hipMemcpyAsync(counts, d_counts, (size_t)bins * 4, hipMemcpyDeviceToHost, s) : hipSuccess; });
+        if (rc) return rc;
     } else {
         for (uint32_t b = 0; b < bins; ++b) counts[b] = 0u;
     }

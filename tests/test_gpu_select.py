@@ -258,6 +258,53 @@ def test_measure_cloud_counts_boxes_and_sums(grid_cap, spatial, monkeypatch):
     r.close()
 
 
+PINNED = "select_pinned_bytes.npz"       # tests/golden: recorded by pinned_results() (see test_measure_and_summary_bytes_are_pinned)
+
+
+def pinned_results(setenv):
+    """{name: array}: the raw msplat_cloud_measure of every selection of the designed cloud, and the raw msplat_value_summary and the
+    counts of every designed value array at 64 bins with and without d_select -- at grid caps 1 and 5 (the two that fix the summation
+    tree) and in both storage orders.  setenv(name, value) sets MSPLAT_GRID_CAP, which a context reads when it is created"""
+    from tests import values_rule as vl
+    out = {}
+    for cap in (1, 5):
+        setenv("MSPLAT_GRID_CAP", str(cap))
+        for spatial, order in ((OFF, "upload_order"), (ON, "morton_order")):
+            r = make_renderer(sr.measure_rows(), spatial_order=spatial)
+            for count in sr.MEASURE_COUNTS + (None,):
+                t = None if count is None else to_device(sr.measure_selection(count))
+                out["measure/cap%d/%s/%s" % (cap, order, count)] = np.frombuffer(raw_measure(r, t), np.uint8).copy()
+            r.close()
+            r = make_renderer(vl.cloud(vl.HIST_N), spatial_order=spatial)
+            for name, (v, lo, hi) in vl.hist_inputs().items():
+                d_v = to_device(v)
+                for sname, sel in (("all", None), ("d_select", to_device(vl.hist_select()))):
+                    counts = np.full(64, 0xAAAAAAAA, np.uint32)
+                    key = "cap%d/%s/%s/%s" % (cap, order, name, sname)
+                    s = _capi.ValueSummary(struct_size=C.sizeof(_capi.ValueSummary))
+                    rc = r._lib.msplat_histogram_values(r._ctx, C.c_void_p(d_v.data_ptr()), C.c_void_p(sel.data_ptr()) if sel is not None else None,
+                                                        r._n, lo, hi, 64, counts.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(s))
+                    assert rc == _capi.OK, r.last_error()
+                    out["summary/" + key] = np.frombuffer(bytes(s), np.uint8).copy()
+                    out["counts/" + key] = counts
+            r.close()
+    return out
+
+
+def test_measure_and_summary_bytes_are_pinned(monkeypatch, golden_dir):
+    """msplat_measure_cloud and msplat_histogram_values return the bytes they returned when the fixture was recorded (with
+    pinned_results(), at the commit before the row reductions were folded into msplat_rows.hip.h): the order of every
+    floating-point addition -- lane loop, wave butterfly, waves in wave order, finish rows in lane stride -- is part of the result"""
+    import os
+    want = np.load(os.path.join(golden_dir, PINNED))
+    got = pinned_results(monkeypatch.setenv)
+    assert sorted(got) == sorted(want.files) and len(got) == 2 * 2 * (len(sr.MEASURE_COUNTS) + 1 + 2 * 2 * 5)
+    for name in sorted(got):
+        kind = name.split("/")[0]
+        assert got[name].size == {"counts": 64, "measure": C.sizeof(_capi.CloudMeasure), "summary": C.sizeof(_capi.ValueSummary)}[kind], name
+        same_bits(got[name], want[name], name)
+
+
 # ---- 7. measure -> box -> mark ---------------------------------------------------------------------------------------------------
 @ORDERS
 def test_the_measured_box_marks_the_selection(spatial):

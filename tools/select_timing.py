@@ -10,7 +10,7 @@ JSON line per child on stdout (and appended to --out):
            --reps calls each of MarkVolume (a sphere that holds ~10 % of the cloud), MarkView (the whole 1920 x 1080 viewport),
            MeasureCloud of the marked selection, and a Sort that starts with visibility_kernel because SetCrop of the SAME matrix was
            called just before -- the yardstick of mark_volume_kernel: the same plane and order table, 16 B + the boxes more written.
-           Average microseconds of mark_volume_kernel, mark_view_kernel, measure_cloud_kernel, measure_cloud_finish,
+           Average microseconds of mark_volume_kernel, mark_view_kernel, measure_cloud_kernel, rows_finish_kernel,
            visibility_kernel and, where the upload ran them (Morton storage), cloud_moments_kernel / cloud_moments_finish.
            With --parent-lib a third child times visibility_kernel on that build (the parent commit's) the same way.
   clock    no profiler: msplat_measure_cloud by the host clock (the stream drain and the 112-byte copy included) and between its own
@@ -32,7 +32,7 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 CHILD_TIMEOUT = 300
-KERNELS = ("mark_volume_kernel", "mark_view_kernel", "measure_cloud_kernel", "measure_cloud_finish", "visibility_kernel",
+KERNELS = ("mark_volume_kernel", "mark_view_kernel", "measure_cloud_kernel", "rows_finish_kernel", "visibility_kernel",
            "cloud_moments_kernel", "cloud_moments_finish")
 W, H = 1920, 1080
 

@@ -34,7 +34,7 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 CHILD_TIMEOUT = 300
-KERNELS = ("cloud_values_kernel", "mark_values_kernel", "histogram_values_kernel", "histogram_values_finish", "mark_volume_kernel", "adjust_kernel")
+KERNELS = ("cloud_values_kernel", "mark_values_kernel", "histogram_values_kernel", "rows_finish_kernel", "mark_volume_kernel", "adjust_kernel")
 # bytes of the store the rule of a kind needs per splat (+ 4 written, + 4 of the order table in Morton order)
 KIND_BYTES = {"x": 16, "alpha": 4, "colour_dist2": 12, "scale_max": 36}
 KINDS = {"colour_dist2": (0.1, 0.8, 0.2)}
