@@ -120,6 +120,11 @@ int msplat_debug_upload_kernel_ms(msplat_ctx* ctx, float* ms);
  * and msplat_measure_cloud are functions of.  Synchronises ---- */
 int msplat_debug_get_positions(msplat_ctx* ctx, float* pos4_out, uint64_t cap_floats);
 
+/* ---- msplat_neighbour_values' hash grid: forces its bucket count for the following calls on the context -- a power of two
+ * 1 .. 2^24; 0 hands it back to the call (the smallest power of two >= N).  No result depends on it; tests/test_gpu_neighbours.py
+ * makes hash collisions certain with it (1 bucket: every source is a candidate of every query) ---- */
+int msplat_debug_set_neighbour_buckets(msplat_ctx* ctx, uint32_t buckets);
+
 #ifdef __cplusplus
 }
 #endif

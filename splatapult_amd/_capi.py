@@ -45,6 +45,8 @@ VALUE_KINDS = {"x": 0, "y": 1, "z": 2, "reach2": 3, "distance2": 4, "alpha": 5, 
 VALUE_KINDS_WITH_PARAM = ("distance2", "colour_dist2")
 RANGE_INSIDE, RANGE_OUTSIDE = 0, 1
 VALUE_BINS_MAX = 4096
+# msplat_neighbour_values: what is around a splat (MSPLAT_NEAR_*)
+NEAR_KINDS = {"count": 0, "dist2": 1}
 # "weighted": contiguous bands, rank 0 (the gather's root) weighted block_rows PERCENT of another rank (msplat.h)
 BAND_KINDS = {"contiguous": BANDS_CONTIGUOUS, "interleaved": BANDS_INTERLEAVED, "block": BANDS_BLOCK_INTERLEAVED,
               "weighted": BANDS_ROOT_WEIGHTED}
@@ -99,6 +101,12 @@ class ValueSummary(C.Structure):
     """msplat_value_summary (msplat_histogram_values)"""
     _fields_ = [("struct_size", C.c_uint32), ("selected", C.c_uint64), ("finite", C.c_uint64), ("nan", C.c_uint64), ("below", C.c_uint64),
                 ("above", C.c_uint64), ("vmin", C.c_float), ("vmax", C.c_float)]
+
+
+class NeighbourInfo(C.Structure):
+    """msplat_neighbour_info (msplat_neighbour_values)"""
+    _fields_ = [("struct_size", C.c_uint32), ("sources", C.c_uint32), ("queries", C.c_uint32), ("buckets", C.c_uint32), ("max_bucket", C.c_uint32),
+                ("reserved", C.c_uint32), ("tests", C.c_uint64)]
 
 
 class Timings(C.Structure):
@@ -184,6 +192,9 @@ SYMBOLS = [
     ("msplat_mark_values", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_float, C.c_float, C.c_int32, C.c_void_p, C.c_uint8]),
     ("msplat_histogram_values", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_float, C.c_float, C.c_uint32, _U32P,
                                           C.POINTER(ValueSummary)]),
+    ("msplat_neighbour_values", C.c_int, [C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_void_p,
+                                          C.POINTER(NeighbourInfo)]),
+    ("msplat_debug_set_neighbour_buckets", C.c_int, [C.c_void_p, C.c_uint32]),
     ("msplat_debug_get_positions", C.c_int, [C.c_void_p, _F16, C.c_uint64]),
     ("msplat_synchronize", C.c_int, [C.c_void_p]),
     ("msplat_read_image", C.c_int, [C.c_char_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),

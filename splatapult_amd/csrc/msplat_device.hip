@@ -219,6 +219,11 @@ struct msplat_ctx {
     StagingSlot ov_stage[2];    // what the latest host classes' / palette's copy reads
     Buf measure_rows;           // msplat_measure_cloud's scratch (msplat_select.hip.h): MeasureRow[kGridCap] partials, then the total; first use
     Buf value_hist;             // msplat_histogram_values' scratch (msplat_values.hip.h): uint32[4096] counts, ValueRow[kGridCap] partials, the total; first use
+    // msplat_neighbour_values' scratch (msplat_neighbours.hip.h), first use; [0] the sources' list, [1] a query set's that is another array
+    Buf near_cells[2];          // uint32: cnt[cells] | start[cells] | sums[chunks] | total, cells = chunks * 4096 > the buckets
+    Buf near_ent[2];            // float4[N]: (x, y, z, bits of the upload index) in bucket order
+    Buf near_rows;              // TestsRow[kGridCap] partials, the total, the fullest bucket
+    uint32_t near_buckets = 0;  // msplat_debug_set_neighbour_buckets: the forced bucket count; 0: automatic
     uint32_t sort_parity = 0;
     bool tables_dirty = false;  // a launch failed: clear every self-cleaning table before the next frame
     // per-bin pair counts taken by the row pass's upsweep (r3): list offsets + work order (no kernel of their own)
@@ -1982,6 +1987,7 @@ int msplat_render_stereo_layers(msplat_ctx* ctx, const float cameraMat0[16], con
 #include "msplat_scores.hip.inc"
 #include "msplat_select.hip.inc"
 #include "msplat_values.hip.inc"
+#include "msplat_neighbours.hip.inc"
 
 #include "msplat_getters.hip.inc"
 

@@ -1,4 +1,4 @@
-// msplat_kernels.hip.h -- hand-written CDNA4 (gfx950, wave64) kernels of the splat hot path, in nineteen parts.
+// msplat_kernels.hip.h -- hand-written CDNA4 (gfx950, wave64) kernels of the splat hot path, in twenty parts.
 //
 // Replaces (not ports) the reference's GL pipeline:
 //   shader/presort_compute.glsl + shader/multi_radixsort*.glsl  -> msplat_sort.hip.h      radix_* / ws_* (cull fused in pass 0)
@@ -11,6 +11,7 @@
 //   GaussianCloud::ImportPly's per-vertex math, storage order   -> msplat_cloud.hip.h     ingest_kernel, morton / gather / cull boxes
 //   splats selected by position, a selection measured (no ref.) -> msplat_select.hip.h    mark_volume_kernel, mark_view_kernel, measure_cloud_kernel
 //   splats selected by attribute: values, range, histogram      -> msplat_values.hip.h    cloud_values_kernel, mark_values_kernel, histogram_values_kernel
+//   splats selected by neighbourhood: count, nearest (no ref.) -> msplat_neighbours.hip.h neighbour_* (count, sums, starts, scatter, tests, fill, search)
 //   the row reduction both measures end with (no ref. part)     -> msplat_rows.hip.h      row_reduce_store, rows_finish_kernel
 //   a mask or crop made permanent (no reference part)          -> msplat_compact.hip.h   compact_* (flags, count, offsets, index, gather)
 //   splats moved, rotated, scaled in the store (no ref. part)   -> msplat_transform.hip.h transform_kernel
@@ -36,6 +37,7 @@
 #include "msplat_adjust.hip.h"
 #include "msplat_download.hip.h"
 #include "msplat_values.hip.h"
+#include "msplat_neighbours.hip.h"
 #include "msplat_project.hip.h"
 #include "msplat_binning.hip.h"
 #include "msplat_composite.hip.h"

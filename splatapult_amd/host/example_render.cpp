@@ -3,7 +3,7 @@
 // Sort + Render into an explicit RGBA32F framebuffer, dumped as a binary PPM-like float file.
 //
 //   g++ -std=c++17 -I. splatapult_amd/host/example_render.cpp -Lsplatapult_amd/lib -lmsplat -o example_render
-//   ./example_render scene.ply out.f32 [width height] [--nosh] [--frames-in-flight N] [--devices 0,1,2,...] [--over-gradient] [--depth out_depth.f32] [--srgb8 out.png] [--crop-sphere cx cy cz r] [--pick X,Y] [--min-score S] [--highlight R,G,B,A] [--compact] [--append OTHER.ply] [--save OUT.ply] [--fade S] [--tint R,G,B,A] [--select-sphere CX,CY,CZ,R] [--min-alpha T]
+//   ./example_render scene.ply out.f32 [width height] [--nosh] [--frames-in-flight N] [--devices 0,1,2,...] [--over-gradient] [--depth out_depth.f32] [--srgb8 out.png] [--crop-sphere cx cy cz r] [--pick X,Y] [--min-score S] [--highlight R,G,B,A] [--compact] [--append OTHER.ply] [--save OUT.ply] [--fade S] [--tint R,G,B,A] [--select-sphere CX,CY,CZ,R] [--min-alpha T] [--min-neighbours K,R]
 // With --frames-in-flight N the same frame is issued N + 1 times round-robin over N contexts that share the cloud
 // (SplatRenderer::SetFramesInFlight); the last one is written.  With --devices the frame's bin rows are dealt to the
 // listed GPUs (SplatRenderer::ConfigureDevices, msplat_group_*): same pixels.  With --over-gradient the target is first filled with
@@ -35,6 +35,10 @@
 // SplatRenderer::HistogramValues: first the range, then the counts) is printed, the splats with alpha below T are hidden
 // (MSPLAT_VALUE_ALPHA, SplatRenderer::MarkValues of 0 into a mask of ones, SetVisibilityDevice) and the frame is sorted and rendered
 // again.  One device, one frame in flight.
+// With --min-neighbours K,R the splats with fewer than K other splats within R of their centre -- floaters are isolated splats -- are
+// hidden (SplatRenderer::NeighbourValues with MSPLAT_NEAR_COUNT and cap K, SplatRenderer::MarkValues of 0 into a mask of ones,
+// SetVisibilityDevice), the grid's numbers are printed and the frame is sorted and rendered again; --compact and --save then drop
+// and write them.  One device, one frame in flight.
 // With --compact, after --min-score / --crop-sphere, the hidden splats are dropped for good (SplatRenderer::CompactCloud,
 // msplat_compact_cloud: the kept records gathered into a new store on the device), the splat counts before and after are printed and
 // the frame is sorted and rendered once more from the smaller cloud: the same pixels.  One device only.
@@ -95,6 +99,8 @@ int main(int argc, char** argv)
     std::vector<int> devices;
     float cropSphere[4] = {0.0f, 0.0f, 0.0f, 0.0f};       // centre, radius; radius 0: no crop
     float selectSphere[4] = {0.0f, 0.0f, 0.0f, 0.0f};     // --select-sphere: centre, radius; radius 0: not given
+    int minNeighbours = 0;           // --min-neighbours K,R: hide the splats with fewer than K neighbours within R; 0: not given
+    float neighbourRadius = 0.0f;
     float minAlpha = -1.0f;          // --min-alpha: hide the splats whose alpha is below it; < 0: not given
     for (int i = 3; i < argc; ++i) {
         if (!std::strcmp(argv[i], "--select-sphere") && i + 1 < argc &&
@@ -116,6 +122,11 @@ int main(int argc, char** argv)
             std::sscanf(argv[i + 1], "%f,%f,%f,%f", &highlight[4], &highlight[5], &highlight[6], &highlight[7]) != 4)
             highlight[7] = -1.0f;
         if (!std::strcmp(argv[i], "--min-alpha") && i + 1 < argc) minAlpha = (float)std::atof(argv[i + 1]);
+        if (!std::strcmp(argv[i], "--min-neighbours") && i + 1 < argc &&
+            (std::sscanf(argv[i + 1], "%d,%f", &minNeighbours, &neighbourRadius) != 2 || minNeighbours < 1 || !(neighbourRadius > 0.0f))) {
+            std::fprintf(stderr, "--min-neighbours takes K,R with K >= 1 and R > 0\n");
+            return 1;
+        }
         if (!std::strcmp(argv[i], "--fade") && i + 1 < argc) fade = (float)std::atof(argv[i + 1]);
         if (!std::strcmp(argv[i], "--tint") && i + 1 < argc && std::sscanf(argv[i + 1], "%f,%f,%f,%f", &tintTo[0], &tintTo[1], &tintTo[2], &tintTo[3]) != 4)
             tintTo[3] = -1.0f;
@@ -309,6 +320,30 @@ int main(int argc, char** argv)
         uint64_t hidden = 0;
         if (msplat_get_visibility(renderer.GetContext(), nullptr, nullptr, &hidden) != MSPLAT_OK) return 1;
         std::printf("min alpha %g: %llu of %zu splats hidden\n", minAlpha, (unsigned long long)hidden, n);
+        dm.release(values);
+        dm.release(mask);
+    }
+
+    if (minNeighbours > 0 && inFlight == 1 && devices.size() <= 1) {
+        const size_t n = cloud->GetNumGaussians();
+        DeviceMemory dm;
+        void *values = nullptr, *mask = nullptr;
+        if (!dm.Load() || dm.alloc(&values, n * 4) != 0 || dm.alloc(&mask, n) != 0 || dm.fill(mask, 1, n) != 0 || dm.wait() != 0) return 1;
+        float* v = static_cast<float*>(values);
+        // count up to K neighbours (a lane stops there), then hide the counts below K: inside [0, K - 1]
+        msplat_neighbour_info info;
+        if (!renderer.NeighbourValues(MSPLAT_NEAR_COUNT, neighbourRadius, nullptr, nullptr, n, (uint32_t)minNeighbours, 0, v, &info) ||
+            !renderer.MarkValues(v, n, 0.0f, (float)(minNeighbours - 1), MSPLAT_RANGE_INSIDE, static_cast<uint8_t*>(mask), 0) ||
+            !renderer.SetVisibilityDevice(static_cast<const uint8_t*>(mask), n))
+            return 1;
+        renderer.Sort(cameraMat, projMat, viewport, nearFar);
+        if (depthPath) renderer.RenderWithDepth(cameraMat, projMat, viewport, nearFar, depth.data());
+        else renderer.Render(cameraMat, projMat, viewport, nearFar);
+        renderer.Synchronize();
+        uint64_t hidden = 0;
+        if (msplat_get_visibility(renderer.GetContext(), nullptr, nullptr, &hidden) != MSPLAT_OK) return 1;
+        std::printf("fewer than %d neighbours within %g: %llu of %zu splats hidden (%u buckets, fullest %u, %llu candidate pairs)\n", minNeighbours,
+                    neighbourRadius, (unsigned long long)hidden, n, info.buckets, info.max_bucket, (unsigned long long)info.tests);
         dm.release(values);
         dm.release(mask);
     }

@@ -617,6 +617,17 @@ public:
         if (out) out->struct_size = sizeof(msplat_value_summary);
         return Select("HistogramValues", [&](msplat_ctx* h) { return msplat_histogram_values(h, d_values, d_select, n, lo, hi, bins, counts, out); });
     }
+    // Selection by neighbourhood (msplat_neighbour_values): d_values[i] = how many splats of d_source (nullptr: all) lie within `radius`
+    // of splat i (kind = MSPLAT_NEAR_COUNT, at most cap; 0: no cap) or the squared distance to the nearest (MSPLAT_NEAR_DIST2), for the
+    // splats d_query selects (nullptr: all).  max_tests == 0: the library's budget.  info may be nullptr.  Synchronous.
+    bool NeighbourValues(int32_t kind, float radius, const uint8_t* d_source, const uint8_t* d_query, size_t n, uint32_t cap, uint64_t max_tests,
+                         float* d_values, msplat_neighbour_info* info = nullptr)
+    {
+        if (info) info->struct_size = sizeof(msplat_neighbour_info);
+        return Select("NeighbourValues", [&](msplat_ctx* h) {
+            return msplat_neighbour_values(h, kind, radius, d_source, d_query, n, cap, max_tests, d_values, info);
+        });
+    }
     template <class Call>
     bool Select(const char* who, Call&& call)
     {

@@ -1258,6 +1258,74 @@ class SplatRenderer:
         return dict(selected=int(s.selected), finite=int(s.finite), nan=int(s.nan), below=int(s.below), above=int(s.above),
                     vmin=np.float32(s.vmin), vmax=np.float32(s.vmax), counts=counts)
 
+    # -- selection by neighbourhood (msplat_neighbour_values) --
+    def NeighbourValues(self, radius, kind="count", source=None, query=None, cap=0, max_tests=None, out=None, info=False):
+        """What is around every splat, one float32 per splat in upload numbering (msplat_neighbour_values).  kind "count": the
+        number of source splats within `radius` of the splat's centre, itself excluded, at most `cap` (0: no cap); "dist2": the
+        squared distance to the nearest one within the radius, +inf if there is none.  source / query: N values as TransformCloud's
+        select takes them (None: every splat) -- which splats count as neighbours, and which values are written; the words of
+        unselected queries keep their bytes (a new tensor starts as zeros).  max_tests: the budget of candidate pairs (None: the
+        library's default); a radius that is too large for the cloud raises MsplatError ERR_UNSUPPORTED and writes nothing.
+        out: a float32 tensor of N values on this renderer's device to write into (None: a new one).  The cloud itself is read,
+        whatever a mask or crop hides; no Sort is needed.  Synchronous.  Returns the tensor, or (tensor, dict of sources, queries,
+        buckets, max_bucket, tests) with info=True."""
+        import torch
+        if isinstance(kind, str):
+            if kind not in _capi.NEAR_KINDS:
+                raise ValueError("kind must be one of %s (got %r)" % (sorted(_capi.NEAR_KINDS), kind))
+            code = _capi.NEAR_KINDS[kind]
+        else:
+            code = int(kind)
+            if code not in _capi.NEAR_KINDS.values():
+                raise ValueError("kind %r is not an MSPLAT_NEAR_* number" % (kind,))
+        radius, cap = float(radius), int(cap)
+        if not (np.isfinite(radius) and radius > 0.0):
+            raise ValueError("radius must be finite and > 0 (got %r)" % radius)
+        if not 0 <= cap < 2 ** 32:
+            raise ValueError("cap is an unsigned 32-bit value (got %d)" % cap)
+        if cap and code == _capi.NEAR_KINDS["dist2"]:
+            raise ValueError("cap goes with kind \"count\" (a cap stops a count)")
+        max_tests = 0 if max_tests is None else int(max_tests)
+        if not 0 <= max_tests < 2 ** 64:
+            raise ValueError("max_tests is an unsigned 64-bit value (got %d)" % max_tests)
+        if not self._ctx:
+            raise _capi.MsplatError(_capi.ERR_NO_CLOUD, "NeighbourValues: no cloud (Init first)")
+        dev = torch.device("cuda", self._device)
+        src = self._device_select(source, self._n)
+        src_alive = self._select_arg
+        qry = src if query is source else self._device_select(query, self._n)
+        self._select_arg = (src_alive, self._select_arg)
+        if out is None:
+            out = torch.zeros(self._n, dtype=torch.float32, device=dev)
+        else:
+            self._device_vector("out", out, torch.float32)
+        torch.cuda.current_stream(dev).synchronize()
+        ni = _capi.NeighbourInfo(struct_size=C.sizeof(_capi.NeighbourInfo))
+        _capi.check(self._ctx, self._lib.msplat_neighbour_values(self._ctx, code, radius, src, qry, self._n, cap, max_tests,
+                                                                 C.c_void_p(out.data_ptr()), C.byref(ni)))
+        if not info:
+            return out
+        return out, {k: int(getattr(ni, k)) for k in ("sources", "queries", "buckets", "max_bucket", "tests")}
+
+    def GrowSelection(self, mask, radius, steps=1, max_tests=None):
+        """The selection grown by `radius`, `steps` times: a copy of `mask` (a torch uint8 / bool tensor of N bytes on this
+        renderer's device) in which, per step, every splat with a selected splat within the radius gets byte 1; other bytes stay.
+        NeighbourValues(cap=1, source=the mask so far) plus MarkValues per step; compose with MeasureCloud's count for a flood
+        fill.  Returns the new mask."""
+        import torch
+        steps = int(steps)
+        if steps < 0:
+            raise ValueError("steps must be >= 0 (got %d)" % steps)
+        if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.uint8, torch.bool):
+            raise ValueError("mask must be a torch uint8 / bool tensor")
+        self._device_vector("mask", mask, mask.dtype)
+        grown = mask.clone()
+        near = None
+        for _ in range(steps):
+            near = self.NeighbourValues(radius, "count", source=grown, cap=1, max_tests=max_tests, out=near)
+            self.MarkValues(near, 1.0, 1.0, grown, 1)
+        return grown
+
     def synchronize(self):
         """blocks until every frame in flight has been issued (async_submit) AND has finished on the GPU"""
         for h in self._ctxs:
