@@ -17,6 +17,14 @@ extern "C" {
 /* per draw-order rank r < V: 12 floats {px, py, A, B, C, log2(alpha), r, g, b, alpha, 0, 0} with
  * w(dx, dy) = exp2(A dx^2 + B dx dy + C dy^2 + log2 alpha); rect = bin rectangle tx0 | ty0<<8 | tx1<<16 | ty1<<24 (tx0 > tx1: empty) */
 int msplat_debug_get_projected(msplat_ctx* ctx, float* rec12, uint32_t* rect, uint32_t cap);
+/* the same for one view of the latest Render -- view 1: the second eye of msplat_render_stereo, whose ranks follow the first eye's at
+ * V rounded up to 64 -- and for `count` ranks from the view's first one, which may be more than V: what lies beyond V is what the
+ * buffers held before (fails when the buffers are smaller).  rect as the binning reads it: the second view's bin rows follow the
+ * first's */
+int msplat_debug_get_projected_view(msplat_ctx* ctx, int32_t view, float* rec12, uint32_t* rect, uint32_t count);
+/* fills both buffers, whole: every byte of the records with `byte`, every rectangle with the empty rectangle 0xFF | byte << 8.
+ * With the getter above tests/test_gpu_projection_limits.py shows that a projection writes its V ranks and nothing behind them */
+int msplat_debug_fill_projected(msplat_ctx* ctx, int32_t byte);
 /* tile_start has tiles_x * tiles_y + 1 entries; pairs[k] & 0xFFFFFF = draw-order rank.  After a two-pass Render both (and
  * msplat_get_stats().pairs / drawn) describe the SECOND pass */
 int msplat_debug_get_tile_lists(msplat_ctx* ctx, uint32_t* tile_start, uint32_t tile_cap, uint32_t* pairs, uint64_t pair_cap);

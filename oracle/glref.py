@@ -68,18 +68,27 @@ def rgc_sort(keys, values):
     return k, v
 
 
-def render(aos, sorted_idx, view_mat, proj_mat, viewport, near_far, eye, target="fp32", depth_bits=0):
+def render(aos, sorted_idx, view_mat, proj_mat, viewport, near_far, eye, target="fp32", depth_bits=0, capture=False):
     """SplatRenderer::Render on the reference's vertex / geometry / fragment shaders: (H, W, 4) float32, row 0 = bottom.
     target: "fp32" = the colour-only RGBA32F FBO of --fp32, "rgba8" = an 8-bit target like the default back buffer (GL's ROP
-    clamps + quantises after every blend), "fp16" = the --fp16 target; depth_bits 24 / 32: with a depth attachment (GL_DEPTH_TEST live)"""
+    clamps + quantises after every blend), "fp16" = the --fp16 target; depth_bits 24 / 32: with a depth attachment (GL_DEPTH_TEST live).
+    capture: also what the geometry shader emitted, by transform feedback: (image, (count, 6, 8) float32) -- per splat its two
+    triangles' vertices as (gl_Position, frag_cov2inv); every splat of sorted_idx must pass the shader's guard tests (asserted:
+    a splat that emits nothing would shift the records)"""
     W, H = int(viewport[2]), int(viewport[3])
     img = np.zeros((H, W, 4), np.float32)
     aos = np.ascontiguousarray(aos, np.float32)
     si = np.ascontiguousarray(sorted_idx, np.uint32)
     tgt = {"fp32": 0, "rgba8": 1, "fp16": 2}[target]
+    rec = np.full((si.shape[0], 6, 8), -777.0, np.float32) if capture else None
+    if capture:
+        _lib.glref_capture(rec.ctypes.data_as(C.POINTER(C.c_float)), rec.size)
     if _lib.glref_render_target(_f(aos), aos.shape[0], _u(si), si.shape[0], _f(view_mat), _f(proj_mat), _f(viewport), _f(near_far), _f(eye),
                                 tgt, int(depth_bits), img.ctypes.data_as(C.POINTER(C.c_float))) != 0:
         raise RuntimeError("glref_render: " + _lib.glref_last_error().decode())
+    if capture:
+        assert not (rec[:, :, 0] == -777.0).any(), "%d splat(s) emitted no quad" % (rec[:, 0, 0] == -777.0).sum()
+        return img, rec
     return img
 
 

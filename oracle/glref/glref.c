@@ -49,6 +49,8 @@ static const __DRIswrastLoaderExtension swrast_loader = {
 static const __DRIextension* loader_exts[] = {&swrast_loader.base, NULL};
 
 #define GLF(type, name) static type p##name
+GLF(PFNGLTRANSFORMFEEDBACKVARYINGSPROC, glTransformFeedbackVaryings); GLF(PFNGLBEGINTRANSFORMFEEDBACKPROC, glBeginTransformFeedback);
+GLF(PFNGLENDTRANSFORMFEEDBACKPROC, glEndTransformFeedback);
 GLF(PFNGLGETSTRINGPROC, glGetString); GLF(PFNGLGETERRORPROC, glGetError);
 GLF(PFNGLCREATESHADERPROC, glCreateShader); GLF(PFNGLSHADERSOURCEPROC, glShaderSource); GLF(PFNGLCOMPILESHADERPROC, glCompileShader);
 GLF(PFNGLGETSHADERIVPROC, glGetShaderiv); GLF(PFNGLGETSHADERINFOLOGPROC, glGetShaderInfoLog); GLF(PFNGLCREATEPROGRAMPROC, glCreateProgram);
@@ -134,12 +136,24 @@ static GLuint compile(GLenum type, const char* dir, const char* name, const char
     return sh;
 }
 
+/* glref_capture: the next glref_render* also records what the geometry shader emits, through transform feedback: per splat that
+ * passes the shader's guard tests, in draw order, its two triangles = 6 vertices of 8 floats (gl_Position, frag_cov2inv).  The
+ * shaders' own fp32 values, not their pixels: tests/test_reference_shaders.py compares them with the restatement bit for bit */
+static float* g_capture = NULL;
+static uint32_t g_capture_floats = 0;
+static int g_linking_splat = 0;
+void glref_capture(float* out, uint32_t floats) { g_capture = out; g_capture_floats = floats; }
+
 static GLuint link_program(GLuint a, GLuint b, GLuint c)
 {
     GLuint p = pglCreateProgram();
     if (a) pglAttachShader(p, a);
     if (b) pglAttachShader(p, b);
     if (c) pglAttachShader(p, c);
+    if (g_linking_splat) {                          /* inert until a capture is begun */
+        const char* varyings[2] = {"gl_Position", "frag_cov2inv"};
+        pglTransformFeedbackVaryings(p, 2, varyings, GL_INTERLEAVED_ATTRIBS);
+    }
     pglLinkProgram(p);
     GLint ok = 0;
     pglGetProgramiv(p, GL_LINK_STATUS, &ok);
@@ -193,6 +207,8 @@ int glref_init(const char* shader_dir, int full_sh, int srgb)
     if (!gpa) return fail("no _glapi_get_proc_address");
 #define LOAD(type, name) do { p##name = (type)gpa(#name); if (!p##name) return fail("GL entry point %s missing", #name); } while (0)
     LOAD(PFNGLGETSTRINGPROC, glGetString); LOAD(PFNGLGETERRORPROC, glGetError);
+    LOAD(PFNGLTRANSFORMFEEDBACKVARYINGSPROC, glTransformFeedbackVaryings); LOAD(PFNGLBEGINTRANSFORMFEEDBACKPROC, glBeginTransformFeedback);
+    LOAD(PFNGLENDTRANSFORMFEEDBACKPROC, glEndTransformFeedback);
     LOAD(PFNGLCREATESHADERPROC, glCreateShader); LOAD(PFNGLSHADERSOURCEPROC, glShaderSource); LOAD(PFNGLCOMPILESHADERPROC, glCompileShader);
     LOAD(PFNGLGETSHADERIVPROC, glGetShaderiv); LOAD(PFNGLGETSHADERINFOLOGPROC, glGetShaderInfoLog); LOAD(PFNGLCREATEPROGRAMPROC, glCreateProgram);
     LOAD(PFNGLATTACHSHADERPROC, glAttachShader); LOAD(PFNGLLINKPROGRAMPROC, glLinkProgram); LOAD(PFNGLGETPROGRAMIVPROC, glGetProgramiv);
@@ -239,7 +255,9 @@ static int glref_configure(int full_sh, int srgb)
         GLuint gs = vs ? compile(GL_GEOMETRY_SHADER, g_dir, "splat_geom.glsl", defines) : 0;
         GLuint fs = gs ? compile(GL_FRAGMENT_SHADER, g_dir, "splat_frag.glsl", defines) : 0;
         if (!fs) return -1;
+        g_linking_splat = 1;
         g_splat_cfg[full_sh][srgb] = link_program(vs, gs, fs);
+        g_linking_splat = 0;
         if (!g_splat_cfg[full_sh][srgb]) return -1;
     }
     g_splat = g_splat_cfg[full_sh][srgb];
@@ -362,8 +380,22 @@ int glref_render_target(const float* aos, uint32_t n, const uint32_t* sorted_idx
     const float projParams[4] = {0.0f, nearFar[0], nearFar[1], 0.0f};
     pglUniform4fv(pglGetUniformLocation(g_splat, "projParams"), 1, projParams);
     pglUniform3fv(pglGetUniformLocation(g_splat, "eye"), 1, eye);
+    GLuint tfb = 0;
+    if (g_capture) {                              /* filled with what the caller put there: an unwritten record shows */
+        pglGenBuffers(1, &tfb);
+        pglBindBuffer(GL_TRANSFORM_FEEDBACK_BUFFER, tfb);
+        pglBufferData(GL_TRANSFORM_FEEDBACK_BUFFER, (GLsizeiptr)g_capture_floats * 4, g_capture, GL_DYNAMIC_READ);
+        pglBindBufferBase(GL_TRANSFORM_FEEDBACK_BUFFER, 0, tfb);
+        pglBeginTransformFeedback(GL_TRIANGLES);
+    }
     pglDrawElements(GL_POINTS, (GLsizei)count, GL_UNSIGNED_INT, NULL);
+    if (g_capture) pglEndTransformFeedback();
     pglFinish();
+    if (g_capture) {
+        pglGetBufferSubData(GL_TRANSFORM_FEEDBACK_BUFFER, 0, (GLsizeiptr)g_capture_floats * 4, g_capture);
+        pglDeleteBuffers(1, &tfb);
+        g_capture = NULL;
+    }
     pglPixelStorei(GL_PACK_ALIGNMENT, 1);
     pglReadPixels(0, 0, W, H, GL_RGBA, GL_FLOAT, rgba_out);
     const GLenum e = pglGetError();

@@ -250,9 +250,9 @@ uint32_t orc_render_frame_tiled(size_t n, const float* aos, size_t stride, int f
             const orc_splat2d* g = &ws->splats[r];
             uint32_t* rc = ws->rect + (size_t)r * 4;
             rc[0] = 1; rc[2] = 0;
-            /* degenerate covariance: nothing sensible to rasterise (the HIP path rejects the same splats) */
-            const float det = g->cov[0] * g->cov[3] - g->cov[1] * g->cov[2];
-            if (g->reject || !(det > 0.0f) || !(g->cov[0] > 0.0f) || !(g->cov[3] > 0.0f) || !(g->alpha > 1.0f / 256.0f)) continue;
+            /* the footprint rule (msplat.h): a NaN quad (Q) and a covariance that is no Gaussian's (X) draw nothing, here, in
+             * the literal oracle (orc_project has set g->reject for both) and in the HIP path */
+            if (g->reject || orc_cov2_class(g->cov) != ORC_COV2_G || !(g->alpha > 1.0f / 256.0f)) continue;
             /* fragments survive the discard only inside w > 1/256 <=> d^T inv d < rho2 = 2 ln(256 alpha), whose axis-aligned
              * extents sqrt(rho2 cov_xx), sqrt(rho2 cov_yy) lie inside the 3.5-sigma quad's AABB (rho <= 3.33): a tighter
              * rectangle that drops no contributing pixel */

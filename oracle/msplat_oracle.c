@@ -364,6 +364,20 @@ static float srgb_to_linear(float s)
     return powf((s + 0.055f) / 1.055f, 2.4f);
 }
 
+int orc_cov2_class(const float cov[4])
+{
+    /* splat_geom.glsl:59-66, every operation rounded once; b = cov2D[0][1] (column 0, row 1) */
+    float a = cov[0], b = cov[1], c = cov[3];
+    float apco2 = (a + c) / 2.0f;
+    float amco2 = (a - c) / 2.0f;
+    float term = sqrtf(amco2 * amco2 + b * b);
+    float mn = apco2 - term;
+    if (!(mn >= 0.0f)) return ORC_COV2_Q;
+    float det = a * c - b * cov[2];
+    if (!(det > 0.0f) || !(a > 0.0f) || !(c > 0.0f)) return ORC_COV2_X;
+    return ORC_COV2_G;
+}
+
 static void project_one(const float* rec, int full_sh, int srgb, const float viewMat[16],
                         const float projMat[16], const float viewport[4], const float nearFar[2],
                         const float eye[3], orc_splat2d* o)
@@ -469,6 +483,9 @@ static void project_one(const float* rec, int full_sh, int srgb, const float vie
     o->hx = fabsf(majx) + fabsf(minx);
     o->hy = fabsf(majy) + fabsf(miny);
     if (!(o->hx == o->hx) || !(o->hy == o->hy)) reject = 1;   /* NaN quad: nothing rasterised */
+    /* the footprint rule (msplat.h): Q is the NaN quad again, by the test the product makes; X is the one place where the
+       oracle does not follow the shaders, which would blend exp(+q) or NaN */
+    if (orc_cov2_class(o->cov) != ORC_COV2_G) reject = 1;
     o->reject = reject;
 }
 

@@ -87,6 +87,14 @@ void orc_project(uint32_t v, const uint32_t* idx, const float* aos, size_t strid
                  const float viewport[4], const float nearFar[2], const float eye[3],
                  orc_splat2d* out);
 
+/* The footprint rule of include/msplat.h for one fp32 cov2D = (m00, m01, m10, m11) with the +0.3 added, as orc_project leaves
+ * it in orc_splat2d.cov: G drawable; Q the geometry shader's minor-axis variance (splat_geom.glsl:59-66, b = cov2D[0][1] = m01)
+ * is negative or NaN, its quad is NaN and the reference draws nothing; X that variance is >= 0 but det <= 0 or a diagonal
+ * element is not positive: the reference blends exp(+q) or NaN, the product and this oracle draw nothing.  orc_project sets
+ * `reject` for Q and X. */
+enum { ORC_COV2_G = 0, ORC_COV2_Q = 1, ORC_COV2_X = 2 };
+int orc_cov2_class(const float cov[4]);
+
 /* splat_frag.glsl:18-42 + blend state app.cpp:153-160. Back-to-front in array order.
  * rgba is W*H*4 floats, row 0 = GL bottom row. nthreads>1 splits pixel rows across OpenMP
  * threads (each pixel still sees the identical blend sequence). Rows [row0,row1) only. */

@@ -120,6 +120,20 @@ def sh_basis(v, full):
     return np.stack(b, axis=1).astype(F)
 
 
+def cov2_class(a, b01, b10, c):
+    """the footprint rule of include/msplat.h per splat: 0 = G drawable, 1 = Q the geometry shader's minor-axis variance
+    (splat_geom.glsl:59-66, b = cov2D[0][1]) is negative or NaN, 2 = X that variance is >= 0 but the matrix is no Gaussian's"""
+    a, b01, b10, c = (np.asarray(v, F) for v in (a, b01, b10, c))
+    with np.errstate(invalid="ignore", over="ignore"):
+        apco2 = (a + c) / F(2)
+        amco2 = (a - c) / F(2)
+        mn = apco2 - np.sqrt(amco2 * amco2 + b01 * b01)
+        det = a * c - b01 * b10
+        q = ~(mn >= 0)
+        x = ~q & (~(det > 0) | ~(a > 0) | ~(c > 0))
+    return np.where(q, 1, np.where(x, 2, 0)).astype(np.int32)
+
+
 def project(aos, idx, full_sh, srgb, viewMat, projMat, viewport, nearFar, eye):
     """returns dict of per-splat arrays in idx order"""
     rec = aos[idx]
@@ -181,6 +195,7 @@ def project(aos, idx, full_sh, srgb, viewMat, projMat, viewport, nearFar, eye):
     with np.errstate(invalid="ignore"):
         reject = (ndc[:, 2] < 0.25) | (np.abs(ndc[:, 0]) > 2) | (np.abs(ndc[:, 1]) > 2) | ~(ndc[:, 2] <= 1) \
             | ~(p4[:, 3] > 0)
+    reject = reject | (cov2_class(a, b01, b10, c) != 0)
     return dict(px=px, py=py, cov=np.stack([a, b01, b10, c], axis=1), inv=inv, rgb=rgb, alpha=rec[:, 3],
                 ndc=ndc, depth=p4[:, 3], reject=reject)
 

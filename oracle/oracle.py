@@ -59,6 +59,8 @@ def lib():
     L.orc_sort.argtypes = [C.c_uint32, u32p, u32p]
     L.orc_project.argtypes = [C.c_uint32, u32p, fp, C.c_size_t, C.c_int, C.c_int, fp, fp, fp, fp, fp,
                               C.c_void_p]
+    L.orc_cov2_class.argtypes = [fp]
+    L.orc_cov2_class.restype = C.c_int
     L.orc_composite.argtypes = [C.c_uint32, C.c_void_p, C.c_int, C.c_int, fp, C.c_int, C.c_int, C.c_int]
     L.orc_composite_flip.argtypes = [C.c_uint32, C.c_void_p, C.c_int, C.c_int, fp, C.c_int, C.c_int, C.c_int, fp, C.c_float]
     L.orc_composite_depth.argtypes = [C.c_uint32, C.c_void_p, C.c_int, C.c_int, fp, C.c_int, C.c_int]
@@ -156,6 +158,16 @@ def project(idx, aos, full_sh, srgb, viewMat, projMat, viewport, nearFar, eye):
     lib().orc_project(v, _u(idx), pa, aos.shape[1], int(bool(full_sh)), int(bool(srgb)), pv, pp, pvp, pnf, pe,
                       out.ctypes.data)
     return out[:v]
+
+
+COV2_G, COV2_Q, COV2_X = 0, 1, 2
+
+
+def cov2_class(cov):
+    """orc_cov2_class per row of an (n, 4) float32 array (m00, m01, m10, m11): the footprint rule's class G / Q / X"""
+    cov = np.ascontiguousarray(cov, np.float32).reshape(-1, 4)
+    f = lib().orc_cov2_class
+    return np.array([f(row.ctypes.data_as(C.POINTER(C.c_float))) for row in cov], np.int32)
 
 
 def composite(splats, W, H, nthreads=1, row0=0, row1=None):

@@ -238,6 +238,8 @@ SYMBOLS = [
     ("msplat_get_stats", C.c_int, [C.c_void_p, C.POINTER(Stats)]),
     ("msplat_get_timings", C.c_int, [C.c_void_p, C.POINTER(Timings)]),
     ("msplat_debug_get_projected", C.c_int, [C.c_void_p, _F16, _U32P, C.c_uint32]),
+    ("msplat_debug_get_projected_view", C.c_int, [C.c_void_p, C.c_int32, _F16, _U32P, C.c_uint32]),
+    ("msplat_debug_fill_projected", C.c_int, [C.c_void_p, C.c_int32]),
     ("msplat_debug_get_tile_lists", C.c_int, [C.c_void_p, _U32P, C.c_uint32, _U32P, C.c_uint64]),
     ("msplat_debug_get_tile_probe8", C.c_int, [C.c_void_p, _U32P, C.c_uint32]),
     ("msplat_set_tile_probe", C.c_int, [C.c_void_p, C.c_int]),

@@ -212,6 +212,39 @@ int msplat_debug_get_projected(msplat_ctx* ctx, float* rec12, uint32_t* rect, ui
     return MSPLAT_OK;
 }
 
+int msplat_debug_get_projected_view(msplat_ctx* ctx, int32_t view, float* rec12, uint32_t* rect, uint32_t count)
+{
+    drain_async(ctx);
+    if (!ctx) return fail(nullptr, MSPLAT_ERR_INVALID_ARG, "ctx is NULL");
+    if (!ctx->has_render) return fail(ctx, MSPLAT_ERR_NO_SORT, "no render yet");
+    if (view < 0 || view >= std::max(ctx->last_fp.views, 1))
+        return fail(ctx, MSPLAT_ERR_INVALID_ARG, "view %d: the latest Render had %d view(s)", view, std::max(ctx->last_fp.views, 1));
+    uint32_t v = 0;
+    int rc = msplat_sort_count(ctx, &v);
+    if (rc) return rc;
+    const uint64_t first = view ? ((uint64_t)v + 63u) & ~(uint64_t)63u : 0u;      // project_kernel<PROJ_TWO_VIEWS>: V1
+    const uint64_t have = std::min<uint64_t>(ctx->rec2d.bytes / 48, ctx->rect.bytes / 4);
+    if (first + count > have)
+        return fail(ctx, MSPLAT_ERR_INVALID_ARG, "ranks %llu .. %llu: the buffers hold %llu", (unsigned long long)first,
+                    (unsigned long long)(first + count), (unsigned long long)have);
+    if (count && rec12) HIP_TRY(ctx, hipMemcpy(rec12, (const char*)ctx->rec2d.p + first * 48, (size_t)count * 48, hipMemcpyDeviceToHost));
+    if (count && rect) HIP_TRY(ctx, hipMemcpy(rect, (const char*)ctx->rect.p + first * 4, (size_t)count * 4, hipMemcpyDeviceToHost));
+    return MSPLAT_OK;
+}
+
+int msplat_debug_fill_projected(msplat_ctx* ctx, int32_t byte)
+{
+    drain_async(ctx);
+    if (!ctx) return fail(nullptr, MSPLAT_ERR_INVALID_ARG, "ctx is NULL");
+    if (!ctx->rec2d.p || !ctx->rect.p) return fail(ctx, MSPLAT_ERR_NO_SORT, "no cloud yet");
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    HIP_TRY(ctx, hipMemset(ctx->rec2d.p, byte & 255, ctx->rec2d.bytes));
+    // (an EMPTY rectangle that is not kRectEmpty: tx0 = 255 > tx1 = 0, ty0 = the byte -- whoever read it would bin nothing)
+    HIP_TRY(ctx, hipMemsetD32((hipDeviceptr_t)ctx->rect.p, (int)(kRectEmpty | (uint32_t)(byte & 255) << 8), ctx->rect.bytes / 4));
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    return MSPLAT_OK;
+}
+
 // On-device check of the ordering contracts of the last Sort (+ the last Render's bin lists, if there was one):
 // sorted keys ascend with ties in ascending splat index, every bin list ascends in draw-order rank.  A cheap guard
 // for the lane-ordered LDS-atomic ranking (probed at msplat_create, not documented hardware behaviour): call it in

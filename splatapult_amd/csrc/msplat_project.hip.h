@@ -210,12 +210,16 @@ __device__ __forceinline__ void project_block(const uint32_t r, const uint32_t r
     }
 
     // footprint: w = alpha*exp(-q/2) > 1/256  <=>  q < 2 ln(256 alpha) =: rho2 (splat_frag.glsl:37-40).
-    // The 3.5-sigma quad of splat_geom.glsl:56-106 always contains it (rho <= 3.33), so the discard
-    // test alone defines coverage.
+    // Where the 3.5-sigma quad of splat_geom.glsl:56-106 exists it contains it (rho <= 3.33), so the discard
+    // test alone defines coverage.  It exists where the shader's minor-axis variance is no NaN and not negative (class Q of
+    // msplat.h's footprint rule: in fp32 det > 0 does not imply it); m01 is the shader's cov2D[0][1] (column 0, row 1).
     uint32_t rect = kRectEmpty;
     const float rho2 = 2.0f * logf(256.0f * alpha);
     if (!(rho2 > 0.0f)) reject = true;                      // alpha <= 1/256 (or NaN): never visible
-    if (!(det > 0.0f) || !(m00 > 0.0f) || !(m11 > 0.0f)) reject = true;   // degenerate/NaN covariance
+    const float apco2 = (m00 + m11) / 2.0f, amco2 = (m00 - m11) / 2.0f;
+    const float mn = apco2 - sqrtf(amco2 * amco2 + m01 * m01);
+    if (!(mn >= 0.0f)) reject = true;                       // Q: the reference's quad is NaN, it draws nothing
+    if (!(det > 0.0f) || !(m00 > 0.0f) || !(m11 > 0.0f)) reject = true;   // X: no Gaussian (the reference would blend exp(+q) or NaN)
     float ex = 0.0f, ey = 0.0f;       // conservative half extents of the footprint (pixels)
     if (!reject) {
         ex = sqrtf(rho2 * m00) * 1.0001f + 0.01f;

@@ -1446,6 +1446,20 @@ class SplatRenderer:
             self._ctx, rec.ctypes.data_as(C.POINTER(C.c_float)), rect.ctypes.data_as(C.POINTER(C.c_uint32)), rec.shape[0]))
         return rec[:v], rect[:v]
 
+    def debug_projected_view(self, view=0, extra=0):
+        """debug_projected() for one view of the latest Render (1: the second eye of RenderStereo) and `extra` ranks beyond the
+        visible ones: what the buffers held before (msplat_debug_get_projected_view)"""
+        n = self.sort_count() + int(extra)
+        rec = np.zeros((max(n, 1), 12), np.float32)
+        rect = np.zeros(max(n, 1), np.uint32)
+        _capi.check(self._ctx, self._lib.msplat_debug_get_projected_view(
+            self._ctx, int(view), rec.ctypes.data_as(C.POINTER(C.c_float)), rect.ctypes.data_as(C.POINTER(C.c_uint32)), n))
+        return rec[:n], rect[:n]
+
+    def debug_fill_projected(self, byte):
+        """fills the projection's record and rectangle buffers (msplat_debug_fill_projected)"""
+        _capi.check(self._ctx, self._lib.msplat_debug_fill_projected(self._ctx, int(byte)))
+
     def set_tile_probe(self, enable=True):
         """per-work-item compositor counters for the following renders (off by default: a few clock reads per batch)"""
         for h in self._ctxs:

@@ -15,6 +15,9 @@ glref_cfg2_1m_1080p.npz is BASELINE configs[1] itself (1 M splats, SH3, 1920x108
 the draw order, a 512 x 256 window of its image and 8x8 box means of the whole frame (a full float image would be 25 MB).
 glref_points.npz: the point-cloud renderer's shaders (point_vert / point_geom / point_frag + the sprite texture) for the scenes of
 glref_cases.point_cases(): image and draw order per scene.
+glref_projection_limits.npz: the projection's conditioning ladder (tests/projection_limit_cases.py) under two cameras at 128 x 96:
+digest, keys, indices, draw order, the footprint rule's class per draw-order rank, and the frame of the drawable splats below
+glref_cases.LADDER_IMAGE_L drawn alone.
 No reference source or shader text is stored."""
 import os
 import sys
@@ -26,6 +29,29 @@ sys.path.insert(0, ROOT)
 
 from oracle import glref, oracle as orc          # noqa: E402
 from tests import glref_cases                    # noqa: E402
+
+
+def ladder():
+    """glref_projection_limits.npz alone: `python tests/golden/make_glref_golden.py ladder`"""
+    # the projection's conditioning ladder under two cameras: keys, indices, draw order, the footprint rule's class per rank, and
+    # the frame of the G splats below glref_cases.LADDER_IMAGE_L drawn alone
+    out = {}
+    for name in glref_cases.LADDER_NAMES:
+        c = glref_cases.ladder_case(name)
+        version = glref.init(True, False)
+        vp = [0, 0, c["W"], c["H"]]
+        mvp = orc.mat4_mul(c["proj"], orc.mat4_inverse(c["cam"]))
+        keys, idx = glref.presort(c["aos"], mvp, c["nf"])
+        sk, si = orc.sort(keys, idx)
+        assert (si == c["order"]).all()
+        eye = np.asarray(c["cam"], np.float32).reshape(16)[12:15].copy()
+        img = glref.render(c["aos"], si[glref_cases.ladder_g_image(c)], orc.mat4_inverse(c["cam"]), c["proj"], vp, c["nf"], eye)
+        assert (img[..., 3] == 1.0).all()
+        out.update({name + "_digest": glref_cases.digest(c["aos"]), name + "_keys": keys, name + "_idx": idx, name + "_draw_order": si,
+                    name + "_cls": c["cls"], name + "_rgb_g": img[..., :3].copy()})
+    path = os.path.join(glref_cases.GOLDEN, "glref_projection_limits.npz")
+    np.savez_compressed(path, gl_version=version, image_l=glref_cases.LADDER_IMAGE_L, **out)
+    print("%-24s %7.0f KB" % ("projection_limits", os.path.getsize(path) / 1024.0))
 
 
 def main():
@@ -64,6 +90,8 @@ def main():
                         window=img[y0:y1, x0:x1, :3].copy(), mean8=glref_cases.box_mean8(img[..., :3]), gl_version=version)
     print("%-24s V %6d  lit %6d  %7.0f KB" % ("cfg2_1m_1080p", keys.shape[0], int((img[..., :3].sum(-1) != 0).sum()), os.path.getsize(path) / 1024.0))
 
+    ladder()
+
     # PointRenderer: shader/point_{vert,geom,frag}.glsl with the sprite texture (pointrenderer.cpp:54-63, 168-195)
     out = {}
     for name, c in glref_cases.point_cases().items():
@@ -84,4 +112,4 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    ladder() if sys.argv[1:] == ["ladder"] else main()

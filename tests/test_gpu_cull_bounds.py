@@ -23,12 +23,6 @@ pytestmark = pytest.mark.gpu
 N, W, H = cc.N, cc.W, cc.H
 ROWS = (H + 31) // 32
 SHARES = (1.0 / 64.0, 0.3)
-# Cameras whose UNCULLED frame is not the oracle's, which is no matter of the culls: under "squashed" the projection draws one
-# splat the oracle's geometry stage rejects (886 of 105 600 pixels differ by more than 1e-4, up to 0.12; visible set, order and
-# keys agree).  For them the culled frames are still compared with the unculled one, bit for bit; only what is derived from the
-# oracle -- the list of splats a rank must keep -- is left out.
-ORACLE_DISAGREES = ("squashed",)
-
 
 @functools.lru_cache(maxsize=None)
 def hostile_cloud():
@@ -81,10 +75,12 @@ def assert_sorted_like_the_reference(r, R, what):
     return idx
 
 
-@pytest.mark.parametrize("name", [n for n in cc.CAMERA_NAMES if n not in ORACLE_DISAGREES])
+@pytest.mark.parametrize("name", cc.CAMERA_NAMES)
 def test_the_reference_frame_is_the_oracles(name):
     """what the culled frames are compared with is itself right: visible set, order and pixels of the oracle -- for the cameras
-    that are no rotation too (the projection takes mat3(view) as it is)"""
+    that are no rotation too (the projection takes mat3(view) as it is).  Under "squashed" one visible splat (upload index 70) has a
+    projected covariance whose minor-axis variance is negative in fp32 although det > 0: class Q of the footprint rule
+    (include/msplat.h), which the reference, the oracle and the projection all draw nothing for"""
     R = reference(name)
     ref = R["oracle"]
     assert R["idx"].shape[0] == ref["V"], (R["idx"].shape[0], ref["V"])
@@ -112,7 +108,7 @@ def test_band_cull_per_splat_keeps_every_splat_that_reaches_an_owned_row(name):
             ratios.append(idx.shape[0] / V)
             # the oracle's footprint of splat s spans the bin rows ty0 .. ty1: it must be kept if one of them is owned
             reach = R["drawn"] & ((R["ty0"][:, None] <= mine[None, :]) & (mine[None, :] <= R["ty1"][:, None])).any(axis=1)
-            lost = np.setdiff1d(ref["sorted_idx"][reach], idx) if name not in ORACLE_DISAGREES else np.zeros(0, np.uint32)
+            lost = np.setdiff1d(ref["sorted_idx"][reach], idx)
             assert lost.size == 0, "%s: the band cull dropped %d splat(s) whose footprint reaches an owned row, e.g. upload index %s" % (
                 what, lost.size, lost[:8])
             part = rb.Render(*view)

@@ -53,6 +53,48 @@ def test_hip_path_matches_the_reference_shaders(name):
     assert (d.max(axis=-1) <= 5e-3 + budget).all(), "max |diff| %.3g beyond the threshold-flip budget" % d.max()
 
 
+@pytest.mark.parametrize("name", glref_cases.LADDER_NAMES)
+def test_projection_ladder_matches_the_reference_shaders(name):
+    """the projection's conditioning ladder (glref_projection_limits.npz): visible set, keys and draw order of the shaders, the
+    footprint rule's class of every rank as the fixture recorded it -- no rank of class Q or X, or rejected by the guard tests, has a
+    rectangle --, and the frame of the drawable splats below glref_cases.LADDER_IMAGE_L drawn alone within SURVEY 8c"""
+    from splatapult_amd import _capi
+    c = glref_cases.ladder_case(name)
+    g = np.load(os.path.join(glref_cases.GOLDEN, "glref_projection_limits.npz"))
+    assert str(g[name + "_digest"]) == glref_cases.digest(c["aos"]), "the scene generator no longer reproduces the fixture's cloud"
+    np.testing.assert_array_equal(g[name + "_cls"], c["cls"])
+    vp = [0, 0, c["W"], c["H"]]
+    one_pass = dict(spatial_order=_capi.SPATIAL_OFF, two_pass=_capi.TWO_PASS_OFF)
+    r = SplatRenderer(device=0, **one_pass)
+    assert r.Init(c["aos"], False, False), r.last_error()
+    r.Sort(c["cam"], c["proj"], vp, c["nf"])
+    order = np.argsort(r.sorted_indices(), kind="stable")
+    np.testing.assert_array_equal(r.sorted_indices()[order], g[name + "_idx"])
+    np.testing.assert_array_equal(r.sorted_keys()[order], g[name + "_keys"])
+    np.testing.assert_array_equal(r.sorted_indices(), g[name + "_draw_order"])
+    r.Render(c["cam"], c["proj"], vp, c["nf"])
+    _, rect = r.debug_projected()
+    drawn = (rect & 255) <= ((rect >> 16) & 255)
+    assert not drawn[c["cls"] != 0].any(), "%d rank(s) of class Q, X or rejected by the guard tests have a rectangle" % drawn[c["cls"] != 0].sum()
+    r.close()
+    sel = glref_cases.ladder_g_image(c)
+    part = np.ascontiguousarray(c["aos"][np.sort(c["order"][sel])])        # upload order kept: the same draw order
+    r = SplatRenderer(device=0, **one_pass)
+    assert r.Init(part, False, False), r.last_error()
+    r.Sort(c["cam"], c["proj"], vp, c["nf"])
+    assert r.sort_count() == sel.sum()
+    img = r.Render(c["cam"], c["proj"], vp, c["nf"])
+    r.close()
+    assert (img[..., 3] == 1.0).all()
+    ref = orc.render_frame(part, True, c["cam"], c["proj"], vp, c["nf"], want_image=False, want_splats=True)
+    _, budget = orc.composite_flip(ref["splats"], c["W"], c["H"])
+    d = np.abs(img[..., :3].astype(np.float64) - g[name + "_rgb_g"])
+    print("HIP vs reference shaders (ladder %s, %d G splats below %g px^2): max |diff| %.3g, mean %.3g, within 1e-4: %.5f" % (
+        name, sel.sum(), float(g["image_l"]), d.max(), d.mean(), (d <= 1e-4).mean()))
+    assert d.mean() <= 1e-4 and (d <= 1e-4).mean() >= 0.999
+    assert (d.max(axis=-1) <= 5e-3 + budget).all(), "max |diff| %.3g beyond the threshold-flip budget" % d.max()
+
+
 def test_baseline_config2_matches_the_reference_shaders():
     """BASELINE configs[1] (1 M splats, SH3, 1920x1080) on the MI355X against what the reference's shaders computed for the same
     frame on llvmpipe (glref_cfg2_1m_1080p.npz): visible count, keys, indices and draw order by digest; a 512 x 256 window of the

@@ -122,6 +122,106 @@ def test_second_eye_drawn_in_the_first_eyes_order():
     check_against_shaders(cloud.as_array(), True, eyes[0], projs[0], 288, 320, render_cam=eyes[1], render_proj=projs[1])
 
 
+CLEAR = np.array([0.0, 0.0, 0.0, 1.0], np.float32)
+
+
+def _ladder_through_shaders(name):
+    """the ladder case, the oracle's frame data, and a function that draws a subset of the draw order with the shaders"""
+    from tests import glref_cases
+    c = glref_cases.ladder_case(name)
+    glref.init(True, False)
+    W, H, vp = c["W"], c["H"], [0, 0, c["W"], c["H"]]
+    mvp = orc.mat4_mul(c["proj"], orc.mat4_inverse(c["cam"]))
+    raw_k, raw_i = glref.presort(c["aos"], mvp, c["nf"], raw=True)
+    o = np.argsort(raw_i, kind="stable")
+    ok, oi = orc.presort(c["aos"], mvp, c["nf"][1])
+    np.testing.assert_array_equal(raw_i[o], oi)                          # the visible set, bit for bit
+    np.testing.assert_array_equal(raw_k[o], ok)                          # ... and the keys
+    sk, si = orc.sort(ok, oi)
+    check_reference_sorter(raw_k, raw_i, sk, si)
+    np.testing.assert_array_equal(si, c["order"])
+    ref = orc.render_frame(c["aos"], True, c["cam"], c["proj"], vp, c["nf"], want_image=False, want_splats=True)
+    np.testing.assert_array_equal(ref["splats"]["reject"] != 0, c["cls"] != 0)      # the oracle rejects what the rule says, no more
+    eye = np.asarray(c["cam"], np.float32).reshape(16)[12:15].copy()
+    draw = lambda sel: glref.render(c["aos"], si[sel], orc.mat4_inverse(c["cam"]), c["proj"], vp, c["nf"], eye)
+    return c, ref, draw
+
+
+@pytest.mark.parametrize("name", ["default", "squashed"])
+def test_ladder_q_splats_draw_nothing_under_the_shaders(name):
+    """The footprint rule's class Q pinned to the shaders themselves, through their own fp32 values (glref.render(capture=True):
+    gl_Position and frag_cov2inv of every vertex the geometry shader emits, by transform feedback):
+      1. the shaders' cov2D is known bit for bit: the captured inverse covariance equals tests/projection_rule.py's for EVERY
+         splat that passes the guard tests;
+      2. the rule is the shaders': a splat's quad is NaN exactly when it is of class Q, for every such splat;
+      3. the Q splats drawn alone leave the frame at the clear colour, exactly.
+    The cov2D of (1) is the one llvmpipe computes, and that is not the source's order: Mesa 23.2's compiler moves the constant of
+    `cov2D[i][i] += 0.3f` to the front of the sum, ((p0 + 0.3) + p1) + p2 instead of ((p0 + p1) + p2) + 0.3 (projection_rule's
+    lowpass_first; GLSL allows it).  With the source's order, which the oracle and the kernel evaluate, (1) holds for 3214 of 4087
+    splats (default) and 2051 of 3739 (squashed) only, the class differs for 32 and 99 ill-conditioned splats, and of the 112 / 272
+    splats that are Q by it llvmpipe draws 1 / 4 (256 / 3189 pixels): printed below, and open in EXPERIMENTS.md -- which order
+    the projection owes the reference is a question about the low-pass term, not about the rule."""
+    from tests import projection_rule as rule
+    c, ref, draw = _ladder_through_shaders(name)
+    vp = [0, 0, c["W"], c["H"]]
+    view, eye = orc.mat4_inverse(c["cam"]), np.asarray(c["cam"], np.float32).reshape(16)[12:15].copy()
+    gl = rule.project(c["aos"], c["order"], True, False, view, c["proj"], vp, c["nf"], eye, lowpass_first=True)
+    ok = np.flatnonzero(c["cls"] >= 0)
+    np.testing.assert_array_equal(gl["guard"], c["cls"] < 0)
+    _, rec = glref.render(c["aos"], c["order"][ok], view, c["proj"], vp, c["nf"], eye, capture=True)
+    inv = np.ascontiguousarray(rec[:, 0, 4:8])
+    same = (inv.view(np.uint32) == gl["inv"][ok].view(np.uint32)) | (np.isnan(inv) & np.isnan(gl["inv"][ok]))
+    literal = ref["splats"]["inv"][ok]
+    same_literal = ((inv.view(np.uint32) == literal.view(np.uint32)) | (np.isnan(inv) & np.isnan(literal))).all(axis=1)
+    quad_nan = np.isnan(rec[:, :, :4]).any(axis=(1, 2))
+    q = gl["cls"][ok] == rule.Q
+    print("ladder %s: %d splats; the shaders' inverse covariance is the rule's bit for bit for %d (the source's order of + 0.3: %d); "
+          "NaN quads %d, class Q %d (by the source's order: %d, %d splat(s) classified differently)" % (
+              name, ok.size, same.all(axis=1).sum(), same_literal.sum(), quad_nan.sum(), q.sum(), (c["cls"][ok] == rule.Q).sum(),
+              (c["cls"][ok] != gl["cls"][ok]).sum()))
+    assert same.all(), "%d splat(s) whose captured inverse covariance is not the rule's" % (~same.all(axis=1)).sum()
+    assert q.sum() >= 16
+    np.testing.assert_array_equal(quad_nan, q)
+    img = draw(ok[q])
+    touched = (img != CLEAR).any(axis=-1)
+    assert not touched.any(), "%d pixel(s) touched by Q splats" % touched.sum()
+    # what the oracle's Q set (the source's order) does under these shaders: reported
+    theirs = draw(np.flatnonzero(c["cls"] == 1))
+    print("ladder %s: the %d splats that are Q by the source's order, drawn alone, touch %d pixel(s)" % (
+        name, (c["cls"] == 1).sum(), (theirs != CLEAR).any(axis=-1).sum()))
+
+
+@pytest.mark.parametrize("name", ["default", "squashed"])
+def test_ladder_g_splats_match_the_oracle_and_x_is_recorded(name):
+    """the G splats below glref_cases.LADDER_IMAGE_L drawn alone: SURVEY 8c's image bounds against the oracle.  All G splats: the
+    share is printed, not asserted (needle-conic cancellation; their records are compared on the device).  X: what the shaders
+    make of it is printed"""
+    from tests import glref_cases
+    c, ref, draw = _ladder_through_shaders(name)
+    W, H, sp = c["W"], c["H"], ref["splats"]
+    sel = glref_cases.ladder_g_image(c)
+    assert sel.sum() >= 16, sel.sum()
+    img = draw(np.flatnonzero(sel))
+    want, budget = orc.composite_flip(sp[sel], W, H)
+    d = np.abs(img[..., :3].astype(np.float64) - want[..., :3])
+    print("ladder %s, %d G splats with L < %g: max |diff| %.3g, mean %.3g, within 1e-4: %.5f" % (
+        name, sel.sum(), glref_cases.LADDER_IMAGE_L, d.max(), d.mean(), (d <= 1e-4).mean()))
+    assert np.isfinite(img).all() and (img[..., 3] == 1.0).all()
+    assert d.mean() <= 1e-4 and (d <= 1e-4).mean() >= 0.999
+    assert (d.max(axis=-1) <= 5e-3 + budget).all()
+    g = c["cls"] == 0
+    img = draw(np.flatnonzero(g))
+    with np.errstate(invalid="ignore"):
+        d = np.abs(img[..., :3].astype(np.float64) - orc.composite(sp[g], W, H)[..., :3])
+    print("ladder %s, all %d G splats: %d pixel(s) not finite, max |diff| %.3g, within 1e-4: %.5f (reported, not asserted)" % (
+        name, g.sum(), (~np.isfinite(img)).any(axis=-1).sum(), np.nanmax(d), (d <= 1e-4).mean()))
+    x = np.flatnonzero(c["cls"] == 2)
+    img = draw(x)
+    print("ladder %s, %d X splats drawn alone by the shaders: %d pixel(s) touched, %d not finite, largest finite |value| %.3g" % (
+        name, x.size, (img != CLEAR).any(axis=-1).sum(), (~np.isfinite(img)).any(axis=-1).sum(),
+        np.abs(img[np.isfinite(img)]).max()))
+
+
 @pytest.mark.parametrize("bits", [24, 32])
 def test_depth_attachment_makes_gl_depth_test_live(bits):
     """Clear() enables GL_DEPTH_TEST (app.cpp:163); with a depth attachment (the default back buffer's 24 bits,
